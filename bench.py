@@ -10,7 +10,7 @@ and pairs travel to their owners by RCCL all-to-all (breakid_amd/sharded.py) - s
 scaling; `--scaling weak` shards one sample of N x that size instead: record indices of a sample are 64-bit, only one
 rank's table stays below 2^32 records).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--records R]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--records R] [--dump-outputs DIR]
 
 Prints ONE JSON line on rank 0 with `roofline` (dominant kernel k_stream, live HIP-event timing) and
 `cpu_baseline` (the CPU oracle port timed on a bounded sample of the same workload, rank 0, N=1)."""
@@ -19,11 +19,6 @@ import json
 import os
 import sys
 import time
-
-# the lanes of chromosome-pair groups in bk_mask_and_cluster (csrc/api.hip; the library's default) need more hardware queues than
-# ROCm's default of 4 (every lane's heap kernels sit on side streams); the runtime reads this when it starts, i.e. before torch
-# touches the GPU (importing breakid_amd.capi sets it as well)
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "20")
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 if ROOT not in sys.path:
@@ -80,6 +75,60 @@ def from_bam_side_line(n_pairs, device, fast, reps=5):
             "feed_only_s": round(min(feed), 4), "feed_only_M_records_per_s": round(n / min(feed) / 1e6, 1),
             "feed_plus_stream_pass_overlapped_s": round(min(over), 4), "feed_plus_stream_pass_M_records_per_s": round(n / min(over) / 1e6, 1),
             "rest_of_hot_path_s": round(min(rest), 4), "file_to_calls_s": round(min(total), 4), "file_to_calls_M_records_per_s": round(n / min(total) / 1e6, 1)}
+
+
+DUMP_BUDGET = 64_000_000  # bytes --dump-outputs writes at most (.npy headers included)
+DUMP_SEED = 20240601  # the row sample of a table larger than its share of the budget
+
+
+def dump_outputs(out_dir, ctx, w, n_valid, sharded_run):
+    """What the timed path handed its caller in the last step: w and the count of valid clusters from bk_run, and the stage tables
+    it left in the context (only the assembled cluster table for a sharded run: the other stages hold this rank's part).  A table is
+    written as float64 rows x fields in the order of its abi dtype, a 64-bit field as two columns (high, low 32 bits) so that every
+    value is exact.  The cluster table (the calls) and the group keys are written whole; the intermediate stages share what is left
+    of DUMP_BUDGET, and one too large for its share is reduced to a fixed, seeded sample of its rows (sorted)."""
+    import numpy as np
+    from breakid_amd import abi
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "w.npy"), np.array([w], np.float64))
+    np.save(os.path.join(out_dir, "n_valid.npy"), np.array([n_valid], np.float64))
+    names = {abi.STAGE_CLUSTERS: "clusters", abi.STAGE_GROUP_KEYS: "group_keys", abi.STAGE_SCAN: "scan", abi.STAGE_ISO: "iso",
+             abi.STAGE_CLUSTERED: "clustered", abi.STAGE_SPLITS: "splits"}
+    whole = (abi.STAGE_CLUSTERS, abi.STAGE_GROUP_KEYS)
+    stages = [abi.STAGE_CLUSTERS] if sharded_run else list(names)
+    left = DUMP_BUDGET - 16 * 1024  # (the headers of the files)
+
+    def save(name, a, cap):
+        if a.shape[0] > cap:
+            a = a[np.sort(np.random.default_rng(DUMP_SEED).choice(a.shape[0], cap, replace=False))]
+        cols = []
+        for f in a.dtype.names:
+            if a.dtype[f].itemsize == 8:
+                u = a[f].view(np.uint64)
+                cols += [u >> np.uint64(32), u & np.uint64(0xFFFFFFFF)]
+            else:
+                cols.append(a[f])
+        m = np.stack([c.astype(np.float64) for c in cols], axis=1)
+        np.save(os.path.join(out_dir, name + ".npy"), m)
+        return m.nbytes
+
+    def row_bytes(a):
+        return 8 * sum(2 if a.dtype[f].itemsize == 8 else 1 for f in a.dtype.names)
+
+    rest = []
+    for st in stages:
+        a, goff = ctx.fetch(st)
+        if goff is not None:
+            np.save(os.path.join(out_dir, names[st] + "_group_offsets.npy"), goff.astype(np.float64))  # (< 2^53: exact)
+            left -= goff.size * 8
+        if st in whole:
+            left -= save(names[st], a, max(0, left) // row_bytes(a))
+        else:
+            rest.append((names[st], a))
+    # smallest tables first: what one does not need of its share goes to the larger ones
+    rest.sort(key=lambda t: t[1].shape[0] * row_bytes(t[1]))
+    for k, (name, a) in enumerate(rest):
+        left -= save(name, a, max(0, left) // (len(rest) - k) // row_bytes(a))
 
 
 def spawn_ranks(n):
@@ -141,9 +190,13 @@ def main():
     ap.add_argument("--scaling", default="strong", choices=["strong", "weak"],
                     help="N > 1: strong = configs[2], the --records sample sharded over the ranks (default); weak = one sample of N x --records")
     ap.add_argument("--sharded", type=int, default=-1, help="1: one sample sharded over the ranks (default when --gpus > 1), 0: plain single-table run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float64, at most 64 MB; rank 0)")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("bench.py: --steps must be >= 1")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # started by hand as `python bench.py --gpus N`: this process never touches a GPU, it starts the N ranks as fresh child
         # processes (one per GPU, torch.distributed.run = what the driver would have started), relays rank 0's line and ends
@@ -174,13 +227,17 @@ def main():
         os.environ.setdefault("MASTER_PORT", "29500")
         dist.init_process_group("nccl", rank=rank, world_size=world, device_id=dev)
 
-    # size the table to the card (configs[1] needs ~60 GB including generator temporaries)
+    # size the table to the card (configs[1] needs ~60 GB including generator temporaries): by its total memory, not what is free at
+    # the moment, so that the same arguments give the same table whatever else holds memory on the device
     free_b, total_b = torch.cuda.mem_get_info(dev)
     n_rec = args.records
     if use_shards and args.scaling == "strong":
         n_rec = max(1_000_000, n_rec // world)
-    while n_rec * 110 > free_b and n_rec > 1_000_000:
+    while n_rec * 110 > total_b and n_rec > 1_000_000:
         n_rec //= 2
+    if n_rec * 110 > free_b:
+        raise SystemExit("bench.py: a table of %d records needs ~%.1f GB on the device, %.1f GB of %.1f GB are free (other processes hold the "
+                         "rest): refusing to run a smaller workload under the same arguments" % (n_rec, n_rec * 110 / 1e9, free_b / 1e9, total_b / 1e9))
     t0 = time.time()
     if use_shards:
         from breakid_amd import sharded
@@ -241,6 +298,8 @@ def main():
         # (bk_fetch assembles on the host: inspection path, outside the timed region)
         cl, _ = ctx.fetch(abi.STAGE_CLUSTERS)
         n_valid = int(((cl["flags"] & 2) != 0).sum())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, ctx, w, n_valid, use_shards)
 
     if rank == 0:
         PEAK = 8000.0  # GB/s, HBM3E (MI355X_MICROARCH.md)

@@ -49,9 +49,8 @@ struct StageTimer
 }  // namespace
 
 // the runtime's hardware-queue count as far as this library can know it: GPU_MAX_HW_QUEUES as the environment had it when the
-// first context was made (bk_init sets 16 when it is unset - that only helps when no HIP call came before; ROCm's default is 4)
+// first context was made (ROCm's default is 4 when it is unset)
 static int g_hw_queues_at_init = 0;
-static bool g_hw_queues_set_here = false;
 
 struct bk_ctx
 {
@@ -406,20 +405,14 @@ void bk_prepare_process()
   std::call_once(once, [] {
     const char *q = getenv("GPU_MAX_HW_QUEUES");
     g_hw_queues_at_init = q ? atoi(q) : 4;
-    if (!q)
-    {
-      setenv("GPU_MAX_HW_QUEUES", "20", 0);
-      g_hw_queues_set_here = true;
-    }
   });
 }
 
 int bk_init(int device, const uint32_t *target_len, const char *const *target_name, int n_targets, bk_ctx **out)
 {
   {
-    // the lanes of bk_mask_and_cluster and the chunk streams of the GPU feed want more hardware queues than ROCm's default of 4;
-    // the runtime reads the variable when it starts, so this helps a caller whose first HIP call is this one (a caller that has
-    // initialised HIP already keeps what it had: lanes_apply tells it once on stderr)
+    // the hardware-queue count the runtime started with (the lanes of bk_mask_and_cluster and the chunk streams of the GPU feed
+    // share queues when there are fewer than they have streams: lanes_apply tells it once on stderr)
     bk_prepare_process();
   }
   if (!out || n_targets < 0 || (n_targets && (!target_len || !target_name)))
@@ -664,8 +657,7 @@ int bk_discordant_pairs(bk_ctx *ctx, int mapq_min, double w, uint64_t *n_pairs, 
 // (BreakID.cc:119-167).  All groups in one pass pay, in each of the five sorts, the longest heapsort segment of ANY group; two
 // disjoint sets of groups on two streams, each driven by its own host thread, overlap the lone-wave heaps of one set with the
 // bandwidth- and launch-bound partition levels of the other.  Needs more hardware queues than ROCm's default of 4 (the heap
-// kernels of both lanes sit on side streams that must not share a queue): enabled by BREAKID_GROUP_LANES=2 (bench.py and the
-// command line set it together with GPU_MAX_HW_QUEUES before the runtime starts).  Results are identical by construction:
+// kernels of both lanes sit on side streams that must not share a queue): enabled by BREAKID_GROUP_LANES=2.  Results are identical by construction:
 // the groups never interact, the lanes' lists are merged back into group order.
 static void run_lane(const bk_pair *pairs, const uint32_t *gof, const uint64_t *gstart, uint32_t ng, uint64_t n, double w, int fast, const uint32_t *drop, PairList &L, PairList &iso,
                      DevBuf &d_cluster, ClusterBufs &cb, AhcBufs &ab, hipStream_t st, const uint64_t *gstart_host, const uint8_t *keep_host)
@@ -701,8 +693,7 @@ __global__ void k_svc_probe() {}
 // Compute queues that exist on the device right now, over ALL processes (the kernel driver's sysfs: /sys/class/kfd/kfd/proc/<pid>/
 // queues/<n>/{gpuid,type}); -1 when that cannot be told.  Measured on MI355X: beyond 24 compute queues on a device - this process's
 // 16-17 plus a second process holding 8 or more - the driver maps the queues in turns, and persistent kernels whose submitters wait
-// for their turn leave jobs unfinished for seconds (tools/gpu_hold_queues.py: 4 streams held by a second process are fine, 8 are
-// not).  The service runs only while the census stays at or below that.
+// for their turn leave jobs unfinished for seconds (4 streams held by a second process were fine, 8 were not: DESIGN.md, "Hardware queues").  The service runs only while the census stays at or below that.
 static int kfd_compute_queues(int device)
 {
   char bus[64] = {0};
@@ -803,7 +794,7 @@ struct SvcStage
     if (bk_debug("lanes"))
       fprintf(stderr, "[lanes] sort service started in %.3f ms; compute queues on the device (all processes): %d (counted in %.3f ms)\n", std::chrono::duration<double, std::milli>(ts1 - ts0).count(), census,
               std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ts1).count());
-    const bool crowded = census > SVC_MAX_DEVICE_QUEUES && !bk_debug("nocensus");
+    const bool crowded = census > SVC_MAX_DEVICE_QUEUES;
     const bool behind = !crowded && !reachable(streams);
     const bool late = !crowded && !behind && !ctx->svc.narrow_running(0.03);
     if (crowded || behind || late)
@@ -920,11 +911,11 @@ static bool lanes_apply(const bk_ctx *ctx, int fast)
   if (yes)
   {
     static bool told = false;
-    if (!told && g_hw_queues_at_init < 8 && !g_hw_queues_set_here && !getenv("BREAKID_QUIET"))
+    if (!told && g_hw_queues_at_init < 8 && bk_debug("lanes"))
     {
       told = true;
-      fprintf(stderr, "[breakid] GPU_MAX_HW_QUEUES=%d: the lanes of chromosome-pair groups (bk_mask_and_cluster) and their heap kernels will share hardware queues; "
-                        "set GPU_MAX_HW_QUEUES=16 in the environment before the process makes its first HIP call (or BREAKID_GROUP_LANES=1)\n", g_hw_queues_at_init);
+      fprintf(stderr, "[breakid] GPU_MAX_HW_QUEUES=%d: the lanes of chromosome-pair groups (bk_mask_and_cluster) and their heap kernels will share hardware queues "
+                        "(BREAKID_GROUP_LANES=1: one pass)\n", g_hw_queues_at_init);
     }
   }
   return yes;

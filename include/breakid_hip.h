@@ -144,9 +144,9 @@ typedef struct bk_cluster {
 /* ---- lifetime ------------------------------------------------------------------------------- */
 /* Replaces: samopen + header parsing (BreakID.cc:1391,1410).  target_name[i] NUL-terminated. */
 int bk_init(int device, const uint32_t *target_len, const char *const *target_name, int n_targets, bk_ctx **out);
-/* Optional, once per process and before its first HIP call: sets GPU_MAX_HW_QUEUES=20 when the environment does not say (the lanes
-   of bk_mask_and_cluster, the resident sort service and the GPU feed each want a hardware queue of their own; the runtime reads the
-   variable when it starts).  bk_init calls it; a caller with threads of its own calls it before it starts them. */
+/* Optional, once per process and before its first HIP call: notes the hardware-queue count the runtime starts with (GPU_MAX_HW_QUEUES,
+   default 4; the lanes of bk_mask_and_cluster, the resident sort service and the GPU feed each want a hardware queue of their own and
+   share one when there are too few).  bk_init calls it; a caller with threads of its own calls it before it starts them. */
 void bk_prepare_process(void);
 void bk_free(bk_ctx *ctx);
 const char *bk_last_error(const bk_ctx *ctx); /* ctx may be NULL: error of the failed bk_init */

@@ -2,7 +2,6 @@
 the path shows up as a run that differs (the std::sort emulation's heap loops are timing sensitive by construction).
     python tools/gpu_determinism.py [records] [runs] [mode fast|ahc]"""
 import hashlib, os, sys
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 os.environ.setdefault("BREAKID_GROUP_LANES", "2")
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np

@@ -2,7 +2,6 @@
 compares every column with the first run's: the feed's chunks, staging buffers and column growth are timing dependent.
     python tools/gpu_feedsoak.py [pairs] [runs]"""
 import hashlib, os, sys
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import torch

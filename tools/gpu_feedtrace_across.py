@@ -2,7 +2,6 @@
     python tools/gpu_feedtrace_across.py write <pairs>   writes /tmp/feedtrace_across.bam
     python tools/gpu_feedtrace_across.py run [reps]"""
 import os, sys, time
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 PATH = "/tmp/feedtrace_across.bam"
 

@@ -2,7 +2,6 @@
 streams that keep launching tiny kernels (nothing that competes for CUs or bandwidth): beyond four active queues every launch /
 round trip of every queue gets slower on this part (tools/ubench/readback.hip).   python tools/gpu_queue_noise.py [records]"""
 import os, sys, threading, time
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from breakid_amd import abi, capi, synth_gpu

@@ -4,7 +4,6 @@ usage: gpu_rehearse8.py [records = 50_000_000] [ranks = 8]"""
 import hashlib, os, re, subprocess, sys, tempfile, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 import numpy as np
 import torch
 from breakid_amd import bamio, synth, synth_gpu
