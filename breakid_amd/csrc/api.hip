@@ -5,6 +5,7 @@
 #include <memory>
 #include <numeric>
 #include <thread>
+#include <atomic>
 #include <chrono>
 
 #include "bk_common.h"
@@ -757,6 +758,13 @@ static int kfd_compute_queues(int device)
 }
 constexpr int SVC_MAX_DEVICE_QUEUES = 24;
 static std::mutex g_svc_device_m[64];
+// once per process on stderr: the stage sorts by launches although the service was wanted
+static void tell_no_service()
+{
+  static std::atomic<bool> told{false};
+  if (!getenv("BREAKID_QUIET") && !told.exchange(true))
+    fprintf(stderr, "[breakid] the resident sort service shares a hardware queue with a stream of its own stage (GPU_MAX_HW_QUEUES too low for the streams of this process), or other processes hold hardware queues on this device: sorting by launches instead\n");
+}
 struct SvcStage
 {
   bk_ctx *ctx;
@@ -805,12 +813,7 @@ struct SvcStage
       // kernel that was merely late (a busy device) gets a second chance
       if (crowded || behind || ++ctx->svc_late >= 2) ctx->svc_refused = true;
       device_turn.unlock();
-      static bool told = false;
-      if (!told && !getenv("BREAKID_QUIET"))
-      {
-        told = true;
-        fprintf(stderr, "[breakid] the resident sort service shares a hardware queue with a stream of its own stage (GPU_MAX_HW_QUEUES too low for the streams of this process), or other processes hold hardware queues on this device: sorting by launches instead\n");
-      }
+      tell_no_service();
       return;
     }
     ctx->svc_late = 0;
@@ -886,18 +889,43 @@ struct SvcStage
     }
   }
 };
+// The hardware queues of the lane stage.  The runtime gives a process GPU_MAX_HW_QUEUES of them (ROCm's default: 4) and maps its
+// streams onto them; two streams on one queue wait for each other's kernels, and a persistent kernel holds its queue for the whole
+// stage.  So the budget is decided from the count the runtime started with, before any stream or persistent kernel of the stage
+// exists:
+//   service   LANE_STREAMS_MAX streams of the lanes + the two persistent kernels' streams + the copy stream of the quit word
+//             (SortService::start) = 7 queues; below that nothing of the service is started (the stage sorts by launches)
+//   launches  one queue stays with the process's first stream (the null stream of torch and of the runtime's copies: the kernel
+//             trace at 4 queues shows it on a queue of its own, and the stage's fourth stream sharing a queue with another lane);
+//             a lane sorts on its own stream and forks the big heaps of each sort onto a side stream only when the other queues
+//             allow two per lane (SortEmuBufs::fork_heaps; without the fork all heaps of a sort are one dispatch); no more lanes
+//             than streams that get a queue each
+constexpr int LANE_STREAMS_MAX = 4;
+constexpr int SVC_STAGE_QUEUES = LANE_STREAMS_MAX + 3;
+static bool lane_service(int fast) { return sort_service_on() && fast && g_hw_queues_at_init >= SVC_STAGE_QUEUES; }
+static int stage_queues() { return std::max(1, g_hw_queues_at_init - 1); }
+// streams per lane of the launch path: 2 (own + side stream for the big heaps) or 1; BREAKID_LANE_STREAMS=1 / 2 overrides
+static int lane_streams_each(int K)
+{
+  static const int want = getenv("BREAKID_LANE_STREAMS") ? atoi(getenv("BREAKID_LANE_STREAMS")) : 0;
+  if (want == 1 || want == 2) return want;
+  return stage_queues() >= 2 * K ? 2 : 1;
+}
 static int lanes_wanted(bool svc)
 {
   // with the resident sort service a lane's sort is a submit and a wait of its thread, so there can be a lane for every one or two
   // of the groups that carry long heap segments: twelve by default (each with a stream of its own; measured 12 / 16 / 18 / 24 lanes
   // on 12 streams: 30.6 / 33.4 / 34.3 / 35.7 ms for the stage - every lane costs its ~160 other launches)
-  static const int want_svc = getenv("BREAKID_GROUP_LANES") ? atoi(getenv("BREAKID_GROUP_LANES")) : 12;
+  const char *env = getenv("BREAKID_GROUP_LANES");
+  static const int want_svc = env ? atoi(env) : 12;
   if (svc) return want_svc < 1 ? 1 : (want_svc > 26 ? 26 : want_svc);
   // four lanes unless the caller says otherwise (BREAKID_GROUP_LANES=1: one pass); lanes_apply decides from the data whether they
   // pay.  Measured on the 30x WGS shape with the segment-per-workgroup tail of the level loop: 2 lanes 42.0 ms, 3 lanes 42.6,
   // 4 lanes 39.6, 5 lanes 48.5 (more lanes shorten a lane's "longest heap of any of its groups" per sort, and cost a level loop,
-  // a ranking and a finisher chain of their own, each ~100 launches that wait for each other across lanes)
-  static const int want = getenv("BREAKID_GROUP_LANES") ? atoi(getenv("BREAKID_GROUP_LANES")) : 4;
+  // a ranking and a finisher chain of their own, each ~100 launches that wait for each other across lanes).  Without an explicit
+  // count no more lanes than hardware queues: a lane whose next small kernel sits behind another lane's heap on a shared queue
+  // waits for that heap.
+  static const int want = env ? atoi(env) : std::max(1, std::min(4, stage_queues() / lane_streams_each(std::min(4, stage_queues()))));
   return want < 1 ? 1 : (want > 26 ? 26 : want);
 }
 static bool lanes_apply(const bk_ctx *ctx, int fast)
@@ -907,11 +935,12 @@ static bool lanes_apply(const bk_ctx *ctx, int fast)
   uint32_t large = 0;
   const uint64_t big = std::max<uint64_t>(2, min_pairs >> 6);  // 16 K pairs with the default threshold
   for (uint32_t g = 0; g < ctx->jr.n_groups && g + 1 < ctx->gstart_host.size(); ++g) large += ctx->gstart_host[g + 1] - ctx->gstart_host[g] >= big ? 1u : 0u;
-  const bool yes = lanes_wanted(sort_service_on() && fast) >= 2 && fast && ctx->jr.n_groups >= 4 && ctx->jr.n_pairs >= min_pairs && large >= 2;
+  const bool yes = lanes_wanted(lane_service(fast)) >= 2 && fast && ctx->jr.n_groups >= 4 && ctx->jr.n_pairs >= min_pairs && large >= 2;
   if (yes)
   {
     static bool told = false;
-    if (!told && g_hw_queues_at_init < 8 && bk_debug("lanes"))
+    const int K = lanes_wanted(lane_service(fast));
+    if (!told && !lane_service(fast) && K * lane_streams_each(K) > stage_queues() && bk_debug("lanes"))
     {
       told = true;
       fprintf(stderr, "[breakid] GPU_MAX_HW_QUEUES=%d: the lanes of chromosome-pair groups (bk_mask_and_cluster) and their heap kernels will share hardware queues "
@@ -1025,11 +1054,11 @@ static void group_lanes(bk_ctx *ctx, double w, int fast)
 {
   const uint32_t ng = ctx->jr.n_groups;
   // With the resident sort service a lane's stream is idle most of the time (its thread waits for the sort's job), so the twelve
-  // lanes share FOUR streams: measured 12 lanes on 12 / 8 / 4 streams 44.5-44.8 / 44.4-44.7 / 44.5-45.2 ms per step (6 streams, two
-  // heavy lanes per stream: 46.7-47.4; round-4 start, with waiting kernels on the streams: 12 / 4 / 3 / 2 streams 31.6 / 31.2 / 35.0 /
-  // 40.2 ms for the stage).  Fewer streams = fewer hardware queues: the stage then needs 4 + 2 of them, and a second process on the
-  // device (a test runner's parent, another sample) leaves the device's queues uncrowded (SVC_MAX_DEVICE_QUEUES).
-  constexpr int lane_streams_max = 4;
+  // lanes share FOUR streams (LANE_STREAMS_MAX): measured 12 lanes on 12 / 8 / 4 streams 44.5-44.8 / 44.4-44.7 / 44.5-45.2 ms per
+  // step (6 streams, two heavy lanes per stream: 46.7-47.4; round-4 start, with waiting kernels on the streams: 12 / 4 / 3 / 2
+  // streams 31.6 / 31.2 / 35.0 / 40.2 ms for the stage).  Fewer streams = fewer hardware queues: the stage then needs 4 + 3 of
+  // them (SVC_STAGE_QUEUES), and a second process on the device (a test runner's parent, another sample) leaves the device's
+  // queues uncrowded (SVC_MAX_DEVICE_QUEUES).
   auto make_lanes = [&](int K, int S) {
     while ((int) ctx->lanes.size() < K - 1)
     {
@@ -1040,8 +1069,15 @@ static void group_lanes(bk_ctx *ctx, double w, int fast)
       if (!ctx->lanes[k]->st) HIP_CHECK(hipStreamCreateWithFlags(&ctx->lanes[k]->st, hipStreamNonBlocking));
   };
   bool use_svc = sort_service_on() && fast;
+  if (use_svc && !lane_service(fast))
+  {
+    // too few hardware queues for the service and the lanes' streams: nothing of the service is started
+    use_svc = false;
+    tell_no_service();
+    if (bk_debug("lanes")) fprintf(stderr, "[lanes] %d hardware queues, the sort service needs %d: not started\n", g_hw_queues_at_init, SVC_STAGE_QUEUES);
+  }
   int K = lanes_wanted(use_svc);
-  int S = use_svc ? std::max(1, std::min(lane_streams_max, K)) : K;
+  int S = use_svc ? std::max(1, std::min(LANE_STREAMS_MAX, K)) : K;
   make_lanes(K, S);
   std::vector<hipStream_t> stage_streams{ctx->st};
   for (int k = 0; k < S - 1; ++k) stage_streams.push_back(ctx->lanes[k]->st);
@@ -1053,6 +1089,18 @@ static void group_lanes(bk_ctx *ctx, double w, int fast)
     K = lanes_wanted(false);
     S = K;
     make_lanes(K, S);
+  }
+  // launch path: the big heaps of a lane's sorts on a side stream of its own only when every lane can have two queues
+  struct ForkReset
+  {
+    bk_ctx *c;
+    ~ForkReset() { c->cb.se.fork_heaps = true; }
+  } fork_reset{ctx};
+  {
+    const bool fork = use_svc || lane_streams_each(K) == 2;
+    ctx->cb.se.fork_heaps = fork;
+    for (int k = 0; k < K - 1; ++k) ctx->lanes[k]->cb.se.fork_heaps = fork;
+    if (!use_svc && bk_debug("lanes")) fprintf(stderr, "[lanes] launch path: %d lanes, %d stream%s each, %d hardware queues\n", K, fork ? 2 : 1, fork ? "s" : "", g_hw_queues_at_init);
   }
   const bool adapt = !use_svc;  // (the service does not report the groups' longest heap segments back to the host)
   auto lane_cb = [&](int l) -> ClusterBufs & { return l == 0 ? ctx->cb : ctx->lanes[l - 1]->cb; };

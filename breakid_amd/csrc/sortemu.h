@@ -40,13 +40,15 @@ struct SortEmuBufs
 {
   SortService *svc = nullptr;  // set (and running): std_sort_groups submits to it instead of launching the phases itself
   uint32_t svc_slot = 0xFFFFFFFFu, svc_epoch = 0;
-  DevBuf cnt, err, segs_a, segs_b, posL, posR, scan_tmp, heap_list, heap_scratch, scratch32, scratch32b, fin_list, lv_tile, lv_segbase, lv_tileseg, lv_bar, chk_key0, chk_cnt, chk_bad, rk_a, rk_b;
+  DevBuf cnt, err, segs_a, segs_b, posL, posR, scan_tmp, heap_list, heap_scratch, scratch32, scratch32b, fin_list, lv_tile, lv_segbase, lv_tileseg, lv_bar, chk_key0, chk_cnt, chk_bad, rk_a, rk_b, heap_tickets;
   prims::RadixBufs radix;
   // optional observer (host): heavy[g] = largest heapsort segment (elements) any sort through these buffers left to group g's
   // lone-wave heap kernels - what the lanes of api.hip balance on.  Set by the caller around the sorts it wants recorded.
   std::vector<uint32_t> *heavy = nullptr;
   bool heavy_all = false;  // record every segment the level loop left to the heapsort kernels (a group that has one went through all ~2 lg n levels), not only the long ones
-  // the three size classes of the heapsort branch run side by side (fork/join around the caller's stream)
+  // the three size classes of the heapsort branch run side by side (fork/join around the caller's stream); false: no side stream,
+  // all heaps of a sort in one dispatch on the caller's stream after the finisher (a caller with one hardware queue per stream)
+  bool fork_heaps = true;
   static constexpr int N_AUX = 5;
   hipStream_t aux[N_AUX] = {};
   hipEvent_t fork = nullptr, join[N_AUX] = {};

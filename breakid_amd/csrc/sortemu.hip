@@ -17,6 +17,7 @@
 //   device-wide level loop (k_se_pivot / flags / lists / swap / child_*)  segments of more than FIN_MAX elements, compact index space
 //   k_se_finish                                                          segments of at most FIN_MAX elements: the same loop in LDS
 //   k_hr_* + k_se_heapsort<0,1,2>                                        segments that hit the depth limit: make_heap + pipelined sort_heap
+//   k_se_heaps_fused                                                     the same heaps in one dispatch (a caller without a side stream)
 //   k_se_window_sort                                                     __final_insertion_sort as two tilings of stable window sorts
 #include "bk_common.h"
 #include "prims.h"
@@ -1393,6 +1394,66 @@ template <int CLS> __global__ __launch_bounds__(CLS == 2 ? HEAP_BIG_THREADS : 64
     heap_big_body(sg.first, sg.last, key, idx, scratch, scratch32, scratch32b, rka, rkb, dyn, HEAP_LARGE32, HEAP_BIG_THREADS);
   else
     heap_small_body(sg.first, sg.last, key, idx, CLS == 0 ? stat : dyn, 64);
+}
+// heap_small_body by ONE wave in its own LDS (buf), beside other waves of the workgroup that do something else (no workgroup barrier)
+__device__ __forceinline__ void heap_wave_body(const uint32_t first, const uint32_t last, uint32_t *key, uint32_t *idx, hent *buf)
+{
+  const uint32_t m = last - first, lane = threadIdx.x & 63;
+  uint32_t *gk = key + first, *gx = idx + first;
+  for (uint32_t i = lane; i < m; i += 64) buf[i] = ((hent) gk[i] << 32) | gx[i];
+  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+  __builtin_amdgcn_wave_barrier();
+  LdsMem mem{buf};
+  make_heap_wave(mem, m);
+  sort_heap_asm<false>(buf, m, 1);
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  __builtin_amdgcn_wave_barrier();
+  for (uint32_t i = lane; i < m; i += 64)
+  {
+    const hent e = buf[i];
+    st_through(gk + i, hkey(e));
+    st_through(gx + i, (uint32_t) e);
+  }
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  __builtin_amdgcn_wave_barrier();
+}
+// Every heap of one sort in ONE dispatch, for a caller whose stream has a hardware queue but no side stream (SortEmuBufs::
+// fork_heaps == false): workgroups [0, n_big) take the segments above HEAP_BIG_MIN, one each, as k_se_heapsort<2> does; every other
+// workgroup is HF_WALKERS waves that take the segments of the list hs[0, nh) by ticket (one counter per size class, so every
+// segment goes to exactly one wave) and heapsort them alone in their own LDS with the body of k_se_heapsort<0 / 1>: wave 0 (33 KB)
+// the segments of (FIN_MAX, HEAP_BIG_MIN] elements first, waves 1.. (16.6 KB) those of at most FIN_MAX.  No wave waits for
+// another's progress; the segments are disjoint, so which wave took which does not change the result.
+constexpr uint32_t HF_WALKERS = 8;
+constexpr uint32_t HF_MAX_WORKERS = 64;  // workgroups of walkers per dispatch (each takes a CU's LDS)
+static_assert(((size_t) HEAP_BIG_MIN + HEAP_PAD + (HF_WALKERS - 1) * ((size_t) FIN_MAX + HEAP_PAD)) * sizeof(hent) <= HEAP_BIG_LDS, "walker LDS");
+__global__ __launch_bounds__(HEAP_BIG_THREADS) void k_se_heaps_fused(const HeapSeg *__restrict__ hs, uint32_t nh, const HeapSeg *__restrict__ big, uint32_t n_big, uint32_t *tickets, uint32_t *key,
+                                                                     uint32_t *idx, hent *scratch, uint32_t *scratch32, uint32_t *scratch32b, unsigned long long *rka, unsigned long long *rkb)
+{
+  extern __shared__ __attribute__((aligned(16))) hent dyn[];
+  if (blockIdx.x < n_big)
+  {
+    const HeapSeg sg = big[blockIdx.x];
+    if (sg.last - sg.first > HEAP_BIG_MIN) heap_big_body(sg.first, sg.last, key, idx, scratch, scratch32, scratch32b, rka, rkb, dyn, HEAP_LARGE32, HEAP_BIG_THREADS);
+    return;
+  }
+  const uint32_t w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  if (w >= HF_WALKERS) return;
+  hent *buf = w == 0 ? dyn : dyn + (HEAP_BIG_MIN + HEAP_PAD) + (size_t) (w - 1) * (FIN_MAX + HEAP_PAD);
+  for (uint32_t c = w == 0 ? 0u : 1u; c < 2; ++c)
+  {
+    const uint32_t lo = c == 0 ? FIN_MAX : 0u, hi = c == 0 ? HEAP_BIG_MIN : FIN_MAX;
+    for (;;)
+    {
+      uint32_t t = 0;
+      if (lane == 0) t = atomicAdd(tickets + c, 1u);
+      t = __shfl(t, 0, 64);
+      if (t >= nh) break;
+      const HeapSeg sg = hs[t];
+      const uint32_t m = sg.last - sg.first;
+      if (m <= lo || m > hi) continue;
+      heap_wave_body(sg.first, sg.last, key, idx, buf);
+    }
+  }
 }
 
 // ---- a partition level in three passes over the keys --------------------------------------------------------------------
@@ -2959,7 +3020,39 @@ void std_sort_groups(uint32_t *key, uint32_t *idx, const uint32_t *gof, const ui
     }
   }
   bool forked = false;
-  if (nh1 && max1 > HEAP_SMALL)
+  static const bool one_stream = getenv("BREAKID_LANE_STREAMS") && atoi(getenv("BREAKID_LANE_STREAMS")) == 1;  // (every launch-path sort so)
+  const bool fork_heaps = b.fork_heaps && !one_stream;
+  if (!fork_heaps)
+  {
+    // one stream, one hardware queue (a lane of api.hip when the process has few queues): the finisher first, then every heap of the
+    // sort - the long ones of the level loop, the mid-size ones, the finisher's - in ONE dispatch, so that they still run side by
+    // side.  (What the fork below overlaps with the long heaps is the finisher as well: ~0.6 ms per sort that run before them here.)
+    if (nfin2[1]) hipLaunchKernelGGL((k_se_finish<FIN_MAX, 256>), dim3(nfin2[1]), dim3(256), 0, st, fin_list + (fin_cap - 1), nfin2[1], -1, key, idx, err, heap_list);
+    if (nfin2[0]) hipLaunchKernelGGL((k_se_finish<FIN_SMALL, 64>), dim3(nfin2[0]), dim3(64), 0, st, fin_list, nfin2[0], 1, key, idx, err, heap_list);
+    if (nfin)
+    {
+      HIP_CHECK(hipMemcpyAsync(e, err, 16, hipMemcpyDeviceToHost, st));
+      HIP_CHECK(hipStreamSynchronize(st));
+    }
+    const uint32_t nh2 = e[3], nbig = max1 > HEAP_BIG_MIN ? n_big : 0u;
+    if (nh2 > max_segs - nbig) throw bk_error(BK_ERR_LIMIT, "std_sort_groups: heap list overflow");
+    if (nbig)
+    {
+      rka = b.rk_a.as<unsigned long long>((uint64_t) n + HEAP_PAD);
+      rkb = b.rk_b.as<unsigned long long>((uint64_t) n + HEAP_PAD);
+      scratch32 = b.scratch32.as<uint32_t>((uint64_t) n + HEAP_PAD);
+      if (max1 > HEAP_LARGE32) scratch32b = b.scratch32b.as<uint32_t>((uint64_t) n + HEAP_PAD);
+    }
+    if (nh2 || nbig)
+    {
+      uint32_t *tickets = b.heap_tickets.as<uint32_t>(2);
+      HIP_CHECK(hipMemsetAsync(tickets, 0, 8, st));
+      const uint32_t workers = std::min<uint32_t>(HF_MAX_WORKERS, cdiv(nh2, HF_WALKERS));
+      HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_se_heaps_fused), hipFuncAttributeMaxDynamicSharedMemorySize, HEAP_BIG_LDS));
+      hipLaunchKernelGGL(k_se_heaps_fused, dim3(nbig + workers), dim3(HEAP_BIG_THREADS), HEAP_BIG_LDS, st, hl, nh2, hl + (max_segs - nbig), nbig, tickets, key, idx, hscratch, scratch32, scratch32b, rka, rkb);
+    }
+  }
+  else if (nh1 && max1 > HEAP_SMALL)
   {
     // heaps above HEAP_BIG_MIN elements: ranked 4-byte entries, one workgroup per CU, on a side stream (the longest of them is the
     // critical path of the sort); the mid-size heaps of the level loop (~1.5 ms) in front of the finisher on the caller's own stream
@@ -2986,9 +3079,9 @@ void std_sort_groups(uint32_t *key, uint32_t *idx, const uint32_t *gof, const ui
     HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_se_heapsort<1>), hipFuncAttributeMaxDynamicSharedMemorySize, ((size_t) HEAP_BIG_MIN + HEAP_PAD) * 8));
     hipLaunchKernelGGL(k_se_heapsort<1>, dim3(nh1), dim3(64), ((size_t) HEAP_BIG_MIN + HEAP_PAD) * 8, st, hl, nh1, key, idx, hscratch, HEAP_SMALL, HEAP_BIG_MIN, scratch32, scratch32b, rka, rkb);
   }
-  if (nfin2[1]) hipLaunchKernelGGL((k_se_finish<FIN_MAX, 256>), dim3(nfin2[1]), dim3(256), 0, st, fin_list + (fin_cap - 1), nfin2[1], -1, key, idx, err, heap_list);
-  if (nfin2[0]) hipLaunchKernelGGL((k_se_finish<FIN_SMALL, 64>), dim3(nfin2[0]), dim3(64), 0, st, fin_list, nfin2[0], 1, key, idx, err, heap_list);
-  if (nh1 || nfin)
+  if (fork_heaps && nfin2[1]) hipLaunchKernelGGL((k_se_finish<FIN_MAX, 256>), dim3(nfin2[1]), dim3(256), 0, st, fin_list + (fin_cap - 1), nfin2[1], -1, key, idx, err, heap_list);
+  if (fork_heaps && nfin2[0]) hipLaunchKernelGGL((k_se_finish<FIN_SMALL, 64>), dim3(nfin2[0]), dim3(64), 0, st, fin_list, nfin2[0], 1, key, idx, err, heap_list);
+  if (fork_heaps && (nh1 || nfin))
   {
     // small heaps (level loop and finisher) and the finisher's own segments above HEAP_SMALL (at most FIN_MAX elements)
     if (nfin)
