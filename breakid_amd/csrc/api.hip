@@ -1101,6 +1101,7 @@ static void group_lanes(bk_ctx *ctx, double w, int fast)
     ctx->cb.se.fork_heaps = fork;
     for (int k = 0; k < K - 1; ++k) ctx->lanes[k]->cb.se.fork_heaps = fork;
     if (!use_svc && bk_debug("lanes")) fprintf(stderr, "[lanes] launch path: %d lanes, %d stream%s each, %d hardware queues\n", K, fork ? 2 : 1, fork ? "s" : "", g_hw_queues_at_init);
+    if (!use_svc && sort_tasks_on() && bk_debug("lanes")) fprintf(stderr, "[lanes] sorts as task dispatches on the lane streams\n");
   }
   const bool adapt = !use_svc;  // (the service does not report the groups' longest heap segments back to the host)
   auto lane_cb = [&](int l) -> ClusterBufs & { return l == 0 ? ctx->cb : ctx->lanes[l - 1]->cb; };
@@ -1708,6 +1709,18 @@ int bk_debug_std_sort(bk_ctx *ctx, const uint32_t *key, const uint64_t *group_of
     svc_stage.finish();
     HIP_CHECK(hipMemcpyAsync(perm_out, dp.get<uint32_t>(), n * 4, hipMemcpyDeviceToHost, ctx->st));
     HIP_CHECK(hipStreamSynchronize(ctx->st));
+  });
+}
+
+int bk_sort_forms(bk_ctx *ctx, uint64_t out[3])
+{
+  return guarded(ctx, [&] {
+    if (!out) throw bk_error(BK_ERR_ARG, "bk_sort_forms: null output");
+    for (int k = 0; k < 3; ++k)
+    {
+      out[k] = ctx->cb.se.sorts[k];
+      for (const auto &l : ctx->lanes) out[k] += l->cb.se.sorts[k];
+    }
   });
 }
 

@@ -49,6 +49,13 @@ struct SortEmuBufs
   // the three size classes of the heapsort branch run side by side (fork/join around the caller's stream); false: no side stream,
   // all heaps of a sort in one dispatch on the caller's stream after the finisher (a caller with one hardware queue per stream)
   bool fork_heaps = true;
+  // the sort as ONE task dispatch on the caller's stream (sortsvc.inc, k_sort_job) when no service runs: this caller's own queues,
+  // job and position lists (BREAKID_SORT_TASKS=0: the launches of the level loop, the tail, the finisher and the heaps instead)
+  DevBuf tj_ctl, tj_jobs, tj_slots[2], tj_seq[2], tj_pos[2], tj_heavy, tj_trace;
+  uint32_t tj_cap[2] = {0, 0}, tj_epoch = 0;
+  bool tj_ready = false;  // the rings are initialised and consistent (a failed sort clears it)
+  // sorts through these buffers by form: [0] jobs of the resident service, [1] task dispatches, [2] launches
+  uint64_t sorts[3] = {0, 0, 0};
   static constexpr int N_AUX = 5;
   hipStream_t aux[N_AUX] = {};
   hipEvent_t fork = nullptr, join[N_AUX] = {};
@@ -65,6 +72,10 @@ struct SortEmuBufs
     if (fork) (void) hipEventDestroy(fork);
   }
 };
+
+// false under BREAKID_SORT_TASKS=0: without a running service, a sort is the chain of launches (level loop, tail, finisher, heaps)
+// instead of one task dispatch on the caller's stream
+bool sort_tasks_on();
 
 // key/idx: n elements, groups are the contiguous ranges goff[g]..goff[g+1]; gof[p] = group of position p.
 // On return every group is ordered exactly as std::sort(begin, end, [](a,b){return a.key < b.key;}) leaves it.

@@ -1232,22 +1232,71 @@ __device__ void wg_ranked_entries(const uint32_t *gk, const uint32_t m, unsigned
     }
   }
 }
-// One heap segment of at most 4096 elements as packed 8-byte entries in LDS (buf): every thread of the workgroup calls this (NT of
-// them), the heap itself belongs to wave 0.
-__device__ __forceinline__ void heap_small_body(const uint32_t first, const uint32_t last, uint32_t *key, uint32_t *idx, hent *buf, const uint32_t NT)
+// Who runs a task body: its thread index, its barrier, and what it counts of the tasks it pushes (sortsvc.inc).  WgTeam = the
+// whole workgroup (every kernel but k_sort_job; compiles to threadIdx.x and __syncthreads, nothing counted).
+struct WgTeam
 {
-  const uint32_t m = last - first;
+  __device__ __forceinline__ uint32_t tid() const { return threadIdx.x; }
+  __device__ __forceinline__ void sync() const { __syncthreads(); }
+  __device__ __forceinline__ void count_pushes(uint32_t) const {}
+};
+// WgLive = the whole workgroup, partition and finisher tasks pushed added to *live (the wide workgroups of k_sort_job)
+struct WgLive : WgTeam
+{
+  uint32_t *live;
+  __device__ __forceinline__ void count_pushes(uint32_t k) const
+  {
+    if (k) atomicAdd(live, k);
+  }
+};
+// LdsTeam = four waves (threads base .. base + 255) of a larger workgroup whose other waves do something else: the barrier is an
+// arrival counter and a generation word in LDS (the waves of a workgroup are co-resident, so the spin always ends); partition and
+// finisher tasks pushed are added to *live (k_sort_job: nothing can arrive any more once that is zero)
+struct LdsTeam
+{
+  uint32_t *bar;  // LDS: [0] arrivals, [1] generation
+  uint32_t base;
+  uint32_t *live;
+  __device__ __forceinline__ uint32_t tid() const { return threadIdx.x - base; }
+  __device__ __forceinline__ void sync() const
+  {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    if ((threadIdx.x & 63u) == 0)
+    {
+      const uint32_t g = __hip_atomic_load(bar + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      if (__hip_atomic_fetch_add(bar, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_WORKGROUP) == 3u)
+      {
+        __hip_atomic_store(bar, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        __hip_atomic_store(bar + 1, g + 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+      }
+      else
+        while (__hip_atomic_load(bar + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) == g) __builtin_amdgcn_s_sleep(1);
+    }
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+  }
+  __device__ __forceinline__ void count_pushes(uint32_t k) const
+  {
+    if (k) atomicAdd(live, k);
+  }
+};
+
+// One heap segment of at most 4096 elements as packed 8-byte entries in LDS (buf): every thread of the team calls this (NT of
+// them), the heap itself belongs to its first wave.
+template <class T = WgTeam> __device__ __forceinline__ void heap_small_body(const uint32_t first, const uint32_t last, uint32_t *key, uint32_t *idx, hent *buf, const uint32_t NT, const T &team = T())
+{
+  const uint32_t m = last - first, tid = team.tid();
   uint32_t *gk = key + first, *gx = idx + first;
-  for (uint32_t i = threadIdx.x; i < m; i += NT) buf[i] = ((hent) gk[i] << 32) | gx[i];
-  __syncthreads();
-  if (threadIdx.x < 64)
+  for (uint32_t i = tid; i < m; i += NT) buf[i] = ((hent) gk[i] << 32) | gx[i];
+  team.sync();
+  if (tid < 64)
   {
     LdsMem mem{buf};
     make_heap_wave(mem, m);
     sort_heap_asm<false>(buf, m, 1);
   }
-  __syncthreads();
-  for (uint32_t i = threadIdx.x; i < m; i += NT)
+  team.sync();
+  for (uint32_t i = tid; i < m; i += NT)
   {
     const hent e = buf[i];
     st_through(gk + i, hkey(e));
@@ -2763,6 +2812,149 @@ static void std_sort_groups_svc(uint32_t *key, uint32_t *idx, const uint32_t *go
   window_sorts(key, idx, gof, n, st);
 }
 
+// the sort as ONE task dispatch on the caller's stream (sortsvc.inc, k_sort_job): the caller's own queues and job, seeded with the
+// root partition nodes of every group; then the insertion sort's windows and ONE look of the host at the job's error word (and at
+// the groups' longest heaps when the caller observes them)
+static void std_sort_groups_tasks(uint32_t *key, uint32_t *idx, const uint32_t *gof, const uint64_t *goff, uint32_t ng, uint32_t n, SortEmuBufs &b, hipStream_t st, const uint32_t *key0)
+{
+  static size_t dyn_lds = 0;
+  static uint32_t cap32 = 0;
+  static std::once_flag once;
+  std::call_once(once, [] {
+    hipFuncAttributes fa;
+    HIP_CHECK(hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(k_sort_job)));
+    // all of a CU's 160 KB but the kernel's static LDS; the ranked entries that fit (+ slot 0 and two zero slots), an odd count
+    dyn_lds = (size_t) ((160u * 1024u - (uint32_t) fa.sharedSizeBytes) & ~15u);
+    cap32 = (uint32_t) (dyn_lds / 4 - 3);
+    if ((cap32 & 1u) == 0) --cap32;
+    if (dyn_lds < SJ_TEAMS * SJ_TEAM_LDS) throw bk_error(BK_ERR_HIP, "k_sort_job: the narrow teams do not fit the LDS");
+    HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_sort_job), hipFuncAttributeMaxDynamicSharedMemorySize, (int) dyn_lds));
+  });
+  // the largest group sizes the wide workgroups' position lists (a wide one may be handed a whole group)
+  std::vector<uint64_t> go((size_t) ng + 1);
+  HIP_CHECK(hipMemcpyAsync(go.data(), goff, go.size() * 8, hipMemcpyDeviceToHost, st));
+  HIP_CHECK(hipStreamSynchronize(st));
+  uint64_t max_group = 0;
+  for (uint32_t g = 0; g < ng; ++g) max_group = std::max<uint64_t>(max_group, go[g + 1] - go[g]);
+  // the grid: bounded, so that three lanes' dispatches and their other kernels share the device (a workgroup holds a CU's LDS)
+  const uint32_t n_wide = std::min<uint32_t>(SJ_MAX_WIDE, std::max<uint32_t>(1, cdiv(n, 1u << 16)));
+  const uint32_t n_narrow = std::min<uint32_t>(SJ_MAX_NARROW, std::max<uint32_t>(1, cdiv(n, 1u << 16)));
+  SjParams S = {};
+  SvcParams &P = S.P;
+  {
+    auto pow2 = [](uint64_t v) {
+      uint32_t c = 1024;
+      while (c < v && c < (1u << 30)) c <<= 1;
+      return c;
+    };
+    // rings as the service sizes them: every live segment holds more than 16 elements, the wide ring only sees those above HEAP_BIG_MIN
+    const uint32_t want[2] = {pow2((uint64_t) n / HEAP_BIG_MIN + 4096), pow2((uint64_t) n / 16 + 4096)};
+    for (int k = 0; k < 2; ++k)
+      if (want[k] > b.tj_cap[k])
+      {
+        b.tj_cap[k] = want[k];
+        b.tj_ready = false;
+      }
+    uint32_t *ctl = b.tj_ctl.as<uint32_t>(SJ_C_WORDS);
+    for (int k = 0; k < 2; ++k)
+    {
+      P.q[k].head = ctl + 64 * k;
+      P.q[k].tail = ctl + 64 * k + 32;
+      P.q[k].slots = b.tj_slots[k].as<SvcTask>(b.tj_cap[k]);
+      P.q[k].seq = b.tj_seq[k].as<uint32_t>(b.tj_cap[k]);
+      P.q[k].mask = b.tj_cap[k] - 1;
+      P.q[k].release = 1u;  // an agent-scope release in front of every push (sortsvc.inc, visibility)
+    }
+    P.error = ctl + SJ_C_ERROR;
+    P.stats = ctl + SJ_C_STATS;
+    P.quit_d = ctl + SJ_C_QUIT;
+    P.host = ctl + SJ_C_HOST;
+    P.jobs = b.tj_jobs.as<SvcJob>(SVC_MAX_JOBS);  // (k_svc_reset clears SVC_MAX_JOBS of them; this caller's job is slot 0)
+    P.cap32 = cap32;
+    P.quit_word = 0u;
+    P.timeout_ticks = SJ_TIMEOUT_TICKS;
+    P.pos_cap[0] = (uint32_t) std::max<uint64_t>(max_group, SVC_WIDE_MIN) + 64;
+    P.pos_cap[1] = SVC_WIDE_MIN + 64;
+    P.pos[0] = b.tj_pos[0].as<uint32_t>(2ull * P.pos_cap[0] * n_wide);
+    P.pos[1] = b.tj_pos[1].as<uint32_t>(2ull * P.pos_cap[1] * n_narrow * SJ_TEAMS);
+    P.dbg = nullptr;
+    S.n_wide = n_wide;
+    S.live = ctl + SJ_C_LIVE;
+    S.gof = gof;
+    S.heavy_min = b.heavy_all ? FIN_MAX : HEAP_RANKED_MIN;
+    if (b.heavy)
+    {
+      S.heavy = b.tj_heavy.as<uint32_t>(ng);
+      HIP_CHECK(hipMemsetAsync(S.heavy, 0, (size_t) ng * 4, st));
+    }
+  }
+  static const bool dbg = bk_debug("svc");
+  if (dbg) S.trace = b.tj_trace.as<unsigned long long>(8);
+  if (!b.tj_ready)
+  {
+    HIP_CHECK(hipMemsetAsync(b.tj_ctl.p, 0, SJ_C_WORDS * 4, st));
+    hipLaunchKernelGGL(k_svc_reset, dim3(cdiv(std::max(b.tj_cap[0], b.tj_cap[1]), 256)), dim3(256), 0, st, P);
+    b.tj_ready = true;
+  }
+  SvcJob d = {};
+  d.key = key;
+  d.idx = idx;
+  d.hscratch = b.heap_scratch.as<hent>((uint64_t) n + HEAP_PAD);
+  d.scratch32 = b.scratch32.as<uint32_t>((uint64_t) n + HEAP_PAD);
+  d.scratch32b = b.scratch32b.as<uint32_t>((uint64_t) n + HEAP_PAD);
+  d.rka = b.rk_a.as<unsigned long long>((uint64_t) n + HEAP_PAD);
+  d.rkb = b.rk_b.as<unsigned long long>((uint64_t) n + HEAP_PAD);
+  d.epoch = (b.tj_epoch++ % 0xFFFFFu) + 1u;  // (never 0)
+  const SvcJobLds J = {d.key, d.idx, nullptr, nullptr, d.hscratch, d.scratch32, d.scratch32b, d.rka, d.rkb, P.jobs, d.epoch << 8};
+  hipLaunchKernelGGL(k_sort_job_submit, dim3(1), dim3(256), 0, st, S, d, goff, ng);
+  hipLaunchKernelGGL(k_sort_job, dim3(n_wide + n_narrow), dim3(1024), dyn_lds, st, S, J);
+  HIP_CHECK(hipGetLastError());
+  ++b.sorts[1];
+  // the job's state: error words, and what the caller observes (the window sorts behind do not change it)
+  if (key0) sort_check("after the task dispatch", key, idx, key0, n, goff, ng, st, b);
+  window_sorts(key, idx, gof, n, st);
+  uint32_t h[16] = {};
+  HIP_CHECK(hipMemcpyAsync(h, P.error, 12 * 4, hipMemcpyDeviceToHost, st));
+  std::vector<uint32_t> hv;
+  if (S.heavy)
+  {
+    hv.resize(ng);
+    HIP_CHECK(hipMemcpyAsync(hv.data(), S.heavy, (size_t) ng * 4, hipMemcpyDeviceToHost, st));
+  }
+  unsigned long long tr[8] = {};
+  if (S.trace) HIP_CHECK(hipMemcpyAsync(tr, S.trace, 5 * 8, hipMemcpyDeviceToHost, st));
+  SvcJob j = {};
+  HIP_CHECK(hipMemcpyAsync(&j, P.jobs, sizeof j, hipMemcpyDeviceToHost, st));
+  HIP_CHECK(hipStreamSynchronize(st));
+  if (h[0] || j.remaining != 0u)
+  {
+    b.tj_ready = false;  // (tasks may be left in the rings: initialised again before the next sort)
+    throw bk_error(h[0] & 2u ? BK_ERR_LIMIT : BK_ERR_HIP, "sort task dispatch: task error " + std::to_string(h[0]) + " (2 = ring overflow, 4 = no progress for 1 s, 8 = a cut outside its segment, 16 = a task in the wrong queue, 32 = a node beyond the position lists, 64 = the finisher), " + std::to_string(j.remaining) + " elements not final; first failing task: code " + std::to_string(h[8]) + ", " + std::to_string(h[9]) + " " + std::to_string(h[10]) + " " + std::to_string(h[11]));
+  }
+  if (S.heavy)
+  {
+    if (b.heavy->size() < ng) b.heavy->resize(ng, 0u);
+    for (uint32_t g = 0; g < ng; ++g) (*b.heavy)[g] = std::max((*b.heavy)[g], hv[g]);
+  }
+  if (S.trace)
+  {
+    // (tools/task_dispatch_heap_waits.py reads these lines)
+    const double t0 = (double) tr[0];
+    const uint32_t hm = (uint32_t) (tr[1] >> 40);
+    const unsigned long long hs = tr[1] & 0xFFFFFFFFFFull, base = tr[0] & ~0xFFFFFFFFFFull;
+    unsigned long long hstart = base | hs;
+    if (hstart < tr[0]) hstart += 1ull << 40;
+    fprintf(stderr, "[svc] task dispatch %u: %u elements in %u groups on %u wide + %u narrow workgroups; longest heap %u elements started %.3f ms after the dispatch and took %.3f ms; partitions and finisher done after %.3f ms, job after %.3f ms; %u elements in heaps, the longest %u\n",
+            d.epoch, n, ng, n_wide, n_narrow, hm, hm ? ((double) hstart - t0) * 1e-5 : 0.0, hm ? (double) (tr[2] & 0xFFFFFFFFFFull) * 1e-5 : 0.0, tr[3] ? ((double) tr[3] - t0) * 1e-5 : 0.0, ((double) tr[4] - t0) * 1e-5, j.n_heap, j.max_heap);
+  }
+}
+
+bool sort_tasks_on()
+{
+  static const bool on = !(getenv("BREAKID_SORT_TASKS") && atoi(getenv("BREAKID_SORT_TASKS")) == 0);
+  return on;
+}
+
 void std_sort_groups(uint32_t *key, uint32_t *idx, const uint32_t *gof, const uint64_t *goff, uint32_t ng, uint64_t n64, SortEmuBufs &b, hipStream_t st)
 {
   if (n64 == 0 || ng == 0) return;
@@ -2787,6 +2979,7 @@ void std_sort_groups(uint32_t *key, uint32_t *idx, const uint32_t *gof, const ui
   const uint32_t n = (uint32_t) n64;
   if (b.svc && b.svc->running)
   {
+    ++b.sorts[0];
     std_sort_groups_svc(key, idx, gof, goff, ng, n, b, st);
     return;
   }
@@ -2834,6 +3027,12 @@ void std_sort_groups(uint32_t *key, uint32_t *idx, const uint32_t *gof, const ui
     }
     ++call;
   }
+  if (sort_tasks_on())
+  {
+    std_sort_groups_tasks(key, idx, gof, goff, ng, n, b, st, chk ? key0 : nullptr);
+    return;
+  }
+  ++b.sorts[2];
   // level 0 segments = groups larger than 16
   const uint32_t fin_cap = (uint32_t) ((uint64_t) n / 16 + ng + 16);  // every entry holds more than 16 elements
   FinSeg *fin_list = b.fin_list.as<FinSeg>(fin_cap);

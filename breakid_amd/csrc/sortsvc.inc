@@ -132,10 +132,10 @@ __device__ __forceinline__ void svc_acquire()
 
 // every wave of the workgroup: its global stores have left the wave, then the workgroup meets (what lane 0 releases afterwards is
 // everything the workgroup has written)
-__device__ __forceinline__ void svc_drain_barrier()
+template <class T = WgTeam> __device__ __forceinline__ void svc_drain_barrier(const T &team = T())
 {
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
+  team.sync();
 }
 
 // one lane.  The caller has released the data the task stands for.
@@ -253,10 +253,11 @@ template <uint32_t NT> struct SvcPartLds
   uint32_t cut;
   int go_on;
 };
-template <uint32_t NT, bool WIDE> __device__ __forceinline__ void svc_part(const SvcParams &P, const SvcJobLds &J, SvcPartLds<NT> &S, const SvcTask t, uint32_t *pos, const uint32_t pos_cap)
+template <uint32_t NT, bool WIDE, class T = WgTeam>
+__device__ __forceinline__ void svc_part(const SvcParams &P, const SvcJobLds &J, SvcPartLds<NT> &S, const SvcTask t, uint32_t *pos, const uint32_t pos_cap, const T &team = T())
 {
   constexpr uint32_t NW = NT / 64;
-  const uint32_t tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const uint32_t tid = team.tid(), lane = tid & 63, w = tid >> 6;
   uint32_t *key = J.key, *idx = J.idx;
   const uint32_t job_tag = t.type_job >> 4;
   uint32_t retired = 0;  // (lane 0 of wave 0 only)
@@ -283,7 +284,7 @@ template <uint32_t NT, bool WIDE> __device__ __forceinline__ void svc_part(const
       S.cut = 0xFFFFFFFFu;
     }
   }
-  __syncthreads();
+  team.sync();
   if (!S.go_on) return;
   unsigned long long tph = 0;  // (BK_DEBUG=svc, wide nodes: ticks per phase of a level)
   uint32_t *phase = (P.dbg && WIDE) ? P.dbg + 12 * 8192 + 32 : nullptr;
@@ -338,7 +339,7 @@ template <uint32_t NT, bool WIDE> __device__ __forceinline__ void svc_part(const
       S.cnt[0][w] = cL;
       S.cnt[1][w] = cR;
     }
-    __syncthreads();
+    team.sync();
     mark(0);
     uint32_t runL = 0, runR = 0, nL = 0, nR = 0;
     for (uint32_t i = 0; i < NW; ++i)
@@ -381,7 +382,7 @@ template <uint32_t NT, bool WIDE> __device__ __forceinline__ void svc_part(const
         place(p, valid, valid ? key[p] : 0u);
       }
     }
-    __syncthreads();
+    team.sync();
     mark(1);
     // pair j = (l_j, r_j): swapped while l_j < r_j; the first pair that is not gives the cut
     const uint32_t mm = nL < nR ? nL : nR;
@@ -443,10 +444,10 @@ template <uint32_t NT, bool WIDE> __device__ __forceinline__ void svc_part(const
       // peeled off - has few swapped pairs and tens of thousands of stoppers: this thread's later pairs need not be looked at)
       if (!sw[SW - 1]) break;
     }
-    svc_drain_barrier();  // (every wave's swaps have left the wave)
+    svc_drain_barrier(team);  // (every wave's swaps have left the wave)
     mark(2);
     const uint32_t cut = S.cut;
-    __syncthreads();  // (everybody has the cut: lane 0 resets it below)
+    team.sync();  // (everybody has the cut: lane 0 resets it below)
     if (cut == 0xFFFFFFFFu || cut <= first || cut > last)
     {
       if (tid == 0) SVC_FAIL(P, 8u, first, last, cut);  // (a partition always yields a cut inside the segment: reported, never silent)
@@ -469,6 +470,7 @@ template <uint32_t NT, bool WIDE> __device__ __forceinline__ void svc_part(const
       const bool carry_heap = carry && depth == 0;
       if (push_g || push_h || carry_heap)
       {
+        team.count_pushes((push_h ? 1u : 0u) + (push_g ? 1u : 0u));
         if (P.q[0].release & 1u) svc_release();  // (one release of everything this workgroup has swapped so far, in front of the pushes)
         if (push_h)
         {
@@ -498,7 +500,7 @@ template <uint32_t NT, bool WIDE> __device__ __forceinline__ void svc_part(const
       else
         S.go_on = 0;
     }
-    svc_drain_barrier();
+    svc_drain_barrier(team);
     mark(3);
     if (!S.go_on) break;
   }
@@ -625,10 +627,10 @@ __device__ __forceinline__ uint32_t f2_partition(Fin2Lds &L, const uint32_t firs
   f2_wsync();
   return cut;
 }
-// every thread of the (256-thread) workgroup calls this; returns (thread 0) the elements handed on as heap tasks via L.ext / L.n_ext
-__device__ __forceinline__ void fin2_body(Fin2Lds &L, const uint32_t g0, const uint32_t g1, const int32_t depth0, uint32_t *key, uint32_t *idx)
+// every thread of the 256-thread team calls this; returns (thread 0) the elements handed on as heap tasks via L.ext / L.n_ext
+template <class T = WgTeam> __device__ __forceinline__ void fin2_body(Fin2Lds &L, const uint32_t g0, const uint32_t g1, const int32_t depth0, uint32_t *key, uint32_t *idx, const T &team = T())
 {
-  const uint32_t tid = threadIdx.x, lane = tid & 63, w = tid >> 6, m = g1 - g0;
+  const uint32_t tid = team.tid(), lane = tid & 63, w = tid >> 6, m = g1 - g0;
   for (uint32_t e = tid; e < m; e += 256) L.ent[e] = ((hent) key[g0 + e] << 32) | idx[g0 + e];
   for (uint32_t e = tid; e < F2_QCAP; e += 256) L.q[e] = 0ull;
   if (tid == 0)
@@ -641,7 +643,7 @@ __device__ __forceinline__ void fin2_body(Fin2Lds &L, const uint32_t g0, const u
     L.ext_elems = 0;
     L.bad = 0;
   }
-  __syncthreads();
+  team.sync();
   for (;;)
   {
     // a ticket, then the entry it stands for - or the end of the task
@@ -728,7 +730,7 @@ __device__ __forceinline__ void fin2_body(Fin2Lds &L, const uint32_t g0, const u
       if (!go_on) break;
     }
   }
-  __syncthreads();
+  team.sync();
   for (uint32_t e = tid; e < m; e += 256)
   {
     const hent v = L.ent[e];
@@ -969,3 +971,229 @@ __global__ __launch_bounds__(256) void k_svc_submit(const SvcParams P, const Svc
   }
 }
 
+// ---- one sort as ONE ordinary dispatch on the caller's stream (the launch path: no service running) ---------------------------------
+// The task bodies above on queues and a job of the caller's own (SortEmuBufs, never shared), seeded by k_sort_job_submit in front of
+// the dispatch.  Every workgroup is 1024 threads with all of a CU's LDS: workgroups [0, n_wide) serve the wide queue as the service's
+// wide kernel does, every other one is SJ_TEAMS teams of 256 threads that serve the narrow queue on their own (LdsTeam: their own
+// barrier, thread index, slice of the LDS and of the position lists).  A task still never waits for another task.  A workgroup
+// (team) leaves when the job is done, when a task failed, or when nothing can arrive any more: no partition or finisher task is
+// queued or running (`live`, counted up before every push of one and down behind the last push of the task that pushed it; heaps
+// push nothing) and its own ticket's slot is empty - so the idle CUs go back to the caller's other kernels while the long heaps run,
+// and a workgroup that starts late finds the job done and leaves.  No progress for SJ_TIMEOUT_TICKS: error 4, never a hang.
+constexpr uint32_t SJ_TEAMS = 4;
+constexpr size_t SJ_TEAM_LDS = ((sizeof(Fin2Lds) > (HEAP_BIG_MIN + HEAP_PAD) * 8 ? sizeof(Fin2Lds) : (HEAP_BIG_MIN + HEAP_PAD) * 8) + 15) & ~(size_t) 15;
+static_assert(SJ_TEAMS * SJ_TEAM_LDS + 4096 <= 160 * 1024, "four narrow teams in a CU's LDS");
+constexpr uint32_t SJ_MAX_WIDE = 32, SJ_MAX_NARROW = 32;        // workgroups per dispatch of each kind (three lanes: 192 of 256 CUs)
+constexpr unsigned long long SJ_TIMEOUT_TICKS = 100000000ull;  // 1 s of wall_clock64 without a task while tasks can still arrive
+// ctl words of a caller's queues (SortEmuBufs::tj_ctl)
+constexpr uint32_t SJ_C_ERROR = 128, SJ_C_STATS = 160, SJ_C_QUIT = 192, SJ_C_LIVE = 224, SJ_C_HOST = 256, SJ_C_WORDS = SJ_C_HOST + SVC_H_WORDS;
+
+struct SjParams
+{
+  SvcParams P;          // the caller's queues; P.jobs = its job (slot 0); P.host = device words that stand in for the service's host words
+  uint32_t n_wide;
+  uint32_t *live;       // partition and finisher tasks pushed and not finished
+  uint32_t *heavy;      // (or null) per group: the longest heap segment of more than heavy_min elements a partition node left
+  const uint32_t *gof;  // group of every position
+  uint32_t heavy_min;
+  unsigned long long *trace;  // (BK_DEBUG=svc, or null) [0] first workgroup start, [1] longest heap: elements << 40 | start, [2] the
+                              // same with its ticks, [3] end of the last partition / finisher task, [4] end of the last task
+};
+
+template <bool WIDE, class T>
+__device__ __forceinline__ void sj_serve(const SjParams &S, const SvcJobLds &J, SvcTask &s_task, int &s_state, SvcPartLds<WIDE ? 1024u : 256u> &s_part, unsigned char *pool, uint32_t *pos, const T &team)
+{
+  constexpr uint32_t NT = WIDE ? 1024u : 256u;
+  const SvcParams &P = S.P;
+  const SvcQueue &q = P.q[WIDE ? 0 : 1];
+  const uint32_t tid = team.tid();
+  SvcJob *job = J.job;
+  unsigned long long t_last = wall_clock64(), t_task = t_last;
+  if (S.trace && tid == 0) atomicMin(S.trace, t_last);
+  for (;;)
+  {
+    if (tid == 0)
+    {
+      int st = 0;
+      SvcTask t;
+      const uint32_t ticket = svc_ticket(q);
+      for (uint32_t polls = 0, nap = 1;; ++polls)
+      {
+        if (svc_take(q, ticket, t))
+        {
+          st = 1;
+          break;
+        }
+        if ((polls & 7u) == 0)
+        {
+          if (svc_read(P.error) != 0u || svc_read(&job->remaining) == 0u)
+          {
+            st = 2;
+            break;
+          }
+          if (svc_read(S.live) == 0u)
+          {
+            // every push there will be has landed (the count goes down behind the pusher's waited stores): one more look at the slot
+            st = svc_take(q, ticket, t) ? 1 : 2;
+            break;
+          }
+          if (wall_clock64() - t_last > P.timeout_ticks)
+          {
+            SVC_FAIL(P, 4u, WIDE ? 1u : 0u, svc_read(&job->remaining), svc_read(S.live));
+            st = 2;
+            break;
+          }
+        }
+        for (uint32_t k = 0; k < nap; ++k) __builtin_amdgcn_s_sleep(32);
+        if (nap < 4) ++nap;
+      }
+      if (st == 1) svc_acquire();  // (also what a team of this CU wrote before it pushed: never optimised away)
+      s_task = t;
+      s_state = st;
+      t_task = wall_clock64();
+    }
+    team.sync();
+    if (s_state != 1) return;
+    const SvcTask t = s_task;
+    const uint32_t type = t.type_job & 15u, job_tag = t.type_job >> 4;
+    if (type == SVC_T_PART)
+    {
+      svc_part<NT, WIDE, T>(P, J, s_part, t, pos, P.pos_cap[WIDE ? 0 : 1], team);
+      if (tid == 0)
+      {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (the pushes have landed)
+        atomicSub(S.live, 1u);
+      }
+    }
+    else if (type == SVC_T_HEAP)
+    {
+      const uint32_t m = t.last - t.first;
+      if (WIDE)
+        heap_big_body(t.first, t.last, J.key, J.idx, J.hscratch, J.scratch32, J.scratch32b, J.rka, J.rkb, reinterpret_cast<hent *>(pool), P.cap32, NT);
+      else
+        heap_small_body<T>(t.first, t.last, J.key, J.idx, reinterpret_cast<hent *>(pool), NT, team);
+      svc_drain_barrier(team);
+      if (tid == 0)
+      {
+        // (what the lanes of api.hip balance on: heaps above FIN_MAX elements are the partition nodes', never the finisher's)
+        if (S.heavy && m > S.heavy_min) atomicMax(S.heavy + S.gof[t.first], m);
+        if (S.trace)
+        {
+          const unsigned long long now = wall_clock64();
+          atomicMax(S.trace + 1, ((unsigned long long) m << 40) | (t_task & 0xFFFFFFFFFFull));
+          atomicMax(S.trace + 2, ((unsigned long long) m << 40) | ((now - t_task) & 0xFFFFFFFFFFull));
+        }
+        svc_retire(P, job, job_tag, m);
+      }
+    }
+    else if (type == SVC_T_FIN && !WIDE)
+    {
+      Fin2Lds &L = *reinterpret_cast<Fin2Lds *>(pool);
+      fin2_body<T>(L, t.first, t.last, t.depth, J.key, J.idx, team);
+      svc_drain_barrier(team);
+      if (tid == 0)
+      {
+        if (L.bad) SVC_FAIL(P, 64u, t.first, t.last, L.bad | (L.q_tail << 8) | (L.n_ext << 20));
+        const uint32_t nh = L.n_ext < F2_EXT ? L.n_ext : F2_EXT;
+        if (nh && (P.q[0].release & 1u)) svc_release();
+        for (uint32_t k = 0; k < nh; ++k) svc_push_heap(P, job, job_tag, L.ext[k].x, L.ext[k].y);
+        svc_retire(P, job, job_tag, (t.last - t.first) - L.ext_elems);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        atomicSub(S.live, 1u);
+      }
+    }
+    else if (tid == 0)
+      SVC_FAIL(P, 16u, type, t.first, t.last);  // a task in the wrong queue
+    if (tid == 0)
+    {
+      t_last = wall_clock64();
+      if (S.trace)
+      {
+        if (type != SVC_T_HEAP) atomicMax(S.trace + 3, t_last);
+        atomicMax(S.trace + 4, t_last);
+      }
+    }
+    team.sync();
+  }
+}
+
+__global__ __launch_bounds__(1024) void k_sort_job(const SjParams S, const SvcJobLds J)
+{
+  extern __shared__ __attribute__((aligned(16))) unsigned char pool[];
+  __shared__ SvcTask s_task[SJ_TEAMS];
+  __shared__ int s_state[SJ_TEAMS];
+  __shared__ uint32_t s_bar[SJ_TEAMS][2];
+  __shared__ union
+  {
+    SvcPartLds<1024> wide;
+    SvcPartLds<256> narrow[SJ_TEAMS];
+  } s_part;
+  if (blockIdx.x < S.n_wide)
+  {
+    sj_serve<true>(S, J, s_task[0], s_state[0], s_part.wide, pool, S.P.pos[0] + 2ull * S.P.pos_cap[0] * blockIdx.x, WgLive{{}, S.live});
+    return;
+  }
+  const uint32_t team = threadIdx.x >> 8;
+  if ((threadIdx.x & 255u) == 0)
+  {
+    s_bar[team][0] = 0u;
+    s_bar[team][1] = 0u;
+  }
+  __syncthreads();  // (the only barrier of the whole workgroup: from here on the teams meet on their own)
+  sj_serve<false>(S, J, s_task[team], s_state[team], s_part.narrow[team], pool + team * SJ_TEAM_LDS,
+                  S.P.pos[1] + 2ull * S.P.pos_cap[1] * ((blockIdx.x - S.n_wide) * SJ_TEAMS + team), LdsTeam{s_bar[team], team * 256u, S.live});
+}
+
+// One block, in front of k_sort_job on the same stream: the queues start where the last sort left them (head = tail: tickets of
+// workgroups that left unserved are given up), the descriptor, then a task per group of more than 16 elements (as k_svc_submit).
+__global__ __launch_bounds__(256) void k_sort_job_submit(const SjParams S, const SvcJob desc, const uint64_t *__restrict__ goff, uint32_t ng)
+{
+  __shared__ uint32_t s_total, s_tasks;
+  const SvcParams &P = S.P;
+  SvcJob *job = P.jobs;
+  const uint32_t job_tag = desc.epoch << 8;
+  if (threadIdx.x == 0)
+  {
+    s_total = 0;
+    s_tasks = 0;
+    for (int k = 0; k < 2; ++k) svc_write(P.q[k].head, svc_read(P.q[k].tail));
+    for (int k = 0; k < 12; ++k) svc_write(P.error + k, 0u);
+    svc_write(S.live, 0u);
+    if (S.trace)
+    {
+      svc_write(S.trace, ~0ull);
+      for (int k = 1; k < 5; ++k) svc_write(S.trace + k, 0ull);
+    }
+    const unsigned long long *src = reinterpret_cast<const unsigned long long *>(&desc);
+    unsigned long long *dst = reinterpret_cast<unsigned long long *>(job);
+    for (uint32_t k = 0; k < sizeof(SvcJob) / 8; ++k)
+      if (k != 9) svc_write(dst + k, src[k]);  // (word 9 = remaining / done, below)
+    svc_write(&job->done, 0u);
+    svc_write(&job->remaining, SVC_BIAS);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    svc_release();
+  }
+  __syncthreads();
+  uint32_t mine = 0, tasks = 0;
+  for (uint32_t g = threadIdx.x; g < ng; g += blockDim.x)
+  {
+    const uint32_t first = (uint32_t) goff[g], last = (uint32_t) goff[g + 1], sz = last - first;
+    if (sz <= 16) continue;
+    mine += sz;
+    ++tasks;
+    const int32_t depth = 2 * (31 - __clz((int) sz));
+    if (sz <= FIN_MAX)
+      svc_push(P.q[1], SvcTask{svc_tag(SVC_T_FIN, job_tag), first, last, depth}, P.error);
+    else
+      svc_push_part(P, job_tag, first, last, depth);
+  }
+  atomicAdd(&s_total, mine);
+  atomicAdd(&s_tasks, tasks);
+  __syncthreads();
+  if (threadIdx.x == 0)
+  {
+    svc_write(S.live, s_tasks);
+    const uint32_t add = s_total - SVC_BIAS;
+    if (atomicAdd(&job->remaining, add) + add == 0u) svc_done(P, job, desc.epoch);
+  }
+}

@@ -254,6 +254,10 @@ int bk_shard_bp_finish(bk_ctx *ctx, const void *depth_total_dev);
  * BreakID.cc:1274-1282,1091,1127) and returns the permutation (perm_out[p] = original index of the element now at p). */
 int bk_debug_std_sort(bk_ctx *ctx, const uint32_t *key, const uint64_t *group_off, uint32_t n_groups, uint32_t *perm_out);
 
+/* Test hook: how the std::sort replays of this context ran so far, summed over its lanes: out[0] jobs of the resident sort
+ * service, out[1] task dispatches on the caller's stream, out[2] chains of launches (BREAKID_SORT_TASKS=0). */
+int bk_sort_forms(bk_ctx *ctx, uint64_t out[3]);
+
 /* Test hook: find_cluster_pairs_enspan_ahc (BreakID.cc:1304-1352) on one group of x-sorted points; returns the
  * surviving point indices in output order with their cluster numbers. */
 int bk_debug_ahc(bk_ctx *ctx, const uint32_t *x, const uint32_t *y, uint32_t n, double w, uint32_t *idx_out, int32_t *cluster_out, uint32_t *n_out);
