@@ -15,6 +15,7 @@
 #include "join.h"
 #include "cluster.h"
 #include "bp.h"
+#include "normal.h"
 #include "ahc.h"
 #include "bgzf_gpu.h"
 
@@ -136,6 +137,13 @@ struct bk_ctx
   BpBufs bb;
   DevBuf d_clusters;
   uint64_t n_clusters = 0;
+
+  // call order / kind of this context, checked by bk_normal_support
+  bool joined = false, bp_done = false, shard = false;
+  double join_w = 0;
+  // matched normal (bk_normal_support: this context is the tumour)
+  NormalBufs nb;
+  std::vector<struct bk_normal_support> f_normal;
 
   // fetch staging
   std::vector<bk_pair> f_pairs[3];
@@ -498,6 +506,7 @@ int bk_upload_records(bk_ctx *ctx, const bk_soa *s, int mem_space)
     if (!s) throw bk_error(BK_ERR_ARG, "bk_upload_records: null table");
     if (s->n > 0xFFFFFFF0ull) throw bk_error(BK_ERR_LIMIT, "more than 2^32 records in one context (shard across GPUs)");
     ctx->stream_done = ctx->stats_done = ctx->clustered = false;
+    ctx->joined = ctx->bp_done = ctx->shard = false;
     ctx->ext_cand = nullptr;
     ctx->ext_split = nullptr;
     ctx->ext_clusters = nullptr;
@@ -649,6 +658,9 @@ int bk_discordant_pairs(bk_ctx *ctx, int mapq_min, double w, uint64_t *n_pairs, 
     }
     finish_groups(ctx, nullptr);
     ctx->clustered = false;
+    ctx->joined = true;
+    ctx->bp_done = false;
+    ctx->join_w = w;
     if (n_pairs) *n_pairs = ctx->jr.n_pairs;
     if (n_groups) *n_groups = ctx->jr.n_groups;
   });
@@ -1318,6 +1330,7 @@ int bk_cluster_summary(bk_ctx *ctx, double w, uint64_t *n_clusters)
 {
   return guarded(ctx, [&] {
     if (!ctx->clustered) throw bk_error(BK_ERR_ARG, "bk_cluster_summary: call bk_mask_and_cluster first");
+    ctx->bp_done = false;
     Scope s(ctx, "cluster_summary");
     ctx->n_clusters = cluster_summary(ctx->jr.pairs, ctx->list.idx.get<uint32_t>(), ctx->list.gof.get<uint32_t>(), ctx->d_cluster.get<uint32_t>(), ctx->list.n,
                                       ctx->list.ng, ctx->jr.gkey, ctx->d_glex.get<uint32_t>(), ctx->nt, w, ctx->d_clusters, ctx->bb, ctx->st);
@@ -1338,7 +1351,62 @@ int bk_split_breakpoints(bk_ctx *ctx, double w, uint64_t *n_valid)
       split_breakpoints(r, ctx->d_split.get<bk_split>(), ctx->hc.n_split, ctx->clusters_ptr(), ctx->n_clusters, w, (int) ctx->hc.max_span,
                         ctx->d_hdr.get<int32_t>(), ctx->bb, ctx->st);
     }
+    ctx->bp_done = true;
     if (n_valid) *n_valid = count_valid_clusters(ctx->clusters_ptr(), ctx->n_clusters, ctx->bb, ctx->st);
+  });
+}
+
+int bk_normal_support(bk_ctx *tumor, bk_ctx *normal, double w, const struct bk_normal_support **out, uint64_t *count)
+{
+  if (!normal) return guarded(tumor, [&] { throw bk_error(BK_ERR_ARG, "bk_normal_support: null normal context"); });
+  return guarded(tumor, [&] {
+    if (!out || !count) throw bk_error(BK_ERR_ARG, "bk_normal_support: null output");
+    if (tumor->shard || normal->shard) throw bk_error(BK_ERR_ARG, "bk_normal_support: sharded contexts (bk_shard_*) are not supported");
+    if (!tumor->bp_done) throw bk_error(BK_ERR_ARG, "bk_normal_support: call bk_split_breakpoints on the tumour context first");
+    if (!normal->stats_done || !normal->joined || !normal->splits_sorted)
+      throw bk_error(BK_ERR_ARG, "bk_normal_support: call bk_isize_stats, bk_discordant_pairs and bk_split_evidence on the normal context first");
+    if (tumor->join_w != w) throw bk_error(BK_ERR_ARG, "bk_normal_support: w is not the tumour's distance (its bk_discordant_pairs w)");
+    if (normal->stream_mapq != tumor->stream_mapq || normal->join_w != w)
+      throw bk_error(BK_ERR_ARG, "bk_normal_support: the normal's bk_discordant_pairs must use the tumour's mapq_min and w");
+    if (normal->device != tumor->device)
+      throw bk_error(BK_ERR_ARG, "bk_normal_support: tumour (device " + std::to_string(tumor->device) + ") and normal (device " + std::to_string(normal->device) +
+                                     ") contexts are on different devices");
+    if (normal->nt != tumor->nt || normal->tname != tumor->tname || normal->tlen != tumor->tlen)
+      throw bk_error(BK_ERR_ARG, "bk_normal_support: tumour and normal reference lists differ (names or lengths)");
+    Scope s(tumor, "normal_support");
+    HIP_CHECK(hipStreamSynchronize(normal->st));  // the normal's stages ran on its own stream
+    NormalSide ns;
+    ns.pairs = normal->jr.pairs;
+    ns.n_pairs = normal->jr.n_pairs;
+    ns.sp = normal->d_split.get<bk_split>();
+    ns.n_split = normal->hc.n_split;
+    ns.rec = rec_view(normal);
+    ns.maxspan = (int) normal->hc.max_span;
+    ns.hdr_id = normal->d_hdr.get<int32_t>();
+    ns.own_id = normal->names.own_id;
+    ns.empty_id = normal->names.empty_id;
+    const uint64_t ncl = tumor->n_clusters;
+    struct bk_normal_support *d_res;
+    uint32_t *d_grp;
+    normal_support(ns, tumor->clusters_ptr(), ncl, tumor->nt, w, tumor->nb, tumor->st, &d_res, &d_grp);
+    std::vector<struct bk_normal_support> res(ncl);
+    std::vector<uint32_t> grp(ncl);
+    if (ncl)
+    {
+      HIP_CHECK(hipMemcpyAsync(res.data(), d_res, ncl * sizeof(struct bk_normal_support), hipMemcpyDeviceToHost, tumor->st));
+      HIP_CHECK(hipMemcpyAsync(grp.data(), d_grp, ncl * 4, hipMemcpyDeviceToHost, tumor->st));
+    }
+    HIP_CHECK(hipStreamSynchronize(tumor->st));
+    // device order is (numeric chr-pair key, id); BK_STAGE_CLUSTERS is the stable order by `group` (bk_fetch): a counting sort
+    uint32_t gmax = 0;
+    for (uint32_t g : grp) gmax = std::max(gmax, g);
+    std::vector<uint64_t> start(ncl ? (size_t) gmax + 2 : 1, 0);
+    for (uint32_t g : grp) ++start[g + 1];
+    for (size_t g = 1; g < start.size(); ++g) start[g] += start[g - 1];
+    tumor->f_normal.resize(ncl);
+    for (uint64_t c = 0; c < ncl; ++c) tumor->f_normal[start[grp[c]]++] = res[c];
+    *out = tumor->f_normal.data();
+    *count = ncl;
   });
 }
 
@@ -1450,6 +1518,7 @@ int bk_shard_begin(bk_ctx *ctx, uint64_t rec_base, int mapq_min)
 {
   return guarded(ctx, [&] {
     ctx->rec_base = rec_base;
+    ctx->shard = true;
     ctx->mapq_min = mapq_min;
     ctx->ext_cand = nullptr;
     ctx->ext_split = nullptr;

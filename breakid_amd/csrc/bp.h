@@ -3,6 +3,27 @@
 #include "bk_common.h"
 #include "prims.h"
 
+// Lower bound by a whole wavefront: every lookup of bp.hip and normal.hip is made by all 64 lanes of a wave with the same arguments (one
+// wave per cluster), and a binary search is a chain of dependent memory round trips - 30 of them for a record lookup, ~22 for
+// a tuple lookup, the better part of k_bp_cov / k_bp_regions / k_bp_depth.  64 probes per round trip cut the range 65-fold:
+// `less(i)` = "element i orders before the target" (monotone over [lo, hi)); returns the first index for which it is false.
+template <class Less> __device__ __forceinline__ uint64_t wave_lower(uint64_t lo, uint64_t hi, Less less)
+{
+  const uint32_t lane = threadIdx.x & 63;
+  while (hi - lo > 64)
+  {
+    const uint64_t width = hi - lo;
+    const uint64_t p = lo + width * (lane + 1) / 65;  // lo < p < hi
+    const uint32_t c = (uint32_t) __popcll(__ballot(less(p)));  // the probes that order before the target are a prefix of the lanes
+    const uint64_t nlo = c ? lo + width * c / 65 + 1 : lo;
+    const uint64_t nhi = c < 64 ? lo + width * (c + 1) / 65 : hi;
+    lo = nlo;
+    hi = nhi;
+  }
+  const uint64_t i = lo + lane;
+  return lo + (uint64_t) __popcll(__ballot(i < hi && less(i)));
+}
+
 struct ClusterAcc
 {
   uint32_t *n;

@@ -179,26 +179,6 @@ __device__ __forceinline__ int32_t rec_endpos(const RecView &r, uint64_t i)
 // cache resident) the first ~20 steps stay in the cache and only the last 10 touch the record columns.
 constexpr uint32_t REC_SAMPLE_SHIFT = 10;
 __device__ __forceinline__ unsigned long long rec_key(int32_t tid, long long pos) { return ((unsigned long long) (uint32_t) tid << 32) | (uint32_t) (pos + 0x80000000ll); }
-// Lower bound by a whole wavefront: every lookup of this file is made by all 64 lanes of a wave with the same arguments (one
-// wave per cluster), and a binary search is a chain of dependent memory round trips - 30 of them for a record lookup, ~22 for
-// a tuple lookup, the better part of k_bp_cov / k_bp_regions / k_bp_depth.  64 probes per round trip cut the range 65-fold:
-// `less(i)` = "element i orders before the target" (monotone over [lo, hi)); returns the first index for which it is false.
-template <class Less> __device__ __forceinline__ uint64_t wave_lower(uint64_t lo, uint64_t hi, Less less)
-{
-  const uint32_t lane = threadIdx.x & 63;
-  while (hi - lo > 64)
-  {
-    const uint64_t width = hi - lo;
-    const uint64_t p = lo + width * (lane + 1) / 65;  // lo < p < hi
-    const uint32_t c = (uint32_t) __popcll(__ballot(less(p)));  // the probes that order before the target are a prefix of the lanes
-    const uint64_t nlo = c ? lo + width * c / 65 + 1 : lo;
-    const uint64_t nhi = c < 64 ? lo + width * (c + 1) / 65 : hi;
-    lo = nlo;
-    hi = nhi;
-  }
-  const uint64_t i = lo + lane;
-  return lo + (uint64_t) __popcll(__ballot(i < hi && less(i)));
-}
 __device__ uint64_t rec_lower(const RecView &r, int32_t T, long long P)
 {
   uint64_t lo = 0, hi = r.n;

@@ -24,6 +24,10 @@
 #include "../../include/breakid_hip.h"
 #include "../../include/breakid_multi.h"
 
+// -normal: looked up at run time, so that this file also links against a library without the call (the CPU build of the host
+// code, oracle/Makefile); -normal then ends with an error
+extern "C" int bk_normal_support(bk_ctx *tumor, bk_ctx *normal, double w, const struct bk_normal_support **out, uint64_t *count) __attribute__((weak));
+
 // bam_index_load (htslib-1.3.1 sam.h:302 -> hts.c:2042 hts_idx_load, :1580 hts_idx_load_local, :1528 hts_idx_load_core): the index is
 // <bam>.csi, <bam with its extension replaced>.csi, <bam>.bai, <...>.bai - the first that can be opened - and it must parse to the
 // end: magic, counts, every bin's chunk list and every linear index (a truncated or foreign file gives NULL, i.e. the reference's
@@ -352,13 +356,14 @@ static const char *fusion_type(uint32_t mask)  // determine_fusion_type_from_drp
 struct OutRow
 {
   bk_cluster c;
+  uint64_t idx;  // row of BK_STAGE_CLUSTERS (the matched normal's counts, bk_normal_support)
   string p1_chr, p2_chr, g1, g2, e1, e2, s1, s2, rpt1, rpt2;
   bool is_rpt;
   float af1, af2;
 };
 static bool cmp_cluster(OutRow a, OutRow b) { return a.c.n_drp > b.c.n_drp; }  // BreakID.h:185-188 (by value, like the reference)
 
-static void write_row(std::ostream &o, const OutRow &r)
+static void write_row(std::ostream &o, const OutRow &r, const struct bk_normal_support *ns = nullptr)
 {
   o << fusion_type(r.c.type_mask) << "\t";
   o << r.p1_chr << ":" << r.c.p1_exact << "\t";
@@ -368,20 +373,37 @@ static void write_row(std::ostream &o, const OutRow &r)
   o << (long) r.c.n_drp << "\t" << (long) r.c.n_sr << "\t";
   o << (double) r.c.depth1 << "\t" << (double) r.c.depth2 << "\t";
   o << r.af1 << "\t" << r.af2 << "\t";
-  o << r.rpt1 << "\t" << r.rpt2 << "\n";
+  o << r.rpt1 << "\t" << r.rpt2;
+  if (ns) o << "\t" << ns->n_drp << "\t" << ns->n_sr << "\t" << ns->depth1 << "\t" << ns->depth2;
+  o << "\n";
 }
 
 static const char *HEADER =
     "Fusion_Type\tBreakPoint1\tBreakPoint2\tGene1\tBreakPoint_Info_Pair1\tGene2\tBreakPoint_Info_Pair2\tN_DRP\tN_SR\t"
     "BreakPoint1_Depth\tBreakPoint2_Depth\tBreakPoint1_AF\tBreakPoint2_AF\tBP1_Neighbour_Seq\tBP2_Neighbour_Seq\n";
+static const char *NORMAL_COLUMNS = "\tNormal_DRP\tNormal_SR\tNormal_Depth1\tNormal_Depth2\n";
+
+// one input BAM: its decoded table (host or device) and, once created, its context
+struct Sample
+{
+  string path;
+  bk_bam *bam = nullptr;
+  bk_bam_dev *dbam = nullptr;
+  int nt = 0;
+  const char *const *names = nullptr;
+  const uint32_t *lens = nullptr;
+  bk_soa soa{};
+  int soa_where = BK_MEM_HOST;
+  bk_ctx *ctx = nullptr;
+};
 
 int main(int argc, char *argv[])
 {
   clock_t start = clock();
   static struct option longopts[] = {{"help", 0, 0, 'h'}, {"i", 1, 0, 1}, {"o", 1, 0, 2}, {"q", 1, 0, 3}, {"n", 1, 0, 4},
                                      {"fast", 0, 0, 5},   {"t", 0, 0, 6}, {"all", 0, 0, 7}, {"gpu", 1, 0, 8}, {"gpus", 1, 0, 9},
-                                     {"comm", 1, 0, 10},  {0, 0, 0, 0}};
-  string inp_file, out_file, nib_dir, build = "hg19";
+                                     {"comm", 1, 0, 10},  {"normal", 1, 0, 11}, {0, 0, 0, 0}};
+  string inp_file, out_file, nib_dir, normal_file, build = "hg19";
   int qual = 20, device = 0, n_gpus = 0, transport = BK_TRANSPORT_AUTO;  // -gpus N: one sample over N GPUs (include/breakid_multi.h)
   bool fast = false, filter = true;
   int opt, li;
@@ -401,6 +423,7 @@ int main(int argc, char *argv[])
     case 8: device = atoi(optarg); break;
     case 9: n_gpus = atoi(optarg); break;
     case 10: transport = !strcmp(optarg, "rccl") ? BK_TRANSPORT_RCCL : !strcmp(optarg, "local") ? BK_TRANSPORT_LOCAL : BK_TRANSPORT_AUTO; break;
+    case 11: normal_file = optarg; break;
     default: std::cerr << "Error: cannot parse arguments.\n"; exit(1);
     }
   }
@@ -414,18 +437,39 @@ int main(int argc, char *argv[])
     std::cerr << HELP << "Error: nib file's root dir is required.\n";
     exit(1);
   }
+  if (!normal_file.empty())
+  {
+    if (n_gpus >= 1)
+    {
+      std::cerr << HELP << "Error: -normal cannot be combined with -gpus.\n";
+      exit(1);
+    }
+    if (!bk_normal_support)
+    {
+      std::cerr << "Error: -normal needs the GPU library" << std::endl;
+      exit(1);
+    }
+    FILE *probe = fopen(normal_file.c_str(), "rb");
+    if (!probe)
+    {
+      std::cerr << "Error: can not open normal bam-file: " << normal_file << std::endl;
+      exit(1);
+    }
+    fclose(probe);
+  }
   std::cout << "start to stats the insert size...\n";
   // feed: the GPU decoder first (BGZF inflate + record decode on the device; every htslib-written BAM qualifies), the
   // host decoder (all cores, pinned columns) for files whose records straddle BGZF blocks or that exceed one batch.
   // BREAKID_HOST_DECODE=1 forces the host path.
   char err[512];
-  bk_bam *bam = nullptr;
-  bk_bam_dev *dbam = nullptr;
-  int nt = 0;
-  const char *const *names = nullptr;
-  const uint32_t *lens = nullptr;
-  bk_soa soa;
-  int soa_where = BK_MEM_HOST;
+  Sample tumor, normal;
+  tumor.path = inp_file;
+  normal.path = normal_file;
+  int &nt = tumor.nt;
+  const char *const *&names = tumor.names;
+  const uint32_t *&lens = tumor.lens;
+  bk_soa &soa = tumor.soa;
+  int &soa_where = tumor.soa_where;
   {
     FILE *probe = fopen(inp_file.c_str(), "rb");
     if (!probe)
@@ -436,28 +480,37 @@ int main(int argc, char *argv[])
     fclose(probe);
   }
   const bool multi = n_gpus >= 1;  // the sharded run: every rank decodes its part of the file on its own GPU (below), or takes its range of the host table
-  bk_ctx *ctx = nullptr;
-  auto host_decode = [&] {
-    dbam = nullptr;
-    if (bk_bam_open(inp_file.c_str(), &bam, err, sizeof err) != BK_OK)
+  bk_ctx *&ctx = tumor.ctx;
+  auto host_decode_sample = [&](Sample &s) {
+    s.dbam = nullptr;
+    if (bk_bam_open(s.path.c_str(), &s.bam, err, sizeof err) != BK_OK)
     {
-      std::cerr << "Error: can not open bam-file: " << inp_file << std::endl;
+      std::cerr << "Error: can not open bam-file: " << s.path << std::endl;
       exit(1);
     }
-    bk_bam_header(bam, &nt, &names, &lens);
-    if (bk_bam_decode(bam, &soa, err, sizeof err) != BK_OK)
+    bk_bam_header(s.bam, &s.nt, &s.names, &s.lens);
+    if (bk_bam_decode(s.bam, &s.soa, err, sizeof err) != BK_OK)
     {
       std::cerr << "Error: " << err << std::endl;
       exit(1);
     }
   };
-  const bool multi_from_file = multi && !getenv("BREAKID_HOST_DECODE");
+  auto host_decode = [&] { host_decode_sample(tumor); };
   // one read of the file: BGZF inflate + record decode on the device, the stream pass of the hot path running on the chunks
-  // already decoded while the rest of the file is still arriving (the reference reads the BAM twice, BreakID.cc:1929, :1414)
-  if (!multi && !getenv("BREAKID_HOST_DECODE") && bk_bam_decode_device_ctx(inp_file.c_str(), device, qual, &dbam, &ctx, &nt, &names, &lens, err, sizeof err) == BK_OK)
+  // already decoded while the rest of the file is still arriving (the reference reads the BAM twice, BreakID.cc:1929, :1414);
+  // false when the GPU feed refuses the file (or BREAKID_HOST_DECODE=1): the host decoder takes it then
+  auto gpu_decode = [&](Sample &s) {
+    if (getenv("BREAKID_HOST_DECODE") ||
+        bk_bam_decode_device_ctx(s.path.c_str(), device, qual, &s.dbam, &s.ctx, &s.nt, &s.names, &s.lens, err, sizeof err) != BK_OK)
+      return false;
+    s.soa_where = BK_MEM_DEVICE;
+    return true;
+  };
+  const bool multi_from_file = multi && !getenv("BREAKID_HOST_DECODE");
+  if (!multi && gpu_decode(tumor))
   {
-    soa_where = BK_MEM_DEVICE;
-    bk_feed_release_caches();  // this process decodes one file: the feed's staging buffers and slots (1-2.5 GB of device memory) go back
+    // the feed's staging buffers and slots (1-2.5 GB of device memory) go back once the last file of the process is decoded
+    if (normal_file.empty()) bk_feed_release_caches();
   }
   else if (!multi_from_file)
     host_decode();
@@ -542,6 +595,38 @@ int main(int argc, char *argv[])
     if ((rc = bk_split_breakpoints(ctx, w, &n_valid)) != BK_OK) die(rc);
     bp_end = clock();
   }
+  // matched normal: decoded now (both record tables stay resident), then only its record-level stages and the per-call search
+  const struct bk_normal_support *nsup = nullptr;
+  uint64_t n_nsup = 0;
+  if (!normal_file.empty())
+  {
+    if (!gpu_decode(normal)) host_decode_sample(normal);
+    bk_feed_release_caches();
+    bool same = normal.nt == nt;
+    for (int i = 0; same && i < nt; ++i) same = !strcmp(normal.names[i], names[i]) && normal.lens[i] == lens[i];
+    if (!same)
+    {
+      std::cerr << "Error: tumor and normal BAM headers differ" << std::endl;
+      exit(1);
+    }
+    auto die_normal = [&] {
+      std::cerr << "Error: normal " << normal.path << ": " << bk_last_error(normal.ctx) << std::endl;
+      exit(1);
+    };
+    if (!normal.ctx)
+    {
+      if (bk_init(device, normal.lens, normal.names, normal.nt, &normal.ctx) != BK_OK)
+      {
+        std::cerr << "Error: " << bk_last_error(nullptr) << std::endl;
+        exit(1);
+      }
+      if (bk_upload_records(normal.ctx, &normal.soa, normal.soa_where) != BK_OK) die_normal();
+    }
+    if (bk_isize_stats(normal.ctx, nullptr, nullptr) != BK_OK || bk_discordant_pairs(normal.ctx, qual, w, nullptr, nullptr) != BK_OK ||
+        bk_split_evidence(normal.ctx, nullptr) != BK_OK)
+      die_normal();
+    if ((rc = bk_normal_support(ctx, normal.ctx, w, &nsup, &n_nsup)) != BK_OK) die(rc);
+  }
   const void *data = nullptr;
   uint64_t cnt = 0;
   if ((rc = bk_fetch(ctx, BK_STAGE_CLUSTERS, &data, &cnt, nullptr, nullptr)) != BK_OK) die(rc);
@@ -573,6 +658,7 @@ int main(int argc, char *argv[])
     if (!(cl[i].flags & 2u)) continue;
     OutRow r;
     r.c = cl[i];
+    r.idx = i;
     r.p1_chr = cl[i].p1_tid < 0 ? "*" : names[cl[i].p1_tid];
     r.p2_chr = cl[i].p2_tid < 0 ? "*" : names[cl[i].p2_tid];
     long p1 = (long) cl[i].p1_exact, p2 = (long) cl[i].p2_exact;  // exact positions are never -1 for valid clusters
@@ -587,23 +673,45 @@ int main(int argc, char *argv[])
   }
   // write_enspan_out (BreakID.cc:1184-1263): std::sort with the reference's comparator
   std::sort(rows.begin(), rows.end(), cmp_cluster);
-  std::ofstream out, outf;
+  std::ofstream out, outf, out_n, outf_n;  // (_n: the twins with the matched normal's four counts)
+  const bool with_normal = !normal_file.empty();  // (a tumour without calls still gets header-only twins)
+  const string header_n = string(HEADER, strlen(HEADER) - 1) + NORMAL_COLUMNS;
   if (!filter)
   {
     out.open((out_file + "_fusion_all.txt").c_str());
     out << HEADER;
+    if (with_normal)
+    {
+      out_n.open((out_file + "_fusion_all_normal.txt").c_str());
+      out_n << header_n;
+    }
   }
   outf.open((out_file + "_fusion.txt").c_str());
   outf << HEADER;
+  if (with_normal)
+  {
+    outf_n.open((out_file + "_fusion_normal.txt").c_str());
+    outf_n << header_n;
+  }
   for (auto &r : rows)
   {
     bool all_ok = r.c.n_sr > 0 && r.c.p1_exact != 0xFFFFFFFFu && r.c.p2_exact != -1;
     bool filt_ok = all_ok && (!(r.g1 == "intergenic" && r.g2 == "intergenic") && r.g1 != r.g2) && !r.is_rpt;
     if (filt_ok) write_row(outf, r);
     if (!filter && all_ok) write_row(out, r);
+    if (with_normal && r.idx < n_nsup)
+    {
+      if (filt_ok) write_row(outf_n, r, &nsup[r.idx]);
+      if (!filter && all_ok) write_row(out_n, r, &nsup[r.idx]);
+    }
   }
   if (!filter) out.close();
   outf.close();
+  if (with_normal)
+  {
+    if (!filter) out_n.close();
+    outf_n.close();
+  }
   {
     std::ofstream p((out_file + "_params.txt").c_str());  // write_enspan_params :1170-1182
     p << "ENSPAN" << std::endl;
@@ -612,6 +720,7 @@ int main(int argc, char *argv[])
     p << "qual\t" << (long) qual << std::endl;
     p << "w\t" << w << std::endl;
     p << "build\t" << build << std::endl;
+    if (!normal_file.empty()) p << "normal_file\t" << normal_file << std::endl;
   }
   clock_t end = clock();
   std::cout << "the fusion process of file " << inp_file << "  costs time: " << (end - start) / double(CLOCKS_PER_SEC) << " seconds" << std::endl;
@@ -641,7 +750,11 @@ int main(int argc, char *argv[])
     bk_multi_free(ctx);
   else
     bk_free(ctx);
-  if (bam) bk_bam_close(bam);
-  if (dbam) bk_bam_dev_free(dbam);
+  if (normal.ctx) bk_free(normal.ctx);
+  for (Sample *s : {&tumor, &normal})
+  {
+    if (s->bam) bk_bam_close(s->bam);
+    if (s->dbam) bk_bam_dev_free(s->dbam);
+  }
   return 0;
 }

@@ -175,6 +175,28 @@ int bk_split_breakpoints(bk_ctx *ctx, double w, uint64_t *n_valid);
  * w_out receives times*sqrt(times)*(mean+3sd) (:103). */
 int bk_run(bk_ctx *ctx, int mapq_min, int fast, double *w_out, uint64_t *n_valid);
 
+/* ---- matched normal --------------------------------------------------------------------------------------------------
+ * Evidence for every tumour cluster in a second sample (the patient's normal), one row per BK_STAGE_CLUSTERS row, same order.
+ * W = (int) w, the tumour's distance (the integer the breakpoint stage uses).
+ *   n_drp   the normal's discordant pairs (its BK_STAGE_SCAN table) with the cluster's p1_tid / p2_tid, p1_pos in
+ *           [p1_min - W, p1_max + W], p2_pos in [p2_min - W, p2_max + W] and an orientation bit (BK_TYPE_*, computed as for the
+ *           cluster's type_mask) in the cluster's type_mask
+ *   n_sr    voted clusters only (flags bit 1; 0 otherwise): the normal's split-evidence tuples (BK_STAGE_SPLITS) whose own
+ *           record lies on p1_tid or p2_tid (the tuples the vote itself looks at), without the "error cigar" flag, and whose
+ *           (prim_chr, prim_bp, sec_chr, sec_bp) is (p1 chromosome, p1_exact, p2 chromosome, p2_exact) or (p2 chromosome,
+ *           p2_exact, p1 chromosome, p1_exact), each breakpoint within +-2 bp; chromosomes compared as the vote compares them
+ *           (interned ids: the header name's for the call, and for a tuple's own side the id the stream pass gives it).  The unit
+ *           is tuples, not read names: a read whose two alignments both carry SA tags counts twice, as in BK_STAGE_SPLITS.
+ *   depth1, depth2  voted clusters only: cal_single_base_depth at p1_exact / p2_exact on the normal's records.
+ * The struct has no typedef: the name belongs to the call below (as with `struct stat` and stat()). */
+struct bk_normal_support { uint32_t n_drp, n_sr, depth1, depth2; }; /* 16 bytes */
+/* tumor: after bk_split_breakpoints.  normal: after bk_isize_stats, bk_discordant_pairs(same mapq_min, tumour's w) and
+ * bk_split_evidence; w = the tumour's own distance (its bk_discordant_pairs w); same device, identical reference list (names and
+ * lengths); neither may be a shard (bk_shard_*).  *out: one row
+ * per BK_STAGE_CLUSTERS row, library-owned until the next call or bk_free(tumor).  BK_ERR_ARG (with the reason in bk_last_error)
+ * when one of these does not hold.  A normal without pairs or tuples is no error: its counts are 0. */
+int bk_normal_support(bk_ctx *tumor, bk_ctx *normal, double w, const struct bk_normal_support **out, uint64_t *count);
+
 /* Copy a stage's result to library-owned host memory.  *data stays valid until the next bk_fetch
  * of the same stage or bk_free.  group_off (may be NULL) receives n_groups+1 offsets for pair stages. */
 int bk_fetch(bk_ctx *ctx, int stage, const void **data, uint64_t *count, const uint64_t **group_off, uint32_t *n_groups);
