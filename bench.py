@@ -10,10 +10,12 @@ and pairs travel to their owners by RCCL all-to-all (breakid_amd/sharded.py) - s
 scaling; `--scaling weak` shards one sample of N x that size instead: record indices of a sample are 64-bit, only one
 rank's table stays below 2^32 records).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--records R] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--records R] [--dump-outputs DIR] [--full]
 
-Prints ONE JSON line on rank 0 with `roofline` (dominant kernel k_stream, live HIP-event timing) and
-`cpu_baseline` (the CPU oracle port timed on a bounded sample of the same workload, rank 0, N=1)."""
+Prints ONE JSON line on rank 0 with `roofline` (dominant kernel k_stream, live HIP-event timing of the timed steps).  A plain
+run sets up, warms up, times the steps, dumps if asked and prints that line.  `--full` adds the side measurements after the
+timed steps (N=1): `cpu_baseline` (the CPU oracle port timed on a bounded sample of the same workload, with a bit-identity check
+of the GPU result on it) and `from_bam` (file -> calls on a generated BAM)."""
 import argparse
 import json
 import os
@@ -176,17 +178,21 @@ def main():
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--records", type=int, default=620_000_000, help="records per GPU (configs[1]: ~620 M)")
-    ap.add_argument("--cpu-sample", type=int, default=160_000_000, help="records in the CPU-baseline sample (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side measurements beside the headline line (N=1): `cpu_baseline` (--cpu-sample) and `from_bam` "
+                         "(--from-bam, --from-bam-big); without it the run does only what the headline figure needs")
+    ap.add_argument("--cpu-sample", type=int, default=None, help="with --full: records in the CPU-baseline sample (default 160 000 000, 0 = skip)")
     ap.add_argument("--mode", default="fast", choices=["fast", "ahc"])
     ap.add_argument("--seed", type=int, default=12346)
     ap.add_argument("--workload", default="wgs", choices=["wgs", "panel"],
                     help="wgs = configs[1] (the headline line); panel = configs[3] targeted-panel shape (500 loci x 2000x, single GPU, side measurement)")
-    ap.add_argument("--from-bam", type=int, default=4_000_000, metavar="PAIRS",
-                    help="side measurement (N=1, 0 = skip): write a synthetic BAM of PAIRS read pairs and time file -> calls end to end: GPU feed alone, feed "
-                         "with the stream pass overlapped (bk_bam_decode_device_ctx), rest of the hot path; reported as `from_bam` beside the headline line "
-                         "(the metric itself is defined on the resident table)")
+    ap.add_argument("--from-bam", type=int, default=None, metavar="PAIRS",
+                    help="side measurement with --full (N=1, default 4 000 000, 0 = skip): write a synthetic BAM of PAIRS read pairs and time file -> calls "
+                         "end to end: GPU feed alone, feed with the stream pass overlapped (bk_bam_decode_device_ctx), rest of the hot path; reported as "
+                         "`from_bam` beside the headline line (the metric itself is defined on the resident table)")
     ap.add_argument("--from-bam-big", type=int, default=0, metavar="PAIRS",
-                    help="a second file -> calls leg on a file of this many pairs (32 000 000 = 64 M records = 8 GB: a file that does not fit a burst); 0 = skip")
+                    help="with --full: a second file -> calls leg on a file of this many pairs (32 000 000 = 64 M records = 8 GB: a file that does not "
+                         "fit a burst); 0 = skip")
     ap.add_argument("--scaling", default="strong", choices=["strong", "weak"],
                     help="N > 1: strong = configs[2], the --records sample sharded over the ranks (default); weak = one sample of N x --records")
     ap.add_argument("--sharded", type=int, default=-1, help="1: one sample sharded over the ranks (default when --gpus > 1), 0: plain single-table run")
@@ -197,6 +203,14 @@ def main():
         raise SystemExit("bench.py: --gpus must be >= 1")
     if args.steps < 1:
         raise SystemExit("bench.py: --steps must be >= 1")
+    if args.full:
+        args.cpu_sample = 160_000_000 if args.cpu_sample is None else args.cpu_sample
+        args.from_bam = 4_000_000 if args.from_bam is None else args.from_bam
+    else:
+        asked = [opt for opt, v in (("--cpu-sample", args.cpu_sample), ("--from-bam", args.from_bam), ("--from-bam-big", args.from_bam_big)) if v]
+        if asked:
+            raise SystemExit("bench.py: %s: side measurements run only with --full" % ", ".join(asked))
+        args.cpu_sample = args.from_bam = 0
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # started by hand as `python bench.py --gpus N`: this process never touches a GPU, it starts the N ranks as fresh child
         # processes (one per GPU, torch.distributed.run = what the driver would have started), relays rank 0's line and ends
@@ -370,7 +384,7 @@ def main():
             "ranks": {"world_size": dist.get_world_size() if dist.is_initialized() else 1, "backend": dist.get_backend() if dist.is_initialized() else None,
                       "devices_visible": torch.cuda.device_count()},
         }
-        # CPU baseline: the oracle port on a bounded sample of the same workload (rank 0, N = 1 only)
+        # --full: CPU baseline, the oracle port on a bounded sample of the same workload (rank 0, N = 1 only)
         if world == 1 and not use_shards and args.cpu_sample > 0:
             from oracle import pyoracle
             ns = min(args.cpu_sample, n)

@@ -101,3 +101,14 @@ def test_bench_gpus_flag_is_honoured_or_refused():
     assert r.returncode != 0 and "refusing to run" in r.stderr and "{" not in r.stdout
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2"], env=dict(env, WORLD_SIZE="1", RANK="0", LOCAL_RANK="0"), capture_output=True, text=True, timeout=300)
     assert r.returncode != 0 and "WORLD_SIZE=1" in r.stderr and "{" not in r.stdout
+
+
+def test_bench_side_measurements_need_full():
+    """a plain bench.py run makes only the headline line: an option that sizes a side measurement (cpu_baseline, from_bam) is
+    refused without --full, before anything is imported that could touch a GPU"""
+    import subprocess
+    import sys
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    for opt in ("--cpu-sample", "--from-bam", "--from-bam-big"):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), opt, "1000"], env=env, capture_output=True, text=True, timeout=300)
+        assert r.returncode != 0 and opt in r.stderr and "only with --full" in r.stderr and "{" not in r.stdout, (opt, r.stderr[-500:])

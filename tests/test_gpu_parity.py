@@ -184,7 +184,7 @@ def test_side_rows_replace_the_four_candidate_columns():
 def test_wgs_shape_100M_oracle_determinism_and_invariants():
     """The largest table the single-thread oracle finishes in seconds (100 M records, ~6 s): bit-identical final calls,
     the same bytes from a second run and from the sharded driver at world size 1 (routed exchange), and the
-    size-independent invariants of the cluster table (full size, 620 M: bench.py re-checks a 160 M sample every run)."""
+    size-independent invariants of the cluster table (full size, 620 M: bench.py --full re-checks a 160 M sample)."""
     import zlib
     import torch
     from breakid_amd import sharded, synth_gpu

@@ -2,7 +2,7 @@ set -e
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 D=gpurun_out/prof_r04
 mkdir -p $D
-python bench.py > $D/bench_final.log 2> $D/bench_final.err
+timeout -k 10 660 python bench.py --full > $D/bench_final.log 2> $D/bench_final.err
 echo bench done
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $D/ks_raw -o ks -- python3 bench.py --steps 3 --warmup 1 --cpu-sample 0 --from-bam 0 > $D/ks.log 2>&1
 cp $(find $D/ks_raw -name "*kernel_stats.csv" | head -n 1) $D/ks_kernel_stats.csv

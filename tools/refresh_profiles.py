@@ -1,11 +1,11 @@
 """Copies the summaries of a bench + rocprofv3 session (<dir>/bench_final.log, <dir>/{ks,fetch,write}_*.csv) into profiles/
-under a round prefix.  Usage: python tools/refresh_profiles.py gpurun_out/prof_r02 r02
+under a round prefix.  Usage: python tools/refresh_profiles.py <dir> r02 (<dir> relative to the repository root)
 
-On the GPU box (one gpurun call):
-  python bench.py > gpurun_out/prof_r02/bench_final.log
-  rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_r02/ks_raw -o ks -- python3 bench.py --steps 3 --warmup 1 --cpu-sample 0
-  rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d gpurun_out/prof_r02/f_raw -o fetch -- python3 bench.py --steps 1 --warmup 0 --cpu-sample 0
-  rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d gpurun_out/prof_r02/w_raw -o write -- python3 bench.py --steps 1 --warmup 0 --cpu-sample 0
+On an MI355X, from the repository root:
+  python bench.py --full > <dir>/bench_final.log
+  rocprofv3 --kernel-trace --stats --output-format csv -d <dir>/ks_raw -o ks -- python3 bench.py --steps 3 --warmup 1
+  rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d <dir>/f_raw -o fetch -- python3 bench.py --steps 1 --warmup 0
+  rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d <dir>/w_raw -o write -- python3 bench.py --steps 1 --warmup 0
 then copy <raw>/*/ks_kernel_stats.csv, fetch_counter_collection.csv, write_counter_collection.csv next to bench_final.log."""
 import csv, json, os, shutil, sys
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
