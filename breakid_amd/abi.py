@@ -36,6 +36,11 @@ class Soa(C.Structure):
                 ("n_aux_bytes", C.c_uint64), ("qcheck", C.c_void_p), ("side", C.c_void_p)]
 
 
+class Regions(C.Structure):
+    """bk_regions: the exclude list of bk_exclude_regions (host arrays, [beg, end) 0-based)"""
+    _fields_ = [("tid", C.c_void_p), ("beg", C.c_void_p), ("end", C.c_void_p), ("n", C.c_uint64)]
+
+
 SOA_COLS = [("tid", np.int32), ("pos", np.int32), ("mtid", np.int32), ("mpos", np.int32), ("isize", np.int32),
             ("flag", np.uint16), ("mapq", np.uint8), ("qhash", np.uint64), ("cigar_off", np.uint32),
             ("cigar", np.uint32), ("aux_off", np.uint32), ("aux", np.uint8)]

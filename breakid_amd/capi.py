@@ -33,7 +33,7 @@ def build(verbose=False):
         raise RuntimeError("building libbreakid_hip.so failed:\n" + (r.stdout or "")[-4000:] + (r.stderr or "")[-4000:])
 
 
-EXPORTS = ["bk_init", "bk_prepare_process", "bk_free", "bk_last_error", "bk_set_stream", "bk_sync", "bk_get_stream", "bk_upload_records", "bk_isize_stats",
+EXPORTS = ["bk_init", "bk_prepare_process", "bk_free", "bk_last_error", "bk_set_stream", "bk_sync", "bk_get_stream", "bk_upload_records", "bk_exclude_regions", "bk_isize_stats",
            "bk_discordant_pairs", "bk_mask_and_cluster", "bk_split_evidence", "bk_cluster_summary",
            "bk_split_breakpoints", "bk_normal_support", "bk_run", "bk_fetch", "bk_timing", "bk_timing_enable", "bk_timing_touched", "bk_group_stats", "bk_qname_hash", "bk_qname_check",
            "bk_bam_open", "bk_bam_header", "bk_bam_decode", "bk_bam_close", "bk_bam_decode_device", "bk_bam_decode_device_part", "bk_bam_decode_device_ctx", "bk_bam_dev_free", "bk_feed_release_caches", "bk_debug_bgzf_inflate", "bk_debug_std_sort", "bk_sort_forms", "bk_debug_ahc", "bk_debug_points", "bk_debug_cigar", "bk_debug_vote", "bk_debug_region", "bk_shard_begin", "bk_shard_get_stats", "bk_shard_set_stats",
@@ -62,6 +62,7 @@ def lib():
         L.bk_set_stream.argtypes = [vp, vp]
         L.bk_sync.argtypes = [vp]
         L.bk_upload_records.argtypes = [vp, C.POINTER(abi.Soa), C.c_int]
+        L.bk_exclude_regions.argtypes = [vp, C.POINTER(abi.Regions), u64p]
         L.bk_isize_stats.argtypes = [vp, dp, dp]
         L.bk_discordant_pairs.argtypes = [vp, C.c_int, C.c_double, u64p, C.POINTER(C.c_uint32)]
         L.bk_mask_and_cluster.argtypes = [vp, C.c_double, C.c_int, u64p]
@@ -202,6 +203,17 @@ class Context:
         s.n_aux_bytes = n_aux_bytes
         self._keep = (ptrs, s)
         self._check(self.L.bk_upload_records(self.h, C.byref(s), abi.BK_MEM_DEVICE))
+
+    def exclude_regions(self, tid, beg, end):
+        """Take the records that overlap any interval [beg[k], end[k]) on contig tid[k] out of the uploaded table (bk_exclude_regions:
+        after upload / attach, before isize_stats).  Returns the number of records removed."""
+        tid, beg, end = (np.ascontiguousarray(a, np.int32).reshape(-1) for a in (tid, beg, end))
+        if not len(tid) == len(beg) == len(end):
+            raise ValueError("exclude_regions: tid, beg and end differ in length")
+        r = abi.Regions(tid.ctypes.data, beg.ctypes.data, end.ctypes.data, len(tid))
+        n = C.c_uint64()
+        self._check(self.L.bk_exclude_regions(self.h, C.byref(r), C.byref(n)))
+        return n.value
 
     def isize_stats(self):
         m, s = C.c_double(), C.c_double()

@@ -16,6 +16,7 @@
 #include "cluster.h"
 #include "bp.h"
 #include "normal.h"
+#include "exclude.h"
 #include "ahc.h"
 #include "bgzf_gpu.h"
 
@@ -71,7 +72,9 @@ struct bk_ctx
   bk_soa rec{};
   DevBuf col[13];
   DevBuf d_side;  // bk_side rows of an uploaded host table
+  DevBuf xcol[13];  // bk_exclude_regions: the kept records are written here, then the two sets swap
   bool have_records = false;
+  bool streamed = false;  // a stream pass has started on this table (bk_exclude_regions is refused from then on)
 
   // stream pass
   DevBuf d_counters, d_sd, d_cand, d_split_raw, d_split, d_sa_list;
@@ -306,6 +309,7 @@ StreamArgs stream_args(bk_ctx *c, uint64_t n)
 }
 void stream_prepare(bk_ctx *c, uint64_t n_expected)
 {
+  c->streamed = true;
   c->cand_cap = std::max<uint64_t>(c->cand_cap, std::max<uint64_t>(1u << 16, n_expected / 8 + 1024));
   c->split_cap = std::max<uint64_t>(c->split_cap, std::max<uint64_t>(1u << 14, n_expected / 32 + 1024));
   c->sa_cap = std::max<uint64_t>(c->sa_cap, std::max<uint64_t>(1u << 14, n_expected / 16 + 1024));
@@ -512,6 +516,7 @@ int bk_upload_records(bk_ctx *ctx, const bk_soa *s, int mem_space)
     ctx->ext_clusters = nullptr;
     ctx->own_groups.clear();
     ctx->rec_base = 0;
+    ctx->streamed = false;
     if (mem_space == BK_MEM_DEVICE)
     {
       // the columns are used in place: they must live on this context's GPU (a table decoded on another device would be
@@ -553,6 +558,82 @@ int bk_upload_records(bk_ctx *ctx, const bk_soa *s, int mem_space)
       ctx->rec = d;
     }
     ctx->have_records = true;
+  });
+}
+
+int bk_exclude_regions(bk_ctx *ctx, const bk_regions *r, uint64_t *n_removed)
+{
+  return guarded(ctx, [&] {
+    if (!ctx->have_records || ctx->streamed || ctx->shard)
+      throw bk_error(BK_ERR_ARG, "bk_exclude_regions: call it after bk_upload_records and before the stream pass (bk_isize_stats, bk_shard_begin, "
+                                 "or a context of bk_bam_decode_device_ctx)");
+    if (!r || (r->n && (!r->tid || !r->beg || !r->end))) throw bk_error(BK_ERR_ARG, "bk_exclude_regions: null interval list");
+    const bk_soa &s = ctx->rec;
+    if (s.n && (!s.tid || !s.pos || !s.mtid || !s.mpos || !s.isize || !s.flag || !s.mapq || !s.qhash || !s.cigar_off || !s.aux_off))
+      throw bk_error(BK_ERR_ARG, "bk_exclude_regions: the table lacks a column");
+    // merged per contig on the host: sorted by start, overlapping and touching intervals joined (their ends are sorted then too)
+    std::vector<std::vector<std::pair<int32_t, int32_t>>> by(ctx->nt);
+    for (uint64_t k = 0; k < r->n; ++k)
+    {
+      const int32_t t = r->tid[k], b = r->beg[k], e = r->end[k];
+      if (t < 0 || t >= ctx->nt || b < 0 || e <= b)
+        throw bk_error(BK_ERR_ARG, "bk_exclude_regions: interval " + std::to_string(k) + " (tid " + std::to_string(t) + ", [" + std::to_string(b) + ", " +
+                                       std::to_string(e) + ")): needs 0 <= tid < n_targets, 0 <= beg < end");
+      by[t].emplace_back(b, e);
+    }
+    std::vector<uint32_t> off(ctx->nt + 1, 0);
+    std::vector<int32_t> beg, end;
+    for (int t = 0; t < ctx->nt; ++t)
+    {
+      auto &v = by[t];
+      std::sort(v.begin(), v.end());
+      for (auto &iv : v)
+        if (beg.size() > off[t] && iv.first <= end.back())
+          end.back() = std::max(end.back(), iv.second);
+        else
+        {
+          beg.push_back(iv.first);
+          end.push_back(iv.second);
+        }
+      off[t + 1] = (uint32_t) beg.size();
+    }
+    const bool owned = s.tid && s.tid == ctx->col[0].get<int32_t>();  // (a host upload, or a table this call made before)
+    if (beg.empty() && owned)
+    {
+      // nothing to take out, and the context already owns its columns
+      if (n_removed) *n_removed = 0;
+      return;
+    }
+    DevBuf d_off, d_beg, d_end;
+    ExclRegions rg;
+    rg.n_targets = ctx->nt;
+    rg.off = d_off.as<uint32_t>(off.size());
+    rg.beg = d_beg.as<int32_t>(beg.size() + 1);
+    rg.end = d_end.as<int32_t>(end.size() + 1);
+    HIP_CHECK(hipMemcpyAsync((void *) rg.off, off.data(), off.size() * 4, hipMemcpyHostToDevice, ctx->st));
+    if (!beg.empty())
+    {
+      HIP_CHECK(hipMemcpyAsync((void *) rg.beg, beg.data(), beg.size() * 4, hipMemcpyHostToDevice, ctx->st));
+      HIP_CHECK(hipMemcpyAsync((void *) rg.end, end.data(), end.size() * 4, hipMemcpyHostToDevice, ctx->st));
+    }
+    bk_soa out;
+    const uint64_t n_before = s.n;
+    exclude_compact(s, rg, ctx->xcol, out, ctx->st, [&](const char *name, uint64_t bytes, bool begin) { ctx->tick(name ? name : "", bytes, begin, bytes); });
+    // the kept table becomes the context's own: the caller's device table is never read again, the columns of a host upload are released
+    for (int k = 0; k < 13; ++k)
+    {
+      std::swap(ctx->col[k], ctx->xcol[k]);
+      ctx->xcol[k].release();
+    }
+    {
+      Scope sc(ctx, "make_side", (out.qcheck ? 56ull : 52ull) * out.n, (out.qcheck ? 56ull : 52ull) * out.n);  // qhash, mtid, mpos (qcheck) in, 32-byte rows out
+      bk_side *side = ctx->d_side.as<bk_side>(out.n + 1);
+      launch_make_side(out.qhash, out.mtid, out.mpos, out.qcheck, out.n, side, ctx->st);
+      out.side = side;
+    }
+    HIP_CHECK(hipStreamSynchronize(ctx->st));
+    ctx->rec = out;
+    if (n_removed) *n_removed = n_before - out.n;
   });
 }
 
@@ -1519,6 +1600,7 @@ int bk_shard_begin(bk_ctx *ctx, uint64_t rec_base, int mapq_min)
   return guarded(ctx, [&] {
     ctx->rec_base = rec_base;
     ctx->shard = true;
+    ctx->streamed = true;
     ctx->mapq_min = mapq_min;
     ctx->ext_cand = nullptr;
     ctx->ext_split = nullptr;

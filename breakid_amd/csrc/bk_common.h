@@ -122,6 +122,24 @@ struct DevBuf
 
 static inline unsigned cdiv(uint64_t a, uint64_t b) { return (unsigned) ((a + b - 1) / b); }
 
+// bam_endpos (sam.c:344-350) with BAM_CIGAR_TYPE 0x3C1A7: reference length of BAM CIGAR words (M, D, N, =, X)
+__device__ __forceinline__ int32_t cigar_reflen_hts(const uint32_t *__restrict__ w, uint32_t n)
+{
+  int l = 0;
+  for (uint32_t k = 0; k < n; ++k)
+  {
+    uint32_t v = w[k], op = v & 15u;
+    if ((0x3C1A7u >> (op << 1)) & 2u) l += (int) (v >> 4);
+  }
+  return l;
+}
+// bam_endpos of a record whose CIGAR words are cigar[c0, c1): pos + their reference length, pos + 1 without CIGAR or with flag 0x4
+// (the region predicate of the breakpoint stage and of bk_exclude_regions)
+__device__ __forceinline__ int32_t bam_endpos_hts(uint16_t flag, int32_t pos, const uint32_t *__restrict__ cigar, uint32_t c0, uint32_t c1)
+{
+  return !(flag & 4) && c1 > c0 ? pos + cigar_reflen_hts(cigar + c0, c1 - c0) : pos + 1;
+}
+
 // ---- candidate of the discordant filter (BreakID.cc:1419-1420), 32 bytes ------------------------
 struct Cand
 {

@@ -160,19 +160,7 @@ __global__ __launch_bounds__(256) void k_compact_clusters(const uint32_t *__rest
 // ---- region machinery ----------------------------------------------------------------------------------------
 __device__ __forceinline__ int32_t rec_endpos(const RecView &r, uint64_t i)
 {
-  uint32_t c0 = r.cigar_off[i], c1 = r.cigar_off[i + 1];
-  int32_t pos = r.pos[i];
-  if (!(r.flag[i] & 4) && c1 > c0)
-  {
-    int l = 0;
-    for (uint32_t k = c0; k < c1; ++k)
-    {
-      uint32_t v = r.cigar[k], op = v & 15u;
-      if ((0x3C1A7u >> (op << 1)) & 2u) l += (int) (v >> 4);
-    }
-    return pos + l;
-  }
-  return pos + 1;
+  return bam_endpos_hts(r.flag[i], r.pos[i], r.cigar, r.cigar_off[i], r.cigar_off[i + 1]);
 }
 // first record index with (tid,pos) >= (T,P) in coordinate order (unmapped tid=-1 sorts last).  A search over the whole table
 // is ~30 dependent HBM round trips per region; with the sampled keys of every REC_SAMPLE-th record (5 MB for 620 M records:

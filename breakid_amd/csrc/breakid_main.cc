@@ -7,6 +7,7 @@
 #include <getopt.h>
 
 #include <algorithm>
+#include <cerrno>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -14,6 +15,7 @@
 #include <ctime>
 #include <fstream>
 #include <iostream>
+#include <map>
 #include <set>
 #include <sstream>
 #include <string>
@@ -27,6 +29,14 @@
 // -normal: looked up at run time, so that this file also links against a library without the call (the CPU build of the host
 // code, oracle/Makefile); -normal then ends with an error
 extern "C" int bk_normal_support(bk_ctx *tumor, bk_ctx *normal, double w, const struct bk_normal_support **out, uint64_t *count) __attribute__((weak));
+// -x: the same for the exclude list (the CPU build refuses -x)
+extern "C" int bk_exclude_regions(bk_ctx *ctx, const bk_regions *r, uint64_t *n_removed) __attribute__((weak));
+extern "C" int bk_multi_run_ex(const bk_soa *host_table, const uint32_t *target_len, const char *const *target_name, int n_targets, const bk_regions *exclude, int n_gpus,
+                               int transport, int mapq_min, int fast, double *w_out, uint64_t *n_clustered_total, bk_ctx **ctx0_out, char *err, size_t errlen)
+    __attribute__((weak));
+extern "C" int bk_multi_run_bam_ex(const char *path, const bk_regions *exclude, int n_gpus, int transport, int mapq_min, int fast, double *w_out, uint64_t *n_clustered_total,
+                                   bk_ctx **ctx0_out, int *n_targets, const char *const **names, const uint32_t **lens, char *err, size_t errlen) __attribute__((weak));
+extern "C" int bk_multi_excluded(bk_ctx *ctx, uint64_t *n_removed) __attribute__((weak));
 
 // bam_index_load (htslib-1.3.1 sam.h:302 -> hts.c:2042 hts_idx_load, :1580 hts_idx_load_local, :1528 hts_idx_load_core): the index is
 // <bam>.csi, <bam with its extension replaced>.csi, <bam>.bai, <...>.bai - the first that can be opened - and it must parse to the
@@ -127,6 +137,114 @@ static bool index_loads(const std::string &bam)
   return ok;
 }
 
+// the reference list of a BAM file (magic, header text, n_ref, name / length pairs); gzread reads the BGZF members in turn, so only
+// the first blocks of the file are inflated
+static bool bam_header_list(const std::string &path, std::vector<std::string> &names, std::vector<uint32_t> &lens)
+{
+  gzFile fp = gzopen(path.c_str(), "rb");
+  if (!fp) return false;
+  auto rd = [&](void *dst, size_t n) { return n == 0 || gzread(fp, dst, (unsigned) n) == (int) n; };
+  bool ok = false;
+  do
+  {
+    char magic[4];
+    int32_t l_text = 0, n_ref = 0;
+    if (!rd(magic, 4) || memcmp(magic, "BAM\1", 4) || !rd(&l_text, 4) || l_text < 0) break;
+    std::vector<char> text((size_t) l_text);
+    if (!rd(text.data(), text.size()) || !rd(&n_ref, 4) || n_ref < 0) break;
+    bool good = true;
+    for (int32_t i = 0; i < n_ref && good; ++i)
+    {
+      int32_t l_name = 0;
+      uint32_t l_ref = 0;
+      good = rd(&l_name, 4) && l_name > 0;
+      std::vector<char> nm(good ? (size_t) l_name : 0);
+      good = good && rd(nm.data(), nm.size()) && rd(&l_ref, 4);
+      if (good)
+      {
+        names.emplace_back(nm.data(), strnlen(nm.data(), nm.size()));
+        lens.push_back(l_ref);
+      }
+    }
+    ok = good;
+  } while (false);
+  gzclose(fp);
+  return ok;
+}
+
+// -x regions.bed: whitespace-separated fields, 0-based half-open coordinates.  Blank lines and lines that start with '#', "track" or
+// "browser" are skipped; one field excludes the whole contig, three or more give an interval, clamped to the contig's length.  Names
+// match the header's exactly.  Lines on contigs the header does not have are counted; two fields, a field that is not a number, a
+// negative coordinate or end <= beg end the run.
+struct ExcludeList
+{
+  std::vector<int32_t> tid, beg, end;
+  uint64_t unknown = 0, lines = 0;
+};
+static ExcludeList read_exclude_bed(const std::string &path, const std::vector<std::string> &names, const std::vector<uint32_t> &lens)
+{
+  std::ifstream in(path.c_str());
+  if (!in.is_open())
+  {
+    std::cerr << "Error: can not open exclude file: " << path << std::endl;
+    exit(1);
+  }
+  std::map<std::string, int> id;
+  for (size_t i = 0; i < names.size(); ++i) id.emplace(names[i], (int) i);
+  ExcludeList x;
+  std::string line;
+  uint64_t no = 0;
+  auto fail = [&](const std::string &why) {
+    std::cerr << "Error: exclude file " << path << ", line " << no << ": " << why << std::endl;
+    exit(1);
+  };
+  auto number = [&](const std::string &f) {
+    char *e = nullptr;
+    errno = 0;
+    const long long v = strtoll(f.c_str(), &e, 10);
+    if (f.empty() || *e || errno) fail("not a number: " + f);
+    if (v < 0) fail("negative coordinate: " + f);
+    return v;
+  };
+  while (std::getline(in, line))
+  {
+    ++no;
+    std::istringstream ss(line);
+    std::vector<std::string> f;
+    for (std::string w; ss >> w;) f.push_back(w);
+    if (f.empty() || f[0][0] == '#' || f[0] == "track" || f[0] == "browser") continue;
+    if (f.size() == 2) fail("two fields (a line needs a contig name alone, or contig, start and end)");
+    long long b = 0, e = 0;
+    if (f.size() >= 3)
+    {
+      b = number(f[1]);
+      e = number(f[2]);
+      if (e <= b) fail("end <= start");
+    }
+    ++x.lines;
+    auto it = id.find(f[0]);
+    if (it == id.end())
+    {
+      ++x.unknown;
+      continue;
+    }
+    const long long len = lens[it->second];
+    if (f.size() == 1) e = len;
+    b = std::min(b, len);
+    e = std::min(e, len);
+    if (e <= b) continue;  // (behind the contig's end)
+    x.tid.push_back(it->second);
+    x.beg.push_back((int32_t) b);
+    x.end.push_back((int32_t) e);
+  }
+  if (x.unknown && x.unknown == x.lines)
+    std::cerr << "Warning: no line of the exclude file " << path << " names a contig of the BAM header (" << x.unknown
+              << " lines; names must match exactly): nothing is excluded" << std::endl;
+  else if (x.unknown)
+    std::cerr << "Warning: " << x.unknown << " lines of the exclude file " << path << " name contigs that are not in the BAM header" << std::endl;
+  return x;
+}
+
 #ifndef BREAKID_INSTALLDIR
 #define BREAKID_INSTALLDIR "."
 #endif
@@ -144,7 +262,8 @@ static const char *HELP =
      \t -q         \t encompassing reads quality thresholds  [20]\n\
      \t -t         \t distance relative to (sqrt(2)*(insert size mean +3* insert size sd))  [2]\n \
      \t -fast      \t use the fast cluster strategy [default no] \n \
-     \t -all       \t no filter enspan out [default is filter]  \n ";
+     \t -all       \t no filter enspan out [default is filter]  \n \
+     \t -x         \t exclude list (BED: contig [start end]); records that overlap it are ignored  \n ";
 
 // ---- RefSeqTranscript.{h,cc} -------------------------------------------------------------------------------
 struct Txpt
@@ -395,6 +514,19 @@ struct Sample
   bk_soa soa{};
   int soa_where = BK_MEM_HOST;
   bk_ctx *ctx = nullptr;
+  // a copy of the reference list, so that the decoded table can be released once the context holds its kept records (-x)
+  vector<string> name_copy;
+  vector<const char *> name_ptrs;
+  vector<uint32_t> len_copy;
+  void own_header()
+  {
+    name_copy.assign(names, names + nt);
+    len_copy.assign(lens, lens + nt);
+    name_ptrs.clear();
+    for (auto &n : name_copy) name_ptrs.push_back(n.c_str());
+    names = name_ptrs.data();
+    lens = len_copy.data();
+  }
 };
 
 int main(int argc, char *argv[])
@@ -402,8 +534,8 @@ int main(int argc, char *argv[])
   clock_t start = clock();
   static struct option longopts[] = {{"help", 0, 0, 'h'}, {"i", 1, 0, 1}, {"o", 1, 0, 2}, {"q", 1, 0, 3}, {"n", 1, 0, 4},
                                      {"fast", 0, 0, 5},   {"t", 0, 0, 6}, {"all", 0, 0, 7}, {"gpu", 1, 0, 8}, {"gpus", 1, 0, 9},
-                                     {"comm", 1, 0, 10},  {"normal", 1, 0, 11}, {0, 0, 0, 0}};
-  string inp_file, out_file, nib_dir, normal_file, build = "hg19";
+                                     {"comm", 1, 0, 10},  {"normal", 1, 0, 11}, {"x", 1, 0, 12}, {0, 0, 0, 0}};
+  string inp_file, out_file, nib_dir, normal_file, exclude_file, build = "hg19";
   int qual = 20, device = 0, n_gpus = 0, transport = BK_TRANSPORT_AUTO;  // -gpus N: one sample over N GPUs (include/breakid_multi.h)
   bool fast = false, filter = true;
   int opt, li;
@@ -424,6 +556,7 @@ int main(int argc, char *argv[])
     case 9: n_gpus = atoi(optarg); break;
     case 10: transport = !strcmp(optarg, "rccl") ? BK_TRANSPORT_RCCL : !strcmp(optarg, "local") ? BK_TRANSPORT_LOCAL : BK_TRANSPORT_AUTO; break;
     case 11: normal_file = optarg; break;
+    case 12: exclude_file = optarg; break;
     default: std::cerr << "Error: cannot parse arguments.\n"; exit(1);
     }
   }
@@ -457,6 +590,21 @@ int main(int argc, char *argv[])
     }
     fclose(probe);
   }
+  const bool exclude = !exclude_file.empty();
+  if (exclude)
+  {
+    if (!bk_exclude_regions || !bk_multi_run_ex || !bk_multi_run_bam_ex || !bk_multi_excluded)
+    {
+      std::cerr << "Error: -x needs the GPU library" << std::endl;
+      exit(1);
+    }
+    std::ifstream probe(exclude_file.c_str());
+    if (!probe.is_open())
+    {
+      std::cerr << "Error: can not open exclude file: " << exclude_file << std::endl;
+      exit(1);
+    }
+  }
   std::cout << "start to stats the insert size...\n";
   // feed: the GPU decoder first (BGZF inflate + record decode on the device; every htslib-written BAM qualifies), the
   // host decoder (all cores, pinned columns) for files whose records straddle BGZF blocks or that exceed one batch.
@@ -479,6 +627,25 @@ int main(int argc, char *argv[])
     }
     fclose(probe);
   }
+  // -x: the list is read against the file's reference list before anything is decoded
+  ExcludeList xl;
+  bk_regions regions{};
+  if (exclude)
+  {
+    vector<string> hn;
+    vector<uint32_t> hl;
+    if (!bam_header_list(inp_file, hn, hl))
+    {
+      std::cerr << "Error: can not read the header of bam-file: " << inp_file << std::endl;
+      exit(1);
+    }
+    xl = read_exclude_bed(exclude_file, hn, hl);
+    regions.tid = xl.tid.data();
+    regions.beg = xl.beg.data();
+    regions.end = xl.end.data();
+    regions.n = xl.tid.size();
+  }
+  uint64_t n_excluded = 0, n_excluded_normal = 0;
   const bool multi = n_gpus >= 1;  // the sharded run: every rank decodes its part of the file on its own GPU (below), or takes its range of the host table
   bk_ctx *&ctx = tumor.ctx;
   auto host_decode_sample = [&](Sample &s) {
@@ -500,11 +667,44 @@ int main(int argc, char *argv[])
   // already decoded while the rest of the file is still arriving (the reference reads the BAM twice, BreakID.cc:1929, :1414);
   // false when the GPU feed refuses the file (or BREAKID_HOST_DECODE=1): the host decoder takes it then
   auto gpu_decode = [&](Sample &s) {
-    if (getenv("BREAKID_HOST_DECODE") ||
-        bk_bam_decode_device_ctx(s.path.c_str(), device, qual, &s.dbam, &s.ctx, &s.nt, &s.names, &s.lens, err, sizeof err) != BK_OK)
+    if (exclude)
+    {
+      // -x: the table first (bk_init, bk_upload_records and bk_exclude_regions follow), the stream pass after the exclusion
+      if (getenv("BREAKID_HOST_DECODE") || bk_bam_decode_device(s.path.c_str(), device, &s.dbam, &s.soa, &s.nt, &s.names, &s.lens, err, sizeof err) != BK_OK)
+      {
+        s.dbam = nullptr;
+        return false;
+      }
+    }
+    else if (getenv("BREAKID_HOST_DECODE") ||
+             bk_bam_decode_device_ctx(s.path.c_str(), device, qual, &s.dbam, &s.ctx, &s.nt, &s.names, &s.lens, err, sizeof err) != BK_OK)
       return false;
     s.soa_where = BK_MEM_DEVICE;
     return true;
+  };
+  // -x: context, upload, exclusion; then the decoded table goes (the context holds the kept records), the reference list stays as a copy
+  auto exclude_sample = [&](Sample &s) {
+    uint64_t removed = 0;
+    s.own_header();
+    if (!s.ctx)
+    {
+      if (bk_init(device, s.lens, s.names, s.nt, &s.ctx) != BK_OK)
+      {
+        std::cerr << "Error: " << bk_last_error(nullptr) << std::endl;
+        exit(1);
+      }
+      if (bk_upload_records(s.ctx, &s.soa, s.soa_where) != BK_OK || bk_exclude_regions(s.ctx, &regions, &removed) != BK_OK)
+      {
+        std::cerr << "Error: " << s.path << ": " << bk_last_error(s.ctx) << std::endl;
+        exit(1);
+      }
+    }
+    if (s.dbam) bk_bam_dev_free(s.dbam);
+    if (s.bam) bk_bam_close(s.bam);
+    s.dbam = nullptr;
+    s.bam = nullptr;
+    s.soa = bk_soa{};
+    return removed;
   };
   const bool multi_from_file = multi && !getenv("BREAKID_HOST_DECODE");
   if (!multi && gpu_decode(tumor))
@@ -514,6 +714,7 @@ int main(int argc, char *argv[])
   }
   else if (!multi_from_file)
     host_decode();
+  if (exclude && !multi) n_excluded = exclude_sample(tumor);
   {
     std::ifstream rn((nib_dir + "/ref_names.txt").c_str());
     if (!rn.is_open())
@@ -544,16 +745,25 @@ int main(int argc, char *argv[])
     // the GPU feed per rank first (bk_bam_decode_device_part); files it cannot cut into parts (records across BGZF blocks) and
     // anything else it refuses go through the host decoder and the record ranges of its table
     rc = BK_ERR_IO;
-    if (multi_from_file) rc = bk_multi_run_bam(inp_file.c_str(), n_gpus, transport, qual, fast ? 1 : 0, &w, &n_clustered, &ctx, &nt, &names, &lens, err, sizeof err);
+    // (-x: the _ex entry points, every rank excludes on its own table before the record bases are counted)
+    if (multi_from_file)
+      rc = exclude ? bk_multi_run_bam_ex(inp_file.c_str(), &regions, n_gpus, transport, qual, fast ? 1 : 0, &w, &n_clustered, &ctx, &nt, &names, &lens, err, sizeof err)
+                   : bk_multi_run_bam(inp_file.c_str(), n_gpus, transport, qual, fast ? 1 : 0, &w, &n_clustered, &ctx, &nt, &names, &lens, err, sizeof err);
     if (rc != BK_OK && (!multi_from_file || rc == BK_ERR_IO || rc == BK_ERR_LIMIT))
     {
       host_decode();
-      rc = bk_multi_run(&soa, lens, names, nt, n_gpus, transport, qual, fast ? 1 : 0, &w, &n_clustered, &ctx, err, sizeof err);
+      rc = exclude ? bk_multi_run_ex(&soa, lens, names, nt, &regions, n_gpus, transport, qual, fast ? 1 : 0, &w, &n_clustered, &ctx, err, sizeof err)
+                   : bk_multi_run(&soa, lens, names, nt, n_gpus, transport, qual, fast ? 1 : 0, &w, &n_clustered, &ctx, err, sizeof err);
     }
     if (rc != BK_OK)
     {
       std::cerr << (rc == BK_ERR_CIGAR ? "error cigar: " : err) << std::endl;
       exit(rc == BK_ERR_CIGAR ? -1 : 1);
+    }
+    if (exclude)
+    {
+      (void) bk_multi_excluded(ctx, &n_excluded);
+      std::cout << "excluded " << n_excluded << " records overlapping " << xl.tid.size() << " intervals of " << exclude_file << "\n";
     }
     double mean = 0, sd = 0;
     (void) bk_multi_stats(ctx, &mean, &sd, nullptr, nullptr);
@@ -574,6 +784,7 @@ int main(int argc, char *argv[])
       }
       if ((rc = bk_upload_records(ctx, &soa, soa_where)) != BK_OK) die(rc);
     }
+    if (exclude) std::cout << "excluded " << n_excluded << " records overlapping " << xl.tid.size() << " intervals of " << exclude_file << "\n";
     double mean = 0, sd = 0;
     if ((rc = bk_isize_stats(ctx, &mean, &sd)) != BK_OK) die(rc);
     std::cout << "the insert size mean: " << mean << ", the insert size sd:" << sd << " .\n";
@@ -608,6 +819,11 @@ int main(int argc, char *argv[])
     {
       std::cerr << "Error: tumor and normal BAM headers differ" << std::endl;
       exit(1);
+    }
+    if (exclude)
+    {
+      n_excluded_normal = exclude_sample(normal);
+      std::cout << "excluded " << n_excluded_normal << " records of the normal overlapping " << xl.tid.size() << " intervals of " << exclude_file << "\n";
     }
     auto die_normal = [&] {
       std::cerr << "Error: normal " << normal.path << ": " << bk_last_error(normal.ctx) << std::endl;
@@ -720,6 +936,7 @@ int main(int argc, char *argv[])
     p << "qual\t" << (long) qual << std::endl;
     p << "w\t" << w << std::endl;
     p << "build\t" << build << std::endl;
+    if (exclude) p << "exclude_file\t" << exclude_file << std::endl;
     if (!normal_file.empty()) p << "normal_file\t" << normal_file << std::endl;
   }
   clock_t end = clock();

@@ -580,6 +580,7 @@ struct Owned
   Keep keep;
   bk_bam_dev *bam = nullptr;
   RankSummary sum;
+  uint64_t excluded = 0;  // records the exclude list took out, over all ranks
 };
 std::map<bk_ctx *, Owned> &owned()
 {
@@ -710,8 +711,40 @@ int multi_run_common(int n_gpus, int transport, int mapq_min, int fast, double *
 }
 }  // namespace
 
+// a rank's table without the records that overlap the exclude list (bk_exclude_regions), before the record bases are counted: the
+// ranks number the kept records; returns the rank's kept count
+namespace
+{
+uint64_t exclude_rank(bk_ctx *ctx, const bk_regions *exclude, uint64_t n, uint64_t &removed)
+{
+  removed = 0;
+  if (!exclude) return n;
+  const int rc = bk_exclude_regions(ctx, exclude, &removed);
+  if (rc != BK_OK)
+  {
+    const bk_error e(rc, bk_last_error(ctx));
+    bk_free(ctx);
+    throw e;
+  }
+  return n - removed;
+}
+void note_excluded(bk_ctx *ctx0, const std::vector<uint64_t> &removed)
+{
+  uint64_t sum = 0;
+  for (uint64_t v : removed) sum += v;
+  std::lock_guard<std::mutex> l(owned_m());
+  owned()[ctx0].excluded = sum;
+}
+}  // namespace
+
 extern "C" int bk_multi_run(const bk_soa *tab, const uint32_t *target_len, const char *const *target_name, int n_targets, int n_gpus, int transport, int mapq_min, int fast,
                             double *w_out, uint64_t *n_clustered_total, bk_ctx **ctx0_out, char *err, size_t errlen)
+{
+  return bk_multi_run_ex(tab, target_len, target_name, n_targets, nullptr, n_gpus, transport, mapq_min, fast, w_out, n_clustered_total, ctx0_out, err, errlen);
+}
+
+extern "C" int bk_multi_run_ex(const bk_soa *tab, const uint32_t *target_len, const char *const *target_name, int n_targets, const bk_regions *exclude, int n_gpus,
+                               int transport, int mapq_min, int fast, double *w_out, uint64_t *n_clustered_total, bk_ctx **ctx0_out, char *err, size_t errlen)
 {
   if (!tab)
   {
@@ -719,6 +752,7 @@ extern "C" int bk_multi_run(const bk_soa *tab, const uint32_t *target_len, const
     return BK_ERR_ARG;
   }
   const uint64_t n = tab->n;
+  std::vector<uint64_t> removed(n_gpus, 0);
   auto load = [&](int r, int W, int dev) {
     RankInput in;
     if (bk_init(dev, target_len, target_name, n_targets, &in.ctx) != BK_OK) throw bk_error(BK_ERR_NO_DEVICE, bk_last_error(nullptr));
@@ -748,15 +782,24 @@ extern "C" int bk_multi_run(const bk_soa *tab, const uint32_t *target_len, const
       bk_free(in.ctx);
       throw e;
     }
-    in.n = m;
+    in.n = exclude_rank(in.ctx, exclude, m, removed[r]);
     return in;
   };
-  return multi_run_common(n_gpus, transport, mapq_min, fast, w_out, n_clustered_total, ctx0_out, err, errlen, "bk_multi_run", load, [](int) {});
+  const int rc = multi_run_common(n_gpus, transport, mapq_min, fast, w_out, n_clustered_total, ctx0_out, err, errlen, "bk_multi_run", load, [](int) {});
+  if (rc == BK_OK) note_excluded(*ctx0_out, removed);
+  return rc;
 }
 
 // the same with every rank decoding its own part of the file on its own GPU (bk_bam_decode_device_part)
 extern "C" int bk_multi_run_bam(const char *path, int n_gpus, int transport, int mapq_min, int fast, double *w_out, uint64_t *n_clustered_total, bk_ctx **ctx0_out,
                                 int *n_targets, const char *const **names, const uint32_t **lens, char *err, size_t errlen)
+{
+  return bk_multi_run_bam_ex(path, nullptr, n_gpus, transport, mapq_min, fast, w_out, n_clustered_total, ctx0_out, n_targets, names, lens, err, errlen);
+}
+
+extern "C" int bk_multi_run_bam_ex(const char *path, const bk_regions *exclude, int n_gpus, int transport, int mapq_min, int fast, double *w_out,
+                                   uint64_t *n_clustered_total, bk_ctx **ctx0_out, int *n_targets, const char *const **names, const uint32_t **lens, char *err,
+                                   size_t errlen)
 {
   if (!path || n_gpus < 1 || n_gpus > 64)
   {
@@ -767,6 +810,7 @@ extern "C" int bk_multi_run_bam(const char *path, int n_gpus, int transport, int
   std::vector<int> nts(n_gpus, 0);
   std::vector<const char *const *> nms(n_gpus, nullptr);
   std::vector<const uint32_t *> lns(n_gpus, nullptr);
+  std::vector<uint64_t> removed(n_gpus, 0);
   auto load = [&](int r, int W, int dev) {
     RankInput in;
     bk_soa cols;
@@ -782,7 +826,13 @@ extern "C" int bk_multi_run_bam(const char *path, int n_gpus, int transport, int
       bk_free(in.ctx);
       throw ex;
     }
-    in.n = cols.n;
+    in.n = exclude_rank(in.ctx, exclude, cols.n, removed[r]);
+    // the context holds the kept records now: the decoded part goes (rank 0's stays, it owns the reference list handed out)
+    if (exclude && r != 0)
+    {
+      bk_bam_dev_free(bams[r]);
+      bams[r] = nullptr;
+    }
     return in;
   };
   // the records of a rank live in its bk_bam_dev: released behind its context (multi_run_common does that for rank 0 only when
@@ -795,6 +845,7 @@ extern "C" int bk_multi_run_bam(const char *path, int n_gpus, int transport, int
   const bool ok = rc == BK_OK;
   if (ok)
   {
+    note_excluded(*ctx0_out, removed);
     {
       std::lock_guard<std::mutex> l(owned_m());
       owned()[*ctx0_out].bam = bams[0];
@@ -825,6 +876,16 @@ extern "C" void bk_multi_free(bk_ctx *ctx)
   }
   bk_free(ctx);  // first the context, then what it pointed at
   if (found && o.bam) bk_bam_dev_free(o.bam);
+}
+
+// records the exclude list took out in the finished run behind `ctx` (bk_multi_run_ex / bk_multi_run_bam_ex; 0 without a list)
+extern "C" int bk_multi_excluded(bk_ctx *ctx, uint64_t *n_removed)
+{
+  std::lock_guard<std::mutex> l(owned_m());
+  auto it = owned().find(ctx);
+  if (it == owned().end() || !n_removed) return BK_ERR_ARG;
+  *n_removed = it->second.excluded;
+  return BK_OK;
 }
 
 // insert-size statistics and per-group counters of the finished run behind `ctx` (what bk_isize_stats / bk_group_stats give for one GPU)

@@ -208,18 +208,6 @@ __device__ int32_t intern_name(const NameTableDev &nt, const uint8_t *__restrict
   return (int32_t) (0x40000000u | (uint32_t) (fnv_bytes(s, len) & 0x3FFFFFFFu));
 }
 
-// bam_endpos (sam.c:344-350) with BAM_CIGAR_TYPE 0x3C1A7
-__device__ __forceinline__ int32_t cigar_reflen_hts(const uint32_t *__restrict__ w, uint32_t n)
-{
-  int l = 0;
-  for (uint32_t k = 0; k < n; ++k)
-  {
-    uint32_t v = w[k], op = v & 15u;
-    if ((0x3C1A7u >> (op << 1)) & 2u) l += (int) (v >> 4);
-  }
-  return l;
-}
-
 // CigarRoller::is_complementary_cigar (CigarRoller.cc:323-346): c1 = this read's rolled cigar, c2 = the SA entry's raw text
 // (rolled into `sac`); both must match ([0-9]+[MS]){2} - c1 as its rolled string, c2 as written
 __device__ __forceinline__ bool is_complementary(const Roll &c1, const Roll &sac, const uint8_t *__restrict__ c2, uint32_t c2len, int e)

@@ -157,6 +157,29 @@ int bk_get_stream(bk_ctx *ctx, void **hip_stream); /* the hipStream_t the contex
 /* Replaces: the two sequential BAM passes' record access (BreakID.cc:1414, :1929). */
 int bk_upload_records(bk_ctx *ctx, const bk_soa *cols, int mem_space);
 
+/* ---- exclude list ------------------------------------------------------------------------------------------------------
+ * Every stage then behaves as if the table had no record that overlaps an excluded interval.  Overlap is htslib's region
+ * predicate, the one the breakpoint stage uses: a record is excluded when tid == T && pos < end && bam_endpos > beg for an interval
+ * [beg, end) on contig T, bam_endpos = pos + the reference length of the CIGAR (M, D, N, =, X), or pos + 1 for a record without
+ * CIGAR or with flag 0x4.  A record with tid == -1 is never excluded.  What follows from that definition, with no special case:
+ * insert-size statistics (and so w) come from the kept records only; a pair with either mate excluded does not form at the mate
+ * join (its other record has no partner); excluded records give no split-evidence tuples and add nothing to depth; the kept
+ * records are renumbered in file order as in a filtered file, and join order, sort ties and the 64-bit record indices of a sharded
+ * run follow from that numbering.  The result equals that of bk_upload_records on the table without those records.
+ * Call order: after bk_upload_records and before the stream pass; BK_ERR_ARG otherwise, with the context unchanged (after
+ * bk_isize_stats or any stage, after bk_shard_begin, and on a context of bk_bam_decode_device_ctx, which has streamed already).
+ * Intervals: host arrays; 0 <= tid < n_targets and 0 <= beg < end, BK_ERR_ARG otherwise; unsorted and overlapping intervals are
+ * merged.  n_removed (may be NULL) receives the number of records taken out.
+ * Memory: the kept records are copied, in order, into columns the context owns (the layout of a device table, bk_side rows
+ * included).  After the call the context never reads the caller's BK_MEM_DEVICE table again (the caller may free it); for a
+ * host upload the uploaded columns are released, so peak device memory is one table plus its kept part.  An empty list leaves a
+ * host upload as it is and copies a device table. */
+typedef struct bk_regions {
+  const int32_t *tid, *beg, *end; /* n entries each (host memory); [beg, end) 0-based, half-open */
+  uint64_t n;
+} bk_regions;
+int bk_exclude_regions(bk_ctx *ctx, const bk_regions *r, uint64_t *n_removed);
+
 /* ---- stages (call in this order) ------------------------------------------------------------ */
 /* get_mean_insert_size (BreakID.cc:1909-1954): bit-exact mean and sd. */
 int bk_isize_stats(bk_ctx *ctx, double *mean, double *sd);

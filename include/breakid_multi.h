@@ -43,6 +43,18 @@ int bk_multi_run(const bk_soa *host_table, const uint32_t *target_len, const cha
 int bk_multi_run_bam(const char *path, int n_gpus, int transport, int mapq_min, int fast, double *w_out, uint64_t *n_clustered_total, bk_ctx **ctx0_out, int *n_targets,
                      const char *const **names, const uint32_t **lens, char *err, size_t errlen);
 
+/* The same two calls with an exclude list (bk_exclude_regions, include/breakid_hip.h; NULL = none, which is what bk_multi_run and
+ * bk_multi_run_bam pass): every rank takes the records that overlap the list out of its own table before the ranks' record counts
+ * give their rec_base, so the kept records are numbered as in the filtered file and the run equals one on a file without them.  The
+ * list is checked by every rank (BK_ERR_ARG as there).  A rank's decoded part is released once its context holds the kept records
+ * (rank 0's stays with the context: it owns the reference list handed out). */
+int bk_multi_run_ex(const bk_soa *host_table, const uint32_t *target_len, const char *const *target_name, int n_targets, const bk_regions *exclude, int n_gpus,
+                    int transport, int mapq_min, int fast, double *w_out, uint64_t *n_clustered_total, bk_ctx **ctx0_out, char *err, size_t errlen);
+int bk_multi_run_bam_ex(const char *path, const bk_regions *exclude, int n_gpus, int transport, int mapq_min, int fast, double *w_out, uint64_t *n_clustered_total,
+                        bk_ctx **ctx0_out, int *n_targets, const char *const **names, const uint32_t **lens, char *err, size_t errlen);
+/* Records the exclude list took out, summed over the ranks, in the run that returned `ctx`; valid until bk_multi_free. */
+int bk_multi_excluded(bk_ctx *ctx, uint64_t *n_removed);
+
 /* Frees a context returned by bk_multi_run / bk_multi_run_bam AND the device tables it points at (the gathered tuple / cluster
  * tables; for bk_multi_run_bam also rank 0's decoded records and the reference names).  bk_free alone would leave those allocated. */
 void bk_multi_free(bk_ctx *ctx);

@@ -1,0 +1,472 @@
+"""Exclude list (`bk_exclude_regions`, `-x regions.bed`): every stage behaves as if the input had no record that overlaps an
+excluded interval (tid == T && pos < end && bam_endpos > beg).  A context that ran the exclusion is compared with a context given
+the table filtered in numpy, and the command line with a plain run on a BAM of the kept records."""
+import os
+import subprocess
+import tempfile
+
+import numpy as np
+import pytest
+
+from breakid_amd import abi, bamio, capi, synth
+from tests.test_gpu_normal import rec_endpos
+from tools import make_golden
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+BIN = os.path.join(ROOT, "breakid_amd", "bin", "BreakID")
+QUAL = 20
+STAGES = (abi.STAGE_SCAN, abi.STAGE_ISO, abi.STAGE_CLUSTERED, abi.STAGE_SPLITS, abi.STAGE_CLUSTERS)
+FIXED = ("tid", "pos", "mtid", "mpos", "isize", "flag", "mapq", "qhash", "qcheck")
+
+
+# ---- the definition, in numpy -----------------------------------------------------------------------------------------------
+def excluded_mask(cols, tid, beg, end):
+    ep = rec_endpos(cols)
+    t = cols["tid"]
+    p = cols["pos"].astype(np.int64)
+    ex = np.zeros(len(t), bool)
+    for T, b, e in zip(tid, beg, end):
+        ex |= (t == T) & (p < e) & (ep > b)
+    return ex
+
+
+def filtered(cols, keep):
+    """the table without the records where keep is False, CIGAR words and aux bytes repacked"""
+    out = {k: np.ascontiguousarray(cols[k][keep]) for k in FIXED if k in cols}
+    for blob, off in (("cigar", "cigar_off"), ("aux", "aux_off")):
+        o = cols[off].astype(np.int64)
+        ln = np.diff(o)
+        out[blob] = np.ascontiguousarray(cols[blob][:o[-1]][np.repeat(keep, ln)])
+        out[off] = np.concatenate([[0], np.cumsum(ln[keep])]).astype(np.uint32)
+    return out
+
+
+def seeded_list(cols, contigs, seed, whole=True):
+    """intervals through records of the cluster loci (not a proper pair) and through random records, overlapping and touching
+    copies of some of them, one whole contig; shuffled"""
+    rng = np.random.default_rng(seed)
+    t, p = cols["tid"], cols["pos"]
+    mapped = np.nonzero(t >= 0)[0]
+    disc = np.nonzero((t >= 0) & ((cols["flag"] & 2) == 0))[0]
+    picks = list(rng.choice(disc, min(10, len(disc)), replace=False)) + list(rng.choice(mapped, 10, replace=False))
+    iv = []
+    for i in picks:
+        b = max(0, int(p[i]) - int(rng.integers(0, 400)))
+        iv.append((int(t[i]), b, b + int(rng.integers(1, 900))))
+    for T, b, e in iv[:5]:
+        iv.append((T, (b + e) // 2, e + 300))
+        iv.append((T, e, e + 50))
+    if whole and len(contigs) > 1:
+        iv.append((len(contigs) - 1, 0, contigs[-1][1]))
+    rng.shuffle(iv)
+    a = np.asarray(iv, np.int64)
+    return a[:, 0], a[:, 1], a[:, 2]
+
+
+def hg19_like_list(contigs, seed, n_random=40):
+    """10 kb at each contig end, one 3 Mb block per contig (shorter contigs: a tenth of it), random intervals of 1-50 kb"""
+    rng = np.random.default_rng(seed)
+    iv = []
+    for t, (_, ln) in enumerate(contigs):
+        iv += [(t, 0, min(10_000, ln)), (t, max(0, ln - 10_000), ln)]
+        blk = min(3_000_000, ln // 10)
+        b = int(rng.integers(0, ln - blk))
+        iv.append((t, b, b + blk))
+    for _ in range(n_random):
+        t = int(rng.integers(0, len(contigs)))
+        ln = contigs[t][1]
+        w = int(rng.integers(1_000, 50_001))
+        b = int(rng.integers(0, max(1, ln - w)))
+        iv.append((t, b, min(ln, b + w)))
+    a = np.asarray(iv, np.int64)
+    return a[:, 0], a[:, 1], a[:, 2]
+
+
+# ---- contexts ---------------------------------------------------------------------------------------------------------------
+def to_device(cols, qcheck=True):
+    """torch copies of the columns on cuda:0 (same bits; unsigned columns as their signed twins) and their device pointers"""
+    import torch
+    dev = torch.device("cuda", 0)
+    signed = {np.dtype(np.uint16): np.int16, np.dtype(np.uint32): np.int32, np.dtype(np.uint64): np.int64}
+    t = {}
+    for k, dt in abi.SOA_COLS_ALL:
+        if k == "qcheck" and (not qcheck or k not in cols):
+            continue
+        a = np.ascontiguousarray(cols[k], dt)
+        if a.size == 0:
+            a = np.zeros(1, dt)
+        s = signed.get(np.dtype(dt))
+        t[k] = torch.from_numpy(a.view(s) if s is not None else a).to(dev)
+    return t, abi.device_ptrs(t)
+
+
+def make_ctx(contigs, cols, where, qcheck=True):
+    """(context, what must stay alive); where = 'host' (bk_upload_records) or 'device' (BK_MEM_DEVICE)"""
+    ctx = capi.Context(contigs)
+    c = dict(cols)
+    if not qcheck:
+        c.pop("qcheck", None)
+    if where == "host":
+        ctx.upload(c)
+        return ctx, None
+    t, ptrs = to_device(c, qcheck)
+    ctx.attach_device(ptrs, len(c["tid"]), int(c["cigar_off"][-1]), int(c["aux_off"][-1]))
+    return ctx, t
+
+
+def stages(ctx, fast):
+    w, nv = ctx.run(qual=QUAL, fast=fast)
+    mean, sd = ctx.isize_stats()
+    return [w, nv, mean, sd] + [ctx.fetch(st)[0] for st in STAGES]
+
+
+def assert_same(a, b):
+    assert np.array_equal(np.asarray(a[:4], np.float64), np.asarray(b[:4], np.float64), equal_nan=True), (a[:4], b[:4])
+    for st, x, y in zip(STAGES, a[4:], b[4:]):
+        assert x.dtype == y.dtype and np.array_equal(x, y), "stage %d differs (%d / %d rows)" % (st, len(x), len(y))
+
+
+def check_against_filtered(contigs, cols, lst, fast, where="host", qcheck=True):
+    tid, beg, end = lst
+    keep = ~excluded_mask(cols, tid, beg, end)
+    ctx, hold = make_ctx(contigs, cols, where, qcheck)
+    n_removed = ctx.exclude_regions(tid, beg, end)
+    assert n_removed == int((~keep).sum())
+    got = stages(ctx, fast)
+    ref_ctx, _ = make_ctx(contigs, filtered(cols, keep), "host", qcheck)
+    exp = stages(ref_ctx, fast)
+    assert_same(got, exp)
+    ctx.close()
+    ref_ctx.close()
+    del hold
+    return n_removed, got
+
+
+_DATA = {}
+
+
+def dataset(name):
+    if name not in _DATA:
+        _DATA[name] = next(ds for n, ds, _ in make_golden.datasets() if n == name)
+    return _DATA[name]
+
+
+# ---- 1. equal to the filtered table -----------------------------------------------------------------------------------------
+@pytest.mark.parametrize("qcheck", [True, False])
+@pytest.mark.parametrize("where", ["host", "device"])
+@pytest.mark.parametrize("fast", [True, False])
+@pytest.mark.parametrize("name", ["small", "edge", "g1", "ties"])
+def test_exclude_equals_filtered_table(name, fast, where, qcheck):
+    ds = dataset(name)
+    cols = ds.to_soa()
+    lst = seeded_list(cols, ds.contigs, seed=len(name) * 7 + fast)
+    n_removed, got = check_against_filtered(ds.contigs, cols, lst, fast, where, qcheck)
+    assert 0 < n_removed < len(cols["tid"])
+
+
+def test_exclude_wgs_table_fast():
+    """1.5 M records generated in HBM (BK_MEM_DEVICE, with bk_side rows and qcheck), an hg19-shaped list"""
+    import torch
+    from breakid_amd import synth_gpu
+    dev = torch.device("cuda", 0)
+    contigs, cols = synth_gpu.make_wgs(1_500_000, 777, dev)
+    host = synth_gpu.to_numpy_cols(cols)
+    tid, beg, end = hg19_like_list(contigs, 5)
+    keep = ~excluded_mask(host, tid, beg, end)
+    ctx = capi.Context(contigs)
+    ctx.attach_device(abi.device_ptrs(cols), cols["n"], cols["n_cigar_words"], cols["n_aux_bytes"])
+    assert ctx.exclude_regions(tid, beg, end) == int((~keep).sum())
+    got = stages(ctx, True)
+    ref = capi.Context(contigs)
+    ref.upload(filtered(host, keep))
+    assert_same(got, stages(ref, True))
+    assert 0.01 < (~keep).mean() < 0.5 and got[1] > 0
+    ctx.close()
+    ref.close()
+
+
+# ---- 2. boundaries ----------------------------------------------------------------------------------------------------------
+def boundary_dataset():
+    ds = synth.Dataset([("chr1", 10_000), ("chr2", 10_000)])
+    ds.recs = [
+        synth.Rec("a", 0x1 | 0x2 | 0x40, 0, 100, 60, "100M", 0, 5000, 5000),          # [100, 200)
+        synth.Rec("u", 0x1 | 0x4 | 0x80, 0, 500, 0, "100M", 0, 500, 0),             # flag 0x4: [500, 501)
+        synth.Rec("n", 0x1 | 0x40, 0, 800, 60, "*", 0, 800, 0),                      # no CIGAR: [800, 801)
+        synth.Rec("a", 0x1 | 0x2 | 0x10 | 0x80, 0, 5000, 60, "40S60M", 0, 100, -5000),  # [5000, 5060)
+        synth.Rec("b", 0x1 | 0x40, 1, 300, 60, "50M10D50M", 1, 300, 0),             # [300, 410)
+        synth.Rec("z", 0x1 | 0x4 | 0x8 | 0x40, -1, -1, 0, "*", -1, -1, 0),          # tid -1
+    ]
+    return ds
+
+
+@pytest.mark.parametrize("iv,removed", [
+    ((0, 200, 300), 0), ((0, 50, 100), 0), ((0, 199, 200), 1), ((0, 100, 101), 1),
+    ((0, 500, 501), 1), ((0, 501, 600), 0), ((0, 550, 560), 0),
+    ((0, 800, 801), 1), ((0, 801, 900), 0), ((0, 799, 800), 0),
+    ((0, 5059, 5060), 1), ((0, 5060, 6000), 0), ((1, 409, 410), 1), ((1, 410, 500), 0),
+])
+def test_exclude_boundaries(iv, removed):
+    ds = boundary_dataset()
+    cols = ds.to_soa()
+    assert list(rec_endpos(cols)) == [200, 501, 801, 5060, 410, 0]
+    ctx = capi.Context(ds.contigs)
+    ctx.upload(cols)
+    assert ctx.exclude_regions([iv[0]], [iv[1]], [iv[2]]) == removed
+    ctx.close()
+
+
+def test_exclude_everything_mapped_keeps_tid_minus_one():
+    ds = boundary_dataset()
+    cols = ds.to_soa()
+    lst = ([0, 1], [0, 0], [10_000, 10_000])
+    for where in ("host", "device"):
+        n_removed, _ = check_against_filtered(ds.contigs, cols, lst, True, where)
+        assert n_removed == len(ds.recs) - 1
+
+
+@pytest.mark.parametrize("name", ["g1", "small"])
+def test_exclude_all_mapped_records(name):
+    """a list that removes every mapped record still runs, equal to the filtered table"""
+    ds = dataset(name)
+    cols = ds.to_soa()
+    T = len(ds.contigs)
+    lst = (np.arange(T), np.zeros(T, np.int64), np.asarray([ln for _, ln in ds.contigs], np.int64))
+    for fast in (True, False):
+        n_removed, _ = check_against_filtered(ds.contigs, cols, lst, fast, "host")
+        assert n_removed == int((cols["tid"] >= 0).sum())
+
+
+@pytest.mark.parametrize("where", ["host", "device"])
+def test_exclude_empty_list_is_identity(where):
+    ds = dataset("g1")
+    cols = ds.to_soa()
+    for fast in (True, False):
+        ctx, hold = make_ctx(ds.contigs, cols, where)
+        assert ctx.exclude_regions([], [], []) == 0
+        got = stages(ctx, fast)
+        ref, _ = make_ctx(ds.contigs, cols, "host")
+        assert_same(got, stages(ref, fast))
+        ctx.close()
+        ref.close()
+        del hold
+
+
+# ---- 3. errors and ownership ------------------------------------------------------------------------------------------------
+def test_exclude_call_order_and_arguments():
+    ds = dataset("g1")
+    cols = ds.to_soa()
+    ref = capi.Context(ds.contigs)
+    ref.upload(cols)
+    exp = stages(ref, True)
+    ref.close()
+    nt = len(ds.contigs)
+    # arguments: refused, context unchanged
+    ctx = capi.Context(ds.contigs)
+    ctx.upload(cols)
+    for tid, beg, end in ((-1, 0, 10), (nt, 0, 10), (0, -1, 10), (0, 10, 10), (0, 10, 5)):
+        with pytest.raises(capi.BreakIDError) as e:
+            ctx.exclude_regions([0, tid], [100, beg], [200, end])
+        assert e.value.code == abi.BK_ERR_ARG
+    assert_same(stages(ctx, True), exp)
+    # after the stream pass (isize_stats): refused, the context still runs
+    with pytest.raises(capi.BreakIDError) as e:
+        ctx.exclude_regions([0], [0], [1_000_000])
+    assert e.value.code == abi.BK_ERR_ARG and "before the stream pass" in str(e.value)
+    assert_same(stages(ctx, True), exp)
+    ctx.close()
+    ctx = capi.Context(ds.contigs)
+    ctx.upload(cols)
+    ctx.isize_stats()
+    with pytest.raises(capi.BreakIDError) as e:
+        ctx.exclude_regions([0], [0], [1_000_000])
+    assert e.value.code == abi.BK_ERR_ARG
+    assert_same(stages(ctx, True), exp)
+    ctx.close()
+
+
+def test_exclude_refused_on_a_decode_ctx_context():
+    ds = dataset("g1")
+    with tempfile.TemporaryDirectory() as tmp:
+        path = os.path.join(tmp, "g1.bam")
+        ds.write_bam(path, aligned=True)
+        ctx, table = capi.decode_bam_device_ctx(path, qual=QUAL)
+        with pytest.raises(capi.BreakIDError) as e:
+            ctx.exclude_regions([0], [0], [1_000_000])
+        assert e.value.code == abi.BK_ERR_ARG
+        w, nv = ctx.run(qual=QUAL, fast=True)
+        ref = capi.Context(ds.contigs)
+        ref.upload(ds.to_soa())
+        assert (w, nv) == ref.run(qual=QUAL, fast=True)
+        assert np.array_equal(ctx.fetch(abi.STAGE_CLUSTERS)[0], ref.fetch(abi.STAGE_CLUSTERS)[0])
+        ctx.close()
+        table.close()
+        ref.close()
+
+
+def test_exclude_device_table_overwritten_after_the_call():
+    """the context owns the kept records: the caller's BK_MEM_DEVICE columns are never read again"""
+    ds = dataset("small")
+    cols = ds.to_soa()
+    lst = seeded_list(cols, ds.contigs, seed=3)
+    keep = ~excluded_mask(cols, *lst)
+    ctx, t = make_ctx(ds.contigs, cols, "device")
+    ctx.exclude_regions(*lst)
+    for k, v in t.items():
+        v.fill_(3 if k in ("cigar", "cigar_off", "aux_off") else 7)
+    got = stages(ctx, True)
+    ref, _ = make_ctx(ds.contigs, filtered(cols, keep), "host")
+    assert_same(got, stages(ref, True))
+    ctx.close()
+    ref.close()
+
+
+# ---- 4. command line --------------------------------------------------------------------------------------------------------
+def cli_data():
+    """the small golden dataset (calls on all three contigs) and its refGene"""
+    return next((ds, rg) for n, ds, rg in make_golden.datasets() if n == "small")
+
+
+def write_bed(path, ds, cols, seed, unknown=True):
+    """a BED file as users write them: header lines, unsorted and overlapping intervals with extra columns, one contig by name
+    alone; returns the (tid, beg, end) it stands for"""
+    tid, beg, end = seeded_list(cols, ds.contigs, seed, whole=False)
+    names = [n for n, _ in ds.contigs]
+    lines = ["# exclude list", "track name=excl", "browser position chr1:1-100", ""]
+    lines += ["%s\t%d\t%d\tr%d\t0\t+" % (names[t], b, e, k) if k % 2 else "%s %d  %d" % (names[t], b, e) for k, (t, b, e) in enumerate(zip(tid, beg, end))]
+    last = len(names) - 1
+    lines.insert(6, names[last])
+    if unknown:
+        lines.append("chrUn_gl000220\t100\t200")
+    open(path, "w").write("\n".join(lines) + "\n")
+    ln = ds.contigs[last][1]
+    return np.append(tid, last), np.append(beg, 0), np.append(end, ln)
+
+
+def kept_dataset(ds, keep):
+    return synth.Dataset(list(ds.contigs), [r for r, k in zip(ds.recs, keep) if k])
+
+
+def write_indexed(ds, path, aligned=True):
+    ds.write_bam(path, aligned=aligned)
+    bamio.write_bai(path)
+
+
+def run_cli(args, env):
+    r = subprocess.run([BIN] + args, env=env, capture_output=True, text=True, timeout=300)
+    return r
+
+
+def mean_line(stdout):
+    return [l for l in stdout.split("\n") if "insert size mean" in l]
+
+
+def assert_same_outputs(a, b, ra, rb):
+    for suffix in ("_fusion.txt", "_fusion_all.txt"):
+        assert open(a + suffix).read() == open(b + suffix).read(), suffix
+    fa, fb = open(a + "_performance.txt").read().split("\n"), open(b + "_performance.txt").read().split("\n")
+    assert fa[0] == fb[0] and fa[1].split("\t")[:5] == fb[1].split("\t")[:5], (fa, fb)
+    assert mean_line(ra.stdout) == mean_line(rb.stdout) and len(mean_line(ra.stdout)) == 1, (ra.stdout, rb.stdout)
+
+
+@pytest.mark.parametrize("gpus", ["", "local3", "rccl1"])
+@pytest.mark.parametrize("feed", ["gpu", "blocks", "host"])
+@pytest.mark.parametrize("mode", ["fast", "ahc"])
+def test_cli_exclude_equals_filtered_bam(mode, feed, gpus):
+    """-x r.bed on the whole BAM = a plain run on a BAM of the kept records.  feed: the GPU feed (records inside their BGZF blocks),
+    records across blocks, the host decoder (BREAKID_HOST_DECODE=1); gpus: one GPU, three contexts on one GPU (bk_multi_run_bam_ex,
+    or bk_multi_run_ex for the host decoder), RCCL with one rank"""
+    ds, refgene = cli_data()
+    cols = ds.to_soa()
+    with tempfile.TemporaryDirectory() as tmp:
+        full, kept, bed = os.path.join(tmp, "full.bam"), os.path.join(tmp, "kept.bam"), os.path.join(tmp, "r.bed")
+        keep = ~excluded_mask(cols, *write_bed(bed, ds, cols, seed=11))
+        assert 0 < keep.sum() < len(keep)
+        write_indexed(ds, full, aligned=feed != "blocks")
+        write_indexed(kept_dataset(ds, keep), kept, aligned=feed != "blocks")
+        side = synth.write_side_files(ds, tmp, refgene_lines=refgene)
+        env = dict(os.environ, BREAKID_INSTALLDIR=side["install"])
+        if feed == "host":
+            env["BREAKID_HOST_DECODE"] = "1"
+        extra = ["-all", "-n", side["nib"]] + (["-fast"] if mode == "fast" else [])
+        extra += {"": [], "local3": ["-gpus", "3", "-comm", "local"], "rccl1": ["-gpus", "1", "-comm", "rccl"]}[gpus]
+        a, b = os.path.join(tmp, "a"), os.path.join(tmp, "b")
+        ra = run_cli(["-i", kept, "-o", a] + extra, env)
+        assert ra.returncode == 0, ra.stderr[-2000:]
+        rb = run_cli(["-i", full, "-o", b, "-x", bed] + extra, env)
+        assert rb.returncode == 0, rb.stderr[-2000:]
+        assert_same_outputs(a, b, ra, rb)
+        assert "exclude_file" not in open(a + "_params.txt").read()
+        pa = open(a + "_params.txt").read().replace(kept, full).replace("out_file\t" + a, "out_file\t" + b)
+        assert open(b + "_params.txt").read() == pa + "exclude_file\t" + bed + "\n"
+        assert "excluded %d records overlapping" % int((~keep).sum()) in rb.stdout, rb.stdout
+        assert "1 lines of the exclude file" in rb.stderr and "not in the BAM header" in rb.stderr, rb.stderr[-2000:]
+        assert open(a + "_fusion_all.txt").read().count("\n") > 1  # calls are left
+
+
+@pytest.mark.parametrize("mode", ["fast", "ahc"])
+def test_cli_exclude_with_normal(mode):
+    """-normal n.bam -x r.bed: the list applies to both samples; the twin files equal those of -normal on both filtered BAMs"""
+    from tests.test_gpu_normal import tumor_normal
+    tum, nor = tumor_normal()
+    refgene = synth.random_refgene(tum.contigs, 60, 5)
+    tcols, ncols = tum.to_soa(), nor.to_soa()
+    with tempfile.TemporaryDirectory() as tmp:
+        bed = os.path.join(tmp, "r.bed")
+        # through the first germline locus in both samples, through one somatic locus, around random records
+        lst = write_bed(bed, tum, tcols, seed=5, unknown=False)
+        with open(bed, "a") as f:
+            f.write("chr1\t299500\t300400\nchr1\t1699800\t1700200\n")
+        lst = (np.append(lst[0], [0, 0]), np.append(lst[1], [299_500, 1_699_800]), np.append(lst[2], [300_400, 1_700_200]))
+        tkeep, nkeep = ~excluded_mask(tcols, *lst), ~excluded_mask(ncols, *lst)
+        assert 0 < tkeep.sum() < len(tkeep) and 0 < nkeep.sum() < len(nkeep)
+        tb, nb, tk, nk = (os.path.join(tmp, f) for f in ("t.bam", "n.bam", "tk.bam", "nk.bam"))
+        write_indexed(tum, tb)
+        write_indexed(nor, nb)
+        write_indexed(kept_dataset(tum, tkeep), tk)
+        write_indexed(kept_dataset(nor, nkeep), nk)
+        side = synth.write_side_files(tum, tmp, refgene_lines=refgene)
+        env = dict(os.environ, BREAKID_INSTALLDIR=side["install"])
+        extra = ["-all", "-n", side["nib"]] + (["-fast"] if mode == "fast" else [])
+        a, b = os.path.join(tmp, "a"), os.path.join(tmp, "b")
+        ra = run_cli(["-i", tk, "-o", a, "-normal", nk] + extra, env)
+        assert ra.returncode == 0, ra.stderr[-2000:]
+        rb = run_cli(["-i", tb, "-o", b, "-normal", nb, "-x", bed] + extra, env)
+        assert rb.returncode == 0, rb.stderr[-2000:]
+        assert_same_outputs(a, b, ra, rb)
+        for suffix in ("_fusion_normal.txt", "_fusion_all_normal.txt"):
+            assert open(a + suffix).read() == open(b + suffix).read(), suffix
+        assert open(a + "_fusion_all_normal.txt").read().count("\n") > 1
+        pa = open(a + "_params.txt").read().replace(tk, tb).replace(nk, nb).replace("out_file\t" + a, "out_file\t" + b).split("\n")
+        pb = open(b + "_params.txt").read().split("\n")
+        assert pb == pa[:-2] + ["exclude_file\t" + bed] + pa[-2:], (pa, pb)  # before normal_file, which stays the last line
+        assert "excluded %d records of the normal" % int((~nkeep).sum()) in rb.stdout, rb.stdout
+
+
+def test_cli_exclude_errors():
+    ds, refgene = cli_data()
+    with tempfile.TemporaryDirectory() as tmp:
+        bam = os.path.join(tmp, "t.bam")
+        write_indexed(ds, bam)
+        side = synth.write_side_files(ds, tmp, refgene_lines=refgene)
+        env = dict(os.environ, BREAKID_INSTALLDIR=side["install"])
+        base = ["-i", bam, "-n", side["nib"], "-fast", "-o", os.path.join(tmp, "o")]
+        missing = os.path.join(tmp, "missing.bed")
+        r = run_cli(base + ["-x", missing], env)
+        assert r.returncode == 1 and "Error: can not open exclude file: " + missing in r.stderr, r.stderr[-2000:]
+        bad = os.path.join(tmp, "bad.bed")
+        for text, why in (("# c\nchr1\t10\t20\nchr1\t30\n", "line 3"), ("chr1\t20\t20\n", "line 1"), ("chr1\t30\t20\n", "line 1"),
+                          ("\nchr2\tx\t20\n", "line 2"), ("chr2\t-5\t20\n", "line 1")):
+            open(bad, "w").write(text)
+            r = run_cli(base + ["-x", bad], env)
+            assert r.returncode == 1 and "Error: exclude file" in r.stderr and why in r.stderr, (text, r.stderr[-2000:])
+        assert not os.path.exists(os.path.join(tmp, "o_fusion.txt"))
+        open(bad, "w").write("chrUn_x\t0\t100\nchr9\n")
+        r = run_cli(base + ["-x", bad], env)
+        assert r.returncode == 0 and "Warning: no line of the exclude file" in r.stderr, r.stderr[-2000:]
+        assert "excluded 0 records overlapping 0 intervals" in r.stdout
+        # coordinates past the contig's end are clamped
+        open(bad, "w").write("chr1\t2999000\t9999999999\n")
+        r = run_cli(base + ["-x", bad], env)
+        assert r.returncode == 0 and "excluded" in r.stdout, r.stderr[-2000:]
+        assert "-x" in run_cli(["-h"], env).stderr
