@@ -35,7 +35,7 @@ def build(verbose=False):
 
 EXPORTS = ["bk_init", "bk_prepare_process", "bk_free", "bk_last_error", "bk_set_stream", "bk_sync", "bk_get_stream", "bk_upload_records", "bk_exclude_regions", "bk_isize_stats",
            "bk_discordant_pairs", "bk_mask_and_cluster", "bk_split_evidence", "bk_cluster_summary",
-           "bk_split_breakpoints", "bk_normal_support", "bk_run", "bk_fetch", "bk_timing", "bk_timing_enable", "bk_timing_touched", "bk_group_stats", "bk_qname_hash", "bk_qname_check",
+           "bk_split_breakpoints", "bk_normal_support", "bk_ref_support", "bk_genotype_call", "bk_run", "bk_fetch", "bk_timing", "bk_timing_enable", "bk_timing_touched", "bk_group_stats", "bk_qname_hash", "bk_qname_check",
            "bk_bam_open", "bk_bam_header", "bk_bam_decode", "bk_bam_close", "bk_bam_decode_device", "bk_bam_decode_device_part", "bk_bam_decode_device_ctx", "bk_bam_dev_free", "bk_feed_release_caches", "bk_debug_bgzf_inflate", "bk_debug_std_sort", "bk_sort_forms", "bk_debug_ahc", "bk_debug_points", "bk_debug_cigar", "bk_debug_vote", "bk_debug_region", "bk_shard_begin", "bk_shard_get_stats", "bk_shard_set_stats",
            "bk_shard_sd_local", "bk_shard_sd_finish", "bk_shard_buffer", "bk_shard_set_buffer", "bk_shard_group_sizes",
            "bk_shard_own_groups", "bk_shard_route_candidates", "bk_shard_group_keys", "bk_shard_route_pairs", "bk_shard_group_pairs", "bk_shard_bp_cov", "bk_shard_bp_vote", "bk_shard_bp_vote_slice", "bk_shard_bp_set_voted", "bk_shard_bp_depth", "bk_shard_bp_finish"]
@@ -71,6 +71,8 @@ def lib():
         L.bk_split_breakpoints.argtypes = [vp, C.c_double, u64p]
         L.bk_run.argtypes = [vp, C.c_int, C.c_int, dp, u64p]
         L.bk_normal_support.argtypes = [vp, vp, C.c_double, C.POINTER(vp), u64p]
+        L.bk_ref_support.argtypes = [vp, vp, C.c_int, C.c_int, C.c_double, C.POINTER(vp), u64p]
+        L.bk_genotype_call.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), C.POINTER(C.c_float)]
         L.bk_fetch.argtypes = [vp, C.c_int, C.POINTER(vp), u64p, C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(C.c_uint32)]
         L.bk_timing.argtypes = [vp, C.POINTER(C.POINTER(C.c_char_p)), C.POINTER(C.POINTER(C.c_float)),
                                 C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(C.c_int)]
@@ -128,6 +130,16 @@ def lib():
 def w_from(mean, sd):
     times = 2
     return times * math.sqrt(times) * (mean + 3 * sd)  # BreakID.cc:103
+
+
+def genotype_call(alt, ref):
+    """The library's genotype model (bk_genotype_call; no GPU): (gt, gq, vaf) with gt 0 = 0/0, 1 = 0/1, 2 = 1/1, 255 = ./.;
+    vaf is a numpy float32 (NaN without evidence)."""
+    gt, gq, vaf = C.c_uint8(), C.c_uint8(), C.c_float()
+    rc = lib().bk_genotype_call(int(alt), int(ref), C.byref(gt), C.byref(gq), C.byref(vaf))
+    if rc != 0:
+        raise BreakIDError(rc, "bk_genotype_call")
+    return gt.value, gq.value, np.float32(vaf.value)
 
 
 class Context:
@@ -255,6 +267,17 @@ class Context:
             return np.zeros(0, abi.NORMAL_SUPPORT)
         buf = (C.c_char * (n.value * abi.NORMAL_SUPPORT.itemsize)).from_address(data.value)
         return np.frombuffer(buf, dtype=abi.NORMAL_SUPPORT, count=n.value).copy()
+
+    def ref_support(self, records, mapq_min, anchor, w):
+        """Reference-allele evidence of this context's calls on the record table of `records` (bk_ref_support): one abi.REF_SUPPORT
+        row per STAGE_CLUSTERS row.  `records`: this context itself, or a Context on the same device and reference list (the
+        matched normal), after isize_stats; `w`: this context's distance."""
+        data, n = C.c_void_p(), C.c_uint64()
+        self._check(self.L.bk_ref_support(self.h, records.h, int(mapq_min), int(anchor), w, C.byref(data), C.byref(n)))
+        if not n.value:
+            return np.zeros(0, abi.REF_SUPPORT)
+        buf = (C.c_char * (n.value * abi.REF_SUPPORT.itemsize)).from_address(data.value)
+        return np.frombuffer(buf, dtype=abi.REF_SUPPORT, count=n.value).copy()
 
     def run(self, qual=20, fast=True):
         w, n = C.c_double(), C.c_uint64()

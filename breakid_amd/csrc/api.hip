@@ -1,6 +1,7 @@
 // C ABI of libbreakid_hip.so (include/breakid_hip.h): context, record upload, stage drivers, fetch.
 #include <algorithm>
 #include <cmath>
+#include <limits>
 #include <cstring>
 #include <memory>
 #include <numeric>
@@ -16,6 +17,7 @@
 #include "cluster.h"
 #include "bp.h"
 #include "normal.h"
+#include "genotype.h"
 #include "exclude.h"
 #include "ahc.h"
 #include "bgzf_gpu.h"
@@ -147,6 +149,9 @@ struct bk_ctx
   // matched normal (bk_normal_support: this context is the tumour)
   NormalBufs nb;
   std::vector<struct bk_normal_support> f_normal;
+  // reference-allele evidence (bk_ref_support: this context holds the calls)
+  RefBufs rb;
+  std::vector<struct bk_ref_support> f_ref;
 
   // fetch staging
   std::vector<bk_pair> f_pairs[3];
@@ -186,6 +191,7 @@ static RecView rec_view(const bk_ctx *ctx)
   r.n = ctx->rec.n;
   r.tid = ctx->rec.tid; r.pos = ctx->rec.pos; r.flag = ctx->rec.flag; r.mapq = ctx->rec.mapq;
   r.cigar_off = ctx->rec.cigar_off; r.cigar = ctx->rec.cigar;
+  r.isize = ctx->rec.isize; r.aux_off = ctx->rec.aux_off;
   return r;
 }
 
@@ -1489,6 +1495,104 @@ int bk_normal_support(bk_ctx *tumor, bk_ctx *normal, double w, const struct bk_n
     *out = tumor->f_normal.data();
     *count = ncl;
   });
+}
+
+int bk_ref_support(bk_ctx *calls, bk_ctx *records, int mapq_min, int anchor, double w, const struct bk_ref_support **out, uint64_t *count)
+{
+  if (!records) return guarded(calls, [&] { throw bk_error(BK_ERR_ARG, "bk_ref_support: null records context"); });
+  return guarded(calls, [&] {
+    if (!out || !count) throw bk_error(BK_ERR_ARG, "bk_ref_support: null output");
+    if (calls->shard || records->shard) throw bk_error(BK_ERR_ARG, "bk_ref_support: sharded contexts (bk_shard_*) are not supported");
+    if (!calls->bp_done) throw bk_error(BK_ERR_ARG, "bk_ref_support: call bk_split_breakpoints on the calls context first");
+    if (!records->have_records || !records->stats_done) throw bk_error(BK_ERR_ARG, "bk_ref_support: call bk_isize_stats on the records context first");
+    if (anchor < 0) throw bk_error(BK_ERR_ARG, "bk_ref_support: anchor must not be negative");
+    if (mapq_min < 0) throw bk_error(BK_ERR_ARG, "bk_ref_support: mapq_min must not be negative");
+    if (!(w >= 0.0 && w < 2147483648.0)) throw bk_error(BK_ERR_ARG, "bk_ref_support: w is out of range");
+    if (records->device != calls->device)
+      throw bk_error(BK_ERR_ARG, "bk_ref_support: calls (device " + std::to_string(calls->device) + ") and records (device " + std::to_string(records->device) +
+                                     ") contexts are on different devices");
+    if (records != calls && (records->nt != calls->nt || records->tname != calls->tname || records->tlen != calls->tlen))
+      throw bk_error(BK_ERR_ARG, "bk_ref_support: calls and records reference lists differ (names or lengths)");
+    const bk_soa &t = records->rec;
+    if (t.n && (!t.tid || !t.pos || !t.isize || !t.flag || !t.mapq || !t.cigar_off || !t.aux_off))
+      throw bk_error(BK_ERR_ARG, "bk_ref_support: the record table lacks a column");
+    const uint64_t ncl = calls->n_clusters;
+    if (records != calls) HIP_CHECK(hipStreamSynchronize(records->st));  // its stages ran on its own stream
+    struct bk_ref_support *d_res;
+    uint32_t *d_grp;
+    RefStat *d_stat = nullptr;
+    {
+      Scope s(calls, "ref_support");  // the device work alone: the copies below would hide it
+      ref_support(rec_view(records), (int) records->hc.max_span, calls->clusters_ptr(), ncl, mapq_min, anchor, w, calls->rb, calls->st, &d_res, &d_grp,
+                  calls->timing ? &d_stat : nullptr);
+    }
+    std::vector<struct bk_ref_support> res(ncl);
+    std::vector<uint32_t> grp(ncl);
+    std::vector<RefStat> stat(d_stat ? 2 * ncl : 0);
+    if (ncl)
+    {
+      HIP_CHECK(hipMemcpyAsync(res.data(), d_res, ncl * sizeof(struct bk_ref_support), hipMemcpyDeviceToHost, calls->st));
+      HIP_CHECK(hipMemcpyAsync(grp.data(), d_grp, ncl * 4, hipMemcpyDeviceToHost, calls->st));
+      if (d_stat) HIP_CHECK(hipMemcpyAsync(stat.data(), d_stat, 2 * ncl * sizeof(RefStat), hipMemcpyDeviceToHost, calls->st));
+    }
+    HIP_CHECK(hipStreamSynchronize(calls->st));
+    if (calls->timing && !calls->timers.empty())
+    {
+      // bytes: pos, flag, mapq, isize and two aux_off words of every record of a window (19 B each; bytes / 19 = records visited).
+      // touched: those, the CIGAR words that were walked, and per call two bk_cluster reads (one per side), the row and its group.
+      uint64_t visited = 0, words = 0;
+      for (const RefStat &x : stat)
+      {
+        visited += x.visited;
+        words += x.words;
+      }
+      calls->timers.back().bytes = 19ull * visited;
+      calls->timers.back().touched = 19ull * visited + 4ull * words + ncl * (2ull * sizeof(bk_cluster) + sizeof(struct bk_ref_support) + 4ull);
+    }
+    // device order is (numeric chr-pair key, id); BK_STAGE_CLUSTERS is the stable order by `group` (bk_fetch): a counting sort
+    uint32_t gmax = 0;
+    for (uint32_t g : grp) gmax = std::max(gmax, g);
+    std::vector<uint64_t> start(ncl ? (size_t) gmax + 2 : 1, 0);
+    for (uint32_t g : grp) ++start[g + 1];
+    for (size_t g = 1; g < start.size(); ++g) start[g] += start[g - 1];
+    calls->f_ref.resize(ncl);
+    for (uint64_t c = 0; c < ncl; ++c) calls->f_ref[start[grp[c]]++] = res[c];
+    *out = calls->f_ref.data();
+    *count = ncl;
+  });
+}
+
+// The genotype model of one call (include/breakid_hip.h): pure host code, every product rounded on its own (the library is built
+// with -ffp-contract=off).
+int bk_genotype_call(uint32_t alt, uint32_t ref, uint8_t *gt, uint8_t *gq, float *vaf)
+{
+  if (!gt || !gq || !vaf) return BK_ERR_ARG;
+  if ((uint64_t) alt + ref == 0)
+  {
+    *gt = 255;
+    *gq = 0;
+    *vaf = std::numeric_limits<float>::quiet_NaN();
+    return BK_OK;
+  }
+  static const double c[3] = {-0x1.4d104d427de80p+0, -0x1.34413509f79ffp-2, -0x1.6cf9f8b075bd8p-6};  // log10 of 0.05, 0.5, 0.95
+  const double k = (double) alt, r = (double) ref;
+  double L[3];
+  for (int g = 0; g < 3; ++g)
+  {
+    const double a = k * c[g], b = r * c[2 - g];
+    L[g] = a + b;
+  }
+  int best = 0;
+  for (int g = 1; g < 3; ++g)
+    if (L[g] > L[best]) best = g;
+  int second = -1;
+  for (int g = 0; g < 3; ++g)
+    if (g != best && (second < 0 || L[g] > L[second])) second = g;
+  const double q = std::floor(10.0 * (L[best] - L[second]) + 0.5);
+  *gt = (uint8_t) best;
+  *gq = (uint8_t) (q < 99.0 ? q : 99.0);
+  *vaf = (float) alt / (float) ((uint64_t) alt + ref);
+  return BK_OK;
 }
 
 int bk_run(bk_ctx *ctx, int mapq_min, int fast, double *w_out, uint64_t *n_valid)

@@ -39,9 +39,35 @@ struct RecView
   const uint16_t *flag;
   const uint8_t *mapq;
   const uint32_t *cigar_off, *cigar;
-  const unsigned long long *samp = nullptr;  // search keys of every 1024th record (bp.hip: rec_lower), or null
+  const unsigned long long *samp = nullptr;  // search keys of every 1024th record (rec_lower), or null
   uint64_t n_samp = 0;
+  const int32_t *isize = nullptr;     // the two columns only bk_ref_support reads (genotype.hip)
+  const uint32_t *aux_off = nullptr;
 };
+
+// first record index with (tid,pos) >= (T,P) in coordinate order (unmapped tid=-1 sorts last).  A search over the whole table
+// is ~30 dependent HBM round trips per region; with the sampled keys of every REC_SAMPLE-th record (5 MB for 620 M records:
+// cache resident) the first ~20 steps stay in the cache and only the last 10 touch the record columns.
+constexpr uint32_t REC_SAMPLE_SHIFT = 10;
+__device__ __forceinline__ unsigned long long rec_key(int32_t tid, long long pos) { return ((unsigned long long) (uint32_t) tid << 32) | (uint32_t) (pos + 0x80000000ll); }
+__device__ inline uint64_t rec_lower(const RecView &r, int32_t T, long long P)
+{
+  uint64_t lo = 0, hi = r.n;
+  if (r.samp)
+  {
+    // samp[j] = key of record j << REC_SAMPLE_SHIFT; first sample >= target bounds the answer to one stride
+    const unsigned long long want = rec_key(T, P < -0x80000000ll ? -0x80000000ll : P);
+    const unsigned long long *__restrict__ samp = r.samp;
+    const uint64_t a = wave_lower(0, r.n_samp, [&](uint64_t m) { return samp[m] < want; });
+    lo = a ? ((a - 1) << REC_SAMPLE_SHIFT) + 1 : 0;  // record (a-1)<<shift is < target, record a<<shift is >= target
+    hi = a < r.n_samp ? (a << REC_SAMPLE_SHIFT) : r.n;
+  }
+  const uint32_t Tu = (uint32_t) T;
+  return wave_lower(lo, hi, [&](uint64_t m) {
+    const uint32_t t = (uint32_t) r.tid[m];
+    return t != Tu ? (t < Tu) : ((long long) r.pos[m] < P);
+  });
+}
 
 struct BpWork
 {
@@ -62,6 +88,8 @@ void sort_splits(bk_split *unsorted, uint64_t n, bk_split *sorted, BpBufs &b, hi
 // returns the number of clusters that passed the near-diagonal filter; clusters_out holds them in (group key order, id) order
 uint64_t cluster_summary(const bk_pair *pairs, const uint32_t *idx, const uint32_t *gof, const uint32_t *cl, uint64_t n, uint32_t ng, const uint32_t *gkey,
                          const uint32_t *glex, int32_t nt, double w, DevBuf &clusters_out, BpBufs &b, hipStream_t st);
+// r with the sampled search keys of rec_lower, built into `samp` (tables of fewer than 64 strides are searched directly)
+RecView rec_sampled(const RecView &r, DevBuf &samp, hipStream_t st);
 // phases of the breakpoint stage (a sharded run sums `cov` and `depth` over the record shards between them)
 uint32_t *bp_cov_partial(const RecView &r, const bk_cluster *cl, uint64_t ncl, double w, int maxspan, BpBufs &b, hipStream_t st);
 void bp_vote(const bk_split *sp, uint64_t nsp, bk_cluster *cl, uint64_t ncl, double w, int maxspan, const uint32_t *cov, const int32_t *hdr_id, BpBufs &b, hipStream_t st);

@@ -162,29 +162,7 @@ __device__ __forceinline__ int32_t rec_endpos(const RecView &r, uint64_t i)
 {
   return bam_endpos_hts(r.flag[i], r.pos[i], r.cigar, r.cigar_off[i], r.cigar_off[i + 1]);
 }
-// first record index with (tid,pos) >= (T,P) in coordinate order (unmapped tid=-1 sorts last).  A search over the whole table
-// is ~30 dependent HBM round trips per region; with the sampled keys of every REC_SAMPLE-th record (5 MB for 620 M records:
-// cache resident) the first ~20 steps stay in the cache and only the last 10 touch the record columns.
-constexpr uint32_t REC_SAMPLE_SHIFT = 10;
-__device__ __forceinline__ unsigned long long rec_key(int32_t tid, long long pos) { return ((unsigned long long) (uint32_t) tid << 32) | (uint32_t) (pos + 0x80000000ll); }
-__device__ uint64_t rec_lower(const RecView &r, int32_t T, long long P)
-{
-  uint64_t lo = 0, hi = r.n;
-  if (r.samp)
-  {
-    // samp[j] = key of record j << REC_SAMPLE_SHIFT; first sample >= target bounds the answer to one stride
-    const unsigned long long want = rec_key(T, P < -0x80000000ll ? -0x80000000ll : P);
-    const unsigned long long *__restrict__ samp = r.samp;
-    const uint64_t a = wave_lower(0, r.n_samp, [&](uint64_t m) { return samp[m] < want; });
-    lo = a ? ((a - 1) << REC_SAMPLE_SHIFT) + 1 : 0;  // record (a-1)<<shift is < target, record a<<shift is >= target
-    hi = a < r.n_samp ? (a << REC_SAMPLE_SHIFT) : r.n;
-  }
-  const uint32_t Tu = (uint32_t) T;
-  return wave_lower(lo, hi, [&](uint64_t m) {
-    const uint32_t t = (uint32_t) r.tid[m];
-    return t != Tu ? (t < Tu) : ((long long) r.pos[m] < P);
-  });
-}
+// (rec_lower, the record lookup of every region query: bp.h)
 __global__ __launch_bounds__(256) void k_rec_sample(const int32_t *__restrict__ tid, const int32_t *__restrict__ pos, uint64_t n_samp, unsigned long long *__restrict__ samp)
 {
   const uint64_t j = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x;
@@ -724,19 +702,20 @@ uint64_t cluster_summary(const bk_pair *pairs, const uint32_t *idx, const uint32
 }
 
 // the record view with the sampled search keys behind it (rebuilt per call: the table may have been replaced)
-static RecView sampled(const RecView &r, BpBufs &b, hipStream_t st)
+RecView rec_sampled(const RecView &r, DevBuf &samp, hipStream_t st)
 {
   RecView v = r;
   v.n_samp = (r.n + (1ull << REC_SAMPLE_SHIFT) - 1) >> REC_SAMPLE_SHIFT;
   v.samp = nullptr;
   if (r.n >= (64ull << REC_SAMPLE_SHIFT))
   {
-    unsigned long long *sp = b.samp.as<unsigned long long>(v.n_samp + 1);
+    unsigned long long *sp = samp.as<unsigned long long>(v.n_samp + 1);
     hipLaunchKernelGGL(k_rec_sample, dim3(cdiv(v.n_samp, 256)), dim3(256), 0, st, r.tid, r.pos, v.n_samp, sp);
     v.samp = sp;
   }
   return v;
 }
+static RecView sampled(const RecView &r, BpBufs &b, hipStream_t st) { return rec_sampled(r, b.samp, st); }
 
 uint32_t *bp_cov_partial(const RecView &r0, const bk_cluster *cl, uint64_t ncl, double w, int maxspan, BpBufs &b, hipStream_t st)
 {

@@ -29,6 +29,10 @@
 // -normal: looked up at run time, so that this file also links against a library without the call (the CPU build of the host
 // code, oracle/Makefile); -normal then ends with an error
 extern "C" int bk_normal_support(bk_ctx *tumor, bk_ctx *normal, double w, const struct bk_normal_support **out, uint64_t *count) __attribute__((weak));
+// -genotype: the same for the reference-allele counts and the genotype model (the CPU build refuses -genotype)
+extern "C" int bk_ref_support(bk_ctx *calls, bk_ctx *records, int mapq_min, int anchor, double w, const struct bk_ref_support **out, uint64_t *count)
+    __attribute__((weak));
+extern "C" int bk_genotype_call(uint32_t alt, uint32_t ref, uint8_t *gt, uint8_t *gq, float *vaf) __attribute__((weak));
 // -x: the same for the exclude list (the CPU build refuses -x)
 extern "C" int bk_exclude_regions(bk_ctx *ctx, const bk_regions *r, uint64_t *n_removed) __attribute__((weak));
 extern "C" int bk_multi_run_ex(const bk_soa *host_table, const uint32_t *target_len, const char *const *target_name, int n_targets, const bk_regions *exclude, int n_gpus,
@@ -263,7 +267,9 @@ static const char *HELP =
      \t -t         \t distance relative to (sqrt(2)*(insert size mean +3* insert size sd))  [2]\n \
      \t -fast      \t use the fast cluster strategy [default no] \n \
      \t -all       \t no filter enspan out [default is filter]  \n \
-     \t -x         \t exclude list (BED: contig [start end]); records that overlap it are ignored  \n ";
+     \t -x         \t exclude list (BED: contig [start end]); records that overlap it are ignored  \n \
+     \t -genotype  \t count reference-allele evidence and genotype every call (twin files *_genotype.txt)  \n \
+     \t -anchor    \t bases a reference read must cover on either side of a breakpoint (with -genotype)  [10]\n ";
 
 // ---- RefSeqTranscript.{h,cc} -------------------------------------------------------------------------------
 struct Txpt
@@ -482,7 +488,28 @@ struct OutRow
 };
 static bool cmp_cluster(OutRow a, OutRow b) { return a.c.n_drp > b.c.n_drp; }  // BreakID.h:185-188 (by value, like the reference)
 
-static void write_row(std::ostream &o, const OutRow &r, const struct bk_normal_support *ns = nullptr)
+// the eight genotype columns of one sample: a call is genotyped on its junction reads (alt = n_sr against the mean of the two sides'
+// reference reads, rounded up); the pair counts stand beside it (include/breakid_hip.h: bk_genotype_call)
+static void write_genotype(std::ostream &o, const struct bk_ref_support &rs, uint32_t n_drp, uint32_t n_sr)
+{
+  uint8_t gt = 255, gq = 0, gtp = 255, gqp = 0;
+  float vaf = 0, vaf_pairs = 0;
+  bk_genotype_call(n_sr, (uint32_t) (((uint64_t) rs.ref_reads1 + rs.ref_reads2 + 1) / 2), &gt, &gq, &vaf);
+  bk_genotype_call(n_drp, (uint32_t) (((uint64_t) rs.ref_pairs1 + rs.ref_pairs2 + 1) / 2), &gtp, &gqp, &vaf_pairs);
+  auto put_vaf = [&](float v) {
+    if (v != v)
+      o << "\t.";
+    else
+      o << "\t" << v;
+  };
+  o << "\t" << rs.ref_pairs1 << "\t" << rs.ref_pairs2 << "\t" << rs.ref_reads1 << "\t" << rs.ref_reads2;
+  put_vaf(vaf_pairs);
+  put_vaf(vaf);
+  o << "\t" << (gt == 0 ? "0/0" : gt == 1 ? "0/1" : gt == 2 ? "1/1" : "./.") << "\t" << (int) gq;
+}
+
+static void write_row(std::ostream &o, const OutRow &r, const struct bk_normal_support *ns = nullptr, const struct bk_ref_support *gt = nullptr,
+                      const struct bk_ref_support *gt_normal = nullptr)
 {
   o << fusion_type(r.c.type_mask) << "\t";
   o << r.p1_chr << ":" << r.c.p1_exact << "\t";
@@ -493,7 +520,9 @@ static void write_row(std::ostream &o, const OutRow &r, const struct bk_normal_s
   o << (double) r.c.depth1 << "\t" << (double) r.c.depth2 << "\t";
   o << r.af1 << "\t" << r.af2 << "\t";
   o << r.rpt1 << "\t" << r.rpt2;
+  if (gt) write_genotype(o, *gt, r.c.n_drp, r.c.n_sr);
   if (ns) o << "\t" << ns->n_drp << "\t" << ns->n_sr << "\t" << ns->depth1 << "\t" << ns->depth2;
+  if (ns && gt_normal) write_genotype(o, *gt_normal, ns->n_drp, ns->n_sr);
   o << "\n";
 }
 
@@ -501,6 +530,10 @@ static const char *HEADER =
     "Fusion_Type\tBreakPoint1\tBreakPoint2\tGene1\tBreakPoint_Info_Pair1\tGene2\tBreakPoint_Info_Pair2\tN_DRP\tN_SR\t"
     "BreakPoint1_Depth\tBreakPoint2_Depth\tBreakPoint1_AF\tBreakPoint2_AF\tBP1_Neighbour_Seq\tBP2_Neighbour_Seq\n";
 static const char *NORMAL_COLUMNS = "\tNormal_DRP\tNormal_SR\tNormal_Depth1\tNormal_Depth2\n";
+// -genotype: the twin files' columns for the sample itself, and behind the four Normal_* columns the same eight for the normal
+static const char *GENOTYPE_COLUMNS = "\tRef_Pairs1\tRef_Pairs2\tRef_Reads1\tRef_Reads2\tVAF_Pairs\tVAF_Reads\tGT\tGQ";
+static const char *GENOTYPE_COLUMNS_NORMAL =
+    "\tNormal_Ref_Pairs1\tNormal_Ref_Pairs2\tNormal_Ref_Reads1\tNormal_Ref_Reads2\tNormal_VAF_Pairs\tNormal_VAF_Reads\tNormal_GT\tNormal_GQ";
 
 // one input BAM: its decoded table (host or device) and, once created, its context
 struct Sample
@@ -534,10 +567,12 @@ int main(int argc, char *argv[])
   clock_t start = clock();
   static struct option longopts[] = {{"help", 0, 0, 'h'}, {"i", 1, 0, 1}, {"o", 1, 0, 2}, {"q", 1, 0, 3}, {"n", 1, 0, 4},
                                      {"fast", 0, 0, 5},   {"t", 0, 0, 6}, {"all", 0, 0, 7}, {"gpu", 1, 0, 8}, {"gpus", 1, 0, 9},
-                                     {"comm", 1, 0, 10},  {"normal", 1, 0, 11}, {"x", 1, 0, 12}, {0, 0, 0, 0}};
+                                     {"comm", 1, 0, 10},  {"normal", 1, 0, 11}, {"x", 1, 0, 12}, {"genotype", 0, 0, 13},
+                                     {"anchor", 1, 0, 14}, {0, 0, 0, 0}};
   string inp_file, out_file, nib_dir, normal_file, exclude_file, build = "hg19";
   int qual = 20, device = 0, n_gpus = 0, transport = BK_TRANSPORT_AUTO;  // -gpus N: one sample over N GPUs (include/breakid_multi.h)
-  bool fast = false, filter = true;
+  bool fast = false, filter = true, genotype = false, anchor_given = false;
+  long anchor = 10;  // -anchor: bases a reference read must cover on either side of the breakpoint base
   int opt, li;
   optind = 0;
   while ((opt = getopt_long_only(argc, argv, "h?", longopts, &li)) != -1)
@@ -557,6 +592,11 @@ int main(int argc, char *argv[])
     case 10: transport = !strcmp(optarg, "rccl") ? BK_TRANSPORT_RCCL : !strcmp(optarg, "local") ? BK_TRANSPORT_LOCAL : BK_TRANSPORT_AUTO; break;
     case 11: normal_file = optarg; break;
     case 12: exclude_file = optarg; break;
+    case 13: genotype = true; break;
+    case 14:
+      anchor = atol(optarg);
+      anchor_given = true;
+      break;
     default: std::cerr << "Error: cannot parse arguments.\n"; exit(1);
     }
   }
@@ -589,6 +629,29 @@ int main(int argc, char *argv[])
       exit(1);
     }
     fclose(probe);
+  }
+  if (anchor_given && !genotype)
+  {
+    std::cerr << HELP << "Error: -anchor needs -genotype.\n";
+    exit(1);
+  }
+  if (genotype)
+  {
+    if (n_gpus >= 1)
+    {
+      std::cerr << HELP << "Error: -genotype cannot be combined with -gpus.\n";
+      exit(1);
+    }
+    if (anchor < 0 || anchor > 0x7FFFFFFFl)
+    {
+      std::cerr << HELP << "Error: -anchor must be a number from 0 to 2147483647.\n";
+      exit(1);
+    }
+    if (!bk_ref_support || !bk_genotype_call)
+    {
+      std::cerr << "Error: -genotype needs the GPU library" << std::endl;
+      exit(1);
+    }
   }
   const bool exclude = !exclude_file.empty();
   if (exclude)
@@ -843,6 +906,21 @@ int main(int argc, char *argv[])
       die_normal();
     if ((rc = bk_normal_support(ctx, normal.ctx, w, &nsup, &n_nsup)) != BK_OK) die(rc);
   }
+  // -genotype: reference-allele counts of every call on the sample's own records, then on the normal's (both record tables are
+  // still resident: the contexts and the decoded tables are released at the end)
+  vector<struct bk_ref_support> gsup, gsup_normal;
+  if (genotype)
+  {
+    const struct bk_ref_support *rs = nullptr;
+    uint64_t n_rs = 0;
+    if ((rc = bk_ref_support(ctx, ctx, qual, (int) anchor, w, &rs, &n_rs)) != BK_OK) die(rc);
+    gsup.assign(rs, rs + n_rs);  // (the rows are the library's until the next call)
+    if (normal.ctx)
+    {
+      if ((rc = bk_ref_support(ctx, normal.ctx, qual, (int) anchor, w, &rs, &n_rs)) != BK_OK) die(rc);
+      gsup_normal.assign(rs, rs + n_rs);
+    }
+  }
   const void *data = nullptr;
   uint64_t cnt = 0;
   if ((rc = bk_fetch(ctx, BK_STAGE_CLUSTERS, &data, &cnt, nullptr, nullptr)) != BK_OK) die(rc);
@@ -890,8 +968,12 @@ int main(int argc, char *argv[])
   // write_enspan_out (BreakID.cc:1184-1263): std::sort with the reference's comparator
   std::sort(rows.begin(), rows.end(), cmp_cluster);
   std::ofstream out, outf, out_n, outf_n;  // (_n: the twins with the matched normal's four counts)
+  std::ofstream out_g, outf_g;             // (_g: the twins with the genotype columns, -genotype)
   const bool with_normal = !normal_file.empty();  // (a tumour without calls still gets header-only twins)
   const string header_n = string(HEADER, strlen(HEADER) - 1) + NORMAL_COLUMNS;
+  string header_g = string(HEADER, strlen(HEADER) - 1) + GENOTYPE_COLUMNS;
+  if (with_normal) header_g += string(NORMAL_COLUMNS, strlen(NORMAL_COLUMNS) - 1) + GENOTYPE_COLUMNS_NORMAL;
+  header_g += "\n";
   if (!filter)
   {
     out.open((out_file + "_fusion_all.txt").c_str());
@@ -901,6 +983,11 @@ int main(int argc, char *argv[])
       out_n.open((out_file + "_fusion_all_normal.txt").c_str());
       out_n << header_n;
     }
+    if (genotype)
+    {
+      out_g.open((out_file + "_fusion_all_genotype.txt").c_str());
+      out_g << header_g;
+    }
   }
   outf.open((out_file + "_fusion.txt").c_str());
   outf << HEADER;
@@ -908,6 +995,11 @@ int main(int argc, char *argv[])
   {
     outf_n.open((out_file + "_fusion_normal.txt").c_str());
     outf_n << header_n;
+  }
+  if (genotype)
+  {
+    outf_g.open((out_file + "_fusion_genotype.txt").c_str());
+    outf_g << header_g;
   }
   for (auto &r : rows)
   {
@@ -920,6 +1012,13 @@ int main(int argc, char *argv[])
       if (filt_ok) write_row(outf_n, r, &nsup[r.idx]);
       if (!filter && all_ok) write_row(out_n, r, &nsup[r.idx]);
     }
+    if (genotype && r.idx < gsup.size() && (!with_normal || (r.idx < n_nsup && r.idx < gsup_normal.size())))
+    {
+      const struct bk_normal_support *ns = with_normal ? &nsup[r.idx] : nullptr;
+      const struct bk_ref_support *gn = with_normal ? &gsup_normal[r.idx] : nullptr;
+      if (filt_ok) write_row(outf_g, r, ns, &gsup[r.idx], gn);
+      if (!filter && all_ok) write_row(out_g, r, ns, &gsup[r.idx], gn);
+    }
   }
   if (!filter) out.close();
   outf.close();
@@ -927,6 +1026,11 @@ int main(int argc, char *argv[])
   {
     if (!filter) out_n.close();
     outf_n.close();
+  }
+  if (genotype)
+  {
+    if (!filter) out_g.close();
+    outf_g.close();
   }
   {
     std::ofstream p((out_file + "_params.txt").c_str());  // write_enspan_params :1170-1182
@@ -938,6 +1042,7 @@ int main(int argc, char *argv[])
     p << "build\t" << build << std::endl;
     if (exclude) p << "exclude_file\t" << exclude_file << std::endl;
     if (!normal_file.empty()) p << "normal_file\t" << normal_file << std::endl;
+    if (genotype) p << "genotype_anchor\t" << anchor << std::endl;
   }
   clock_t end = clock();
   std::cout << "the fusion process of file " << inp_file << "  costs time: " << (end - start) / double(CLOCKS_PER_SEC) << " seconds" << std::endl;

@@ -220,6 +220,38 @@ struct bk_normal_support { uint32_t n_drp, n_sr, depth1, depth2; }; /* 16 bytes 
  * when one of these does not hold.  A normal without pairs or tuples is no error: its counts are 0. */
 int bk_normal_support(bk_ctx *tumor, bk_ctx *normal, double w, const struct bk_normal_support **out, uint64_t *count);
 
+/* ---- genotype: reference-allele evidence -------------------------------------------------------------------------------
+ * Only voted clusters (flags bit 1) get counts; the rows of all others are zero.  For a voted cluster and each of its two sides s
+ * (chromosome T = ps_tid, exact 1-based breakpoint e = ps_exact), let b = e - 1 (0-based), A = anchor >= 0, W = (int) w.  A record
+ * i of the `records` context is eligible when
+ *   - tid[i] == T, flag has 0x1, flag has none of 0x4 0x100 0x200 0x400 0x800, mapq[i] >= mapq_min,
+ *   - its aux blob is empty (aux_off[i+1] == aux_off[i]: a read with an SA tag is junction evidence, never reference evidence),
+ *   - pos[i] <= b - A.
+ * Then
+ *   ref_reads_s = eligible records with bam_endpos(i) >= b + 1 + A (bam_endpos as in bk_exclude_regions: the aligned reference
+ *                 interval covers the breakpoint base with at least A bases on either side; soft clips do not count, D and N do),
+ *   ref_pairs_s = eligible records that also have flag 0x2, lack 0x8, and have 0 < isize[i] <= W and
+ *                 pos[i] + isize[i] >= b + 1 + A (the left mate of a properly paired fragment that spans the breakpoint;
+ *                 isize > 0 counts a fragment once; only the left mate's own mapq and aux are looked at).
+ * All comparisons in signed 64-bit.  A read can count in both.  T < 0 gives zeros.
+ * The struct has no typedef: the name belongs to the call below. */
+struct bk_ref_support { uint32_t ref_pairs1, ref_pairs2, ref_reads1, ref_reads2; }; /* 16 bytes */
+/* calls: after bk_split_breakpoints.  records: after bk_isize_stats (the stream pass gives the longest alignment); records == calls
+ * genotypes the sample itself, another context on the same device with an identical reference list (names and lengths) is the
+ * matched normal.  Neither may be a shard (bk_shard_*).  *out: one row per BK_STAGE_CLUSTERS row, same order, library-owned until
+ * the next call or bk_free(calls).  BK_ERR_ARG (with the reason in bk_last_error) for wrong call order, anchor < 0, mapq_min < 0,
+ * differing reference lists, shards.  It changes nothing a later bk_fetch or stage returns, and works on every table form the
+ * context can hold (host upload, BK_MEM_DEVICE with and without `side`, the table bk_exclude_regions left behind, the context of
+ * bk_bam_decode_device_ctx while its bk_bam_dev lives). */
+int bk_ref_support(bk_ctx *calls, bk_ctx *records, int mapq_min, int anchor, double w, const struct bk_ref_support **out, uint64_t *count);
+/* The genotype model, a pure host function (no context, no GPU).  With k = alt, r = ref and c = (log10 0.05, log10 0.5, log10 0.95)
+ * (a 5 % error rate, as SV genotypers use: the model's constants, not measurements): L[g] = k * c[g] + r * c[2 - g] for g = 0, 1, 2
+ * in double precision, each product rounded on its own; gt = the g with the largest L (the smaller g on a tie; 0 = 0/0, 1 = 0/1,
+ * 2 = 1/1); gq = min(99, floor(10 * (L[best] - L[second]) + 0.5)); vaf = (float) k / (float) ((uint64_t) k + r).  k + r == 0:
+ * gt = 255 ("./."), gq = 0, vaf = NaN.  A call is genotyped on its junction reads: alt = n_sr, ref = (ref_reads1 + ref_reads2 + 1) / 2;
+ * the pair counts stand beside it: n_drp against (ref_pairs1 + ref_pairs2 + 1) / 2.  BK_ERR_ARG for a null output. */
+int bk_genotype_call(uint32_t alt, uint32_t ref, uint8_t *gt, uint8_t *gq, float *vaf);
+
 /* Copy a stage's result to library-owned host memory.  *data stays valid until the next bk_fetch
  * of the same stage or bk_free.  group_off (may be NULL) receives n_groups+1 offsets for pair stages. */
 int bk_fetch(bk_ctx *ctx, int stage, const void **data, uint64_t *count, const uint64_t **group_off, uint32_t *n_groups);
