@@ -3,14 +3,9 @@
 #include <cmath>
 #include <limits>
 #include <cstring>
-#include <memory>
 #include <numeric>
-#include <thread>
-#include <atomic>
-#include <chrono>
 
 #include "bk_common.h"
-#include <dirent.h>
 #include "prims.h"
 #include "stream.h"
 #include "join.h"
@@ -20,6 +15,7 @@
 #include "genotype.h"
 #include "exclude.h"
 #include "ahc.h"
+#include "lanes.h"
 #include "bgzf_gpu.h"
 
 namespace
@@ -52,10 +48,6 @@ struct StageTimer
   uint64_t touched = 0;  // bytes this stage's kernels themselves load + store (0 = not modelled)
 };
 }  // namespace
-
-// the runtime's hardware-queue count as far as this library can know it: GPU_MAX_HW_QUEUES as the environment had it when the
-// first context was made (ROCm's default is 4 when it is unset)
-static int g_hw_queues_at_init = 0;
 
 struct bk_ctx
 {
@@ -94,7 +86,6 @@ struct bk_ctx
   const bk_split *ext_split = nullptr;
   bk_cluster *ext_clusters = nullptr;
   std::vector<uint8_t> own_groups;  // per group (numeric key order): 1 = this rank clusters it; empty = all
-  DevBuf d_drop;
   const Cand *cand_ptr() const { return ext_cand ? ext_cand : d_cand.get<Cand>(); }
   const bk_split *split_raw_ptr() const { return ext_split ? ext_split : d_split_raw.get<bk_split>(); }
   bk_cluster *clusters_ptr() const { return ext_clusters ? ext_clusters : d_clusters.get<bk_cluster>(); }
@@ -109,34 +100,9 @@ struct bk_ctx
   std::vector<uint64_t> gstart_host;
   DevBuf d_glex;
 
-  // mask + cluster
-  SortService svc;  // resident sort service of the stage (sortsvc.inc)
-  std::vector<hipEvent_t> svc_probe;
-  int svc_late = 0;
-  bool svc_refused = false;  // a stage of this context found the service out of reach once (shared hardware queue, crowded device): not tried again
-  ClusterBufs cb;
-  PairList list;
-  DevBuf iso_idx, iso_goff, d_cluster;
-  // second lane of chromosome-pair groups (bk_mask_and_cluster): its own buffers, stream and host thread
-  struct Lane
-  {
-    ClusterBufs cb;
-    PairList list, iso;
-    DevBuf d_cluster;
-    hipStream_t st = nullptr;
-    ~Lane()
-    {
-      if (st) (void) hipStreamDestroy(st);
-    }
-  };
-  std::vector<std::unique_ptr<Lane>> lanes;  // lanes 1 .. K-1 (lane 0 uses the context's own stream and buffers)
-  PairList listA, isoA;  // first lane's lists before the merge
-  PairList lane_mid, lane_iso_m, lane_acc[4];  // kept between calls: a list that is a local is allocated and freed (a device-wide wait) in every call
-  DevBuf lane_cacc[4];
-  DevBuf d_clusterA, d_dropA;
-  uint64_t iso_n = 0;
+  // mask + cluster (lanes.hip): the lists and cluster numbers it leaves, its lanes, its sort service
+  ClusterStage stage;
   bool clustered = false;
-  AhcBufs ab;
 
   // summary + breakpoints
   BpBufs bb;
@@ -423,7 +389,7 @@ void bk_prepare_process()
   static std::once_flag once;
   std::call_once(once, [] {
     const char *q = getenv("GPU_MAX_HW_QUEUES");
-    g_hw_queues_at_init = q ? atoi(q) : 4;
+    stage_set_hw_queues(q ? atoi(q) : 4);  // (ROCm's default is 4 when it is unset)
   });
 }
 
@@ -431,7 +397,7 @@ int bk_init(int device, const uint32_t *target_len, const char *const *target_na
 {
   {
     // the hardware-queue count the runtime started with (the lanes of bk_mask_and_cluster and the chunk streams of the GPU feed
-    // share queues when there are fewer than they have streams: lanes_apply tells it once on stderr)
+    // share queues when there are fewer than they have streams: the stage tells it once on stderr)
     bk_prepare_process();
   }
   if (!out || n_targets < 0 || (n_targets && (!target_len || !target_name)))
@@ -753,654 +719,15 @@ int bk_discordant_pairs(bk_ctx *ctx, int mapq_min, double w, uint64_t *n_pairs, 
   });
 }
 
-// Two lanes.  The reference clusters its chromosome-pair groups one after the other and independently of each other
-// (BreakID.cc:119-167).  All groups in one pass pay, in each of the five sorts, the longest heapsort segment of ANY group; two
-// disjoint sets of groups on two streams, each driven by its own host thread, overlap the lone-wave heaps of one set with the
-// bandwidth- and launch-bound partition levels of the other.  Needs more hardware queues than ROCm's default of 4 (the heap
-// kernels of both lanes sit on side streams that must not share a queue): enabled by BREAKID_GROUP_LANES=2.  Results are identical by construction:
-// the groups never interact, the lanes' lists are merged back into group order.
-static void run_lane(const bk_pair *pairs, const uint32_t *gof, const uint64_t *gstart, uint32_t ng, uint64_t n, double w, int fast, const uint32_t *drop, PairList &L, PairList &iso,
-                     DevBuf &d_cluster, ClusterBufs &cb, AhcBufs &ab, hipStream_t st, const uint64_t *gstart_host, const uint8_t *keep_host)
-{
-  remove_isolated_begin(pairs, gof, gstart, ng, n, w, L, cb, st, drop, gstart_host, keep_host);
-  remove_isolated_end(pairs, L, cb, st);
-  iso.n = L.n;
-  iso.ng = L.ng;
-  uint32_t *ii = iso.idx.as<uint32_t>(L.n + 1), *ig = iso.gof.as<uint32_t>(L.n + 1);
-  uint64_t *io = iso.goff.as<uint64_t>((uint64_t) L.ng + 1);
-  if (L.n) HIP_CHECK(hipMemcpyAsync(ii, L.idx.get<uint32_t>(), L.n * 4, hipMemcpyDeviceToDevice, st));
-  if (L.n) HIP_CHECK(hipMemcpyAsync(ig, L.gof.get<uint32_t>(), L.n * 4, hipMemcpyDeviceToDevice, st));
-  HIP_CHECK(hipMemcpyAsync(io, L.goff.get<uint64_t>(), ((uint64_t) L.ng + 1) * 8, hipMemcpyDeviceToDevice, st));
-  if (fast)
-    fast_cluster_all(pairs, L, w, d_cluster, cb, st);
-  else
-    ahc_cluster_all(pairs, L, w, d_cluster, ab, cb, st);
-}
-
-static bool sort_service_on()
-{
-  // BREAKID_SORT_SERVICE=0: every std::sort replay as its own chain of launches (the earlier form)
-  static const bool on = !(getenv("BREAKID_SORT_SERVICE") && atoi(getenv("BREAKID_SORT_SERVICE")) == 0);
-  return on;
-}
-// The resident sort service runs while one of these lives: every sort through the context's (and its lanes') buffers is a job.
-// Its two persistent kernels occupy a hardware queue each until the stage ends, so a stream of this stage that shares one of those
-// queues (more streams in the process than the runtime has hardware queues: GPU_MAX_HW_QUEUES) would never get its turn.  That is
-// why the stage (a) is the only one on its device (contexts of one process on one GPU - `-comm local` - take turns: the others sort
-// by launches), and (b) probes every stream it is going to use after the kernels have started: an empty kernel that has not run
-// after 50 ms sends the whole stage back to the launch path (the service stops, the stream drains).
-__global__ void k_svc_probe() {}
-// Compute queues that exist on the device right now, over ALL processes (the kernel driver's sysfs: /sys/class/kfd/kfd/proc/<pid>/
-// queues/<n>/{gpuid,type}); -1 when that cannot be told.  Measured on MI355X: beyond 24 compute queues on a device - this process's
-// 16-17 plus a second process holding 8 or more - the driver maps the queues in turns, and persistent kernels whose submitters wait
-// for their turn leave jobs unfinished for seconds (4 streams held by a second process were fine, 8 were not: DESIGN.md, "Hardware queues").  The service runs only while the census stays at or below that.
-static int kfd_compute_queues(int device)
-{
-  char bus[64] = {0};
-  if (hipDeviceGetPCIBusId(bus, (int) sizeof bus, device) != hipSuccess) return -1;
-  unsigned dom = 0, b = 0, d = 0, f = 0;
-  if (sscanf(bus, "%x:%x:%x.%x", &dom, &b, &d, &f) != 4) return -1;
-  const unsigned long want_loc = (b << 8) | (d << 3) | f;
-  auto read_file = [](const std::string &path, std::string &out) {
-    FILE *fp = fopen(path.c_str(), "r");
-    if (!fp) return false;
-    char buf[4096];
-    const size_t n = fread(buf, 1, sizeof buf - 1, fp);
-    fclose(fp);
-    buf[n] = 0;
-    out = buf;
-    return true;
-  };
-  auto list_dir = [](const std::string &path, std::vector<std::string> &names) {
-    DIR *dp = opendir(path.c_str());
-    if (!dp) return false;
-    while (dirent *e = readdir(dp))
-      if (e->d_name[0] != '.') names.push_back(e->d_name);
-    closedir(dp);
-    return true;
-  };
-  // the device's gpu_id: the topology node with its PCI location
-  unsigned long gpu_id = 0;
-  {
-    std::vector<std::string> nodes;
-    if (!list_dir("/sys/class/kfd/kfd/topology/nodes", nodes)) return -1;
-    for (const std::string &n : nodes)
-    {
-      std::string props, id;
-      const std::string base = "/sys/class/kfd/kfd/topology/nodes/" + n;
-      if (!read_file(base + "/properties", props) || !read_file(base + "/gpu_id", id)) continue;
-      unsigned long loc = ~0ul, domain = ~0ul;
-      size_t p = props.find("location_id ");
-      if (p != std::string::npos) loc = strtoul(props.c_str() + p + 12, nullptr, 10);
-      p = props.find("domain ");
-      if (p != std::string::npos) domain = strtoul(props.c_str() + p + 7, nullptr, 10);
-      if (loc == want_loc && (domain == ~0ul || domain == dom) && strtoul(id.c_str(), nullptr, 10) != 0) gpu_id = strtoul(id.c_str(), nullptr, 10);
-    }
-  }
-  if (!gpu_id) return -1;
-  std::vector<std::string> procs;
-  if (!list_dir("/sys/class/kfd/kfd/proc", procs)) return -1;
-  int total = 0;
-  for (const std::string &pid : procs)
-  {
-    std::vector<std::string> qs;
-    const std::string qdir = "/sys/class/kfd/kfd/proc/" + pid + "/queues";
-    if (!list_dir(qdir, qs)) continue;  // (another user's process: not readable - and not on a GPU this process may use either)
-    for (const std::string &q : qs)
-    {
-      std::string g, t;
-      if (!read_file(qdir + "/" + q + "/gpuid", g) || !read_file(qdir + "/" + q + "/type", t)) continue;
-      if (strtoul(g.c_str(), nullptr, 10) == gpu_id && strtoul(t.c_str(), nullptr, 10) == 0) ++total;
-    }
-  }
-  return total;
-}
-constexpr int SVC_MAX_DEVICE_QUEUES = 24;
-static std::mutex g_svc_device_m[64];
-// once per process on stderr: the stage sorts by launches although the service was wanted
-static void tell_no_service()
-{
-  static std::atomic<bool> told{false};
-  if (!getenv("BREAKID_QUIET") && !told.exchange(true))
-    fprintf(stderr, "[breakid] the resident sort service shares a hardware queue with a stream of its own stage (GPU_MAX_HW_QUEUES too low for the streams of this process), or other processes hold hardware queues on this device: sorting by launches instead\n");
-}
-struct SvcStage
-{
-  bk_ctx *ctx;
-  bool on;
-  std::unique_lock<std::mutex> device_turn;
-  SvcStage(bk_ctx *c, bool want, uint64_t n_bound, uint64_t max_group, const std::vector<hipStream_t> &streams) : ctx(c), on(want && sort_service_on() && !c->svc_refused)
-  {
-    if (on && ctx->device >= 0 && ctx->device < 64)
-    {
-      device_turn = std::unique_lock<std::mutex>(g_svc_device_m[ctx->device], std::try_to_lock);
-      on = device_turn.owns_lock();
-    }
-    if (!on) return;
-    const auto ts0 = std::chrono::steady_clock::now();
-    ctx->svc.start(n_bound, max_group + 2, ctx->st);  // (+2: a mask may emit one element twice)
-    const auto ts1 = std::chrono::steady_clock::now();
-    // (the count is kept for a quarter of a second per device: reading it is ~0.5 ms of sysfs, and a sample's stages - or a bench's
-    // steps - follow each other faster than processes come and go)
-    int census;
-    {
-      static std::mutex cm;
-      static std::chrono::steady_clock::time_point when[64];
-      static int last[64];
-      static bool have[64] = {};
-      std::lock_guard<std::mutex> l(cm);
-      const int d = ctx->device & 63;
-      if (!have[d] || std::chrono::duration<double>(ts1 - when[d]).count() > 0.25)
-      {
-        last[d] = kfd_compute_queues(ctx->device);
-        when[d] = std::chrono::steady_clock::now();
-        have[d] = true;
-      }
-      census = last[d];
-    }
-    if (bk_debug("lanes"))
-      fprintf(stderr, "[lanes] sort service started in %.3f ms; compute queues on the device (all processes): %d (counted in %.3f ms)\n", std::chrono::duration<double, std::milli>(ts1 - ts0).count(), census,
-              std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ts1).count());
-    const bool crowded = census > SVC_MAX_DEVICE_QUEUES;
-    const bool behind = !crowded && !reachable(streams);
-    const bool late = !crowded && !behind && !ctx->svc.narrow_running(0.03);
-    if (crowded || behind || late)
-    {
-      ctx->svc.stop();
-      on = false;
-      // a stream behind a persistent kernel's queue or a crowded device stay that way: this context does not try again; a narrow
-      // kernel that was merely late (a busy device) gets a second chance
-      if (crowded || behind || ++ctx->svc_late >= 2) ctx->svc_refused = true;
-      device_turn.unlock();
-      tell_no_service();
-      return;
-    }
-    ctx->svc_late = 0;
-    set(&ctx->svc);
-  }
-  bool reachable(const std::vector<hipStream_t> &streams)
-  {
-    while (ctx->svc_probe.size() < streams.size())
-    {
-      hipEvent_t e;
-      HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-      ctx->svc_probe.push_back(e);
-    }
-    for (size_t k = 0; k < streams.size(); ++k)
-    {
-      hipLaunchKernelGGL(k_svc_probe, dim3(1), dim3(64), 0, streams[k]);
-      HIP_CHECK(hipEventRecord(ctx->svc_probe[k], streams[k]));
-    }
-    const auto t0 = std::chrono::steady_clock::now();
-    auto since = [&] { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); };
-    bool ok = true;
-    for (size_t k = 0; k < streams.size() && ok; ++k)
-      for (;;)
-      {
-        const hipError_t e = hipEventQuery(ctx->svc_probe[k]);
-        if (e == hipSuccess) break;
-        if (e != hipErrorNotReady) throw bk_error(BK_ERR_HIP, std::string("sort service probe: ") + hipGetErrorString(e));
-        if (since() > 0.05)
-        {
-          ok = false;
-          break;
-        }
-      }
-    // An empty kernel per stream comes back within ~0.1-0.3 ms.  Milliseconds mean that the device's hardware queues are
-    // oversubscribed (other processes hold queues too: the scheduler then maps the queues in turns, and persistent kernels whose
-    // submitters wait for their turn crawl - measured with a second process holding 16 queues: the stage 3-6 times slower or a job
-    // that never finished) - no service then either.
-    const double took = since();
-    if (bk_debug("lanes")) fprintf(stderr, "[lanes] sort service probe: %zu streams in %.3f ms%s\n", streams.size(), took * 1e3, ok ? "" : " (gave up)");
-    return ok && took < 0.003;
-  }
-  void set(SortService *s)
-  {
-    ctx->cb.se.svc = s;
-    ctx->cb.se.svc_slot = 0xFFFFFFFFu;
-    for (auto &l : ctx->lanes)
-    {
-      l->cb.se.svc = s;
-      l->cb.se.svc_slot = 0xFFFFFFFFu;
-    }
-  }
-  void finish()
-  {
-    if (!on) return;
-    on = false;
-    set(nullptr);
-    // every job has been waited for by its caller: the streams must be through before the workgroups are told to leave
-    hipError_t e = hipStreamSynchronize(ctx->st);
-    for (auto &l : ctx->lanes)
-      if (l->st && e == hipSuccess) e = hipStreamSynchronize(l->st);
-    ctx->svc.stop();
-    device_turn.unlock();
-    if (e != hipSuccess) throw bk_error(BK_ERR_HIP, std::string("sort service: ") + hipGetErrorString(e));
-  }
-  ~SvcStage()
-  {
-    try
-    {
-      finish();
-    }
-    catch (const bk_error &)
-    {
-    }
-  }
-};
-// The hardware queues of the lane stage.  The runtime gives a process GPU_MAX_HW_QUEUES of them (ROCm's default: 4) and maps its
-// streams onto them; two streams on one queue wait for each other's kernels, and a persistent kernel holds its queue for the whole
-// stage.  So the budget is decided from the count the runtime started with, before any stream or persistent kernel of the stage
-// exists:
-//   service   LANE_STREAMS_MAX streams of the lanes + the two persistent kernels' streams + the copy stream of the quit word
-//             (SortService::start) = 7 queues; below that nothing of the service is started (the stage sorts by launches)
-//   launches  one queue stays with the process's first stream (the null stream of torch and of the runtime's copies: the kernel
-//             trace at 4 queues shows it on a queue of its own, and the stage's fourth stream sharing a queue with another lane);
-//             a lane sorts on its own stream and forks the big heaps of each sort onto a side stream only when the other queues
-//             allow two per lane (SortEmuBufs::fork_heaps; without the fork all heaps of a sort are one dispatch); no more lanes
-//             than streams that get a queue each
-constexpr int LANE_STREAMS_MAX = 4;
-constexpr int SVC_STAGE_QUEUES = LANE_STREAMS_MAX + 3;
-static bool lane_service(int fast) { return sort_service_on() && fast && g_hw_queues_at_init >= SVC_STAGE_QUEUES; }
-static int stage_queues() { return std::max(1, g_hw_queues_at_init - 1); }
-// streams per lane of the launch path: 2 (own + side stream for the big heaps) or 1; BREAKID_LANE_STREAMS=1 / 2 overrides
-static int lane_streams_each(int K)
-{
-  static const int want = getenv("BREAKID_LANE_STREAMS") ? atoi(getenv("BREAKID_LANE_STREAMS")) : 0;
-  if (want == 1 || want == 2) return want;
-  return stage_queues() >= 2 * K ? 2 : 1;
-}
-static int lanes_wanted(bool svc)
-{
-  // with the resident sort service a lane's sort is a submit and a wait of its thread, so there can be a lane for every one or two
-  // of the groups that carry long heap segments: twelve by default (each with a stream of its own; measured 12 / 16 / 18 / 24 lanes
-  // on 12 streams: 30.6 / 33.4 / 34.3 / 35.7 ms for the stage - every lane costs its ~160 other launches)
-  const char *env = getenv("BREAKID_GROUP_LANES");
-  static const int want_svc = env ? atoi(env) : 12;
-  if (svc) return want_svc < 1 ? 1 : (want_svc > 26 ? 26 : want_svc);
-  // four lanes unless the caller says otherwise (BREAKID_GROUP_LANES=1: one pass); lanes_apply decides from the data whether they
-  // pay.  Measured on the 30x WGS shape with the segment-per-workgroup tail of the level loop: 2 lanes 42.0 ms, 3 lanes 42.6,
-  // 4 lanes 39.6, 5 lanes 48.5 (more lanes shorten a lane's "longest heap of any of its groups" per sort, and cost a level loop,
-  // a ranking and a finisher chain of their own, each ~100 launches that wait for each other across lanes).  Without an explicit
-  // count no more lanes than hardware queues: a lane whose next small kernel sits behind another lane's heap on a shared queue
-  // waits for that heap.
-  static const int want = env ? atoi(env) : std::max(1, std::min(4, stage_queues() / lane_streams_each(std::min(4, stage_queues()))));
-  return want < 1 ? 1 : (want > 26 ? 26 : want);
-}
-static bool lanes_apply(const bk_ctx *ctx, int fast)
-{
-  static const uint64_t min_pairs = getenv("BREAKID_LANES_MIN_PAIRS") ? strtoull(getenv("BREAKID_LANES_MIN_PAIRS"), nullptr, 10) : (1ull << 20);  // below: launch-bound anyway
-  // picked from the data: lanes pay when at least two groups are large enough to run into long sorts side by side
-  uint32_t large = 0;
-  const uint64_t big = std::max<uint64_t>(2, min_pairs >> 6);  // 16 K pairs with the default threshold
-  for (uint32_t g = 0; g < ctx->jr.n_groups && g + 1 < ctx->gstart_host.size(); ++g) large += ctx->gstart_host[g + 1] - ctx->gstart_host[g] >= big ? 1u : 0u;
-  const bool yes = lanes_wanted(lane_service(fast)) >= 2 && fast && ctx->jr.n_groups >= 4 && ctx->jr.n_pairs >= min_pairs && large >= 2;
-  if (yes)
-  {
-    static bool told = false;
-    const int K = lanes_wanted(lane_service(fast));
-    if (!told && !lane_service(fast) && K * lane_streams_each(K) > stage_queues() && bk_debug("lanes"))
-    {
-      told = true;
-      fprintf(stderr, "[breakid] GPU_MAX_HW_QUEUES=%d: the lanes of chromosome-pair groups (bk_mask_and_cluster) and their heap kernels will share hardware queues "
-                        "(BREAKID_GROUP_LANES=1: one pass)\n", g_hw_queues_at_init);
-    }
-  }
-  return yes;
-}
-
-// K lanes of groups.  A lane's time is (a) per sort the LONGEST heapsort segment of any of its groups - a serial chain of one wave
-// - plus (b) partition levels and masks in proportion to its pairs plus (c) a fixed number of launch-bound late levels.  Which
-// groups own long heap segments cannot be told from their sizes (all same-chromosome groups of a WGS sample are about equally
-// large; two or three of them carry segments of 30-46 K elements, most carry a few thousand), but it can be OBSERVED: a group
-// whose sort by x (by y) ran into the depth limit does so again in the next sort by the same coordinate.  So the stage runs in
-// two parts:
-//   part 1  sorts 1-3 (x, mask, y, mask, x: remove_isolated_pairs) in K lanes split blindly (longest-processing-time on size^e);
-//           every lane records the longest heap segment of each of its groups in the sort by y and in the LAST sort by x;
-//   part 2  sorts 4-5 (x-windows, y, y-windows, x) in K lanes split on what was observed: the groups are placed, heaviest
-//           chain first, where the lane's longest segment by y + longest segment by x (+ a term for its pair count) grows least.
-// BREAKID_LANE_ADAPT=0 keeps the blind split for the whole stage.  On the 30x WGS shape part 2 comes out balanced (18.9 / 21.4 ms
-// with two lanes) where the blind split leaves one lane 9 ms behind the other (46.6 / 37 ms); part 1 stays as the blind split
-// leaves it (24.1 / 21.3 ms); the barrier and the re-split cost ~1 ms.
-// Results are identical whatever the split: the groups never
-// interact, a lane's list keeps every group's order, and the lists are merged back into group order.
-struct LanePlan
-{
-  std::vector<int> lane_of;
-};
-static LanePlan plan_blind(const bk_ctx *ctx, int K)
-{
-  const uint32_t ng = ctx->jr.n_groups;
-  std::vector<uint32_t> order(ng);
-  std::iota(order.begin(), order.end(), 0u);
-  auto size_of = [&](uint32_t g) { return ctx->gstart_host[g + 1] - ctx->gstart_host[g]; };
-  std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return size_of(a) > size_of(b); });
-  constexpr double wexp = 2.0;  // longest-processing-time on size^2
-  LanePlan p;
-  p.lane_of.assign(ng, 0);
-  std::vector<double> load(K, 0.0);
-  // sharded sample: this rank only masks and clusters the groups it owns (bk_shard_own_groups); the others belong to no lane
-  const bool owned_only = !ctx->own_groups.empty();
-  if (owned_only && ctx->own_groups.size() != ng) throw bk_error(BK_ERR_ARG, "bk_shard_own_groups: group count changed");
-  for (uint32_t i = 0; i < ng; ++i)
-  {
-    const uint32_t g = order[i];
-    if (owned_only && !ctx->own_groups[g])
-    {
-      p.lane_of[g] = -1;
-      continue;
-    }
-    int l = 0;
-    for (int k = 1; k < K; ++k)
-      if (load[k] < load[l]) l = k;
-    load[l] += std::pow((double) size_of(g), wexp);
-    p.lane_of[g] = l;
-  }
-  return p;
-}
-// sizes = pairs per group now; hx / hy = longest heap segment per group seen in a sort by x / by y (0: none)
-static LanePlan plan_observed(const std::vector<uint64_t> &sizes, const std::vector<uint32_t> &hx, const std::vector<uint32_t> &hy, int K, double x_sorts = 1.0)
-{
-  const uint32_t ng = (uint32_t) sizes.size();
-  // in units of one pop of a lone wave in LDS (~0.15 us): a pair costs a lane ~0.15 ns in the two sorts that are left (most of a
-  // lane's time outside the heaps is a fixed number of launches), an element of a heap segment beyond what fits the LDS of a
-  // CU costs twice as much (the hybrid loop: 0.30 us per pop while the heap's tail is in global memory)
-  constexpr double per_pair = 0.001;
-  auto heap_cost = [](uint32_t m) { return (double) m + (m > 40947u ? 1.0 * (double) (m - 40947u) : 0.0); };
-  std::vector<uint32_t> order(ng);
-  std::iota(order.begin(), order.end(), 0u);
-  auto chain = [&](uint32_t g) { return heap_cost(hx[g]) + heap_cost(hy[g]); };
-  std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) {
-    const double ca = chain(a), cb = chain(b);
-    return ca != cb ? ca > cb : sizes[a] > sizes[b];
-  });
-  LanePlan p;
-  p.lane_of.assign(ng, 0);
-  std::vector<double> mx(K, 0.0), my(K, 0.0), pairs(K, 0.0);
-  auto cost = [&](int l) { return x_sorts * mx[l] + my[l] + per_pair * pairs[l]; };  // x_sorts: how many sorts by x are left (one by y)
-  for (uint32_t g : order)
-  {
-    const int l0 = 0;
-    int best = l0;
-    double best_cost = 0;
-    for (int l = l0; l < K; ++l)
-    {
-      const double c = x_sorts * std::max(mx[l], heap_cost(hx[g])) + std::max(my[l], heap_cost(hy[g])) + per_pair * (pairs[l] + (double) sizes[g]);
-      // the lane whose own cost ends lowest takes the group (ties: the emptier lane)
-      if (l == l0 || c < best_cost || (c == best_cost && cost(l) < cost(best)))
-      {
-        best = l;
-        best_cost = c;
-      }
-    }
-    mx[best] = std::max(mx[best], heap_cost(hx[g]));
-    my[best] = std::max(my[best], heap_cost(hy[g]));
-    pairs[best] += (double) sizes[g];
-    p.lane_of[g] = best;
-  }
-  if (bk_debug("lanes"))
-    for (int l = 0; l < K; ++l)
-    {
-      fprintf(stderr, "[lanes] lane %d: max heap x %.0f y %.0f, %.0f pairs, cost %.0f; heavy groups:", l, mx[l], my[l], pairs[l], cost(l));
-      for (uint32_t g = 0; g < ng; ++g)
-        if (p.lane_of[g] == l && (hx[g] || hy[g])) fprintf(stderr, " %u(%u,%u)", g, hx[g], hy[g]);
-      fprintf(stderr, "\n");
-    }
-  return p;
-}
-
-static void group_lanes(bk_ctx *ctx, double w, int fast)
-{
-  const uint32_t ng = ctx->jr.n_groups;
-  // With the resident sort service a lane's stream is idle most of the time (its thread waits for the sort's job), so the twelve
-  // lanes share FOUR streams (LANE_STREAMS_MAX): measured 12 lanes on 12 / 8 / 4 streams 44.5-44.8 / 44.4-44.7 / 44.5-45.2 ms per
-  // step (6 streams, two heavy lanes per stream: 46.7-47.4; round-4 start, with waiting kernels on the streams: 12 / 4 / 3 / 2
-  // streams 31.6 / 31.2 / 35.0 / 40.2 ms for the stage).  Fewer streams = fewer hardware queues: the stage then needs 4 + 3 of
-  // them (SVC_STAGE_QUEUES), and a second process on the device (a test runner's parent, another sample) leaves the device's
-  // queues uncrowded (SVC_MAX_DEVICE_QUEUES).
-  auto make_lanes = [&](int K, int S) {
-    while ((int) ctx->lanes.size() < K - 1)
-    {
-      ctx->lanes.emplace_back(new bk_ctx::Lane());
-      ctx->lanes.back()->cb.max_group_bound = ctx->cb.max_group_bound;
-    }
-    for (int k = 0; k < S - 1; ++k)
-      if (!ctx->lanes[k]->st) HIP_CHECK(hipStreamCreateWithFlags(&ctx->lanes[k]->st, hipStreamNonBlocking));
-  };
-  bool use_svc = sort_service_on() && fast;
-  if (use_svc && !lane_service(fast))
-  {
-    // too few hardware queues for the service and the lanes' streams: nothing of the service is started
-    use_svc = false;
-    tell_no_service();
-    if (bk_debug("lanes")) fprintf(stderr, "[lanes] %d hardware queues, the sort service needs %d: not started\n", g_hw_queues_at_init, SVC_STAGE_QUEUES);
-  }
-  int K = lanes_wanted(use_svc);
-  int S = use_svc ? std::max(1, std::min(LANE_STREAMS_MAX, K)) : K;
-  make_lanes(K, S);
-  std::vector<hipStream_t> stage_streams{ctx->st};
-  for (int k = 0; k < S - 1; ++k) stage_streams.push_back(ctx->lanes[k]->st);
-  SvcStage svc_stage(ctx, use_svc, ctx->jr.n_pairs + 2ull * ng + 4096, ctx->cb.max_group_bound, stage_streams);  // the service runs from here to the end of the lanes (also when one of them throws)
-  if (use_svc && !svc_stage.on)
-  {
-    // the service is not to be had (another context of this process has it on this device, or a hardware queue is shared): the lanes of the launch path
-    use_svc = false;
-    K = lanes_wanted(false);
-    S = K;
-    make_lanes(K, S);
-  }
-  // launch path: the big heaps of a lane's sorts on a side stream of its own only when every lane can have two queues
-  struct ForkReset
-  {
-    bk_ctx *c;
-    ~ForkReset() { c->cb.se.fork_heaps = true; }
-  } fork_reset{ctx};
-  {
-    const bool fork = use_svc || lane_streams_each(K) == 2;
-    ctx->cb.se.fork_heaps = fork;
-    for (int k = 0; k < K - 1; ++k) ctx->lanes[k]->cb.se.fork_heaps = fork;
-    if (!use_svc && bk_debug("lanes")) fprintf(stderr, "[lanes] launch path: %d lanes, %d stream%s each, %d hardware queues\n", K, fork ? 2 : 1, fork ? "s" : "", g_hw_queues_at_init);
-    if (!use_svc && sort_tasks_on() && bk_debug("lanes")) fprintf(stderr, "[lanes] sorts as task dispatches on the lane streams\n");
-  }
-  const bool adapt = !use_svc;  // (the service does not report the groups' longest heap segments back to the host)
-  auto lane_cb = [&](int l) -> ClusterBufs & { return l == 0 ? ctx->cb : ctx->lanes[l - 1]->cb; };
-  auto lane_st = [&](int l) { const int k = l % S; return k == 0 ? ctx->st : ctx->lanes[k - 1]->st; };
-  auto lane_list = [&](int l) -> PairList & { return l == 0 ? ctx->listA : ctx->lanes[l - 1]->list; };
-  auto lane_iso = [&](int l) -> PairList & { return l == 0 ? ctx->isoA : ctx->lanes[l - 1]->iso; };
-  auto lane_cl = [&](int l) -> DevBuf & { return l == 0 ? ctx->d_clusterA : ctx->lanes[l - 1]->d_cluster; };
-  uint32_t *drop_base = nullptr;  // the lanes' plans, one row of ng + 1 words each, uploaded in one copy
-  auto lane_drop = [&](int l) { return drop_base + (size_t) l * ((size_t) ng + 1); };
-  std::vector<std::vector<uint8_t>> keep(K, std::vector<uint8_t>(ng, 0));  // keep[l][g]: lane l owns group g (host copy of the plan)
-  auto upload_plan = [&](const LanePlan &p) {
-    for (int l = 0; l < K; ++l)
-      for (uint32_t g = 0; g < ng; ++g) keep[l][g] = p.lane_of[g] == l ? 1 : 0;
-    std::vector<uint32_t> drop((size_t) K * ((size_t) ng + 1), 0u);
-    for (int l = 0; l < K; ++l)
-      for (uint32_t g = 0; g < ng; ++g) drop[(size_t) l * ((size_t) ng + 1) + g] = p.lane_of[g] == l ? 0u : 1u;  // a lane drops what the others own
-    drop_base = ctx->d_dropA.as<uint32_t>(drop.size() + 1);
-    HIP_CHECK(hipMemcpyAsync(drop_base, drop.data(), drop.size() * 4, hipMemcpyHostToDevice, ctx->st));
-    HIP_CHECK(hipStreamSynchronize(ctx->st));  // (the pair table and the masks are ready for all lanes)
-  };
-  // runs body(l) for every lane, lane 0 on this thread; the lanes' streams are synchronised when this returns
-  auto in_lanes = [&](auto body) {
-    std::vector<std::string> err(K);
-    std::vector<int> code(K, BK_OK);
-    static const bool dbg_lanes = bk_debug("lanes");
-    const auto t_start = std::chrono::steady_clock::now();
-    auto guarded_body = [&](int l) {
-      try
-      {
-        body(l);
-        HIP_CHECK(hipStreamSynchronize(lane_st(l)));
-        if (dbg_lanes)
-          fprintf(stderr, "[lanes] lane %d done after %.2f ms\n", l, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count());
-      }
-      catch (const bk_error &e)
-      {
-        code[l] = e.code;
-        err[l] = e.msg;
-      }
-    };
-    std::vector<std::thread> th;
-    for (int l = 1; l < K; ++l)
-      th.emplace_back([&, l] {
-        (void) hipSetDevice(ctx->device);
-        guarded_body(l);
-      });
-    guarded_body(0);
-    for (std::thread &t : th) t.join();
-    for (int l = 0; l < K; ++l)
-      if (code[l] != BK_OK) throw bk_error(code[l], err[l]);
-  };
-  // folds the lanes' lists (disjoint groups) into one list in group order; cl = the cluster numbers travel along
-  auto merge_all = [&](auto list_of, auto cl_of, PairList &out, DevBuf *cl_out, PairList *, DevBuf *) {
-    std::vector<const PairList *> ls(K);
-    std::vector<const uint32_t *> cs(K);
-    for (int l = 0; l < K; ++l)
-    {
-      ls[l] = &list_of(l);
-      cs[l] = cl_of(l);
-    }
-    merge_lists_many(ls.data(), cl_out ? cs.data() : nullptr, K, out, cl_out, ctx->st);
-  };
-  const bk_pair *pairs = ctx->jr.pairs;
-  static const bool dbg_phases = bk_debug("lanes");
-  const auto tp0 = std::chrono::steady_clock::now();
-  auto phase = [&](const char *what) {
-    if (dbg_phases) fprintf(stderr, "[lanes] %s at %.2f ms\n", what, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tp0).count());
-  };
-  upload_plan(plan_blind(ctx, K));
-  phase("plan uploaded");
-  phase("service started");
-  if (!adapt)
-  {
-    in_lanes([&](int l) { run_lane(pairs, ctx->jr.gof, ctx->jr.gstart, ng, ctx->jr.n_pairs, w, fast, lane_drop(l), lane_list(l), lane_iso(l), lane_cl(l), lane_cb(l), ctx->ab, lane_st(l), ctx->gstart_host.data(), keep[l].data()); });
-  }
-  else
-  {
-    // part 1: sorts 1-3, observed.  (Dealing again after the second sort already - x from the first sort, y from the second, three
-    // sorts left - was measured worse, 42.0 ms against 38.1: the heaps of the FIRST sort by x, short, on the unmasked list, say
-    // little about the later ones.)
-    constexpr bool split_early = false;
-    in_lanes([&](int l) {
-      ClusterBufs &cb = lane_cb(l);
-      cb.heavy_x.assign(ng, 0u);
-      cb.heavy_y.assign(ng, 0u);
-      cb.observe = true;
-      cb.se.heavy_all = false;
-      remove_isolated_begin(pairs, ctx->jr.gof, ctx->jr.gstart, ng, ctx->jr.n_pairs, w, lane_list(l), cb, lane_st(l), lane_drop(l), ctx->gstart_host.data(), keep[l].data());
-      if (!split_early)
-      {
-        cb.heavy_x.assign(ng, 0u);  // the third sort (by x, on the masked list) is the one that tells about the fifth
-        remove_isolated_end(pairs, lane_list(l), cb, lane_st(l));
-      }
-      cb.observe = false;
-    });
-    PairList &mid = ctx->lane_mid;
-    PairList *acc = ctx->lane_acc;
-    DevBuf *cacc = ctx->lane_cacc;
-    merge_all([&](int l) -> const PairList & { return lane_list(l); }, [&](int) -> const uint32_t * { return nullptr; }, mid, nullptr, acc, cacc);
-    std::vector<uint64_t> goff_h((size_t) ng + 1);
-    HIP_CHECK(hipMemcpyAsync(goff_h.data(), mid.goff.get<uint64_t>(), ((size_t) ng + 1) * 8, hipMemcpyDeviceToHost, ctx->st));
-    HIP_CHECK(hipStreamSynchronize(ctx->st));
-    std::vector<uint64_t> sizes(ng);
-    std::vector<uint32_t> hx(ng, 0u), hy(ng, 0u);
-    for (uint32_t g = 0; g < ng; ++g) sizes[g] = goff_h[g + 1] - goff_h[g];
-    for (int l = 0; l < K; ++l)
-      for (uint32_t g = 0; g < ng; ++g)
-      {
-        hx[g] = std::max(hx[g], lane_cb(l).heavy_x[g]);
-        hy[g] = std::max(hy[g], lane_cb(l).heavy_y[g]);
-      }
-    upload_plan(plan_observed(sizes, hx, hy, K, split_early ? 2.0 : 1.0));
-    // part 2: sorts (3,) 4, 5
-    in_lanes([&](int l) {
-      PairList &L = lane_list(l), &iso = lane_iso(l);
-      hipStream_t st = lane_st(l);
-      list_subset_ranges(mid, goff_h.data(), keep[l].data(), L, st);
-      if (split_early) remove_isolated_end(pairs, L, lane_cb(l), st);
-      iso.n = L.n;
-      iso.ng = L.ng;
-      uint32_t *ii = iso.idx.as<uint32_t>(L.n + 1), *ig = iso.gof.as<uint32_t>(L.n + 1);
-      uint64_t *io = iso.goff.as<uint64_t>((uint64_t) L.ng + 1);
-      if (L.n) HIP_CHECK(hipMemcpyAsync(ii, L.idx.get<uint32_t>(), L.n * 4, hipMemcpyDeviceToDevice, st));
-      if (L.n) HIP_CHECK(hipMemcpyAsync(ig, L.gof.get<uint32_t>(), L.n * 4, hipMemcpyDeviceToDevice, st));
-      HIP_CHECK(hipMemcpyAsync(io, L.goff.get<uint64_t>(), ((uint64_t) L.ng + 1) * 8, hipMemcpyDeviceToDevice, st));
-      if (fast)
-        fast_cluster_all(pairs, L, w, lane_cl(l), lane_cb(l), st);
-      else
-        ahc_cluster_all(pairs, L, w, lane_cl(l), ctx->ab, lane_cb(l), st);
-    });
-  }
-  phase("lanes done");
-  svc_stage.finish();  // (throws what a task reported)
-  phase("service stopped");
-  if (use_svc && bk_debug("lanes")) fprintf(stderr, "[svc] tasks: %u wide, %u narrow\n", ctx->svc.stats[0], ctx->svc.stats[1]);
-  // one list in group order again
-  PairList &iso_m = ctx->lane_iso_m;
-  PairList *iacc = ctx->lane_acc, *lacc = ctx->lane_acc + 2;
-  DevBuf *icacc = ctx->lane_cacc, *lcacc = ctx->lane_cacc + 2;
-  merge_all([&](int l) -> const PairList & { return lane_iso(l); }, [&](int) -> const uint32_t * { return nullptr; }, iso_m, nullptr, iacc, icacc);
-  merge_all([&](int l) -> const PairList & { return lane_list(l); }, [&](int l) -> const uint32_t * { return lane_cl(l).get<uint32_t>(); }, ctx->list, &ctx->d_cluster, lacc, lcacc);
-  HIP_CHECK(hipStreamSynchronize(ctx->st));
-  phase("lists merged");
-  ctx->iso_n = iso_m.n;
-  std::swap(ctx->iso_idx, iso_m.idx);
-  std::swap(ctx->iso_goff, iso_m.goff);
-}
-
 int bk_mask_and_cluster(bk_ctx *ctx, double w, int fast, uint64_t *n_clustered)
 {
   return guarded(ctx, [&] {
-    {
-      uint64_t mg = 0;
-      for (uint32_t g = 0; g < ctx->jr.n_groups && g + 1 < ctx->gstart_host.size(); ++g) mg = std::max<uint64_t>(mg, ctx->gstart_host[g + 1] - ctx->gstart_host[g]);
-      ctx->cb.max_group_bound = mg;
-      for (auto &l : ctx->lanes) l->cb.max_group_bound = mg;
-    }
-    if (lanes_apply(ctx, fast))
-    {
-      {
-        Scope s(ctx, "mask_and_cluster_lanes");
-        group_lanes(ctx, w, fast);
-      }
-      ctx->clustered = true;
-      if (n_clustered) *n_clustered = ctx->list.n;
-      return;
-    }
-    SvcStage svc_stage(ctx, true, ctx->jr.n_pairs + 2ull * ctx->jr.n_groups + 4096, ctx->cb.max_group_bound, {ctx->st});
-    {
-      Scope s(ctx, "remove_isolated");
-      const uint32_t *drop = nullptr;
-      if (!ctx->own_groups.empty())
-      {
-        // sharded sample: this rank masks and clusters only the chromosome-pair groups it owns
-        if (ctx->own_groups.size() != ctx->jr.n_groups) throw bk_error(BK_ERR_ARG, "bk_shard_own_groups: group count changed");
-        std::vector<uint32_t> d(ctx->jr.n_groups);
-        for (uint32_t g = 0; g < ctx->jr.n_groups; ++g) d[g] = ctx->own_groups[g] ? 0u : 1u;
-        uint32_t *dd = ctx->d_drop.as<uint32_t>((uint64_t) ctx->jr.n_groups + 1);
-        if (ctx->jr.n_groups) HIP_CHECK(hipMemcpyAsync(dd, d.data(), d.size() * 4, hipMemcpyHostToDevice, ctx->st));
-        HIP_CHECK(hipStreamSynchronize(ctx->st));
-        drop = dd;
-      }
-      remove_isolated_all(ctx->jr.pairs, ctx->jr.gof, ctx->jr.gstart, ctx->jr.n_groups, ctx->jr.n_pairs, w, ctx->list, ctx->cb, ctx->st, drop);
-    }
-    ctx->iso_n = ctx->list.n;
-    uint32_t *ii = ctx->iso_idx.as<uint32_t>(ctx->list.n + 1);
-    uint64_t *ig = ctx->iso_goff.as<uint64_t>((uint64_t) ctx->list.ng + 1);
-    if (ctx->list.n) HIP_CHECK(hipMemcpyAsync(ii, ctx->list.idx.get<uint32_t>(), ctx->list.n * 4, hipMemcpyDeviceToDevice, ctx->st));
-    if (ctx->list.ng) HIP_CHECK(hipMemcpyAsync(ig, ctx->list.goff.get<uint64_t>(), ((uint64_t) ctx->list.ng + 1) * 8, hipMemcpyDeviceToDevice, ctx->st));
-    if (!fast) svc_stage.finish();  // (the exact UPGMA replay sorts nothing and may take long: the service's workgroups would hold their CUs, then leave on their own)
-    {
-      Scope s(ctx, fast ? "fast_cluster" : "ahc_cluster");
-      if (fast)
-        fast_cluster_all(ctx->jr.pairs, ctx->list, w, ctx->d_cluster, ctx->cb, ctx->st);
-      else
-        ahc_cluster_all(ctx->jr.pairs, ctx->list, w, ctx->d_cluster, ctx->ab, ctx->cb, ctx->st);
-    }
-    svc_stage.finish();
+    // the stage itself, its lanes and its sort service: lanes.hip
+    const StageInput in{ctx->device, ctx->st, ctx->jr, ctx->gstart_host, ctx->own_groups,
+                        [&](const char *name, const std::function<void()> &body) { Scope s(ctx, name); body(); }};
+    ctx->stage.run(in, w, fast);
     ctx->clustered = true;
-    if (n_clustered) *n_clustered = ctx->list.n;
+    if (n_clustered) *n_clustered = ctx->stage.list.n;
   });
 }
 
@@ -1419,8 +746,8 @@ int bk_cluster_summary(bk_ctx *ctx, double w, uint64_t *n_clusters)
     if (!ctx->clustered) throw bk_error(BK_ERR_ARG, "bk_cluster_summary: call bk_mask_and_cluster first");
     ctx->bp_done = false;
     Scope s(ctx, "cluster_summary");
-    ctx->n_clusters = cluster_summary(ctx->jr.pairs, ctx->list.idx.get<uint32_t>(), ctx->list.gof.get<uint32_t>(), ctx->d_cluster.get<uint32_t>(), ctx->list.n,
-                                      ctx->list.ng, ctx->jr.gkey, ctx->d_glex.get<uint32_t>(), ctx->nt, w, ctx->d_clusters, ctx->bb, ctx->st);
+    ctx->n_clusters = cluster_summary(ctx->jr.pairs, ctx->stage.list.idx.get<uint32_t>(), ctx->stage.list.gof.get<uint32_t>(), ctx->stage.d_cluster.get<uint32_t>(), ctx->stage.list.n,
+                                      ctx->stage.list.ng, ctx->jr.gkey, ctx->d_glex.get<uint32_t>(), ctx->nt, w, ctx->d_clusters, ctx->bb, ctx->st);
     if (n_clusters) *n_clusters = ctx->n_clusters;
   });
 }
@@ -1656,11 +983,11 @@ int bk_fetch(bk_ctx *ctx, int stage, const void **data, uint64_t *count, const u
       fetch_list(0, nullptr, ctx->jr.gstart, nullptr, ctx->jr.n_pairs);
       break;
     case BK_STAGE_ISO:
-      fetch_list(1, ctx->iso_idx.get<uint32_t>(), ctx->iso_goff.get<uint64_t>(), nullptr, ctx->iso_n);
+      fetch_list(1, ctx->stage.iso_idx.get<uint32_t>(), ctx->stage.iso_goff.get<uint64_t>(), nullptr, ctx->stage.iso_n);
       break;
     case BK_STAGE_CLUSTERED:
       if (!ctx->clustered) throw bk_error(BK_ERR_ARG, "bk_fetch: not clustered yet");
-      fetch_list(2, ctx->list.idx.get<uint32_t>(), ctx->list.goff.get<uint64_t>(), ctx->d_cluster.get<uint32_t>(), ctx->list.n);
+      fetch_list(2, ctx->stage.list.idx.get<uint32_t>(), ctx->stage.list.goff.get<uint64_t>(), ctx->stage.d_cluster.get<uint32_t>(), ctx->stage.list.n);
       break;
     case BK_STAGE_SPLITS:
       ensure_splits_sorted(ctx);
@@ -1959,9 +1286,7 @@ int bk_debug_std_sort(bk_ctx *ctx, const uint32_t *key, const uint64_t *group_of
     HIP_CHECK(hipMemcpy(dgoff.as<uint64_t>((uint64_t) n_groups + 1), group_off, ((uint64_t) n_groups + 1) * 8, hipMemcpyHostToDevice));
     uint64_t max_group = 0;
     for (uint32_t g = 0; g < n_groups; ++g) max_group = std::max<uint64_t>(max_group, group_off[g + 1] - group_off[g]);
-    SvcStage svc_stage(ctx, true, n + 2ull * n_groups + 4096, max_group, {ctx->st});
-    std_sort_groups(dk.get<uint32_t>(), dp.get<uint32_t>(), dgof.get<uint32_t>(), dgoff.get<uint64_t>(), n_groups, n, ctx->cb.se, ctx->st);
-    svc_stage.finish();
+    ctx->stage.debug_sort(ctx->device, ctx->st, dk.get<uint32_t>(), dp.get<uint32_t>(), dgof.get<uint32_t>(), dgoff.get<uint64_t>(), n_groups, n, max_group);
     HIP_CHECK(hipMemcpyAsync(perm_out, dp.get<uint32_t>(), n * 4, hipMemcpyDeviceToHost, ctx->st));
     HIP_CHECK(hipStreamSynchronize(ctx->st));
   });
@@ -1971,11 +1296,7 @@ int bk_sort_forms(bk_ctx *ctx, uint64_t out[3])
 {
   return guarded(ctx, [&] {
     if (!out) throw bk_error(BK_ERR_ARG, "bk_sort_forms: null output");
-    for (int k = 0; k < 3; ++k)
-    {
-      out[k] = ctx->cb.se.sorts[k];
-      for (const auto &l : ctx->lanes) out[k] += l->cb.se.sorts[k];
-    }
+    ctx->stage.sort_forms(out);
   });
 }
 
@@ -2001,7 +1322,7 @@ int bk_debug_ahc(bk_ctx *ctx, const uint32_t *x, const uint32_t *y, uint32_t n, 
     HIP_CHECK(hipMemcpy(L.idx.as<uint32_t>(n + 1), iota.data(), n * 4, hipMemcpyHostToDevice));
     HIP_CHECK(hipMemcpy(L.gof.as<uint32_t>(n + 1), gof.data(), n * 4, hipMemcpyHostToDevice));
     HIP_CHECK(hipMemcpy(L.goff.as<uint64_t>(2), goff, 16, hipMemcpyHostToDevice));
-    ahc_cluster_all(dp.get<bk_pair>(), L, w, dcl, ctx->ab, ctx->cb, ctx->st);
+    ahc_cluster_all(dp.get<bk_pair>(), L, w, dcl, ctx->stage.ab, ctx->stage.cb(), ctx->st);
     *n_out = (uint32_t) L.n;
     if (L.n)
     {
@@ -2172,9 +1493,9 @@ int bk_group_stats(bk_ctx *ctx, const bk_group_stat **out, uint32_t *n_groups)
     std::vector<uint32_t> kmax(ng + 1, 0);
     if (ng)
     {
-      HIP_CHECK(hipMemcpyAsync(iso.data(), ctx->iso_goff.get<uint64_t>(), ((uint64_t) ng + 1) * 8, hipMemcpyDeviceToHost, ctx->st));
-      HIP_CHECK(hipMemcpyAsync(clu.data(), ctx->list.goff.get<uint64_t>(), ((uint64_t) ng + 1) * 8, hipMemcpyDeviceToHost, ctx->st));
-      if (ctx->list.n && ctx->bb.kmax.p) HIP_CHECK(hipMemcpyAsync(kmax.data(), ctx->bb.kmax.get<uint32_t>(), (uint64_t) ng * 4, hipMemcpyDeviceToHost, ctx->st));
+      HIP_CHECK(hipMemcpyAsync(iso.data(), ctx->stage.iso_goff.get<uint64_t>(), ((uint64_t) ng + 1) * 8, hipMemcpyDeviceToHost, ctx->st));
+      HIP_CHECK(hipMemcpyAsync(clu.data(), ctx->stage.list.goff.get<uint64_t>(), ((uint64_t) ng + 1) * 8, hipMemcpyDeviceToHost, ctx->st));
+      if (ctx->stage.list.n && ctx->bb.kmax.p) HIP_CHECK(hipMemcpyAsync(kmax.data(), ctx->bb.kmax.get<uint32_t>(), (uint64_t) ng * 4, hipMemcpyDeviceToHost, ctx->st));
       HIP_CHECK(hipStreamSynchronize(ctx->st));
     }
     ctx->f_gstats.assign(ng, bk_group_stat{});
@@ -2216,7 +1537,7 @@ int bk_debug_points(bk_ctx *ctx, int mode, const uint32_t *x, const uint32_t *y,
     HIP_CHECK(hipMemcpy(dgoff.as<uint64_t>(2), goff, 16, hipMemcpyHostToDevice));
     const bk_pair *pairs = dp.as<bk_pair>(n + 1);
     // one group holding the points in the given order
-    remove_isolated_all(pairs, dgof.get<uint32_t>(), dgoff.get<uint64_t>(), 1, mode == 1 ? n : 0, w, L, ctx->cb, ctx->st);
+    remove_isolated_all(pairs, dgof.get<uint32_t>(), dgoff.get<uint64_t>(), 1, mode == 1 ? n : 0, w, L, ctx->stage.cb(), ctx->st);
     if (mode != 1)
     {
       // the list as given (remove_isolated_all sized the buffers; fill identity order)
@@ -2228,9 +1549,9 @@ int bk_debug_points(bk_ctx *ctx, int mode, const uint32_t *x, const uint32_t *y,
       if (n) HIP_CHECK(hipMemcpy(L.gof.as<uint32_t>(n + 1), gof.data(), n * 4, hipMemcpyHostToDevice));
       HIP_CHECK(hipMemcpy(L.goff.as<uint64_t>(2), goff, 16, hipMemcpyHostToDevice));
       if (mode == 0)
-        debug_mask_list(pairs, L, (long) w, ctx->cb, ctx->st);
+        debug_mask_list(pairs, L, (long) w, ctx->stage.cb(), ctx->st);
       else
-        fast_cluster_all(pairs, L, w, dcl, ctx->cb, ctx->st);
+        fast_cluster_all(pairs, L, w, dcl, ctx->stage.cb(), ctx->st);
     }
     *n_out = (uint32_t) L.n;
     if (L.n)

@@ -17,7 +17,7 @@ struct PairList
 
 struct ClusterBufs
 {
-  // observers for the lanes of api.hip (host, may stay empty): the longest heapsort segment of every group in the sorts by x / by y
+  // observers for the lanes of lanes.hip (host, may stay empty): the longest heapsort segment of every group in the sorts by x / by y
   std::vector<uint32_t> heavy_x, heavy_y;
   bool observe = false;
   // upper bound on the pairs of any one group (host; 0 = unknown): the anchored-window passes need log2 of it pointer-jumping levels
@@ -35,17 +35,14 @@ void remove_isolated_all(const bk_pair *pairs, const uint32_t *gof0, const uint6
 void remove_isolated_begin(const bk_pair *pairs, const uint32_t *gof0, const uint64_t *gstart, uint32_t ng, uint64_t n, double w, PairList &L, ClusterBufs &b, hipStream_t st,
                            const uint32_t *drop_group = nullptr, const uint64_t *gstart_host = nullptr, const uint8_t *keep_host = nullptr);
 void remove_isolated_end(const bk_pair *pairs, PairList &L, ClusterBufs &b, hipStream_t st);
-// dst = src without the groups flagged in drop[] (device, one u32 per group; offsets for all groups are kept)
-void list_subset(const PairList &src, const uint32_t *drop, PairList &dst, ClusterBufs &b, hipStream_t st);
-// the same from host knowledge: keep_host[g] != 0 selects group g, src_goff_host = src's offsets; one launch over the subset
+// dst = the groups of src with keep_host[g] != 0 (offsets for all groups are kept); src_goff_host = src's offsets; one launch
 void list_subset_ranges(const PairList &src, const uint64_t *src_goff_host, const uint8_t *keep_host, PairList &dst, hipStream_t st);
 // removes the groups that keep fewer than 2 pairs (they are not clustered, BreakID.cc:125)
 void drop_small_groups(PairList &L, ClusterBufs &b, hipStream_t st);
 // find_cluster_pairs_enspan_fast for every group with >= 2 pairs; L becomes the clustered list, cluster_out[p] its cluster number
 void fast_cluster_all(const bk_pair *pairs, PairList &L, double w, DevBuf &cluster_out, ClusterBufs &b, hipStream_t st);
-// two lists over disjoint sets of groups (both with offsets for all ng groups) -> one list in group order; cl_* = the cluster
-// numbers that travel with the elements (may be null)
+// K lists over disjoint sets of groups (each with offsets for all ng groups) -> one list in group order; cls[l] = the cluster
+// numbers that travel with the elements of list l (cls and cl_out may be null)
 void merge_lists_many(const PairList *const *lists, const uint32_t *const *cls, int K, PairList &out, DevBuf *cl_out, hipStream_t st);
-void merge_lists(const PairList &A, const uint32_t *clA, const PairList &B, const uint32_t *clB, PairList &out, DevBuf *cl_out, hipStream_t st);
 // test hook: mask_pairs_chr_pos on the list in its current order
 void debug_mask_list(const bk_pair *pairs, PairList &L, long dist, ClusterBufs &b, hipStream_t st);

@@ -346,21 +346,6 @@ void remove_isolated_end(const bk_pair *pairs, PairList &L, ClusterBufs &b, hipS
   sort_list(pairs, L, 0, nullptr, 0, b, st);
 }
 
-void list_subset(const PairList &src, const uint32_t *drop, PairList &dst, ClusterBufs &b, hipStream_t st)
-{
-  dst.n = src.n;
-  dst.ng = src.ng;
-  uint32_t *idx = dst.idx.as<uint32_t>(src.n + 1), *gof = dst.gof.as<uint32_t>(src.n + 1);
-  uint64_t *goff = dst.goff.as<uint64_t>((uint64_t) src.ng + 1);
-  if (src.n)
-  {
-    HIP_CHECK(hipMemcpyAsync(idx, src.idx.get<uint32_t>(), src.n * 4, hipMemcpyDeviceToDevice, st));
-    HIP_CHECK(hipMemcpyAsync(gof, src.gof.get<uint32_t>(), src.n * 4, hipMemcpyDeviceToDevice, st));
-  }
-  HIP_CHECK(hipMemcpyAsync(goff, src.goff.get<uint64_t>(), ((uint64_t) src.ng + 1) * 8, hipMemcpyDeviceToDevice, st));
-  filter_groups(dst, drop, b, st);
-}
-
 // list of the pairs of the groups with keep[g] != 0, straight from the group ranges of the pair table (the pairs of a group are
 // contiguous there): what iota + copy + filter_groups over all n pairs would leave, in one launch over the list itself
 namespace
@@ -601,13 +586,13 @@ void fast_cluster_all(const bk_pair *pairs, PairList &L, double w, DevBuf &clust
 // test hook: mask_pairs_chr_pos (BreakID.cc:1813-1877) on the list in its current order
 void debug_mask_list(const bk_pair *pairs, PairList &L, long dist, ClusterBufs &b, hipStream_t st) { mask_list(pairs, L, dist, b, st); }
 
-// ---- two lanes of chromosome-pair groups (api.hip: bk_mask_and_cluster) -> one list in group order --------------------
+// ---- K lanes of chromosome-pair groups (lanes.hip: bk_mask_and_cluster) -> one list in group order -------------------
 namespace
 {
-__global__ __launch_bounds__(256) void k_merge_goff(const uint64_t *__restrict__ a, const uint64_t *__restrict__ b, uint32_t ng, uint64_t *__restrict__ out)
+__global__ __launch_bounds__(256) void k_merge_goff(const uint64_t *__restrict__ b, uint32_t ng, uint64_t *__restrict__ out)
 {
   uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
-  if (g <= ng) out[g] = a[g] + b[g];  // the lanes own disjoint groups: the offsets add
+  if (g <= ng) out[g] += b[g];  // the lanes own disjoint groups: the offsets add
 }
 __global__ __launch_bounds__(256) void k_merge_copy(const uint32_t *__restrict__ idx, const uint32_t *__restrict__ gof, const uint32_t *__restrict__ cl, const uint64_t *__restrict__ goff,
                                                     uint64_t n, const uint64_t *__restrict__ mgoff, uint32_t *__restrict__ oidx, uint32_t *__restrict__ ogof, uint32_t *__restrict__ ocl)
@@ -634,23 +619,10 @@ void merge_lists_many(const PairList *const *lists, const uint32_t *const *cls, 
   uint64_t *ogoff = out.goff.as<uint64_t>((uint64_t) ng + 1);
   uint32_t *ocl = cl_out ? cl_out->as<uint32_t>(out.n + 1) : nullptr;
   HIP_CHECK(hipMemsetAsync(ogoff, 0, ((size_t) ng + 1) * 8, st));
-  for (int l = 0; l < K; ++l) hipLaunchKernelGGL(k_merge_goff, dim3(cdiv(ng + 1, 256)), dim3(256), 0, st, ogoff, lists[l]->goff.get<uint64_t>(), ng, ogoff);
+  for (int l = 0; l < K; ++l) hipLaunchKernelGGL(k_merge_goff, dim3(cdiv(ng + 1, 256)), dim3(256), 0, st, lists[l]->goff.get<uint64_t>(), ng, ogoff);
   for (int l = 0; l < K; ++l)
   {
     const PairList &A = *lists[l];
     if (A.n) hipLaunchKernelGGL(k_merge_copy, dim3(nb(A.n)), dim3(256), 0, st, A.idx.get<uint32_t>(), A.gof.get<uint32_t>(), cls ? cls[l] : nullptr, A.goff.get<uint64_t>(), A.n, ogoff, oidx, ogof, ocl);
   }
-}
-
-void merge_lists(const PairList &A, const uint32_t *clA, const PairList &B, const uint32_t *clB, PairList &out, DevBuf *cl_out, hipStream_t st)
-{
-  const uint32_t ng = A.ng;
-  out.ng = ng;
-  out.n = A.n + B.n;
-  uint32_t *oidx = out.idx.as<uint32_t>(out.n + 1), *ogof = out.gof.as<uint32_t>(out.n + 1);
-  uint64_t *ogoff = out.goff.as<uint64_t>((uint64_t) ng + 1);
-  uint32_t *ocl = cl_out ? cl_out->as<uint32_t>(out.n + 1) : nullptr;
-  hipLaunchKernelGGL(k_merge_goff, dim3(cdiv(ng + 1, 256)), dim3(256), 0, st, A.goff.get<uint64_t>(), B.goff.get<uint64_t>(), ng, ogoff);
-  if (A.n) hipLaunchKernelGGL(k_merge_copy, dim3(nb(A.n)), dim3(256), 0, st, A.idx.get<uint32_t>(), A.gof.get<uint32_t>(), clA, A.goff.get<uint64_t>(), A.n, ogoff, oidx, ogof, ocl);
-  if (B.n) hipLaunchKernelGGL(k_merge_copy, dim3(nb(B.n)), dim3(256), 0, st, B.idx.get<uint32_t>(), B.gof.get<uint32_t>(), clB, B.goff.get<uint64_t>(), B.n, ogoff, oidx, ogof, ocl);
 }

@@ -43,7 +43,7 @@ struct SortEmuBufs
   DevBuf cnt, err, segs_a, segs_b, posL, posR, scan_tmp, heap_list, heap_scratch, scratch32, scratch32b, fin_list, lv_tile, lv_segbase, lv_tileseg, lv_bar, chk_key0, chk_cnt, chk_bad, rk_a, rk_b, heap_tickets;
   prims::RadixBufs radix;
   // optional observer (host): heavy[g] = largest heapsort segment (elements) any sort through these buffers left to group g's
-  // lone-wave heap kernels - what the lanes of api.hip balance on.  Set by the caller around the sorts it wants recorded.
+  // lone-wave heap kernels - what the lanes of lanes.hip balance on.  Set by the caller around the sorts it wants recorded.
   std::vector<uint32_t> *heavy = nullptr;
   bool heavy_all = false;  // record every segment the level loop left to the heapsort kernels (a group that has one went through all ~2 lg n levels), not only the long ones
   // the three size classes of the heapsort branch run side by side (fork/join around the caller's stream); false: no side stream,

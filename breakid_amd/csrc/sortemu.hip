@@ -3223,7 +3223,7 @@ void std_sort_groups(uint32_t *key, uint32_t *idx, const uint32_t *gof, const ui
   const bool fork_heaps = b.fork_heaps && !one_stream;
   if (!fork_heaps)
   {
-    // one stream, one hardware queue (a lane of api.hip when the process has few queues): the finisher first, then every heap of the
+    // one stream, one hardware queue (a lane of lanes.hip when the process has few queues): the finisher first, then every heap of the
     // sort - the long ones of the level loop, the mid-size ones, the finisher's - in ONE dispatch, so that they still run side by
     // side.  (What the fork below overlaps with the long heaps is the finisher as well: ~0.6 ms per sort that run before them here.)
     if (nfin2[1]) hipLaunchKernelGGL((k_se_finish<FIN_MAX, 256>), dim3(nfin2[1]), dim3(256), 0, st, fin_list + (fin_cap - 1), nfin2[1], -1, key, idx, err, heap_list);

@@ -6,7 +6,7 @@
 // i.e. 1.5-2.8 ms per sort in front of and behind the one thing that is inherently serial (the pops of the longest heap
 // segment).  Here a sort is a set of tasks: a partition node pushes its children, a finished segment counts its elements off the
 // job's `remaining`, the job is done when that reaches zero.  Nothing waits for a launch boundary: the critical path of a sort
-// becomes root partition -> spine -> heap of ITS longest segment, and a lane of groups (api.hip) costs a submit kernel and a wait of
+// becomes root partition -> spine -> heap of ITS longest segment, and a lane of groups (lanes.hip) costs a submit kernel and a wait of
 // its THREAD per sort instead of a hundred launches (the thread polls a word in host memory that the task which counts the job's
 // last elements off writes: a kernel spinning on the lane's stream instead made every other queue's dependent launches 7x slower).
 //
@@ -29,7 +29,7 @@
 // write back every L2.  Queue words, task slots, job descriptors, the error and the quit word are only touched by atomic
 // read-modify-writes, on both sides (svc_read / svc_write below, with what was seen without them).
 // Hardware queues.  The two kernels hold a queue each until the stage ends; what that asks of the process and of the device is
-// handled where the stage starts (api.hip: SvcStage - one stage per device, probes of the stage's streams, the census of the
+// handled where the stage starts (lanes.hip: SvcStage - one stage per device, probes of the stage's streams, the census of the
 // device's compute queues) and where it stops (SortService::stop: the quit word by two routes).
 
 constexpr uint32_t SVC_T_PART = 1, SVC_T_FIN = 2, SVC_T_HEAP = 3;
@@ -1075,7 +1075,7 @@ __device__ __forceinline__ void sj_serve(const SjParams &S, const SvcJobLds &J, 
       svc_drain_barrier(team);
       if (tid == 0)
       {
-        // (what the lanes of api.hip balance on: heaps above FIN_MAX elements are the partition nodes', never the finisher's)
+        // (what the lanes of lanes.hip balance on: heaps above FIN_MAX elements are the partition nodes', never the finisher's)
         if (S.heavy && m > S.heavy_min) atomicMax(S.heavy + S.gof[t.first], m);
         if (S.trace)
         {
