@@ -23,6 +23,8 @@ CLUSTER = np.dtype([("group", "<u4"), ("id", "<i4"), ("p1_tid", "<i4"), ("p2_tid
 GROUP_KEY = np.dtype([("p1_tid", "<i4"), ("p2_tid", "<i4")])
 NORMAL_SUPPORT = np.dtype([("n_drp", "<u4"), ("n_sr", "<u4"), ("depth1", "<u4"), ("depth2", "<u4")])  # struct bk_normal_support
 REF_SUPPORT = np.dtype([("ref_pairs1", "<u4"), ("ref_pairs2", "<u4"), ("ref_reads1", "<u4"), ("ref_reads2", "<u4")])  # struct bk_ref_support
+JUNCTION = np.dtype([("pairs", "<u4", (4,)), ("splits", "<u4", (4,)), ("mapq_sum1", "<u8"), ("mapq_sum2", "<u8")])  # struct bk_junction
+assert JUNCTION.itemsize == 48
 assert PAIR.itemsize == 56 and SPLIT.itemsize == 88 and CLUSTER.itemsize == 72 and NORMAL_SUPPORT.itemsize == 16 and REF_SUPPORT.itemsize == 16
 
 STAGE_DTYPE = {STAGE_SCAN: PAIR, STAGE_ISO: PAIR, STAGE_CLUSTERED: PAIR, STAGE_SPLITS: SPLIT,

@@ -35,7 +35,7 @@ def build(verbose=False):
 
 EXPORTS = ["bk_init", "bk_prepare_process", "bk_free", "bk_last_error", "bk_set_stream", "bk_sync", "bk_get_stream", "bk_upload_records", "bk_exclude_regions", "bk_isize_stats",
            "bk_discordant_pairs", "bk_mask_and_cluster", "bk_split_evidence", "bk_cluster_summary",
-           "bk_split_breakpoints", "bk_normal_support", "bk_ref_support", "bk_genotype_call", "bk_run", "bk_fetch", "bk_timing", "bk_timing_enable", "bk_timing_touched", "bk_group_stats", "bk_qname_hash", "bk_qname_check",
+           "bk_split_breakpoints", "bk_normal_support", "bk_ref_support", "bk_genotype_call", "bk_junctions", "bk_junction_sides", "bk_vcf_breakend_alt", "bk_run", "bk_fetch", "bk_timing", "bk_timing_enable", "bk_timing_touched", "bk_group_stats", "bk_qname_hash", "bk_qname_check",
            "bk_bam_open", "bk_bam_header", "bk_bam_decode", "bk_bam_close", "bk_bam_decode_device", "bk_bam_decode_device_part", "bk_bam_decode_device_ctx", "bk_bam_dev_free", "bk_feed_release_caches", "bk_debug_bgzf_inflate", "bk_debug_std_sort", "bk_sort_forms", "bk_debug_ahc", "bk_debug_points", "bk_debug_cigar", "bk_debug_vote", "bk_debug_region", "bk_shard_begin", "bk_shard_get_stats", "bk_shard_set_stats",
            "bk_shard_sd_local", "bk_shard_sd_finish", "bk_shard_buffer", "bk_shard_set_buffer", "bk_shard_group_sizes",
            "bk_shard_own_groups", "bk_shard_route_candidates", "bk_shard_group_keys", "bk_shard_route_pairs", "bk_shard_group_pairs", "bk_shard_bp_cov", "bk_shard_bp_vote", "bk_shard_bp_vote_slice", "bk_shard_bp_set_voted", "bk_shard_bp_depth", "bk_shard_bp_finish"]
@@ -73,6 +73,9 @@ def lib():
         L.bk_normal_support.argtypes = [vp, vp, C.c_double, C.POINTER(vp), u64p]
         L.bk_ref_support.argtypes = [vp, vp, C.c_int, C.c_int, C.c_double, C.POINTER(vp), u64p]
         L.bk_genotype_call.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), C.POINTER(C.c_float)]
+        L.bk_junctions.argtypes = [vp, C.POINTER(vp), u64p]
+        L.bk_junction_sides.argtypes = [vp, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), C.POINTER(C.c_uint8)]
+        L.bk_vcf_breakend_alt.argtypes = [C.c_char, C.c_int, C.c_char_p, C.c_uint32, C.c_int, C.c_char_p, C.c_size_t]
         L.bk_fetch.argtypes = [vp, C.c_int, C.POINTER(vp), u64p, C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(C.c_uint32)]
         L.bk_timing.argtypes = [vp, C.POINTER(C.POINTER(C.c_char_p)), C.POINTER(C.POINTER(C.c_float)),
                                 C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(C.c_int)]
@@ -140,6 +143,31 @@ def genotype_call(alt, ref):
     if rc != 0:
         raise BreakIDError(rc, "bk_genotype_call")
     return gt.value, gq.value, np.float32(vaf.value)
+
+
+def junction_sides(row):
+    """The library's side rule (bk_junction_sides; no GPU) for one abi.JUNCTION row: (right1, right2, source), source 2 = split
+    reads, 1 = pairs, 0 = no evidence."""
+    a = np.zeros(1, abi.JUNCTION)
+    a[0] = row
+    r1, r2, src = C.c_uint8(), C.c_uint8(), C.c_uint8()
+    rc = lib().bk_junction_sides(a.ctypes.data, C.byref(r1), C.byref(r2), C.byref(src))
+    if rc != 0:
+        raise BreakIDError(rc, "bk_junction_sides")
+    return r1.value, r2.value, src.value
+
+
+def vcf_breakend_alt(ref_base, own_right, mate_chr, mate_pos, mate_right, cap=None):
+    """The ALT text of one VCF breakend (bk_vcf_breakend_alt; no GPU).  cap: the buffer size handed to the library (default: large
+    enough); a buffer that is too small raises BreakIDError(BK_ERR_ARG)."""
+    chrom = mate_chr.encode()
+    if cap is None:
+        cap = len(chrom) + 32
+    buf = C.create_string_buffer(max(int(cap), 1))
+    rc = lib().bk_vcf_breakend_alt(ref_base.encode(), int(bool(own_right)), chrom, int(mate_pos), int(bool(mate_right)), buf, int(cap))
+    if rc != 0:
+        raise BreakIDError(rc, "bk_vcf_breakend_alt")
+    return buf.value.decode()
 
 
 class Context:
@@ -267,6 +295,15 @@ class Context:
             return np.zeros(0, abi.NORMAL_SUPPORT)
         buf = (C.c_char * (n.value * abi.NORMAL_SUPPORT.itemsize)).from_address(data.value)
         return np.frombuffer(buf, dtype=abi.NORMAL_SUPPORT, count=n.value).copy()
+
+    def junctions(self):
+        """Junction evidence of this context's clusters (bk_junctions): one abi.JUNCTION row per STAGE_CLUSTERS row, same order."""
+        data, n = C.c_void_p(), C.c_uint64()
+        self._check(self.L.bk_junctions(self.h, C.byref(data), C.byref(n)))
+        if not n.value:
+            return np.zeros(0, abi.JUNCTION)
+        buf = (C.c_char * (n.value * abi.JUNCTION.itemsize)).from_address(data.value)
+        return np.frombuffer(buf, dtype=abi.JUNCTION, count=n.value).copy()
 
     def ref_support(self, records, mapq_min, anchor, w):
         """Reference-allele evidence of this context's calls on the record table of `records` (bk_ref_support): one abi.REF_SUPPORT

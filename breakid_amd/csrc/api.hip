@@ -13,6 +13,7 @@
 #include "bp.h"
 #include "normal.h"
 #include "genotype.h"
+#include "junction.h"
 #include "exclude.h"
 #include "ahc.h"
 #include "lanes.h"
@@ -118,6 +119,10 @@ struct bk_ctx
   // reference-allele evidence (bk_ref_support: this context holds the calls)
   RefBufs rb;
   std::vector<struct bk_ref_support> f_ref;
+  // junction evidence (bk_junctions); summary_map: bb still holds the slot -> cluster-row map of the last bk_cluster_summary
+  JunctionBufs jnb;
+  std::vector<struct bk_junction> f_junction;
+  bool summary_map = false;
 
   // fetch staging
   std::vector<bk_pair> f_pairs[3];
@@ -725,6 +730,7 @@ int bk_mask_and_cluster(bk_ctx *ctx, double w, int fast, uint64_t *n_clustered)
     // the stage itself, its lanes and its sort service: lanes.hip
     const StageInput in{ctx->device, ctx->st, ctx->jr, ctx->gstart_host, ctx->own_groups,
                         [&](const char *name, const std::function<void()> &body) { Scope s(ctx, name); body(); }};
+    ctx->summary_map = false;
     ctx->stage.run(in, w, fast);
     ctx->clustered = true;
     if (n_clustered) *n_clustered = ctx->stage.list.n;
@@ -748,6 +754,7 @@ int bk_cluster_summary(bk_ctx *ctx, double w, uint64_t *n_clusters)
     Scope s(ctx, "cluster_summary");
     ctx->n_clusters = cluster_summary(ctx->jr.pairs, ctx->stage.list.idx.get<uint32_t>(), ctx->stage.list.gof.get<uint32_t>(), ctx->stage.d_cluster.get<uint32_t>(), ctx->stage.list.n,
                                       ctx->stage.list.ng, ctx->jr.gkey, ctx->d_glex.get<uint32_t>(), ctx->nt, w, ctx->d_clusters, ctx->bb, ctx->st);
+    ctx->summary_map = true;
     if (n_clusters) *n_clusters = ctx->n_clusters;
   });
 }
@@ -919,6 +926,101 @@ int bk_genotype_call(uint32_t alt, uint32_t ref, uint8_t *gt, uint8_t *gq, float
   *gt = (uint8_t) best;
   *gq = (uint8_t) (q < 99.0 ? q : 99.0);
   *vaf = (float) alt / (float) ((uint64_t) alt + ref);
+  return BK_OK;
+}
+
+int bk_junctions(bk_ctx *ctx, const struct bk_junction **out, uint64_t *count)
+{
+  return guarded(ctx, [&] {
+    if (!out || !count) throw bk_error(BK_ERR_ARG, "bk_junctions: null output");
+    if (ctx->shard) throw bk_error(BK_ERR_ARG, "bk_junctions: sharded contexts (bk_shard_*) are not supported");
+    if (!ctx->bp_done || !ctx->clustered || !ctx->summary_map) throw bk_error(BK_ERR_ARG, "bk_junctions: call bk_split_breakpoints first");
+    const uint64_t ncl = ctx->n_clusters;
+    JunctionPairs jp{};
+    if (ncl)  // (no cluster: bk_cluster_summary may have returned before it built the map)
+    {
+      jp.pairs = ctx->jr.pairs;
+      jp.idx = ctx->stage.list.idx.get<uint32_t>();
+      jp.gof = ctx->stage.list.gof.get<uint32_t>();
+      jp.cl = ctx->stage.d_cluster.get<uint32_t>();
+      jp.n = ctx->stage.list.n;
+      jp.ng = ctx->stage.list.ng;
+      jp.slotbase = ctx->bb.slotbase.get<uint32_t>();
+      jp.keep = ctx->bb.keep.get<uint32_t>();
+      jp.off = ctx->bb.off.get<uint32_t>();
+    }
+    struct bk_junction *d_res;
+    uint32_t *d_grp, *d_vis;
+    {
+      // bytes: per list entry its three list words and the four mapq / strand bytes of its pair row (a 32-byte sector of the 56-byte
+      // row is what the load fetches); touched adds the tuples searched and, per cluster, its row read and the result written
+      Scope s(ctx, "junctions", jp.n * (12ull + 4ull));
+      junctions(jp, ctx->d_split.get<bk_split>(), ctx->hc.n_split, ctx->clusters_ptr(), ncl, (int) ctx->hc.max_span, ctx->d_hdr.get<int32_t>(), ctx->names.own_id, ctx->nt,
+                ctx->names.empty_id, ctx->jnb, ctx->st, &d_res, &d_grp, &d_vis);
+    }
+    std::vector<struct bk_junction> res(ncl);
+    std::vector<uint32_t> grp(ncl), vis(ctx->timing ? ncl : 0);
+    if (ncl)
+    {
+      HIP_CHECK(hipMemcpyAsync(res.data(), d_res, ncl * sizeof(struct bk_junction), hipMemcpyDeviceToHost, ctx->st));
+      HIP_CHECK(hipMemcpyAsync(grp.data(), d_grp, ncl * 4, hipMemcpyDeviceToHost, ctx->st));
+      if (ctx->timing) HIP_CHECK(hipMemcpyAsync(vis.data(), d_vis, ncl * 4, hipMemcpyDeviceToHost, ctx->st));
+    }
+    HIP_CHECK(hipStreamSynchronize(ctx->st));
+    if (ctx->timing && !ctx->timers.empty())
+    {
+      uint64_t visited = 0;
+      for (uint32_t v : vis) visited += v;
+      ctx->timers.back().touched = jp.n * (12ull + 32ull) + visited * sizeof(bk_split) + ncl * (sizeof(bk_cluster) + 2ull * sizeof(struct bk_junction) + 8ull);
+    }
+    // device order is (numeric chr-pair key, id); BK_STAGE_CLUSTERS is the stable order by `group` (bk_fetch): a counting sort
+    uint32_t gmax = 0;
+    for (uint32_t g : grp) gmax = std::max(gmax, g);
+    std::vector<uint64_t> start(ncl ? (size_t) gmax + 2 : 1, 0);
+    for (uint32_t g : grp) ++start[g + 1];
+    for (size_t g = 1; g < start.size(); ++g) start[g] += start[g - 1];
+    ctx->f_junction.resize(ncl);
+    for (uint64_t c = 0; c < ncl; ++c) ctx->f_junction[start[grp[c]]++] = res[c];
+    *out = ctx->f_junction.data();
+    *count = ncl;
+  });
+}
+
+// The side rule of one call and the ALT text of one breakend (include/breakid_hip.h): pure host code.
+int bk_junction_sides(const struct bk_junction *j, uint8_t *right1, uint8_t *right2, uint8_t *source)
+{
+  if (!j || !right1 || !right2 || !source) return BK_ERR_ARG;
+  auto largest = [](const uint32_t *v) {
+    int best = 0;
+    for (int i = 1; i < 4; ++i)
+      if (v[i] > v[best]) best = i;
+    return v[best] ? best : -1;
+  };
+  int idx = largest(j->splits);
+  *source = 2;
+  if (idx < 0)
+  {
+    idx = largest(j->pairs);
+    *source = 1;
+  }
+  if (idx < 0)
+  {
+    idx = 1;
+    *source = 0;
+  }
+  *right1 = (uint8_t) (idx >> 1);
+  *right2 = (uint8_t) (idx & 1);
+  return BK_OK;
+}
+
+int bk_vcf_breakend_alt(char ref_base, int own_right, const char *mate_chr, uint32_t mate_pos, int mate_right, char *buf, size_t cap)
+{
+  if (!mate_chr || !buf) return BK_ERR_ARG;
+  const char br = mate_right ? '[' : ']';
+  const std::string mate = br + std::string(mate_chr) + ":" + std::to_string(mate_pos) + br;
+  const std::string alt = own_right ? mate + ref_base : ref_base + mate;
+  if (alt.size() + 1 > cap) return BK_ERR_ARG;
+  std::memcpy(buf, alt.c_str(), alt.size() + 1);
   return BK_OK;
 }
 

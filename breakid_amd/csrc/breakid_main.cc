@@ -33,6 +33,10 @@ extern "C" int bk_normal_support(bk_ctx *tumor, bk_ctx *normal, double w, const 
 extern "C" int bk_ref_support(bk_ctx *calls, bk_ctx *records, int mapq_min, int anchor, double w, const struct bk_ref_support **out, uint64_t *count)
     __attribute__((weak));
 extern "C" int bk_genotype_call(uint32_t alt, uint32_t ref, uint8_t *gt, uint8_t *gq, float *vaf) __attribute__((weak));
+// -vcf: the same for the junction evidence and the two breakend rules (the CPU build refuses -vcf)
+extern "C" int bk_junctions(bk_ctx *ctx, const struct bk_junction **out, uint64_t *count) __attribute__((weak));
+extern "C" int bk_junction_sides(const struct bk_junction *j, uint8_t *right1, uint8_t *right2, uint8_t *source) __attribute__((weak));
+extern "C" int bk_vcf_breakend_alt(char ref_base, int own_right, const char *mate_chr, uint32_t mate_pos, int mate_right, char *buf, size_t cap) __attribute__((weak));
 // -x: the same for the exclude list (the CPU build refuses -x)
 extern "C" int bk_exclude_regions(bk_ctx *ctx, const bk_regions *r, uint64_t *n_removed) __attribute__((weak));
 extern "C" int bk_multi_run_ex(const bk_soa *host_table, const uint32_t *target_len, const char *const *target_name, int n_targets, const bk_regions *exclude, int n_gpus,
@@ -269,7 +273,8 @@ static const char *HELP =
      \t -all       \t no filter enspan out [default is filter]  \n \
      \t -x         \t exclude list (BED: contig [start end]); records that overlap it are ignored  \n \
      \t -genotype  \t count reference-allele evidence and genotype every call (twin files *_genotype.txt)  \n \
-     \t -anchor    \t bases a reference read must cover on either side of a breakpoint (with -genotype)  [10]\n ";
+     \t -anchor    \t bases a reference read must cover on either side of a breakpoint (with -genotype)  [10]\n \
+     \t -vcf       \t also write the calls as VCF breakends (*_fusion.vcf)  \n ";
 
 // ---- RefSeqTranscript.{h,cc} -------------------------------------------------------------------------------
 struct Txpt
@@ -535,6 +540,139 @@ static const char *GENOTYPE_COLUMNS = "\tRef_Pairs1\tRef_Pairs2\tRef_Reads1\tRef
 static const char *GENOTYPE_COLUMNS_NORMAL =
     "\tNormal_Ref_Pairs1\tNormal_Ref_Pairs2\tNormal_Ref_Reads1\tNormal_Ref_Reads2\tNormal_VAF_Pairs\tNormal_VAF_Reads\tNormal_GT\tNormal_GQ";
 
+// ---- -vcf: the calls of the fusion files as VCF 4.2 breakends (section 5.4), two records per call ------------------------------
+struct VcfInput
+{
+  int nt = 0;
+  const char *const *names = nullptr;
+  const uint32_t *lens = nullptr;
+  string nib_dir;
+  bool all = false;                                   // -all: the rows of _fusion_all.txt, the filtered ones with a FILTER
+  const vector<struct bk_junction> *jsup = nullptr;   // per BK_STAGE_CLUSTERS row
+  bool with_normal = false;                           // -normal: a NORMAL sample column from nsup
+  const struct bk_normal_support *nsup = nullptr;
+  uint64_t n_nsup = 0;
+  const vector<struct bk_ref_support> *gsup = nullptr, *gsup_normal = nullptr;  // -genotype (else null): GT:GQ:DR:DV:RR:RV
+};
+
+static char nib_base(const string &nib_dir, const string &chr, long pos1)  // the base at a 1-based position; N without a file or beyond it
+{
+  char b = 'N';
+  if (pos1 < 1) return b;
+  Nib n;
+  n.open(nib_dir + "/hg19_" + chr + ".nib");
+  n.base(&b, (unsigned long) (pos1 - 1));
+  return b;
+}
+
+static string vcf_info_text(string s)  // an INFO value holds no blank, ';', '=' or ','
+{
+  for (char &c : s)
+    if (c == ' ' || c == '\t' || c == ';' || c == '=' || c == ',') c = '_';
+  return s.empty() ? "." : s;
+}
+
+// one sample column: DV:RV, or with the reference-allele counts GT:GQ:DR:DV:RR:RV (GT / GQ as in the *_genotype.txt twins: the call
+// is genotyped on its junction reads; DR / RR are the counts of the record's own side)
+static string vcf_sample(uint32_t n_drp, uint32_t n_sr, const struct bk_ref_support *rs, int side)
+{
+  std::ostringstream o;
+  if (rs)
+  {
+    uint8_t gt = 255, gq = 0;
+    float vaf = 0;
+    bk_genotype_call(n_sr, (uint32_t) (((uint64_t) rs->ref_reads1 + rs->ref_reads2 + 1) / 2), &gt, &gq, &vaf);
+    o << (gt == 0 ? "0/0" : gt == 1 ? "0/1" : gt == 2 ? "1/1" : "./.") << ":" << (int) gq << ":" << (side ? rs->ref_pairs2 : rs->ref_pairs1) << ":" << n_drp << ":"
+      << (side ? rs->ref_reads2 : rs->ref_reads1) << ":" << n_sr;
+  }
+  else
+    o << n_drp << ":" << n_sr;
+  return o.str();
+}
+
+struct VcfRecord
+{
+  int tid;
+  uint32_t pos;
+  string id, line;
+};
+
+// false when an evidence table lacks a row of a call (nothing is written then)
+static bool write_vcf(const string &path, const vector<OutRow> &rows, const VcfInput &in)
+{
+  vector<VcfRecord> recs;
+  for (const OutRow &r : rows)
+  {
+    const bool all_ok = r.c.n_sr > 0 && r.c.p1_exact != 0xFFFFFFFFu && r.c.p2_exact != -1;
+    const bool no_gene_pair = (r.g1 == "intergenic" && r.g2 == "intergenic") || r.g1 == r.g2;
+    const bool filt_ok = all_ok && !no_gene_pair && !r.is_rpt;
+    if (!all_ok || (!in.all && !filt_ok)) continue;
+    if (r.idx >= in.jsup->size() || (in.with_normal && r.idx >= in.n_nsup) || (in.gsup && r.idx >= in.gsup->size()) || (in.gsup_normal && r.idx >= in.gsup_normal->size()))
+      return false;
+    const struct bk_junction &j = (*in.jsup)[r.idx];
+    uint8_t right[2] = {0, 1}, source = 0;
+    bk_junction_sides(&j, &right[0], &right[1], &source);
+    const uint64_t n_members = (uint64_t) j.pairs[0] + j.pairs[1] + j.pairs[2] + j.pairs[3];
+    string filter = "PASS";
+    if (!filt_ok) filter = no_gene_pair ? (r.is_rpt ? "NoGenePair;Repeat" : "NoGenePair") : "Repeat";
+    const string id = "bk" + std::to_string(r.idx);
+    for (int s = 0; s < 2; ++s)
+    {
+      const string &chr = s ? r.p2_chr : r.p1_chr, &mate_chr = s ? r.p1_chr : r.p2_chr;
+      const uint32_t pos = s ? (uint32_t) r.c.p2_exact : r.c.p1_exact, mate_pos = s ? r.c.p1_exact : (uint32_t) r.c.p2_exact;
+      const char ref = nib_base(in.nib_dir, chr, (long) pos);
+      vector<char> alt(mate_chr.size() + 32);
+      if (bk_vcf_breakend_alt(ref, right[s], mate_chr.c_str(), mate_pos, right[1 - s], alt.data(), alt.size()) != BK_OK) return false;
+      std::ostringstream o;
+      o << chr << "\t" << pos << "\t" << id << "_" << s + 1 << "\t" << ref << "\t" << alt.data() << "\t.\t" << filter << "\t";
+      o << "SVTYPE=BND;MATEID=" << id << "_" << 2 - s << ";EVENTTYPE=" << fusion_type(r.c.type_mask) << ";PE=" << r.c.n_drp << ";SR=" << r.c.n_sr
+        << ";MAPQ=" << (n_members ? (s ? j.mapq_sum2 : j.mapq_sum1) / n_members : 0) << ";DP=" << (s ? r.c.depth2 : r.c.depth1) << ";GENE=" << vcf_info_text(s ? r.g2 : r.g1)
+        << ";SIDES=" << (source == 2 ? "SR" : source == 1 ? "PE" : "NONE");
+      o << "\t" << (in.gsup ? "GT:GQ:DR:DV:RR:RV" : "DV:RV") << "\t" << vcf_sample(r.c.n_drp, r.c.n_sr, in.gsup ? &(*in.gsup)[r.idx] : nullptr, s);
+      if (in.with_normal) o << "\t" << vcf_sample(in.nsup[r.idx].n_drp, in.nsup[r.idx].n_sr, in.gsup_normal ? &(*in.gsup_normal)[r.idx] : nullptr, s);
+      o << "\n";
+      VcfRecord rec;
+      rec.tid = s ? r.c.p2_tid : r.c.p1_tid;
+      rec.pos = pos;
+      rec.id = id + "_" + std::to_string(s + 1);
+      rec.line = o.str();
+      recs.push_back(rec);
+    }
+  }
+  std::sort(recs.begin(), recs.end(), [](const VcfRecord &a, const VcfRecord &b) {
+    if (a.tid != b.tid) return a.tid < b.tid;
+    if (a.pos != b.pos) return a.pos < b.pos;
+    return a.id < b.id;
+  });
+  std::ofstream v(path.c_str());
+  // no date and no command line: two runs write the same bytes
+  v << "##fileformat=VCFv4.2\n##source=BreakID\n";
+  for (int t = 0; t < in.nt; ++t) v << "##contig=<ID=" << in.names[t] << ",length=" << in.lens[t] << ">\n";
+  v << "##INFO=<ID=SVTYPE,Number=1,Type=String,Description=\"Type of structural variant\">\n"
+       "##INFO=<ID=MATEID,Number=1,Type=String,Description=\"ID of the mate breakend\">\n"
+       "##INFO=<ID=EVENTTYPE,Number=1,Type=String,Description=\"Fusion_Type of the call in the fusion tables\">\n"
+       "##INFO=<ID=PE,Number=1,Type=Integer,Description=\"Discordant read pairs of the call (N_DRP)\">\n"
+       "##INFO=<ID=SR,Number=1,Type=Integer,Description=\"Split reads of the call (N_SR)\">\n"
+       "##INFO=<ID=MAPQ,Number=1,Type=Integer,Description=\"Mean mapping quality of the member pairs' reads on this side\">\n"
+       "##INFO=<ID=DP,Number=1,Type=Integer,Description=\"Read depth at this breakpoint\">\n"
+       "##INFO=<ID=GENE,Number=1,Type=String,Description=\"Gene at this breakpoint, or intergenic\">\n"
+       "##INFO=<ID=SIDES,Number=1,Type=String,Description=\"Evidence the breakend orientation comes from: SR split reads, PE read pairs, NONE\">\n";
+  if (in.gsup)
+    v << "##FORMAT=<ID=GT,Number=1,Type=String,Description=\"Genotype\">\n"
+         "##FORMAT=<ID=GQ,Number=1,Type=Integer,Description=\"Genotype quality\">\n"
+         "##FORMAT=<ID=DR,Number=1,Type=Integer,Description=\"Reference read pairs that span this breakpoint\">\n";
+  v << "##FORMAT=<ID=DV,Number=1,Type=Integer,Description=\"Discordant read pairs that support the call\">\n";
+  if (in.gsup) v << "##FORMAT=<ID=RR,Number=1,Type=Integer,Description=\"Reference reads across this breakpoint\">\n";
+  v << "##FORMAT=<ID=RV,Number=1,Type=Integer,Description=\"Split reads that support the call\">\n";
+  v << "##FILTER=<ID=PASS,Description=\"All filters passed\">\n";
+  if (in.all)
+    v << "##FILTER=<ID=NoGenePair,Description=\"Both sides intergenic, or both in the same gene\">\n"
+         "##FILTER=<ID=Repeat,Description=\"A homopolymer run above 10 in the sequence next to a breakpoint\">\n";
+  v << "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\tTUMOR" << (in.with_normal ? "\tNORMAL" : "") << "\n";
+  for (const VcfRecord &rec : recs) v << rec.line;
+  return v.good();
+}
+
 // one input BAM: its decoded table (host or device) and, once created, its context
 struct Sample
 {
@@ -568,10 +706,10 @@ int main(int argc, char *argv[])
   static struct option longopts[] = {{"help", 0, 0, 'h'}, {"i", 1, 0, 1}, {"o", 1, 0, 2}, {"q", 1, 0, 3}, {"n", 1, 0, 4},
                                      {"fast", 0, 0, 5},   {"t", 0, 0, 6}, {"all", 0, 0, 7}, {"gpu", 1, 0, 8}, {"gpus", 1, 0, 9},
                                      {"comm", 1, 0, 10},  {"normal", 1, 0, 11}, {"x", 1, 0, 12}, {"genotype", 0, 0, 13},
-                                     {"anchor", 1, 0, 14}, {0, 0, 0, 0}};
+                                     {"anchor", 1, 0, 14}, {"vcf", 0, 0, 15}, {0, 0, 0, 0}};
   string inp_file, out_file, nib_dir, normal_file, exclude_file, build = "hg19";
   int qual = 20, device = 0, n_gpus = 0, transport = BK_TRANSPORT_AUTO;  // -gpus N: one sample over N GPUs (include/breakid_multi.h)
-  bool fast = false, filter = true, genotype = false, anchor_given = false;
+  bool fast = false, filter = true, genotype = false, anchor_given = false, vcf = false;
   long anchor = 10;  // -anchor: bases a reference read must cover on either side of the breakpoint base
   int opt, li;
   optind = 0;
@@ -597,6 +735,7 @@ int main(int argc, char *argv[])
       anchor = atol(optarg);
       anchor_given = true;
       break;
+    case 15: vcf = true; break;
     default: std::cerr << "Error: cannot parse arguments.\n"; exit(1);
     }
   }
@@ -650,6 +789,19 @@ int main(int argc, char *argv[])
     if (!bk_ref_support || !bk_genotype_call)
     {
       std::cerr << "Error: -genotype needs the GPU library" << std::endl;
+      exit(1);
+    }
+  }
+  if (vcf)
+  {
+    if (n_gpus >= 1)
+    {
+      std::cerr << HELP << "Error: -vcf cannot be combined with -gpus.\n";
+      exit(1);
+    }
+    if (!bk_junctions || !bk_junction_sides || !bk_vcf_breakend_alt)
+    {
+      std::cerr << "Error: -vcf needs the GPU library" << std::endl;
       exit(1);
     }
   }
@@ -921,6 +1073,15 @@ int main(int argc, char *argv[])
       gsup_normal.assign(rs, rs + n_rs);
     }
   }
+  // -vcf: the junction evidence of every call (member pairs by strands, split tuples by clip side)
+  vector<struct bk_junction> jsup;
+  if (vcf)
+  {
+    const struct bk_junction *js = nullptr;
+    uint64_t n_js = 0;
+    if ((rc = bk_junctions(ctx, &js, &n_js)) != BK_OK) die(rc);
+    jsup.assign(js, js + n_js);
+  }
   const void *data = nullptr;
   uint64_t cnt = 0;
   if ((rc = bk_fetch(ctx, BK_STAGE_CLUSTERS, &data, &cnt, nullptr, nullptr)) != BK_OK) die(rc);
@@ -1032,6 +1193,26 @@ int main(int argc, char *argv[])
     if (!filter) out_g.close();
     outf_g.close();
   }
+  if (vcf)
+  {
+    VcfInput vi;
+    vi.nt = nt;
+    vi.names = names;
+    vi.lens = lens;
+    vi.nib_dir = nib_dir;
+    vi.all = !filter;
+    vi.jsup = &jsup;
+    vi.with_normal = with_normal;
+    vi.nsup = nsup;
+    vi.n_nsup = n_nsup;
+    vi.gsup = genotype ? &gsup : nullptr;
+    vi.gsup_normal = genotype && with_normal ? &gsup_normal : nullptr;
+    if (!write_vcf(out_file + "_fusion.vcf", rows, vi))
+    {
+      std::cerr << "Error: cannot write " << out_file << "_fusion.vcf: the evidence tables do not cover every call" << std::endl;
+      exit(1);
+    }
+  }
   {
     std::ofstream p((out_file + "_params.txt").c_str());  // write_enspan_params :1170-1182
     p << "ENSPAN" << std::endl;
@@ -1043,6 +1224,7 @@ int main(int argc, char *argv[])
     if (exclude) p << "exclude_file\t" << exclude_file << std::endl;
     if (!normal_file.empty()) p << "normal_file\t" << normal_file << std::endl;
     if (genotype) p << "genotype_anchor\t" << anchor << std::endl;
+    if (vcf) p << "vcf\t1" << std::endl;
   }
   clock_t end = clock();
   std::cout << "the fusion process of file " << inp_file << "  costs time: " << (end - start) / double(CLOCKS_PER_SEC) << " seconds" << std::endl;

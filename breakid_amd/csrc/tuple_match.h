@@ -1,0 +1,75 @@
+// The tuple search shared by bk_normal_support's n_sr (normal.hip) and bk_junctions' splits[] (junction.hip): the split-evidence
+// tuples that carry a voted cluster's breakpoint pair.  One wavefront per cluster; every lane calls with the same arguments.
+#pragma once
+#include "bk_common.h"
+#include "bp.h"
+
+__device__ __forceinline__ bool near2(uint32_t bp, long long exact)
+{
+  const long long d = (long long) bp - exact;
+  return d >= -2 && d <= 2;
+}
+// first tuple with (tid, pos) >= (T, P): the tuples are in record order = coordinate order (bp.hip: split_lower_pos)
+__device__ __forceinline__ uint64_t tuple_lower(const bk_split *__restrict__ sp, uint64_t ns, int32_t T, long long P)
+{
+  const uint32_t Tu = (uint32_t) T;
+  return wave_lower(0, ns, [&](uint64_t m) {
+    const uint32_t t = (uint32_t) sp[m].tid;
+    return t != Tu ? (t < Tu) : ((long long) sp[m].pos < P);
+  });
+}
+// Only tuples whose own record lies on the call's chromosomes (p1_tid, p2_tid) count: the tuples the vote itself looks at.  A
+// matching tuple's own alignment carries one of its two breakpoints (prim_* of a primary record, sec_* of a 0x100 one,
+// stream.hip), and that breakpoint lies inside the alignment: the record starts in [e - 2 - maxspan, e + 2] around the exact
+// breakpoint e it is compared with.  The own side's chromosome id is own_id[tid] (the reference's chromID2ChrName of the tid), so
+// a record on chromosome T can stand for p1 (around p1_exact) when own_id[T] == c1 and for p2 (around p2_exact) when own_id[T] ==
+// c2: up to four ranges, (p1_tid | p2_tid) x (p1_exact | p2_exact); two for a header that lists chr1..chr22, chrX, chrY first and
+// in that order (own_id[T] == c(T)).  A range skips the indices of the ranges before it: a tuple is visited once.
+// `hit(s, swapped)` runs on the lane that holds a matching tuple s: swapped == false when (prim, sec) is (p1, p2), true when it is
+// (p2, p1) and not also (p1, p2).  Returns the number of tuples the wave looked at (the same value on every lane).
+template <class Hit>
+__device__ __forceinline__ uint32_t for_matching_tuples(const bk_split *__restrict__ sp, uint64_t nsp, const bk_cluster &k, int maxspan,
+                                                        const int32_t *__restrict__ hdr_id, const int32_t *__restrict__ own_id, int32_t nt, int32_t empty_id, Hit hit)
+{
+  const int lane = threadIdx.x & 63;
+  const long long e1 = (long long) k.p1_exact, e2 = (long long) k.p2_exact;
+  const int32_t c1 = hdr_id[k.p1_tid + 1], c2 = hdr_id[k.p2_tid + 1];  // interned chromosome ids, as the vote compares them (k_bp_vote)
+  uint64_t lo[4], hi[4];
+  bool on[4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q)
+  {
+    const int32_t T = (q >> 1) ? k.p2_tid : k.p1_tid;  // the tuple's own record lies on T ...
+    const long long e = (q & 1) ? e2 : e1;           // ... and its own breakpoint is compared with e
+    const int32_t own = (T >= 0 && T < nt) ? own_id[T] : empty_id;
+    on[q] = own == ((q & 1) ? c2 : c1) && !((q >> 1) && k.p1_tid == k.p2_tid);  // (one chromosome: q = 2, 3 repeat q = 0, 1)
+    lo[q] = hi[q] = 0;
+    if (on[q])
+    {
+      lo[q] = tuple_lower(sp, nsp, T, e - 2 - maxspan);
+      hi[q] = tuple_lower(sp, nsp, T, e + 3);
+    }
+  }
+  uint32_t visited = 0;
+#pragma unroll
+  for (int q = 0; q < 4; ++q)
+  {
+    visited += hi[q] > lo[q] ? (uint32_t) (hi[q] - lo[q]) : 0u;
+    for (uint64_t t = lo[q] + lane; t < hi[q]; t += 64)
+    {
+      bool seen = false;
+#pragma unroll
+      for (int p = 0; p < q; ++p) seen |= t >= lo[p] && t < hi[p];
+      if (seen) continue;
+      const bk_split &s = sp[t];
+      if (s.flags & 2u) continue;  // "error cigar" tuple
+      const int32_t pc = s.prim_chr, sc = s.sec_chr;
+      const uint32_t pb = s.prim_bp, sb = s.sec_bp;
+      if (pc == c1 && sc == c2 && near2(pb, e1) && near2(sb, e2))
+        hit(s, false);
+      else if (pc == c2 && sc == c1 && near2(pb, e2) && near2(sb, e1))
+        hit(s, true);
+    }
+  }
+  return visited;
+}

@@ -252,6 +252,42 @@ int bk_ref_support(bk_ctx *calls, bk_ctx *records, int mapq_min, int anchor, dou
  * the pair counts stand beside it: n_drp against (ref_pairs1 + ref_pairs2 + 1) / 2.  BK_ERR_ARG for a null output. */
 int bk_genotype_call(uint32_t alt, uint32_t ref, uint8_t *gt, uint8_t *gq, float *vaf);
 
+/* ---- junction evidence: which side of each breakpoint the retained sequence lies on (what a VCF breakend must say) -------
+ * One row per BK_STAGE_CLUSTERS row, same order.
+ *   Member pairs of a cluster c are the rows of BK_STAGE_CLUSTERED with group == c.group && cluster == c.id.
+ *     pairs[2 * p1_rev + p2_rev] counts them, mapq_sum1 / mapq_sum2 add their p1_mapq / p2_mapq.  Every row gets these, voted or
+ *     not, so pairs[0] + pairs[1] + pairs[2] + pairs[3] == n_drp.  A forward-strand read lies left of its breakpoint, a
+ *     reverse-strand read right of it.
+ *   Matching tuples, voted clusters only (flags bit 1; zeros otherwise): exactly the set bk_normal_support.n_sr is defined over,
+ *     but on the context's own BK_STAGE_SPLITS: tuples whose own record lies on p1_tid or p2_tid, without the "error cigar" flag,
+ *     whose (prim_chr, prim_bp, sec_chr, sec_bp) is within +-2 bp of (p1 chromosome, p1_exact, p2 chromosome, p2_exact) - then side
+ *     1 is prim and side 2 is sec - or else of (p2 chromosome, p2_exact, p1 chromosome, p1_exact) - then side 1 is sec and side 2
+ *     is prim; chromosomes compared as interned ids, as there; when both hold the first wins; the unit is tuples, each counted once.
+ *     A side is RIGHT when its *_bp == *_start (the alignment begins at the breakpoint and extends to the right: a leading clip),
+ *     otherwise LEFT (*_bp == *_end).  splits[2 * right1 + right2] counts them, so the four bins sum to the n_sr that
+ *     bk_normal_support reports for a normal that holds the same table.
+ * The struct has no typedef: the name belongs to the call below. */
+struct bk_junction {
+  uint32_t pairs[4];    /* member pairs of the cluster by strands, index = 2 * p1_rev + p2_rev */
+  uint32_t splits[4];   /* matching split tuples by clip side, index = 2 * right1 + right2; voted clusters only, else 0 */
+  uint64_t mapq_sum1, mapq_sum2;   /* sums of p1_mapq / p2_mapq over the member pairs */
+};                      /* 48 bytes */
+/* ctx: after bk_split_breakpoints, with the lists of its bk_mask_and_cluster / bk_cluster_summary still in place; not a shard
+ * (bk_shard_*).  *out: library-owned until the next call or bk_free(ctx).  BK_ERR_ARG (with the reason in bk_last_error) for wrong
+ * call order, null outputs and shards.  It changes nothing a later bk_fetch or stage returns, and works on every table form the
+ * context can hold.  A context without clusters is no error: *count = 0. */
+int bk_junctions(bk_ctx *ctx, const struct bk_junction **out, uint64_t *count);
+/* Pure host functions (no context, no GPU), so that every caller shares one rule.
+ * bk_junction_sides: which side of each breakpoint the retained sequence lies on.  If any splits[] is non-zero: the index of the
+ * largest splits[] bin, *source = 2; else if any pairs[] is non-zero: the index of the largest pairs[] bin, *source = 1 (the index
+ * means the same: forward = left, reverse = right); else index 1, *source = 0.  The smallest index wins a tie.
+ * *right1 = index >> 1, *right2 = index & 1.  BK_ERR_ARG for a null argument. */
+int bk_junction_sides(const struct bk_junction *j, uint8_t *right1, uint8_t *right2, uint8_t *source);
+/* bk_vcf_breakend_alt: the ALT text of one breakend (VCF 4.2, section 5.4) into buf, NUL-terminated.  Own side left: the base
+ * comes first; mate right: '[', mate left: ']'.  (own, mate) = (left, right): N[chr:pos[, (left, left): N]chr:pos], (right, left):
+ * ]chr:pos]N, (right, right): [chr:pos[N.  BK_ERR_ARG for a null mate_chr or buf, or a buffer too small for the text and its NUL. */
+int bk_vcf_breakend_alt(char ref_base, int own_right, const char *mate_chr, uint32_t mate_pos, int mate_right, char *buf, size_t cap);
+
 /* Copy a stage's result to library-owned host memory.  *data stays valid until the next bk_fetch
  * of the same stage or bk_free.  group_off (may be NULL) receives n_groups+1 offsets for pair stages. */
 int bk_fetch(bk_ctx *ctx, int stage, const void **data, uint64_t *count, const uint64_t **group_off, uint32_t *n_groups);
