@@ -25,6 +25,11 @@ NORMAL_SUPPORT = np.dtype([("n_drp", "<u4"), ("n_sr", "<u4"), ("depth1", "<u4"),
 REF_SUPPORT = np.dtype([("ref_pairs1", "<u4"), ("ref_pairs2", "<u4"), ("ref_reads1", "<u4"), ("ref_reads2", "<u4")])  # struct bk_ref_support
 JUNCTION = np.dtype([("pairs", "<u4", (4,)), ("splits", "<u4", (4,)), ("mapq_sum1", "<u8"), ("mapq_sum2", "<u8")])  # struct bk_junction
 assert JUNCTION.itemsize == 48
+EV_PAIR, EV_SPLIT = 1, 2
+EVIDENCE = np.dtype([("rec", "<u8"), ("qhash", "<u8"), ("qcheck", "<u4"), ("call", "<u4"), ("tid1", "<i4"), ("pos1", "<u4"), ("tid2", "<i4"),
+                     ("pos2", "<u4"), ("flag1", "<u2"), ("flag2", "<u2"), ("mapq1", "u1"), ("mapq2", "u1"), ("kind", "u1"), ("sides", "u1")])  # struct bk_evidence
+READ_KEY = np.dtype([("qhash", "<u8"), ("qcheck", "<u4"), ("tag", "<u4")])  # bk_read_key
+assert EVIDENCE.itemsize == 48 and READ_KEY.itemsize == 16
 assert PAIR.itemsize == 56 and SPLIT.itemsize == 88 and CLUSTER.itemsize == 72 and NORMAL_SUPPORT.itemsize == 16 and REF_SUPPORT.itemsize == 16
 
 STAGE_DTYPE = {STAGE_SCAN: PAIR, STAGE_ISO: PAIR, STAGE_CLUSTERED: PAIR, STAGE_SPLITS: SPLIT,

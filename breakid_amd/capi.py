@@ -35,8 +35,8 @@ def build(verbose=False):
 
 EXPORTS = ["bk_init", "bk_prepare_process", "bk_free", "bk_last_error", "bk_set_stream", "bk_sync", "bk_get_stream", "bk_upload_records", "bk_exclude_regions", "bk_isize_stats",
            "bk_discordant_pairs", "bk_mask_and_cluster", "bk_split_evidence", "bk_cluster_summary",
-           "bk_split_breakpoints", "bk_normal_support", "bk_ref_support", "bk_genotype_call", "bk_junctions", "bk_junction_sides", "bk_vcf_breakend_alt", "bk_run", "bk_fetch", "bk_timing", "bk_timing_enable", "bk_timing_touched", "bk_group_stats", "bk_qname_hash", "bk_qname_check",
-           "bk_bam_open", "bk_bam_header", "bk_bam_decode", "bk_bam_close", "bk_bam_decode_device", "bk_bam_decode_device_part", "bk_bam_decode_device_ctx", "bk_bam_dev_free", "bk_feed_release_caches", "bk_debug_bgzf_inflate", "bk_debug_std_sort", "bk_sort_forms", "bk_debug_ahc", "bk_debug_points", "bk_debug_cigar", "bk_debug_vote", "bk_debug_region", "bk_shard_begin", "bk_shard_get_stats", "bk_shard_set_stats",
+           "bk_split_breakpoints", "bk_normal_support", "bk_ref_support", "bk_genotype_call", "bk_junctions", "bk_junction_sides", "bk_vcf_breakend_alt", "bk_evidence", "bk_run", "bk_fetch", "bk_timing", "bk_timing_enable", "bk_timing_touched", "bk_group_stats", "bk_qname_hash", "bk_qname_check",
+           "bk_bam_open", "bk_bam_header", "bk_bam_decode", "bk_bam_close", "bk_bam_extract", "bk_bam_names_free", "bk_bam_decode_device", "bk_bam_decode_device_part", "bk_bam_decode_device_ctx", "bk_bam_dev_free", "bk_feed_release_caches", "bk_debug_bgzf_inflate", "bk_debug_std_sort", "bk_sort_forms", "bk_debug_ahc", "bk_debug_points", "bk_debug_cigar", "bk_debug_vote", "bk_debug_region", "bk_shard_begin", "bk_shard_get_stats", "bk_shard_set_stats",
            "bk_shard_sd_local", "bk_shard_sd_finish", "bk_shard_buffer", "bk_shard_set_buffer", "bk_shard_group_sizes",
            "bk_shard_own_groups", "bk_shard_route_candidates", "bk_shard_group_keys", "bk_shard_route_pairs", "bk_shard_group_pairs", "bk_shard_bp_cov", "bk_shard_bp_vote", "bk_shard_bp_vote_slice", "bk_shard_bp_set_voted", "bk_shard_bp_depth", "bk_shard_bp_finish"]
 
@@ -76,6 +76,7 @@ def lib():
         L.bk_junctions.argtypes = [vp, C.POINTER(vp), u64p]
         L.bk_junction_sides.argtypes = [vp, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), C.POINTER(C.c_uint8)]
         L.bk_vcf_breakend_alt.argtypes = [C.c_char, C.c_int, C.c_char_p, C.c_uint32, C.c_int, C.c_char_p, C.c_size_t]
+        L.bk_evidence.argtypes = [vp, C.POINTER(vp), u64p, C.POINTER(C.POINTER(C.c_uint64))]
         L.bk_fetch.argtypes = [vp, C.c_int, C.POINTER(vp), u64p, C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(C.c_uint32)]
         L.bk_timing.argtypes = [vp, C.POINTER(C.POINTER(C.c_char_p)), C.POINTER(C.POINTER(C.c_float)),
                                 C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(C.c_int)]
@@ -116,6 +117,9 @@ def lib():
         L.bk_bam_header.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.POINTER(C.c_char_p)), C.POINTER(C.POINTER(C.c_uint32))]
         L.bk_bam_decode.argtypes = [vp, C.POINTER(abi.Soa), C.c_char_p, C.c_size_t]
         L.bk_bam_close.argtypes = [vp]
+        L.bk_bam_extract.argtypes = [C.c_char_p, C.c_char_p, vp, C.c_uint64, C.POINTER(C.c_char_p), C.c_uint64, C.POINTER(vp), u64p, C.c_char_p, C.c_size_t]
+        L.bk_bam_names_free.argtypes = [vp]
+        L.bk_bam_names_free.restype = None
         L.bk_bam_decode_device.argtypes = [C.c_char_p, C.c_int, C.POINTER(vp), C.POINTER(abi.Soa), C.POINTER(C.c_int), C.POINTER(C.POINTER(C.c_char_p)),
                                            C.POINTER(C.POINTER(C.c_uint32)), C.c_char_p, C.c_size_t]
         L.bk_bam_decode_device_part.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_int, C.POINTER(vp), C.POINTER(abi.Soa), C.POINTER(C.c_int), C.POINTER(C.POINTER(C.c_char_p)),
@@ -305,6 +309,19 @@ class Context:
         buf = (C.c_char * (n.value * abi.JUNCTION.itemsize)).from_address(data.value)
         return np.frombuffer(buf, dtype=abi.JUNCTION, count=n.value).copy()
 
+    def evidence(self):
+        """The reads behind this context's clusters (bk_evidence): (rows, call_off) with one abi.EVIDENCE row per member pair and per
+        matching split tuple, ordered by call, and call_off[c] .. call_off[c + 1] the rows of STAGE_CLUSTERS row c."""
+        data, n, off = C.c_void_p(), C.c_uint64(), C.POINTER(C.c_uint64)()
+        self._check(self.L.bk_evidence(self.h, C.byref(data), C.byref(n), C.byref(off)))
+        rows = np.zeros(0, abi.EVIDENCE)
+        if n.value:
+            buf = (C.c_char * (n.value * abi.EVIDENCE.itemsize)).from_address(data.value)
+            rows = np.frombuffer(buf, dtype=abi.EVIDENCE, count=n.value).copy()
+        d2, ncl = C.c_void_p(), C.c_uint64()  # call_off has one entry more than STAGE_CLUSTERS has rows
+        self._check(self.L.bk_fetch(self.h, abi.STAGE_CLUSTERS, C.byref(d2), C.byref(ncl), None, None))
+        return rows, np.ctypeslib.as_array(off, shape=(ncl.value + 1,)).copy()
+
     def ref_support(self, records, mapq_min, anchor, w):
         """Reference-allele evidence of this context's calls on the record table of `records` (bk_ref_support): one abi.REF_SUPPORT
         row per STAGE_CLUSTERS row.  `records`: this context itself, or a Context on the same device and reference list (the
@@ -486,6 +503,30 @@ def decode_bam_device_ctx(path, qual=20, device=0):
     table = DeviceBamTable(L, hb, None, contigs)
     ctx._keep = table
     return ctx, table
+
+
+def bam_extract(in_bam, out_bam, keys, tags):
+    """Read names back from their hashes, and the reads themselves (bk_bam_extract; host code, no GPU).  keys: abi.READ_KEY array
+    (qcheck 0 = compare qhash alone; tag indexes `tags`); out_bam: path or None (names only).  Returns (names, n_written): one
+    name per key, "" for a key no record matched."""
+    keys = np.ascontiguousarray(keys, abi.READ_KEY)
+    tag_arr = (C.c_char_p * max(len(tags), 1))(*[t.encode() for t in tags])
+    names, n = C.c_void_p(), C.c_uint64()
+    err = C.create_string_buffer(512)
+    L = lib()
+    rc = L.bk_bam_extract(os.fsencode(in_bam), None if out_bam is None else os.fsencode(out_bam), keys.ctypes.data if len(keys) else None, len(keys),
+                          tag_arr if len(tags) else None, len(tags), C.byref(names), C.byref(n), err, 512)
+    if rc != 0:
+        raise BreakIDError(rc, err.value.decode())
+    try:
+        out, p = [], names.value
+        for _ in range(len(keys)):
+            t = C.string_at(p)
+            out.append(t.decode())
+            p += len(t) + 1
+    finally:
+        L.bk_bam_names_free(names)
+    return out, n.value
 
 
 class BamTable:

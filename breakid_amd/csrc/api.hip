@@ -14,6 +14,7 @@
 #include "normal.h"
 #include "genotype.h"
 #include "junction.h"
+#include "evidence.h"
 #include "exclude.h"
 #include "ahc.h"
 #include "lanes.h"
@@ -123,6 +124,10 @@ struct bk_ctx
   JunctionBufs jnb;
   std::vector<struct bk_junction> f_junction;
   bool summary_map = false;
+  // evidence export (bk_evidence)
+  EvidenceBufs evb;
+  std::vector<struct bk_evidence> f_evidence;
+  std::vector<uint64_t> f_ev_off;
 
   // fetch staging
   std::vector<bk_pair> f_pairs[3];
@@ -983,6 +988,68 @@ int bk_junctions(bk_ctx *ctx, const struct bk_junction **out, uint64_t *count)
     for (uint64_t c = 0; c < ncl; ++c) ctx->f_junction[start[grp[c]]++] = res[c];
     *out = ctx->f_junction.data();
     *count = ncl;
+  });
+}
+
+int bk_evidence(bk_ctx *ctx, const struct bk_evidence **out, uint64_t *count, const uint64_t **call_off)
+{
+  return guarded(ctx, [&] {
+    if (!out || !count || !call_off) throw bk_error(BK_ERR_ARG, "bk_evidence: null output");
+    if (ctx->shard) throw bk_error(BK_ERR_ARG, "bk_evidence: sharded contexts (bk_shard_*) are not supported");
+    if (!ctx->bp_done || !ctx->clustered || !ctx->summary_map) throw bk_error(BK_ERR_ARG, "bk_evidence: call bk_split_breakpoints first");
+    const uint64_t ncl = ctx->n_clusters;
+    const bk_soa &t = ctx->rec;
+    if (ncl && (!ctx->have_records || !t.mapq || (!t.side && !t.qhash))) throw bk_error(BK_ERR_ARG, "bk_evidence: the record table lacks a column");
+    JunctionPairs jp{};
+    if (ncl)  // (no cluster: bk_cluster_summary may have returned before it built the map)
+    {
+      jp.pairs = ctx->jr.pairs;
+      jp.idx = ctx->stage.list.idx.get<uint32_t>();
+      jp.gof = ctx->stage.list.gof.get<uint32_t>();
+      jp.cl = ctx->stage.d_cluster.get<uint32_t>();
+      jp.n = ctx->stage.list.n;
+      jp.ng = ctx->stage.list.ng;
+      jp.slotbase = ctx->bb.slotbase.get<uint32_t>();
+      jp.keep = ctx->bb.keep.get<uint32_t>();
+      jp.off = ctx->bb.off.get<uint32_t>();
+    }
+    EvidenceRecs er{t.n, t.side, t.qhash, t.qcheck, t.mapq};
+    struct bk_evidence *d_rows;
+    uint64_t *d_off;
+    EvidenceStat *d_stat;
+    {
+      // bytes: what bk_junctions reads (the counts are its own) and, per list entry, its sort key and value written and read once
+      Scope s(ctx, "evidence", jp.n * (12ull + 4ull + 2ull * 12ull));
+      evidence(jp, ctx->d_split.get<bk_split>(), ctx->hc.n_split, ctx->clusters_ptr(), ncl, ctx->jr.n_groups, (int) ctx->hc.max_span, ctx->d_hdr.get<int32_t>(),
+               ctx->names.own_id, ctx->nt, ctx->names.empty_id, er, ctx->evb, ctx->st, &d_rows, &d_off, &d_stat);
+    }
+    ctx->f_ev_off.assign(ncl + 1, 0);
+    EvidenceStat stat{};
+    HIP_CHECK(hipMemcpyAsync(ctx->f_ev_off.data(), d_off, (ncl + 1) * 8, hipMemcpyDeviceToHost, ctx->st));
+    HIP_CHECK(hipMemcpyAsync(&stat, d_stat, sizeof stat, hipMemcpyDeviceToHost, ctx->st));
+    HIP_CHECK(hipStreamSynchronize(ctx->st));
+    if (stat.bad) throw bk_error(BK_ERR_HIP, "bk_evidence: the listing and the counts of bk_junctions disagree (internal error)");
+    const uint64_t n = ctx->f_ev_off[ncl];
+    ctx->f_evidence.resize(n);
+    if (n) HIP_CHECK(hipMemcpyAsync(ctx->f_evidence.data(), d_rows, n * sizeof(struct bk_evidence), hipMemcpyDeviceToHost, ctx->st));
+    HIP_CHECK(hipStreamSynchronize(ctx->st));
+    if (ctx->timing && !ctx->timers.empty())
+    {
+      // touched: the counting pass as in bk_junctions (the tuples are searched twice: counted, then listed), the radix passes over
+      // the list (8-byte key + 4-byte value, read twice and written once per 8-bit digit), the pair rows gathered (a 56-byte row
+      // and a 32-byte sector of the hashes each), and every row written
+      uint64_t n_pair_rows = 0;
+      for (uint64_t i = 0; i < n; ++i) n_pair_rows += ctx->f_evidence[i].kind == BK_EV_PAIR;
+      int bits = 1;
+      while ((ncl >> bits) != 0) ++bits;
+      const uint64_t passes = (uint64_t) (bits + 7) / 8;
+      ctx->timers.back().touched = jp.n * (12ull + 32ull) + 2ull * stat.visited * sizeof(bk_split) + ncl * (2ull * sizeof(bk_cluster) + 2ull * sizeof(struct bk_junction) + 40ull) +
+                                   jp.n * (12ull + 12ull + passes * 32ull + 12ull) + n_pair_rows * (64ull + 32ull) + (n - n_pair_rows) * 32ull +
+                                   n * sizeof(struct bk_evidence);
+    }
+    *out = ctx->f_evidence.data();
+    *count = n;
+    *call_off = ctx->f_ev_off.data();
   });
 }
 

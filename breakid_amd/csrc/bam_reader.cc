@@ -12,6 +12,7 @@
 #include <hip/hip_runtime_api.h>
 #include <zlib.h>
 
+#include <algorithm>
 #include <atomic>
 #include <memory>
 #include <ctime>
@@ -21,6 +22,8 @@
 #include <string>
 #include "bk_debug.h"
 #include <thread>
+#include <unistd.h>
+#include <unordered_map>
 #include <vector>
 
 #include "../../include/breakid_hip.h"
@@ -559,3 +562,357 @@ extern "C" int bk_bam_decode(bk_bam *b, bk_soa *out, char *err, size_t errlen)
   return no_throw(err, errlen, [&] { return bam_decode_impl(b, out, err, errlen); });
 }
 extern "C" void bk_bam_close(bk_bam *b) { delete b; }
+
+// ---- bk_bam_extract: read names back from their hashes, and the reads themselves (include/breakid_hip.h) -----------------------
+// One streaming pass with bounded memory: the file is read in chunks, every BGZF block is inflated on its own into a carry buffer
+// that holds the bytes of the header or record still incomplete (records may cross blocks), and selected records go straight
+// into the BGZF writer.  Nothing of bk_bam_open is used: it holds the whole inflated file.
+
+namespace
+{
+struct ExtractError
+{
+  int code;
+  std::string msg;
+};
+
+// BGZF writer with htslib's layout (bgzf.c: bgzf_write / bgzf_flush_try / deflate_block): a block takes at most 0xff00 payload bytes,
+// it is flushed before a record that would not fit, a longer record spans blocks, the 28-byte EOF block ends the file.
+struct BgzfWriter
+{
+  static constexpr size_t BLOCK = 0xff00;
+  FILE *f = nullptr;
+  std::vector<uint8_t> buf, zbuf;
+  BgzfWriter() { buf.reserve(BLOCK); }
+  void flush()
+  {
+    if (buf.empty()) return;
+    z_stream zs;
+    memset(&zs, 0, sizeof zs);
+    if (deflateInit2(&zs, Z_DEFAULT_COMPRESSION, Z_DEFLATED, -15, 8, Z_DEFAULT_STRATEGY) != Z_OK) throw ExtractError{BK_ERR_IO, "deflateInit2 failed"};
+    zbuf.resize(18 + deflateBound(&zs, (uLong) buf.size()) + 8);
+    zs.next_in = buf.data();
+    zs.avail_in = (uInt) buf.size();
+    zs.next_out = zbuf.data() + 18;
+    zs.avail_out = (uInt) (zbuf.size() - 18 - 8);
+    const int rc = deflate(&zs, Z_FINISH);
+    const size_t clen = zs.total_out;
+    deflateEnd(&zs);
+    size_t total = 18 + clen + 8;
+    if (rc != Z_STREAM_END || total > 65536)
+    {
+      // (incompressible data: stored deflate blocks of 0xff00 bytes fit, as in htslib, which retries at level 0)
+      memset(&zs, 0, sizeof zs);
+      if (deflateInit2(&zs, 0, Z_DEFLATED, -15, 8, Z_DEFAULT_STRATEGY) != Z_OK) throw ExtractError{BK_ERR_IO, "deflateInit2 failed"};
+      zs.next_in = buf.data();
+      zs.avail_in = (uInt) buf.size();
+      zs.next_out = zbuf.data() + 18;
+      zs.avail_out = (uInt) (zbuf.size() - 18 - 8);
+      const int rc0 = deflate(&zs, Z_FINISH);
+      total = 18 + zs.total_out + 8;
+      deflateEnd(&zs);
+      if (rc0 != Z_STREAM_END || total > 65536) throw ExtractError{BK_ERR_IO, "cannot deflate a BGZF block"};
+    }
+    static const uint8_t head[16] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0};
+    memcpy(zbuf.data(), head, 16);
+    zbuf[16] = (uint8_t) ((total - 1) & 0xff);
+    zbuf[17] = (uint8_t) ((total - 1) >> 8);
+    const uint32_t crc = (uint32_t) crc32(crc32(0L, nullptr, 0), buf.data(), (uInt) buf.size()), isize = (uint32_t) buf.size();
+    uint8_t *t = zbuf.data() + total - 8;
+    for (int i = 0; i < 4; ++i)
+    {
+      t[i] = (uint8_t) (crc >> (8 * i));
+      t[4 + i] = (uint8_t) (isize >> (8 * i));
+    }
+    if (fwrite(zbuf.data(), 1, total, f) != total) throw ExtractError{BK_ERR_IO, "cannot write the output BAM"};
+    buf.clear();
+  }
+  void write(const uint8_t *p, size_t n)
+  {
+    while (n)
+    {
+      const size_t take = std::min(n, BLOCK - buf.size());
+      buf.insert(buf.end(), p, p + take);
+      p += take;
+      n -= take;
+      if (buf.size() == BLOCK) flush();
+    }
+  }
+  // a record of n bytes follows: it starts a new block unless it fits into this one
+  void record_follows(size_t n)
+  {
+    if (buf.size() + n > BLOCK) flush();
+  }
+  void finish()
+  {
+    flush();
+    static const uint8_t eof[28] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    if (fwrite(eof, 1, 28, f) != 28 || fflush(f) != 0) throw ExtractError{BK_ERR_IO, "cannot write the output BAM"};
+  }
+};
+
+// the inflated stream, one BGZF block at a time: `buf` holds the bytes not consumed yet
+struct BgzfStream
+{
+  static constexpr size_t CHUNK_BYTES = 4u << 20;
+  FILE *f = nullptr;
+  std::vector<uint8_t> in;   // file bytes not parsed yet
+  size_t in_pos = 0;
+  bool file_end = false;
+  std::vector<uint8_t> buf;  // inflated bytes not consumed yet
+  size_t pos = 0;
+  void refill()
+  {
+    in.erase(in.begin(), in.begin() + (ptrdiff_t) in_pos);
+    in_pos = 0;
+    const size_t old = in.size();
+    in.resize(old + CHUNK_BYTES);
+    const size_t got = fread(in.data() + old, 1, CHUNK_BYTES, f);
+    if (got < CHUNK_BYTES)
+    {
+      if (ferror(f)) throw ExtractError{BK_ERR_IO, "read error on the input BAM"};
+      file_end = true;
+    }
+    in.resize(old + got);
+  }
+  bool have(size_t n)  // n bytes of the file at in_pos; false at a clean end of file (no byte left)
+  {
+    while (in.size() - in_pos < n && !file_end) refill();
+    if (in.size() - in_pos >= n) return true;
+    if (in.size() == in_pos) return false;
+    throw ExtractError{BK_ERR_IO, "truncated BGZF block"};
+  }
+  // appends the next block's data to buf; false at the end of the file
+  bool next_block()
+  {
+    if (!have(18)) return false;
+    const uint8_t *h = in.data() + in_pos;
+    if (h[0] != 0x1f || h[1] != 0x8b || h[2] != 8 || !(h[3] & 4)) throw ExtractError{BK_ERR_IO, "not a BGZF block"};
+    const uint16_t xlen = rd16(h + 10);
+    if (!have(12 + (size_t) xlen)) throw ExtractError{BK_ERR_IO, "truncated BGZF block"};
+    h = in.data() + in_pos;
+    const uint8_t *x = h + 12;
+    int bsize = -1;
+    for (size_t k = 0; k + 4 <= xlen;)
+    {
+      const uint16_t slen = rd16(x + k + 2);
+      if (x[k] == 66 && x[k + 1] == 67 && slen == 2 && k + 6 <= xlen) bsize = rd16(x + k + 4);
+      k += 4 + (size_t) slen;
+    }
+    if (bsize < 0 || (size_t) bsize + 1 < 12 + (size_t) xlen + 8) throw ExtractError{BK_ERR_IO, "bad BGZF block size"};
+    if (!have((size_t) bsize + 1)) throw ExtractError{BK_ERR_IO, "truncated BGZF block"};
+    h = in.data() + in_pos;
+    const size_t clen = (size_t) bsize + 1 - (12 + (size_t) xlen) - 8;
+    const uint32_t crc = rd32(h + bsize + 1 - 8), isize = rd32(h + bsize + 1 - 4);
+    if (isize > 65536u) throw ExtractError{BK_ERR_IO, "BGZF block claims more than 64 KiB of data"};
+    if (pos > (1u << 20) && pos * 2 > buf.size())  // drop what was consumed, now and then
+    {
+      buf.erase(buf.begin(), buf.begin() + (ptrdiff_t) pos);
+      pos = 0;
+    }
+    const size_t old = buf.size();
+    buf.resize(old + isize);
+    if (isize)
+    {
+      z_stream zs;
+      memset(&zs, 0, sizeof zs);
+      if (inflateInit2(&zs, -15) != Z_OK) throw ExtractError{BK_ERR_IO, "inflateInit2 failed"};
+      zs.next_in = const_cast<Bytef *>(h + 12 + xlen);
+      zs.avail_in = (uInt) clen;
+      zs.next_out = buf.data() + old;
+      zs.avail_out = isize;
+      const int rc = inflate(&zs, Z_FINISH);
+      const bool whole = zs.avail_out == 0;
+      inflateEnd(&zs);
+      if (rc != Z_STREAM_END || !whole) throw ExtractError{BK_ERR_IO, "inflate failed: bad BGZF block"};
+      if ((uint32_t) crc32(crc32(0L, nullptr, 0), buf.data() + old, isize) != crc) throw ExtractError{BK_ERR_IO, "bad BGZF block: CRC mismatch"};
+    }
+    in_pos += (size_t) bsize + 1;
+    return true;
+  }
+  // at least n unconsumed bytes in buf; false when the stream ends before that (avail() tells how many there are)
+  bool need(size_t n)
+  {
+    while (buf.size() - pos < n)
+      if (!next_block()) return false;
+    return true;
+  }
+  size_t avail() const { return buf.size() - pos; }
+  const uint8_t *ptr() const { return buf.data() + pos; }
+};
+
+struct KeyHash
+{
+  size_t operator()(uint64_t h) const { return (size_t) h; }
+};
+
+int bam_extract_impl(const char *in_bam, const char *out_bam, const bk_read_key *keys, uint64_t n_keys, const char *const *tags, uint64_t n_tags, char **names_out,
+                     uint64_t *n_written, std::string &tmp_path, FILE *&fin, FILE *&fout)
+{
+  if (!in_bam) throw ExtractError{BK_ERR_ARG, "bk_bam_extract: null input path"};
+  if ((n_keys && !keys) || (n_tags && !tags)) throw ExtractError{BK_ERR_ARG, "bk_bam_extract: null keys or tags"};
+  // qhash -> the keys that carry it, in key order
+  std::unordered_map<uint64_t, std::vector<uint64_t>, KeyHash> by_hash;
+  by_hash.reserve((size_t) n_keys * 2 + 1);
+  for (uint64_t k = 0; k < n_keys; ++k)
+  {
+    if (keys[k].tag >= n_tags) throw ExtractError{BK_ERR_ARG, "bk_bam_extract: key " + std::to_string(k) + " has tag " + std::to_string(keys[k].tag) + " of " + std::to_string(n_tags)};
+    if (!tags[keys[k].tag]) throw ExtractError{BK_ERR_ARG, "bk_bam_extract: null tag text"};
+    std::vector<uint64_t> &v = by_hash[keys[k].qhash];
+    for (uint64_t o : v)
+      if (keys[o].qcheck == keys[k].qcheck) throw ExtractError{BK_ERR_ARG, "bk_bam_extract: duplicate key " + std::to_string(k)};
+    v.push_back(k);
+  }
+  std::vector<std::string> names(n_keys);
+  std::vector<uint8_t> seen(n_keys, 0);
+  fin = fopen(in_bam, "rb");
+  if (!fin) throw ExtractError{BK_ERR_IO, std::string("cannot open ") + in_bam};
+  BgzfStream s;
+  s.f = fin;
+  BgzfWriter w;
+  if (out_bam)
+  {
+    tmp_path = std::string(out_bam) + ".tmp." + std::to_string((long) getpid());
+    fout = fopen(tmp_path.c_str(), "wb");
+    if (!fout)
+    {
+      tmp_path.clear();
+      throw ExtractError{BK_ERR_IO, std::string("cannot write ") + out_bam};
+    }
+    w.f = fout;
+  }
+  // header: copied byte for byte
+  if (!s.need(12) || memcmp(s.ptr(), "BAM\1", 4) != 0) throw ExtractError{BK_ERR_IO, "not a BAM file"};
+  const size_t l_text = rd32(s.ptr() + 4);
+  if (!s.need(12 + l_text)) throw ExtractError{BK_ERR_IO, "truncated BAM header"};
+  const uint32_t n_ref = rd32(s.ptr() + 8 + l_text);
+  size_t hlen = 12 + l_text;
+  for (uint32_t i = 0; i < n_ref; ++i)
+  {
+    if (!s.need(hlen + 4)) throw ExtractError{BK_ERR_IO, "truncated BAM header"};
+    const size_t l_name = rd32(s.ptr() + hlen);
+    hlen += 4 + l_name + 4;
+    if (!s.need(hlen)) throw ExtractError{BK_ERR_IO, "truncated BAM header"};
+  }
+  if (out_bam)
+  {
+    w.write(s.ptr(), hlen);
+    w.flush();  // (htslib ends the header's block before the first record)
+  }
+  s.pos += hlen;
+  uint64_t written = 0;
+  std::vector<uint8_t> rec;
+  for (;;)
+  {
+    if (!s.need(4))
+    {
+      if (s.avail() == 0) break;
+      throw ExtractError{BK_ERR_IO, "truncated BAM record"};
+    }
+    const size_t bs = rd32(s.ptr());
+    if (bs < 32) throw ExtractError{BK_ERR_IO, "corrupt BAM record"};
+    if (!s.need(4 + bs)) throw ExtractError{BK_ERR_IO, "truncated BAM record: it is longer than its stream"};
+    const uint8_t *r = s.ptr() + 4;
+    const size_t l_name = r[8], n_cig = rd16(r + 12), l_seq = rd32(r + 16);
+    if (32 + l_name + n_cig * 4 + (l_seq + 1) / 2 + l_seq > bs) throw ExtractError{BK_ERR_IO, "corrupt BAM record"};
+    const char *qn = (const char *) r + 32;
+    const size_t qlen = l_name ? strnlen(qn, l_name) : 0;  // bam_get_qname is a C string
+    const auto it = by_hash.find(bk_qname_hash(qn, qlen));
+    if (it != by_hash.end())
+    {
+      const uint32_t check = bk_qname_check(qn, qlen);
+      int64_t first = -1;
+      for (uint64_t k : it->second)
+        if (keys[k].qcheck == 0 || keys[k].qcheck == check)
+        {
+          if (first < 0) first = (int64_t) k;
+          if (!seen[k])
+          {
+            seen[k] = 1;
+            names[k].assign(qn, qlen);
+          }
+        }
+      if (first >= 0)
+      {
+        ++written;
+        if (out_bam)
+        {
+          const char *tag = tags[keys[first].tag];
+          const size_t tl = strlen(tag), nbs = bs + 3 + tl + 1;
+          if (nbs > 0x7FFFFFFFull) throw ExtractError{BK_ERR_IO, "record too long for a bk tag"};
+          rec.resize(4 + nbs);
+          for (int i = 0; i < 4; ++i) rec[i] = (uint8_t) (nbs >> (8 * i));
+          memcpy(rec.data() + 4, r, bs);
+          uint8_t *a = rec.data() + 4 + bs;
+          a[0] = 'b';
+          a[1] = 'k';
+          a[2] = 'Z';
+          memcpy(a + 3, tag, tl + 1);
+          w.record_follows(rec.size());
+          w.write(rec.data(), rec.size());
+        }
+      }
+    }
+    s.pos += 4 + bs;
+  }
+  if (names_out)  // (before the rename: a failure here must leave no output file)
+  {
+    size_t total = 0;
+    for (const std::string &n : names) total += n.size() + 1;
+    char *p = (char *) malloc(total ? total : 1);
+    if (!p) throw std::bad_alloc();
+    *names_out = p;
+    for (const std::string &n : names)
+    {
+      memcpy(p, n.c_str(), n.size() + 1);
+      p += n.size() + 1;
+    }
+  }
+  if (out_bam)
+  {
+    w.finish();
+    FILE *f = fout;
+    fout = nullptr;
+    if (fclose(f) != 0) throw ExtractError{BK_ERR_IO, std::string("cannot write ") + out_bam};
+    if (rename(tmp_path.c_str(), out_bam) != 0) throw ExtractError{BK_ERR_IO, std::string("cannot rename the output to ") + out_bam};
+    tmp_path.clear();
+  }
+  if (n_written) *n_written = written;
+  return BK_OK;
+}
+}  // namespace
+
+extern "C" int bk_bam_extract(const char *in_bam, const char *out_bam, const bk_read_key *keys, uint64_t n_keys, const char *const *tags, uint64_t n_tags,
+                              char **names_out, uint64_t *n_written, char *err, size_t errlen)
+{
+  if (names_out) *names_out = nullptr;
+  if (n_written) *n_written = 0;
+  std::string tmp_path;
+  FILE *fin = nullptr, *fout = nullptr;
+  int rc = no_throw(err, errlen, [&] {
+    try
+    {
+      return bam_extract_impl(in_bam, out_bam, keys, n_keys, tags, n_tags, names_out, n_written, tmp_path, fin, fout);
+    }
+    catch (const ExtractError &e)
+    {
+      set_err(err, errlen, e.msg);
+      return e.code;
+    }
+  });
+  if (fin) fclose(fin);
+  if (fout) fclose(fout);
+  if (rc != BK_OK)
+  {
+    if (!tmp_path.empty()) (void) remove(tmp_path.c_str());  // no output file on any failure (the target itself is only ever renamed into)
+    if (names_out && *names_out)
+    {
+      free(*names_out);
+      *names_out = nullptr;
+    }
+    if (n_written) *n_written = 0;
+  }
+  return rc;
+}
+
+extern "C" void bk_bam_names_free(char *names) { free(names); }

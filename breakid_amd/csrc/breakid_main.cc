@@ -37,6 +37,8 @@ extern "C" int bk_genotype_call(uint32_t alt, uint32_t ref, uint8_t *gt, uint8_t
 extern "C" int bk_junctions(bk_ctx *ctx, const struct bk_junction **out, uint64_t *count) __attribute__((weak));
 extern "C" int bk_junction_sides(const struct bk_junction *j, uint8_t *right1, uint8_t *right2, uint8_t *source) __attribute__((weak));
 extern "C" int bk_vcf_breakend_alt(char ref_base, int own_right, const char *mate_chr, uint32_t mate_pos, int mate_right, char *buf, size_t cap) __attribute__((weak));
+// -evidence: the same for the evidence rows (the CPU build refuses -evidence; bk_bam_extract is host code and always there)
+extern "C" int bk_evidence(bk_ctx *ctx, const struct bk_evidence **out, uint64_t *count, const uint64_t **call_off) __attribute__((weak));
 // -x: the same for the exclude list (the CPU build refuses -x)
 extern "C" int bk_exclude_regions(bk_ctx *ctx, const bk_regions *r, uint64_t *n_removed) __attribute__((weak));
 extern "C" int bk_multi_run_ex(const bk_soa *host_table, const uint32_t *target_len, const char *const *target_name, int n_targets, const bk_regions *exclude, int n_gpus,
@@ -274,7 +276,8 @@ static const char *HELP =
      \t -x         \t exclude list (BED: contig [start end]); records that overlap it are ignored  \n \
      \t -genotype  \t count reference-allele evidence and genotype every call (twin files *_genotype.txt)  \n \
      \t -anchor    \t bases a reference read must cover on either side of a breakpoint (with -genotype)  [10]\n \
-     \t -vcf       \t also write the calls as VCF breakends (*_fusion.vcf)  \n ";
+     \t -vcf       \t also write the calls as VCF breakends (*_fusion.vcf)  \n \
+     \t -evidence  \t also list the reads behind every call (*_evidence.txt) and write them as a BAM (*_evidence.bam)  \n ";
 
 // ---- RefSeqTranscript.{h,cc} -------------------------------------------------------------------------------
 struct Txpt
@@ -540,6 +543,13 @@ static const char *GENOTYPE_COLUMNS = "\tRef_Pairs1\tRef_Pairs2\tRef_Reads1\tRef
 static const char *GENOTYPE_COLUMNS_NORMAL =
     "\tNormal_Ref_Pairs1\tNormal_Ref_Pairs2\tNormal_Ref_Reads1\tNormal_Ref_Reads2\tNormal_VAF_Pairs\tNormal_VAF_Reads\tNormal_GT\tNormal_GQ";
 
+// Which rows the fusion files hold, and with them -vcf and -evidence: `all_ok` rows go to _fusion_all.txt (-all), those that also pass
+// the gene-pair and repeat filters to _fusion.txt.
+static bool call_all_ok(const OutRow &r) { return r.c.n_sr > 0 && r.c.p1_exact != 0xFFFFFFFFu && r.c.p2_exact != -1; }
+static bool call_no_gene_pair(const OutRow &r) { return (r.g1 == "intergenic" && r.g2 == "intergenic") || r.g1 == r.g2; }
+static bool call_filt_ok(const OutRow &r) { return call_all_ok(r) && !call_no_gene_pair(r) && !r.is_rpt; }
+static bool call_written(const OutRow &r, bool all) { return all ? call_all_ok(r) : call_filt_ok(r); }
+
 // ---- -vcf: the calls of the fusion files as VCF 4.2 breakends (section 5.4), two records per call ------------------------------
 struct VcfInput
 {
@@ -603,10 +613,8 @@ static bool write_vcf(const string &path, const vector<OutRow> &rows, const VcfI
   vector<VcfRecord> recs;
   for (const OutRow &r : rows)
   {
-    const bool all_ok = r.c.n_sr > 0 && r.c.p1_exact != 0xFFFFFFFFu && r.c.p2_exact != -1;
-    const bool no_gene_pair = (r.g1 == "intergenic" && r.g2 == "intergenic") || r.g1 == r.g2;
-    const bool filt_ok = all_ok && !no_gene_pair && !r.is_rpt;
-    if (!all_ok || (!in.all && !filt_ok)) continue;
+    if (!call_written(r, in.all)) continue;
+    const bool no_gene_pair = call_no_gene_pair(r), filt_ok = call_filt_ok(r);
     if (r.idx >= in.jsup->size() || (in.with_normal && r.idx >= in.n_nsup) || (in.gsup && r.idx >= in.gsup->size()) || (in.gsup_normal && r.idx >= in.gsup_normal->size()))
       return false;
     const struct bk_junction &j = (*in.jsup)[r.idx];
@@ -673,6 +681,100 @@ static bool write_vcf(const string &path, const vector<OutRow> &rows, const VcfI
   return v.good();
 }
 
+// ---- -evidence: the reads behind the written calls: <prefix>_evidence.txt and <prefix>_evidence.bam ------------------------------
+struct EvidenceInput
+{
+  int nt = 0;
+  const char *const *names = nullptr;
+  bool all = false;  // -all: the calls of _fusion_all.txt
+  const vector<struct bk_evidence> *rows = nullptr;
+  const vector<uint64_t> *call_off = nullptr;  // per BK_STAGE_CLUSTERS row, one more entry than rows
+};
+
+// The calls covered are those of -vcf, with its ids (bk<row>).  One pass over the input BAM (bk_bam_extract) gives the names of the
+// listed reads and writes every alignment of theirs, tagged bk:Z:<the read's call ids, ascending, joined with commas>.
+static bool write_evidence(const string &prefix, const string &inp_bam, const vector<OutRow> &rows, const EvidenceInput &in, string &why)
+{
+  vector<uint64_t> calls;
+  for (const OutRow &r : rows)
+  {
+    if (!call_written(r, in.all)) continue;
+    if (r.idx + 1 >= in.call_off->size() || (*in.call_off)[r.idx + 1] > in.rows->size())
+    {
+      why = "the evidence table does not cover every call";
+      return false;
+    }
+    calls.push_back(r.idx);
+  }
+  std::sort(calls.begin(), calls.end());  // ABI order: by row
+  // the unique reads of those calls and, per read, its calls (ascending, each once)
+  std::map<std::pair<uint64_t, uint32_t>, size_t> key_of;
+  vector<bk_read_key> keys;
+  vector<vector<uint64_t>> key_calls;
+  for (uint64_t c : calls)
+    for (uint64_t i = (*in.call_off)[c]; i < (*in.call_off)[c + 1]; ++i)
+    {
+      const struct bk_evidence &e = (*in.rows)[i];
+      auto it = key_of.emplace(std::make_pair(e.qhash, e.qcheck), keys.size());
+      if (it.second)
+      {
+        keys.push_back(bk_read_key{e.qhash, e.qcheck, 0});
+        key_calls.emplace_back();
+      }
+      vector<uint64_t> &kc = key_calls[it.first->second];
+      if (kc.empty() || kc.back() != c) kc.push_back(c);
+    }
+  std::map<string, uint32_t> tag_of;
+  vector<string> tag_text;
+  for (size_t k = 0; k < keys.size(); ++k)
+  {
+    string t;
+    for (uint64_t c : key_calls[k]) t += (t.empty() ? "bk" : ",bk") + std::to_string(c);
+    auto it = tag_of.emplace(t, (uint32_t) tag_text.size());
+    if (it.second) tag_text.push_back(t);
+    keys[k].tag = it.first->second;
+  }
+  vector<const char *> tag_ptrs;
+  for (const string &t : tag_text) tag_ptrs.push_back(t.c_str());
+  char *names = nullptr, err[512] = "";
+  if (bk_bam_extract(inp_bam.c_str(), (prefix + "_evidence.bam").c_str(), keys.data(), keys.size(), tag_ptrs.data(), tag_ptrs.size(), &names, nullptr, err, sizeof err) != BK_OK)
+  {
+    why = err;
+    return false;
+  }
+  vector<const char *> name_of(keys.size(), "");
+  {
+    const char *p = names;
+    for (size_t k = 0; k < keys.size(); ++k)
+    {
+      name_of[k] = p;
+      p += strlen(p) + 1;
+    }
+  }
+  std::ofstream o((prefix + "_evidence.txt").c_str());
+  o << "Call\tKind\tRead\tChr1\tPos1\tChr2\tPos2\tSides\tFlag1\tFlag2\tMapq1\tMapq2\tRecord\n";
+  auto chr = [&](int32_t tid) { return tid < 0 || tid >= in.nt ? "*" : in.names[tid]; };
+  for (uint64_t c : calls)
+    for (uint64_t i = (*in.call_off)[c]; i < (*in.call_off)[c + 1]; ++i)
+    {
+      const struct bk_evidence &e = (*in.rows)[i];
+      const char *name = name_of[key_of[std::make_pair(e.qhash, e.qcheck)]];
+      o << "bk" << c << "\t" << (e.kind == BK_EV_PAIR ? "PE" : "SR") << "\t" << (*name ? name : ".") << "\t" << chr(e.tid1) << "\t" << e.pos1 << "\t" << chr(e.tid2) << "\t"
+        << e.pos2 << "\t" << ((e.sides >> 1) & 1 ? 'R' : 'L') << ((e.sides & 1) ? 'R' : 'L') << "\t" << e.flag1 << "\t" << e.flag2 << "\t" << (unsigned) e.mapq1 << "\t"
+        << (unsigned) e.mapq2 << "\t" << e.rec << "\n";
+    }
+  o.close();
+  bk_bam_names_free(names);
+  if (!o)
+  {
+    (void) remove((prefix + "_evidence.txt").c_str());  // neither file stays without the other
+    (void) remove((prefix + "_evidence.bam").c_str());
+    why = "cannot write " + prefix + "_evidence.txt";
+    return false;
+  }
+  return true;
+}
+
 // one input BAM: its decoded table (host or device) and, once created, its context
 struct Sample
 {
@@ -706,10 +808,10 @@ int main(int argc, char *argv[])
   static struct option longopts[] = {{"help", 0, 0, 'h'}, {"i", 1, 0, 1}, {"o", 1, 0, 2}, {"q", 1, 0, 3}, {"n", 1, 0, 4},
                                      {"fast", 0, 0, 5},   {"t", 0, 0, 6}, {"all", 0, 0, 7}, {"gpu", 1, 0, 8}, {"gpus", 1, 0, 9},
                                      {"comm", 1, 0, 10},  {"normal", 1, 0, 11}, {"x", 1, 0, 12}, {"genotype", 0, 0, 13},
-                                     {"anchor", 1, 0, 14}, {"vcf", 0, 0, 15}, {0, 0, 0, 0}};
+                                     {"anchor", 1, 0, 14}, {"vcf", 0, 0, 15}, {"evidence", 0, 0, 16}, {0, 0, 0, 0}};
   string inp_file, out_file, nib_dir, normal_file, exclude_file, build = "hg19";
   int qual = 20, device = 0, n_gpus = 0, transport = BK_TRANSPORT_AUTO;  // -gpus N: one sample over N GPUs (include/breakid_multi.h)
-  bool fast = false, filter = true, genotype = false, anchor_given = false, vcf = false;
+  bool fast = false, filter = true, genotype = false, anchor_given = false, vcf = false, evidence = false;
   long anchor = 10;  // -anchor: bases a reference read must cover on either side of the breakpoint base
   int opt, li;
   optind = 0;
@@ -736,6 +838,7 @@ int main(int argc, char *argv[])
       anchor_given = true;
       break;
     case 15: vcf = true; break;
+    case 16: evidence = true; break;
     default: std::cerr << "Error: cannot parse arguments.\n"; exit(1);
     }
   }
@@ -802,6 +905,19 @@ int main(int argc, char *argv[])
     if (!bk_junctions || !bk_junction_sides || !bk_vcf_breakend_alt)
     {
       std::cerr << "Error: -vcf needs the GPU library" << std::endl;
+      exit(1);
+    }
+  }
+  if (evidence)
+  {
+    if (n_gpus >= 1)
+    {
+      std::cerr << HELP << "Error: -evidence cannot be combined with -gpus.\n";
+      exit(1);
+    }
+    if (!bk_evidence)
+    {
+      std::cerr << "Error: -evidence needs the GPU library" << std::endl;
       exit(1);
     }
   }
@@ -1086,6 +1202,18 @@ int main(int argc, char *argv[])
   uint64_t cnt = 0;
   if ((rc = bk_fetch(ctx, BK_STAGE_CLUSTERS, &data, &cnt, nullptr, nullptr)) != BK_OK) die(rc);
   const bk_cluster *cl = (const bk_cluster *) data;
+  // -evidence: the reads behind every call (one row per member pair and per matching split tuple), listed on the device
+  vector<struct bk_evidence> ev_rows;
+  vector<uint64_t> ev_off;
+  if (evidence)
+  {
+    const struct bk_evidence *ev = nullptr;
+    const uint64_t *off = nullptr;
+    uint64_t n_ev = 0;
+    if ((rc = bk_evidence(ctx, &ev, &n_ev, &off)) != BK_OK) die(rc);
+    ev_rows.assign(ev, ev + n_ev);
+    ev_off.assign(off, off + cnt + 1);
+  }
   if (multi)
   {
     n_valid = 0;
@@ -1164,8 +1292,7 @@ int main(int argc, char *argv[])
   }
   for (auto &r : rows)
   {
-    bool all_ok = r.c.n_sr > 0 && r.c.p1_exact != 0xFFFFFFFFu && r.c.p2_exact != -1;
-    bool filt_ok = all_ok && (!(r.g1 == "intergenic" && r.g2 == "intergenic") && r.g1 != r.g2) && !r.is_rpt;
+    const bool all_ok = call_all_ok(r), filt_ok = call_filt_ok(r);
     if (filt_ok) write_row(outf, r);
     if (!filter && all_ok) write_row(out, r);
     if (with_normal && r.idx < n_nsup)
@@ -1213,6 +1340,21 @@ int main(int argc, char *argv[])
       exit(1);
     }
   }
+  if (evidence)
+  {
+    EvidenceInput ei;
+    ei.nt = nt;
+    ei.names = names;
+    ei.all = !filter;
+    ei.rows = &ev_rows;
+    ei.call_off = &ev_off;
+    string why;
+    if (!write_evidence(out_file, inp_file, rows, ei, why))
+    {
+      std::cerr << "Error: cannot write " << out_file << "_evidence.txt / _evidence.bam: " << why << std::endl;
+      exit(1);
+    }
+  }
   {
     std::ofstream p((out_file + "_params.txt").c_str());  // write_enspan_params :1170-1182
     p << "ENSPAN" << std::endl;
@@ -1225,6 +1367,7 @@ int main(int argc, char *argv[])
     if (!normal_file.empty()) p << "normal_file\t" << normal_file << std::endl;
     if (genotype) p << "genotype_anchor\t" << anchor << std::endl;
     if (vcf) p << "vcf\t1" << std::endl;
+    if (evidence) p << "evidence\t1" << std::endl;
   }
   clock_t end = clock();
   std::cout << "the fusion process of file " << inp_file << "  costs time: " << (end - start) / double(CLOCKS_PER_SEC) << " seconds" << std::endl;

@@ -1,0 +1,306 @@
+// The reads behind every call (bk_evidence): what bk_junctions counts, listed.  Count, scan, emit: the counts are
+// those of junctions() itself (junction.hip); an exclusive scan over the calls in BK_STAGE_CLUSTERS order gives every call its
+// range of rows; the rows are then written at ranks that depend on the data alone, so two runs give the same bytes:
+//   pair rows   the clustered list is sorted (stable, prims.h) by the call a list entry belongs to, so the entries of a call are
+//               neighbours in ascending list position = ascending BK_STAGE_CLUSTERED row (members of an AHC cluster need not be
+//               neighbours in the list itself); entry i of the sorted list is row i - pair_off[call] of its call
+//   split rows  one wavefront per voted cluster walks the tuple ranges of tuple_match.h in ascending tuple index, 64 at a time; a
+//               matching tuple's rank is the matches before it: a running count plus a ballot prefix
+// No atomic hands out a slot.  A row is three 16-byte stores.
+#include "evidence.h"
+#include "tuple_match.h"
+#include <cstddef>
+
+namespace
+{
+static_assert(sizeof(struct bk_evidence) == 48 && offsetof(struct bk_evidence, qcheck) == 16 && offsetof(struct bk_evidence, tid1) == 24 &&
+                  offsetof(struct bk_evidence, flag1) == 40 && offsetof(struct bk_evidence, kind) == 46 && offsetof(struct bk_evidence, sides) == 47,
+              "bk_evidence must be 48 bytes");
+
+__device__ __forceinline__ void store_row(struct bk_evidence *__restrict__ o, const struct bk_evidence &v)
+{
+  uint4 t[3];
+  __builtin_memcpy(t, &v, sizeof v);
+  uint4 *o4 = reinterpret_cast<uint4 *>(o);  // (rows start 16-byte aligned: 48-byte rows in a hipMalloc'ed array)
+  o4[0] = t[0];
+  o4[1] = t[1];
+  o4[2] = t[2];
+}
+
+// Device order of the cluster table is (numeric chr-pair key, id) (bp.hip: a slot is slotbase[group in key order] + id, and the rows
+// are the kept slots in slot order); BK_STAGE_CLUSTERS is its stable order by `group` (bk_fetch).  So the clusters of a group are
+// neighbours in both, and the final row of cluster c is gstart[group] + (c - first cluster of the group).  The kernels do not take
+// that on trust: every head of a run of equal `group` is counted, and a group with a second head ends the call with an error.
+__global__ __launch_bounds__(256) void k_ev_group_bounds(const uint32_t *__restrict__ grp, uint32_t ncl, uint32_t ng, uint32_t *__restrict__ first,
+                                                         uint32_t *__restrict__ last, uint32_t *__restrict__ heads, EvidenceStat *__restrict__ stat)
+{
+  const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= ncl) return;
+  const uint32_t g = grp[c];
+  if (g >= ng)
+  {
+    stat->bad = 1u;
+    return;
+  }
+  if (c == 0 || grp[c - 1] != g)
+  {
+    first[g] = c;
+    atomicAdd(&heads[g], 1u);  // (a count, whatever the order: a group has one run, so one head)
+  }
+  if (c == ncl - 1 || grp[c + 1] != g) last[g] = c + 1;
+}
+__global__ __launch_bounds__(256) void k_ev_group_sizes(const uint32_t *__restrict__ first, uint32_t *__restrict__ last, const uint32_t *__restrict__ heads, uint32_t ng,
+                                                        EvidenceStat *__restrict__ stat)
+{
+  const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= ng) return;
+  if (heads[g] > 1u) stat->bad = 1u;  // the clusters of group g are not neighbours: first / last mean nothing
+  last[g] -= first[g];  // (a group without clusters: 0 - 0)
+}
+__global__ __launch_bounds__(256) void k_ev_counts(const struct bk_junction *__restrict__ res, const uint32_t *__restrict__ grp, uint32_t ncl, uint32_t ng,
+                                                   const uint32_t *__restrict__ first, const uint32_t *__restrict__ gstart, uint32_t *__restrict__ fin,
+                                                   uint64_t *__restrict__ cnt, uint64_t *__restrict__ npair, EvidenceStat *__restrict__ stat)
+{
+  const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= ncl) return;
+  const uint32_t g = grp[c];
+  fin[c] = ncl;  // (no row)
+  if (g >= ng) return;
+  const uint32_t f = gstart[g] + (c - first[g]);
+  if (c < first[g] || f >= gstart[g + 1] || f >= ncl)
+  {
+    stat->bad = 1u;
+    return;
+  }
+  const struct bk_junction j = res[c];
+  const uint64_t np = (uint64_t) j.pairs[0] + j.pairs[1] + j.pairs[2] + j.pairs[3];
+  const uint64_t ns = (uint64_t) j.splits[0] + j.splits[1] + j.splits[2] + j.splits[3];
+  fin[c] = f;
+  cnt[f] = np + ns;
+  npair[f] = np;
+}
+
+// sort key of a list entry: the BK_STAGE_CLUSTERS row of its cluster, ncl for an entry whose cluster has no row (k_junction_pairs)
+__global__ __launch_bounds__(256) void k_ev_pair_keys(JunctionPairs in, uint32_t ncl, const uint32_t *__restrict__ fin, uint64_t *__restrict__ keys,
+                                                      uint32_t *__restrict__ vals)
+{
+  const uint64_t p = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= in.n) return;
+  const uint32_t s = in.slotbase[in.gof[p]] + in.cl[p];
+  uint32_t key = ncl;
+  if (s < in.slotbase[in.ng] && in.keep[s])
+  {
+    const uint32_t row = in.off[s];
+    if (row < ncl) key = fin[row];
+  }
+  keys[p] = key;
+  vals[p] = (uint32_t) p;
+}
+
+__global__ __launch_bounds__(256) void k_ev_emit_pairs(JunctionPairs in, const uint64_t *__restrict__ keys, const uint32_t *__restrict__ vals, uint32_t ncl,
+                                                       const uint64_t *__restrict__ call_off, const uint64_t *__restrict__ pair_off, EvidenceRecs recs,
+                                                       struct bk_evidence *__restrict__ rows, uint64_t n_rows, EvidenceStat *__restrict__ stat)
+{
+  const uint64_t i = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= in.n) return;
+  const uint64_t c = keys[i];
+  if (c >= ncl) return;
+  const uint64_t p0 = pair_off[c], p1 = pair_off[c + 1];
+  const uint64_t dest = call_off[c] + (i - p0);
+  const uint32_t p = vals[i];
+  if (i < p0 || i >= p1 || dest >= call_off[c + 1] || dest >= n_rows || p >= in.n)
+  {
+    stat->bad = 1u;
+    return;
+  }
+  const bk_pair pr = in.pairs[in.idx[p]];
+  struct bk_evidence v;
+  v.rec = pr.rec;
+  v.qhash = 0;
+  v.qcheck = 0;
+  if (pr.rec < recs.n)
+  {
+    if (recs.side)
+    {
+      v.qhash = recs.side[pr.rec].qhash;
+      v.qcheck = recs.side[pr.rec].qcheck;
+    }
+    else
+    {
+      v.qhash = recs.qhash[pr.rec];
+      v.qcheck = recs.qcheck ? recs.qcheck[pr.rec] : 0u;
+    }
+  }
+  else
+    stat->bad = 1u;
+  v.call = (uint32_t) c;
+  v.tid1 = pr.p1_tid;
+  v.pos1 = pr.p1_pos;
+  v.tid2 = pr.p2_tid;
+  v.pos2 = pr.p2_pos;
+  v.flag1 = pr.p1_flag;
+  v.flag2 = pr.p2_flag;
+  v.mapq1 = pr.p1_mapq;
+  v.mapq2 = pr.p2_mapq;
+  v.kind = BK_EV_PAIR;
+  v.sides = (uint8_t) (2u * (pr.p1_rev ? 1u : 0u) + (pr.p2_rev ? 1u : 0u));
+  store_row(rows + dest, v);
+}
+
+// One wave per cluster (device order).  The up to four tuple ranges are put in ascending order and walked as their union, so the
+// matches come in ascending BK_STAGE_SPLITS row; sides as in k_junction_sr.
+__global__ __launch_bounds__(256) void k_ev_emit_splits(const bk_split *__restrict__ sp, uint64_t nsp, const bk_cluster *__restrict__ cl, uint32_t ncl, int maxspan,
+                                                        const int32_t *__restrict__ hdr_id, const int32_t *__restrict__ own_id, int32_t nt, int32_t empty_id,
+                                                        const uint32_t *__restrict__ fin, const uint64_t *__restrict__ call_off, const uint64_t *__restrict__ pair_off,
+                                                        EvidenceRecs recs, struct bk_evidence *__restrict__ rows, uint64_t n_rows, EvidenceStat *__restrict__ stat)
+{
+  const uint32_t c = blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (c >= ncl) return;
+  const bk_cluster k = cl[c];
+  if (!(k.flags & 2u)) return;
+  const uint32_t f = fin[c];
+  if (f >= ncl) return;
+  const uint64_t base = call_off[f] + (pair_off[f + 1] - pair_off[f]), limit = call_off[f + 1];
+  const TupleRanges r = tuple_ranges(sp, nsp, k, maxspan, hdr_id, own_id, nt, empty_id);
+  uint64_t lo[4], hi[4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q)
+  {
+    const bool some = r.hi[q] > r.lo[q];
+    lo[q] = some ? r.lo[q] : ~0ull;  // (empty ranges go last)
+    hi[q] = some ? r.hi[q] : ~0ull;
+  }
+  auto order = [&](int a, int b) {
+    if (lo[b] < lo[a])
+    {
+      const uint64_t tl = lo[a], th = hi[a];
+      lo[a] = lo[b];
+      hi[a] = hi[b];
+      lo[b] = tl;
+      hi[b] = th;
+    }
+  };
+  order(0, 1);
+  order(2, 3);
+  order(0, 2);
+  order(1, 3);
+  order(1, 2);
+  const uint64_t below = (1ull << lane) - 1ull;
+  uint64_t done = 0, n_out = 0;
+  uint32_t visited = 0;
+#pragma unroll
+  for (int q = 0; q < 4; ++q)
+  {
+    if (lo[q] == ~0ull) continue;
+    const uint64_t a = lo[q] > done ? lo[q] : done, e = hi[q];
+    for (uint64_t t0 = a; t0 < e; t0 += 64)  // (the same trip count on every lane)
+    {
+      const uint64_t t = t0 + lane;
+      int side = 0;
+      bk_split s;
+      if (t < e)
+      {
+        s = sp[t];
+        side = tuple_side(s, r, k);
+      }
+      const uint64_t m = __ballot(side != 0);
+      if (side)
+      {
+        const uint64_t dest = base + n_out + (uint64_t) __popcll(m & below);
+        if (dest >= limit || dest >= n_rows)
+          stat->bad = 1u;
+        else
+        {
+          const bool swapped = side == 2;
+          const uint32_t rp = s.prim_bp == s.prim_start ? 1u : 0u, rs = s.sec_bp == s.sec_start ? 1u : 0u;
+          struct bk_evidence v;
+          v.rec = s.rec;
+          v.qhash = s.qhash;
+          v.qcheck = s.qcheck;
+          v.call = f;
+          v.tid1 = k.p1_tid;
+          v.pos1 = swapped ? s.sec_bp : s.prim_bp;
+          v.tid2 = k.p2_tid;
+          v.pos2 = swapped ? s.prim_bp : s.sec_bp;
+          v.flag1 = (uint16_t) (s.flags & 0xFFFFu);
+          v.flag2 = swapped ? 1 : 0;
+          v.mapq1 = 0;
+          if (s.rec < recs.n)
+            v.mapq1 = recs.mapq[s.rec];
+          else
+            stat->bad = 1u;
+          v.mapq2 = 0;
+          v.kind = BK_EV_SPLIT;
+          v.sides = (uint8_t) (swapped ? 2u * rs + rp : 2u * rp + rs);  // side 1 is prim unless the tuple names the pair the other way round
+          store_row(rows + dest, v);
+        }
+      }
+      n_out += (uint64_t) __popcll(m);
+    }
+    if (e > a) visited += (uint32_t) (e - a);
+    if (e > done) done = e;
+  }
+  if (lane == 0)
+  {
+    if (base + n_out != limit) stat->bad = 1u;  // the listing and the count of k_junction_sr disagree
+    if (visited) atomicAdd(&stat->visited, (unsigned long long) visited);  // (a statistic for the byte model, not a slot)
+  }
+}
+}  // namespace
+
+void evidence(const JunctionPairs &p, const bk_split *sp, uint64_t nsp, const bk_cluster *cl, uint64_t ncl, uint32_t ng, int maxspan, const int32_t *hdr_id,
+              const int32_t *own_id, int32_t nt, int32_t empty_id, const EvidenceRecs &recs, EvidenceBufs &b, hipStream_t st, struct bk_evidence **rows_out,
+              uint64_t **call_off_out, EvidenceStat **stat_out)
+{
+  uint64_t *call_off = b.call_off.as<uint64_t>(ncl + 1);
+  EvidenceStat *stat = b.stat.as<EvidenceStat>(1);
+  *call_off_out = call_off;
+  *stat_out = stat;
+  *rows_out = b.rows.as<struct bk_evidence>(1);
+  HIP_CHECK(hipMemsetAsync(stat, 0, sizeof(EvidenceStat), st));
+  if (ncl == 0)
+  {
+    HIP_CHECK(hipMemsetAsync(call_off, 0, sizeof(uint64_t), st));
+    return;
+  }
+  if (ncl > 0x7FFFFFFFull) throw bk_error(BK_ERR_LIMIT, "too many clusters");
+  if (p.n > 0xFFFFFFF0ull) throw bk_error(BK_ERR_LIMIT, "too many clustered pairs");
+  const uint32_t n32 = (uint32_t) ncl;
+  struct bk_junction *res;
+  uint32_t *grp, *vis;
+  junctions(p, sp, nsp, cl, ncl, maxspan, hdr_id, own_id, nt, empty_id, b.jn, st, &res, &grp, &vis);
+  // every cluster's row in BK_STAGE_CLUSTERS order, its counts there, the two scans
+  uint32_t *first = b.first.as<uint32_t>((uint64_t) ng + 1), *last = b.last.as<uint32_t>((uint64_t) ng + 1), *gstart = b.gstart.as<uint32_t>((uint64_t) ng + 1);
+  uint32_t *fin = b.fin.as<uint32_t>(ncl), *heads = b.heads.as<uint32_t>((uint64_t) ng + 1);
+  uint64_t *cnt = b.cnt.as<uint64_t>(ncl + 1), *npair = b.npair.as<uint64_t>(ncl + 1), *pair_off = b.pair_off.as<uint64_t>(ncl + 1);
+  HIP_CHECK(hipMemsetAsync(first, 0, ((uint64_t) ng + 1) * 4, st));
+  HIP_CHECK(hipMemsetAsync(last, 0, ((uint64_t) ng + 1) * 4, st));
+  HIP_CHECK(hipMemsetAsync(heads, 0, ((uint64_t) ng + 1) * 4, st));
+  HIP_CHECK(hipMemsetAsync(cnt, 0, (ncl + 1) * 8, st));
+  HIP_CHECK(hipMemsetAsync(npair, 0, (ncl + 1) * 8, st));
+  hipLaunchKernelGGL(k_ev_group_bounds, dim3(cdiv(ncl, 256)), dim3(256), 0, st, grp, n32, ng, first, last, heads, stat);
+  hipLaunchKernelGGL(k_ev_group_sizes, dim3(cdiv(ng, 256)), dim3(256), 0, st, first, last, heads, ng, stat);
+  prims::exclusive_scan<uint32_t>(last, gstart, ng, b.scan_tmp, st);
+  hipLaunchKernelGGL(k_ev_counts, dim3(cdiv(ncl, 256)), dim3(256), 0, st, res, grp, n32, ng, first, gstart, fin, cnt, npair, stat);
+  prims::exclusive_scan<uint64_t>(cnt, call_off, ncl, b.scan_tmp, st);
+  prims::exclusive_scan<uint64_t>(npair, pair_off, ncl, b.scan_tmp, st);
+  uint64_t total = 0;
+  HIP_CHECK(hipMemcpyAsync(&total, call_off + ncl, 8, hipMemcpyDeviceToHost, st));
+  HIP_CHECK(hipStreamSynchronize(st));  // the row count sizes the output
+  struct bk_evidence *rows = b.rows.as<struct bk_evidence>(total + 1);
+  *rows_out = rows;
+  if (total == 0) return;
+  if (p.n)
+  {
+    uint64_t *keys = b.keys.as<uint64_t>(p.n);
+    uint32_t *vals = b.vals.as<uint32_t>(p.n);
+    hipLaunchKernelGGL(k_ev_pair_keys, dim3(cdiv(p.n, 256)), dim3(256), 0, st, p, n32, fin, keys, vals);
+    int bits = 1;
+    while ((ncl >> bits) != 0) ++bits;  // keys are 0 .. ncl
+    prims::radix_sort_pairs(keys, vals, p.n, 0, bits, b.radix, st, &keys, &vals);
+    hipLaunchKernelGGL(k_ev_emit_pairs, dim3(cdiv(p.n, 256)), dim3(256), 0, st, p, keys, vals, n32, call_off, pair_off, recs, rows, total, stat);
+  }
+  hipLaunchKernelGGL(k_ev_emit_splits, dim3(cdiv(ncl, 4)), dim3(256), 0, st, sp, nsp, cl, n32, maxspan, hdr_id, own_id, nt, empty_id, fin, call_off, pair_off, recs, rows,
+                     total, stat);
+}

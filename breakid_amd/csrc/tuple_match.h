@@ -1,5 +1,5 @@
-// The tuple search shared by bk_normal_support's n_sr (normal.hip) and bk_junctions' splits[] (junction.hip): the split-evidence
-// tuples that carry a voted cluster's breakpoint pair.  One wavefront per cluster; every lane calls with the same arguments.
+// The tuple search shared by bk_normal_support's n_sr (normal.hip), bk_junctions' splits[] (junction.hip) and bk_evidence's split rows
+// (evidence.hip): the split-evidence tuples that carry a voted cluster's breakpoint pair.  One wavefront per cluster; every lane calls with the same arguments.
 #pragma once
 #include "bk_common.h"
 #include "bp.h"
@@ -24,51 +24,70 @@ __device__ __forceinline__ uint64_t tuple_lower(const bk_split *__restrict__ sp,
 // breakpoint e it is compared with.  The own side's chromosome id is own_id[tid] (the reference's chromID2ChrName of the tid), so
 // a record on chromosome T can stand for p1 (around p1_exact) when own_id[T] == c1 and for p2 (around p2_exact) when own_id[T] ==
 // c2: up to four ranges, (p1_tid | p2_tid) x (p1_exact | p2_exact); two for a header that lists chr1..chr22, chrX, chrY first and
-// in that order (own_id[T] == c(T)).  A range skips the indices of the ranges before it: a tuple is visited once.
-// `hit(s, swapped)` runs on the lane that holds a matching tuple s: swapped == false when (prim, sec) is (p1, p2), true when it is
-// (p2, p1) and not also (p1, p2).  Returns the number of tuples the wave looked at (the same value on every lane).
-template <class Hit>
-__device__ __forceinline__ uint32_t for_matching_tuples(const bk_split *__restrict__ sp, uint64_t nsp, const bk_cluster &k, int maxspan,
-                                                        const int32_t *__restrict__ hdr_id, const int32_t *__restrict__ own_id, int32_t nt, int32_t empty_id, Hit hit)
+// in that order (own_id[T] == c(T)).  The ranges may overlap: whoever walks them visits a tuple once.
+// The up to four index ranges of a cluster (empty: lo == hi) and the interned ids of its two chromosomes.
+struct TupleRanges
 {
-  const int lane = threadIdx.x & 63;
-  const long long e1 = (long long) k.p1_exact, e2 = (long long) k.p2_exact;
-  const int32_t c1 = hdr_id[k.p1_tid + 1], c2 = hdr_id[k.p2_tid + 1];  // interned chromosome ids, as the vote compares them (k_bp_vote)
   uint64_t lo[4], hi[4];
-  bool on[4];
+  int32_t c1, c2;
+};
+__device__ __forceinline__ TupleRanges tuple_ranges(const bk_split *__restrict__ sp, uint64_t nsp, const bk_cluster &k, int maxspan, const int32_t *__restrict__ hdr_id,
+                                                    const int32_t *__restrict__ own_id, int32_t nt, int32_t empty_id)
+{
+  TupleRanges r;
+  const long long e1 = (long long) k.p1_exact, e2 = (long long) k.p2_exact;
+  r.c1 = hdr_id[k.p1_tid + 1];  // interned chromosome ids, as the vote compares them (k_bp_vote)
+  r.c2 = hdr_id[k.p2_tid + 1];
 #pragma unroll
   for (int q = 0; q < 4; ++q)
   {
     const int32_t T = (q >> 1) ? k.p2_tid : k.p1_tid;  // the tuple's own record lies on T ...
     const long long e = (q & 1) ? e2 : e1;           // ... and its own breakpoint is compared with e
     const int32_t own = (T >= 0 && T < nt) ? own_id[T] : empty_id;
-    on[q] = own == ((q & 1) ? c2 : c1) && !((q >> 1) && k.p1_tid == k.p2_tid);  // (one chromosome: q = 2, 3 repeat q = 0, 1)
-    lo[q] = hi[q] = 0;
-    if (on[q])
+    const bool on = own == ((q & 1) ? r.c2 : r.c1) && !((q >> 1) && k.p1_tid == k.p2_tid);  // (one chromosome: q = 2, 3 repeat q = 0, 1)
+    r.lo[q] = r.hi[q] = 0;
+    if (on)
     {
-      lo[q] = tuple_lower(sp, nsp, T, e - 2 - maxspan);
-      hi[q] = tuple_lower(sp, nsp, T, e + 3);
+      r.lo[q] = tuple_lower(sp, nsp, T, e - 2 - maxspan);
+      r.hi[q] = tuple_lower(sp, nsp, T, e + 3);
     }
   }
+  return r;
+}
+// 0: the tuple does not carry the breakpoint pair; 1: (prim, sec) is (p1, p2); 2: it is (p2, p1) and not also (p1, p2)
+__device__ __forceinline__ int tuple_side(const bk_split &s, const TupleRanges &r, const bk_cluster &k)
+{
+  if (s.flags & 2u) return 0;  // "error cigar" tuple
+  const long long e1 = (long long) k.p1_exact, e2 = (long long) k.p2_exact;
+  const int32_t pc = s.prim_chr, sc = s.sec_chr;
+  const uint32_t pb = s.prim_bp, sb = s.sec_bp;
+  if (pc == r.c1 && sc == r.c2 && near2(pb, e1) && near2(sb, e2)) return 1;
+  if (pc == r.c2 && sc == r.c1 && near2(pb, e2) && near2(sb, e1)) return 2;
+  return 0;
+}
+// Walks the ranges, a range skipping the indices of the ranges before it.  `hit(s, swapped)` runs on the lane that holds a matching
+// tuple s: swapped == false when (prim, sec) is (p1, p2), true when it is (p2, p1) and not also (p1, p2).  Returns the number of
+// tuples the wave looked at (the same value on every lane).
+template <class Hit>
+__device__ __forceinline__ uint32_t for_matching_tuples(const bk_split *__restrict__ sp, uint64_t nsp, const bk_cluster &k, int maxspan,
+                                                        const int32_t *__restrict__ hdr_id, const int32_t *__restrict__ own_id, int32_t nt, int32_t empty_id, Hit hit)
+{
+  const int lane = threadIdx.x & 63;
+  const TupleRanges r = tuple_ranges(sp, nsp, k, maxspan, hdr_id, own_id, nt, empty_id);
   uint32_t visited = 0;
 #pragma unroll
   for (int q = 0; q < 4; ++q)
   {
-    visited += hi[q] > lo[q] ? (uint32_t) (hi[q] - lo[q]) : 0u;
-    for (uint64_t t = lo[q] + lane; t < hi[q]; t += 64)
+    visited += r.hi[q] > r.lo[q] ? (uint32_t) (r.hi[q] - r.lo[q]) : 0u;
+    for (uint64_t t = r.lo[q] + lane; t < r.hi[q]; t += 64)
     {
       bool seen = false;
 #pragma unroll
-      for (int p = 0; p < q; ++p) seen |= t >= lo[p] && t < hi[p];
+      for (int p = 0; p < q; ++p) seen |= t >= r.lo[p] && t < r.hi[p];
       if (seen) continue;
       const bk_split &s = sp[t];
-      if (s.flags & 2u) continue;  // "error cigar" tuple
-      const int32_t pc = s.prim_chr, sc = s.sec_chr;
-      const uint32_t pb = s.prim_bp, sb = s.sec_bp;
-      if (pc == c1 && sc == c2 && near2(pb, e1) && near2(sb, e2))
-        hit(s, false);
-      else if (pc == c2 && sc == c1 && near2(pb, e2) && near2(sb, e1))
-        hit(s, true);
+      const int side = tuple_side(s, r, k);
+      if (side) hit(s, side == 2);
     }
   }
   return visited;

@@ -288,6 +288,38 @@ int bk_junction_sides(const struct bk_junction *j, uint8_t *right1, uint8_t *rig
  * ]chr:pos]N, (right, right): [chr:pos[N.  BK_ERR_ARG for a null mate_chr or buf, or a buffer too small for the text and its NUL. */
 int bk_vcf_breakend_alt(char ref_base, int own_right, const char *mate_chr, uint32_t mate_pos, int mate_right, char *buf, size_t cap);
 
+/* ---- evidence export: the reads behind every call -----------------------------------------------------------------------
+ * bk_junctions counts a cluster's member pairs and, for a voted cluster, its matching tuples; bk_evidence lists the same rows, one
+ * bk_evidence row each.  Membership is exactly that of bk_junctions (above): a BK_EV_PAIR row for every member pair of every
+ * BK_STAGE_CLUSTERS row, voted or not, and a BK_EV_SPLIT row for every matching tuple of a voted one, side 1 and side 2 assigned
+ * as there (the first orientation wins when both hold).  So, per call, the BK_EV_PAIR rows number n_drp, their histogram over
+ * `sides` is bk_junction.pairs, and that of the BK_EV_SPLIT rows is bk_junction.splits.
+ * Order (part of the contract; two runs give the same bytes): by `call` ascending, within a call pairs before splits, pairs in
+ * ascending BK_STAGE_CLUSTERED row, splits in ascending BK_STAGE_SPLITS row.  call_off[c] .. call_off[c + 1] bounds call c.
+ * A read name is not kept on the device: a row carries its two hashes (qhash, qcheck), which bk_bam_extract turns back into names
+ * and records.  The struct has no typedef: the name belongs to the call below. */
+#define BK_EV_PAIR 1
+#define BK_EV_SPLIT 2
+struct bk_evidence {
+  uint64_t rec;               /* pair: bk_pair.rec; split: bk_split.rec */
+  uint64_t qhash;             /* pair: qhash of record `rec` of the context's table; split: bk_split.qhash */
+  uint32_t qcheck;            /* likewise (0 when the table has no qcheck) */
+  uint32_t call;              /* row in BK_STAGE_CLUSTERS */
+  int32_t tid1; uint32_t pos1; /* pair: p1_tid, p1_pos (1-based); split: the call's p1_tid and the tuple's breakpoint on side 1 */
+  int32_t tid2; uint32_t pos2; /* pair: p2_tid, p2_pos; split: p2_tid and the tuple's breakpoint on side 2 */
+  uint16_t flag1, flag2;      /* pair: p1_flag, p2_flag; split: low 16 bits of bk_split.flags, and 1 if (prim, sec) = (side 2, side 1) else 0 */
+  uint8_t mapq1, mapq2;       /* pair: p1_mapq, p2_mapq; split: mapq of record `rec`, 0 */
+  uint8_t kind;               /* BK_EV_PAIR / BK_EV_SPLIT */
+  uint8_t sides;              /* pair: 2 * p1_rev + p2_rev; split: 2 * right1 + right2, as bk_junction.splits is indexed */
+};                            /* 48 bytes */
+/* ctx: as for bk_junctions (after bk_split_breakpoints, the lists still in place, not a shard).  *out (count rows) and *call_off
+ * (n_clusters + 1 entries) are library-owned until the next call or bk_free(ctx).  BK_ERR_ARG (with the reason in bk_last_error) for
+ * wrong call order, null arguments and shards.  It changes nothing a later bk_fetch or stage returns, and works on every table
+ * form the context can hold (host upload, BK_MEM_DEVICE with and without `side`, the table bk_exclude_regions left behind, the
+ * context of bk_bam_decode_device_ctx while its bk_bam_dev lives).  A context without clusters is no error: *count = 0 and
+ * call_off has its one entry, 0. */
+int bk_evidence(bk_ctx *ctx, const struct bk_evidence **out, uint64_t *count, const uint64_t **call_off);
+
 /* Copy a stage's result to library-owned host memory.  *data stays valid until the next bk_fetch
  * of the same stage or bk_free.  group_off (may be NULL) receives n_groups+1 offsets for pair stages. */
 int bk_fetch(bk_ctx *ctx, int stage, const void **data, uint64_t *count, const uint64_t **group_off, uint32_t *n_groups);
@@ -403,6 +435,25 @@ int bk_bam_header(const bk_bam *b, int *n_targets, const char *const **names, co
 /* decode all records into a SoA owned by the bk_bam (pinned when a GPU is present) */
 int bk_bam_decode(bk_bam *b, bk_soa *out, char *err, size_t errlen);
 void bk_bam_close(bk_bam *b);
+/* Read names back from their hashes, and the reads themselves: one streaming pass over in_bam (read in chunks, inflated block by
+ * block, a record that crosses BGZF blocks carried over: both file layouts; memory is bounded by the chunk, the longest record and
+ * the keys - the inflated file is never held).  A record is selected when its read name (the C string, as the decoders hash it) has
+ * bk_qname_hash == keys[k].qhash and, unless keys[k].qcheck is 0, bk_qname_check == keys[k].qcheck: both mates and every secondary
+ * and supplementary alignment of that name.  names_out (may be NULL) receives n_keys NUL-terminated names back to back in key order,
+ * "" for a key no record matched; free it with bk_bam_names_free.  out_bam (may be NULL: names only, no file) receives the selected
+ * records in file order (the output stays coordinate sorted) behind the input's header bytes, unchanged (text, reference names and
+ * lengths); every record gets bk:Z:<tags[keys[k].tag]> appended to its aux data, its block_size corrected.  BGZF as htslib writes it:
+ * at most 0xff00 payload bytes per block, a block is flushed before a record that would not fit, a longer record spans blocks, the
+ * 28-byte EOF block comes last.  The file is written under a temporary name in the target directory and renamed on success; on any
+ * failure no output file exists.  n_written (may be NULL): records selected.  An empty key set gives a header-only BAM.
+ * BK_ERR_ARG: null in_bam, null keys or tags with a non-zero count, duplicate keys (equal qhash and qcheck), tag >= n_tags.
+ * BK_ERR_IO: unreadable or truncated input, a bad BGZF block, a record longer than its stream, an unwritable output.  The text
+ * is in err.  Limits: a record that already carries a bk tag gets a second one; two different names that agree in all 96 hash
+ * bits are both written (and the key's name is that of the first of them in the file). */
+typedef struct bk_read_key { uint64_t qhash; uint32_t qcheck; uint32_t tag; } bk_read_key; /* tag: index into tags[] */
+int bk_bam_extract(const char *in_bam, const char *out_bam, const bk_read_key *keys, uint64_t n_keys, const char *const *tags, uint64_t n_tags, char **names_out,
+                   uint64_t *n_written, char *err, size_t errlen);
+void bk_bam_names_free(char *names);
 
 /* The same feed on the GPU: BGZF blocks are inflated on the device (bgzf_gpu.hip) and the records are decoded into
  * device-resident columns (cols holds device pointers: bk_upload_records(ctx, cols, BK_MEM_DEVICE)).
