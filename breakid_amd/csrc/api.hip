@@ -100,7 +100,7 @@ struct bk_ctx
   JoinResult jr;
   std::vector<uint32_t> gkey_host, glex_host, lex_to_num;
   std::vector<uint64_t> gstart_host;
-  DevBuf d_glex;
+  DevBuf d_glex, d_lex_to_num;  // device copies of glex_host and lex_to_num (cluster_summary numbers the slots in lexicographic group order)
 
   // mask + cluster (lanes.hip): the lists and cluster numbers it leaves, its lanes, its sort service
   ClusterStage stage;
@@ -208,6 +208,14 @@ template <class F> int guarded(bk_ctx *ctx, F &&f)
     ctx->err = e.what();
     return BK_ERR_HIP;
   }
+}
+
+// n device rows into `out`; returns when they (and every copy queued before them) have arrived
+template <class T> void rows_to_host(bk_ctx *ctx, const T *d_rows, uint64_t n, std::vector<T> &out)
+{
+  out.resize(n);
+  if (n) HIP_CHECK(hipMemcpyAsync(out.data(), d_rows, n * sizeof(T), hipMemcpyDeviceToHost, ctx->st));
+  HIP_CHECK(hipStreamSynchronize(ctx->st));
 }
 
 void build_name_tables(bk_ctx *c)
@@ -693,8 +701,9 @@ static void finish_groups(bk_ctx *ctx, const std::vector<uint32_t> *all_keys)
       ctx->glex_host[g] = (uint32_t) (it - names.begin());
     }
   }
-  uint32_t *dg = ctx->d_glex.as<uint32_t>((uint64_t) ng + 1);
+  uint32_t *dg = ctx->d_glex.as<uint32_t>((uint64_t) ng + 1), *dl = ctx->d_lex_to_num.as<uint32_t>((uint64_t) ng + 1);
   if (ng) HIP_CHECK(hipMemcpyAsync(dg, ctx->glex_host.data(), ng * 4, hipMemcpyHostToDevice, ctx->st));
+  if (ng) HIP_CHECK(hipMemcpyAsync(dl, ctx->lex_to_num.data(), ng * 4, hipMemcpyHostToDevice, ctx->st));
   join_assign_ids(ctx->jr, dg, ctx->st);
 }
 
@@ -756,9 +765,11 @@ int bk_cluster_summary(bk_ctx *ctx, double w, uint64_t *n_clusters)
   return guarded(ctx, [&] {
     if (!ctx->clustered) throw bk_error(BK_ERR_ARG, "bk_cluster_summary: call bk_mask_and_cluster first");
     ctx->bp_done = false;
+    // (lex_to_num, glex and gkey are tables over the groups of the join; the list's groups are the same ones: lanes.hip)
+    if (ctx->stage.list.ng != ctx->jr.n_groups) throw bk_error(BK_ERR_HIP, "bk_cluster_summary: the clustered list and the join disagree on the groups (internal error)");
     Scope s(ctx, "cluster_summary");
     ctx->n_clusters = cluster_summary(ctx->jr.pairs, ctx->stage.list.idx.get<uint32_t>(), ctx->stage.list.gof.get<uint32_t>(), ctx->stage.d_cluster.get<uint32_t>(), ctx->stage.list.n,
-                                      ctx->stage.list.ng, ctx->jr.gkey, ctx->d_glex.get<uint32_t>(), ctx->nt, w, ctx->d_clusters, ctx->bb, ctx->st);
+                                      ctx->stage.list.ng, ctx->jr.gkey, ctx->d_glex.get<uint32_t>(), ctx->d_lex_to_num.get<uint32_t>(), ctx->nt, w, ctx->d_clusters, ctx->bb, ctx->st);
     ctx->summary_map = true;
     if (n_clusters) *n_clusters = ctx->n_clusters;
   });
@@ -782,6 +793,41 @@ int bk_split_breakpoints(bk_ctx *ctx, double w, uint64_t *n_valid)
   });
 }
 
+// ---- the frame of the per-call outputs (bk_normal_support, bk_ref_support, bk_junctions, bk_evidence) -----------------------------
+// Each runs one wave per row of the device cluster table and returns one row per call.  The table is in BK_STAGE_CLUSTERS order
+// (bp.hip, cluster_summary), so the rows go to the caller as the kernels wrote them.
+static TupleTable tuple_table(const bk_ctx *ctx)
+{
+  return TupleTable{ctx->d_split.get<bk_split>(), ctx->hc.n_split, (int) ctx->hc.max_span, ctx->d_hdr.get<int32_t>(), ctx->names.own_id, ctx->nt, ctx->names.empty_id};
+}
+// the clustered list and the slot -> row map of the last bk_cluster_summary
+static JunctionPairs junction_pairs(const bk_ctx *ctx)
+{
+  JunctionPairs jp{};
+  if (ctx->n_clusters)  // (no cluster: bk_cluster_summary may have returned before it built the map)
+  {
+    jp.pairs = ctx->jr.pairs;
+    jp.idx = ctx->stage.list.idx.get<uint32_t>();
+    jp.gof = ctx->stage.list.gof.get<uint32_t>();
+    jp.cl = ctx->stage.d_cluster.get<uint32_t>();
+    jp.n = ctx->stage.list.n;
+    jp.ng = ctx->stage.list.ng;
+    jp.slotbase = ctx->bb.slotbase.get<uint32_t>();
+    jp.keep = ctx->bb.keep.get<uint32_t>();
+    jp.off = ctx->bb.off.get<uint32_t>();
+  }
+  return jp;
+}
+// two contexts of one call: the same device and the same reference list
+static void require_same_reference(const std::string &who, const char *role_a, const bk_ctx *a, const char *role_b, const bk_ctx *b)
+{
+  if (b->device != a->device)
+    throw bk_error(BK_ERR_ARG, who + ": " + role_a + " (device " + std::to_string(a->device) + ") and " + role_b + " (device " + std::to_string(b->device) +
+                                   ") contexts are on different devices");
+  if (b != a && (b->nt != a->nt || b->tname != a->tname || b->tlen != a->tlen))
+    throw bk_error(BK_ERR_ARG, who + ": " + role_a + " and " + role_b + " reference lists differ (names or lengths)");
+}
+
 int bk_normal_support(bk_ctx *tumor, bk_ctx *normal, double w, const struct bk_normal_support **out, uint64_t *count)
 {
   if (!normal) return guarded(tumor, [&] { throw bk_error(BK_ERR_ARG, "bk_normal_support: null normal context"); });
@@ -794,43 +840,14 @@ int bk_normal_support(bk_ctx *tumor, bk_ctx *normal, double w, const struct bk_n
     if (tumor->join_w != w) throw bk_error(BK_ERR_ARG, "bk_normal_support: w is not the tumour's distance (its bk_discordant_pairs w)");
     if (normal->stream_mapq != tumor->stream_mapq || normal->join_w != w)
       throw bk_error(BK_ERR_ARG, "bk_normal_support: the normal's bk_discordant_pairs must use the tumour's mapq_min and w");
-    if (normal->device != tumor->device)
-      throw bk_error(BK_ERR_ARG, "bk_normal_support: tumour (device " + std::to_string(tumor->device) + ") and normal (device " + std::to_string(normal->device) +
-                                     ") contexts are on different devices");
-    if (normal->nt != tumor->nt || normal->tname != tumor->tname || normal->tlen != tumor->tlen)
-      throw bk_error(BK_ERR_ARG, "bk_normal_support: tumour and normal reference lists differ (names or lengths)");
+    require_same_reference("bk_normal_support", "tumour", tumor, "normal", normal);
     Scope s(tumor, "normal_support");
     HIP_CHECK(hipStreamSynchronize(normal->st));  // the normal's stages ran on its own stream
-    NormalSide ns;
-    ns.pairs = normal->jr.pairs;
-    ns.n_pairs = normal->jr.n_pairs;
-    ns.sp = normal->d_split.get<bk_split>();
-    ns.n_split = normal->hc.n_split;
-    ns.rec = rec_view(normal);
-    ns.maxspan = (int) normal->hc.max_span;
-    ns.hdr_id = normal->d_hdr.get<int32_t>();
-    ns.own_id = normal->names.own_id;
-    ns.empty_id = normal->names.empty_id;
+    const NormalSide ns{normal->jr.pairs, normal->jr.n_pairs, tuple_table(normal), rec_view(normal)};
     const uint64_t ncl = tumor->n_clusters;
     struct bk_normal_support *d_res;
-    uint32_t *d_grp;
-    normal_support(ns, tumor->clusters_ptr(), ncl, tumor->nt, w, tumor->nb, tumor->st, &d_res, &d_grp);
-    std::vector<struct bk_normal_support> res(ncl);
-    std::vector<uint32_t> grp(ncl);
-    if (ncl)
-    {
-      HIP_CHECK(hipMemcpyAsync(res.data(), d_res, ncl * sizeof(struct bk_normal_support), hipMemcpyDeviceToHost, tumor->st));
-      HIP_CHECK(hipMemcpyAsync(grp.data(), d_grp, ncl * 4, hipMemcpyDeviceToHost, tumor->st));
-    }
-    HIP_CHECK(hipStreamSynchronize(tumor->st));
-    // device order is (numeric chr-pair key, id); BK_STAGE_CLUSTERS is the stable order by `group` (bk_fetch): a counting sort
-    uint32_t gmax = 0;
-    for (uint32_t g : grp) gmax = std::max(gmax, g);
-    std::vector<uint64_t> start(ncl ? (size_t) gmax + 2 : 1, 0);
-    for (uint32_t g : grp) ++start[g + 1];
-    for (size_t g = 1; g < start.size(); ++g) start[g] += start[g - 1];
-    tumor->f_normal.resize(ncl);
-    for (uint64_t c = 0; c < ncl; ++c) tumor->f_normal[start[grp[c]]++] = res[c];
+    normal_support(ns, tumor->clusters_ptr(), ncl, w, tumor->nb, tumor->st, &d_res);
+    rows_to_host(tumor, d_res, ncl, tumor->f_normal);
     *out = tumor->f_normal.data();
     *count = ncl;
   });
@@ -847,38 +864,26 @@ int bk_ref_support(bk_ctx *calls, bk_ctx *records, int mapq_min, int anchor, dou
     if (anchor < 0) throw bk_error(BK_ERR_ARG, "bk_ref_support: anchor must not be negative");
     if (mapq_min < 0) throw bk_error(BK_ERR_ARG, "bk_ref_support: mapq_min must not be negative");
     if (!(w >= 0.0 && w < 2147483648.0)) throw bk_error(BK_ERR_ARG, "bk_ref_support: w is out of range");
-    if (records->device != calls->device)
-      throw bk_error(BK_ERR_ARG, "bk_ref_support: calls (device " + std::to_string(calls->device) + ") and records (device " + std::to_string(records->device) +
-                                     ") contexts are on different devices");
-    if (records != calls && (records->nt != calls->nt || records->tname != calls->tname || records->tlen != calls->tlen))
-      throw bk_error(BK_ERR_ARG, "bk_ref_support: calls and records reference lists differ (names or lengths)");
+    require_same_reference("bk_ref_support", "calls", calls, "records", records);
     const bk_soa &t = records->rec;
     if (t.n && (!t.tid || !t.pos || !t.isize || !t.flag || !t.mapq || !t.cigar_off || !t.aux_off))
       throw bk_error(BK_ERR_ARG, "bk_ref_support: the record table lacks a column");
     const uint64_t ncl = calls->n_clusters;
     if (records != calls) HIP_CHECK(hipStreamSynchronize(records->st));  // its stages ran on its own stream
     struct bk_ref_support *d_res;
-    uint32_t *d_grp;
     RefStat *d_stat = nullptr;
     {
       Scope s(calls, "ref_support");  // the device work alone: the copies below would hide it
-      ref_support(rec_view(records), (int) records->hc.max_span, calls->clusters_ptr(), ncl, mapq_min, anchor, w, calls->rb, calls->st, &d_res, &d_grp,
+      ref_support(rec_view(records), (int) records->hc.max_span, calls->clusters_ptr(), ncl, mapq_min, anchor, w, calls->rb, calls->st, &d_res,
                   calls->timing ? &d_stat : nullptr);
     }
-    std::vector<struct bk_ref_support> res(ncl);
-    std::vector<uint32_t> grp(ncl);
     std::vector<RefStat> stat(d_stat ? 2 * ncl : 0);
-    if (ncl)
-    {
-      HIP_CHECK(hipMemcpyAsync(res.data(), d_res, ncl * sizeof(struct bk_ref_support), hipMemcpyDeviceToHost, calls->st));
-      HIP_CHECK(hipMemcpyAsync(grp.data(), d_grp, ncl * 4, hipMemcpyDeviceToHost, calls->st));
-      if (d_stat) HIP_CHECK(hipMemcpyAsync(stat.data(), d_stat, 2 * ncl * sizeof(RefStat), hipMemcpyDeviceToHost, calls->st));
-    }
-    HIP_CHECK(hipStreamSynchronize(calls->st));
+    if (!stat.empty()) HIP_CHECK(hipMemcpyAsync(stat.data(), d_stat, 2 * ncl * sizeof(RefStat), hipMemcpyDeviceToHost, calls->st));
+    rows_to_host(calls, d_res, ncl, calls->f_ref);
     if (calls->timing && !calls->timers.empty())
     {
       // bytes: pos, flag, mapq, isize and two aux_off words of every record of a window (19 B each; bytes / 19 = records visited).
-      // touched: those, the CIGAR words that were walked, and per call two bk_cluster reads (one per side), the row and its group.
+      // touched: those, the CIGAR words that were walked, and per call two bk_cluster reads (one per side) and the row.
       uint64_t visited = 0, words = 0;
       for (const RefStat &x : stat)
       {
@@ -886,16 +891,8 @@ int bk_ref_support(bk_ctx *calls, bk_ctx *records, int mapq_min, int anchor, dou
         words += x.words;
       }
       calls->timers.back().bytes = 19ull * visited;
-      calls->timers.back().touched = 19ull * visited + 4ull * words + ncl * (2ull * sizeof(bk_cluster) + sizeof(struct bk_ref_support) + 4ull);
+      calls->timers.back().touched = 19ull * visited + 4ull * words + ncl * (2ull * sizeof(bk_cluster) + sizeof(struct bk_ref_support));
     }
-    // device order is (numeric chr-pair key, id); BK_STAGE_CLUSTERS is the stable order by `group` (bk_fetch): a counting sort
-    uint32_t gmax = 0;
-    for (uint32_t g : grp) gmax = std::max(gmax, g);
-    std::vector<uint64_t> start(ncl ? (size_t) gmax + 2 : 1, 0);
-    for (uint32_t g : grp) ++start[g + 1];
-    for (size_t g = 1; g < start.size(); ++g) start[g] += start[g - 1];
-    calls->f_ref.resize(ncl);
-    for (uint64_t c = 0; c < ncl; ++c) calls->f_ref[start[grp[c]]++] = res[c];
     *out = calls->f_ref.data();
     *count = ncl;
   });
@@ -941,51 +938,24 @@ int bk_junctions(bk_ctx *ctx, const struct bk_junction **out, uint64_t *count)
     if (ctx->shard) throw bk_error(BK_ERR_ARG, "bk_junctions: sharded contexts (bk_shard_*) are not supported");
     if (!ctx->bp_done || !ctx->clustered || !ctx->summary_map) throw bk_error(BK_ERR_ARG, "bk_junctions: call bk_split_breakpoints first");
     const uint64_t ncl = ctx->n_clusters;
-    JunctionPairs jp{};
-    if (ncl)  // (no cluster: bk_cluster_summary may have returned before it built the map)
-    {
-      jp.pairs = ctx->jr.pairs;
-      jp.idx = ctx->stage.list.idx.get<uint32_t>();
-      jp.gof = ctx->stage.list.gof.get<uint32_t>();
-      jp.cl = ctx->stage.d_cluster.get<uint32_t>();
-      jp.n = ctx->stage.list.n;
-      jp.ng = ctx->stage.list.ng;
-      jp.slotbase = ctx->bb.slotbase.get<uint32_t>();
-      jp.keep = ctx->bb.keep.get<uint32_t>();
-      jp.off = ctx->bb.off.get<uint32_t>();
-    }
+    const JunctionPairs jp = junction_pairs(ctx);
     struct bk_junction *d_res;
-    uint32_t *d_grp, *d_vis;
+    uint32_t *d_vis;
     {
       // bytes: per list entry its three list words and the four mapq / strand bytes of its pair row (a 32-byte sector of the 56-byte
       // row is what the load fetches); touched adds the tuples searched and, per cluster, its row read and the result written
       Scope s(ctx, "junctions", jp.n * (12ull + 4ull));
-      junctions(jp, ctx->d_split.get<bk_split>(), ctx->hc.n_split, ctx->clusters_ptr(), ncl, (int) ctx->hc.max_span, ctx->d_hdr.get<int32_t>(), ctx->names.own_id, ctx->nt,
-                ctx->names.empty_id, ctx->jnb, ctx->st, &d_res, &d_grp, &d_vis);
+      junctions(jp, tuple_table(ctx), ctx->clusters_ptr(), ncl, ctx->jnb, ctx->st, &d_res, &d_vis);
     }
-    std::vector<struct bk_junction> res(ncl);
-    std::vector<uint32_t> grp(ncl), vis(ctx->timing ? ncl : 0);
-    if (ncl)
-    {
-      HIP_CHECK(hipMemcpyAsync(res.data(), d_res, ncl * sizeof(struct bk_junction), hipMemcpyDeviceToHost, ctx->st));
-      HIP_CHECK(hipMemcpyAsync(grp.data(), d_grp, ncl * 4, hipMemcpyDeviceToHost, ctx->st));
-      if (ctx->timing) HIP_CHECK(hipMemcpyAsync(vis.data(), d_vis, ncl * 4, hipMemcpyDeviceToHost, ctx->st));
-    }
-    HIP_CHECK(hipStreamSynchronize(ctx->st));
+    std::vector<uint32_t> vis(ctx->timing ? ncl : 0);
+    if (!vis.empty()) HIP_CHECK(hipMemcpyAsync(vis.data(), d_vis, ncl * 4, hipMemcpyDeviceToHost, ctx->st));
+    rows_to_host(ctx, d_res, ncl, ctx->f_junction);
     if (ctx->timing && !ctx->timers.empty())
     {
       uint64_t visited = 0;
       for (uint32_t v : vis) visited += v;
-      ctx->timers.back().touched = jp.n * (12ull + 32ull) + visited * sizeof(bk_split) + ncl * (sizeof(bk_cluster) + 2ull * sizeof(struct bk_junction) + 8ull);
+      ctx->timers.back().touched = jp.n * (12ull + 32ull) + visited * sizeof(bk_split) + ncl * (sizeof(bk_cluster) + 2ull * sizeof(struct bk_junction) + 4ull);
     }
-    // device order is (numeric chr-pair key, id); BK_STAGE_CLUSTERS is the stable order by `group` (bk_fetch): a counting sort
-    uint32_t gmax = 0;
-    for (uint32_t g : grp) gmax = std::max(gmax, g);
-    std::vector<uint64_t> start(ncl ? (size_t) gmax + 2 : 1, 0);
-    for (uint32_t g : grp) ++start[g + 1];
-    for (size_t g = 1; g < start.size(); ++g) start[g] += start[g - 1];
-    ctx->f_junction.resize(ncl);
-    for (uint64_t c = 0; c < ncl; ++c) ctx->f_junction[start[grp[c]]++] = res[c];
     *out = ctx->f_junction.data();
     *count = ncl;
   });
@@ -1000,19 +970,7 @@ int bk_evidence(bk_ctx *ctx, const struct bk_evidence **out, uint64_t *count, co
     const uint64_t ncl = ctx->n_clusters;
     const bk_soa &t = ctx->rec;
     if (ncl && (!ctx->have_records || !t.mapq || (!t.side && !t.qhash))) throw bk_error(BK_ERR_ARG, "bk_evidence: the record table lacks a column");
-    JunctionPairs jp{};
-    if (ncl)  // (no cluster: bk_cluster_summary may have returned before it built the map)
-    {
-      jp.pairs = ctx->jr.pairs;
-      jp.idx = ctx->stage.list.idx.get<uint32_t>();
-      jp.gof = ctx->stage.list.gof.get<uint32_t>();
-      jp.cl = ctx->stage.d_cluster.get<uint32_t>();
-      jp.n = ctx->stage.list.n;
-      jp.ng = ctx->stage.list.ng;
-      jp.slotbase = ctx->bb.slotbase.get<uint32_t>();
-      jp.keep = ctx->bb.keep.get<uint32_t>();
-      jp.off = ctx->bb.off.get<uint32_t>();
-    }
+    const JunctionPairs jp = junction_pairs(ctx);
     EvidenceRecs er{t.n, t.side, t.qhash, t.qcheck, t.mapq};
     struct bk_evidence *d_rows;
     uint64_t *d_off;
@@ -1020,8 +978,7 @@ int bk_evidence(bk_ctx *ctx, const struct bk_evidence **out, uint64_t *count, co
     {
       // bytes: what bk_junctions reads (the counts are its own) and, per list entry, its sort key and value written and read once
       Scope s(ctx, "evidence", jp.n * (12ull + 4ull + 2ull * 12ull));
-      evidence(jp, ctx->d_split.get<bk_split>(), ctx->hc.n_split, ctx->clusters_ptr(), ncl, ctx->jr.n_groups, (int) ctx->hc.max_span, ctx->d_hdr.get<int32_t>(),
-               ctx->names.own_id, ctx->nt, ctx->names.empty_id, er, ctx->evb, ctx->st, &d_rows, &d_off, &d_stat);
+      evidence(jp, tuple_table(ctx), ctx->clusters_ptr(), ncl, er, ctx->evb, ctx->st, &d_rows, &d_off, &d_stat);
     }
     ctx->f_ev_off.assign(ncl + 1, 0);
     EvidenceStat stat{};
@@ -1030,20 +987,19 @@ int bk_evidence(bk_ctx *ctx, const struct bk_evidence **out, uint64_t *count, co
     HIP_CHECK(hipStreamSynchronize(ctx->st));
     if (stat.bad) throw bk_error(BK_ERR_HIP, "bk_evidence: the listing and the counts of bk_junctions disagree (internal error)");
     const uint64_t n = ctx->f_ev_off[ncl];
-    ctx->f_evidence.resize(n);
-    if (n) HIP_CHECK(hipMemcpyAsync(ctx->f_evidence.data(), d_rows, n * sizeof(struct bk_evidence), hipMemcpyDeviceToHost, ctx->st));
-    HIP_CHECK(hipStreamSynchronize(ctx->st));
+    rows_to_host(ctx, d_rows, n, ctx->f_evidence);
     if (ctx->timing && !ctx->timers.empty())
     {
-      // touched: the counting pass as in bk_junctions (the tuples are searched twice: counted, then listed), the radix passes over
-      // the list (8-byte key + 4-byte value, read twice and written once per 8-bit digit), the pair rows gathered (a 56-byte row
-      // and a 32-byte sector of the hashes each), and every row written
+      // touched: the counting pass as in bk_junctions (the tuples are searched twice: counted, then listed; the cluster row is read
+      // by both, and per cluster come its tuple count and its two 8-byte counts written: 20 B), the radix passes over the list
+      // (8-byte key + 4-byte value, read twice and written once per 8-bit digit), the pair rows gathered (a 56-byte row and a
+      // 32-byte sector of the hashes each), and every row written
       uint64_t n_pair_rows = 0;
       for (uint64_t i = 0; i < n; ++i) n_pair_rows += ctx->f_evidence[i].kind == BK_EV_PAIR;
       int bits = 1;
       while ((ncl >> bits) != 0) ++bits;
       const uint64_t passes = (uint64_t) (bits + 7) / 8;
-      ctx->timers.back().touched = jp.n * (12ull + 32ull) + 2ull * stat.visited * sizeof(bk_split) + ncl * (2ull * sizeof(bk_cluster) + 2ull * sizeof(struct bk_junction) + 40ull) +
+      ctx->timers.back().touched = jp.n * (12ull + 32ull) + 2ull * stat.visited * sizeof(bk_split) + ncl * (2ull * sizeof(bk_cluster) + 2ull * sizeof(struct bk_junction) + 20ull) +
                                    jp.n * (12ull + 12ull + passes * 32ull + 12ull) + n_pair_rows * (64ull + 32ull) + (n - n_pair_rows) * 32ull +
                                    n * sizeof(struct bk_evidence);
     }
@@ -1168,12 +1124,16 @@ int bk_fetch(bk_ctx *ctx, int stage, const void **data, uint64_t *count, const u
       *count = ctx->f_splits.size();
       break;
     case BK_STAGE_CLUSTERS:
-      ctx->f_clusters.resize(ctx->n_clusters);
-      if (ctx->n_clusters)
-        HIP_CHECK(hipMemcpyAsync(ctx->f_clusters.data(), ctx->clusters_ptr(), ctx->n_clusters * sizeof(bk_cluster), hipMemcpyDeviceToHost, ctx->st));
-      HIP_CHECK(hipStreamSynchronize(ctx->st));
-      // device order is (numeric chr-pair key, id); the reference appends groups in std::map<string> order
-      std::stable_sort(ctx->f_clusters.begin(), ctx->f_clusters.end(), [](const bk_cluster &a, const bk_cluster &b) { return a.group < b.group; });
+      rows_to_host(ctx, ctx->clusters_ptr(), ctx->n_clusters, ctx->f_clusters);
+      // The reference appends groups in std::map<string> order.  A context's own table is built in that order (bp.hip,
+      // cluster_summary); a sharded one holds the ranks' tables one after the other.
+      {
+        auto by_group = [](const bk_cluster &a, const bk_cluster &b) { return a.group < b.group; };
+        if (ctx->ext_clusters)
+          std::stable_sort(ctx->f_clusters.begin(), ctx->f_clusters.end(), by_group);
+        else if (!std::is_sorted(ctx->f_clusters.begin(), ctx->f_clusters.end(), by_group))
+          throw bk_error(BK_ERR_HIP, "bk_fetch: the cluster table is not in group order (internal error)");
+      }
       *data = ctx->f_clusters.data();
       *count = ctx->f_clusters.size();
       break;

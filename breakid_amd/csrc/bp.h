@@ -23,6 +23,12 @@ template <class Less> __device__ __forceinline__ uint64_t wave_lower(uint64_t lo
   const uint64_t i = lo + lane;
   return lo + (uint64_t) __popcll(__ballot(i < hi && less(i)));
 }
+// sum of v over the 64 lanes of a wave, on every lane
+__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v)
+{
+  for (int d = 32; d; d >>= 1) v += (uint32_t) __shfl_xor((int) v, d, 64);
+  return v;
+}
 
 struct ClusterAcc
 {
@@ -77,7 +83,7 @@ struct BpWork
 
 struct BpBufs
 {
-  DevBuf samp, key, val, kmax, slotbase, an, as1, as2, amin1, amax1, amin2, amax2, atype, keep, off, tmpc, work, nmatch, moff, err, emit, ecount, scan_tmp, cov, depth, voted, nvalid, maxrec;
+  DevBuf samp, key, val, kmax, lexbase, slotbase, an, as1, as2, amin1, amax1, amin2, amax2, atype, keep, off, tmpc, work, nmatch, moff, err, emit, ecount, scan_tmp, cov, depth, voted, nvalid, maxrec;
   prims::RadixBufs radix;
 };
 
@@ -85,9 +91,10 @@ struct BpBufs
 uint64_t count_valid_clusters(const bk_cluster *cl, uint64_t ncl, BpBufs &b, hipStream_t st);
 // rec_bits = bits of the largest record index a tuple may carry (the sort key)
 void sort_splits(bk_split *unsorted, uint64_t n, bk_split *sorted, BpBufs &b, hipStream_t st, int rec_bits);
-// returns the number of clusters that passed the near-diagonal filter; clusters_out holds them in (group key order, id) order
+// returns the number of clusters that passed the near-diagonal filter; clusters_out holds them in BK_STAGE_CLUSTERS order (the
+// invariant: bp.hip).  lex_to_num[l] = numeric index of the group at position l of the context's lexicographic group order.
 uint64_t cluster_summary(const bk_pair *pairs, const uint32_t *idx, const uint32_t *gof, const uint32_t *cl, uint64_t n, uint32_t ng, const uint32_t *gkey,
-                         const uint32_t *glex, int32_t nt, double w, DevBuf &clusters_out, BpBufs &b, hipStream_t st);
+                         const uint32_t *glex, const uint32_t *lex_to_num, int32_t nt, double w, DevBuf &clusters_out, BpBufs &b, hipStream_t st);
 // r with the sampled search keys of rec_lower, built into `samp` (tables of fewer than 64 strides are searched directly)
 RecView rec_sampled(const RecView &r, DevBuf &samp, hipStream_t st);
 // phases of the breakpoint stage (a sharded run sums `cov` and `depth` over the record shards between them)

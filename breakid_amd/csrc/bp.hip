@@ -105,9 +105,34 @@ __global__ __launch_bounds__(256) void k_accumulate(const bk_pair *__restrict__ 
   atomicMax(&acc.max2[s], mx2);
   atomicOr(&acc.type[s], type);
 }
-// slot -> (group, id): group found by binary search on slotbase
-__global__ __launch_bounds__(256) void k_finalize(ClusterAcc acc, const uint32_t *__restrict__ slotbase, uint32_t ng, uint32_t nslots, const uint32_t *__restrict__ gkey,
-                                                  const uint32_t *__restrict__ glex, int32_t nt, double w, uint32_t *__restrict__ keep, bk_cluster *__restrict__ tmp)
+// The slots are numbered over the groups in lexicographic order: one workgroup walks lex_to_num, a permutation of 0 .. ng - 1, and
+// scans kmax in that order, 256 groups per round, as prims::k_scan_one scans a short array.  lexbase[l] = the slots before position
+// l, and every group g (numeric index, as gof[] names it) gets the base of its position in slotbase[g]; lexbase[ng] = slotbase[ng] =
+// the number of slots.  One launch, where a gather, prims::exclusive_scan and a scatter are three: the two extra launches cost the
+// stage 0.04 of its 0.51 ms at the bench shape (300 groups).  The groups are the chromosome pairs that hold a discordant pair; a
+// reference list of thousands of contigs can give 10^5 of them, which is 400 rounds of this loop: still short beside the sorts of
+// as many groups.
+__global__ __launch_bounds__(prims::BLOCK) void k_slot_bases(const uint32_t *__restrict__ kmax, const uint32_t *__restrict__ lex_to_num, uint32_t ng,
+                                                             uint32_t *__restrict__ lexbase, uint32_t *__restrict__ slotbase)
+{
+  __shared__ uint32_t lds[prims::WAVES];
+  uint32_t carry = 0;
+  for (uint32_t base = 0; base < ng; base += prims::BLOCK)
+  {
+    const uint32_t l = base + threadIdx.x;
+    const uint32_t g = l < ng ? lex_to_num[l] : 0u;
+    const uint32_t v = l < ng ? kmax[g] : 0u;
+    uint32_t tot;
+    const uint32_t ex = prims::block_exclusive_scan(v, lds, tot);
+    if (l < ng) lexbase[l] = slotbase[g] = carry + ex;
+    carry += tot;
+  }
+  if (threadIdx.x == 0) lexbase[ng] = slotbase[ng] = carry;
+}
+// slot -> (group, id): lexicographic position found by binary search on the scan, group = lex_to_num of it
+__global__ __launch_bounds__(256) void k_finalize(ClusterAcc acc, const uint32_t *__restrict__ lexbase, const uint32_t *__restrict__ lex_to_num, uint32_t ng, uint32_t nslots,
+                                                  const uint32_t *__restrict__ gkey, const uint32_t *__restrict__ glex, int32_t nt, double w, uint32_t *__restrict__ keep,
+                                                  bk_cluster *__restrict__ tmp)
 {
   uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
   if (s >= nslots) return;
@@ -115,16 +140,16 @@ __global__ __launch_bounds__(256) void k_finalize(ClusterAcc acc, const uint32_t
   uint32_t n = acc.n[s];
   if (n)
   {
-    uint32_t lo = 0, hi = ng;  // largest g with slotbase[g] <= s
+    uint32_t lo = 0, hi = ng;  // largest l with lexbase[l] <= s
     while (lo < hi)
     {
       uint32_t m = (lo + hi) >> 1;
-      if (slotbase[m] <= s) lo = m + 1; else hi = m;
+      if (lexbase[m] <= s) lo = m + 1; else hi = m;
     }
-    uint32_t g = lo - 1;
+    const uint32_t g = lex_to_num[lo - 1];
     bk_cluster c;
     c.group = glex[g];
-    c.id = (int32_t) (s - slotbase[g]);
+    c.id = (int32_t) (s - lexbase[lo - 1]);
     c.p1_tid = (int32_t) (gkey[g] / (uint32_t) (nt + 1)) - 1;
     c.p2_tid = (int32_t) (gkey[g] % (uint32_t) (nt + 1)) - 1;
     unsigned long long m1 = (uint32_t) ((double) acc.sum1[s] / (double) n);  // :342-343
@@ -658,17 +683,22 @@ void sort_splits(bk_split *unsorted, uint64_t n, bk_split *sorted, BpBufs &b, hi
   hipLaunchKernelGGL(k_split_gather, dim3(nb(n)), dim3(256), 0, st, unsorted, vs, n, sorted);
 }
 
+// INVARIANT: the table this leaves in clusters_out is in BK_STAGE_CLUSTERS order.  A slot is slotbase[group] +
+// cluster number, the groups' bases ascend in the context's lexicographic group order (lex_to_num), and the rows are the kept
+// slots in slot order: `group` (glex, monotone in that order, also when it holds the global ordinals of a sharded sample) is
+// non-decreasing and the rows of a group are in `id` order.  In a non-sharded context row c of the device table is row c of
+// bk_fetch(BK_STAGE_CLUSTERS); every per-call output (normal.hip, genotype.hip, junction.hip, evidence.hip) relies on it.
 uint64_t cluster_summary(const bk_pair *pairs, const uint32_t *idx, const uint32_t *gof, const uint32_t *cl, uint64_t n, uint32_t ng, const uint32_t *gkey,
-                         const uint32_t *glex, int32_t nt, double w, DevBuf &clusters_out, BpBufs &b, hipStream_t st)
+                         const uint32_t *glex, const uint32_t *lex_to_num, int32_t nt, double w, DevBuf &clusters_out, BpBufs &b, hipStream_t st)
 {
   if (n == 0 || ng == 0) return 0;
   uint32_t *kmax = b.kmax.as<uint32_t>((uint64_t) ng + 1);
   HIP_CHECK(hipMemsetAsync(kmax, 0, ((uint64_t) ng + 1) * 4, st));
   hipLaunchKernelGGL(k_group_kmax, dim3(nb(n)), dim3(256), 0, st, gof, cl, n, kmax);
-  uint32_t *slotbase = b.slotbase.as<uint32_t>((uint64_t) ng + 1);
-  prims::exclusive_scan<uint32_t>(kmax, slotbase, ng, b.scan_tmp, st);
+  uint32_t *slotbase = b.slotbase.as<uint32_t>((uint64_t) ng + 1), *lexbase = b.lexbase.as<uint32_t>((uint64_t) ng + 1);
+  hipLaunchKernelGGL(k_slot_bases, dim3(1), dim3(prims::BLOCK), 0, st, kmax, lex_to_num, ng, lexbase, slotbase);
   uint32_t nslots = 0;
-  HIP_CHECK(hipMemcpyAsync(&nslots, slotbase + ng, 4, hipMemcpyDeviceToHost, st));
+  HIP_CHECK(hipMemcpyAsync(&nslots, lexbase + ng, 4, hipMemcpyDeviceToHost, st));
   HIP_CHECK(hipStreamSynchronize(st));
   if (nslots == 0) return 0;
   ClusterAcc acc;
@@ -691,7 +721,7 @@ uint64_t cluster_summary(const bk_pair *pairs, const uint32_t *idx, const uint32
   hipLaunchKernelGGL(k_accumulate, dim3(nb(n)), dim3(256), 0, st, pairs, idx, gof, cl, slotbase, n, acc);
   uint32_t *keep = b.keep.as<uint32_t>((uint64_t) nslots + 1), *off = b.off.as<uint32_t>((uint64_t) nslots + 1);
   bk_cluster *tmp = b.tmpc.as<bk_cluster>(nslots);
-  hipLaunchKernelGGL(k_finalize, dim3(nb(nslots)), dim3(256), 0, st, acc, slotbase, ng, nslots, gkey, glex, nt, w, keep, tmp);
+  hipLaunchKernelGGL(k_finalize, dim3(nb(nslots)), dim3(256), 0, st, acc, lexbase, lex_to_num, ng, nslots, gkey, glex, nt, w, keep, tmp);
   prims::exclusive_scan<uint32_t>(keep, off, nslots, b.scan_tmp, st);
   uint32_t nk = 0;
   HIP_CHECK(hipMemcpyAsync(&nk, off + nslots, 4, hipMemcpyDeviceToHost, st));

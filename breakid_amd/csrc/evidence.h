@@ -7,7 +7,7 @@
 struct EvidenceBufs
 {
   JunctionBufs jn;  // the counts come from junctions() itself (junction.hip)
-  DevBuf first, last, heads, gstart, fin, cnt, npair, call_off, pair_off, keys, vals, rows, stat, scan_tmp;
+  DevBuf cnt, npair, call_off, pair_off, keys, vals, rows, stat, scan_tmp;
   prims::RadixBufs radix;
 };
 
@@ -30,8 +30,7 @@ struct EvidenceStat
   unsigned long long visited;  // tuples the split waves looked at (the byte model)
 };
 
-// Rows in their final order (include/breakid_hip.h) in *rows_out, call_off_out[ncl + 1] in BK_STAGE_CLUSTERS order, both device
-// arrays owned by `b`; ng = number of groups (every bk_cluster.group is below it).  *stat_out: device, one entry.
-void evidence(const JunctionPairs &p, const bk_split *sp, uint64_t nsp, const bk_cluster *cl, uint64_t ncl, uint32_t ng, int maxspan, const int32_t *hdr_id,
-              const int32_t *own_id, int32_t nt, int32_t empty_id, const EvidenceRecs &recs, EvidenceBufs &b, hipStream_t st, struct bk_evidence **rows_out,
-              uint64_t **call_off_out, EvidenceStat **stat_out);
+// Rows in their final order (include/breakid_hip.h) in *rows_out, call_off_out[ncl + 1] over the rows of `cl` (BK_STAGE_CLUSTERS
+// order: bp.hip, cluster_summary), both device arrays owned by `b`.  *stat_out: device, one entry.
+void evidence(const JunctionPairs &p, const TupleTable &tt, const bk_cluster *cl, uint64_t ncl, const EvidenceRecs &recs, EvidenceBufs &b, hipStream_t st,
+              struct bk_evidence **rows_out, uint64_t **call_off_out, EvidenceStat **stat_out);

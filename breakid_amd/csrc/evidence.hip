@@ -27,62 +27,21 @@ __device__ __forceinline__ void store_row(struct bk_evidence *__restrict__ o, co
   o4[2] = t[2];
 }
 
-// Device order of the cluster table is (numeric chr-pair key, id) (bp.hip: a slot is slotbase[group in key order] + id, and the rows
-// are the kept slots in slot order); BK_STAGE_CLUSTERS is its stable order by `group` (bk_fetch).  So the clusters of a group are
-// neighbours in both, and the final row of cluster c is gstart[group] + (c - first cluster of the group).  The kernels do not take
-// that on trust: every head of a run of equal `group` is counted, and a group with a second head ends the call with an error.
-__global__ __launch_bounds__(256) void k_ev_group_bounds(const uint32_t *__restrict__ grp, uint32_t ncl, uint32_t ng, uint32_t *__restrict__ first,
-                                                         uint32_t *__restrict__ last, uint32_t *__restrict__ heads, EvidenceStat *__restrict__ stat)
+// Row c of the device cluster table is call c (BK_STAGE_CLUSTERS order: bp.hip, cluster_summary), so the counts of junctions() are
+// the per-call counts as they stand: the rows of a call, and how many of them are pair rows.
+__global__ __launch_bounds__(256) void k_ev_counts(const struct bk_junction *__restrict__ res, uint32_t ncl, uint64_t *__restrict__ cnt, uint64_t *__restrict__ npair)
 {
   const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= ncl) return;
-  const uint32_t g = grp[c];
-  if (g >= ng)
-  {
-    stat->bad = 1u;
-    return;
-  }
-  if (c == 0 || grp[c - 1] != g)
-  {
-    first[g] = c;
-    atomicAdd(&heads[g], 1u);  // (a count, whatever the order: a group has one run, so one head)
-  }
-  if (c == ncl - 1 || grp[c + 1] != g) last[g] = c + 1;
-}
-__global__ __launch_bounds__(256) void k_ev_group_sizes(const uint32_t *__restrict__ first, uint32_t *__restrict__ last, const uint32_t *__restrict__ heads, uint32_t ng,
-                                                        EvidenceStat *__restrict__ stat)
-{
-  const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
-  if (g >= ng) return;
-  if (heads[g] > 1u) stat->bad = 1u;  // the clusters of group g are not neighbours: first / last mean nothing
-  last[g] -= first[g];  // (a group without clusters: 0 - 0)
-}
-__global__ __launch_bounds__(256) void k_ev_counts(const struct bk_junction *__restrict__ res, const uint32_t *__restrict__ grp, uint32_t ncl, uint32_t ng,
-                                                   const uint32_t *__restrict__ first, const uint32_t *__restrict__ gstart, uint32_t *__restrict__ fin,
-                                                   uint64_t *__restrict__ cnt, uint64_t *__restrict__ npair, EvidenceStat *__restrict__ stat)
-{
-  const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= ncl) return;
-  const uint32_t g = grp[c];
-  fin[c] = ncl;  // (no row)
-  if (g >= ng) return;
-  const uint32_t f = gstart[g] + (c - first[g]);
-  if (c < first[g] || f >= gstart[g + 1] || f >= ncl)
-  {
-    stat->bad = 1u;
-    return;
-  }
   const struct bk_junction j = res[c];
   const uint64_t np = (uint64_t) j.pairs[0] + j.pairs[1] + j.pairs[2] + j.pairs[3];
   const uint64_t ns = (uint64_t) j.splits[0] + j.splits[1] + j.splits[2] + j.splits[3];
-  fin[c] = f;
-  cnt[f] = np + ns;
-  npair[f] = np;
+  cnt[c] = np + ns;
+  npair[c] = np;
 }
 
-// sort key of a list entry: the BK_STAGE_CLUSTERS row of its cluster, ncl for an entry whose cluster has no row (k_junction_pairs)
-__global__ __launch_bounds__(256) void k_ev_pair_keys(JunctionPairs in, uint32_t ncl, const uint32_t *__restrict__ fin, uint64_t *__restrict__ keys,
-                                                      uint32_t *__restrict__ vals)
+// sort key of a list entry: the row of its cluster, ncl for an entry whose cluster has no row (k_junction_pairs)
+__global__ __launch_bounds__(256) void k_ev_pair_keys(JunctionPairs in, uint32_t ncl, uint64_t *__restrict__ keys, uint32_t *__restrict__ vals)
 {
   const uint64_t p = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= in.n) return;
@@ -91,7 +50,7 @@ __global__ __launch_bounds__(256) void k_ev_pair_keys(JunctionPairs in, uint32_t
   if (s < in.slotbase[in.ng] && in.keep[s])
   {
     const uint32_t row = in.off[s];
-    if (row < ncl) key = fin[row];
+    if (row < ncl) key = row;
   }
   keys[p] = key;
   vals[p] = (uint32_t) p;
@@ -147,22 +106,19 @@ __global__ __launch_bounds__(256) void k_ev_emit_pairs(JunctionPairs in, const u
   store_row(rows + dest, v);
 }
 
-// One wave per cluster (device order).  The up to four tuple ranges are put in ascending order and walked as their union, so the
+// One wave per cluster.  The up to four tuple ranges are put in ascending order and walked as their union, so the
 // matches come in ascending BK_STAGE_SPLITS row; sides as in k_junction_sr.
-__global__ __launch_bounds__(256) void k_ev_emit_splits(const bk_split *__restrict__ sp, uint64_t nsp, const bk_cluster *__restrict__ cl, uint32_t ncl, int maxspan,
-                                                        const int32_t *__restrict__ hdr_id, const int32_t *__restrict__ own_id, int32_t nt, int32_t empty_id,
-                                                        const uint32_t *__restrict__ fin, const uint64_t *__restrict__ call_off, const uint64_t *__restrict__ pair_off,
-                                                        EvidenceRecs recs, struct bk_evidence *__restrict__ rows, uint64_t n_rows, EvidenceStat *__restrict__ stat)
+__global__ __launch_bounds__(256) void k_ev_emit_splits(TupleTable tt, const bk_cluster *__restrict__ cl, uint32_t ncl, const uint64_t *__restrict__ call_off,
+                                                        const uint64_t *__restrict__ pair_off, EvidenceRecs recs, struct bk_evidence *__restrict__ rows, uint64_t n_rows,
+                                                        EvidenceStat *__restrict__ stat)
 {
   const uint32_t c = blockIdx.x * 4 + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   if (c >= ncl) return;
   const bk_cluster k = cl[c];
   if (!(k.flags & 2u)) return;
-  const uint32_t f = fin[c];
-  if (f >= ncl) return;
-  const uint64_t base = call_off[f] + (pair_off[f + 1] - pair_off[f]), limit = call_off[f + 1];
-  const TupleRanges r = tuple_ranges(sp, nsp, k, maxspan, hdr_id, own_id, nt, empty_id);
+  const uint64_t base = call_off[c] + (pair_off[c + 1] - pair_off[c]), limit = call_off[c + 1];
+  const TupleRanges r = tuple_ranges(tt, k);
   uint64_t lo[4], hi[4];
 #pragma unroll
   for (int q = 0; q < 4; ++q)
@@ -201,7 +157,7 @@ __global__ __launch_bounds__(256) void k_ev_emit_splits(const bk_split *__restri
       bk_split s;
       if (t < e)
       {
-        s = sp[t];
+        s = tt.sp[t];
         side = tuple_side(s, r, k);
       }
       const uint64_t m = __ballot(side != 0);
@@ -213,12 +169,11 @@ __global__ __launch_bounds__(256) void k_ev_emit_splits(const bk_split *__restri
         else
         {
           const bool swapped = side == 2;
-          const uint32_t rp = s.prim_bp == s.prim_start ? 1u : 0u, rs = s.sec_bp == s.sec_start ? 1u : 0u;
           struct bk_evidence v;
           v.rec = s.rec;
           v.qhash = s.qhash;
           v.qcheck = s.qcheck;
-          v.call = f;
+          v.call = c;
           v.tid1 = k.p1_tid;
           v.pos1 = swapped ? s.sec_bp : s.prim_bp;
           v.tid2 = k.p2_tid;
@@ -232,7 +187,7 @@ __global__ __launch_bounds__(256) void k_ev_emit_splits(const bk_split *__restri
             stat->bad = 1u;
           v.mapq2 = 0;
           v.kind = BK_EV_SPLIT;
-          v.sides = (uint8_t) (swapped ? 2u * rs + rp : 2u * rp + rs);  // side 1 is prim unless the tuple names the pair the other way round
+          v.sides = (uint8_t) split_sides(s, swapped);
           store_row(rows + dest, v);
         }
       }
@@ -249,9 +204,8 @@ __global__ __launch_bounds__(256) void k_ev_emit_splits(const bk_split *__restri
 }
 }  // namespace
 
-void evidence(const JunctionPairs &p, const bk_split *sp, uint64_t nsp, const bk_cluster *cl, uint64_t ncl, uint32_t ng, int maxspan, const int32_t *hdr_id,
-              const int32_t *own_id, int32_t nt, int32_t empty_id, const EvidenceRecs &recs, EvidenceBufs &b, hipStream_t st, struct bk_evidence **rows_out,
-              uint64_t **call_off_out, EvidenceStat **stat_out)
+void evidence(const JunctionPairs &p, const TupleTable &tt, const bk_cluster *cl, uint64_t ncl, const EvidenceRecs &recs, EvidenceBufs &b, hipStream_t st,
+              struct bk_evidence **rows_out, uint64_t **call_off_out, EvidenceStat **stat_out)
 {
   uint64_t *call_off = b.call_off.as<uint64_t>(ncl + 1);
   EvidenceStat *stat = b.stat.as<EvidenceStat>(1);
@@ -268,21 +222,11 @@ void evidence(const JunctionPairs &p, const bk_split *sp, uint64_t nsp, const bk
   if (p.n > 0xFFFFFFF0ull) throw bk_error(BK_ERR_LIMIT, "too many clustered pairs");
   const uint32_t n32 = (uint32_t) ncl;
   struct bk_junction *res;
-  uint32_t *grp, *vis;
-  junctions(p, sp, nsp, cl, ncl, maxspan, hdr_id, own_id, nt, empty_id, b.jn, st, &res, &grp, &vis);
-  // every cluster's row in BK_STAGE_CLUSTERS order, its counts there, the two scans
-  uint32_t *first = b.first.as<uint32_t>((uint64_t) ng + 1), *last = b.last.as<uint32_t>((uint64_t) ng + 1), *gstart = b.gstart.as<uint32_t>((uint64_t) ng + 1);
-  uint32_t *fin = b.fin.as<uint32_t>(ncl), *heads = b.heads.as<uint32_t>((uint64_t) ng + 1);
+  uint32_t *vis;
+  junctions(p, tt, cl, ncl, b.jn, st, &res, &vis);
+  // every call's counts and the two scans
   uint64_t *cnt = b.cnt.as<uint64_t>(ncl + 1), *npair = b.npair.as<uint64_t>(ncl + 1), *pair_off = b.pair_off.as<uint64_t>(ncl + 1);
-  HIP_CHECK(hipMemsetAsync(first, 0, ((uint64_t) ng + 1) * 4, st));
-  HIP_CHECK(hipMemsetAsync(last, 0, ((uint64_t) ng + 1) * 4, st));
-  HIP_CHECK(hipMemsetAsync(heads, 0, ((uint64_t) ng + 1) * 4, st));
-  HIP_CHECK(hipMemsetAsync(cnt, 0, (ncl + 1) * 8, st));
-  HIP_CHECK(hipMemsetAsync(npair, 0, (ncl + 1) * 8, st));
-  hipLaunchKernelGGL(k_ev_group_bounds, dim3(cdiv(ncl, 256)), dim3(256), 0, st, grp, n32, ng, first, last, heads, stat);
-  hipLaunchKernelGGL(k_ev_group_sizes, dim3(cdiv(ng, 256)), dim3(256), 0, st, first, last, heads, ng, stat);
-  prims::exclusive_scan<uint32_t>(last, gstart, ng, b.scan_tmp, st);
-  hipLaunchKernelGGL(k_ev_counts, dim3(cdiv(ncl, 256)), dim3(256), 0, st, res, grp, n32, ng, first, gstart, fin, cnt, npair, stat);
+  hipLaunchKernelGGL(k_ev_counts, dim3(cdiv(ncl, 256)), dim3(256), 0, st, res, n32, cnt, npair);
   prims::exclusive_scan<uint64_t>(cnt, call_off, ncl, b.scan_tmp, st);
   prims::exclusive_scan<uint64_t>(npair, pair_off, ncl, b.scan_tmp, st);
   uint64_t total = 0;
@@ -295,12 +239,11 @@ void evidence(const JunctionPairs &p, const bk_split *sp, uint64_t nsp, const bk
   {
     uint64_t *keys = b.keys.as<uint64_t>(p.n);
     uint32_t *vals = b.vals.as<uint32_t>(p.n);
-    hipLaunchKernelGGL(k_ev_pair_keys, dim3(cdiv(p.n, 256)), dim3(256), 0, st, p, n32, fin, keys, vals);
+    hipLaunchKernelGGL(k_ev_pair_keys, dim3(cdiv(p.n, 256)), dim3(256), 0, st, p, n32, keys, vals);
     int bits = 1;
     while ((ncl >> bits) != 0) ++bits;  // keys are 0 .. ncl
     prims::radix_sort_pairs(keys, vals, p.n, 0, bits, b.radix, st, &keys, &vals);
     hipLaunchKernelGGL(k_ev_emit_pairs, dim3(cdiv(p.n, 256)), dim3(256), 0, st, p, keys, vals, n32, call_off, pair_off, recs, rows, total, stat);
   }
-  hipLaunchKernelGGL(k_ev_emit_splits, dim3(cdiv(ncl, 4)), dim3(256), 0, st, sp, nsp, cl, n32, maxspan, hdr_id, own_id, nt, empty_id, fin, call_off, pair_off, recs, rows,
-                     total, stat);
+  hipLaunchKernelGGL(k_ev_emit_splits, dim3(cdiv(ncl, 4)), dim3(256), 0, st, tt, cl, n32, call_off, pair_off, recs, rows, total, stat);
 }

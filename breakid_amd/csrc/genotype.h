@@ -5,7 +5,7 @@
 
 struct RefBufs
 {
-  DevBuf samp, res, grp, stat;
+  DevBuf samp, res, stat;
 };
 
 // per (call, side) wave, written only when a byte model is wanted: records of its window, CIGAR words walked
@@ -14,8 +14,8 @@ struct RefStat
   uint32_t visited, words;
 };
 
-// out[c] = the four counts of call c (device order of `cl`) on the record table `rec` (isize and aux_off set; maxspan = its
-// max(bam_endpos - pos)); grp_out[c] = its `group` (the caller restores BK_STAGE_CLUSTERS order).  stat_out (may be null) receives
-// 2 * ncl RefStat rows, [2 * c + side].  All three are device arrays owned by `b`.
+// out[c] = the four counts of call c, row c of `cl` (BK_STAGE_CLUSTERS order: bp.hip, cluster_summary), on the record table `rec`
+// (isize and aux_off set; maxspan = its max(bam_endpos - pos)).  stat_out (may be null) receives 2 * ncl RefStat rows,
+// [2 * c + side].  Both are device arrays owned by `b`.
 void ref_support(const RecView &rec, int maxspan, const bk_cluster *cl, uint64_t ncl, int mapq_min, int anchor, double w, RefBufs &b, hipStream_t st,
-                 struct bk_ref_support **out, uint32_t **grp_out, RefStat **stat_out);
+                 struct bk_ref_support **out, RefStat **stat_out);

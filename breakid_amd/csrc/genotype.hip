@@ -16,7 +16,7 @@ constexpr int REF_STEPS = 4;
 constexpr uint16_t REF_FLAG_NEVER = 0x4 | 0x100 | 0x200 | 0x400 | 0x800;
 
 __global__ __launch_bounds__(256) void k_ref_support(RecView r, const bk_cluster *__restrict__ cl, uint32_t ncl, int mapq_min, int A, int W, int maxspan,
-                                                     uint32_t *__restrict__ res, uint32_t *__restrict__ grp, RefStat *__restrict__ stat)
+                                                     uint32_t *__restrict__ res, RefStat *__restrict__ stat)
 {
   const uint32_t wv = blockIdx.x * 4 + (threadIdx.x >> 6);
   const uint32_t c = wv >> 1, side = wv & 1u;
@@ -72,14 +72,12 @@ __global__ __launch_bounds__(256) void k_ref_support(RecView r, const bk_cluster
       }
     }
   }
-  if (stat)
-    for (int d = 32; d; d >>= 1) words += (uint32_t) __shfl_xor((int) words, d, 64);
+  if (stat) words = wave_sum_u32(words);
   if (lane == 0)
   {
     // struct bk_ref_support { ref_pairs1, ref_pairs2, ref_reads1, ref_reads2 }: each wave stores the two fields of its side
     res[4 * (uint64_t) c + side] = n_pairs;
     res[4 * (uint64_t) c + 2 + side] = n_reads;
-    if (!side) grp[c] = k.group;
     if (stat)
     {
       RefStat o;
@@ -92,18 +90,16 @@ __global__ __launch_bounds__(256) void k_ref_support(RecView r, const bk_cluster
 }  // namespace
 
 void ref_support(const RecView &rec, int maxspan, const bk_cluster *cl, uint64_t ncl, int mapq_min, int anchor, double w, RefBufs &b, hipStream_t st,
-                 struct bk_ref_support **out, uint32_t **grp_out, RefStat **stat_out)
+                 struct bk_ref_support **out, RefStat **stat_out)
 {
   static_assert(sizeof(struct bk_ref_support) == 16, "bk_ref_support must be 16 bytes");
   struct bk_ref_support *res = b.res.as<struct bk_ref_support>(ncl + 1);
-  uint32_t *grp = b.grp.as<uint32_t>(ncl + 1);
   RefStat *stat = stat_out ? b.stat.as<RefStat>(2 * ncl + 2) : nullptr;
   *out = res;
-  *grp_out = grp;
   if (stat_out) *stat_out = stat;
   if (ncl == 0) return;
   if (ncl > 0x3FFFFFFFull) throw bk_error(BK_ERR_LIMIT, "too many clusters");
   const int W = (int) w;  // the integer the breakpoint stage passes as wi (bp.hip: bp_vote)
   const RecView r = rec_sampled(rec, b.samp, st);
-  hipLaunchKernelGGL(k_ref_support, dim3(cdiv(2 * ncl, 4)), dim3(256), 0, st, r, cl, (uint32_t) ncl, mapq_min, anchor, W, maxspan, (uint32_t *) res, grp, stat);
+  hipLaunchKernelGGL(k_ref_support, dim3(cdiv(2 * ncl, 4)), dim3(256), 0, st, r, cl, (uint32_t) ncl, mapq_min, anchor, W, maxspan, (uint32_t *) res, stat);
 }

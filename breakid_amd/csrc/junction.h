@@ -2,10 +2,11 @@
 #pragma once
 #include "bk_common.h"
 #include "bp.h"
+#include "tuple_match.h"
 
 struct JunctionBufs
 {
-  DevBuf res, grp, visited;
+  DevBuf res, visited;
 };
 
 // The clustered pair list (lanes.hip) and the slot -> cluster-row map cluster_summary left behind (bp.hip: slot = slotbase[group] +
@@ -19,7 +20,7 @@ struct JunctionPairs
   const uint32_t *slotbase, *keep, *off;
 };
 
-// out[c] = the junction evidence of cluster c (device order of `cl`); grp_out[c] = its `group` (the caller restores BK_STAGE_CLUSTERS
-// order); visited_out[c] = tuples its wave searched (the byte model).  Device arrays of ncl entries owned by `b`.
-void junctions(const JunctionPairs &p, const bk_split *sp, uint64_t nsp, const bk_cluster *cl, uint64_t ncl, int maxspan, const int32_t *hdr_id, const int32_t *own_id,
-               int32_t nt, int32_t empty_id, JunctionBufs &b, hipStream_t st, struct bk_junction **out, uint32_t **grp_out, uint32_t **visited_out);
+// out[c] = the junction evidence of cluster c, row c of `cl` (BK_STAGE_CLUSTERS order: bp.hip, cluster_summary); visited_out[c] =
+// tuples its wave searched (the byte model).  Device arrays of ncl entries owned by `b`.
+void junctions(const JunctionPairs &p, const TupleTable &tt, const bk_cluster *cl, uint64_t ncl, JunctionBufs &b, hipStream_t st, struct bk_junction **out,
+               uint32_t **visited_out);

@@ -60,17 +60,9 @@ __global__ __launch_bounds__(256) void k_junction_pairs(JunctionPairs in, uint32
   atomicAdd(reinterpret_cast<unsigned long long *>(&o->mapq_sum2), (unsigned long long) (mq >> 16));
 }
 
-__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v)
-{
-  for (int d = 32; d; d >>= 1) v += (uint32_t) __shfl_xor((int) v, d, 64);
-  return v;
-}
-
-// One wave per cluster; a voted one searches its tuples (tuple_match.h) and bins every match by the clip side of its two
-// alignments: a side is right when its breakpoint is the alignment's start (a leading clip), else left.
-__global__ __launch_bounds__(256) void k_junction_sr(const bk_split *__restrict__ sp, uint64_t nsp, const bk_cluster *__restrict__ cl, uint32_t ncl, int maxspan,
-                                                     const int32_t *__restrict__ hdr_id, const int32_t *__restrict__ own_id, int32_t nt, int32_t empty_id,
-                                                     struct bk_junction *__restrict__ res, uint32_t *__restrict__ grp, uint32_t *__restrict__ visited)
+// One wave per cluster; a voted one searches its tuples and bins every match by the clip sides of its two alignments (tuple_match.h).
+__global__ __launch_bounds__(256) void k_junction_sr(TupleTable tt, const bk_cluster *__restrict__ cl, uint32_t ncl, struct bk_junction *__restrict__ res,
+                                                     uint32_t *__restrict__ visited)
 {
   const uint32_t c = blockIdx.x * 4 + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
@@ -79,9 +71,8 @@ __global__ __launch_bounds__(256) void k_junction_sr(const bk_split *__restrict_
   uint32_t n0 = 0, n1 = 0, n2 = 0, n3 = 0, seen = 0;
   if (k.flags & 2u)
   {
-    seen = for_matching_tuples(sp, nsp, k, maxspan, hdr_id, own_id, nt, empty_id, [&](const bk_split &s, bool swapped) {
-      const uint32_t rp = s.prim_bp == s.prim_start ? 1u : 0u, rs = s.sec_bp == s.sec_start ? 1u : 0u;
-      const uint32_t b = swapped ? 2u * rs + rp : 2u * rp + rs;  // side 1 is prim unless the tuple names the pair the other way round
+    seen = for_matching_tuples(tt, k, [&](const bk_split &s, bool swapped) {
+      const uint32_t b = split_sides(s, swapped);
       n0 += b == 0u;
       n1 += b == 1u;
       n2 += b == 2u;
@@ -99,24 +90,21 @@ __global__ __launch_bounds__(256) void k_junction_sr(const bk_split *__restrict_
     res[c].splits[1] = n1;
     res[c].splits[2] = n2;
     res[c].splits[3] = n3;
-    grp[c] = k.group;
     visited[c] = seen;
   }
 }
 }  // namespace
 
-void junctions(const JunctionPairs &p, const bk_split *sp, uint64_t nsp, const bk_cluster *cl, uint64_t ncl, int maxspan, const int32_t *hdr_id, const int32_t *own_id,
-               int32_t nt, int32_t empty_id, JunctionBufs &b, hipStream_t st, struct bk_junction **out, uint32_t **grp_out, uint32_t **visited_out)
+void junctions(const JunctionPairs &p, const TupleTable &tt, const bk_cluster *cl, uint64_t ncl, JunctionBufs &b, hipStream_t st, struct bk_junction **out,
+               uint32_t **visited_out)
 {
   struct bk_junction *res = b.res.as<struct bk_junction>(ncl + 1);
-  uint32_t *grp = b.grp.as<uint32_t>(ncl + 1);
   uint32_t *visited = b.visited.as<uint32_t>(ncl + 1);
   *out = res;
-  *grp_out = grp;
   *visited_out = visited;
   if (ncl == 0) return;
   if (ncl > 0x7FFFFFFFull) throw bk_error(BK_ERR_LIMIT, "too many clusters");
   HIP_CHECK(hipMemsetAsync(res, 0, ncl * sizeof(struct bk_junction), st));
   if (p.n) hipLaunchKernelGGL(k_junction_pairs, dim3(cdiv(p.n, 256)), dim3(256), 0, st, p, (uint32_t) ncl, res);
-  hipLaunchKernelGGL(k_junction_sr, dim3(cdiv(ncl, 4)), dim3(256), 0, st, sp, nsp, cl, (uint32_t) ncl, maxspan, hdr_id, own_id, nt, empty_id, res, grp, visited);
+  hipLaunchKernelGGL(k_junction_sr, dim3(cdiv(ncl, 4)), dim3(256), 0, st, tt, cl, (uint32_t) ncl, res, visited);
 }

@@ -80,12 +80,6 @@ __global__ __launch_bounds__(256) void k_rows(const bk_pair *__restrict__ pairs,
   rows[j] = make_uint2(p.p2_pos, pair_type(p));
 }
 
-__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v)
-{
-  for (int d = 32; d; d >>= 1) v += (uint32_t) __shfl_xor((int) v, d, 64);
-  return v;
-}
-
 // ---- n_drp: one wave per tumour cluster --------------------------------------------------------------------------------------
 // [lo, hi) = the rows of the cluster's chromosome pair with p1_pos in [p1_min - W, p1_max + W] (wave-wide lower bounds on the keys);
 // the rows in between are tested on p2_pos and the orientation bit, 64 per ballot and four ballots' loads in flight at once: a dense
@@ -94,7 +88,7 @@ constexpr int DRP_STEPS = 4;
 __global__ __launch_bounds__(256) void k_normal_drp(const uint64_t *__restrict__ keys, const uint2 *__restrict__ rows, uint64_t nrows, int dense,
                                                     const unsigned long long *__restrict__ gtab, const uint32_t *__restrict__ ngtab_dev, int32_t nt,
                                                     const bk_cluster *__restrict__ cl, uint32_t ncl, int W, struct bk_normal_support *__restrict__ res,
-                                                    uint32_t *__restrict__ grp, uint32_t *__restrict__ voted)
+                                                    uint32_t *__restrict__ voted)
 {
   const uint32_t c = blockIdx.x * 4 + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
@@ -143,16 +137,13 @@ __global__ __launch_bounds__(256) void k_normal_drp(const uint64_t *__restrict__
     o.n_drp = n;
     o.n_sr = o.depth1 = o.depth2 = 0;
     res[c] = o;
-    grp[c] = k.group;
     voted[c] = (k.flags & 2u) ? 1u : 0u;
   }
 }
 
 // ---- n_sr: one wave per voted cluster -----------------------------------------------------------------------------------------
 // (the range construction and the match: tuple_match.h, shared with bk_junctions)
-__global__ __launch_bounds__(256) void k_normal_sr(const bk_split *__restrict__ sp, uint64_t nsp, const bk_cluster *__restrict__ cl, uint32_t ncl, int maxspan,
-                                                   const int32_t *__restrict__ hdr_id, const int32_t *__restrict__ own_id, int32_t nt, int32_t empty_id,
-                                                   struct bk_normal_support *__restrict__ res)
+__global__ __launch_bounds__(256) void k_normal_sr(TupleTable tt, const bk_cluster *__restrict__ cl, uint32_t ncl, struct bk_normal_support *__restrict__ res)
 {
   const uint32_t c = blockIdx.x * 4 + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
@@ -160,7 +151,7 @@ __global__ __launch_bounds__(256) void k_normal_sr(const bk_split *__restrict__ 
   const bk_cluster k = cl[c];
   if (!(k.flags & 2u)) return;
   uint32_t n = 0;
-  for_matching_tuples(sp, nsp, k, maxspan, hdr_id, own_id, nt, empty_id, [&](const bk_split &, bool) { ++n; });
+  for_matching_tuples(tt, k, [&](const bk_split &, bool) { ++n; });
   n = wave_sum_u32(n);
   if (lane == 0) res[c].n_sr = n;
 }
@@ -177,18 +168,16 @@ __global__ __launch_bounds__(256) void k_normal_depth(const uint32_t *__restrict
 
 static inline unsigned nb(uint64_t n) { return cdiv(n ? n : 1, 256); }
 
-void normal_support(const NormalSide &n, const bk_cluster *cl, uint64_t ncl, int32_t nt, double w, NormalBufs &b, hipStream_t st, struct bk_normal_support **out,
-                    uint32_t **grp_out)
+void normal_support(const NormalSide &n, const bk_cluster *cl, uint64_t ncl, double w, NormalBufs &b, hipStream_t st, struct bk_normal_support **out)
 {
   struct bk_normal_support *res = b.res.as<struct bk_normal_support>(ncl + 1);
-  uint32_t *grp = b.grp.as<uint32_t>(ncl + 1);
   uint32_t *voted = b.bb.voted.as<uint32_t>(ncl + 1);
   *out = res;
-  *grp_out = grp;
   if (ncl == 0) return;
   if (ncl > 0x7FFFFFFFull) throw bk_error(BK_ERR_LIMIT, "too many clusters");
   const int W = (int) w;  // the integer the breakpoint stage passes as wi (bp.hip: bp_vote)
   const uint64_t np = n.n_pairs;
+  const int32_t nt = n.tuples.nt;
   const bool dense = nt >= 65535;  // (nt + 1)^2 no longer fits in the 32 high bits of a key
   const uint64_t *keys = nullptr;
   const uint2 *rows = nullptr;
@@ -229,8 +218,8 @@ void normal_support(const NormalSide &n, const bk_cluster *cl, uint64_t ncl, int
     keys = ks;
     rows = rw;
   }
-  hipLaunchKernelGGL(k_normal_drp, dim3(cdiv(ncl, 4)), dim3(256), 0, st, keys, rows, np, dense ? 1 : 0, gtab, ngtab, nt, cl, (uint32_t) ncl, W, res, grp, voted);
-  hipLaunchKernelGGL(k_normal_sr, dim3(cdiv(ncl, 4)), dim3(256), 0, st, n.sp, n.n_split, cl, (uint32_t) ncl, n.maxspan, n.hdr_id, n.own_id, nt, n.empty_id, res);
-  const uint32_t *depth = bp_depth_partial(n.rec, cl, ncl, n.maxspan, b.bb, st);
+  hipLaunchKernelGGL(k_normal_drp, dim3(cdiv(ncl, 4)), dim3(256), 0, st, keys, rows, np, dense ? 1 : 0, gtab, ngtab, nt, cl, (uint32_t) ncl, W, res, voted);
+  hipLaunchKernelGGL(k_normal_sr, dim3(cdiv(ncl, 4)), dim3(256), 0, st, n.tuples, cl, (uint32_t) ncl, res);
+  const uint32_t *depth = bp_depth_partial(n.rec, cl, ncl, n.tuples.maxspan, b.bb, st);
   hipLaunchKernelGGL(k_normal_depth, dim3(nb(ncl)), dim3(256), 0, st, depth, (uint32_t) ncl, res);
 }

@@ -11,13 +11,11 @@ import numpy as np
 import pytest
 
 from breakid_amd import abi, bamio, capi, synth
-from tests import test_gpu_exclude as xt    # (device copies of a table, the filtered table of an exclude list)
-from tests import test_gpu_feed as ft       # (a device table back on the host)
-from tests import test_gpu_vcf as vt        # (its datasets and designed loci)
+from tests import callcases as cc
 
 pytestmark = pytest.mark.gpu
-BIN = vt.BIN
-QUAL = vt.QUAL
+BIN = cc.BIN
+QUAL = cc.QUAL
 
 
 # ---- the definition, in numpy -----------------------------------------------------------------------------------------------
@@ -105,7 +103,7 @@ def columns(cols):
 @pytest.mark.parametrize("name", ["genotype", "edge", "cfg"])
 @pytest.mark.parametrize("fast", [True, False])
 def test_evidence_equals_its_definition(fast, name):
-    ds, cols = vt._dataset(name)
+    ds, cols = cc.call_dataset(name)
     t = capi.Context(ds.contigs)
     t.upload(cols)
     w, n_valid = t.run(qual=QUAL, fast=fast)
@@ -117,7 +115,7 @@ def test_evidence_equals_its_definition(fast, name):
 
 @pytest.mark.parametrize("fast", [True, False])
 def test_evidence_renamed_reference_list(fast):
-    tum, _ = vt.nt.tumor_normal(extra_contigs=300, names4=("chr2", "chr1", "chr3", "chr4"))
+    tum, _ = cc.tumor_normal(extra_contigs=300, names4=("chr2", "chr1", "chr3", "chr4"))
     cols = tum.to_soa()
     t = capi.Context(tum.contigs)
     t.upload(cols)
@@ -145,18 +143,18 @@ def shared_tumor():
     split read of SH (60M40S ending at its breakpoint on chr1, the rest on chr3) and their second mate lies on chr2 beside LOCI[0]'s
     breakpoint, so the pair is a member pair of LOCI[0]"""
     rng = np.random.default_rng(11)
-    ds = vt.designed_tumor()
+    ds = cc.designed_tumor()
     name, ta, bpa, da, tb, bpb, db = SHARED
     for j in range(14):
         ds.recs += synth._discordant_pair("%sD_%d" % (name, j), ta, bpa - int(rng.integers(100, 400)), tb, bpb + int(rng.integers(0, 300)), 100, rev_a=False, rev_b=True)
     for j in range(8):
-        ds.recs += vt.designed_split("%sS_%d" % (name, j), ta, bpa, da, tb, bpb, db)
-    _, _, _, _, t2, bp2, _ = vt.LOCI[0]
+        ds.recs += cc.designed_split("%sS_%d" % (name, j), ta, bpa, da, tb, bpb, db)
+    _, _, _, _, t2, bp2, _ = cc.LOCI[0]
     for j in range(N_SHARE):
         q = "SHARE_%d" % j
         pa, pb, pm = bpa - 60, bpb - 1, bp2 + 40 + 30 * j
-        sa1 = "%s,%d,+,60S40M,60,0;" % (vt.NAMES[tb], pb + 1)
-        sa2 = "%s,%d,+,60M40S,60,0;" % (vt.NAMES[ta], pa + 1)
+        sa1 = "%s,%d,+,60S40M,60,0;" % (cc.NAMES[tb], pb + 1)
+        sa2 = "%s,%d,+,60M40S,60,0;" % (cc.NAMES[ta], pa + 1)
         ds.recs += [synth.Rec(q, 0x1 | 0x40 | 0x20, ta, pa, 60, "60M40S", t2, pm, 0, sa=sa1),
                     synth.Rec(q, 0x1 | 0x40 | 0x20 | 0x100, tb, pb, 60, "60S40M", t2, pm, 0, sa=sa2),
                     synth.Rec(q, 0x1 | 0x80 | 0x10, t2, pm, 60, "100M", ta, pa, 0)]
@@ -215,10 +213,10 @@ def test_designed_reads(fast):
         assert int(got["qhash"][k]) == capi.lib().bk_qname_hash(n, len(n)) and int(got["qcheck"][k]) == capi.lib().bk_qname_check(n, len(n))
     share = ["SHARE_%d" % j for j in range(N_SHARE)]
     calls_of_share = set()
-    for name, ta, bpa, da, tb, bpb, db in vt.LOCI + [SHARED]:
-        rows = vt.rows_of(cl, ta, bpa, tb, bpb)
+    for name, ta, bpa, da, tb, bpb, db in cc.LOCI + [SHARED]:
+        rows = cc.rows_of(cl, ta, bpa, tb, bpb)
         assert rows, "locus %s is not called" % name
-        pe_exp = sorted(["%sD_%d" % (name, j) for j in range(14)] + (share if name == vt.LOCI[0][0] else []))
+        pe_exp = sorted(["%sD_%d" % (name, j) for j in range(14)] + (share if name == cc.LOCI[0][0] else []))
         sr_exp = sorted(["%sS_%d" % (name, j) for j in range(8)] + (share if name == SHARED[0] else []))
         pe_all, sr_all, kept = [], set(), []
         for i, _ in rows:
@@ -238,10 +236,78 @@ def test_designed_reads(fast):
         assert all(in_clustered[n] == 0 for n in missing), (name, missing)                   # a pair not listed is in no cluster at all
         assert all(in_clustered[n] == c for n, c in Counter(pe_all).items()), name           # a pair listed twice is in the table twice
         assert sorted(sr_all) == sr_exp, (name, sr_all)
-        if name == vt.LOCI[0][0]:
+        if name == cc.LOCI[0][0]:
             share_as_pair = set(pe_all) & set(share)
     assert len(calls_of_share) == 2 and share_as_pair  # a shared read is a member pair of one call and a split read of the other
     t.close()
+
+
+# ---- 2b. the order of the calls: a reference list whose numeric and lexicographic group orders differ ---------------------------
+ORDER_CONTIGS = [("chr1", 2_000_000), ("chr2", 2_000_000), ("chr10", 2_000_000)]
+# One locus per chromosome pair, one on chr1 alone and one on chr2 alone.  A record on the third contig carries the id of "chr3" for
+# its own side (the reference's chromID2ChrName of its tid), so the two tuples of a split read there never agree: the loci on chr10
+# get clusters but no vote, on the CPU oracle too.  The locus on chr2 is there so that three groups hold a voted cluster.
+ORDER_LOCI = [("x1_2", 0, 300_000, "L", 1, 700_000, "R"), ("x1_10", 0, 900_000, "L", 2, 500_000, "L"), ("x2_10", 1, 1_300_000, "R", 2, 1_200_000, "R"),
+              ("s1", 0, 1_400_000, "L", 0, 1_800_000, "R"), ("s2", 1, 300_000, "R", 1, 1_000_000, "L")]
+_ORDER = {}
+
+
+def order_tumor():
+    if "t" not in _ORDER:
+        ds = cc.designed_tumor(mix=False, contigs=ORDER_CONTIGS, loci=ORDER_LOCI, n_proper=4000)
+        _ORDER["t"] = (ds, ds.to_soa())
+    return _ORDER["t"]
+
+
+@pytest.mark.parametrize("fast", [True, False])
+def test_per_call_outputs_where_group_orders_differ(fast):
+    """Groups in numeric key order: chr1_chr1, chr1_chr2, chr1_chr10, chr2_chr2, chr2_chr10; in BK_STAGE_CLUSTERS order (the
+    reference's std::map<string>): chr1_chr1, chr1_chr10, chr1_chr2, chr2_chr10, chr2_chr2.  Every row of the four per-call
+    outputs must be the row of its definition over the fetched clusters, with a normal made of the tumour's own records."""
+    ds, cols = order_tumor()
+    names = [n for n, _ in ds.contigs]
+    t = capi.Context(ds.contigs)
+    t.upload(cols)
+    w, n_valid = t.run(qual=QUAL, fast=fast)
+    cl, _ = t.fetch(abi.STAGE_CLUSTERS)
+    # the fixture's own condition
+    keys = sorted({(int(c["p1_tid"]), int(c["p2_tid"])) for c in cl})
+    lexicographic = sorted(keys, key=lambda k: names[k[0]] + "_" + names[k[1]])
+    voted_keys = {(int(c["p1_tid"]), int(c["p2_tid"])) for c in cl if c["flags"] & 2}
+    assert len(voted_keys) >= 3, voted_keys
+    assert keys != lexicographic, keys
+    assert any(keys.index(k) != lexicographic.index(k) for k in voted_keys)  # a voted call moves between the two orders
+    row_keys = [(int(c["p1_tid"]), int(c["p2_tid"])) for c in cl]
+    assert row_keys == sorted(row_keys, key=lexicographic.index)
+    # the four outputs, every row
+    n = capi.Context(ds.contigs)
+    n.upload(cols)
+    n.isize_stats()
+    n.discordant_pairs(QUAL, w)
+    n.split_evidence()
+    got = t.normal_support(n, w)
+    exp = cc.expected_support(cl, n.fetch(abi.STAGE_SCAN)[0], n.fetch(abi.STAGE_SPLITS)[0], cols, w)
+    assert got.dtype == abi.NORMAL_SUPPORT and len(got) == len(cl)
+    bad = np.nonzero(got != exp)[0]
+    assert len(bad) == 0, [(cl[i], got[i], exp[i]) for i in bad[:5]]
+    assert got["n_sr"].any() and got["n_drp"].all()  # (the normal is the tumour: every call finds its own pairs)
+    for records, anchor in ((t, 0), (t, 10), (n, 10)):
+        ref = t.ref_support(records, QUAL, anchor, w)
+        exp = cc.expected_ref_support(cl, cols, QUAL, anchor, w)
+        assert ref.dtype == abi.REF_SUPPORT and len(ref) == len(cl)
+        bad = np.nonzero(ref != exp)[0]
+        assert len(bad) == 0, [(cl[i], ref[i], exp[i]) for i in bad[:5]]
+    junc = t.junctions()
+    exp = cc.expected_junctions(cl, t.fetch(abi.STAGE_CLUSTERED)[0], t.fetch(abi.STAGE_SPLITS)[0])
+    assert junc.dtype == abi.JUNCTION and len(junc) == len(cl)
+    bad = [i for i in range(len(cl)) if junc[i].tobytes() != exp[i].tobytes()]
+    assert not bad, [(cl[i], junc[i], exp[i]) for i in bad[:5]]
+    assert np.array_equal(junc["splits"].astype(np.int64).sum(1), got["n_sr"].astype(np.int64))  # (the normal is the tumour)
+    rows, off, _ = check_context(t, *columns(cols))  # bk_evidence against expected_evidence, call_off against the rows
+    assert junc["splits"].any() and (rows["kind"] == abi.EV_SPLIT).any()
+    assert np.array_equal(t.fetch(abi.STAGE_CLUSTERS)[0], cl)
+    t.close()
+    n.close()
 
 
 # ---- 3. table forms, call order, errors -----------------------------------------------------------------------------------------
@@ -267,12 +333,12 @@ def test_evidence_table_forms(form):
             t, hold = capi.decode_bam_device_ctx(p, qual=QUAL)
     else:
         ds, cols = shared()
-        t, hold = xt.make_ctx(ds.contigs, cols, "device" if form.endswith("device") else "host", qcheck=form != "host_no_qcheck")
+        t, hold = cc.make_ctx(ds.contigs, cols, "device" if form.endswith("device") else "host", qcheck=form != "host_no_qcheck")
         if form == "host_no_qcheck":
             cols = {k: v for k, v in cols.items() if k != "qcheck"}
         if form.startswith("exclude"):
-            assert t.exclude_regions(*vt.EXCLUDE) > 0
-            cols = xt.filtered(cols, ~xt.excluded_mask(cols, *vt.EXCLUDE))  # `rec` numbers the kept records
+            assert t.exclude_regions(*cc.EXCLUDE) > 0
+            cols = cc.filtered(cols, ~cc.excluded_mask(cols, *cc.EXCLUDE))  # `rec` numbers the kept records
     w, n_valid = t.run(qual=QUAL, fast=True)
     assert n_valid > 0
     got, off, cl = check_context(t, *columns(cols))
@@ -326,7 +392,7 @@ def test_evidence_call_order_and_errors():
 
 
 def test_evidence_of_a_context_without_clusters():
-    tum = vt.quiet_tumor()
+    tum = cc.quiet_tumor()
     t = capi.Context(tum.contigs)
     t.upload(tum.to_soa())
     t.run(qual=QUAL, fast=True)
@@ -374,10 +440,10 @@ def assert_other_files_identical(a, b, tmp):
 
 def written_calls(cl, fusion_path):
     """rows of BK_STAGE_CLUSTERS that the fusion table of the run holds (as test_gpu_vcf matches them)"""
-    table = set((f[1], f[2], f[7], f[8]) for f in vt.fusion_rows(fusion_path))
+    table = set((f[1], f[2], f[7], f[8]) for f in cc.fusion_rows(fusion_path))
     out = [i for i, c in enumerate(cl) if c["flags"] & 2 and
-           (vt.NAMES[c["p1_tid"]] + ":%d" % c["p1_exact"], vt.NAMES[c["p2_tid"]] + ":%d" % c["p2_exact"], str(c["n_drp"]), str(c["n_sr"])) in table]
-    assert len(set((vt.NAMES[cl[i]["p1_tid"]], int(cl[i]["p1_exact"]), vt.NAMES[cl[i]["p2_tid"]], int(cl[i]["p2_exact"]), int(cl[i]["n_drp"]), int(cl[i]["n_sr"]))
+           (cc.NAMES[c["p1_tid"]] + ":%d" % c["p1_exact"], cc.NAMES[c["p2_tid"]] + ":%d" % c["p2_exact"], str(c["n_drp"]), str(c["n_sr"])) in table]
+    assert len(set((cc.NAMES[cl[i]["p1_tid"]], int(cl[i]["p1_exact"]), cc.NAMES[cl[i]["p2_tid"]], int(cl[i]["p2_exact"]), int(cl[i]["n_drp"]), int(cl[i]["n_sr"]))
                    for i in out)) == len(table)
     return out
 
@@ -389,15 +455,15 @@ def check_cli_outputs(prefix, bam_path, ds, cols, fast, with_x, fusion_path):
     t.upload(cols)
     kept_names = names
     if with_x:
-        keep = ~xt.excluded_mask(cols, *vt.EXCLUDE)
-        t.exclude_regions(*vt.EXCLUDE)
+        keep = ~cc.excluded_mask(cols, *cc.EXCLUDE)
+        t.exclude_regions(*cc.EXCLUDE)
         kept_names = [n for n, k in zip(names, keep) if k]
     t.run(qual=QUAL, fast=fast)
     got, off = t.evidence()
     cl = t.fetch(abi.STAGE_CLUSTERS)[0]
     t.close()
     calls = written_calls(cl, fusion_path)
-    chrom = lambda tid: "*" if tid < 0 else vt.NAMES[tid]
+    chrom = lambda tid: "*" if tid < 0 else cc.NAMES[tid]
     exp, tags = [HEADER], {}
     for c in calls:
         for r in got[int(off[c]):int(off[c + 1])]:
@@ -422,9 +488,9 @@ def check_cli_outputs(prefix, bam_path, ds, cols, fast, with_x, fusion_path):
     idx = np.asarray(sel, np.int64)
     host = capi.decode_bam(prefix + "_evidence.bam")[1]
     table = capi.decode_bam_device(prefix + "_evidence.bam")  # the GPU feed reads the file too
-    dev = ft._device_cols(table)
+    dev = cc.device_cols(table)
     table.close()
-    for k in xt.FIXED:
+    for k in cc.FIXED:
         assert np.array_equal(host[k], cols[k][idx]) and np.array_equal(dev[k], cols[k][idx]), k
     for k in ("cigar", "aux", "cigar_off", "aux_off"):
         assert np.array_equal(host[k], dev[k]), k
@@ -457,20 +523,20 @@ def test_cli_evidence(mode, variant):
     with_x = variant == "exclude"
     with tempfile.TemporaryDirectory() as tmp:
         tb, nb, bed = os.path.join(tmp, "t.bam"), os.path.join(tmp, "n.bam"), os.path.join(tmp, "x.bed")
-        vt.write_indexed(ds, tb, aligned=variant != "across_blocks")
-        side = synth.write_side_files(ds, tmp, refgene_lines=vt.designed_refgene())
+        cc.write_indexed(ds, tb, aligned=variant != "across_blocks")
+        side = synth.write_side_files(ds, tmp, refgene_lines=cc.designed_refgene())
         env = dict(os.environ, BREAKID_INSTALLDIR=side["install"])
         env.pop("BREAKID_HOST_DECODE", None)
         extra = ["-fast"] if mode == "fast" else []
         if variant != "plain":
             extra += ["-all"]
         if variant == "normal_genotype_vcf":
-            vt.designed_normal().write_bam(nb, aligned=True)
+            cc.designed_normal().write_bam(nb, aligned=True)
             extra += ["-normal", nb, "-genotype", "-vcf"]
         if with_x:
             with open(bed, "w") as f:
-                for t, s, e in zip(*vt.EXCLUDE):
-                    f.write("%s\t%d\t%d\n" % (vt.NAMES[t], s, e))
+                for t, s, e in zip(*cc.EXCLUDE):
+                    f.write("%s\t%d\t%d\n" % (cc.NAMES[t], s, e))
             extra += ["-x", bed]
         base = [BIN, "-i", tb, "-n", side["nib"]] + extra
         a, b = os.path.join(tmp, "a"), os.path.join(tmp, "b")
@@ -493,10 +559,10 @@ def test_cli_evidence(mode, variant):
 
 
 def test_cli_evidence_of_a_sample_without_calls_and_errors():
-    tum = vt.quiet_tumor()
+    tum = cc.quiet_tumor()
     with tempfile.TemporaryDirectory() as tmp:
         tb = os.path.join(tmp, "t.bam")
-        vt.write_indexed(tum, tb)
+        cc.write_indexed(tum, tb)
         side = synth.write_side_files(tum, tmp)
         env = dict(os.environ, BREAKID_INSTALLDIR=side["install"])
         prefix = os.path.join(tmp, "z")

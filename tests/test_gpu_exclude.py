@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 
 from breakid_amd import abi, bamio, capi, synth
-from tests.test_gpu_normal import rec_endpos
+from tests.callcases import excluded_mask, filtered, make_ctx, rec_endpos
 from tools import make_golden
 
 pytestmark = pytest.mark.gpu
@@ -17,29 +17,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BIN = os.path.join(ROOT, "breakid_amd", "bin", "BreakID")
 QUAL = 20
 STAGES = (abi.STAGE_SCAN, abi.STAGE_ISO, abi.STAGE_CLUSTERED, abi.STAGE_SPLITS, abi.STAGE_CLUSTERS)
-FIXED = ("tid", "pos", "mtid", "mpos", "isize", "flag", "mapq", "qhash", "qcheck")
-
-
-# ---- the definition, in numpy -----------------------------------------------------------------------------------------------
-def excluded_mask(cols, tid, beg, end):
-    ep = rec_endpos(cols)
-    t = cols["tid"]
-    p = cols["pos"].astype(np.int64)
-    ex = np.zeros(len(t), bool)
-    for T, b, e in zip(tid, beg, end):
-        ex |= (t == T) & (p < e) & (ep > b)
-    return ex
-
-
-def filtered(cols, keep):
-    """the table without the records where keep is False, CIGAR words and aux bytes repacked"""
-    out = {k: np.ascontiguousarray(cols[k][keep]) for k in FIXED if k in cols}
-    for blob, off in (("cigar", "cigar_off"), ("aux", "aux_off")):
-        o = cols[off].astype(np.int64)
-        ln = np.diff(o)
-        out[blob] = np.ascontiguousarray(cols[blob][:o[-1]][np.repeat(keep, ln)])
-        out[off] = np.concatenate([[0], np.cumsum(ln[keep])]).astype(np.uint32)
-    return out
 
 
 def seeded_list(cols, contigs, seed, whole=True):
@@ -81,38 +58,6 @@ def hg19_like_list(contigs, seed, n_random=40):
         iv.append((t, b, min(ln, b + w)))
     a = np.asarray(iv, np.int64)
     return a[:, 0], a[:, 1], a[:, 2]
-
-
-# ---- contexts ---------------------------------------------------------------------------------------------------------------
-def to_device(cols, qcheck=True):
-    """torch copies of the columns on cuda:0 (same bits; unsigned columns as their signed twins) and their device pointers"""
-    import torch
-    dev = torch.device("cuda", 0)
-    signed = {np.dtype(np.uint16): np.int16, np.dtype(np.uint32): np.int32, np.dtype(np.uint64): np.int64}
-    t = {}
-    for k, dt in abi.SOA_COLS_ALL:
-        if k == "qcheck" and (not qcheck or k not in cols):
-            continue
-        a = np.ascontiguousarray(cols[k], dt)
-        if a.size == 0:
-            a = np.zeros(1, dt)
-        s = signed.get(np.dtype(dt))
-        t[k] = torch.from_numpy(a.view(s) if s is not None else a).to(dev)
-    return t, abi.device_ptrs(t)
-
-
-def make_ctx(contigs, cols, where, qcheck=True):
-    """(context, what must stay alive); where = 'host' (bk_upload_records) or 'device' (BK_MEM_DEVICE)"""
-    ctx = capi.Context(contigs)
-    c = dict(cols)
-    if not qcheck:
-        c.pop("qcheck", None)
-    if where == "host":
-        ctx.upload(c)
-        return ctx, None
-    t, ptrs = to_device(c, qcheck)
-    ctx.attach_device(ptrs, len(c["tid"]), int(c["cigar_off"][-1]), int(c["aux_off"][-1]))
-    return ctx, t
 
 
 def stages(ctx, fast):
@@ -407,7 +352,7 @@ def test_cli_exclude_equals_filtered_bam(mode, feed, gpus):
 @pytest.mark.parametrize("mode", ["fast", "ahc"])
 def test_cli_exclude_with_normal(mode):
     """-normal n.bam -x r.bed: the list applies to both samples; the twin files equal those of -normal on both filtered BAMs"""
-    from tests.test_gpu_normal import tumor_normal
+    from tests.callcases import tumor_normal
     tum, nor = tumor_normal()
     refgene = synth.random_refgene(tum.contigs, 60, 5)
     tcols, ncols = tum.to_soa(), nor.to_soa()

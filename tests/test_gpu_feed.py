@@ -11,23 +11,9 @@ import pytest
 
 from breakid_amd import abi, capi, synth
 from oracle import pyoracle
+from tests.callcases import device_cols
 
 pytestmark = pytest.mark.gpu
-
-
-def _device_cols(table):
-    import torch
-    from breakid_amd.sharded import tensor_from_ptr
-    dev = torch.device("cuda", 0)
-    s = table.soa
-    n = s.n
-    sizes = {"cigar_off": n + 1, "aux_off": n + 1, "cigar": s.n_cigar_words, "aux": s.n_aux_bytes}
-    out = {}
-    for name, dt in abi.SOA_COLS_ALL:
-        cnt = sizes.get(name, n)
-        nb = cnt * np.dtype(dt).itemsize
-        out[name] = tensor_from_ptr(getattr(s, name), nb, dev).cpu().numpy().view(dt).copy() if nb else np.zeros(0, dt)
-    return out
 
 
 def _dataset():
@@ -49,7 +35,7 @@ def test_device_decode_matches_generator_and_pipeline():
         table = capi.decode_bam_device(p)
         host_contigs, host_cols = capi.decode_bam(p)
     assert table.contigs == contigs == host_contigs
-    got = _device_cols(table)
+    got = device_cols(table)
     for k, _ in abi.SOA_COLS_ALL:
         assert np.array_equal(got[k], ref[k]), k
         assert np.array_equal(got[k], host_cols[k]), k
@@ -84,7 +70,7 @@ def test_device_decode_of_records_across_blocks_and_of_the_golden_shapes(packed_
         p = os.path.join(t, "u.bam")
         ds.write_bam(p)                 # fixed-size blocks: records straddle them (htsjdk / Picard style)
         table = capi.decode_bam_device(p)   # record boundaries guessed per block, verified to chain
-        got = _device_cols(table)
+        got = device_cols(table)
         assert table.contigs == contigs
         for k, _ in abi.SOA_COLS_ALL:
             assert np.array_equal(got[k], ref[k]), k
@@ -105,7 +91,7 @@ def test_device_decode_of_records_across_blocks_and_of_the_golden_shapes(packed_
             up = os.path.join(t, "u.bam")
             g.write_bam(up)
             ut = capi.decode_bam_device(up)     # records across blocks
-            ugot = _device_cols(ut)
+            ugot = device_cols(ut)
             for k, _ in abi.SOA_COLS_ALL:
                 assert np.array_equal(ugot[k], ref[k]), (make.__name__, "across blocks", k)
             ut.close()
@@ -113,7 +99,7 @@ def test_device_decode_of_records_across_blocks_and_of_the_golden_shapes(packed_
             ap = os.path.join(t, "a.bam")
             _rewrite_aligned(raw, ap)
             table = capi.decode_bam_device(ap)
-            got = _device_cols(table)
+            got = device_cols(table)
             assert table.contigs == g.contigs
             for k, _ in abi.SOA_COLS_ALL:
                 assert np.array_equal(got[k], ref[k]), (make.__name__, k)
@@ -306,7 +292,7 @@ def test_device_decode_in_chunks_equals_one_chunk():
             finally:
                 for k in env:
                     os.environ.pop(k, None)
-            got = _device_cols(table)
+            got = device_cols(table)
             assert table.contigs == contigs
             for k, _ in abi.SOA_COLS_ALL:
                 assert np.array_equal(got[k], ref[k]), (mb, k)
@@ -329,7 +315,7 @@ def test_feed_keeps_its_buffers_between_files_and_gives_them_back():
                     if rep == 3:
                         capi.lib().bk_feed_release_caches()
                     table = capi.decode_bam_device(p)
-                    got = _device_cols(table)
+                    got = device_cols(table)
                     assert table.contigs == contigs
                     for k, _ in abi.SOA_COLS_ALL:
                         assert np.array_equal(got[k], ref[k]), (aligned, rep, k)
@@ -356,7 +342,7 @@ def test_parts_of_a_file_tile_its_record_table(parts):
         finally:
             os.environ.pop("BREAKID_FEED_CHUNK_MB", None)
         def check(tables):
-            got = [_device_cols(tb) for tb in tables]
+            got = [device_cols(tb) for tb in tables]
             assert all(tb.contigs == contigs for tb in tables)
             assert sum(tb.soa.n for tb in tables) == len(ds.recs)
             assert sum(1 for tb in tables if tb.soa.n) >= min(parts, 2)
@@ -397,7 +383,7 @@ def test_device_decode_of_records_longer_than_a_block(packed_variant):
         bamio.write_bam(p, contigs, gen())
         host_contigs, host_cols = capi.decode_bam(p)
         table = capi.decode_bam_device(p)
-        got = _device_cols(table)
+        got = device_cols(table)
         assert table.contigs == contigs == host_contigs
         for k, _ in abi.SOA_COLS_ALL:
             assert np.array_equal(got[k], ref[k]), k
@@ -434,7 +420,7 @@ def test_device_decode_of_records_across_blocks_in_chunks():
                 bamio.write_bam(p, contigs, gen(long_every))
                 os.environ["BREAKID_FEED_CHUNK_MB"] = repr(mb)
                 table = capi.decode_bam_device(p)
-                got = _device_cols(table)
+                got = device_cols(table)
                 assert table.contigs == contigs
                 for k, _ in abi.SOA_COLS_ALL:
                     assert np.array_equal(got[k], ref[k]), (long_every, mb, k)

@@ -10,60 +10,13 @@ import numpy as np
 import pytest
 
 from breakid_amd import abi, bamio, capi, synth
-from tests import test_gpu_exclude as xt  # (device copies of a table, the filtered table of an exclude list)
+from tests import callcases as cc
+from tests.callcases import CONTIGS, GENOTYPE_LOCI as LOCI, expected_ref_support, genotype_tumor, side_masks, tumor
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BIN = os.path.join(ROOT, "breakid_amd", "bin", "BreakID")
 QUAL = 20
-NEVER = 0x4 | 0x100 | 0x200 | 0x400 | 0x800
-
-# ---- the definition, in numpy -----------------------------------------------------------------------------------------------
-
-
-def rec_endpos(cols):
-    """bam_endpos of every record: pos + reference length of the CIGAR (M D N = X), pos + 1 without CIGAR or with flag 0x4"""
-    cig = cols["cigar"].astype(np.int64)
-    off = cols["cigar_off"].astype(np.int64)
-    cons = np.isin(cig & 15, [0, 2, 3, 7, 8])
-    csum = np.concatenate([[0], np.cumsum(np.where(cons, cig >> 4, 0))])
-    pos = cols["pos"].astype(np.int64)
-    has = (off[1:] > off[:-1]) & ((cols["flag"] & 4) == 0)
-    return np.where(has, pos + csum[off[1:]] - csum[off[:-1]], pos + 1)
-
-
-def side_masks(cols, T, e, mapq_min, anchor, w, endpos=None, ignore_aux=False):
-    """(ref_reads mask, ref_pairs mask) over the records for one side: chromosome T, exact 1-based breakpoint e"""
-    W = int(w)  # (int) w
-    n = len(cols["tid"])
-    if T < 0:
-        return np.zeros(n, bool), np.zeros(n, bool)
-    endpos = rec_endpos(cols) if endpos is None else endpos
-    b = int(e) - 1
-    A = int(anchor)
-    flag = cols["flag"].astype(np.int64)
-    pos = cols["pos"].astype(np.int64)
-    isize = cols["isize"].astype(np.int64)
-    aux_off = cols["aux_off"].astype(np.int64)
-    elig = (cols["tid"] == T) & ((flag & 1) != 0) & ((flag & NEVER) == 0) & (cols["mapq"].astype(np.int64) >= mapq_min) & (pos <= b - A)
-    if not ignore_aux:
-        elig &= aux_off[1:] == aux_off[:-1]
-    reads = elig & (endpos >= b + 1 + A)
-    pairs = elig & ((flag & 2) != 0) & ((flag & 8) == 0) & (isize > 0) & (isize <= W) & (pos + isize >= b + 1 + A)
-    return reads, pairs
-
-
-def expected_ref_support(cl, cols, mapq_min, anchor, w):
-    out = np.zeros(len(cl), abi.REF_SUPPORT)
-    endpos = rec_endpos(cols)
-    for i, c in enumerate(cl):
-        if not c["flags"] & 2:
-            continue
-        for s, (T, e) in enumerate(((int(c["p1_tid"]), int(c["p1_exact"])), (int(c["p2_tid"]), int(c["p2_exact"]))), 1):
-            reads, pairs = side_masks(cols, T, e, mapq_min, anchor, w, endpos)
-            out[i]["ref_reads%d" % s] = int(reads.sum())
-            out[i]["ref_pairs%d" % s] = int(pairs.sum())
-    return out
 
 
 def assert_rows_equal(got, exp, cl):
@@ -78,44 +31,6 @@ def genotype_of(c, s):
 
 
 # ---- a seeded synthetic tumour ----------------------------------------------------------------------------------------------
-# (name, ta, pa, tb, pb, split reads, local proper pairs per side, truth); split reads break at 1-based pa + 30 / pb + 30
-LOCI = [("het1", 0, 300_000, 1, 700_000, 10, 200, 1), ("het2", 2, 400_000, 2, 1_200_000, 10, 200, 1), ("hom", 1, 1_500_000, 3, 250_000, 10, 0, 2),
-        ("sub", 0, 1_700_000, 2, 900_000, 4, 3000, 0), ("deep", 3, 1_200_000, 0, 1_000_000, 10, 12000, 0)]
-CONTIGS = [("chr1", 2_000_000), ("chr2", 2_000_000), ("chr3", 2_000_000), ("chr4", 2_000_000)]
-
-
-def genotype_tumor(seed=11, loci=LOCI, prefix="t", n_background=12000):
-    """12 000 background pairs; per locus 14 discordant pairs, its split reads, and local proper pairs within +-2 kb of either
-    breakpoint (the reference allele).  The homozygous locus has no reference allele: its discordant reads stay off the breakpoint
-    base (left of it on side a, right of it on side b), and no background fragment lies within 1 kb of its breakpoints."""
-    rng = np.random.default_rng(seed)
-    names = [n for n, _ in CONTIGS]
-    ds = synth.Dataset(list(CONTIGS))
-    hom = [(L[1], L[2] + 30) for L in loci if L[7] == 2] + [(L[3], L[4] + 30) for L in loci if L[7] == 2]
-    for i in range(n_background):
-        t = int(rng.integers(0, 4))
-        pr = synth._proper_pair(rng, i, t, 1000, 1_999_000, 100, 350, 40, prefix=prefix + "p")
-        if any(t == ht and pr[0].pos - 1000 < hb < pr[1].pos + 1100 for ht, hb in hom):
-            continue
-        ds.recs += pr
-    k = 0
-    for name, ta, pa, tb, pb, n_split, n_local, truth in loci:
-        for j in range(14):
-            if truth == 2:
-                da, db = -int(rng.integers(80, 300)), int(rng.integers(40, 300))  # a: ends before pa + 30; b: starts behind pb + 30
-            else:
-                da, db = int(rng.integers(-300, 301)), int(rng.integers(-300, 301))
-            ds.recs += synth._discordant_pair("%s%sD_%d" % (prefix, name, j), ta, pa + da, tb, pb + db, 100, False, True)
-        for j in range(n_split):
-            ds.recs += synth._split_pair("%s%sS_%d" % (prefix, name, j), names, ta, pa + 30, tb, pb + 30, 60, 40)
-        for t, p in ((ta, pa), (tb, pb)):
-            for j in range(n_local):
-                ds.recs += synth._proper_pair(rng, k, t, p - 2000, p + 2000, 100, 350, 40, prefix=prefix + name + "L")
-                k += 1
-    ds.sort()
-    return ds
-
-
 def locus_of(c, loci=LOCI, tol=5000):
     for L in loci:
         _, ta, pa, tb, pb = L[:5]
@@ -124,16 +39,6 @@ def locus_of(c, loci=LOCI, tol=5000):
         if (c["p1_tid"], c["p2_tid"]) == (tb, ta) and abs(int(c["p1_mean"]) - pb) < tol and abs(int(c["p2_mean"]) - pa) < tol:
             return L
     return None
-
-
-_TUMOR = {}
-
-
-def tumor():
-    if "t" not in _TUMOR:
-        ds = genotype_tumor()
-        _TUMOR["t"] = (ds, ds.to_soa())
-    return _TUMOR["t"]
 
 
 # ---- 1. the synthetic tumour ------------------------------------------------------------------------------------------------
@@ -315,10 +220,10 @@ def test_ref_support_after_exclude_regions(fast):
     tid = np.asarray([0, 2, 3, 1], np.int32)
     beg = np.asarray([299_900, 899_000, 0, 1_499_990], np.int32)  # through het1's reference reads, next to sub, the head of chr4, a sliver of hom
     end = np.asarray([299_990, 899_800, 50_000, 1_500_000], np.int32)
-    keep = ~xt.excluded_mask(cols, tid, beg, end)
-    kept = xt.filtered(cols, keep)
+    keep = ~cc.excluded_mask(cols, tid, beg, end)
+    kept = cc.filtered(cols, keep)
     for where in ("host", "device"):
-        t, hold = xt.make_ctx(ds.contigs, cols, where)
+        t, hold = cc.make_ctx(ds.contigs, cols, where)
         assert t.exclude_regions(tid, beg, end) == int((~keep).sum()) > 0
         w, _ = t.run(qual=QUAL, fast=fast)
         cl, _ = t.fetch(abi.STAGE_CLUSTERS)
@@ -344,7 +249,7 @@ def test_ref_support_device_table(side):
         hold = dcols
     else:
         ds, cols = tumor()
-        t, hold = xt.make_ctx(ds.contigs, cols, "device")
+        t, hold = cc.make_ctx(ds.contigs, cols, "device")
     w, n_valid = t.run(qual=QUAL, fast=True)
     cl, _ = t.fetch(abi.STAGE_CLUSTERS)
     assert n_valid > 0

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from breakid_amd import abi, bamio, capi, synth
+from tests.callcases import DENSE, GERMLINE, SOMATIC, expected_support, tumor_normal
 from tools import make_golden
 
 pytestmark = pytest.mark.gpu
@@ -16,111 +17,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BIN = os.path.join(ROOT, "breakid_amd", "bin", "BreakID")
 QUAL = 20
 
-# ---- the definition, in numpy -----------------------------------------------------------------------------------------------
-
-
-def pair_type(p):
-    """orientation bit of every pair, as k_accumulate folds it into type_mask"""
-    r1, r2 = p["p1_rev"] != 0, p["p2_rev"] != 0
-    same = (np.where(r1 & ~r2, 4, 0) | np.where(r1 == r2, 2, 0) | np.where(~r1 & r2, 8, 0)).astype(np.uint32)
-    return np.where(p["p1_tid"] != p["p2_tid"], np.uint32(1), same)
-
-
-def rec_endpos(cols):
-    """bam_endpos of every record: pos + reference length of the CIGAR (M D N = X), pos + 1 without CIGAR or when unmapped"""
-    cig = cols["cigar"].astype(np.int64)
-    off = cols["cigar_off"].astype(np.int64)
-    cons = np.isin(cig & 15, [0, 2, 3, 7, 8])
-    csum = np.concatenate([[0], np.cumsum(np.where(cons, cig >> 4, 0))])
-    pos = cols["pos"].astype(np.int64)
-    has = (off[1:] > off[:-1]) & ((cols["flag"] & 4) == 0)
-    return np.where(has, pos + csum[off[1:]] - csum[off[:-1]], pos + 1)
-
-
-def single_base_depth(cols, endpos, tid, bp):
-    """cal_single_base_depth: records overlapping [bp - 1, bp) with mapq > 0, not 0x400, 0x1 set"""
-    beg, end = max(0, bp - 1), bp
-    if end < beg or tid < 0:
-        return 0
-    f = cols["flag"]
-    m = (cols["tid"] == tid) & (cols["pos"].astype(np.int64) < end) & (endpos > beg) & (cols["mapq"] > 0) & ((f & 0x400) == 0) & ((f & 1) != 0)
-    return int(m.sum())
-
-
-def expected_support(cl, scan, splits, cols, w):
-    """(the synthetic reference lists have unique names: the interned id of the call's chromosome is its tid)"""
-    W = int(w)  # (int) w, truncation toward zero like the C conversion
-    out = np.zeros(len(cl), abi.NORMAL_SUPPORT)
-    pt = pair_type(scan)
-    p1 = scan["p1_pos"].astype(np.int64)
-    p2 = scan["p2_pos"].astype(np.int64)
-    ok_sp = (splits["flags"] & 2) == 0
-    pb, sb = splits["prim_bp"].astype(np.int64), splits["sec_bp"].astype(np.int64)
-    endpos = rec_endpos(cols)
-    for i, c in enumerate(cl):
-        m = ((scan["p1_tid"] == c["p1_tid"]) & (scan["p2_tid"] == c["p2_tid"]) & (p1 >= int(c["p1_min"]) - W) & (p1 <= int(c["p1_max"]) + W)
-             & (p2 >= int(c["p2_min"]) - W) & (p2 <= int(c["p2_max"]) + W) & ((pt & c["type_mask"]) != 0))
-        out[i]["n_drp"] = int(m.sum())
-        if not c["flags"] & 2:
-            continue
-        e1, e2 = int(c["p1_exact"]), int(c["p2_exact"])
-        t1, t2 = int(c["p1_tid"]), int(c["p2_tid"])
-        own = (splits["tid"] == t1) | (splits["tid"] == t2)  # tuples whose own record lies on the call's chromosomes
-        f1 = (splits["prim_chr"] == t1) & (splits["sec_chr"] == t2) & (np.abs(pb - e1) <= 2) & (np.abs(sb - e2) <= 2)
-        f2 = (splits["prim_chr"] == t2) & (splits["sec_chr"] == t1) & (np.abs(pb - e2) <= 2) & (np.abs(sb - e1) <= 2)
-        out[i]["n_sr"] = int((own & ok_sp & (f1 | f2)).sum())
-        out[i]["depth1"] = single_base_depth(cols, endpos, t1, e1)
-        out[i]["depth2"] = single_base_depth(cols, endpos, t2, e2)
-    return out
-
 
 # ---- a tumour / normal pair -----------------------------------------------------------------------------------------------
-# (ta, pa, tb, pb, rev_a, rev_b): split reads break at 1-based pa + 30 / pb + 30, as in synth.make_cfg
-GERMLINE = [(0, 300_000, 1, 700_000, False, True), (0, 900_000, 0, 1_400_000, False, True), (2, 400_000, 2, 1_200_000, True, False),
-            (1, 1_500_000, 3, 250_000, True, True)]
-DENSE = (3, 800_000, 3, 1_600_000, False, True)  # germline deletion whose window holds > 256 of the normal's pairs (several k_normal_drp steps)
-SOMATIC = [(0, 1_700_000, 2, 900_000, False, True), (1, 300_000, 1, 1_100_000, False, True), (3, 1_200_000, 2, 1_600_000, True, False)]
-
-
-def tumor_normal(seed=7, extra_contigs=0, names4=("chr1", "chr2", "chr3", "chr4")):
-    """Tumour: every locus with 14 discordant pairs and 6 split reads.  Normal: the germline loci again with fresh read names
-    and jitter (fewer pairs, 3 split reads, plus split reads 2 and 3 bp off the breakpoints and pairs of the wrong orientation),
-    the dense locus with 700 pairs, no somatic locus.  `extra_contigs` pads the reference list (records stay on the first four);
-    `names4` names the first four contigs."""
-    rng = np.random.default_rng(seed)
-    contigs = [(nm, 2_000_000) for nm in names4] + [("u%d" % i, 10_000) for i in range(extra_contigs)]
-    names = [n for n, _ in contigs]
-    tum, nor = synth.Dataset(list(contigs)), synth.Dataset(list(contigs))
-    for ds, prefix, n in ((tum, "tp", 12000), (nor, "np", 12000)):
-        for i in range(n):
-            t = int(rng.integers(0, 4))
-            ds.recs += synth._proper_pair(rng, i, t, 1000, 1_999_000, 100, 350, 40, prefix=prefix)
-
-    def locus(ds, tag, L, n_pairs, n_splits, jitter=300, bp_shift=0, rev=None):
-        ta, pa, tb, pb, ra, rb = L
-        if rev is not None:
-            ra, rb = rev
-        for k in range(n_pairs):
-            ds.recs += synth._discordant_pair("%s_%d" % (tag, k), ta, pa + int(rng.integers(-jitter, jitter + 1)), tb, pb + int(rng.integers(-jitter, jitter + 1)),
-                                              100, ra, rb)
-        for k in range(n_splits):
-            ds.recs += synth._split_pair("%sS_%d" % (tag, k), names, ta, pa + 30 + bp_shift, tb, pb + 30 + bp_shift, 60, 40)
-
-    for li, L in enumerate(GERMLINE):
-        locus(tum, "TG%d" % li, L, 14, 6)
-        locus(nor, "NG%d" % li, L, 6 + li, 3)
-        locus(nor, "NGa%d" % li, L, 0, 1, bp_shift=2)  # inside the +-2 bp of the vote
-        locus(nor, "NGb%d" % li, L, 0, 1, bp_shift=3)  # outside
-        locus(nor, "NGo%d" % li, L, 3, 0, rev=(not L[4], not L[5]) if L[0] != L[2] else (True, True))  # other orientation
-    locus(tum, "TD", DENSE, 14, 6)
-    locus(nor, "ND", DENSE, 700, 3, jitter=400)
-    for li, L in enumerate(SOMATIC):
-        locus(tum, "TS%d" % li, L, 14, 6)
-    tum.sort()
-    nor.sort()
-    return tum, nor
-
-
 def locus_of(c, loci, tol=5000):
     for L in loci:
         ta, pa, tb, pb = L[:4]

@@ -11,43 +11,15 @@ import tempfile
 import numpy as np
 import pytest
 
-from breakid_amd import abi, bamio, capi, synth
-from tests import test_gpu_exclude as xt    # (device copies of a table, the filtered table of an exclude list)
-from tests import test_gpu_genotype as gt   # (the genotype tumour)
-from tests import test_gpu_normal as nt     # (the tumour / normal pair with a padded, renamed reference list)
+from breakid_amd import abi, capi, synth
+from tests import callcases as cc
+from tests.callcases import (EXCLUDE, LOCI, MIX, NAMES, call_dataset, designed_normal, designed_refgene, designed_tumor, expected_junctions, fusion_rows,
+                             quiet_tumor, rows_of, write_indexed)
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BIN = os.path.join(ROOT, "breakid_amd", "bin", "BreakID")
 QUAL = 20
-
-# ---- the definition, in numpy -----------------------------------------------------------------------------------------------
-
-
-def expected_junctions(cl, clustered, splits):
-    """(the synthetic reference lists have unique names: the interned id of a header contig is its tid)"""
-    out = np.zeros(len(cl), abi.JUNCTION)
-    key = (clustered["group"].astype(np.int64) << 32) | (clustered["cluster"].astype(np.int64) & 0xFFFFFFFF)
-    strands = 2 * clustered["p1_rev"].astype(np.int64) + clustered["p2_rev"].astype(np.int64)
-    q1, q2 = clustered["p1_mapq"].astype(np.int64), clustered["p2_mapq"].astype(np.int64)
-    ok_sp = (splits["flags"] & 2) == 0
-    pb, sb = splits["prim_bp"].astype(np.int64), splits["sec_bp"].astype(np.int64)
-    prim_right = (splits["prim_bp"] == splits["prim_start"]).astype(np.int64)
-    sec_right = (splits["sec_bp"] == splits["sec_start"]).astype(np.int64)
-    for i, c in enumerate(cl):
-        m = key == ((int(c["group"]) << 32) | (int(c["id"]) & 0xFFFFFFFF))
-        out["pairs"][i] = np.bincount(strands[m], minlength=4)
-        out["mapq_sum1"][i] = int(q1[m].sum())
-        out["mapq_sum2"][i] = int(q2[m].sum())
-        if not c["flags"] & 2:
-            continue
-        e1, e2 = int(c["p1_exact"]), int(c["p2_exact"])
-        t1, t2 = int(c["p1_tid"]), int(c["p2_tid"])
-        own = ((splits["tid"] == t1) | (splits["tid"] == t2)) & ok_sp
-        f1 = own & (splits["prim_chr"] == t1) & (splits["sec_chr"] == t2) & (np.abs(pb - e1) <= 2) & (np.abs(sb - e2) <= 2)
-        f2 = own & ~f1 & (splits["prim_chr"] == t2) & (splits["sec_chr"] == t1) & (np.abs(pb - e2) <= 2) & (np.abs(sb - e1) <= 2)
-        out["splits"][i] = (np.bincount((2 * prim_right + sec_right)[f1], minlength=4) + np.bincount((2 * sec_right + prim_right)[f2], minlength=4))
-    return out
 
 
 def assert_rows_equal(got, exp, cl):
@@ -86,21 +58,10 @@ def self_normal_sr(contigs, cols, t, w):
 
 
 # ---- 1. the definition, every row ---------------------------------------------------------------------------------------------
-def _dataset(name):
-    if name == "genotype":
-        return gt.tumor()
-    if name == "edge":
-        ds = synth.make_edge()
-    else:
-        contigs = [("chr%d" % i, 3_000_000) for i in range(1, 9)]
-        ds = synth.make_cfg(17, contigs, 120_000, 300, 16, 200, split_every=1, splits_per_locus=6, jitter=250, read_len=100)
-    return ds, ds.to_soa()
-
-
 @pytest.mark.parametrize("name", ["genotype", "edge", "cfg"])
 @pytest.mark.parametrize("fast", [True, False])
 def test_junctions_equal_their_definition(fast, name):
-    ds, cols = _dataset(name)
+    ds, cols = call_dataset(name)
     t = capi.Context(ds.contigs)
     t.upload(cols)
     w, n_valid = t.run(qual=QUAL, fast=fast)
@@ -114,7 +75,7 @@ def test_junctions_equal_their_definition(fast, name):
 def test_junctions_renamed_reference_list(fast):
     """a padded reference list that names chr2 before chr1: a tuple's own side carries the id of chr1 on the first contig and of
     chr2 on the second, and the tuple search must follow those ids"""
-    tum, _ = nt.tumor_normal(extra_contigs=300, names4=("chr2", "chr1", "chr3", "chr4"))
+    tum, _ = cc.tumor_normal(extra_contigs=300, names4=("chr2", "chr1", "chr3", "chr4"))
     cols = tum.to_soa()
     t = capi.Context(tum.contigs)
     t.upload(cols)
@@ -125,54 +86,6 @@ def test_junctions_renamed_reference_list(fast):
 
 
 # ---- 2. designed truth --------------------------------------------------------------------------------------------------------
-CONTIGS = [("chr1", 2_000_000), ("chr2", 2_000_000), ("chr3", 2_000_000), ("chr4", 2_000_000)]
-NAMES = [n for n, _ in CONTIGS]
-# (name, ta, bpa, da, tb, bpb, db): d = 'L' the retained sequence lies left of the breakpoint (the alignment ends at it), 'R' right
-LOCI = [("LR_x", 0, 300_000, "L", 1, 700_000, "R"), ("LL_x", 0, 600_000, "L", 2, 500_000, "L"), ("RR_x", 1, 300_000, "R", 3, 900_000, "R"),
-        ("RL_x", 2, 900_000, "R", 3, 400_000, "L"),
-        ("LR_s", 0, 1_000_000, "L", 0, 1_400_000, "R"), ("LL_s", 1, 1_000_000, "L", 1, 1_400_000, "L"), ("RR_s", 2, 1_200_000, "R", 2, 1_600_000, "R"),
-        ("RL_s", 3, 1_200_000, "R", 3, 1_600_000, "L")]
-MIX = ("MIX", 0, 1_700_000, 2, 1_300_000)  # pairs of strands (forward, reverse), split reads clipped as (L, L)
-
-
-def designed_split(q, ta, bpa, da, tb, bpb, db, m1=60, m2=40):
-    """own record m1M m2S ending at 1-based bpa (left) or m2S m1M starting at it (right); the 0x100 partner m2M m1S ending at / m1S m2M
-    starting at bpb; SA strings as synth._split_pair writes them"""
-    ca = "%dM%dS" % (m1, m2) if da == "L" else "%dS%dM" % (m2, m1)
-    pa = bpa - m1 if da == "L" else bpa - 1
-    cb = "%dM%dS" % (m2, m1) if db == "L" else "%dS%dM" % (m1, m2)
-    pb = bpb - m2 if db == "L" else bpb - 1
-    st = "-" if da == db else "+"
-    sa1 = "%s,%d,%s,%s,60,0;" % (NAMES[tb], pb + 1, st, cb)
-    sa2 = "%s,%d,%s,%s,60,0;" % (NAMES[ta], pa + 1, st, ca)
-    prim = synth.Rec(q, 0x1 | 0x2 | 0x40 | 0x20, ta, pa, 60, ca, ta, pa + 200, 300, sa=sa1)
-    part = synth.Rec(q, 0x1 | 0x40 | 0x20 | 0x100, tb, pb, 60, cb, ta, pa + 200, 0, sa=sa2)
-    mate = synth.Rec(q, 0x1 | 0x2 | 0x80 | 0x10, ta, pa + 200, 60, "100M", ta, pa, -300)
-    return [prim, part, mate]
-
-
-def designed_tumor(mix=True):
-    rng = np.random.default_rng(5)
-    ds = synth.Dataset(list(CONTIGS))
-    for i in range(12000):
-        ds.recs += synth._proper_pair(rng, i, int(rng.integers(0, 4)), 1000, 1_999_000, 100, 350, 40)
-    for name, ta, bpa, da, tb, bpb, db in LOCI:
-        for j in range(14):
-            oa = -int(rng.integers(100, 400)) if da == "L" else int(rng.integers(0, 300))
-            ob = -int(rng.integers(100, 400)) if db == "L" else int(rng.integers(0, 300))
-            ds.recs += synth._discordant_pair("%sD_%d" % (name, j), ta, bpa + oa, tb, bpb + ob, 100, rev_a=(da == "R"), rev_b=(db == "R"))
-        for j in range(8):
-            ds.recs += designed_split("%sS_%d" % (name, j), ta, bpa, da, tb, bpb, db)
-    if mix:
-        _, ta, bpa, tb, bpb = MIX
-        for j in range(14):
-            ds.recs += synth._discordant_pair("MIXD_%d" % j, ta, bpa - int(rng.integers(100, 400)), tb, bpb + int(rng.integers(0, 300)), 100, rev_a=False, rev_b=True)
-        for j in range(8):
-            ds.recs += designed_split("MIXS_%d" % j, ta, bpa, "L", tb, bpb, "L")
-    ds.sort()
-    return ds
-
-
 _DESIGNED = {}
 
 
@@ -181,20 +94,6 @@ def designed():
         ds = designed_tumor()
         _DESIGNED["t"] = (ds, ds.to_soa())
     return _DESIGNED["t"]
-
-
-def rows_of(cl, ta, bpa, tb, bpb):
-    """voted rows whose exact breakpoints are the two given ones: [(row, True when side 1 is A)]"""
-    out = []
-    for i, c in enumerate(cl):
-        if not c["flags"] & 2:
-            continue
-        s1, s2 = (int(c["p1_tid"]), int(c["p1_exact"])), (int(c["p2_tid"]), int(c["p2_exact"]))
-        if (s1, s2) == ((ta, bpa), (tb, bpb)):
-            out.append((i, True))
-        elif (s1, s2) == ((tb, bpb), (ta, bpa)):
-            out.append((i, False))
-    return out
 
 
 def zero_splits(row):
@@ -251,7 +150,7 @@ def test_junctions_table_forms(form):
         hold = dcols
     else:
         ds, cols = designed()
-        t, hold = xt.make_ctx(ds.contigs, cols, "device" if form.endswith("device") else "host")
+        t, hold = cc.make_ctx(ds.contigs, cols, "device" if form.endswith("device") else "host")
         if form.startswith("exclude"):
             tid, beg, end = np.asarray([0, 3], np.int32), np.asarray([50_000, 100_000], np.int32), np.asarray([60_000, 120_000], np.int32)
             assert t.exclude_regions(tid, beg, end) > 0
@@ -300,15 +199,6 @@ def test_junctions_call_order_and_errors():
     s.close()
 
 
-def quiet_tumor():
-    tum = synth.Dataset(list(CONTIGS))
-    rng = np.random.default_rng(3)
-    for i in range(4000):
-        tum.recs += synth._proper_pair(rng, i, int(rng.integers(0, 4)), 1000, 1_999_000, 100, 350, 40)
-    tum.sort()
-    return tum
-
-
 def test_junctions_of_a_context_without_clusters():
     tum = quiet_tumor()
     t = capi.Context(tum.contigs)
@@ -332,17 +222,6 @@ def fusion_type(mask):
         if mask & bit:
             return text
     return "Unknown"
-
-
-def designed_refgene():
-    """a gene on either side of the four loci that join two contigs (they pass the gene-pair filter); none at the other loci"""
-    rows = []
-    for name, ta, bpa, da, tb, bpb, db in LOCI[:4]:
-        for tag, t, bp in (("A", ta, bpa), ("B", tb, bpb)):
-            s, e = bp - 10_000, bp + 10_000
-            rows.append("0\tNM_%s%s\t%s\t+\t%d\t%d\t%d\t%d\t2\t%d,%d,\t%d,%d,\t0\tG%s_%s\tcmpl\tcmpl\t0,0," % (
-                name, tag, NAMES[t], s, e, s + 50, e - 50, s, bp + 2_000, bp - 2_000, e, tag, name))
-    return rows
 
 
 def nib_base(nib_dir, chrom, pos1):
@@ -421,34 +300,6 @@ def read_vcf(path, contigs):
         assert mate["alt"]["mate_right"] == r["alt"]["own_right"], (r, mate)  # the mate's bracket agrees with where this record's base stands
         assert mate["FILTER"] == r["FILTER"] and mate["FORMAT"] == r["FORMAT"]
     return cols[9:], recs
-
-
-def fusion_rows(path):
-    lines = open(path).read().split("\n")
-    return [l.split("\t") for l in lines[1:] if l]
-
-
-def designed_normal():
-    """a normal with background, the first locus again (fewer reads) and nothing else"""
-    rng = np.random.default_rng(23)
-    ds = synth.Dataset(list(CONTIGS))
-    for i in range(8000):
-        ds.recs += synth._proper_pair(rng, i, int(rng.integers(0, 4)), 1000, 1_999_000, 100, 350, 40, prefix="np")
-    name, ta, bpa, da, tb, bpb, db = LOCI[0]
-    for j in range(6):
-        ds.recs += synth._discordant_pair("n%sD_%d" % (name, j), ta, bpa - int(rng.integers(100, 400)), tb, bpb + int(rng.integers(0, 300)), 100, rev_a=False, rev_b=True)
-    for j in range(3):
-        ds.recs += designed_split("n%sS_%d" % (name, j), ta, bpa, da, tb, bpb, db)
-    ds.sort()
-    return ds
-
-
-def write_indexed(ds, path, aligned=True):
-    ds.write_bam(path, aligned=aligned)
-    bamio.write_bai(path)
-
-
-EXCLUDE = (np.asarray([0, 3], np.int32), np.asarray([50_000, 100_000], np.int32), np.asarray([60_000, 120_000], np.int32))
 
 
 def assert_other_files_identical(a, b, tmp):

@@ -3,7 +3,7 @@
 The configs[1]-shaped table is generated in HBM (breakid_amd.synth_gpu.make_wgs, sized as bench.py sizes it), one hot-path step
 (-fast) gives the calls, and the sample itself is genotyped (`records == calls`): a warm-up call, then `--reps` calls, each with the
 HIP-event time of the call's `ref_support` scope (the device work: the sampled search keys and k_ref_support), the wall clock around
-the call from Python (that plus the copy back of one row per call and the host reorder), the records visited and the bytes by the
+the call from Python (that plus the copy back of one row per call), the records visited and the bytes by the
 library's model (bk_timing: 19 B per visited record; bk_timing_touched: those, the CIGAR words walked and the rows).
 
 The yardstick is k_bp_depth of the same process (same calls, same searches, a one-base window); it has no scope of its own, so it

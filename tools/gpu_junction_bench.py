@@ -3,7 +3,7 @@
 Two configs[1]-shaped tables are generated in HBM (breakid_amd.synth_gpu.make_wgs, as tools/gpu_normal_cost.py does), resident
 together: the tumour runs the whole hot path (-fast), the normal only its record-level stages.  After a warm-up of both calls,
 `--reps` calls of each: the HIP-event time of the call's scope (`junctions`: the clear and the two kernels; `normal_support`: index
-sort, kernels, copy back and host reorder, as round 7 reported it), the wall clock around the call from Python, and for
+sort, kernels and copy back), the wall clock around the call from Python, and for
 `junctions` the bytes by the library's model (bk_timing: 16 B per list entry; bk_timing_touched: 44 B per list entry, 88 B per tuple
 searched, the rows).  The normal holds the tumour's own records (same seed), so the four `splits` bins of every row must sum to
 its `n_sr`.
@@ -92,7 +92,7 @@ def main():
         "normal_support_event_ms": [round(x, 4) for x in res["normal_support"][1]], "normal_support_wall_ms": [round(x, 3) for x in res["normal_support"][0]],
         "normal_support_event_ms_median": round(ev_n, 4), "normal_support_wall_ms_median": round(float(np.median(res["normal_support"][0])), 3),
         "junctions_model_bytes": int(res["junctions"][3][-1]),
-        "junctions_tuples_searched": int((res["junctions"][3][-1] - list_entries * 44 - len(cl) * (72 + 2 * 48 + 8)) // 88),
+        "junctions_tuples_searched": int((res["junctions"][3][-1] - list_entries * 44 - len(cl) * (72 + 2 * 48 + 4)) // 88),
         "junctions_model_tb_per_s": round(res["junctions"][3][-1] / (ev_j * 1e-3) / 1e12, 3) if ev_j > 0 else None,
         "pairs_sum_equals_n_drp": bool(np.array_equal(junc["pairs"].astype(np.int64).sum(1), cl["n_drp"].astype(np.int64))),
         "splits_sum_equals_normal_n_sr": bool(np.array_equal(junc["splits"].astype(np.int64).sum(1), sup["n_sr"].astype(np.int64))),

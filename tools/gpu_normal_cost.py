@@ -4,7 +4,7 @@ Two configs[1]-shaped tables are generated in HBM (breakid_amd.synth_gpu.make_wg
 tumour runs the whole hot path (-fast), the normal only its record-level stages (stream pass, mate join with the tumour's w,
 split evidence).  The normal is generated with the tumour's seed, so every tumour call finds its own pairs and tuples in the
 normal: the windows are as full as they get.  Then `normal_support` is timed `--reps` times: wall clock around the call
-(index sort, three kernels, copy back of one 16-byte row per cluster, host reorder) and the HIP-event time of its stage scope.
+(index sort, three kernels, copy back of one 16-byte row per cluster) and the HIP-event time of its stage scope.
 
     python tools/gpu_normal_cost.py [--records 620000000] [--reps 5] [--out profiles/FILE.json]
 
