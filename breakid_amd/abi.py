@@ -25,6 +25,9 @@ NORMAL_SUPPORT = np.dtype([("n_drp", "<u4"), ("n_sr", "<u4"), ("depth1", "<u4"),
 REF_SUPPORT = np.dtype([("ref_pairs1", "<u4"), ("ref_pairs2", "<u4"), ("ref_reads1", "<u4"), ("ref_reads2", "<u4")])  # struct bk_ref_support
 JUNCTION = np.dtype([("pairs", "<u4", (4,)), ("splits", "<u4", (4,)), ("mapq_sum1", "<u8"), ("mapq_sum2", "<u8")])  # struct bk_junction
 assert JUNCTION.itemsize == 48
+CLIP_LEFT, CLIP_RIGHT = 0, 1
+CLIP_SUPPORT = np.dtype([("at", "<u4", (2, 2)), ("peak_pos", "<u4", (2, 2)), ("peak_n", "<u4", (2, 2)), ("events", "<u4", (2, 2))])  # struct bk_clip_support, [side][dir]
+assert CLIP_SUPPORT.itemsize == 64
 EV_PAIR, EV_SPLIT = 1, 2
 EVIDENCE = np.dtype([("rec", "<u8"), ("qhash", "<u8"), ("qcheck", "<u4"), ("call", "<u4"), ("tid1", "<i4"), ("pos1", "<u4"), ("tid2", "<i4"),
                      ("pos2", "<u4"), ("flag1", "<u2"), ("flag2", "<u2"), ("mapq1", "u1"), ("mapq2", "u1"), ("kind", "u1"), ("sides", "u1")])  # struct bk_evidence

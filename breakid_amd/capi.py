@@ -35,7 +35,7 @@ def build(verbose=False):
 
 EXPORTS = ["bk_init", "bk_prepare_process", "bk_free", "bk_last_error", "bk_set_stream", "bk_sync", "bk_get_stream", "bk_upload_records", "bk_exclude_regions", "bk_isize_stats",
            "bk_discordant_pairs", "bk_mask_and_cluster", "bk_split_evidence", "bk_cluster_summary",
-           "bk_split_breakpoints", "bk_normal_support", "bk_ref_support", "bk_genotype_call", "bk_junctions", "bk_junction_sides", "bk_vcf_breakend_alt", "bk_evidence", "bk_run", "bk_fetch", "bk_timing", "bk_timing_enable", "bk_timing_touched", "bk_group_stats", "bk_qname_hash", "bk_qname_check",
+           "bk_split_breakpoints", "bk_normal_support", "bk_ref_support", "bk_genotype_call", "bk_clip_support", "bk_base_depth", "bk_clip_rescue", "bk_junctions", "bk_junction_sides", "bk_vcf_breakend_alt", "bk_evidence", "bk_run", "bk_fetch", "bk_timing", "bk_timing_enable", "bk_timing_touched", "bk_group_stats", "bk_qname_hash", "bk_qname_check",
            "bk_bam_open", "bk_bam_header", "bk_bam_decode", "bk_bam_close", "bk_bam_extract", "bk_bam_names_free", "bk_bam_decode_device", "bk_bam_decode_device_part", "bk_bam_decode_device_ctx", "bk_bam_dev_free", "bk_feed_release_caches", "bk_debug_bgzf_inflate", "bk_debug_std_sort", "bk_sort_forms", "bk_debug_ahc", "bk_debug_points", "bk_debug_cigar", "bk_debug_vote", "bk_debug_region", "bk_shard_begin", "bk_shard_get_stats", "bk_shard_set_stats",
            "bk_shard_sd_local", "bk_shard_sd_finish", "bk_shard_buffer", "bk_shard_set_buffer", "bk_shard_group_sizes",
            "bk_shard_own_groups", "bk_shard_route_candidates", "bk_shard_group_keys", "bk_shard_route_pairs", "bk_shard_group_pairs", "bk_shard_bp_cov", "bk_shard_bp_vote", "bk_shard_bp_vote_slice", "bk_shard_bp_set_voted", "bk_shard_bp_depth", "bk_shard_bp_finish"]
@@ -73,6 +73,9 @@ def lib():
         L.bk_normal_support.argtypes = [vp, vp, C.c_double, C.POINTER(vp), u64p]
         L.bk_ref_support.argtypes = [vp, vp, C.c_int, C.c_int, C.c_double, C.POINTER(vp), u64p]
         L.bk_genotype_call.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), C.POINTER(C.c_float)]
+        L.bk_clip_support.argtypes = [vp, vp, C.c_int, C.c_int, C.c_double, C.POINTER(vp), u64p]
+        L.bk_base_depth.argtypes = [vp, vp, vp, C.c_uint64, C.POINTER(vp)]
+        L.bk_clip_rescue.argtypes = [vp, vp, vp, C.c_uint32] + [C.POINTER(C.c_uint32)] * 4
         L.bk_junctions.argtypes = [vp, C.POINTER(vp), u64p]
         L.bk_junction_sides.argtypes = [vp, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), C.POINTER(C.c_uint8)]
         L.bk_vcf_breakend_alt.argtypes = [C.c_char, C.c_int, C.c_char_p, C.c_uint32, C.c_int, C.c_char_p, C.c_size_t]
@@ -159,6 +162,19 @@ def junction_sides(row):
     if rc != 0:
         raise BreakIDError(rc, "bk_junction_sides")
     return r1.value, r2.value, src.value
+
+
+def clip_rescue(cluster, junction, clip, min_support=3):
+    """The library's rescue rule (bk_clip_rescue; no GPU) for one abi.CLUSTER row with its abi.JUNCTION and abi.CLIP_SUPPORT rows:
+    (pos1, pos2, n1, n2) when the unvoted cluster has a clip peak of at least min_support reads on both sides, in the directions
+    its pairs give; None otherwise.  min_support = 0 raises BreakIDError(BK_ERR_ARG)."""
+    c, j, s = np.zeros(1, abi.CLUSTER), np.zeros(1, abi.JUNCTION), np.zeros(1, abi.CLIP_SUPPORT)
+    c[0], j[0], s[0] = cluster, junction, clip
+    out = [C.c_uint32() for _ in range(4)]
+    rc = lib().bk_clip_rescue(c.ctypes.data, j.ctypes.data, s.ctypes.data, int(min_support), *[C.byref(o) for o in out])
+    if rc < 0:
+        raise BreakIDError(rc, "bk_clip_rescue")
+    return tuple(o.value for o in out) if rc == 1 else None
 
 
 def vcf_breakend_alt(ref_base, own_right, mate_chr, mate_pos, mate_right, cap=None):
@@ -332,6 +348,28 @@ class Context:
             return np.zeros(0, abi.REF_SUPPORT)
         buf = (C.c_char * (n.value * abi.REF_SUPPORT.itemsize)).from_address(data.value)
         return np.frombuffer(buf, dtype=abi.REF_SUPPORT, count=n.value).copy()
+
+    def clip_support(self, records, mapq_min, min_clip, w):
+        """Soft-clip evidence of this context's clusters on the record table of `records` (bk_clip_support): one abi.CLIP_SUPPORT
+        row per STAGE_CLUSTERS row, voted or not.  `records`: this context itself, or a Context on the same device and reference
+        list (the matched normal), after isize_stats; `w`: this context's distance."""
+        data, n = C.c_void_p(), C.c_uint64()
+        self._check(self.L.bk_clip_support(self.h, records.h, int(mapq_min), int(min_clip), w, C.byref(data), C.byref(n)))
+        if not n.value:
+            return np.zeros(0, abi.CLIP_SUPPORT)
+        buf = (C.c_char * (n.value * abi.CLIP_SUPPORT.itemsize)).from_address(data.value)
+        return np.frombuffer(buf, dtype=abi.CLIP_SUPPORT, count=n.value).copy()
+
+    def base_depth(self, tid, pos):
+        """cal_single_base_depth on this context's records at arbitrary 1-based positions (bk_base_depth): one uint32 per entry."""
+        tid = np.ascontiguousarray(tid, np.int32)
+        pos = np.ascontiguousarray(pos, np.uint32)
+        assert tid.shape == pos.shape and tid.ndim == 1
+        data = C.c_void_p()
+        self._check(self.L.bk_base_depth(self.h, tid.ctypes.data, pos.ctypes.data, len(tid), C.byref(data)))
+        if not len(tid):
+            return np.zeros(0, np.uint32)
+        return np.ctypeslib.as_array(C.cast(data, C.POINTER(C.c_uint32)), shape=(len(tid),)).copy()
 
     def run(self, qual=20, fast=True):
         w, n = C.c_double(), C.c_uint64()

@@ -13,6 +13,7 @@
 #include "bp.h"
 #include "normal.h"
 #include "genotype.h"
+#include "clip.h"
 #include "junction.h"
 #include "evidence.h"
 #include "exclude.h"
@@ -120,6 +121,11 @@ struct bk_ctx
   // reference-allele evidence (bk_ref_support: this context holds the calls)
   RefBufs rb;
   std::vector<struct bk_ref_support> f_ref;
+  // soft-clip evidence (bk_clip_support: this context holds the calls) and depth at arbitrary positions (bk_base_depth)
+  ClipBufs cb;
+  std::vector<struct bk_clip_support> f_clip;
+  DevBuf d_bd_tid, d_bd_pos, d_bd_out, d_bd_samp;
+  std::vector<uint32_t> f_base_depth;
   // junction evidence (bk_junctions); summary_map: bb still holds the slot -> cluster-row map of the last bk_cluster_summary
   JunctionBufs jnb;
   std::vector<struct bk_junction> f_junction;
@@ -898,6 +904,76 @@ int bk_ref_support(bk_ctx *calls, bk_ctx *records, int mapq_min, int anchor, dou
   });
 }
 
+int bk_clip_support(bk_ctx *calls, bk_ctx *records, int mapq_min, int min_clip, double w, const struct bk_clip_support **out, uint64_t *count)
+{
+  if (!records) return guarded(calls, [&] { throw bk_error(BK_ERR_ARG, "bk_clip_support: null records context"); });
+  return guarded(calls, [&] {
+    if (!out || !count) throw bk_error(BK_ERR_ARG, "bk_clip_support: null output");
+    if (calls->shard || records->shard) throw bk_error(BK_ERR_ARG, "bk_clip_support: sharded contexts (bk_shard_*) are not supported");
+    if (!calls->bp_done) throw bk_error(BK_ERR_ARG, "bk_clip_support: call bk_split_breakpoints on the calls context first");
+    if (!records->have_records || !records->stats_done) throw bk_error(BK_ERR_ARG, "bk_clip_support: call bk_isize_stats on the records context first");
+    if (min_clip < 1) throw bk_error(BK_ERR_ARG, "bk_clip_support: min_clip must be at least 1");
+    if (mapq_min < 0) throw bk_error(BK_ERR_ARG, "bk_clip_support: mapq_min must not be negative");
+    if (!(w >= 0.0 && w < 2147483648.0)) throw bk_error(BK_ERR_ARG, "bk_clip_support: w is out of range");
+    require_same_reference("bk_clip_support", "calls", calls, "records", records);
+    const bk_soa &t = records->rec;
+    if (t.n && (!t.tid || !t.pos || !t.flag || !t.mapq || !t.cigar_off || !t.aux_off)) throw bk_error(BK_ERR_ARG, "bk_clip_support: the record table lacks a column");
+    const uint64_t ncl = calls->n_clusters;
+    if (records != calls) HIP_CHECK(hipStreamSynchronize(records->st));  // its stages ran on its own stream
+    struct bk_clip_support *d_res;
+    ClipStat *d_stat = nullptr;
+    {
+      Scope s(calls, "clip_support");  // the device work alone: the copies below would hide it
+      clip_support(rec_view(records), (int) records->hc.max_span, calls->clusters_ptr(), ncl, mapq_min, min_clip, w, calls->cb, calls->st, &d_res,
+                   calls->timing ? &d_stat : nullptr);
+    }
+    std::vector<ClipStat> stat(d_stat ? 2 * ncl : 0);
+    if (!stat.empty()) HIP_CHECK(hipMemcpyAsync(stat.data(), d_stat, 2 * ncl * sizeof(ClipStat), hipMemcpyDeviceToHost, calls->st));
+    rows_to_host(calls, d_res, ncl, calls->f_clip);
+    if (calls->timing && !calls->timers.empty())
+    {
+      // bytes: pos, flag, mapq and two aux_off words of every record a tile looks at (15 B each; bytes / 15 = records visited).
+      // touched: those, the CIGAR offsets and words read, and per call two bk_cluster reads (one per side) and the row.
+      uint64_t visited = 0, words = 0;
+      for (const ClipStat &x : stat)
+      {
+        visited += x.visited;
+        words += x.words;
+      }
+      calls->timers.back().bytes = 15ull * visited;
+      calls->timers.back().touched = 15ull * visited + 4ull * words + ncl * (2ull * sizeof(bk_cluster) + sizeof(struct bk_clip_support));
+    }
+    *out = calls->f_clip.data();
+    *count = ncl;
+  });
+}
+
+int bk_base_depth(bk_ctx *records, const int32_t *tid, const uint32_t *pos, uint64_t n, const uint32_t **out)
+{
+  return guarded(records, [&] {
+    if (!out || (n && (!tid || !pos))) throw bk_error(BK_ERR_ARG, "bk_base_depth: null argument");
+    if (records->shard) throw bk_error(BK_ERR_ARG, "bk_base_depth: sharded contexts (bk_shard_*) are not supported");
+    if (!records->have_records || !records->stats_done) throw bk_error(BK_ERR_ARG, "bk_base_depth: call bk_isize_stats first");
+    const bk_soa &t = records->rec;
+    if (t.n && (!t.tid || !t.pos || !t.flag || !t.mapq || !t.cigar_off)) throw bk_error(BK_ERR_ARG, "bk_base_depth: the record table lacks a column");
+    records->f_base_depth.assign(n, 0u);
+    if (n)
+    {
+      int32_t *d_tid = records->d_bd_tid.as<int32_t>(n);
+      uint32_t *d_pos = records->d_bd_pos.as<uint32_t>(n), *d_out = records->d_bd_out.as<uint32_t>(n);
+      HIP_CHECK(hipMemcpyAsync(d_tid, tid, n * 4, hipMemcpyHostToDevice, records->st));
+      HIP_CHECK(hipMemcpyAsync(d_pos, pos, n * 4, hipMemcpyHostToDevice, records->st));
+      {
+        Scope s(records, "base_depth");
+        base_depth_at(rec_view(records), d_tid, d_pos, n, (int) records->hc.max_span, records->d_bd_samp, records->st, d_out);
+      }
+      HIP_CHECK(hipMemcpyAsync(records->f_base_depth.data(), d_out, n * 4, hipMemcpyDeviceToHost, records->st));
+      HIP_CHECK(hipStreamSynchronize(records->st));
+    }
+    *out = records->f_base_depth.data();
+  });
+}
+
 // The genotype model of one call (include/breakid_hip.h): pure host code, every product rounded on its own (the library is built
 // with -ffp-contract=off).
 int bk_genotype_call(uint32_t alt, uint32_t ref, uint8_t *gt, uint8_t *gq, float *vaf)
@@ -1034,6 +1110,22 @@ int bk_junction_sides(const struct bk_junction *j, uint8_t *right1, uint8_t *rig
   *right1 = (uint8_t) (idx >> 1);
   *right2 = (uint8_t) (idx & 1);
   return BK_OK;
+}
+
+// The rescue rule of one unvoted cluster (include/breakid_hip.h): pure host code.
+int bk_clip_rescue(const bk_cluster *c, const struct bk_junction *j, const struct bk_clip_support *s, uint32_t min_support, uint32_t *pos1, uint32_t *pos2, uint32_t *n1,
+                   uint32_t *n2)
+{
+  if (!c || !j || !s || !pos1 || !pos2 || !n1 || !n2 || min_support == 0) return BK_ERR_ARG;
+  if ((c->flags & 2u) || c->p1_tid < 0 || c->p2_tid < 0) return 0;
+  uint8_t d1 = 0, d2 = 1, source = 0;
+  bk_junction_sides(j, &d1, &d2, &source);
+  if (s->peak_n[0][d1] < min_support || s->peak_n[1][d2] < min_support) return 0;
+  *pos1 = s->peak_pos[0][d1];
+  *pos2 = s->peak_pos[1][d2];
+  *n1 = s->peak_n[0][d1];
+  *n2 = s->peak_n[1][d2];
+  return 1;
 }
 
 int bk_vcf_breakend_alt(char ref_base, int own_right, const char *mate_chr, uint32_t mate_pos, int mate_right, char *buf, size_t cap)

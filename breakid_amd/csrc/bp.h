@@ -101,6 +101,9 @@ RecView rec_sampled(const RecView &r, DevBuf &samp, hipStream_t st);
 uint32_t *bp_cov_partial(const RecView &r, const bk_cluster *cl, uint64_t ncl, double w, int maxspan, BpBufs &b, hipStream_t st);
 void bp_vote(const bk_split *sp, uint64_t nsp, bk_cluster *cl, uint64_t ncl, double w, int maxspan, const uint32_t *cov, const int32_t *hdr_id, BpBufs &b, hipStream_t st);
 uint32_t *bp_depth_partial(const RecView &r, const bk_cluster *cl, uint64_t ncl, int maxspan, BpBufs &b, hipStream_t st);
+// cal_single_base_depth (base_depth_wave, the count behind depth1 / depth2) at n arbitrary 1-based positions: tid, pos and depth are
+// device arrays of n entries, `samp` backs the sampled search keys
+void base_depth_at(const RecView &r, const int32_t *tid, const uint32_t *pos, uint64_t n, int maxspan, DevBuf &samp, hipStream_t st, uint32_t *depth);
 void bp_finish(bk_cluster *cl, uint64_t ncl, const uint32_t *depth, BpBufs &b, hipStream_t st);
 void split_breakpoints(const RecView &r, const bk_split *sp, uint64_t nsp, bk_cluster *cl, uint64_t ncl, double w, int maxspan, const int32_t *hdr_id, BpBufs &b,
                        hipStream_t st);

@@ -586,6 +586,16 @@ __global__ __launch_bounds__(256) void k_bp_depth(RecView r, const bk_cluster *_
   }
 }
 
+// bk_base_depth: the same count at n arbitrary positions, one wave each
+__global__ __launch_bounds__(256) void k_base_depth_at(RecView r, const int32_t *__restrict__ tid, const uint32_t *__restrict__ pos, uint32_t n, int maxspan,
+                                                       uint32_t *__restrict__ depth)
+{
+  const uint32_t j = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (j >= n) return;
+  const uint32_t d = base_depth_wave(r, tid[j], (unsigned long long) pos[j], maxspan);
+  if ((threadIdx.x & 63) == 0) depth[j] = d;
+}
+
 // test hook (bk_debug_region): find_sa_reads (BreakID.cc:868-1037) on one raw region with the product's own device code:
 // coverage (capped at 5), the region verdict, and the evidence tuples that survive it; out[0] = n, out[1] = cov, out[2] = depth
 __global__ __launch_bounds__(64) void k_debug_region(RecView r, const bk_split *__restrict__ sp, uint64_t nsp, int32_t tid, uint32_t start, uint32_t end, int maxspan,
@@ -807,6 +817,14 @@ uint32_t *bp_depth_partial(const RecView &r0, const bk_cluster *cl, uint64_t ncl
   uint32_t *depth = b.depth.as<uint32_t>(2 * ncl + 2);
   if (ncl) hipLaunchKernelGGL(k_bp_depth, dim3(cdiv(ncl, 4)), dim3(256), 0, st, r, cl, (uint32_t) ncl, maxspan, b.voted.get<uint32_t>(), depth);
   return depth;
+}
+
+void base_depth_at(const RecView &r0, const int32_t *tid, const uint32_t *pos, uint64_t n, int maxspan, DevBuf &samp, hipStream_t st, uint32_t *depth)
+{
+  if (n == 0) return;
+  if (n > 0x3FFFFFFFull) throw bk_error(BK_ERR_LIMIT, "too many positions");
+  const RecView r = rec_sampled(r0, samp, st);
+  hipLaunchKernelGGL(k_base_depth_at, dim3(cdiv(n, 4)), dim3(256), 0, st, r, tid, pos, (uint32_t) n, maxspan, depth);
 }
 
 void bp_finish(bk_cluster *cl, uint64_t ncl, const uint32_t *depth, BpBufs &b, hipStream_t st)

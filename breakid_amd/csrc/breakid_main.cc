@@ -39,6 +39,12 @@ extern "C" int bk_junction_sides(const struct bk_junction *j, uint8_t *right1, u
 extern "C" int bk_vcf_breakend_alt(char ref_base, int own_right, const char *mate_chr, uint32_t mate_pos, int mate_right, char *buf, size_t cap) __attribute__((weak));
 // -evidence: the same for the evidence rows (the CPU build refuses -evidence; bk_bam_extract is host code and always there)
 extern "C" int bk_evidence(bk_ctx *ctx, const struct bk_evidence **out, uint64_t *count, const uint64_t **call_off) __attribute__((weak));
+// -clip: the same for the soft-clip evidence, the depth at the rescued positions and the rescue rule (the CPU build refuses -clip)
+extern "C" int bk_clip_support(bk_ctx *calls, bk_ctx *records, int mapq_min, int min_clip, double w, const struct bk_clip_support **out, uint64_t *count)
+    __attribute__((weak));
+extern "C" int bk_base_depth(bk_ctx *records, const int32_t *tid, const uint32_t *pos, uint64_t n, const uint32_t **out) __attribute__((weak));
+extern "C" int bk_clip_rescue(const bk_cluster *c, const struct bk_junction *j, const struct bk_clip_support *s, uint32_t min_support, uint32_t *pos1, uint32_t *pos2,
+                              uint32_t *n1, uint32_t *n2) __attribute__((weak));
 // -x: the same for the exclude list (the CPU build refuses -x)
 extern "C" int bk_exclude_regions(bk_ctx *ctx, const bk_regions *r, uint64_t *n_removed) __attribute__((weak));
 extern "C" int bk_multi_run_ex(const bk_soa *host_table, const uint32_t *target_len, const char *const *target_name, int n_targets, const bk_regions *exclude, int n_gpus,
@@ -277,7 +283,10 @@ static const char *HELP =
      \t -genotype  \t count reference-allele evidence and genotype every call (twin files *_genotype.txt)  \n \
      \t -anchor    \t bases a reference read must cover on either side of a breakpoint (with -genotype)  [10]\n \
      \t -vcf       \t also write the calls as VCF breakends (*_fusion.vcf)  \n \
-     \t -evidence  \t also list the reads behind every call (*_evidence.txt) and write them as a BAM (*_evidence.bam)  \n ";
+     \t -evidence  \t also list the reads behind every call (*_evidence.txt) and write them as a BAM (*_evidence.bam)  \n \
+     \t -clip      \t count soft-clipped reads without an SA tag at every call (twin files *_clip.txt) and rescue clusters the vote left out (*_fusion_rescued.txt)  \n \
+     \t -minclip   \t shortest soft clip that counts (with -clip)  [10]\n \
+     \t -clipsupport \t clipped reads at one position that each side of a rescued cluster needs (with -clip)  [3]\n ";
 
 // ---- RefSeqTranscript.{h,cc} -------------------------------------------------------------------------------
 struct Txpt
@@ -516,8 +525,32 @@ static void write_genotype(std::ostream &o, const struct bk_ref_support &rs, uin
   o << "\t" << (gt == 0 ? "0/0" : gt == 1 ? "0/1" : gt == 2 ? "1/1" : "./.") << "\t" << (int) gq;
 }
 
+// -clip: the eight clip columns of one call (the directions d_s are those of its bk_junction row), and with -normal the two of the normal
+struct ClipCols
+{
+  uint32_t at[2], peak_pos[2], peak_n[2], events[2];
+  bool with_normal = false;
+  uint32_t normal_at[2] = {0, 0};
+};
+static ClipCols clip_cols(const struct bk_junction &j, const struct bk_clip_support &s, const struct bk_clip_support *normal)
+{
+  uint8_t d[2] = {0, 1}, source = 0;
+  bk_junction_sides(&j, &d[0], &d[1], &source);
+  ClipCols c;
+  for (int side = 0; side < 2; ++side)
+  {
+    c.at[side] = s.at[side][d[side]];
+    c.peak_pos[side] = s.peak_pos[side][d[side]];
+    c.peak_n[side] = s.peak_n[side][d[side]];
+    c.events[side] = s.events[side][d[side]];
+    if (normal) c.normal_at[side] = normal->at[side][d[side]];
+  }
+  c.with_normal = normal != nullptr;
+  return c;
+}
+
 static void write_row(std::ostream &o, const OutRow &r, const struct bk_normal_support *ns = nullptr, const struct bk_ref_support *gt = nullptr,
-                      const struct bk_ref_support *gt_normal = nullptr)
+                      const struct bk_ref_support *gt_normal = nullptr, const ClipCols *clip = nullptr)
 {
   o << fusion_type(r.c.type_mask) << "\t";
   o << r.p1_chr << ":" << r.c.p1_exact << "\t";
@@ -531,6 +564,12 @@ static void write_row(std::ostream &o, const OutRow &r, const struct bk_normal_s
   if (gt) write_genotype(o, *gt, r.c.n_drp, r.c.n_sr);
   if (ns) o << "\t" << ns->n_drp << "\t" << ns->n_sr << "\t" << ns->depth1 << "\t" << ns->depth2;
   if (ns && gt_normal) write_genotype(o, *gt_normal, ns->n_drp, ns->n_sr);
+  if (clip)
+  {
+    o << "\t" << clip->at[0] << "\t" << clip->at[1] << "\t" << clip->peak_pos[0] << "\t" << clip->peak_n[0] << "\t" << clip->peak_pos[1] << "\t" << clip->peak_n[1] << "\t"
+      << clip->events[0] << "\t" << clip->events[1];
+    if (clip->with_normal) o << "\t" << clip->normal_at[0] << "\t" << clip->normal_at[1];
+  }
   o << "\n";
 }
 
@@ -543,12 +582,18 @@ static const char *GENOTYPE_COLUMNS = "\tRef_Pairs1\tRef_Pairs2\tRef_Reads1\tRef
 static const char *GENOTYPE_COLUMNS_NORMAL =
     "\tNormal_Ref_Pairs1\tNormal_Ref_Pairs2\tNormal_Ref_Reads1\tNormal_Ref_Reads2\tNormal_VAF_Pairs\tNormal_VAF_Reads\tNormal_GT\tNormal_GQ";
 
+// -clip: the twin files' columns, and behind them those of the normal
+static const char *CLIP_COLUMNS = "\tClip1\tClip2\tClipPeak1\tClipPeakN1\tClipPeak2\tClipPeakN2\tClipBg1\tClipBg2";
+static const char *CLIP_COLUMNS_NORMAL = "\tNormal_Clip1\tNormal_Clip2";
+
 // Which rows the fusion files hold, and with them -vcf and -evidence: `all_ok` rows go to _fusion_all.txt (-all), those that also pass
 // the gene-pair and repeat filters to _fusion.txt.
 static bool call_all_ok(const OutRow &r) { return r.c.n_sr > 0 && r.c.p1_exact != 0xFFFFFFFFu && r.c.p2_exact != -1; }
 static bool call_no_gene_pair(const OutRow &r) { return (r.g1 == "intergenic" && r.g2 == "intergenic") || r.g1 == r.g2; }
 static bool call_filt_ok(const OutRow &r) { return call_all_ok(r) && !call_no_gene_pair(r) && !r.is_rpt; }
 static bool call_written(const OutRow &r, bool all) { return all ? call_all_ok(r) : call_filt_ok(r); }
+// a rescued cluster has no split read (N_SR is 0): the gene-pair and repeat filters apply to it as to a call, lifted by -all
+static bool rescued_written(const OutRow &r, bool all) { return all || (!call_no_gene_pair(r) && !r.is_rpt); }
 
 // ---- -vcf: the calls of the fusion files as VCF 4.2 breakends (section 5.4), two records per call ------------------------------
 struct VcfInput
@@ -808,10 +853,13 @@ int main(int argc, char *argv[])
   static struct option longopts[] = {{"help", 0, 0, 'h'}, {"i", 1, 0, 1}, {"o", 1, 0, 2}, {"q", 1, 0, 3}, {"n", 1, 0, 4},
                                      {"fast", 0, 0, 5},   {"t", 0, 0, 6}, {"all", 0, 0, 7}, {"gpu", 1, 0, 8}, {"gpus", 1, 0, 9},
                                      {"comm", 1, 0, 10},  {"normal", 1, 0, 11}, {"x", 1, 0, 12}, {"genotype", 0, 0, 13},
-                                     {"anchor", 1, 0, 14}, {"vcf", 0, 0, 15}, {"evidence", 0, 0, 16}, {0, 0, 0, 0}};
+                                     {"anchor", 1, 0, 14}, {"vcf", 0, 0, 15}, {"evidence", 0, 0, 16}, {"clip", 0, 0, 17},
+                                     {"minclip", 1, 0, 18}, {"clipsupport", 1, 0, 19}, {0, 0, 0, 0}};
   string inp_file, out_file, nib_dir, normal_file, exclude_file, build = "hg19";
   int qual = 20, device = 0, n_gpus = 0, transport = BK_TRANSPORT_AUTO;  // -gpus N: one sample over N GPUs (include/breakid_multi.h)
   bool fast = false, filter = true, genotype = false, anchor_given = false, vcf = false, evidence = false;
+  bool clip = false, minclip_given = false, clipsupport_given = false;
+  long min_clip = 10, clip_support = 3;  // -minclip: shortest clip that counts; -clipsupport: reads at one position a rescued side needs
   long anchor = 10;  // -anchor: bases a reference read must cover on either side of the breakpoint base
   int opt, li;
   optind = 0;
@@ -839,6 +887,15 @@ int main(int argc, char *argv[])
       break;
     case 15: vcf = true; break;
     case 16: evidence = true; break;
+    case 17: clip = true; break;
+    case 18:
+      min_clip = atol(optarg);
+      minclip_given = true;
+      break;
+    case 19:
+      clip_support = atol(optarg);
+      clipsupport_given = true;
+      break;
     default: std::cerr << "Error: cannot parse arguments.\n"; exit(1);
     }
   }
@@ -918,6 +975,29 @@ int main(int argc, char *argv[])
     if (!bk_evidence)
     {
       std::cerr << "Error: -evidence needs the GPU library" << std::endl;
+      exit(1);
+    }
+  }
+  if ((minclip_given || clipsupport_given) && !clip)
+  {
+    std::cerr << HELP << "Error: -minclip and -clipsupport need -clip.\n";
+    exit(1);
+  }
+  if (clip)
+  {
+    if (!bk_clip_support || !bk_base_depth || !bk_clip_rescue || !bk_junctions || !bk_junction_sides)
+    {
+      std::cerr << "Error: -clip needs the GPU library" << std::endl;
+      exit(1);
+    }
+    if (n_gpus >= 1)
+    {
+      std::cerr << HELP << "Error: -clip cannot be combined with -gpus.\n";
+      exit(1);
+    }
+    if (min_clip < 1 || min_clip > 0x7FFFFFFFl || clip_support < 1 || clip_support > 0x7FFFFFFFl)
+    {
+      std::cerr << HELP << "Error: -minclip and -clipsupport must be numbers from 1 to 2147483647.\n";
       exit(1);
     }
   }
@@ -1191,12 +1271,26 @@ int main(int argc, char *argv[])
   }
   // -vcf: the junction evidence of every call (member pairs by strands, split tuples by clip side)
   vector<struct bk_junction> jsup;
-  if (vcf)
+  if (vcf || clip)
   {
     const struct bk_junction *js = nullptr;
     uint64_t n_js = 0;
     if ((rc = bk_junctions(ctx, &js, &n_js)) != BK_OK) die(rc);
     jsup.assign(js, js + n_js);
+  }
+  // -clip: the clipped reads without an SA tag at every cluster, voted or not, on the sample's records and on the normal's
+  vector<struct bk_clip_support> csup, csup_normal;
+  if (clip)
+  {
+    const struct bk_clip_support *cs = nullptr;
+    uint64_t n_cs = 0;
+    if ((rc = bk_clip_support(ctx, ctx, qual, (int) min_clip, w, &cs, &n_cs)) != BK_OK) die(rc);
+    csup.assign(cs, cs + n_cs);
+    if (normal.ctx)
+    {
+      if ((rc = bk_clip_support(ctx, normal.ctx, qual, (int) min_clip, w, &cs, &n_cs)) != BK_OK) die(rc);
+      csup_normal.assign(cs, cs + n_cs);
+    }
   }
   const void *data = nullptr;
   uint64_t cnt = 0;
@@ -1256,13 +1350,68 @@ int main(int argc, char *argv[])
   }
   // write_enspan_out (BreakID.cc:1184-1263): std::sort with the reference's comparator
   std::sort(rows.begin(), rows.end(), cmp_cluster);
+  // -clip: the unvoted clusters whose clipped reads pile up on both sides (bk_clip_rescue), as rows of their own: the peaks are
+  // their breakpoints, N_SR is 0, the depth is counted at the peaks
+  vector<OutRow> rescued;
+  if (clip)
+  {
+    if (csup.size() != cnt || jsup.size() != cnt || (normal.ctx && csup_normal.size() != cnt))
+    {
+      std::cerr << "Error: the clip evidence does not cover every cluster" << std::endl;
+      exit(1);
+    }
+    vector<int32_t> q_tid;
+    vector<uint32_t> q_pos;
+    for (uint64_t i = 0; i < cnt; ++i)
+    {
+      uint32_t pos1 = 0, pos2 = 0, n1 = 0, n2 = 0;
+      rc = bk_clip_rescue(&cl[i], &jsup[i], &csup[i], (uint32_t) clip_support, &pos1, &pos2, &n1, &n2);
+      if (rc < 0)
+      {
+        std::cerr << "Error: bk_clip_rescue refused its arguments" << std::endl;
+        exit(1);
+      }
+      if (rc != 1) continue;
+      OutRow r;
+      r.c = cl[i];
+      r.idx = i;
+      r.c.p1_exact = pos1;
+      r.c.p2_exact = (int32_t) pos2;
+      r.c.n_sr = 0;
+      rescued.push_back(r);
+      q_tid.push_back(cl[i].p1_tid);
+      q_tid.push_back(cl[i].p2_tid);
+      q_pos.push_back(pos1);
+      q_pos.push_back(pos2);
+    }
+    const uint32_t *depth = nullptr;
+    if ((rc = bk_base_depth(ctx, q_tid.data(), q_pos.data(), q_tid.size(), &depth)) != BK_OK) die(rc);
+    for (size_t k = 0; k < rescued.size(); ++k)
+    {
+      OutRow &r = rescued[k];
+      r.c.depth1 = depth[2 * k];
+      r.c.depth2 = depth[2 * k + 1];
+      r.p1_chr = names[r.c.p1_tid];
+      r.p2_chr = names[r.c.p2_tid];
+      annotate_side(txpts, r.p1_chr, (long) r.c.p1_exact, r.g1, r.e1, r.s1);
+      annotate_side(txpts, r.p2_chr, (long) r.c.p2_exact, r.g2, r.e2, r.s2);
+      r.rpt1 = neighbour_seq(nib_dir, r.p1_chr, (int32_t) r.c.p1_exact);
+      r.rpt2 = neighbour_seq(nib_dir, r.p2_chr, r.c.p2_exact);
+      r.is_rpt = longest_run(r.rpt1) > 10 || longest_run(r.rpt2) > 10;
+      r.af1 = r.af2 = 0.0f;  // no split read: 0 of any depth, and 0 where the depth is 0
+    }
+    std::cout << "rescued cluster count: " << rescued.size() << std::endl;
+    std::sort(rescued.begin(), rescued.end(), cmp_cluster);
+  }
   std::ofstream out, outf, out_n, outf_n;  // (_n: the twins with the matched normal's four counts)
   std::ofstream out_g, outf_g;             // (_g: the twins with the genotype columns, -genotype)
+  std::ofstream out_c, outf_c, out_r;      // (_c: the twins with the clip columns, _r: the rescued clusters, -clip)
   const bool with_normal = !normal_file.empty();  // (a tumour without calls still gets header-only twins)
   const string header_n = string(HEADER, strlen(HEADER) - 1) + NORMAL_COLUMNS;
   string header_g = string(HEADER, strlen(HEADER) - 1) + GENOTYPE_COLUMNS;
   if (with_normal) header_g += string(NORMAL_COLUMNS, strlen(NORMAL_COLUMNS) - 1) + GENOTYPE_COLUMNS_NORMAL;
   header_g += "\n";
+  const string header_c = string(HEADER, strlen(HEADER) - 1) + CLIP_COLUMNS + (with_normal ? CLIP_COLUMNS_NORMAL : "") + "\n";
   if (!filter)
   {
     out.open((out_file + "_fusion_all.txt").c_str());
@@ -1277,6 +1426,11 @@ int main(int argc, char *argv[])
       out_g.open((out_file + "_fusion_all_genotype.txt").c_str());
       out_g << header_g;
     }
+    if (clip)
+    {
+      out_c.open((out_file + "_fusion_all_clip.txt").c_str());
+      out_c << header_c;
+    }
   }
   outf.open((out_file + "_fusion.txt").c_str());
   outf << HEADER;
@@ -1290,9 +1444,28 @@ int main(int argc, char *argv[])
     outf_g.open((out_file + "_fusion_genotype.txt").c_str());
     outf_g << header_g;
   }
+  if (clip)
+  {
+    outf_c.open((out_file + "_fusion_clip.txt").c_str());
+    outf_c << header_c;
+    out_r.open((out_file + "_fusion_rescued.txt").c_str());
+    out_r << header_c;
+    for (auto &r : rescued)
+    {
+      const ClipCols cc = clip_cols(jsup[r.idx], csup[r.idx], with_normal ? &csup_normal[r.idx] : nullptr);
+      if (rescued_written(r, !filter)) write_row(out_r, r, nullptr, nullptr, nullptr, &cc);
+    }
+    out_r.close();
+  }
   for (auto &r : rows)
   {
     const bool all_ok = call_all_ok(r), filt_ok = call_filt_ok(r);
+    if (clip)
+    {
+      const ClipCols cc = clip_cols(jsup[r.idx], csup[r.idx], with_normal ? &csup_normal[r.idx] : nullptr);
+      if (filt_ok) write_row(outf_c, r, nullptr, nullptr, nullptr, &cc);
+      if (!filter && all_ok) write_row(out_c, r, nullptr, nullptr, nullptr, &cc);
+    }
     if (filt_ok) write_row(outf, r);
     if (!filter && all_ok) write_row(out, r);
     if (with_normal && r.idx < n_nsup)
@@ -1319,6 +1492,11 @@ int main(int argc, char *argv[])
   {
     if (!filter) out_g.close();
     outf_g.close();
+  }
+  if (clip)
+  {
+    if (!filter) out_c.close();
+    outf_c.close();
   }
   if (vcf)
   {
@@ -1368,6 +1546,8 @@ int main(int argc, char *argv[])
     if (genotype) p << "genotype_anchor\t" << anchor << std::endl;
     if (vcf) p << "vcf\t1" << std::endl;
     if (evidence) p << "evidence\t1" << std::endl;
+    if (clip) p << "clip_min_length\t" << min_clip << std::endl;
+    if (clip) p << "clip_min_support\t" << clip_support << std::endl;
   }
   clock_t end = clock();
   std::cout << "the fusion process of file " << inp_file << "  costs time: " << (end - start) / double(CLOCKS_PER_SEC) << " seconds" << std::endl;

@@ -1,0 +1,215 @@
+// Soft-clip evidence of every cluster (bk_clip_support): on each side of a cluster, the soft-clipped reads without an
+// SA tag whose clip sits inside the cluster's window - how many, where they pile up, and how many sit at the voted breakpoint.  A
+// window search over the resident, coordinate-sorted record table - one wavefront (a workgroup of its own) per (call, side).
+#include "clip.h"
+
+namespace
+{
+constexpr int CLIP_STEPS = 4;
+constexpr uint16_t CLIP_FLAG_NEVER = 0x4 | 0x100 | 0x200 | 0x400 | 0x800;
+constexpr uint32_t CIGAR_S = 4, CIGAR_H = 5;
+
+__device__ __forceinline__ bool cigar_op_ref(uint32_t word) { return ((0x3C1A7u >> ((word & 15u) << 1)) & 2u) && (word >> 4); }
+
+// a pos column is int32: beyond its range a bound is where the next chromosome begins
+__device__ __forceinline__ uint64_t clip_lower(const RecView &r, int32_t T, long long P)
+{
+  return P <= 0x7FFFFFFFll ? rec_lower(r, T, P) : rec_lower(r, T + 1, -0x80000000ll);
+}
+
+// The clip events of record i, whose flag, mapq and aux columns have passed: `lead` (at pos + 1) and `trail` (at *pt = bam_endpos).
+// The first and the last CIGAR word decide (and the words behind hard clips); the whole CIGAR is walked only for a record with a
+// trailing clip that qualifies, or with a leading one that no aligned base follows at once (the reference length must be > 0).
+__device__ __forceinline__ void clip_events(const RecView &r, uint64_t i, int32_t pos, int min_clip, bool &lead, bool &trail, long long &pt, uint32_t &words)
+{
+  lead = trail = false;
+  pt = 0;
+  const uint32_t c0 = r.cigar_off[i], c1 = r.cigar_off[i + 1];
+  words += 2;
+  if (c1 <= c0) return;
+  const uint32_t *__restrict__ cg = r.cigar;
+  uint32_t a = c0, z = c1 - 1;
+  uint32_t wa = cg[a], wz = cg[z];
+  words += 2;
+  while ((wa & 15u) == CIGAR_H && a < z) wa = cg[++a], ++words;
+  while ((wz & 15u) == CIGAR_H && z > a) wz = cg[--z], ++words;
+  const bool l = (wa & 15u) == CIGAR_S && (long long) (wa >> 4) >= min_clip;
+  const bool t = (wz & 15u) == CIGAR_S && (long long) (wz >> 4) >= min_clip;
+  if (!l && !t) return;
+  if (!t && a + 1 < c1 && cigar_op_ref(cg[a + 1]))
+  {
+    ++words;
+    lead = true;
+    return;
+  }
+  const int32_t len = cigar_reflen_hts(cg + c0, c1 - c0);
+  words += c1 - c0;
+  if (len <= 0) return;
+  lead = l;
+  trail = t;
+  pt = (long long) pos + len;
+}
+
+// The window [lo, hi] is data (p_max - p_min) plus a parameter (W): it has no upper bound, so it is walked in tiles of CLIP_TILE
+// positions.  A tile [t0, t1) looks at the records with pos in [t0 - 1 - maxspan, t1 - 1] (a leading event lies at pos + 1, a trailing
+// one at most maxspan further right) and counts only the events that fall into it, each into the LDS counter of its position and
+// direction; a record that two neighbouring tiles see is so counted once.  After the tile every lane scans its share of the
+// counters, and the largest (the smallest position on a tie) is folded into the running best: tiles ascend, so a later tile wins
+// only with a larger count.  Tiles without records are skipped: the next record of the chromosome says where to go on.
+__global__ __launch_bounds__(64) void k_clip_support(RecView r, const bk_cluster *__restrict__ cl, uint32_t ncl, int mapq_min, int min_clip, int W, int maxspan,
+                                                     uint32_t *__restrict__ res, ClipStat *__restrict__ stat)
+{
+  __shared__ uint32_t hist[2][CLIP_TILE];
+  const uint32_t c = blockIdx.x >> 1, side = blockIdx.x & 1u;
+  const int lane = threadIdx.x;
+  if (c >= ncl) return;
+  const bk_cluster k = cl[c];
+  const int32_t T = side ? k.p2_tid : k.p1_tid;
+  const bool voted = (k.flags & 2u) != 0;
+  const long long e = side ? (long long) k.p2_exact : (long long) k.p1_exact;
+  const long long pmin = side ? k.p2_min : k.p1_min, pmax = side ? k.p2_max : k.p1_max;
+  const long long lo = pmin - W > 1 ? pmin - W : 1, hi = pmax + W;
+  uint32_t n_at[2] = {0, 0}, n_ev[2] = {0, 0};      // per lane
+  uint32_t best_n[2] = {0, 0}, best_p[2] = {0, 0};  // the same on every lane
+  uint32_t visited = 0, words = 0, tiles = 0;
+  if (T >= 0 && r.n)
+  {
+    long long t0 = lo;
+    while (t0 <= hi)
+    {
+      const long long t1 = hi - t0 >= CLIP_TILE ? t0 + CLIP_TILE : hi + 1;
+      const uint64_t rlo = clip_lower(r, T, t0 - 1 - maxspan), rhi = clip_lower(r, T, t1);
+      if (rlo >= rhi)
+      {
+        if (t1 > hi || rlo >= r.n || r.tid[rlo] != T) break;
+        t0 += ((long long) r.pos[rlo] + 1 - t0) / CLIP_TILE * CLIP_TILE;  // (that record starts at or behind t1: at least one tile on)
+        continue;
+      }
+      ++tiles;
+      visited += (uint32_t) (rhi - rlo);
+      for (int j = lane; j < 2 * CLIP_TILE; j += 64) (&hist[0][0])[j] = 0u;
+      __syncthreads();
+      for (uint64_t base = rlo; base < rhi; base += CLIP_STEPS * 64)
+      {
+        int32_t p[CLIP_STEPS];
+        uint32_t a0[CLIP_STEPS], a1[CLIP_STEPS];
+        uint16_t f[CLIP_STEPS];
+        uint8_t q[CLIP_STEPS];
+#pragma unroll
+        for (int s = 0; s < CLIP_STEPS; ++s)
+        {
+          const uint64_t i = base + (uint64_t) s * 64 + lane;
+          const bool in = i < rhi;
+          p[s] = in ? r.pos[i] : 0;
+          f[s] = in ? r.flag[i] : (uint16_t) 0x4;  // never eligible
+          q[s] = in ? r.mapq[i] : (uint8_t) 0;
+          a0[s] = in ? r.aux_off[i] : 0u;
+          a1[s] = in ? r.aux_off[i + 1] : 0u;
+        }
+#pragma unroll
+        for (int s = 0; s < CLIP_STEPS; ++s)
+        {
+          if ((f[s] & CLIP_FLAG_NEVER) || (int) q[s] < mapq_min || a1[s] != a0[s]) continue;
+          bool lead, trail;
+          long long pt;
+          clip_events(r, base + (uint64_t) s * 64 + lane, p[s], min_clip, lead, trail, pt, words);
+          const long long pl = (long long) p[s] + 1;
+          if (lead && pl >= t0 && pl < t1)
+          {
+            atomicAdd(&hist[1][pl - t0], 1u);
+            ++n_ev[1];
+            if (voted && pl >= e - 2 && pl <= e + 2) ++n_at[1];
+          }
+          if (trail && pt >= t0 && pt < t1)
+          {
+            atomicAdd(&hist[0][pt - t0], 1u);
+            ++n_ev[0];
+            if (voted && pt >= e - 2 && pt <= e + 2) ++n_at[0];
+          }
+        }
+      }
+      __syncthreads();
+#pragma unroll
+      for (int d = 0; d < 2; ++d)
+      {
+        uint32_t bn = 0, bp = 0;
+        for (int j = lane; j < CLIP_TILE; j += 64)
+        {
+          const uint32_t v = hist[d][j];
+          if (v > bn) bn = v, bp = (uint32_t) j;
+        }
+        for (int x = 32; x; x >>= 1)
+        {
+          const uint32_t on = (uint32_t) __shfl_xor((int) bn, x, 64), op = (uint32_t) __shfl_xor((int) bp, x, 64);
+          if (on > bn || (on == bn && op < bp)) bn = on, bp = op;
+        }
+        if (bn > best_n[d]) best_n[d] = bn, best_p[d] = (uint32_t) (t0 + bp);
+      }
+      __syncthreads();
+      t0 = t1;
+    }
+    // a voted breakpoint lies inside its window; where it does not (a table the caller changed), the +-2 bp around it that the
+    // window does not cover get a lookup of their own
+    if (voted && (e - 2 < lo || e + 2 > hi))
+    {
+      const uint64_t rlo = clip_lower(r, T, e - 3 - maxspan), rhi = clip_lower(r, T, e + 2);
+      visited += (uint32_t) (rhi > rlo ? rhi - rlo : 0);
+      for (uint64_t i = rlo + lane; i < rhi; i += 64)
+      {
+        if ((r.flag[i] & CLIP_FLAG_NEVER) || (int) r.mapq[i] < mapq_min || r.aux_off[i + 1] != r.aux_off[i]) continue;
+        bool lead, trail;
+        long long pt;
+        const int32_t pos = r.pos[i];
+        clip_events(r, i, pos, min_clip, lead, trail, pt, words);
+        const long long pl = (long long) pos + 1;
+        if (lead && pl >= e - 2 && pl <= e + 2 && !(pl >= lo && pl <= hi)) ++n_at[1];
+        if (trail && pt >= e - 2 && pt <= e + 2 && !(pt >= lo && pt <= hi)) ++n_at[0];
+      }
+    }
+  }
+#pragma unroll
+  for (int d = 0; d < 2; ++d)
+  {
+    n_at[d] = wave_sum_u32(n_at[d]);
+    n_ev[d] = wave_sum_u32(n_ev[d]);
+  }
+  if (stat) words = wave_sum_u32(words);
+  if (lane == 0)
+  {
+    // struct bk_clip_support { at, peak_pos, peak_n, events }, each [side][dir]: a wave stores the two directions of its side
+    uint32_t *o = res + 16 * (uint64_t) c + 2 * side;
+#pragma unroll
+    for (int d = 0; d < 2; ++d)
+    {
+      o[d] = n_at[d];
+      o[4 + d] = best_p[d];
+      o[8 + d] = best_n[d];
+      o[12 + d] = n_ev[d];
+    }
+    if (stat)
+    {
+      ClipStat s;
+      s.visited = visited;
+      s.words = words;
+      s.tiles = tiles;
+      s.pad = 0;
+      stat[blockIdx.x] = s;
+    }
+  }
+}
+}  // namespace
+
+void clip_support(const RecView &rec, int maxspan, const bk_cluster *cl, uint64_t ncl, int mapq_min, int min_clip, double w, ClipBufs &b, hipStream_t st,
+                  struct bk_clip_support **out, ClipStat **stat_out)
+{
+  static_assert(sizeof(struct bk_clip_support) == 64, "bk_clip_support must be 64 bytes");
+  struct bk_clip_support *res = b.res.as<struct bk_clip_support>(ncl + 1);
+  ClipStat *stat = stat_out ? b.stat.as<ClipStat>(2 * ncl + 2) : nullptr;
+  *out = res;
+  if (stat_out) *stat_out = stat;
+  if (ncl == 0) return;
+  if (ncl > 0x3FFFFFFFull) throw bk_error(BK_ERR_LIMIT, "too many clusters");
+  const int W = (int) w;  // the integer the breakpoint stage passes as wi (bp.hip: bp_vote)
+  const RecView r = rec_sampled(rec, b.samp, st);
+  hipLaunchKernelGGL(k_clip_support, dim3((unsigned) (2 * ncl)), dim3(64), 0, st, r, cl, (uint32_t) ncl, mapq_min, min_clip, W, maxspan, (uint32_t *) res, stat);
+}

@@ -288,6 +288,49 @@ int bk_junction_sides(const struct bk_junction *j, uint8_t *right1, uint8_t *rig
  * ]chr:pos]N, (right, right): [chr:pos[N.  BK_ERR_ARG for a null mate_chr or buf, or a buffer too small for the text and its NUL. */
 int bk_vcf_breakend_alt(char ref_base, int own_right, const char *mate_chr, uint32_t mate_pos, int mate_right, char *buf, size_t cap);
 
+/* ---- soft-clip evidence: clipped reads without an SA tag, at every cluster ----------------------------------------------------
+ * The vote (bk_split_breakpoints) sees only reads with an SA tag.  A read that is soft-clipped at the junction but carries none (a
+ * clip too short to place, an aligner that writes no SA, a second segment in a repeat) is counted here, for every row of
+ * BK_STAGE_CLUSTERS, voted or not, same order.  Parameters: mapq_min >= 0, min_clip >= 1, W = (int) w (the integer the breakpoint
+ * stage uses).  All comparisons in signed 64-bit.
+ * Clip events of a record i of the `records` context.  The record is eligible when tid[i] >= 0, flag has none of 0x4 0x100 0x200
+ * 0x400 0x800 (0x1 is not required), mapq[i] >= mapq_min, its aux blob is empty (aux_off[i+1] == aux_off[i]: a read with an SA tag
+ * is split-read evidence already, so clip evidence and N_SR stay disjoint) and its CIGAR has a reference length > 0 (M, D, N, =, X).
+ * It gives up to two events (tid, p, dir), p 1-based as p1_exact / prim_bp are, dir 0 = LEFT, 1 = RIGHT as right1 / right2 of
+ * bk_junction_sides:
+ *   leading   after skipping leading H ops the first op is S with length >= min_clip: (tid, pos + 1, RIGHT) - the alignment starts
+ *             at the breakpoint and extends right;
+ *   trailing  after skipping trailing H ops the last op is S with length >= min_clip: (tid, bam_endpos, LEFT), bam_endpos as in
+ *             bk_exclude_regions (the 1-based last aligned base equals the 0-based exclusive end).
+ * Per row and side s (0 = p1, 1 = p2): T = ps_tid, window [max(1, ps_min - W), ps_max + W] (the window of bk_normal_support.n_drp);
+ * T < 0 gives zeros.  For each dir:
+ *   events[s][dir]    events on T with p in the window
+ *   peak_n, peak_pos  the largest number of events of that direction that share one exact p in the window, and that p (the
+ *                     smallest p on a tie); both 0 without an event
+ *   at[s][dir]        voted rows only (flags bit 1; 0 otherwise): events on T with |p - ps_exact| <= 2, the +-2 bp of the tuple
+ *                     matching of bk_normal_support / bk_junctions (counted wherever ps_exact lies, inside the window or not)
+ * The struct has no typedef: the name belongs to the call below. */
+struct bk_clip_support { uint32_t at[2][2], peak_pos[2][2], peak_n[2][2], events[2][2]; }; /* [side][dir], 64 bytes */
+/* calls: after bk_split_breakpoints.  records: after bk_isize_stats (the stream pass gives the longest alignment); records == calls
+ * is the sample itself, another context on the same device with an identical reference list (names and lengths) is the matched
+ * normal.  Neither may be a shard (bk_shard_*).  *out: one row per BK_STAGE_CLUSTERS row, same order, library-owned until the next
+ * call or bk_free(calls).  BK_ERR_ARG (with the reason in bk_last_error) for wrong call order, min_clip < 1, mapq_min < 0, differing
+ * reference lists, shards, null outputs.  It changes nothing a later bk_fetch or stage returns, and works on every table form the
+ * context can hold (host upload, BK_MEM_DEVICE with and without `side`, the table bk_exclude_regions left behind, the context of
+ * bk_bam_decode_device_ctx while its bk_bam_dev lives).  A context without clusters is no error: *count = 0. */
+int bk_clip_support(bk_ctx *calls, bk_ctx *records, int mapq_min, int min_clip, double w, const struct bk_clip_support **out, uint64_t *count);
+/* cal_single_base_depth (the count behind depth1 / depth2) at n arbitrary 1-based positions; tid and pos are host arrays, tid < 0
+ * gives 0.  records: after bk_isize_stats, not a shard.  *out: n counts, library-owned until the next call or bk_free(records). */
+int bk_base_depth(bk_ctx *records, const int32_t *tid, const uint32_t *pos, uint64_t n, const uint32_t **out);
+/* The rescue rule, a pure host function (no context, no GPU), so that every caller shares it.  Returns 1 and fills the outputs when
+ * the row is unvoted (!(flags & 2)), both tids are >= 0, and with (d1, d2) the sides bk_junction_sides(j) gives (for an unvoted row
+ * they come from the strands of its pairs) peak_n[0][d1] >= min_support and peak_n[1][d2] >= min_support; then pos_s =
+ * peak_pos[s][d_s] and n_s = peak_n[s][d_s].  Returns 0 otherwise, BK_ERR_ARG for a null argument or min_support == 0.  The command
+ * line's min_support is 3: one more than the vote's own threshold of 2 (BreakID.cc:446), because no second alignment verifies a
+ * clip position - a constant of the model, not a measurement. */
+int bk_clip_rescue(const bk_cluster *c, const struct bk_junction *j, const struct bk_clip_support *s, uint32_t min_support, uint32_t *pos1, uint32_t *pos2, uint32_t *n1,
+                   uint32_t *n2);
+
 /* ---- evidence export: the reads behind every call -----------------------------------------------------------------------
  * bk_junctions counts a cluster's member pairs and, for a voted cluster, its matching tuples; bk_evidence lists the same rows, one
  * bk_evidence row each.  Membership is exactly that of bk_junctions (above): a BK_EV_PAIR row for every member pair of every
