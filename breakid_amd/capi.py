@@ -137,6 +137,61 @@ def lib():
     return _LIB
 
 
+MULTI_LIB_PATH = os.path.join(_HERE, "libbreakid_rccl.so")
+_MULTI = None
+TRANSPORT_AUTO, TRANSPORT_RCCL, TRANSPORT_LOCAL = 0, 1, 2
+
+
+def multi_lib():
+    """libbreakid_rccl.so (include/breakid_multi.h), loaded behind lib(): the process then has torch's HIP runtime and RCCL, and
+    the library's own references to them resolve to those copies."""
+    global _MULTI
+    if _MULTI is None:
+        lib()
+        if not os.path.exists(MULTI_LIB_PATH):
+            raise BreakIDError(abi.BK_ERR_NO_DEVICE, "libbreakid_rccl.so is not built (run __graft_entry__.build())")
+        M = C.CDLL(MULTI_LIB_PATH)
+        vp, dp = C.c_void_p, C.POINTER(C.c_double)
+        M.bk_multi_run.argtypes = [C.POINTER(abi.Soa), vp, C.POINTER(C.c_char_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, dp, C.POINTER(C.c_uint64), C.POINTER(vp),
+                                   C.c_char_p, C.c_size_t]
+        M.bk_multi_stats.argtypes = [vp, dp, dp, C.POINTER(vp), C.POINTER(C.c_uint32)]
+        M.bk_multi_free.argtypes = [vp]
+        M.bk_multi_free.restype = None
+        _MULTI = M
+    return _MULTI
+
+
+def multi_run(contigs, cols, n_gpus, transport=TRANSPORT_LOCAL, qual=20, fast=True):
+    """bk_multi_run on a host table (dict of numpy arrays as for Context.upload) -> dict with w, n_clustered, mean, sd (bk_multi_stats)
+    and the cluster table of rank 0's context; the context is released (bk_multi_free) before this returns."""
+    M = multi_lib()
+    qc = cols.get("qcheck")
+    cols = {k: np.ascontiguousarray(cols[k], dtype=dt) for k, dt in abi.SOA_COLS}
+    if qc is not None:
+        cols["qcheck"] = np.ascontiguousarray(qc, dtype=np.uint32)
+    for k in ("cigar", "aux"):
+        if cols[k].size == 0:
+            cols[k] = np.zeros(1, cols[k].dtype)
+    soa = abi.soa_from_numpy(cols)
+    lens = np.asarray([l for _, l in contigs], dtype=np.uint32)
+    names = (C.c_char_p * len(contigs))(*[n.encode() for n, _ in contigs])
+    w, ncl, h = C.c_double(), C.c_uint64(), C.c_void_p()
+    err = C.create_string_buffer(512)
+    rc = M.bk_multi_run(C.byref(soa), lens.ctypes.data, names, len(contigs), int(n_gpus), int(transport), int(qual), int(fast), C.byref(w), C.byref(ncl), C.byref(h), err, 512)
+    if rc != 0:
+        raise BreakIDError(rc, err.value.decode())
+    try:
+        mean, sd = C.c_double(), C.c_double()
+        rc = M.bk_multi_stats(h, C.byref(mean), C.byref(sd), None, None)
+        if rc != 0:
+            raise BreakIDError(rc, "bk_multi_stats")
+        L = lib()
+        clusters, _ = abi.fetch_array(L, h, lambda hh, st, d, c, g, ng: L.bk_fetch(hh, st, d, c, g, ng), abi.STAGE_CLUSTERS)
+        return {"w": w.value, "n_clustered": ncl.value, "mean": mean.value, "sd": sd.value, "clusters": clusters}
+    finally:
+        M.bk_multi_free(h)
+
+
 def w_from(mean, sd):
     times = 2
     return times * math.sqrt(times) * (mean + 3 * sd)  # BreakID.cc:103
@@ -278,6 +333,33 @@ class Context:
     def isize_stats(self):
         m, s = C.c_double(), C.c_double()
         self._check(self.L.bk_isize_stats(self.h, C.byref(m), C.byref(s)))
+        return m.value, s.value
+
+    # ---- one sample over several contexts: the statistics steps of the bk_shard_* sequence (sharded.py drives the whole of it) ----
+    def shard_begin(self, rec_base, qual=20):
+        """the stream pass of a context that holds records [rec_base, rec_base + n) of the sample"""
+        self._check(self.L.bk_shard_begin(self.h, int(rec_base), int(qual)))
+
+    def shard_get_stats(self):
+        st = abi.ShardStats()
+        self._check(self.L.bk_shard_get_stats(self.h, C.byref(st)))
+        return st
+
+    def shard_set_stats(self, st):
+        """st: abi.ShardStats with the sums (isize_sum, isize_n, sumsq) and maxima (vmax, max_span) over all shards"""
+        self._check(self.L.bk_shard_set_stats(self.h, C.byref(st)))
+
+    def shard_sd_local(self):
+        """(sum of floor(d) over this shard, device pointer of its exception list, its length); an exception is 16 bytes: l_before
+        (uint64, relative to this shard) and d (double)"""
+        lt, ex, nex = C.c_uint64(), C.c_void_p(), C.c_uint64()
+        self._check(self.L.bk_shard_sd_local(self.h, C.byref(lt), C.byref(ex), C.byref(nex)))
+        return lt.value, ex.value, nex.value
+
+    def shard_sd_finish(self, all_ex_ptr, n_all, l_grand):
+        """replays the exceptions of all shards (device memory, sample order, l_before made global) -> (mean, sd)"""
+        m, s = C.c_double(), C.c_double()
+        self._check(self.L.bk_shard_sd_finish(self.h, C.c_void_p(all_ex_ptr or 0), int(n_all), int(l_grand), C.byref(m), C.byref(s)))
         return m.value, s.value
 
     def discordant_pairs(self, qual, w):

@@ -1292,6 +1292,12 @@ static void sd_mean_thr(bk_ctx *ctx, double &m, double &thr)
 {
   const double n = (double) ctx->hc.isize_n;
   m = (double) (long long) ctx->hc.isize_sum / n;  // (double) long / (double) size_t, BreakID.cc:1941
+  if (ctx->hc.isize_n == 0)
+  {
+    // no eligible record in the whole sample: the mean is NaN (0 / 0), there is nothing to replay, and ilogb(NaN) is no exponent
+    thr = 0;
+    return;
+  }
   double sum_d = ctx->hsd.sumsq - 2.0 * m * (double) ctx->hc.isize_sum + n * m * m;
   if (!(sum_d > 0)) sum_d = 0;
   double da = (double) ctx->hsd.vmax - m, dmax = da * da + m * m;

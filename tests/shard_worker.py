@@ -1,6 +1,7 @@
 """Worker of the 2-rank sharded-sample test: run under torch.distributed.run (gloo), every rank on cuda:0.
 Rank 0 rebuilds the whole sample from the deterministic shard generator and checks the sharded result against
-the CPU oracle."""
+the CPU oracle.  SHARD_WORKER_ISIZE_SPIKES=count:value gives rank 0's first `count` eligible records the insert size `value`: the
+reference's sd accumulation then rounds up on both ranks, and rank 0 also checks (mean, sd) against the plain-Python definition."""
 import os
 import sys
 
@@ -29,6 +30,31 @@ def concat_shards(hosts):
     return full
 
 
+ELIGIBLE_NOT = 0x4 | 0x100 | 0x200 | 0x400
+
+
+def isize_spikes():
+    s = os.environ.get("SHARD_WORKER_ISIZE_SPIKES")
+    if not s:
+        return 0, 0
+    count, value = s.split(":")
+    return int(count), int(value)
+
+
+def spike_device(cols, count, value):
+    """isize of the first `count` eligible records of a device table := value"""
+    f = cols["flag"].to(torch.int32)
+    ok = ((f & 1) != 0) & ((f & 2) != 0) & ((f & ELIGIBLE_NOT) == 0)
+    cols["isize"][ok.nonzero().squeeze(1)[:count]] = value
+
+
+def spike_host(cols, count, value):
+    f = cols["flag"].astype(np.int64)
+    ok = ((f & 1) != 0) & ((f & 2) != 0) & ((f & ELIGIBLE_NOT) == 0)
+    cols["isize"] = cols["isize"].copy()
+    cols["isize"][np.nonzero(ok)[0][:count]] = value
+
+
 def main():
     n_per_rank, seed, mode = int(sys.argv[1]), int(sys.argv[2]), sys.argv[3]
     routed = (sys.argv[4] if len(sys.argv) > 4 else "routed") == "routed"
@@ -43,6 +69,9 @@ def main():
         dist.init_process_group("gloo")
     rank, world = dist.get_rank(), dist.get_world_size()
     contigs, cols = synth_gpu.make_wgs_shard(n_per_rank, seed, dev, rank, world)
+    n_spikes, spike = isize_spikes()
+    if n_spikes and rank == 0:
+        spike_device(cols, n_spikes, spike)
     comm = sharded.Comm(dev)
     counts = comm.all_gather_scalars([cols["n"]])[:, 0].tolist()
     rec_base = int(sum(counts[:rank]))
@@ -60,7 +89,10 @@ def main():
     if rank == 0:
         from oracle import pyoracle
         hosts = [synth_gpu.to_numpy_cols(synth_gpu.make_wgs_shard(n_per_rank, seed, dev, r, world)[1]) for r in range(world)]
-        o = pyoracle.Oracle(contigs, concat_shards(hosts))
+        if n_spikes:
+            spike_host(hosts[0], n_spikes, spike)
+        full = concat_shards(hosts)
+        o = pyoracle.Oracle(contigs, full)
         ow, rc = o.run(20, fast=(mode == "fast"))
         exp, _ = o.fetch(abi.STAGE_CLUSTERS)
         ok = rc == 0 and w == ow and np.array_equal(got, exp)
@@ -73,6 +105,13 @@ def main():
             back["rec"][far] -= gap
             ok = ok and len(gs) == len(es) and np.array_equal(back, es) and bool(far.any()) and int(gs["rec"].max()) >= (1 << 32)
             print("SHARD_REC64", "OK" if ok else "MISMATCH", "largest record index", int(gs["rec"].max()), flush=True)
+        if n_spikes:
+            from tests import isizecases
+            ref = isizecases.reference_sd(full["flag"], full["isize"])
+            n_diff, n_diff_rank1 = sum(ref.differs), sum(ref.differs[counts[0]:])
+            sd_ok = run.mean == ref.mean and run.sd == ref.sd and n_diff >= 100 and n_diff_rank1 >= 1
+            ok = ok and sd_ok
+            print("SHARD_SD_ROUNDUPS", n_diff, "OK" if sd_ok else "MISMATCH", "on rank 1:", n_diff_rank1, "mean", run.mean, ref.mean, "sd", run.sd, ref.sd, flush=True)
         print("SHARD_CHECK", "OK" if ok else "MISMATCH", "w", w, ow, "clusters", len(got), len(exp), "valid", int(((got["flags"] & 2) != 0).sum()), flush=True)
         if not ok and len(got) == len(exp):
             bad = [i for i in range(len(got)) if got[i] != exp[i]][:5]

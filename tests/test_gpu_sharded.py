@@ -12,6 +12,7 @@ from breakid_amd import abi, capi, sharded, synth_gpu
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SD_SEED = "91"  # (a seed of the shard generator on which 40 x 1 200 000 gives thousands of round-ups, half of them on rank 1: 77 gives none)
 
 
 def test_world1_sharded_equals_plain_run():
@@ -43,6 +44,19 @@ def test_two_rank_sharded_sample_matches_oracle(mode, exchange):
            "--master-port", env["MASTER_PORT"], os.path.join(ROOT, "tests", "shard_worker.py"), n, "77", mode, exchange]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0 and "SHARD_CHECK OK" in r.stdout and "SHARD_REPLICAS OK" in r.stdout, (r.stdout[-3000:], r.stderr[-3000:])
+
+
+def test_two_rank_sharded_sample_with_sd_roundups_on_both_ranks():
+    """40 insert sizes of 1 200 000 at the front of rank 0's records lift the reference's running total to where its `long += double`
+    rounds up on ordinary records of BOTH ranks: the exception list of rank 1 is replayed behind rank 0's floor total (the `offset`
+    sharded.py adds to l_before).  Rank 0 checks (mean, sd) against the plain-Python definition on the concatenated sample."""
+    import re
+    env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT="29615", SHARD_WORKER_ISIZE_SPIKES="40:1200000")
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
+           "--master-port", env["MASTER_PORT"], os.path.join(ROOT, "tests", "shard_worker.py"), "600000", SD_SEED, "fast", "routed"]
+    r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
+    assert (r.returncode == 0 and "SHARD_CHECK OK" in r.stdout and "SHARD_REPLICAS OK" in r.stdout
+            and re.search(r"^SHARD_SD_ROUNDUPS \d+ OK", r.stdout, re.M)), (r.stdout[-3000:], r.stderr[-3000:])
 
 
 @pytest.mark.parametrize("exchange", ["routed", "replicated"])
