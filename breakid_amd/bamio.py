@@ -92,11 +92,56 @@ class BgzfWriter:
         self.f.close()
 
 
+_AUX_SCALAR = {"c": "<b", "C": "<B", "s": "<h", "S": "<H", "i": "<i", "I": "<I", "f": "<f", "d": "<d"}
+AUX_ARRAY_SUBTYPES = "cCsSiIf"
+
+
+def _aux_bytes(v) -> bytes:
+    return v if isinstance(v, (bytes, bytearray)) else str(v).encode()
+
+
+def encode_aux_item(item) -> bytes:
+    """One aux field as BAM stores it.  item = (tag, text): a Z string; (tag, type, value) with type one of
+    A c C s S i I f d Z H B: A takes a character (or its code), Z and H take str or bytes (H the hex text itself), B takes
+    (sub-type, values) with a sub-type of AUX_ARRAY_SUBTYPES; raw bytes are written as they are (fields the types above
+    cannot spell, for tests of the decoders)."""
+    if isinstance(item, (bytes, bytearray)):
+        return bytes(item)
+    if len(item) == 2:
+        tag, typ, val = item[0], "Z", item[1]
+    else:
+        tag, typ, val = item
+    head = tag.encode() + typ.encode()
+    assert len(head) == 3, item
+    if typ == "A":
+        return head + (bytes([val]) if isinstance(val, int) else _aux_bytes(val)[:1])
+    if typ in _AUX_SCALAR:
+        return head + struct.pack(_AUX_SCALAR[typ], val)
+    if typ in "ZH":
+        body = _aux_bytes(val)
+        assert b"\0" not in body, item
+        return head + body + b"\0"
+    if typ == "B":
+        sub, vals = val
+        assert sub in AUX_ARRAY_SUBTYPES, item
+        fmt = _AUX_SCALAR[sub][1]
+        if isinstance(vals, (bytes, bytearray)) and sub == "C":
+            return head + b"C" + struct.pack("<I", len(vals)) + bytes(vals)
+        return head + sub.encode() + struct.pack("<I%d%s" % (len(vals), fmt), len(vals), *vals)
+    raise ValueError("aux type %r" % (typ,))
+
+
 def encode_record(qname: str, flag: int, tid: int, pos: int, mapq: int, cigar: Sequence[int],
-                  mtid: int, mpos: int, isize: int, aux: Sequence[Tuple[str, str]] = (),
-                  seq_len: int = 0) -> bytes:
-    """One BAM alignment record (pos/mpos 0-based).  aux = [(tag, string)] written as Z."""
+                  mtid: int, mpos: int, isize: int, aux: Sequence[tuple] = (),
+                  seq_len: int = 0, seq: Optional[bytes] = None, qual: Optional[bytes] = None) -> bytes:
+    """One BAM alignment record (pos/mpos 0-based).  aux = items of encode_aux_item(): (tag, string) written as Z, or
+    (tag, type, value).  seq / qual: the packed bases ((l_seq + 1) / 2 bytes) and the qualities (l_seq bytes) as they are
+    stored, l_seq = len(qual); without them seq_len placeholder bases are written."""
     name = qname.encode() + b"\0"
+    assert len(name) <= 255, "l_read_name is one byte"
+    if qual is not None:
+        seq_len = len(qual)
+        assert seq is not None and len(seq) == (seq_len + 1) // 2
     if flag & 4 or not cigar:
         end = pos + 1
     else:
@@ -105,10 +150,12 @@ def encode_record(qname: str, flag: int, tid: int, pos: int, mapq: int, cigar: S
     body = struct.pack("<iiBBHHHIiii", tid, pos, len(name), mapq, b, len(cigar), flag, seq_len, mtid, mpos, isize)
     body += name
     body += struct.pack("<%dI" % len(cigar), *cigar) if cigar else b""
-    if seq_len:
+    if qual is not None:
+        body += bytes(seq) + bytes(qual)
+    elif seq_len:
         body += b"\x11" * ((seq_len + 1) // 2) + b"\x1e" * seq_len
-    for tag, val in aux:
-        body += tag.encode() + b"Z" + val.encode() + b"\0"
+    for item in aux:
+        body += encode_aux_item(item)
     return struct.pack("<i", len(body)) + body
 
 
@@ -141,6 +188,34 @@ def write_bam(path: str, contigs: Sequence[Tuple[str, int]], records: Iterable[b
     if chunk:
         w.write(bytes(chunk))
     w.close()
+
+
+def inflate(path: str) -> bytes:
+    """the inflated stream of a BGZF file"""
+    raw = open(path, "rb").read()
+    data, off = bytearray(), 0
+    while off < len(raw):
+        bsize = struct.unpack_from("<H", raw, off + 16)[0] + 1
+        data += zlib.decompress(raw[off + 18:off + bsize - 8], -15)
+        off += bsize
+    return bytes(data)
+
+
+def read_records(path: str) -> Tuple[bytes, List[bytes]]:
+    """(the header bytes in front of the first record, [record bytes without the length word]) of a BAM file, in file order"""
+    data = inflate(path)
+    p = 8 + struct.unpack_from("<i", data, 4)[0]
+    n_ref = struct.unpack_from("<i", data, p)[0]
+    p += 4
+    for _ in range(n_ref):
+        p += 8 + struct.unpack_from("<i", data, p)[0]
+    head, recs = data[:p], []
+    while p < len(data):
+        bs = struct.unpack_from("<i", data, p)[0]
+        recs.append(data[p + 4:p + 4 + bs])
+        p += 4 + bs
+    assert p == len(data)
+    return head, recs
 
 
 def write_nib(path: str, seq: str) -> None:

@@ -33,7 +33,7 @@ def build(verbose=False):
         raise RuntimeError("building libbreakid_hip.so failed:\n" + (r.stdout or "")[-4000:] + (r.stderr or "")[-4000:])
 
 
-EXPORTS = ["bk_init", "bk_prepare_process", "bk_free", "bk_last_error", "bk_set_stream", "bk_sync", "bk_get_stream", "bk_upload_records", "bk_exclude_regions", "bk_isize_stats",
+EXPORTS = ["bk_init", "bk_prepare_process", "bk_free", "bk_last_error", "bk_set_stream", "bk_sync", "bk_get_stream", "bk_upload_records", "bk_records", "bk_exclude_regions", "bk_isize_stats",
            "bk_discordant_pairs", "bk_mask_and_cluster", "bk_split_evidence", "bk_cluster_summary",
            "bk_split_breakpoints", "bk_normal_support", "bk_ref_support", "bk_genotype_call", "bk_clip_support", "bk_base_depth", "bk_clip_rescue", "bk_junctions", "bk_junction_sides", "bk_vcf_breakend_alt", "bk_evidence", "bk_run", "bk_fetch", "bk_timing", "bk_timing_enable", "bk_timing_touched", "bk_group_stats", "bk_qname_hash", "bk_qname_check",
            "bk_bam_open", "bk_bam_header", "bk_bam_decode", "bk_bam_close", "bk_bam_extract", "bk_bam_names_free", "bk_bam_decode_device", "bk_bam_decode_device_part", "bk_bam_decode_device_ctx", "bk_bam_dev_free", "bk_feed_release_caches", "bk_debug_bgzf_inflate", "bk_debug_std_sort", "bk_sort_forms", "bk_debug_ahc", "bk_debug_points", "bk_debug_cigar", "bk_debug_vote", "bk_debug_region", "bk_shard_begin", "bk_shard_get_stats", "bk_shard_set_stats",
@@ -62,6 +62,7 @@ def lib():
         L.bk_set_stream.argtypes = [vp, vp]
         L.bk_sync.argtypes = [vp]
         L.bk_upload_records.argtypes = [vp, C.POINTER(abi.Soa), C.c_int]
+        L.bk_records.argtypes = [vp, C.POINTER(abi.Soa)]
         L.bk_exclude_regions.argtypes = [vp, C.POINTER(abi.Regions), u64p]
         L.bk_isize_stats.argtypes = [vp, dp, dp]
         L.bk_discordant_pairs.argtypes = [vp, C.c_int, C.c_double, u64p, C.POINTER(C.c_uint32)]
@@ -622,6 +623,9 @@ def decode_bam_device_ctx(path, qual=20, device=0):
     ctx.L, ctx.contigs, ctx.h = L, contigs, hc
     table = DeviceBamTable(L, hb, None, contigs)
     ctx._keep = table
+    s = abi.Soa()
+    ctx._check(L.bk_records(hc, C.byref(s)))  # the columns the table owns, as the context holds them
+    table.soa = s
     return ctx, table
 
 

@@ -500,6 +500,16 @@ int bk_sync(bk_ctx *ctx)
   return guarded(ctx, [&] { HIP_CHECK(hipStreamSynchronize(ctx->st)); });
 }
 
+int bk_records(bk_ctx *ctx, bk_soa *cols)
+{
+  return guarded(ctx, [&] {
+    if (!cols) throw bk_error(BK_ERR_ARG, "bk_records: null output");
+    if (!ctx->have_records) throw bk_error(BK_ERR_ARG, "bk_records: the context holds no record table");
+    HIP_CHECK(hipStreamSynchronize(ctx->st));
+    *cols = ctx->rec;
+  });
+}
+
 int bk_upload_records(bk_ctx *ctx, const bk_soa *s, int mem_space)
 {
   return guarded(ctx, [&] {

@@ -165,7 +165,12 @@ struct BlockCount
   uint32_t n_rec, n_cig, n_aux, bad;
 };
 
-// aux walk of one record (sam.c:1267-1279 semantics, as bam_reader.cc): first SA:Z and OC:Z
+// aux walk of one record, the same rule as the loop in bam_reader.cc (sam.c bam_aux_get / skip_aux, BamAlignment.cc saTag /
+// originCigar): the FIRST field named SA (OC) is the one that counts, whatever its type, and its text is the C string that
+// starts behind its type byte (cut at the end of the record); an empty one still hides every later field of that name.
+// Fields are skipped by type: A c C 1, s S 2, i I f 4, d 8 bytes, Z H up to and with the NUL, B 5 + count elements of
+// 1 (c C), 2 (s S), 4 (i I f) or 8 (d) bytes.  The walk ends at a type or element type outside these (htslib aborts or goes
+// astray).  Every offset it returns lies inside [q, bs].
 __device__ __forceinline__ void aux_scan(const uint8_t *r, uint32_t q, uint32_t bs, uint32_t &sa_at, uint32_t &sa_len, uint32_t &oc_at, uint32_t &oc_len)
 {
   sa_at = oc_at = 0;
@@ -175,6 +180,24 @@ __device__ __forceinline__ void aux_scan(const uint8_t *r, uint32_t q, uint32_t 
   {
     const uint8_t t0 = r[q], t1 = r[q + 1], type = r[q + 2];
     q += 3;
+    const bool is_sa = !has_sa && t0 == 'S' && t1 == 'A', is_oc = !has_oc && t0 == 'O' && t1 == 'C';
+    if (is_sa || is_oc)
+    {
+      uint32_t e = q;
+      while (e < bs && r[e]) ++e;
+      if (is_sa)
+      {
+        has_sa = true;
+        sa_at = q;
+        sa_len = e - q;
+      }
+      else
+      {
+        has_oc = true;
+        oc_at = q;
+        oc_len = e - q;
+      }
+    }
     uint32_t len;
     switch (type)
     {
@@ -186,21 +209,6 @@ __device__ __forceinline__ void aux_scan(const uint8_t *r, uint32_t q, uint32_t 
     {
       uint32_t e = q;
       while (e < bs && r[e]) ++e;
-      if (type == 'Z')
-      {
-        if (!has_sa && t0 == 'S' && t1 == 'A')
-        {
-          has_sa = true;
-          sa_at = q;
-          sa_len = e - q;
-        }
-        if (!has_oc && t0 == 'O' && t1 == 'C')
-        {
-          has_oc = true;
-          oc_at = q;
-          oc_len = e - q;
-        }
-      }
       len = e - q + 1;
       break;
     }
@@ -209,7 +217,15 @@ __device__ __forceinline__ void aux_scan(const uint8_t *r, uint32_t q, uint32_t 
       if (q + 5 > bs) return;
       const uint8_t sub = r[q];
       const uint32_t cnt = ld32(r + q + 1);
-      const uint32_t es = (sub == 'c' || sub == 'C') ? 1u : (sub == 's' || sub == 'S') ? 2u : 4u;
+      uint32_t es = 0;
+      switch (sub)
+      {
+      case 'c': case 'C': es = 1; break;
+      case 's': case 'S': es = 2; break;
+      case 'i': case 'I': case 'f': es = 4; break;
+      case 'd': es = 8; break;
+      }
+      if (!es) return;
       const unsigned long long l64 = 5ull + (unsigned long long) cnt * es;
       if (l64 > bs) return;
       len = (uint32_t) l64;

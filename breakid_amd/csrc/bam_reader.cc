@@ -372,7 +372,11 @@ void decode_chunk(const uint8_t *d, size_t dsize, size_t p, size_t r0, size_t r1
     c.cigar_off[i] = (uint32_t) o.cigar.size();
     for (uint16_t k = 0; k < n_cig; ++k) o.cigar.push_back(rd32(r + q + 4 * (size_t) k));
     q += (size_t) n_cig * 4 + ((size_t) l_seq + 1) / 2 + l_seq;
-    // aux walk: first SA:Z and OC:Z (bam_aux_get returns the first match)
+    // aux walk, the same rule as aux_scan in bam_gpu.hip (sam.c bam_aux_get / skip_aux, BamAlignment.cc saTag / originCigar):
+    // the FIRST field named SA (OC) is the one that counts, whatever its type, and its text is the C string that starts behind
+    // its type byte (cut at the end of the record); an empty one still hides every later field of that name.  Fields are
+    // skipped by type: A c C 1, s S 2, i I f 4, d 8 bytes, Z H up to and with the NUL, B 5 + count elements of 1 (c C),
+    // 2 (s S), 4 (i I f) or 8 (d) bytes.  The walk ends at a type or element type outside these (htslib aborts or goes astray).
     const uint8_t *sa = nullptr, *oc = nullptr;
     size_t sa_len = 0, oc_len = 0;
     while (q + 3 <= bs)
@@ -380,6 +384,14 @@ void decode_chunk(const uint8_t *d, size_t dsize, size_t p, size_t r0, size_t r1
       const uint8_t *tag = r + q;
       uint8_t type = r[q + 2];
       q += 3;
+      const bool is_sa = !sa && tag[0] == 'S' && tag[1] == 'A', is_oc = !oc && tag[0] == 'O' && tag[1] == 'C';
+      if (is_sa || is_oc)
+      {
+        size_t e = q;
+        while (e < bs && r[e]) ++e;
+        if (is_sa) { sa = r + q; sa_len = e - q; }
+        else { oc = r + q; oc_len = e - q; }
+      }
       size_t len = 0;
       switch (type)
       {
@@ -391,11 +403,6 @@ void decode_chunk(const uint8_t *d, size_t dsize, size_t p, size_t r0, size_t r1
       {
         size_t e = q;
         while (e < bs && r[e]) ++e;
-        if (type == 'Z')
-        {
-          if (!sa && tag[0] == 'S' && tag[1] == 'A') { sa = r + q; sa_len = e - q; }
-          if (!oc && tag[0] == 'O' && tag[1] == 'C') { oc = r + q; oc_len = e - q; }
-        }
         len = e - q + 1;
         break;
       }
@@ -404,7 +411,15 @@ void decode_chunk(const uint8_t *d, size_t dsize, size_t p, size_t r0, size_t r1
         if (q + 5 > bs) { q = bs; continue; }
         uint8_t sub = r[q];
         uint32_t cnt = rd32(r + q + 1);
-        size_t es = (sub == 'c' || sub == 'C') ? 1 : (sub == 's' || sub == 'S') ? 2 : 4;
+        size_t es = 0;
+        switch (sub)
+        {
+        case 'c': case 'C': es = 1; break;
+        case 's': case 'S': es = 2; break;
+        case 'i': case 'I': case 'f': es = 4; break;
+        case 'd': es = 8; break;
+        }
+        if (!es) { q = bs; continue; }
         len = 5 + (size_t) cnt * es;
         break;
       }

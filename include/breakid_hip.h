@@ -531,6 +531,11 @@ void bk_feed_release_caches(void);
  * the columns and must outlive the context.  Same file support and errors as bk_bam_decode_device. */
 int bk_bam_decode_device_ctx(const char *path, int device, int mapq_min, bk_bam_dev **bam_out, bk_ctx **ctx_out, int *n_targets, const char *const **names,
                              const uint32_t **lens, char *err, size_t errlen);
+/* The record table a context holds, as device pointers (cols->n, n_cigar_words, n_aux_bytes say how much lies behind them): the
+ * table of bk_bam_decode_device_ctx, which hands out no bk_soa of its own, a BK_MEM_DEVICE table as it was attached, or the device
+ * copy of a BK_MEM_HOST upload.  The context's stream is synchronised first.  The columns belong to whoever owned them before
+ * (the bk_bam_dev, the caller, the context).  BK_ERR_ARG when the context holds no table. */
+int bk_records(bk_ctx *ctx, bk_soa *cols);
 /* test / measurement hook: inflates a whole BGZF file image on the GPU, bytes back to the host */
 int bk_debug_bgzf_inflate(const void *file, uint64_t n, void *out, uint64_t out_cap, uint64_t *out_len, float *kernel_ms, char *err, size_t errlen);
 

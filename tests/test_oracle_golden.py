@@ -10,7 +10,7 @@ from breakid_amd import abi
 from oracle import pyoracle
 from tests import refdump
 
-DATASETS = ["g1", "g2", "small", "ties", "edge"]
+DATASETS = ["g1", "g2", "small", "ties", "edge", "edge_dressed", "g1_dressed"]
 
 
 @pytest.mark.parametrize("name", DATASETS)

@@ -1,11 +1,12 @@
 """Randomised check of the GPU feed (GPU box): BAMs with random record shapes, block layouts and deflate settings through
 bk_bam_decode_device against the generator's own table and the host decoder.  usage: gpu_feedfuzz.py [cases] [seed]"""
-import os, struct, sys, tempfile, zlib
+import os, random, struct, sys, tempfile, zlib
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import torch
 from breakid_amd import abi, bamio, capi, synth
 from breakid_amd.sharded import tensor_from_ptr
+from breakid_amd import dress
 
 
 def device_cols(table):
@@ -77,9 +78,11 @@ def one(case, seed):
     seq_mode = int(rng.integers(0, 3))
     max_block = int(rng.choice([0xFF00, 0xFF00, 4096, 20000, 65280]))
 
+    aux_rng = random.Random(seed)
+
     def gen():
         for i, r in enumerate(ds.recs):
-            aux = ([("SA", r.sa)] if r.sa else []) + ([("OC", r.oc)] if r.oc else [])
+            aux = dress.dress_aux(aux_rng, r.sa, r.oc)   # typed fields around SA / OC, as an aligner leaves them
             if long_every and i % long_every == 5:
                 sl = int(rng.integers(30_000, 250_000))
             else:
@@ -87,7 +90,7 @@ def one(case, seed):
             rec = bamio.encode_record(r.qname, r.flag, r.tid, r.pos, r.mapq, bamio.parse_cigar(r.cigar), r.mtid, r.mpos, r.isize, aux, seq_len=sl)
             if sl and rng.random() < 0.5:   # random bases / qualities instead of the writer's constant fill
                 body = bytearray(rec)
-                at = len(rec) - sum(3 + len(v) + 1 for _, v in aux) - ((sl + 1) // 2 + sl)
+                at = len(rec) - sum(len(bamio.encode_aux_item(a)) for a in aux) - ((sl + 1) // 2 + sl)
                 body[at:at + (sl + 1) // 2 + sl] = rng.integers(0, 64, (sl + 1) // 2 + sl, dtype=np.uint8).tobytes()
                 rec = bytes(body)
             yield rec

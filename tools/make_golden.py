@@ -53,10 +53,22 @@ SMALL_REFGENE = [
 ]
 
 
-def make_dataset_golden(name, ds, refgene):
+def dressed_datasets():
+    """make_edge() (+ the hand-written aux layouts) and make_g1() written through the dresser of breakid_amd/dress.py: records
+    with bases, qualities and typed aux fields around SA / OC, as an aligner leaves them"""
+    from breakid_amd import dress
+    yield "edge_dressed", dress.with_layouts(synth.make_edge()), EDGE_REFGENE, [dress.LAYOUT_REGION]
+    yield "g1_dressed", synth.make_g1(), synth.G1_REFGENE, []
+
+
+def make_dataset_golden(name, ds, refgene, dressed=False, first_queries=()):
     with tempfile.TemporaryDirectory() as tmp:
         bam = os.path.join(tmp, name + ".bam")
-        ds.write_bam(bam)
+        if dressed:
+            from breakid_amd import dress
+            dress.write_dressed(ds, bam)
+        else:
+            ds.write_bam(bam)
         side = synth.write_side_files(ds, tmp, refgene_lines=refgene)
         run([os.path.join(REF, "ref_index"), bam])
         env = dict(os.environ, BREAKID_REF_INSTALLDIR=side["install"])
@@ -80,7 +92,7 @@ def make_dataset_golden(name, ds, refgene):
                 lines = f.read().split("\n")
                 g.write(lines[0] + "\n" + "\t".join(lines[1].split("\t")[:5]) + "\n")
         # a few raw region / depth queries (find_sa_reads / cal_single_base_depth) incl. edge regions
-        queries = []
+        queries = list(first_queries)
         rng = np.random.default_rng(5)
         for k in range(12):
             t = int(rng.integers(0, len(ds.contigs)))
@@ -241,6 +253,9 @@ def main():
     make_poison_golden()
     for name, ds, refgene in datasets():
         make_dataset_golden(name, ds, refgene)
+        print("golden:", name, len(ds.recs), "records")
+    for name, ds, refgene, first in dressed_datasets():
+        make_dataset_golden(name, ds, refgene, dressed=True, first_queries=first)
         print("golden:", name, len(ds.recs), "records")
 
 
