@@ -28,6 +28,10 @@ assert JUNCTION.itemsize == 48
 CLIP_LEFT, CLIP_RIGHT = 0, 1
 CLIP_SUPPORT = np.dtype([("at", "<u4", (2, 2)), ("peak_pos", "<u4", (2, 2)), ("peak_n", "<u4", (2, 2)), ("events", "<u4", (2, 2))])  # struct bk_clip_support, [side][dir]
 assert CLIP_SUPPORT.itemsize == 64
+CLIP_SITE = np.dtype([("tid", "<i4"), ("pos", "<u4"), ("tol", "<u4"), ("dir", "<u4")])  # struct bk_clip_site; pos 1-based, dir CLIP_LEFT / CLIP_RIGHT
+CLIP_READ = np.dtype([("rec", "<u8"), ("qhash", "<u8"), ("qcheck", "<u4"), ("site", "<u4"), ("tid", "<i4"), ("p", "<u4"), ("clip_len", "<u4"), ("flag", "<u2"),
+                      ("mapq", "u1"), ("dir", "u1")])  # struct bk_clip_read
+assert CLIP_SITE.itemsize == 16 and CLIP_READ.itemsize == 40
 EV_PAIR, EV_SPLIT = 1, 2
 EVIDENCE = np.dtype([("rec", "<u8"), ("qhash", "<u8"), ("qcheck", "<u4"), ("call", "<u4"), ("tid1", "<i4"), ("pos1", "<u4"), ("tid2", "<i4"),
                      ("pos2", "<u4"), ("flag1", "<u2"), ("flag2", "<u2"), ("mapq1", "u1"), ("mapq2", "u1"), ("kind", "u1"), ("sides", "u1")])  # struct bk_evidence

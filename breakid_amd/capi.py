@@ -35,7 +35,7 @@ def build(verbose=False):
 
 EXPORTS = ["bk_init", "bk_prepare_process", "bk_free", "bk_last_error", "bk_set_stream", "bk_sync", "bk_get_stream", "bk_upload_records", "bk_records", "bk_exclude_regions", "bk_isize_stats",
            "bk_discordant_pairs", "bk_mask_and_cluster", "bk_split_evidence", "bk_cluster_summary",
-           "bk_split_breakpoints", "bk_normal_support", "bk_ref_support", "bk_genotype_call", "bk_clip_support", "bk_base_depth", "bk_clip_rescue", "bk_junctions", "bk_junction_sides", "bk_vcf_breakend_alt", "bk_evidence", "bk_run", "bk_fetch", "bk_timing", "bk_timing_enable", "bk_timing_touched", "bk_group_stats", "bk_qname_hash", "bk_qname_check",
+           "bk_split_breakpoints", "bk_normal_support", "bk_ref_support", "bk_genotype_call", "bk_clip_support", "bk_clip_reads", "bk_base_depth", "bk_clip_rescue", "bk_junctions", "bk_junction_sides", "bk_vcf_breakend_alt", "bk_evidence", "bk_run", "bk_fetch", "bk_timing", "bk_timing_enable", "bk_timing_touched", "bk_group_stats", "bk_qname_hash", "bk_qname_check",
            "bk_bam_open", "bk_bam_header", "bk_bam_decode", "bk_bam_close", "bk_bam_extract", "bk_bam_names_free", "bk_bam_decode_device", "bk_bam_decode_device_part", "bk_bam_decode_device_ctx", "bk_bam_dev_free", "bk_feed_release_caches", "bk_debug_bgzf_inflate", "bk_debug_std_sort", "bk_sort_forms", "bk_debug_ahc", "bk_debug_points", "bk_debug_cigar", "bk_debug_vote", "bk_debug_region", "bk_shard_begin", "bk_shard_get_stats", "bk_shard_set_stats",
            "bk_shard_sd_local", "bk_shard_sd_finish", "bk_shard_buffer", "bk_shard_set_buffer", "bk_shard_group_sizes",
            "bk_shard_own_groups", "bk_shard_route_candidates", "bk_shard_group_keys", "bk_shard_route_pairs", "bk_shard_group_pairs", "bk_shard_bp_cov", "bk_shard_bp_vote", "bk_shard_bp_vote_slice", "bk_shard_bp_set_voted", "bk_shard_bp_depth", "bk_shard_bp_finish"]
@@ -75,6 +75,7 @@ def lib():
         L.bk_ref_support.argtypes = [vp, vp, C.c_int, C.c_int, C.c_double, C.POINTER(vp), u64p]
         L.bk_genotype_call.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), C.POINTER(C.c_float)]
         L.bk_clip_support.argtypes = [vp, vp, C.c_int, C.c_int, C.c_double, C.POINTER(vp), u64p]
+        L.bk_clip_reads.argtypes = [vp, vp, C.c_uint64, C.c_int, C.c_int, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
         L.bk_base_depth.argtypes = [vp, vp, vp, C.c_uint64, C.POINTER(vp)]
         L.bk_clip_rescue.argtypes = [vp, vp, vp, C.c_uint32] + [C.POINTER(C.c_uint32)] * 4
         L.bk_junctions.argtypes = [vp, C.POINTER(vp), u64p]
@@ -442,6 +443,27 @@ class Context:
             return np.zeros(0, abi.CLIP_SUPPORT)
         buf = (C.c_char * (n.value * abi.CLIP_SUPPORT.itemsize)).from_address(data.value)
         return np.frombuffer(buf, dtype=abi.CLIP_SUPPORT, count=n.value).copy()
+
+    def clip_reads(self, sites, mapq_min, min_clip, listing=True):
+        """The clip events of this context's records at `sites` (bk_clip_reads; abi.CLIP_SITE rows, or anything np.asarray turns into
+        them): (counts, rows, site_off) with one uint32 per site, one abi.CLIP_READ row per event ordered by site and record, and
+        site_off[k] .. site_off[k + 1] the rows of site k; with listing=False the counts alone (no listing is made).  After
+        isize_stats."""
+        sites = np.ascontiguousarray(sites, abi.CLIP_SITE)
+        assert sites.ndim == 1
+        n = len(sites)
+        counts, rows, off = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        self._check(self.L.bk_clip_reads(self.h, sites.ctypes.data if n else None, n, int(mapq_min), int(min_clip), C.byref(counts),
+                                         C.byref(rows) if listing else None, C.byref(off) if listing else None))
+        cnt = np.ctypeslib.as_array(C.cast(counts, C.POINTER(C.c_uint32)), shape=(n,)).copy() if n else np.zeros(0, np.uint32)
+        if not listing:
+            return cnt
+        site_off = np.ctypeslib.as_array(C.cast(off, C.POINTER(C.c_uint64)), shape=(n + 1,)).copy()
+        out = np.zeros(0, abi.CLIP_READ)
+        if site_off[-1]:
+            buf = (C.c_char * (int(site_off[-1]) * abi.CLIP_READ.itemsize)).from_address(rows.value)
+            out = np.frombuffer(buf, dtype=abi.CLIP_READ, count=int(site_off[-1])).copy()
+        return cnt, out, site_off
 
     def base_depth(self, tid, pos):
         """cal_single_base_depth on this context's records at arbitrary 1-based positions (bk_base_depth): one uint32 per entry."""

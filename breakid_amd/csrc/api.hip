@@ -126,6 +126,11 @@ struct bk_ctx
   std::vector<struct bk_clip_support> f_clip;
   DevBuf d_bd_tid, d_bd_pos, d_bd_out, d_bd_samp;
   std::vector<uint32_t> f_base_depth;
+  // the clipped reads at given sites (bk_clip_reads: this context holds the records)
+  ClipReadBufs crb;
+  std::vector<uint32_t> f_cr_counts;
+  std::vector<struct bk_clip_read> f_cr_rows;
+  std::vector<uint64_t> f_cr_off;
   // junction evidence (bk_junctions); summary_map: bb still holds the slot -> cluster-row map of the last bk_cluster_summary
   JunctionBufs jnb;
   std::vector<struct bk_junction> f_junction;
@@ -955,6 +960,63 @@ int bk_clip_support(bk_ctx *calls, bk_ctx *records, int mapq_min, int min_clip, 
     }
     *out = calls->f_clip.data();
     *count = ncl;
+  });
+}
+
+int bk_clip_reads(bk_ctx *records, const struct bk_clip_site *sites, uint64_t n_sites, int mapq_min, int min_clip, const uint32_t **counts,
+                  const struct bk_clip_read **rows, const uint64_t **site_off)
+{
+  return guarded(records, [&] {
+    if (!counts) throw bk_error(BK_ERR_ARG, "bk_clip_reads: null counts");
+    if ((rows == nullptr) != (site_off == nullptr)) throw bk_error(BK_ERR_ARG, "bk_clip_reads: rows and site_off go together (both, or neither for the counts only)");
+    if (n_sites && !sites) throw bk_error(BK_ERR_ARG, "bk_clip_reads: null sites");
+    if (records->shard) throw bk_error(BK_ERR_ARG, "bk_clip_reads: sharded contexts (bk_shard_*) are not supported");
+    if (!records->have_records || !records->stats_done) throw bk_error(BK_ERR_ARG, "bk_clip_reads: call bk_isize_stats first");
+    if (min_clip < 1) throw bk_error(BK_ERR_ARG, "bk_clip_reads: min_clip must be at least 1");
+    if (mapq_min < 0) throw bk_error(BK_ERR_ARG, "bk_clip_reads: mapq_min must not be negative");
+    if (n_sites > 0x40000000ull) throw bk_error(BK_ERR_LIMIT, "bk_clip_reads: more than 2^30 sites");
+    for (uint64_t k = 0; k < n_sites; ++k)
+      if (sites[k].dir > 1u) throw bk_error(BK_ERR_ARG, "bk_clip_reads: site " + std::to_string(k) + " has a dir above 1 (0 = LEFT, 1 = RIGHT)");
+    const bool listing = rows != nullptr;
+    const bk_soa &t = records->rec;
+    if (t.n && (!t.tid || !t.pos || !t.flag || !t.mapq || !t.cigar_off || !t.aux_off)) throw bk_error(BK_ERR_ARG, "bk_clip_reads: the record table lacks a column");
+    if (listing && t.n && !t.side && !t.qhash) throw bk_error(BK_ERR_ARG, "bk_clip_reads: a listing needs the read-name hashes: the record table has neither qhash nor side");
+    const ClipNames nm{listing ? t.side : nullptr, listing ? t.qhash : nullptr, listing ? t.qcheck : nullptr};
+    ClipReadsOut o{};
+    {
+      Scope s(records, "clip_reads");
+      clip_reads(rec_view(records), nm, (int) records->hc.max_span, sites, n_sites, mapq_min, min_clip, listing, records->timing, records->crb, records->st, o);
+    }
+    if (o.bad) throw bk_error(BK_ERR_HIP, "bk_clip_reads: the listing and the counts disagree (internal error)");
+    std::vector<ClipStat> stat(o.stat ? n_sites : 0);
+    if (!stat.empty()) HIP_CHECK(hipMemcpyAsync(stat.data(), o.stat, n_sites * sizeof(ClipStat), hipMemcpyDeviceToHost, records->st));
+    records->f_cr_off.assign(listing ? n_sites + 1 : 0, 0);
+    if (listing) HIP_CHECK(hipMemcpyAsync(records->f_cr_off.data(), o.site_off, (n_sites + 1) * 8, hipMemcpyDeviceToHost, records->st));
+    records->f_cr_rows.resize(o.n_rows);
+    if (o.n_rows) HIP_CHECK(hipMemcpyAsync(records->f_cr_rows.data(), o.rows, o.n_rows * sizeof(struct bk_clip_read), hipMemcpyDeviceToHost, records->st));
+    rows_to_host(records, o.counts, n_sites, records->f_cr_counts);
+    if (records->timing && !records->timers.empty())
+    {
+      // bytes: pos, flag, mapq and two aux_off words of every record a site looks at (15 B each, as clip_support models it), per pass.
+      // touched: those, the CIGAR offsets and words read, per site its 16 bytes read and its count (4 + 8 B) written; a listing
+      // walks the records a second time, reads the offsets (16 B per site), gathers a 32-byte sector of hashes per row and writes the row.
+      uint64_t visited = 0, words = 0;
+      for (const ClipStat &x : stat)
+      {
+        visited += x.visited;
+        words += x.words;
+      }
+      const uint64_t passes = listing && o.n_rows ? 2 : 1;
+      records->timers.back().bytes = passes * 15ull * visited;
+      records->timers.back().touched = passes * (15ull * visited + 4ull * words + n_sites * sizeof(struct bk_clip_site)) + n_sites * 12ull +
+                                       (listing ? n_sites * 16ull + o.n_rows * (32ull + sizeof(struct bk_clip_read)) : 0ull);
+    }
+    *counts = records->f_cr_counts.data();
+    if (listing)
+    {
+      *rows = records->f_cr_rows.data();
+      *site_off = records->f_cr_off.data();
+    }
   });
 }
 

@@ -42,6 +42,8 @@ extern "C" int bk_evidence(bk_ctx *ctx, const struct bk_evidence **out, uint64_t
 // -clip: the same for the soft-clip evidence, the depth at the rescued positions and the rescue rule (the CPU build refuses -clip)
 extern "C" int bk_clip_support(bk_ctx *calls, bk_ctx *records, int mapq_min, int min_clip, double w, const struct bk_clip_support **out, uint64_t *count)
     __attribute__((weak));
+extern "C" int bk_clip_reads(bk_ctx *records, const struct bk_clip_site *sites, uint64_t n_sites, int mapq_min, int min_clip, const uint32_t **counts,
+                             const struct bk_clip_read **rows, const uint64_t **site_off) __attribute__((weak));
 extern "C" int bk_base_depth(bk_ctx *records, const int32_t *tid, const uint32_t *pos, uint64_t n, const uint32_t **out) __attribute__((weak));
 extern "C" int bk_clip_rescue(const bk_cluster *c, const struct bk_junction *j, const struct bk_clip_support *s, uint32_t min_support, uint32_t *pos1, uint32_t *pos2,
                               uint32_t *n1, uint32_t *n2) __attribute__((weak));
@@ -550,7 +552,7 @@ static ClipCols clip_cols(const struct bk_junction &j, const struct bk_clip_supp
 }
 
 static void write_row(std::ostream &o, const OutRow &r, const struct bk_normal_support *ns = nullptr, const struct bk_ref_support *gt = nullptr,
-                      const struct bk_ref_support *gt_normal = nullptr, const ClipCols *clip = nullptr)
+                      const struct bk_ref_support *gt_normal = nullptr, const ClipCols *clip = nullptr, const string *tail = nullptr)
 {
   o << fusion_type(r.c.type_mask) << "\t";
   o << r.p1_chr << ":" << r.c.p1_exact << "\t";
@@ -570,6 +572,7 @@ static void write_row(std::ostream &o, const OutRow &r, const struct bk_normal_s
       << clip->events[0] << "\t" << clip->events[1];
     if (clip->with_normal) o << "\t" << clip->normal_at[0] << "\t" << clip->normal_at[1];
   }
+  if (tail) o << *tail;
   o << "\n";
 }
 
@@ -585,6 +588,17 @@ static const char *GENOTYPE_COLUMNS_NORMAL =
 // -clip: the twin files' columns, and behind them those of the normal
 static const char *CLIP_COLUMNS = "\tClip1\tClip2\tClipPeak1\tClipPeakN1\tClipPeak2\tClipPeakN2\tClipBg1\tClipBg2";
 static const char *CLIP_COLUMNS_NORMAL = "\tNormal_Clip1\tNormal_Clip2";
+// -clip -normal: what _fusion_rescued_normal.txt adds to a row of _fusion_rescued.txt
+static const char *RESCUED_COLUMNS_NORMAL = "\tNormal_DRP\tNormal_ClipAt1\tNormal_ClipAt2\tNormal_Depth1\tNormal_Depth2";
+
+// A rescued call: a row that _fusion_rescued.txt writes.  Its breakends are its two clip peaks, in the directions of
+// bk_junction_sides; the normal's counts are filled with -normal (bk_clip_reads within 2 bp of the peaks, bk_base_depth at them).
+struct RescuedCall
+{
+  uint8_t right[2] = {0, 1};
+  uint32_t peak_n[2] = {0, 0};
+  uint32_t normal_drp = 0, normal_at[2] = {0, 0}, normal_depth[2] = {0, 0};
+};
 
 // Which rows the fusion files hold, and with them -vcf and -evidence: `all_ok` rows go to _fusion_all.txt (-all), those that also pass
 // the gene-pair and repeat filters to _fusion.txt.
@@ -608,6 +622,9 @@ struct VcfInput
   const struct bk_normal_support *nsup = nullptr;
   uint64_t n_nsup = 0;
   const vector<struct bk_ref_support> *gsup = nullptr, *gsup_normal = nullptr;  // -genotype (else null): GT:GQ:DR:DV:RR:RV
+  // _fusion_rescued.vcf (else null): `rows` are the rescued clusters, rescued[k] belongs to rows[k]; the records get INFO/SC and a
+  // third sample field CV, the clipped reads of the side, and are never genotyped
+  const vector<RescuedCall> *rescued = nullptr;
 };
 
 static char nib_base(const string &nib_dir, const string &chr, long pos1)  // the base at a 1-based position; N without a file or beyond it
@@ -656,11 +673,15 @@ struct VcfRecord
 static bool write_vcf(const string &path, const vector<OutRow> &rows, const VcfInput &in)
 {
   vector<VcfRecord> recs;
-  for (const OutRow &r : rows)
+  if (in.rescued && (in.rescued->size() != rows.size() || in.gsup || in.gsup_normal)) return false;
+  for (size_t k = 0; k < rows.size(); ++k)
   {
-    if (!call_written(r, in.all)) continue;
-    const bool no_gene_pair = call_no_gene_pair(r), filt_ok = call_filt_ok(r);
-    if (r.idx >= in.jsup->size() || (in.with_normal && r.idx >= in.n_nsup) || (in.gsup && r.idx >= in.gsup->size()) || (in.gsup_normal && r.idx >= in.gsup_normal->size()))
+    const OutRow &r = rows[k];
+    const RescuedCall *rc = in.rescued ? &(*in.rescued)[k] : nullptr;
+    if (rc ? !rescued_written(r, in.all) : !call_written(r, in.all)) continue;
+    const bool no_gene_pair = call_no_gene_pair(r), filt_ok = rc ? !no_gene_pair && !r.is_rpt : call_filt_ok(r);
+    if (r.idx >= in.jsup->size() || (in.with_normal && !rc && r.idx >= in.n_nsup) || (in.gsup && r.idx >= in.gsup->size()) ||
+        (in.gsup_normal && r.idx >= in.gsup_normal->size()))
       return false;
     const struct bk_junction &j = (*in.jsup)[r.idx];
     uint8_t right[2] = {0, 1}, source = 0;
@@ -681,8 +702,16 @@ static bool write_vcf(const string &path, const vector<OutRow> &rows, const VcfI
       o << "SVTYPE=BND;MATEID=" << id << "_" << 2 - s << ";EVENTTYPE=" << fusion_type(r.c.type_mask) << ";PE=" << r.c.n_drp << ";SR=" << r.c.n_sr
         << ";MAPQ=" << (n_members ? (s ? j.mapq_sum2 : j.mapq_sum1) / n_members : 0) << ";DP=" << (s ? r.c.depth2 : r.c.depth1) << ";GENE=" << vcf_info_text(s ? r.g2 : r.g1)
         << ";SIDES=" << (source == 2 ? "SR" : source == 1 ? "PE" : "NONE");
-      o << "\t" << (in.gsup ? "GT:GQ:DR:DV:RR:RV" : "DV:RV") << "\t" << vcf_sample(r.c.n_drp, r.c.n_sr, in.gsup ? &(*in.gsup)[r.idx] : nullptr, s);
-      if (in.with_normal) o << "\t" << vcf_sample(in.nsup[r.idx].n_drp, in.nsup[r.idx].n_sr, in.gsup_normal ? &(*in.gsup_normal)[r.idx] : nullptr, s);
+      if (rc)
+      {
+        o << ";SC=" << rc->peak_n[s] << "\tDV:RV:CV\t" << vcf_sample(r.c.n_drp, 0, nullptr, s) << ":" << rc->peak_n[s];
+        if (in.with_normal) o << "\t" << vcf_sample(rc->normal_drp, 0, nullptr, s) << ":" << rc->normal_at[s];
+      }
+      else
+      {
+        o << "\t" << (in.gsup ? "GT:GQ:DR:DV:RR:RV" : "DV:RV") << "\t" << vcf_sample(r.c.n_drp, r.c.n_sr, in.gsup ? &(*in.gsup)[r.idx] : nullptr, s);
+        if (in.with_normal) o << "\t" << vcf_sample(in.nsup[r.idx].n_drp, in.nsup[r.idx].n_sr, in.gsup_normal ? &(*in.gsup_normal)[r.idx] : nullptr, s);
+      }
       o << "\n";
       VcfRecord rec;
       rec.tid = s ? r.c.p2_tid : r.c.p1_tid;
@@ -710,6 +739,7 @@ static bool write_vcf(const string &path, const vector<OutRow> &rows, const VcfI
        "##INFO=<ID=DP,Number=1,Type=Integer,Description=\"Read depth at this breakpoint\">\n"
        "##INFO=<ID=GENE,Number=1,Type=String,Description=\"Gene at this breakpoint, or intergenic\">\n"
        "##INFO=<ID=SIDES,Number=1,Type=String,Description=\"Evidence the breakend orientation comes from: SR split reads, PE read pairs, NONE\">\n";
+  if (in.rescued) v << "##INFO=<ID=SC,Number=1,Type=Integer,Description=\"Soft-clipped reads without an SA tag that end at this position (the clip peak)\">\n";
   if (in.gsup)
     v << "##FORMAT=<ID=GT,Number=1,Type=String,Description=\"Genotype\">\n"
          "##FORMAT=<ID=GQ,Number=1,Type=Integer,Description=\"Genotype quality\">\n"
@@ -717,6 +747,7 @@ static bool write_vcf(const string &path, const vector<OutRow> &rows, const VcfI
   v << "##FORMAT=<ID=DV,Number=1,Type=Integer,Description=\"Discordant read pairs that support the call\">\n";
   if (in.gsup) v << "##FORMAT=<ID=RR,Number=1,Type=Integer,Description=\"Reference reads across this breakpoint\">\n";
   v << "##FORMAT=<ID=RV,Number=1,Type=Integer,Description=\"Split reads that support the call\">\n";
+  if (in.rescued) v << "##FORMAT=<ID=CV,Number=1,Type=Integer,Description=\"Soft-clipped reads without an SA tag at this breakpoint\">\n";
   v << "##FILTER=<ID=PASS,Description=\"All filters passed\">\n";
   if (in.all)
     v << "##FILTER=<ID=NoGenePair,Description=\"Both sides intergenic, or both in the same gene\">\n"
@@ -736,8 +767,95 @@ struct EvidenceInput
   const vector<uint64_t> *call_off = nullptr;  // per BK_STAGE_CLUSTERS row, one more entry than rows
 };
 
-// The calls covered are those of -vcf, with its ids (bk<row>).  One pass over the input BAM (bk_bam_extract) gives the names of the
-// listed reads and writes every alignment of theirs, tagged bk:Z:<the read's call ids, ascending, joined with commas>.
+// One listed read of a call: the hashes of its name, and the call (bk<call>) it stands behind
+struct ReadRef
+{
+  uint64_t qhash;
+  uint32_t qcheck;
+  uint64_t call;
+};
+// the names bk_bam_extract gave back, by (qhash, qcheck)
+struct ReadNames
+{
+  std::map<std::pair<uint64_t, uint32_t>, size_t> key_of;
+  vector<const char *> name_of;
+  char *names = nullptr;
+  ~ReadNames() { bk_bam_names_free(names); }
+  const char *operator()(uint64_t qhash, uint32_t qcheck) const
+  {
+    const char *name = name_of[key_of.at(std::make_pair(qhash, qcheck))];
+    return *name ? name : ".";
+  }
+};
+
+// One pass over the input BAM (bk_bam_extract) gives the names of the listed reads and writes every alignment of theirs to out_bam,
+// tagged bk:Z:<the read's call ids, ascending, joined with commas>.  `refs` comes with its calls ascending.
+static bool extract_reads(const string &inp_bam, const string &out_bam, const vector<ReadRef> &refs, ReadNames &rn, string &why)
+{
+  // the unique reads and, per read, its calls (ascending, each once)
+  vector<bk_read_key> keys;
+  vector<vector<uint64_t>> key_calls;
+  for (const ReadRef &e : refs)
+  {
+    auto it = rn.key_of.emplace(std::make_pair(e.qhash, e.qcheck), keys.size());
+    if (it.second)
+    {
+      keys.push_back(bk_read_key{e.qhash, e.qcheck, 0});
+      key_calls.emplace_back();
+    }
+    vector<uint64_t> &kc = key_calls[it.first->second];
+    if (kc.empty() || kc.back() != e.call) kc.push_back(e.call);
+  }
+  std::map<string, uint32_t> tag_of;
+  vector<string> tag_text;
+  for (size_t k = 0; k < keys.size(); ++k)
+  {
+    string t;
+    for (uint64_t c : key_calls[k]) t += (t.empty() ? "bk" : ",bk") + std::to_string(c);
+    auto it = tag_of.emplace(t, (uint32_t) tag_text.size());
+    if (it.second) tag_text.push_back(t);
+    keys[k].tag = it.first->second;
+  }
+  vector<const char *> tag_ptrs;
+  for (const string &t : tag_text) tag_ptrs.push_back(t.c_str());
+  char err[512] = "";
+  if (bk_bam_extract(inp_bam.c_str(), out_bam.c_str(), keys.data(), keys.size(), tag_ptrs.data(), tag_ptrs.size(), &rn.names, nullptr, err, sizeof err) != BK_OK)
+  {
+    why = err;
+    return false;
+  }
+  rn.name_of.assign(keys.size(), "");
+  const char *p = rn.names;
+  for (size_t k = 0; k < keys.size(); ++k)
+  {
+    rn.name_of[k] = p;
+    p += strlen(p) + 1;
+  }
+  return true;
+}
+
+static const char *EVIDENCE_HEADER = "Call\tKind\tRead\tChr1\tPos1\tChr2\tPos2\tSides\tFlag1\tFlag2\tMapq1\tMapq2\tRecord";
+
+static void write_evidence_line(std::ostream &o, uint64_t c, const struct bk_evidence &e, const ReadNames &rn, const EvidenceInput &in)
+{
+  auto chr = [&](int32_t tid) { return tid < 0 || tid >= in.nt ? "*" : in.names[tid]; };
+  o << "bk" << c << "\t" << (e.kind == BK_EV_PAIR ? "PE" : "SR") << "\t" << rn(e.qhash, e.qcheck) << "\t" << chr(e.tid1) << "\t" << e.pos1 << "\t" << chr(e.tid2) << "\t"
+    << e.pos2 << "\t" << ((e.sides >> 1) & 1 ? 'R' : 'L') << ((e.sides & 1) ? 'R' : 'L') << "\t" << e.flag1 << "\t" << e.flag2 << "\t" << (unsigned) e.mapq1 << "\t"
+    << (unsigned) e.mapq2 << "\t" << e.rec;
+}
+
+// both files or neither
+static bool close_evidence(std::ofstream &o, const string &txt, const string &bam, string &why)
+{
+  o.close();
+  if (o) return true;
+  (void) remove(txt.c_str());
+  (void) remove(bam.c_str());
+  why = "cannot write " + txt;
+  return false;
+}
+
+// The calls covered are those of -vcf, with its ids (bk<row>).
 static bool write_evidence(const string &prefix, const string &inp_bam, const vector<OutRow> &rows, const EvidenceInput &in, string &why)
 {
   vector<uint64_t> calls;
@@ -752,72 +870,78 @@ static bool write_evidence(const string &prefix, const string &inp_bam, const ve
     calls.push_back(r.idx);
   }
   std::sort(calls.begin(), calls.end());  // ABI order: by row
-  // the unique reads of those calls and, per read, its calls (ascending, each once)
-  std::map<std::pair<uint64_t, uint32_t>, size_t> key_of;
-  vector<bk_read_key> keys;
-  vector<vector<uint64_t>> key_calls;
+  vector<ReadRef> refs;
   for (uint64_t c : calls)
-    for (uint64_t i = (*in.call_off)[c]; i < (*in.call_off)[c + 1]; ++i)
-    {
-      const struct bk_evidence &e = (*in.rows)[i];
-      auto it = key_of.emplace(std::make_pair(e.qhash, e.qcheck), keys.size());
-      if (it.second)
-      {
-        keys.push_back(bk_read_key{e.qhash, e.qcheck, 0});
-        key_calls.emplace_back();
-      }
-      vector<uint64_t> &kc = key_calls[it.first->second];
-      if (kc.empty() || kc.back() != c) kc.push_back(c);
-    }
-  std::map<string, uint32_t> tag_of;
-  vector<string> tag_text;
-  for (size_t k = 0; k < keys.size(); ++k)
-  {
-    string t;
-    for (uint64_t c : key_calls[k]) t += (t.empty() ? "bk" : ",bk") + std::to_string(c);
-    auto it = tag_of.emplace(t, (uint32_t) tag_text.size());
-    if (it.second) tag_text.push_back(t);
-    keys[k].tag = it.first->second;
-  }
-  vector<const char *> tag_ptrs;
-  for (const string &t : tag_text) tag_ptrs.push_back(t.c_str());
-  char *names = nullptr, err[512] = "";
-  if (bk_bam_extract(inp_bam.c_str(), (prefix + "_evidence.bam").c_str(), keys.data(), keys.size(), tag_ptrs.data(), tag_ptrs.size(), &names, nullptr, err, sizeof err) != BK_OK)
-  {
-    why = err;
-    return false;
-  }
-  vector<const char *> name_of(keys.size(), "");
-  {
-    const char *p = names;
-    for (size_t k = 0; k < keys.size(); ++k)
-    {
-      name_of[k] = p;
-      p += strlen(p) + 1;
-    }
-  }
+    for (uint64_t i = (*in.call_off)[c]; i < (*in.call_off)[c + 1]; ++i) refs.push_back(ReadRef{(*in.rows)[i].qhash, (*in.rows)[i].qcheck, c});
+  ReadNames rn;
+  if (!extract_reads(inp_bam, prefix + "_evidence.bam", refs, rn, why)) return false;
   std::ofstream o((prefix + "_evidence.txt").c_str());
-  o << "Call\tKind\tRead\tChr1\tPos1\tChr2\tPos2\tSides\tFlag1\tFlag2\tMapq1\tMapq2\tRecord\n";
-  auto chr = [&](int32_t tid) { return tid < 0 || tid >= in.nt ? "*" : in.names[tid]; };
+  o << EVIDENCE_HEADER << "\n";
   for (uint64_t c : calls)
     for (uint64_t i = (*in.call_off)[c]; i < (*in.call_off)[c + 1]; ++i)
     {
-      const struct bk_evidence &e = (*in.rows)[i];
-      const char *name = name_of[key_of[std::make_pair(e.qhash, e.qcheck)]];
-      o << "bk" << c << "\t" << (e.kind == BK_EV_PAIR ? "PE" : "SR") << "\t" << (*name ? name : ".") << "\t" << chr(e.tid1) << "\t" << e.pos1 << "\t" << chr(e.tid2) << "\t"
-        << e.pos2 << "\t" << ((e.sides >> 1) & 1 ? 'R' : 'L') << ((e.sides & 1) ? 'R' : 'L') << "\t" << e.flag1 << "\t" << e.flag2 << "\t" << (unsigned) e.mapq1 << "\t"
-        << (unsigned) e.mapq2 << "\t" << e.rec << "\n";
+      write_evidence_line(o, c, (*in.rows)[i], rn, in);
+      o << "\n";
     }
-  o.close();
-  bk_bam_names_free(names);
-  if (!o)
+  return close_evidence(o, prefix + "_evidence.txt", prefix + "_evidence.bam", why);
+}
+
+// -clip -evidence: the reads behind the rescued calls: <prefix>_evidence_rescued.txt and <prefix>_evidence_rescued.bam.  Per call, ids
+// ascending: its member pairs (the BK_EV_PAIR rows of bk_evidence: an unvoted row has no others), then the reads clipped exactly at
+// its two peaks (bk_clip_reads, tol 0), side 1 before side 2.  `rescued` / `calls`: the rescued clusters and their RescuedCall;
+// clip rows of sites 2 * j and 2 * j + 1 belong to the j-th written one of them.
+static bool write_evidence_rescued(const string &prefix, const string &inp_bam, const vector<OutRow> &rescued, const vector<RescuedCall> &calls, const EvidenceInput &in,
+                                   const vector<struct bk_clip_read> &clip_rows, const vector<uint64_t> &site_off, string &why)
+{
+  struct Item
   {
-    (void) remove((prefix + "_evidence.txt").c_str());  // neither file stays without the other
-    (void) remove((prefix + "_evidence.bam").c_str());
-    why = "cannot write " + prefix + "_evidence.txt";
-    return false;
+    uint64_t call;
+    size_t k, j;  // index into rescued, ordinal among the written
+  };
+  vector<Item> items;
+  for (size_t k = 0; k < rescued.size(); ++k)
+  {
+    const OutRow &r = rescued[k];
+    if (!rescued_written(r, in.all)) continue;
+    const size_t j = items.size();
+    if (r.idx + 1 >= in.call_off->size() || (*in.call_off)[r.idx + 1] > in.rows->size() || 2 * j + 2 >= site_off.size() || site_off[2 * j + 2] > clip_rows.size())
+    {
+      why = "the evidence tables do not cover every rescued call";
+      return false;
+    }
+    items.push_back(Item{r.idx, k, j});
   }
-  return true;
+  std::sort(items.begin(), items.end(), [](const Item &a, const Item &b) { return a.call < b.call; });
+  vector<ReadRef> refs;
+  for (const Item &it : items)
+  {
+    for (uint64_t i = (*in.call_off)[it.call]; i < (*in.call_off)[it.call + 1]; ++i) refs.push_back(ReadRef{(*in.rows)[i].qhash, (*in.rows)[i].qcheck, it.call});
+    for (uint64_t i = site_off[2 * it.j]; i < site_off[2 * it.j + 2]; ++i) refs.push_back(ReadRef{clip_rows[i].qhash, clip_rows[i].qcheck, it.call});
+  }
+  const string txt = prefix + "_evidence_rescued.txt", bam = prefix + "_evidence_rescued.bam";
+  ReadNames rn;
+  if (!extract_reads(inp_bam, bam, refs, rn, why)) return false;
+  std::ofstream o(txt.c_str());
+  o << EVIDENCE_HEADER << "\tClip\n";
+  auto chr = [&](int32_t tid) { return tid < 0 || tid >= in.nt ? "*" : in.names[tid]; };
+  for (const Item &it : items)
+  {
+    const OutRow &r = rescued[it.k];
+    for (uint64_t i = (*in.call_off)[it.call]; i < (*in.call_off)[it.call + 1]; ++i)
+    {
+      write_evidence_line(o, it.call, (*in.rows)[i], rn, in);
+      o << "\t.\n";
+    }
+    for (int s = 0; s < 2; ++s)
+      for (uint64_t i = site_off[2 * it.j + s]; i < site_off[2 * it.j + s + 1]; ++i)
+      {
+        const struct bk_clip_read &e = clip_rows[i];
+        o << "bk" << it.call << "\tSC\t" << rn(e.qhash, e.qcheck) << "\t" << chr(e.tid) << "\t" << e.p << "\t" << (s ? r.p1_chr : r.p2_chr) << "\t"
+          << (s ? r.c.p1_exact : (uint32_t) r.c.p2_exact) << "\t" << s + 1 << (calls[it.k].right[s] ? 'R' : 'L') << "\t" << e.flag << "\t0\t" << (unsigned) e.mapq << "\t0\t"
+          << e.rec << "\t" << e.clip_len << "\n";
+      }
+  }
+  return close_evidence(o, txt, bam, why);
 }
 
 // one input BAM: its decoded table (host or device) and, once created, its context
@@ -985,7 +1109,7 @@ int main(int argc, char *argv[])
   }
   if (clip)
   {
-    if (!bk_clip_support || !bk_base_depth || !bk_clip_rescue || !bk_junctions || !bk_junction_sides)
+    if (!bk_clip_support || !bk_clip_reads || !bk_base_depth || !bk_clip_rescue || !bk_junctions || !bk_junction_sides)
     {
       std::cerr << "Error: -clip needs the GPU library" << std::endl;
       exit(1);
@@ -1403,6 +1527,67 @@ int main(int argc, char *argv[])
     std::cout << "rescued cluster count: " << rescued.size() << std::endl;
     std::sort(rescued.begin(), rescued.end(), cmp_cluster);
   }
+  // the rescued calls (the rows _fusion_rescued.txt writes, in its order): their two sites (ps_tid, peak, d_s), for the normal's
+  // counts (-normal), the VCF records (-vcf) and the clipped reads themselves (-evidence)
+  vector<RescuedCall> rescued_calls(rescued.size());
+  vector<struct bk_clip_read> rescued_reads;
+  vector<uint64_t> rescued_read_off;
+  if (clip && (normal.ctx || vcf || evidence))
+  {
+    vector<struct bk_clip_site> sites;
+    vector<size_t> written;
+    for (size_t k = 0; k < rescued.size(); ++k)
+    {
+      const OutRow &r = rescued[k];
+      RescuedCall &rcall = rescued_calls[k];
+      uint8_t source = 0;
+      bk_junction_sides(&jsup[r.idx], &rcall.right[0], &rcall.right[1], &source);
+      for (int s = 0; s < 2; ++s) rcall.peak_n[s] = csup[r.idx].peak_n[s][rcall.right[s]];
+      if (!rescued_written(r, !filter)) continue;
+      written.push_back(k);
+      sites.push_back(bk_clip_site{r.c.p1_tid, r.c.p1_exact, 0u, rcall.right[0]});
+      sites.push_back(bk_clip_site{r.c.p2_tid, (uint32_t) r.c.p2_exact, 0u, rcall.right[1]});
+    }
+    if (evidence)
+    {
+      const uint32_t *counts = nullptr;
+      const struct bk_clip_read *cr = nullptr;
+      const uint64_t *off = nullptr;
+      if ((rc = bk_clip_reads(ctx, sites.data(), sites.size(), qual, (int) min_clip, &counts, &cr, &off)) != BK_OK) die(rc);
+      rescued_read_off.assign(off, off + sites.size() + 1);
+      rescued_reads.assign(cr, cr + off[sites.size()]);
+    }
+    if (normal.ctx)
+    {
+      // the +-2 bp of every other count of the normal
+      for (struct bk_clip_site &x : sites) x.tol = 2;
+      vector<int32_t> q_tid;
+      vector<uint32_t> q_pos;
+      for (const struct bk_clip_site &x : sites)
+      {
+        q_tid.push_back(x.tid);
+        q_pos.push_back(x.pos);
+      }
+      const uint32_t *counts = nullptr, *depth = nullptr;
+      auto die_normal = [&] {
+        std::cerr << "Error: normal " << normal.path << ": " << bk_last_error(normal.ctx) << std::endl;
+        exit(1);
+      };
+      if (bk_clip_reads(normal.ctx, sites.data(), sites.size(), qual, (int) min_clip, &counts, nullptr, nullptr) != BK_OK) die_normal();
+      if (bk_base_depth(normal.ctx, q_tid.data(), q_pos.data(), q_tid.size(), &depth) != BK_OK) die_normal();
+      for (size_t j = 0; j < written.size(); ++j)
+      {
+        RescuedCall &rcall = rescued_calls[written[j]];
+        const uint64_t idx = rescued[written[j]].idx;
+        rcall.normal_drp = idx < n_nsup ? nsup[idx].n_drp : 0;
+        for (int s = 0; s < 2; ++s)
+        {
+          rcall.normal_at[s] = counts[2 * j + s];
+          rcall.normal_depth[s] = depth[2 * j + s];
+        }
+      }
+    }
+  }
   std::ofstream out, outf, out_n, outf_n;  // (_n: the twins with the matched normal's four counts)
   std::ofstream out_g, outf_g;             // (_g: the twins with the genotype columns, -genotype)
   std::ofstream out_c, outf_c, out_r;      // (_c: the twins with the clip columns, _r: the rescued clusters, -clip)
@@ -1450,12 +1635,29 @@ int main(int argc, char *argv[])
     outf_c << header_c;
     out_r.open((out_file + "_fusion_rescued.txt").c_str());
     out_r << header_c;
-    for (auto &r : rescued)
+    std::ofstream out_rn;  // (with -normal: the same rows with the normal's evidence at the rescued peaks)
+    if (with_normal)
     {
+      out_rn.open((out_file + "_fusion_rescued_normal.txt").c_str());
+      out_rn << string(header_c, 0, header_c.size() - 1) << RESCUED_COLUMNS_NORMAL << "\n";
+    }
+    for (size_t k = 0; k < rescued.size(); ++k)
+    {
+      const OutRow &r = rescued[k];
+      if (!rescued_written(r, !filter)) continue;
       const ClipCols cc = clip_cols(jsup[r.idx], csup[r.idx], with_normal ? &csup_normal[r.idx] : nullptr);
-      if (rescued_written(r, !filter)) write_row(out_r, r, nullptr, nullptr, nullptr, &cc);
+      write_row(out_r, r, nullptr, nullptr, nullptr, &cc);
+      if (with_normal)
+      {
+        const RescuedCall &x = rescued_calls[k];
+        std::ostringstream tail;
+        tail << "\t" << x.normal_drp << "\t" << x.normal_at[0] << "\t" << x.normal_at[1] << "\t" << x.normal_depth[0] << "\t" << x.normal_depth[1];
+        const string t = tail.str();
+        write_row(out_rn, r, nullptr, nullptr, nullptr, &cc, &t);
+      }
     }
     out_r.close();
+    if (with_normal) out_rn.close();
   }
   for (auto &r : rows)
   {
@@ -1517,6 +1719,16 @@ int main(int argc, char *argv[])
       std::cerr << "Error: cannot write " << out_file << "_fusion.vcf: the evidence tables do not cover every call" << std::endl;
       exit(1);
     }
+    if (clip)
+    {
+      vi.gsup = vi.gsup_normal = nullptr;  // rescued calls are not genotyped
+      vi.rescued = &rescued_calls;
+      if (!write_vcf(out_file + "_fusion_rescued.vcf", rescued, vi))
+      {
+        std::cerr << "Error: cannot write " << out_file << "_fusion_rescued.vcf: the evidence tables do not cover every call" << std::endl;
+        exit(1);
+      }
+    }
   }
   if (evidence)
   {
@@ -1530,6 +1742,11 @@ int main(int argc, char *argv[])
     if (!write_evidence(out_file, inp_file, rows, ei, why))
     {
       std::cerr << "Error: cannot write " << out_file << "_evidence.txt / _evidence.bam: " << why << std::endl;
+      exit(1);
+    }
+    if (clip && !write_evidence_rescued(out_file, inp_file, rescued, rescued_calls, ei, rescued_reads, rescued_read_off, why))
+    {
+      std::cerr << "Error: cannot write " << out_file << "_evidence_rescued.txt / _evidence_rescued.bam: " << why << std::endl;
       exit(1);
     }
   }

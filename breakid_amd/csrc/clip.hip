@@ -2,6 +2,7 @@
 // SA tag whose clip sits inside the cluster's window - how many, where they pile up, and how many sit at the voted breakpoint.  A
 // window search over the resident, coordinate-sorted record table - one wavefront (a workgroup of its own) per (call, side).
 #include "clip.h"
+#include <cstddef>
 
 namespace
 {
@@ -14,16 +15,19 @@ __device__ __forceinline__ bool cigar_op_ref(uint32_t word) { return ((0x3C1A7u 
 // a pos column is int32: beyond its range a bound is where the next chromosome begins
 __device__ __forceinline__ uint64_t clip_lower(const RecView &r, int32_t T, long long P)
 {
-  return P <= 0x7FFFFFFFll ? rec_lower(r, T, P) : rec_lower(r, T + 1, -0x80000000ll);
+  return P <= 0x7FFFFFFFll ? rec_lower(r, T, P) : rec_lower(r, (int32_t) ((uint32_t) T + 1u), -0x80000000ll);
 }
 
 // The clip events of record i, whose flag, mapq and aux columns have passed: `lead` (at pos + 1) and `trail` (at *pt = bam_endpos).
 // The first and the last CIGAR word decide (and the words behind hard clips); the whole CIGAR is walked only for a record with a
 // trailing clip that qualifies, or with a leading one that no aligned base follows at once (the reference length must be > 0).
-__device__ __forceinline__ void clip_events(const RecView &r, uint64_t i, int32_t pos, int min_clip, bool &lead, bool &trail, long long &pt, uint32_t &words)
+// len_lead / len_trail: the lengths of the two S ops (of use where the event is set).
+__device__ __forceinline__ void clip_events(const RecView &r, uint64_t i, int32_t pos, int min_clip, bool &lead, bool &trail, long long &pt, uint32_t &words,
+                                            uint32_t &len_lead, uint32_t &len_trail)
 {
   lead = trail = false;
   pt = 0;
+  len_lead = len_trail = 0;
   const uint32_t c0 = r.cigar_off[i], c1 = r.cigar_off[i + 1];
   words += 2;
   if (c1 <= c0) return;
@@ -36,6 +40,8 @@ __device__ __forceinline__ void clip_events(const RecView &r, uint64_t i, int32_
   const bool l = (wa & 15u) == CIGAR_S && (long long) (wa >> 4) >= min_clip;
   const bool t = (wz & 15u) == CIGAR_S && (long long) (wz >> 4) >= min_clip;
   if (!l && !t) return;
+  len_lead = wa >> 4;
+  len_trail = wz >> 4;
   if (!t && a + 1 < c1 && cigar_op_ref(cg[a + 1]))
   {
     ++words;
@@ -112,7 +118,8 @@ __global__ __launch_bounds__(64) void k_clip_support(RecView r, const bk_cluster
           if ((f[s] & CLIP_FLAG_NEVER) || (int) q[s] < mapq_min || a1[s] != a0[s]) continue;
           bool lead, trail;
           long long pt;
-          clip_events(r, base + (uint64_t) s * 64 + lane, p[s], min_clip, lead, trail, pt, words);
+          uint32_t ll, lt;
+          clip_events(r, base + (uint64_t) s * 64 + lane, p[s], min_clip, lead, trail, pt, words, ll, lt);
           const long long pl = (long long) p[s] + 1;
           if (lead && pl >= t0 && pl < t1)
           {
@@ -160,7 +167,8 @@ __global__ __launch_bounds__(64) void k_clip_support(RecView r, const bk_cluster
         bool lead, trail;
         long long pt;
         const int32_t pos = r.pos[i];
-        clip_events(r, i, pos, min_clip, lead, trail, pt, words);
+        uint32_t ll, lt;
+        clip_events(r, i, pos, min_clip, lead, trail, pt, words, ll, lt);
         const long long pl = (long long) pos + 1;
         if (lead && pl >= e - 2 && pl <= e + 2 && !(pl >= lo && pl <= hi)) ++n_at[1];
         if (trail && pt >= e - 2 && pt <= e + 2 && !(pt >= lo && pt <= hi)) ++n_at[0];
@@ -197,6 +205,168 @@ __global__ __launch_bounds__(64) void k_clip_support(RecView r, const bk_cluster
     }
   }
 }
+// ---- bk_clip_reads: the clip events at caller-given sites, counted and listed -------------------------------------
+// Count, scan, emit, as bk_evidence does it: no atomic hands out a slot.  One wavefront per site, four to a workgroup (a site is a
+// handful of positions: no LDS counters, nothing shared between the waves).  The records that can hold an event of the site are
+// those a tile [pos - tol, pos + tol] of k_clip_support would look at; both passes walk them in the same order with the same
+// predicate, so the listing fills exactly the range the scan of the counts gave it - and says so when it does not.
+static_assert(sizeof(struct bk_clip_site) == 16, "bk_clip_site must be 16 bytes");
+static_assert(sizeof(struct bk_clip_read) == 40 && offsetof(struct bk_clip_read, qcheck) == 16 && offsetof(struct bk_clip_read, tid) == 24 &&
+                  offsetof(struct bk_clip_read, clip_len) == 32 && offsetof(struct bk_clip_read, flag) == 36 && offsetof(struct bk_clip_read, dir) == 39,
+              "bk_clip_read must be 40 bytes");
+
+__device__ __forceinline__ void store_clip_read(struct bk_clip_read *__restrict__ o, const struct bk_clip_read &v)
+{
+  uint2 t[5];
+  __builtin_memcpy(t, &v, sizeof v);
+  uint2 *o2 = reinterpret_cast<uint2 *>(o);  // (40-byte rows in a hipMalloc'ed array start 8-byte aligned)
+#pragma unroll
+  for (int j = 0; j < 5; ++j) o2[j] = t[j];
+}
+
+struct ClipSiteOut
+{
+  // count pass
+  uint32_t *counts;
+  uint64_t *counts64;  // the same numbers as the scan's input
+  ClipStat *stat;      // may be null
+  // emit pass
+  const uint64_t *site_off;
+  struct bk_clip_read *rows;
+  uint64_t n_rows;
+  uint32_t *bad;
+};
+
+template <bool EMIT>
+__device__ __forceinline__ void clip_site_walk(const RecView &r, const ClipNames &nm, const struct bk_clip_site *__restrict__ sites, uint32_t n_sites, int mapq_min,
+                                               int min_clip, int maxspan, const ClipSiteOut &out)
+{
+  const uint32_t k = blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (k >= n_sites) return;  // (the whole wave)
+  const struct bk_clip_site site = sites[k];
+  const int32_t T = site.tid;
+  const long long p_lo = (long long) site.pos - (long long) site.tol, p_hi = (long long) site.pos + (long long) site.tol;
+  const bool want_lead = site.dir == 1u;  // RIGHT: leading events; LEFT: trailing ones
+  uint64_t rlo = 0, rhi = 0;
+  if (T >= 0 && r.n)
+  {
+    rlo = clip_lower(r, T, p_lo - 1 - maxspan);
+    rhi = clip_lower(r, T, p_hi);
+  }
+  const uint64_t below = (1ull << lane) - 1ull;
+  const uint64_t row0 = EMIT ? out.site_off[k] : 0, limit = EMIT ? out.site_off[k + 1] : 0;
+  uint32_t n_mine = 0, words = 0;
+  uint64_t n_out = 0;
+  bool wrong = false;
+  for (uint64_t base = rlo; base < rhi; base += CLIP_STEPS * 64)  // (rlo and rhi are the same on every lane: so is the trip count)
+  {
+    int32_t p[CLIP_STEPS];
+    uint32_t a0[CLIP_STEPS], a1[CLIP_STEPS];
+    uint16_t f[CLIP_STEPS];
+    uint8_t q[CLIP_STEPS];
+#pragma unroll
+    for (int s = 0; s < CLIP_STEPS; ++s)
+    {
+      const uint64_t i = base + (uint64_t) s * 64 + lane;
+      const bool in = i < rhi;
+      p[s] = in ? r.pos[i] : 0;
+      f[s] = in ? r.flag[i] : (uint16_t) 0x4;  // never eligible
+      q[s] = in ? r.mapq[i] : (uint8_t) 0;
+      a0[s] = in ? r.aux_off[i] : 0u;
+      a1[s] = in ? r.aux_off[i + 1] : 0u;
+    }
+#pragma unroll
+    for (int s = 0; s < CLIP_STEPS; ++s)
+    {
+      const uint64_t i = base + (uint64_t) s * 64 + lane;
+      bool hit = false;
+      long long pe = 0;
+      uint32_t len = 0;
+      if (!((f[s] & CLIP_FLAG_NEVER) || (int) q[s] < mapq_min || a1[s] != a0[s]))
+      {
+        bool lead, trail;
+        long long pt;
+        uint32_t ll, lt;
+        clip_events(r, i, p[s], min_clip, lead, trail, pt, words, ll, lt);
+        pe = want_lead ? (long long) p[s] + 1 : pt;
+        len = want_lead ? ll : lt;
+        hit = (want_lead ? lead : trail) && pe >= p_lo && pe <= p_hi;
+      }
+      if (!EMIT)
+        n_mine += hit ? 1u : 0u;
+      else
+      {
+        const uint64_t m = __ballot(hit);  // (every lane is here: the filter above has closed)
+        if (hit)
+        {
+          const uint64_t dest = row0 + n_out + (uint64_t) __popcll(m & below);
+          if (dest >= limit || dest >= out.n_rows)
+            wrong = true;  // a row outside its range is never written
+          else
+          {
+            struct bk_clip_read v;
+            v.rec = i;
+            if (nm.side)
+            {
+              v.qhash = nm.side[i].qhash;
+              v.qcheck = nm.side[i].qcheck;
+            }
+            else
+            {
+              v.qhash = nm.qhash[i];
+              v.qcheck = nm.qcheck ? nm.qcheck[i] : 0u;
+            }
+            v.site = k;
+            v.tid = T;
+            v.p = (uint32_t) pe;
+            v.clip_len = len;
+            v.flag = f[s];
+            v.mapq = q[s];
+            v.dir = (uint8_t) site.dir;
+            store_clip_read(out.rows + dest, v);
+          }
+        }
+        n_out += (uint64_t) __popcll(m);
+      }
+    }
+  }
+  if (!EMIT)
+  {
+    const uint32_t n = wave_sum_u32(n_mine);
+    if (out.stat) words = wave_sum_u32(words);
+    if (lane == 0)
+    {
+      out.counts[k] = n;
+      out.counts64[k] = n;
+      if (out.stat)
+      {
+        ClipStat st;
+        st.visited = (uint32_t) (rhi - rlo);
+        st.words = words;
+        st.tiles = 1;
+        st.pad = 0;
+        out.stat[k] = st;
+      }
+    }
+  }
+  else
+  {
+    const bool any_wrong = __ballot(wrong) != 0ull;
+    if (lane == 0 && (any_wrong || row0 + n_out != limit)) *out.bad = 1u;  // the listing and the counts disagree
+  }
+}
+
+__global__ __launch_bounds__(256) void k_clip_site_count(RecView r, ClipNames nm, const struct bk_clip_site *__restrict__ sites, uint32_t n_sites, int mapq_min, int min_clip,
+                                                         int maxspan, ClipSiteOut out)
+{
+  clip_site_walk<false>(r, nm, sites, n_sites, mapq_min, min_clip, maxspan, out);
+}
+__global__ __launch_bounds__(256) void k_clip_site_emit(RecView r, ClipNames nm, const struct bk_clip_site *__restrict__ sites, uint32_t n_sites, int mapq_min, int min_clip,
+                                                        int maxspan, ClipSiteOut out)
+{
+  clip_site_walk<true>(r, nm, sites, n_sites, mapq_min, min_clip, maxspan, out);
+}
 }  // namespace
 
 void clip_support(const RecView &rec, int maxspan, const bk_cluster *cl, uint64_t ncl, int mapq_min, int min_clip, double w, ClipBufs &b, hipStream_t st,
@@ -212,4 +382,49 @@ void clip_support(const RecView &rec, int maxspan, const bk_cluster *cl, uint64_
   const int W = (int) w;  // the integer the breakpoint stage passes as wi (bp.hip: bp_vote)
   const RecView r = rec_sampled(rec, b.samp, st);
   hipLaunchKernelGGL(k_clip_support, dim3((unsigned) (2 * ncl)), dim3(64), 0, st, r, cl, (uint32_t) ncl, mapq_min, min_clip, W, maxspan, (uint32_t *) res, stat);
+}
+
+void clip_reads(const RecView &rec, const ClipNames &nm, int maxspan, const struct bk_clip_site *sites, uint64_t n_sites, int mapq_min, int min_clip, bool listing,
+                bool want_stat, ClipReadBufs &b, hipStream_t st, ClipReadsOut &o)
+{
+  o.counts = b.counts.as<uint32_t>(n_sites + 1);
+  o.site_off = b.site_off.as<uint64_t>(n_sites + 1);
+  o.rows = b.rows.as<struct bk_clip_read>(1);
+  o.stat = want_stat ? b.stat.as<ClipStat>(n_sites + 1) : nullptr;
+  o.n_rows = 0;
+  o.bad = false;
+  if (n_sites == 0)
+  {
+    HIP_CHECK(hipMemsetAsync(o.site_off, 0, sizeof(uint64_t), st));
+    return;
+  }
+  struct bk_clip_site *d_sites = b.sites.as<struct bk_clip_site>(n_sites);
+  HIP_CHECK(hipMemcpyAsync(d_sites, sites, n_sites * sizeof(struct bk_clip_site), hipMemcpyHostToDevice, st));
+  const RecView r = rec_sampled(rec, b.samp, st);
+  const uint32_t n32 = (uint32_t) n_sites;
+  ClipSiteOut out{};
+  out.counts = o.counts;
+  out.counts64 = b.counts64.as<uint64_t>(n_sites + 1);
+  out.stat = o.stat;
+  hipLaunchKernelGGL(k_clip_site_count, dim3(cdiv(n_sites, 4)), dim3(256), 0, st, r, nm, d_sites, n32, mapq_min, min_clip, maxspan, out);
+  if (!listing) return;
+  prims::exclusive_scan<uint64_t>(out.counts64, o.site_off, n_sites, b.scan_tmp, st);
+  uint64_t total = 0;
+  HIP_CHECK(hipMemcpyAsync(&total, o.site_off + n_sites, 8, hipMemcpyDeviceToHost, st));
+  HIP_CHECK(hipStreamSynchronize(st));  // the row count sizes the listing
+  if (total > 0xFFFFFFFFull) throw bk_error(BK_ERR_LIMIT, "bk_clip_reads: more than 2^32 rows");
+  o.n_rows = total;
+  if (total == 0) return;
+  o.rows = b.rows.as<struct bk_clip_read>(total + 1);
+  uint32_t *bad = b.bad.as<uint32_t>(1);
+  HIP_CHECK(hipMemsetAsync(bad, 0, sizeof(uint32_t), st));
+  out.site_off = o.site_off;
+  out.rows = o.rows;
+  out.n_rows = total;
+  out.bad = bad;
+  hipLaunchKernelGGL(k_clip_site_emit, dim3(cdiv(n_sites, 4)), dim3(256), 0, st, r, nm, d_sites, n32, mapq_min, min_clip, maxspan, out);
+  uint32_t h_bad = 0;
+  HIP_CHECK(hipMemcpyAsync(&h_bad, bad, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  HIP_CHECK(hipStreamSynchronize(st));
+  o.bad = h_bad != 0;
 }

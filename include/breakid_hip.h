@@ -331,6 +331,46 @@ int bk_base_depth(bk_ctx *records, const int32_t *tid, const uint32_t *pos, uint
 int bk_clip_rescue(const bk_cluster *c, const struct bk_junction *j, const struct bk_clip_support *s, uint32_t min_support, uint32_t *pos1, uint32_t *pos2, uint32_t *n1,
                    uint32_t *n2);
 
+/* ---- the clipped reads at a site ------------------------------------------------------------------------------------------
+ * bk_clip_support counts the clip events of every cluster window; bk_clip_reads counts, and lists, the clip events at sites the
+ * caller names, on any records context.  Which records are eligible and which events (tid, p, dir) a record has is exactly what
+ * bk_clip_support (above) defines, with the same mapq_min and min_clip; nothing of it is restated here.  An event (tid, p, d) belongs
+ * to site k when, compared in signed 64-bit,
+ *   tid == sites[k].tid,  d == sites[k].dir,  |p - sites[k].pos| <= sites[k].tol.
+ * counts[k] is the number of such events; a site with tid < 0 gives 0.  Two sites may overlap or be equal: an event is then counted,
+ * and its record listed, under each.
+ * rows lists the events, one bk_clip_read each.  Order (part of the contract; two runs give the same bytes): by site ascending,
+ * within a site by `rec` ascending - a record has at most one event per direction, so this is a total order.
+ * site_off[k] .. site_off[k + 1] bounds site k; site_off has n_sites + 1 entries.  A read name is not kept on the device: a row
+ * carries the two hashes of its record, which bk_bam_extract turns back into names and records.
+ * Two identities tie the call to bk_clip_support(calls, records, mapq_min, min_clip, w): for every row c, side s and direction d
+ *   a site (ps_tid, peak_pos[s][d], 0, d) counts peak_n[s][d], and
+ *   for a voted row a site (ps_tid, ps_exact, 2, d) counts at[s][d].
+ * Neither struct has a typedef: the names belong to the call below. */
+struct bk_clip_site { int32_t tid; uint32_t pos; uint32_t tol; uint32_t dir; }; /* 16 bytes; pos 1-based, dir 0 = LEFT, 1 = RIGHT */
+struct bk_clip_read {
+  uint64_t rec;               /* index of the record in the context's table, as bk_evidence.rec is */
+  uint64_t qhash;             /* qhash of record `rec` */
+  uint32_t qcheck;            /* likewise (0 when the table has no qcheck) */
+  uint32_t site;              /* k */
+  int32_t tid; uint32_t p;    /* the event's own contig and position (1-based) */
+  uint32_t clip_len;          /* length of the S op that made the event */
+  uint16_t flag;              /* of the record */
+  uint8_t mapq;               /* of the record */
+  uint8_t dir;                /* 0 = LEFT, 1 = RIGHT */
+};                            /* 40 bytes */
+/* records: after bk_isize_stats (the stream pass gives the longest alignment), not a shard (bk_shard_*).  sites: a host array.
+ * *counts (n_sites entries), *rows (site_off[n_sites] rows) and *site_off are library-owned until the next call or bk_free(records).
+ * rows == NULL && site_off == NULL asks for the counts only: no listing is made (this is how a matched normal is counted).
+ * BK_ERR_ARG (with the reason in bk_last_error) for wrong call order, shards, min_clip < 1, mapq_min < 0, a dir above 1, null counts,
+ * exactly one of rows / site_off null, null sites with n_sites > 0, and for a listing asked of a table that has neither a qhash
+ * column nor `side` rows.  BK_ERR_LIMIT beyond 2^30 sites or 2^32 rows.  n_sites == 0 is no error: site_off has its one entry, 0.
+ * It changes nothing a later bk_fetch or stage returns, and works on every table form the context can hold (host upload,
+ * BK_MEM_DEVICE with and without `side`, the table bk_exclude_regions left behind, the context of bk_bam_decode_device_ctx while its
+ * bk_bam_dev lives). */
+int bk_clip_reads(bk_ctx *records, const struct bk_clip_site *sites, uint64_t n_sites, int mapq_min, int min_clip, const uint32_t **counts,
+                  const struct bk_clip_read **rows, const uint64_t **site_off);
+
 /* ---- evidence export: the reads behind every call -----------------------------------------------------------------------
  * bk_junctions counts a cluster's member pairs and, for a voted cluster, its matching tuples; bk_evidence lists the same rows, one
  * bk_evidence row each.  Membership is exactly that of bk_junctions (above): a BK_EV_PAIR row for every member pair of every
