@@ -35,6 +35,8 @@ assert CLIP_SITE.itemsize == 16 and CLIP_READ.itemsize == 40
 EV_PAIR, EV_SPLIT = 1, 2
 EVIDENCE = np.dtype([("rec", "<u8"), ("qhash", "<u8"), ("qcheck", "<u4"), ("call", "<u4"), ("tid1", "<i4"), ("pos1", "<u4"), ("tid2", "<i4"),
                      ("pos2", "<u4"), ("flag1", "<u2"), ("flag2", "<u2"), ("mapq1", "u1"), ("mapq2", "u1"), ("kind", "u1"), ("sides", "u1")])  # struct bk_evidence
+UNIQUE_SUPPORT = np.dtype([("uniq_pairs", "<u4"), ("top_pairs", "<u4"), ("uniq_splits", "<u4"), ("top_splits", "<u4")])  # struct bk_unique_support
+assert UNIQUE_SUPPORT.itemsize == 16
 READ_KEY = np.dtype([("qhash", "<u8"), ("qcheck", "<u4"), ("tag", "<u4")])  # bk_read_key
 assert EVIDENCE.itemsize == 48 and READ_KEY.itemsize == 16
 assert PAIR.itemsize == 56 and SPLIT.itemsize == 88 and CLUSTER.itemsize == 72 and NORMAL_SUPPORT.itemsize == 16 and REF_SUPPORT.itemsize == 16

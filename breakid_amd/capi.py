@@ -35,7 +35,7 @@ def build(verbose=False):
 
 EXPORTS = ["bk_init", "bk_prepare_process", "bk_free", "bk_last_error", "bk_set_stream", "bk_sync", "bk_get_stream", "bk_upload_records", "bk_records", "bk_exclude_regions", "bk_isize_stats",
            "bk_discordant_pairs", "bk_mask_and_cluster", "bk_split_evidence", "bk_cluster_summary",
-           "bk_split_breakpoints", "bk_normal_support", "bk_ref_support", "bk_genotype_call", "bk_clip_support", "bk_clip_reads", "bk_base_depth", "bk_clip_rescue", "bk_junctions", "bk_junction_sides", "bk_vcf_breakend_alt", "bk_evidence", "bk_run", "bk_fetch", "bk_timing", "bk_timing_enable", "bk_timing_touched", "bk_group_stats", "bk_qname_hash", "bk_qname_check",
+           "bk_split_breakpoints", "bk_normal_support", "bk_ref_support", "bk_genotype_call", "bk_clip_support", "bk_clip_reads", "bk_base_depth", "bk_clip_rescue", "bk_junctions", "bk_junction_sides", "bk_vcf_breakend_alt", "bk_evidence", "bk_unique_support", "bk_run", "bk_fetch", "bk_timing", "bk_timing_enable", "bk_timing_touched", "bk_group_stats", "bk_qname_hash", "bk_qname_check",
            "bk_bam_open", "bk_bam_header", "bk_bam_decode", "bk_bam_close", "bk_bam_extract", "bk_bam_names_free", "bk_bam_decode_device", "bk_bam_decode_device_part", "bk_bam_decode_device_ctx", "bk_bam_dev_free", "bk_feed_release_caches", "bk_debug_bgzf_inflate", "bk_debug_std_sort", "bk_sort_forms", "bk_debug_ahc", "bk_debug_points", "bk_debug_cigar", "bk_debug_vote", "bk_debug_region", "bk_shard_begin", "bk_shard_get_stats", "bk_shard_set_stats",
            "bk_shard_sd_local", "bk_shard_sd_finish", "bk_shard_buffer", "bk_shard_set_buffer", "bk_shard_group_sizes",
            "bk_shard_own_groups", "bk_shard_route_candidates", "bk_shard_group_keys", "bk_shard_route_pairs", "bk_shard_group_pairs", "bk_shard_bp_cov", "bk_shard_bp_vote", "bk_shard_bp_vote_slice", "bk_shard_bp_set_voted", "bk_shard_bp_depth", "bk_shard_bp_finish"]
@@ -82,6 +82,7 @@ def lib():
         L.bk_junction_sides.argtypes = [vp, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), C.POINTER(C.c_uint8)]
         L.bk_vcf_breakend_alt.argtypes = [C.c_char, C.c_int, C.c_char_p, C.c_uint32, C.c_int, C.c_char_p, C.c_size_t]
         L.bk_evidence.argtypes = [vp, C.POINTER(vp), u64p, C.POINTER(C.POINTER(C.c_uint64))]
+        L.bk_unique_support.argtypes = [vp, C.POINTER(vp), u64p, C.POINTER(C.POINTER(C.c_uint64)), u64p]
         L.bk_fetch.argtypes = [vp, C.c_int, C.POINTER(vp), u64p, C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(C.c_uint32)]
         L.bk_timing.argtypes = [vp, C.POINTER(C.POINTER(C.c_char_p)), C.POINTER(C.POINTER(C.c_float)),
                                 C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(C.c_int)]
@@ -421,6 +422,22 @@ class Context:
         d2, ncl = C.c_void_p(), C.c_uint64()  # call_off has one entry more than STAGE_CLUSTERS has rows
         self._check(self.L.bk_fetch(self.h, abi.STAGE_CLUSTERS, C.byref(d2), C.byref(ncl), None, None))
         return rows, np.ctypeslib.as_array(off, shape=(ncl.value + 1,)).copy()
+
+    def unique_support(self, listing=True):
+        """The unique fragments behind this context's clusters (bk_unique_support): one abi.UNIQUE_SUPPORT row per STAGE_CLUSTERS row
+        and, with `listing`, first[r] = the smallest row of evidence() that is the same fragment as row r: (rows, first), or rows."""
+        data, n, first, n_rows = C.c_void_p(), C.c_uint64(), C.POINTER(C.c_uint64)(), C.c_uint64()
+        if listing:
+            self._check(self.L.bk_unique_support(self.h, C.byref(data), C.byref(n), C.byref(first), C.byref(n_rows)))
+        else:
+            self._check(self.L.bk_unique_support(self.h, C.byref(data), C.byref(n), None, None))
+        rows = np.zeros(0, abi.UNIQUE_SUPPORT)
+        if n.value:
+            buf = (C.c_char * (n.value * abi.UNIQUE_SUPPORT.itemsize)).from_address(data.value)
+            rows = np.frombuffer(buf, dtype=abi.UNIQUE_SUPPORT, count=n.value).copy()
+        if not listing:
+            return rows
+        return rows, (np.ctypeslib.as_array(first, shape=(n_rows.value,)).copy() if n_rows.value else np.zeros(0, np.uint64))
 
     def ref_support(self, records, mapq_min, anchor, w):
         """Reference-allele evidence of this context's calls on the record table of `records` (bk_ref_support): one abi.REF_SUPPORT

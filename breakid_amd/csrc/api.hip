@@ -16,6 +16,7 @@
 #include "clip.h"
 #include "junction.h"
 #include "evidence.h"
+#include "unique.h"
 #include "exclude.h"
 #include "ahc.h"
 #include "lanes.h"
@@ -139,6 +140,10 @@ struct bk_ctx
   EvidenceBufs evb;
   std::vector<struct bk_evidence> f_evidence;
   std::vector<uint64_t> f_ev_off;
+  // unique fragments (bk_unique_support)
+  UniqueBufs uqb;
+  std::vector<struct bk_unique_support> f_unique;
+  std::vector<uint64_t> f_uq_first;
 
   // fetch staging
   std::vector<bk_pair> f_pairs[3];
@@ -1154,6 +1159,63 @@ int bk_evidence(bk_ctx *ctx, const struct bk_evidence **out, uint64_t *count, co
     *out = ctx->f_evidence.data();
     *count = n;
     *call_off = ctx->f_ev_off.data();
+  });
+}
+
+int bk_unique_support(bk_ctx *ctx, const struct bk_unique_support **out, uint64_t *count, const uint64_t **first, uint64_t *n_rows)
+{
+  return guarded(ctx, [&] {
+    if (!out || !count) throw bk_error(BK_ERR_ARG, "bk_unique_support: null output");
+    if (!first != !n_rows) throw bk_error(BK_ERR_ARG, "bk_unique_support: first and n_rows go together (both, or both null for the counts alone)");
+    if (ctx->shard) throw bk_error(BK_ERR_ARG, "bk_unique_support: sharded contexts (bk_shard_*) are not supported");
+    if (!ctx->bp_done || !ctx->clustered || !ctx->summary_map) throw bk_error(BK_ERR_ARG, "bk_unique_support: call bk_split_breakpoints first");
+    const uint64_t ncl = ctx->n_clusters;
+    const bk_soa &t = ctx->rec;
+    if (ncl && (!ctx->have_records || !t.mapq || (!t.side && (!t.qhash || !t.mtid || !t.mpos))))
+      throw bk_error(BK_ERR_ARG, "bk_unique_support: the record table lacks a column (mtid and mpos, or bk_side rows)");
+    const JunctionPairs jp = junction_pairs(ctx);
+    EvidenceRecs er{t.n, t.side, t.qhash, t.qcheck, t.mapq, t.mtid, t.mpos};
+    const bool listing = first != nullptr;
+    struct bk_unique_support *d_res;
+    uint64_t *d_first;
+    EvidenceStat *d_stat;
+    UniqueStat us;
+    {
+      // bytes: what bk_evidence reads to list the rows, and the four key words of every row written once and read once
+      Scope s(ctx, "unique", jp.n * (12ull + 4ull + 2ull * 12ull));
+      unique_support(jp, tuple_table(ctx), ctx->clusters_ptr(), ncl, er, listing, ctx->uqb, ctx->st, &d_res, &d_first, &d_stat, &us);
+    }
+    EvidenceStat stat{};
+    HIP_CHECK(hipMemcpyAsync(&stat, d_stat, sizeof stat, hipMemcpyDeviceToHost, ctx->st));
+    if (listing)
+    {
+      ctx->f_uq_first.resize(us.n_rows);
+      if (us.n_rows) HIP_CHECK(hipMemcpyAsync(ctx->f_uq_first.data(), d_first, us.n_rows * 8, hipMemcpyDeviceToHost, ctx->st));
+    }
+    rows_to_host(ctx, d_res, ncl, ctx->f_unique);
+    if (stat.bad) throw bk_error(BK_ERR_HIP, "bk_unique_support: the listing and the counts of bk_junctions disagree (internal error)");
+    if (ctx->timing && !ctx->timers.empty())
+    {
+      // touched: the listing as in bk_evidence without the rows written (a row's source is read all the same: a 56-byte pair row or
+      // an 88-byte tuple, and a 32-byte sector of the mate columns per split row), the radix passes over the list, then per row:
+      // four key words written (32 B) and read for the OR / AND (32 B), per key word that is sorted a gather (8 B read, 8 B
+      // written, 4 B index), per radix pass 8-byte key + 4-byte index read twice and written once (36 B), the last pass (index, two
+      // rows' key words: 4 + 64 B) and `first`; per call its two offsets read and its row written
+      int bits = 1;
+      while ((ncl >> bits) != 0) ++bits;
+      const uint64_t ev_passes = (uint64_t) (bits + 7) / 8, n = us.n_rows;
+      ctx->timers.back().bytes += n * 64ull;
+      ctx->timers.back().touched = jp.n * (12ull + 32ull) + 2ull * stat.visited * sizeof(bk_split) + ncl * (2ull * sizeof(bk_cluster) + 2ull * sizeof(struct bk_junction) + 20ull) +
+                                   jp.n * (12ull + 12ull + ev_passes * 32ull + 12ull) + n * (64ull + 32ull) +
+                                   n * (64ull + us.gathers * 20ull + us.passes * 36ull + 68ull + (listing ? 8ull : 0ull)) + ncl * (32ull + sizeof(struct bk_unique_support));
+    }
+    *out = ctx->f_unique.data();
+    *count = ncl;
+    if (listing)
+    {
+      *first = ctx->f_uq_first.data();
+      *n_rows = us.n_rows;
+    }
   });
 }
 

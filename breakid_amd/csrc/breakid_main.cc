@@ -39,6 +39,8 @@ extern "C" int bk_junction_sides(const struct bk_junction *j, uint8_t *right1, u
 extern "C" int bk_vcf_breakend_alt(char ref_base, int own_right, const char *mate_chr, uint32_t mate_pos, int mate_right, char *buf, size_t cap) __attribute__((weak));
 // -evidence: the same for the evidence rows (the CPU build refuses -evidence; bk_bam_extract is host code and always there)
 extern "C" int bk_evidence(bk_ctx *ctx, const struct bk_evidence **out, uint64_t *count, const uint64_t **call_off) __attribute__((weak));
+// -dedup: the same for the unique fragments behind every call (the CPU build refuses -dedup)
+extern "C" int bk_unique_support(bk_ctx *ctx, const struct bk_unique_support **out, uint64_t *count, const uint64_t **first, uint64_t *n_rows) __attribute__((weak));
 // -clip: the same for the soft-clip evidence, the depth at the rescued positions and the rescue rule (the CPU build refuses -clip)
 extern "C" int bk_clip_support(bk_ctx *calls, bk_ctx *records, int mapq_min, int min_clip, double w, const struct bk_clip_support **out, uint64_t *count)
     __attribute__((weak));
@@ -286,6 +288,7 @@ static const char *HELP =
      \t -anchor    \t bases a reference read must cover on either side of a breakpoint (with -genotype)  [10]\n \
      \t -vcf       \t also write the calls as VCF breakends (*_fusion.vcf)  \n \
      \t -evidence  \t also list the reads behind every call (*_evidence.txt) and write them as a BAM (*_evidence.bam)  \n \
+     \t -dedup     \t count the different fragments behind every call (twin files *_dedup.txt; UPE / USR with -vcf, a Dup column with -evidence)  \n \
      \t -clip      \t count soft-clipped reads without an SA tag at every call (twin files *_clip.txt) and rescue clusters the vote left out (*_fusion_rescued.txt)  \n \
      \t -minclip   \t shortest soft clip that counts (with -clip)  [10]\n \
      \t -clipsupport \t clipped reads at one position that each side of a rescued cluster needs (with -clip)  [3]\n ";
@@ -588,6 +591,8 @@ static const char *GENOTYPE_COLUMNS_NORMAL =
 // -clip: the twin files' columns, and behind them those of the normal
 static const char *CLIP_COLUMNS = "\tClip1\tClip2\tClipPeak1\tClipPeakN1\tClipPeak2\tClipPeakN2\tClipBg1\tClipBg2";
 static const char *CLIP_COLUMNS_NORMAL = "\tNormal_Clip1\tNormal_Clip2";
+// -dedup: the twin files' columns (bk_unique_support: fragments among the N_DRP rows and the N_SR tuples, and the rows of the largest one)
+static const char *DEDUP_COLUMNS = "\tUniq_DRP\tUniq_SR\tTop_DRP\tTop_SR";
 // -clip -normal: what _fusion_rescued_normal.txt adds to a row of _fusion_rescued.txt
 static const char *RESCUED_COLUMNS_NORMAL = "\tNormal_DRP\tNormal_ClipAt1\tNormal_ClipAt2\tNormal_Depth1\tNormal_Depth2";
 
@@ -625,6 +630,7 @@ struct VcfInput
   // _fusion_rescued.vcf (else null): `rows` are the rescued clusters, rescued[k] belongs to rows[k]; the records get INFO/SC and a
   // third sample field CV, the clipped reads of the side, and are never genotyped
   const vector<RescuedCall> *rescued = nullptr;
+  const vector<struct bk_unique_support> *usup = nullptr;  // -dedup (else null; never for the rescued clusters): INFO/UPE and INFO/USR, last
 };
 
 static char nib_base(const string &nib_dir, const string &chr, long pos1)  // the base at a 1-based position; N without a file or beyond it
@@ -681,7 +687,7 @@ static bool write_vcf(const string &path, const vector<OutRow> &rows, const VcfI
     if (rc ? !rescued_written(r, in.all) : !call_written(r, in.all)) continue;
     const bool no_gene_pair = call_no_gene_pair(r), filt_ok = rc ? !no_gene_pair && !r.is_rpt : call_filt_ok(r);
     if (r.idx >= in.jsup->size() || (in.with_normal && !rc && r.idx >= in.n_nsup) || (in.gsup && r.idx >= in.gsup->size()) ||
-        (in.gsup_normal && r.idx >= in.gsup_normal->size()))
+        (in.gsup_normal && r.idx >= in.gsup_normal->size()) || (in.usup && !rc && r.idx >= in.usup->size()))
       return false;
     const struct bk_junction &j = (*in.jsup)[r.idx];
     uint8_t right[2] = {0, 1}, source = 0;
@@ -702,6 +708,7 @@ static bool write_vcf(const string &path, const vector<OutRow> &rows, const VcfI
       o << "SVTYPE=BND;MATEID=" << id << "_" << 2 - s << ";EVENTTYPE=" << fusion_type(r.c.type_mask) << ";PE=" << r.c.n_drp << ";SR=" << r.c.n_sr
         << ";MAPQ=" << (n_members ? (s ? j.mapq_sum2 : j.mapq_sum1) / n_members : 0) << ";DP=" << (s ? r.c.depth2 : r.c.depth1) << ";GENE=" << vcf_info_text(s ? r.g2 : r.g1)
         << ";SIDES=" << (source == 2 ? "SR" : source == 1 ? "PE" : "NONE");
+      if (in.usup && !rc) o << ";UPE=" << (*in.usup)[r.idx].uniq_pairs << ";USR=" << (*in.usup)[r.idx].uniq_splits;
       if (rc)
       {
         o << ";SC=" << rc->peak_n[s] << "\tDV:RV:CV\t" << vcf_sample(r.c.n_drp, 0, nullptr, s) << ":" << rc->peak_n[s];
@@ -739,6 +746,9 @@ static bool write_vcf(const string &path, const vector<OutRow> &rows, const VcfI
        "##INFO=<ID=DP,Number=1,Type=Integer,Description=\"Read depth at this breakpoint\">\n"
        "##INFO=<ID=GENE,Number=1,Type=String,Description=\"Gene at this breakpoint, or intergenic\">\n"
        "##INFO=<ID=SIDES,Number=1,Type=String,Description=\"Evidence the breakend orientation comes from: SR split reads, PE read pairs, NONE\">\n";
+  if (in.usup && !in.rescued)
+    v << "##INFO=<ID=UPE,Number=1,Type=Integer,Description=\"Different fragments among the discordant read pairs of the call\">\n"
+         "##INFO=<ID=USR,Number=1,Type=Integer,Description=\"Different fragments among the split-read alignments of the call\">\n";
   if (in.rescued) v << "##INFO=<ID=SC,Number=1,Type=Integer,Description=\"Soft-clipped reads without an SA tag that end at this position (the clip peak)\">\n";
   if (in.gsup)
     v << "##FORMAT=<ID=GT,Number=1,Type=String,Description=\"Genotype\">\n"
@@ -765,6 +775,7 @@ struct EvidenceInput
   bool all = false;  // -all: the calls of _fusion_all.txt
   const vector<struct bk_evidence> *rows = nullptr;
   const vector<uint64_t> *call_off = nullptr;  // per BK_STAGE_CLUSTERS row, one more entry than rows
+  const vector<uint64_t> *first = nullptr;     // -dedup (else null): bk_unique_support's first[], a last column Dup in _evidence.txt
 };
 
 // One listed read of a call: the hashes of its name, and the call (bk<call>) it stands behind
@@ -873,14 +884,20 @@ static bool write_evidence(const string &prefix, const string &inp_bam, const ve
   vector<ReadRef> refs;
   for (uint64_t c : calls)
     for (uint64_t i = (*in.call_off)[c]; i < (*in.call_off)[c + 1]; ++i) refs.push_back(ReadRef{(*in.rows)[i].qhash, (*in.rows)[i].qcheck, c});
+  if (in.first && in.first->size() != in.rows->size())
+  {
+    why = "the unique-support listing does not cover every evidence row";
+    return false;
+  }
   ReadNames rn;
   if (!extract_reads(inp_bam, prefix + "_evidence.bam", refs, rn, why)) return false;
   std::ofstream o((prefix + "_evidence.txt").c_str());
-  o << EVIDENCE_HEADER << "\n";
+  o << EVIDENCE_HEADER << (in.first ? "\tDup" : "") << "\n";
   for (uint64_t c : calls)
     for (uint64_t i = (*in.call_off)[c]; i < (*in.call_off)[c + 1]; ++i)
     {
       write_evidence_line(o, c, (*in.rows)[i], rn, in);
+      if (in.first) o << "\t" << ((*in.first)[i] == i ? 0 : 1);  // 0 on a fragment's first line
       o << "\n";
     }
   return close_evidence(o, prefix + "_evidence.txt", prefix + "_evidence.bam", why);
@@ -978,11 +995,11 @@ int main(int argc, char *argv[])
                                      {"fast", 0, 0, 5},   {"t", 0, 0, 6}, {"all", 0, 0, 7}, {"gpu", 1, 0, 8}, {"gpus", 1, 0, 9},
                                      {"comm", 1, 0, 10},  {"normal", 1, 0, 11}, {"x", 1, 0, 12}, {"genotype", 0, 0, 13},
                                      {"anchor", 1, 0, 14}, {"vcf", 0, 0, 15}, {"evidence", 0, 0, 16}, {"clip", 0, 0, 17},
-                                     {"minclip", 1, 0, 18}, {"clipsupport", 1, 0, 19}, {0, 0, 0, 0}};
+                                     {"minclip", 1, 0, 18}, {"clipsupport", 1, 0, 19}, {"dedup", 0, 0, 20}, {0, 0, 0, 0}};
   string inp_file, out_file, nib_dir, normal_file, exclude_file, build = "hg19";
   int qual = 20, device = 0, n_gpus = 0, transport = BK_TRANSPORT_AUTO;  // -gpus N: one sample over N GPUs (include/breakid_multi.h)
   bool fast = false, filter = true, genotype = false, anchor_given = false, vcf = false, evidence = false;
-  bool clip = false, minclip_given = false, clipsupport_given = false;
+  bool clip = false, minclip_given = false, clipsupport_given = false, dedup = false;
   long min_clip = 10, clip_support = 3;  // -minclip: shortest clip that counts; -clipsupport: reads at one position a rescued side needs
   long anchor = 10;  // -anchor: bases a reference read must cover on either side of the breakpoint base
   int opt, li;
@@ -1020,6 +1037,7 @@ int main(int argc, char *argv[])
       clip_support = atol(optarg);
       clipsupport_given = true;
       break;
+    case 20: dedup = true; break;
     default: std::cerr << "Error: cannot parse arguments.\n"; exit(1);
     }
   }
@@ -1099,6 +1117,19 @@ int main(int argc, char *argv[])
     if (!bk_evidence)
     {
       std::cerr << "Error: -evidence needs the GPU library" << std::endl;
+      exit(1);
+    }
+  }
+  if (dedup)
+  {
+    if (n_gpus >= 1)
+    {
+      std::cerr << HELP << "Error: -dedup cannot be combined with -gpus.\n";
+      exit(1);
+    }
+    if (!bk_unique_support)
+    {
+      std::cerr << "Error: -dedup needs the GPU library" << std::endl;
       exit(1);
     }
   }
@@ -1432,6 +1463,23 @@ int main(int argc, char *argv[])
     ev_rows.assign(ev, ev + n_ev);
     ev_off.assign(off, off + cnt + 1);
   }
+  // -dedup: the different fragments among those rows, per call, and for every row the first row of its fragment
+  vector<struct bk_unique_support> usup;
+  vector<uint64_t> ufirst;
+  if (dedup)
+  {
+    const struct bk_unique_support *us = nullptr;
+    const uint64_t *first = nullptr;
+    uint64_t n_us = 0, n_first = 0;
+    if ((rc = bk_unique_support(ctx, &us, &n_us, &first, &n_first)) != BK_OK) die(rc);
+    usup.assign(us, us + n_us);
+    ufirst.assign(first, first + n_first);
+    if (n_us != cnt)
+    {
+      std::cerr << "Error: the unique-support table does not cover every cluster" << std::endl;
+      exit(1);
+    }
+  }
   if (multi)
   {
     n_valid = 0;
@@ -1591,16 +1639,23 @@ int main(int argc, char *argv[])
   std::ofstream out, outf, out_n, outf_n;  // (_n: the twins with the matched normal's four counts)
   std::ofstream out_g, outf_g;             // (_g: the twins with the genotype columns, -genotype)
   std::ofstream out_c, outf_c, out_r;      // (_c: the twins with the clip columns, _r: the rescued clusters, -clip)
+  std::ofstream out_d, outf_d;             // (_d: the twins with the unique-support columns, -dedup)
   const bool with_normal = !normal_file.empty();  // (a tumour without calls still gets header-only twins)
   const string header_n = string(HEADER, strlen(HEADER) - 1) + NORMAL_COLUMNS;
   string header_g = string(HEADER, strlen(HEADER) - 1) + GENOTYPE_COLUMNS;
   if (with_normal) header_g += string(NORMAL_COLUMNS, strlen(NORMAL_COLUMNS) - 1) + GENOTYPE_COLUMNS_NORMAL;
   header_g += "\n";
   const string header_c = string(HEADER, strlen(HEADER) - 1) + CLIP_COLUMNS + (with_normal ? CLIP_COLUMNS_NORMAL : "") + "\n";
+  const string header_d = string(HEADER, strlen(HEADER) - 1) + DEDUP_COLUMNS + "\n";
   if (!filter)
   {
     out.open((out_file + "_fusion_all.txt").c_str());
     out << HEADER;
+    if (dedup)
+    {
+      out_d.open((out_file + "_fusion_all_dedup.txt").c_str());
+      out_d << header_d;
+    }
     if (with_normal)
     {
       out_n.open((out_file + "_fusion_all_normal.txt").c_str());
@@ -1619,6 +1674,11 @@ int main(int argc, char *argv[])
   }
   outf.open((out_file + "_fusion.txt").c_str());
   outf << HEADER;
+  if (dedup)
+  {
+    outf_d.open((out_file + "_fusion_dedup.txt").c_str());
+    outf_d << header_d;
+  }
   if (with_normal)
   {
     outf_n.open((out_file + "_fusion_normal.txt").c_str());
@@ -1670,6 +1730,15 @@ int main(int argc, char *argv[])
     }
     if (filt_ok) write_row(outf, r);
     if (!filter && all_ok) write_row(out, r);
+    if (dedup && r.idx < usup.size())
+    {
+      const struct bk_unique_support &u = usup[r.idx];
+      std::ostringstream tail;
+      tail << "\t" << u.uniq_pairs << "\t" << u.uniq_splits << "\t" << u.top_pairs << "\t" << u.top_splits;
+      const string t = tail.str();
+      if (filt_ok) write_row(outf_d, r, nullptr, nullptr, nullptr, nullptr, &t);
+      if (!filter && all_ok) write_row(out_d, r, nullptr, nullptr, nullptr, nullptr, &t);
+    }
     if (with_normal && r.idx < n_nsup)
     {
       if (filt_ok) write_row(outf_n, r, &nsup[r.idx]);
@@ -1700,6 +1769,11 @@ int main(int argc, char *argv[])
     if (!filter) out_c.close();
     outf_c.close();
   }
+  if (dedup)
+  {
+    if (!filter) out_d.close();
+    outf_d.close();
+  }
   if (vcf)
   {
     VcfInput vi;
@@ -1714,6 +1788,7 @@ int main(int argc, char *argv[])
     vi.n_nsup = n_nsup;
     vi.gsup = genotype ? &gsup : nullptr;
     vi.gsup_normal = genotype && with_normal ? &gsup_normal : nullptr;
+    vi.usup = dedup ? &usup : nullptr;
     if (!write_vcf(out_file + "_fusion.vcf", rows, vi))
     {
       std::cerr << "Error: cannot write " << out_file << "_fusion.vcf: the evidence tables do not cover every call" << std::endl;
@@ -1722,6 +1797,7 @@ int main(int argc, char *argv[])
     if (clip)
     {
       vi.gsup = vi.gsup_normal = nullptr;  // rescued calls are not genotyped
+      vi.usup = nullptr;                   // ... and their files stay as they are with -dedup
       vi.rescued = &rescued_calls;
       if (!write_vcf(out_file + "_fusion_rescued.vcf", rescued, vi))
       {
@@ -1738,6 +1814,7 @@ int main(int argc, char *argv[])
     ei.all = !filter;
     ei.rows = &ev_rows;
     ei.call_off = &ev_off;
+    ei.first = dedup ? &ufirst : nullptr;
     string why;
     if (!write_evidence(out_file, inp_file, rows, ei, why))
     {
@@ -1765,6 +1842,7 @@ int main(int argc, char *argv[])
     if (evidence) p << "evidence\t1" << std::endl;
     if (clip) p << "clip_min_length\t" << min_clip << std::endl;
     if (clip) p << "clip_min_support\t" << clip_support << std::endl;
+    if (dedup) p << "dedup\t1" << std::endl;
   }
   clock_t end = clock();
   std::cout << "the fusion process of file " << inp_file << "  costs time: " << (end - start) / double(CLOCKS_PER_SEC) << " seconds" << std::endl;

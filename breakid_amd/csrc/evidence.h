@@ -20,6 +20,21 @@ struct EvidenceRecs
   const uint64_t *qhash;
   const uint32_t *qcheck;
   const uint8_t *mapq;
+  const int32_t *mtid = nullptr, *mpos = nullptr;  // only the fragment keys read them (EvidenceKeys), and only without `side`
+};
+
+// The fragment key of every row (bk_unique_support, include/breakid_hip.h), written by the kernels that list the rows so that
+// membership, order and side assignment are stated once.  Four columns of `n` words each at d + j * n, word j of row r:
+//   pair   0: p1_pos << 32 | p2_pos   1: 2 * (p1_rev != 0) + (p2_rev != 0)   2: 0
+//   split  0: A1_start << 32 | A1_end   1: A2_start << 32 | A2_end   2: mtid << 32 | mpos of record `rec` (A1 = prim unless swapped)
+//   both   3: call << 1 | (kind == BK_EV_SPLIT): ascending in r
+// evidence() sizes `w` once it knows the row count and leaves `d` and `n` behind; with keys_only the rows themselves are not written.
+struct EvidenceKeys
+{
+  DevBuf w;
+  uint64_t *d = nullptr;
+  uint64_t n = 0;
+  bool keys_only = true;
 };
 
 // what the kernels report besides the rows (read back after the call)
@@ -31,6 +46,7 @@ struct EvidenceStat
 };
 
 // Rows in their final order (include/breakid_hip.h) in *rows_out, call_off_out[ncl + 1] over the rows of `cl` (BK_STAGE_CLUSTERS
-// order: bp.hip, cluster_summary), both device arrays owned by `b`.  *stat_out: device, one entry.
+// order: bp.hip, cluster_summary), both device arrays owned by `b`.  *stat_out: device, one entry.  keys != nullptr: the fragment
+// keys as well (above).
 void evidence(const JunctionPairs &p, const TupleTable &tt, const bk_cluster *cl, uint64_t ncl, const EvidenceRecs &recs, EvidenceBufs &b, hipStream_t st,
-              struct bk_evidence **rows_out, uint64_t **call_off_out, EvidenceStat **stat_out);
+              struct bk_evidence **rows_out, uint64_t **call_off_out, EvidenceStat **stat_out, EvidenceKeys *keys = nullptr);

@@ -58,7 +58,7 @@ __global__ __launch_bounds__(256) void k_ev_pair_keys(JunctionPairs in, uint32_t
 
 __global__ __launch_bounds__(256) void k_ev_emit_pairs(JunctionPairs in, const uint64_t *__restrict__ keys, const uint32_t *__restrict__ vals, uint32_t ncl,
                                                        const uint64_t *__restrict__ call_off, const uint64_t *__restrict__ pair_off, EvidenceRecs recs,
-                                                       struct bk_evidence *__restrict__ rows, uint64_t n_rows, EvidenceStat *__restrict__ stat)
+                                                       struct bk_evidence *__restrict__ rows, uint64_t n_rows, EvidenceStat *__restrict__ stat, uint64_t *__restrict__ kw)
 {
   const uint64_t i = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= in.n) return;
@@ -73,6 +73,14 @@ __global__ __launch_bounds__(256) void k_ev_emit_pairs(JunctionPairs in, const u
     return;
   }
   const bk_pair pr = in.pairs[in.idx[p]];
+  if (kw)  // (the fragment key of the row: evidence.h)
+  {
+    kw[dest] = (uint64_t) pr.p1_pos << 32 | pr.p2_pos;
+    kw[n_rows + dest] = 2u * (pr.p1_rev ? 1u : 0u) + (pr.p2_rev ? 1u : 0u);
+    kw[2 * n_rows + dest] = 0;
+    kw[3 * n_rows + dest] = c << 1;
+  }
+  if (!rows) return;
   struct bk_evidence v;
   v.rec = pr.rec;
   v.qhash = 0;
@@ -110,7 +118,7 @@ __global__ __launch_bounds__(256) void k_ev_emit_pairs(JunctionPairs in, const u
 // matches come in ascending BK_STAGE_SPLITS row; sides as in k_junction_sr.
 __global__ __launch_bounds__(256) void k_ev_emit_splits(TupleTable tt, const bk_cluster *__restrict__ cl, uint32_t ncl, const uint64_t *__restrict__ call_off,
                                                         const uint64_t *__restrict__ pair_off, EvidenceRecs recs, struct bk_evidence *__restrict__ rows, uint64_t n_rows,
-                                                        EvidenceStat *__restrict__ stat)
+                                                        EvidenceStat *__restrict__ stat, uint64_t *__restrict__ kw)
 {
   const uint32_t c = blockIdx.x * 4 + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
@@ -169,26 +177,45 @@ __global__ __launch_bounds__(256) void k_ev_emit_splits(TupleTable tt, const bk_
         else
         {
           const bool swapped = side == 2;
-          struct bk_evidence v;
-          v.rec = s.rec;
-          v.qhash = s.qhash;
-          v.qcheck = s.qcheck;
-          v.call = c;
-          v.tid1 = k.p1_tid;
-          v.pos1 = swapped ? s.sec_bp : s.prim_bp;
-          v.tid2 = k.p2_tid;
-          v.pos2 = swapped ? s.prim_bp : s.sec_bp;
-          v.flag1 = (uint16_t) (s.flags & 0xFFFFu);
-          v.flag2 = swapped ? 1 : 0;
-          v.mapq1 = 0;
-          if (s.rec < recs.n)
-            v.mapq1 = recs.mapq[s.rec];
-          else
-            stat->bad = 1u;
-          v.mapq2 = 0;
-          v.kind = BK_EV_SPLIT;
-          v.sides = (uint8_t) split_sides(s, swapped);
-          store_row(rows + dest, v);
+          if (kw)  // (the fragment key of the row: evidence.h)
+          {
+            int32_t mt = 0, mp = 0;
+            if (s.rec < recs.n)
+            {
+              mt = recs.side ? recs.side[s.rec].mtid : recs.mtid[s.rec];
+              mp = recs.side ? recs.side[s.rec].mpos : recs.mpos[s.rec];
+            }
+            else
+              stat->bad = 1u;
+            const uint64_t prim = (uint64_t) s.prim_start << 32 | s.prim_end, sec = (uint64_t) s.sec_start << 32 | s.sec_end;
+            kw[dest] = swapped ? sec : prim;
+            kw[n_rows + dest] = swapped ? prim : sec;
+            kw[2 * n_rows + dest] = (uint64_t) (uint32_t) mt << 32 | (uint32_t) mp;
+            kw[3 * n_rows + dest] = (uint64_t) c << 1 | 1u;
+          }
+          if (rows)
+          {
+            struct bk_evidence v;
+            v.rec = s.rec;
+            v.qhash = s.qhash;
+            v.qcheck = s.qcheck;
+            v.call = c;
+            v.tid1 = k.p1_tid;
+            v.pos1 = swapped ? s.sec_bp : s.prim_bp;
+            v.tid2 = k.p2_tid;
+            v.pos2 = swapped ? s.prim_bp : s.sec_bp;
+            v.flag1 = (uint16_t) (s.flags & 0xFFFFu);
+            v.flag2 = swapped ? 1 : 0;
+            v.mapq1 = 0;
+            if (s.rec < recs.n)
+              v.mapq1 = recs.mapq[s.rec];
+            else
+              stat->bad = 1u;
+            v.mapq2 = 0;
+            v.kind = BK_EV_SPLIT;
+            v.sides = (uint8_t) split_sides(s, swapped);
+            store_row(rows + dest, v);
+          }
         }
       }
       n_out += (uint64_t) __popcll(m);
@@ -205,13 +232,18 @@ __global__ __launch_bounds__(256) void k_ev_emit_splits(TupleTable tt, const bk_
 }  // namespace
 
 void evidence(const JunctionPairs &p, const TupleTable &tt, const bk_cluster *cl, uint64_t ncl, const EvidenceRecs &recs, EvidenceBufs &b, hipStream_t st,
-              struct bk_evidence **rows_out, uint64_t **call_off_out, EvidenceStat **stat_out)
+              struct bk_evidence **rows_out, uint64_t **call_off_out, EvidenceStat **stat_out, EvidenceKeys *keys)
 {
   uint64_t *call_off = b.call_off.as<uint64_t>(ncl + 1);
   EvidenceStat *stat = b.stat.as<EvidenceStat>(1);
   *call_off_out = call_off;
   *stat_out = stat;
   *rows_out = b.rows.as<struct bk_evidence>(1);
+  if (keys)
+  {
+    keys->d = nullptr;
+    keys->n = 0;
+  }
   HIP_CHECK(hipMemsetAsync(stat, 0, sizeof(EvidenceStat), st));
   if (ncl == 0)
   {
@@ -232,9 +264,16 @@ void evidence(const JunctionPairs &p, const TupleTable &tt, const bk_cluster *cl
   uint64_t total = 0;
   HIP_CHECK(hipMemcpyAsync(&total, call_off + ncl, 8, hipMemcpyDeviceToHost, st));
   HIP_CHECK(hipStreamSynchronize(st));  // the row count sizes the output
-  struct bk_evidence *rows = b.rows.as<struct bk_evidence>(total + 1);
-  *rows_out = rows;
+  const bool keys_only = keys && keys->keys_only;
+  struct bk_evidence *rows = keys_only ? nullptr : b.rows.as<struct bk_evidence>(total + 1);
+  if (!keys_only) *rows_out = rows;
   if (total == 0) return;
+  uint64_t *kw = nullptr;
+  if (keys)
+  {
+    kw = keys->d = keys->w.as<uint64_t>(4 * total);
+    keys->n = total;
+  }
   if (p.n)
   {
     uint64_t *keys = b.keys.as<uint64_t>(p.n);
@@ -243,7 +282,7 @@ void evidence(const JunctionPairs &p, const TupleTable &tt, const bk_cluster *cl
     int bits = 1;
     while ((ncl >> bits) != 0) ++bits;  // keys are 0 .. ncl
     prims::radix_sort_pairs(keys, vals, p.n, 0, bits, b.radix, st, &keys, &vals);
-    hipLaunchKernelGGL(k_ev_emit_pairs, dim3(cdiv(p.n, 256)), dim3(256), 0, st, p, keys, vals, n32, call_off, pair_off, recs, rows, total, stat);
+    hipLaunchKernelGGL(k_ev_emit_pairs, dim3(cdiv(p.n, 256)), dim3(256), 0, st, p, keys, vals, n32, call_off, pair_off, recs, rows, total, stat, kw);
   }
-  hipLaunchKernelGGL(k_ev_emit_splits, dim3(cdiv(ncl, 4)), dim3(256), 0, st, tt, cl, n32, call_off, pair_off, recs, rows, total, stat);
+  hipLaunchKernelGGL(k_ev_emit_splits, dim3(cdiv(ncl, 4)), dim3(256), 0, st, tt, cl, n32, call_off, pair_off, recs, rows, total, stat, kw);
 }

@@ -403,6 +403,33 @@ struct bk_evidence {
  * call_off has its one entry, 0. */
 int bk_evidence(bk_ctx *ctx, const struct bk_evidence **out, uint64_t *count, const uint64_t **call_off);
 
+/* ---- unique support: how many different fragments stand behind every call ---------------------------------------------------
+ * n_drp and n_sr count rows: a PCR duplicate that the BAM does not mark (0x400) counts again, the isolation and clustering stages
+ * keep some pairs twice, and a split read whose two alignments both carry an SA tag gives two tuples.  bk_unique_support groups the
+ * rows of bk_evidence by fragment.  Membership, order and side assignment are exactly those of bk_evidence (above); row r below
+ * is row r of what bk_evidence would return.
+ * Fragment key, compared as exact integers (no hash decides that two rows are equal):
+ *   BK_EV_PAIR row of member pair p    (p1_pos, p2_pos, p1_rev != 0, p2_rev != 0)
+ *   BK_EV_SPLIT row of tuple t         (A1_start, A1_end, A2_start, A2_end, mtid[t.rec], mpos[t.rec]): A1, A2 = the tuple's prim_* and
+ *                                      sec_* start and end, A1 = prim unless the row is swapped (the row's flag2); mtid / mpos of
+ *                                      record t.rec of the context's table (from the bk_side row when the table has them).  Both
+ *                                      tuples of one read give the same key; the mate position separates fragments that share a
+ *                                      read start.
+ * Two rows are the same fragment when they have the same call, the same kind and equal keys.  first[r] = the smallest row index of
+ * r's fragment (first[first[r]] == first[r] <= r); n_rows = bk_evidence's count.
+ * Per BK_STAGE_CLUSTERS row, for pair rows and for split rows: uniq_* = the number of fragments (rows with first[r] == r), top_* =
+ * the rows of the largest fragment (0 without rows).  An unvoted row has no split rows: uniq_splits = top_splits = 0.
+ * Limits: positions are leftmost alignment starts, not unclipped 5' ends, so duplicates that differ in soft clipping stay apart
+ * (the count errs towards more fragments); a pair row and a split row of one fragment are counted each in its own column.
+ * The struct has no typedef: the name belongs to the call below. */
+struct bk_unique_support { uint32_t uniq_pairs, top_pairs, uniq_splits, top_splits; }; /* 16 bytes */
+/* ctx, call order, errors and table forms: as for bk_evidence; it needs no earlier bk_evidence call, leaves the buffers bk_evidence
+ * returned valid and unchanged, and changes nothing a later bk_fetch or stage returns.  *out (*count = n_clusters rows) and *first
+ * (*n_rows entries) are library-owned until the next bk_unique_support or bk_free(ctx).  first == NULL and n_rows == NULL asks for
+ * the counts alone; exactly one of them null is BK_ERR_ARG, as are null out / count, shards, wrong call order, and a table with
+ * clusters but neither mtid / mpos columns nor bk_side rows.  A context without clusters is no error: *count = 0, *n_rows = 0. */
+int bk_unique_support(bk_ctx *ctx, const struct bk_unique_support **out, uint64_t *count, const uint64_t **first, uint64_t *n_rows);
+
 /* Copy a stage's result to library-owned host memory.  *data stays valid until the next bk_fetch
  * of the same stage or bk_free.  group_off (may be NULL) receives n_groups+1 offsets for pair stages. */
 int bk_fetch(bk_ctx *ctx, int stage, const void **data, uint64_t *count, const uint64_t **group_off, uint32_t *n_groups);
