@@ -15,12 +15,12 @@
 // stage.  So the budget is decided from the count the runtime started with, before any stream or persistent kernel of the stage
 // exists:
 //   service   LANE_STREAMS_MAX streams of the lanes + the two persistent kernels' streams + the copy stream of the quit word
-//             (SortService::start) = 7 queues; below that nothing of the service is started (the stage sorts by launches)
+//             (SortService::start) = 7 queues; below that nothing of the service is started (every sort of the stage is one task
+//             dispatch on its lane's stream: the launch path)
 //   launches  one queue stays with the process's first stream (the null stream of torch and of the runtime's copies: the kernel
 //             trace at 4 queues shows it on a queue of its own, and the stage's fourth stream sharing a queue with another lane);
-//             a lane sorts on its own stream and forks the big heaps of each sort onto a side stream only when the other queues
-//             allow two per lane (SortEmuBufs::fork_heaps; without the fork all heaps of a sort are one dispatch); no more lanes
-//             than streams that get a queue each.  At ROCm's four queues that is three lanes with one stream each
+//             a lane has one stream and sorts on it; no more lanes than streams that get a queue each.  At ROCm's four queues
+//             that is three lanes
 static int g_hw_queues_at_init = 0;
 void stage_set_hw_queues(int n) { g_hw_queues_at_init = n; }
 
@@ -34,13 +34,6 @@ constexpr int LANE_STREAMS_MAX = 4;
 constexpr int SVC_STAGE_QUEUES = LANE_STREAMS_MAX + 3;
 static bool lane_service(int fast) { return sort_service_on() && fast && g_hw_queues_at_init >= SVC_STAGE_QUEUES; }
 static int stage_queues() { return std::max(1, g_hw_queues_at_init - 1); }
-// streams per lane of the launch path: 2 (own + side stream for the big heaps) or 1; BREAKID_LANE_STREAMS=1 / 2 overrides
-static int lane_streams_each(int K)
-{
-  static const int want = getenv("BREAKID_LANE_STREAMS") ? atoi(getenv("BREAKID_LANE_STREAMS")) : 0;
-  if (want == 1 || want == 2) return want;
-  return stage_queues() >= 2 * K ? 2 : 1;
-}
 static int lanes_wanted(bool svc)
 {
   // with the resident sort service a lane's sort is a submit and a wait of its thread, so there can be a lane for every one or two
@@ -50,12 +43,11 @@ static int lanes_wanted(bool svc)
   static const int want_svc = env ? atoi(env) : 12;
   if (svc) return want_svc < 1 ? 1 : (want_svc > 26 ? 26 : want_svc);
   // four lanes unless the caller says otherwise (BREAKID_GROUP_LANES=1: one pass); lanes_apply decides from the data whether they
-  // pay.  Measured on the 30x WGS shape with the segment-per-workgroup tail of the level loop: 2 lanes 42.0 ms, 3 lanes 42.6,
-  // 4 lanes 39.6, 5 lanes 48.5 (more lanes shorten a lane's "longest heap of any of its groups" per sort, and cost a level loop,
-  // a ranking and a finisher chain of their own, each ~100 launches that wait for each other across lanes).  Without an explicit
-  // count no more lanes than hardware queues: a lane whose next small kernel sits behind another lane's heap on a shared queue
-  // waits for that heap.
-  static const int want = env ? atoi(env) : std::max(1, std::min(4, stage_queues() / lane_streams_each(std::min(4, stage_queues()))));
+  // pay.  Measured on the 30x WGS shape when a sort was still a chain of launches: 2 lanes 42.0 ms, 3 lanes 42.6, 4 lanes 39.6,
+  // 5 lanes 48.5 (more lanes shorten a lane's "longest heap of any of its groups" per sort, and each costs the stage's other
+  // launches once more).  Without an explicit count no more lanes than hardware queues (min(4, stage_queues())): a lane whose next
+  // small kernel sits behind another lane's sort on a shared queue waits for that sort.
+  static const int want = env ? atoi(env) : std::min(4, stage_queues());
   return want < 1 ? 1 : (want > 26 ? 26 : want);
 }
 static bool lanes_apply(const StageInput &in, int fast)
@@ -70,7 +62,7 @@ static bool lanes_apply(const StageInput &in, int fast)
   {
     static bool told = false;
     const int K = lanes_wanted(lane_service(fast));
-    if (!told && !lane_service(fast) && K * lane_streams_each(K) > stage_queues() && bk_debug("lanes"))
+    if (!told && !lane_service(fast) && K > stage_queues() && bk_debug("lanes"))
     {
       told = true;
       fprintf(stderr, "[breakid] GPU_MAX_HW_QUEUES=%d: the lanes of chromosome-pair groups (bk_mask_and_cluster) and their heap kernels will share hardware queues "
@@ -461,17 +453,10 @@ static void group_lanes(ClusterStage &cs, const StageInput &in, double w, int fa
     S = K;
     make_lanes(K, S);
   }
-  // launch path: the big heaps of a lane's sorts on a side stream of its own only when every lane can have two queues
-  struct ForkReset
+  if (!use_svc && bk_debug("lanes"))
   {
-    ClusterBufs &cb;
-    ~ForkReset() { cb.se.fork_heaps = true; }
-  } fork_reset{cs.cb()};
-  {
-    const bool fork = use_svc || lane_streams_each(K) == 2;
-    for (int k = 0; k < K; ++k) cs.lanes[k]->cb.se.fork_heaps = fork;
-    if (!use_svc && bk_debug("lanes")) fprintf(stderr, "[lanes] launch path: %d lanes, %d stream%s each, %d hardware queues\n", K, fork ? 2 : 1, fork ? "s" : "", g_hw_queues_at_init);
-    if (!use_svc && sort_tasks_on() && bk_debug("lanes")) fprintf(stderr, "[lanes] sorts as task dispatches on the lane streams\n");
+    fprintf(stderr, "[lanes] launch path: %d lanes, 1 stream each, %d hardware queues\n", K, g_hw_queues_at_init);
+    fprintf(stderr, "[lanes] sorts as task dispatches on the lane streams\n");
   }
   auto lane = [&](int l) -> ClusterStage::Lane & { return *cs.lanes[l]; };
   auto lane_st = [&](int l) { const int k = l % S; return k == 0 ? in.st : cs.lanes[k]->st; };
@@ -628,11 +613,9 @@ void ClusterStage::run(const StageInput &in, double w, int fast)
 
 void ClusterStage::sort_forms(uint64_t out[3]) const
 {
-  for (int k = 0; k < 3; ++k)
-  {
-    out[k] = 0;
-    for (const auto &l : lanes) out[k] += l->cb.se.sorts[k];
-  }
+  out[0] = out[1] = out[2] = 0;  // (out[2] counted a form that no longer exists)
+  for (const auto &l : lanes)
+    for (int k = 0; k < 2; ++k) out[k] += l->cb.se.sorts[k];
 }
 
 void ClusterStage::debug_sort(int device, hipStream_t st, uint32_t *key, uint32_t *idx, const uint32_t *gof, const uint64_t *goff, uint32_t ng, uint64_t n, uint64_t max_group)

@@ -1,7 +1,6 @@
 // std::sort (libstdc++ introsort) emulation over all groups at once — see sortemu.hip.
 #pragma once
 #include "bk_common.h"
-#include "prims.h"
 #include <vector>
 #include <atomic>
 
@@ -38,44 +37,24 @@ struct SortService
 
 struct SortEmuBufs
 {
-  SortService *svc = nullptr;  // set (and running): std_sort_groups submits to it instead of launching the phases itself
+  SortService *svc = nullptr;  // set (and running): std_sort_groups submits to it instead of dispatching the tasks itself
   uint32_t svc_slot = 0xFFFFFFFFu, svc_epoch = 0;
-  DevBuf cnt, err, segs_a, segs_b, posL, posR, scan_tmp, heap_list, heap_scratch, scratch32, scratch32b, fin_list, lv_tile, lv_segbase, lv_tileseg, lv_bar, chk_key0, chk_cnt, chk_bad, rk_a, rk_b, heap_tickets;
-  prims::RadixBufs radix;
-  // optional observer (host): heavy[g] = largest heapsort segment (elements) any sort through these buffers left to group g's
-  // lone-wave heap kernels - what the lanes of lanes.hip balance on.  Set by the caller around the sorts it wants recorded.
+  DevBuf heap_scratch, scratch32, scratch32b, rk_a, rk_b, chk_key0, chk_cnt, chk_bad;
+  // optional observer (host): heavy[g] = largest heapsort segment (elements) any task dispatch through these buffers met in group g
+  // - what the lanes of lanes.hip balance on.  Set by the caller around the sorts it wants recorded.
   std::vector<uint32_t> *heavy = nullptr;
-  bool heavy_all = false;  // record every segment the level loop left to the heapsort kernels (a group that has one went through all ~2 lg n levels), not only the long ones
-  // the three size classes of the heapsort branch run side by side (fork/join around the caller's stream); false: no side stream,
-  // all heaps of a sort in one dispatch on the caller's stream after the finisher (a caller with one hardware queue per stream)
-  bool fork_heaps = true;
+  bool heavy_all = false;  // record every segment that went to a heapsort task (a group that has one went through all ~2 lg n levels), not only the long ones
   // the sort as ONE task dispatch on the caller's stream (sortsvc.inc, k_sort_job) when no service runs: this caller's own queues,
-  // job and position lists (BREAKID_SORT_TASKS=0: the launches of the level loop, the tail, the finisher and the heaps instead)
+  // job and position lists
   DevBuf tj_ctl, tj_jobs, tj_slots[2], tj_seq[2], tj_pos[2], tj_heavy, tj_trace;
   uint32_t tj_cap[2] = {0, 0}, tj_epoch = 0;
   bool tj_ready = false;  // the rings are initialised and consistent (a failed sort clears it)
-  // sorts through these buffers by form: [0] jobs of the resident service, [1] task dispatches, [2] launches
-  uint64_t sorts[3] = {0, 0, 0};
-  static constexpr int N_AUX = 5;
-  hipStream_t aux[N_AUX] = {};
-  hipEvent_t fork = nullptr, join[N_AUX] = {};
+  // sorts through these buffers by form: [0] jobs of the resident service, [1] task dispatches
+  uint64_t sorts[2] = {0, 0};
   SortEmuBufs() = default;
   SortEmuBufs(const SortEmuBufs &) = delete;
   SortEmuBufs &operator=(const SortEmuBufs &) = delete;
-  ~SortEmuBufs()
-  {
-    for (int i = 0; i < N_AUX; ++i)
-    {
-      if (aux[i]) (void) hipStreamDestroy(aux[i]);
-      if (join[i]) (void) hipEventDestroy(join[i]);
-    }
-    if (fork) (void) hipEventDestroy(fork);
-  }
 };
-
-// false under BREAKID_SORT_TASKS=0: without a running service, a sort is the chain of launches (level loop, tail, finisher, heaps)
-// instead of one task dispatch on the caller's stream
-bool sort_tasks_on();
 
 // key/idx: n elements, groups are the contiguous ranges goff[g]..goff[g+1]; gof[p] = group of position p.
 // On return every group is ordered exactly as std::sort(begin, end, [](a,b){return a.key < b.key;}) leaves it.

@@ -37,7 +37,7 @@ constexpr uint32_t SVC_WIDE_MIN = 16384;    // partition nodes above this size g
 constexpr uint32_t SVC_BIAS = 0x80000000u;  // held in `remaining` while the groups of a job are being submitted
 constexpr uint32_t SVC_MAX_JOBS = 64;
 constexpr uint32_t SVC_H_QUIT = 0, SVC_H_ERROR = 1, SVC_H_NARROW = 8, SVC_H_STARTED = 16, SVC_H_DONE = SVC_H_STARTED + 1024, SVC_H_WORDS = SVC_H_DONE + SVC_MAX_JOBS;
-constexpr uint32_t SVC_NARROW_LDS = 45056;  // FinLds<FIN_MAX> + the finisher's heap hand-over list; (HEAP_BIG_MIN + HEAP_PAD) * 8 fits too
+constexpr uint32_t SVC_NARROW_LDS = 45056;  // Fin2Lds and (HEAP_BIG_MIN + HEAP_PAD) * 8 fit (static_asserts below)
 constexpr unsigned long long SVC_TIMEOUT_TICKS = 800000000ull;  // 8 s of wall_clock64 (100 MHz): a workgroup that saw no task for that long leaves
 
 struct SvcTask
@@ -51,7 +51,7 @@ static_assert(sizeof(SvcTask) == 16, "two 8-byte halves");
 // one std::sort call over the groups of a list.  Written by k_svc_submit, read by the workgroups with agent-scope loads.
 struct SvcJob
 {
-  uint32_t *key, *idx, *posL, *posR;
+  uint32_t *key, *idx, *posL, *posR;  // (posL, posR: null, read by nobody; the descriptor keeps its nine leading 8-byte words)
   hent *hscratch;
   uint32_t *scratch32, *scratch32b;
   unsigned long long *rka, *rkb;
@@ -220,7 +220,7 @@ struct SvcJobLds
   uint32_t tag;  // job slot | epoch << 8 of the descriptor held (0xFFFFFFFF: none)
 };
 
-// __move_median_to_first(first, first+1, mid, last-1); one lane.  (pivot_one without the heap hand-over)
+// __move_median_to_first(first, first+1, mid, last-1); one lane
 __device__ __forceinline__ uint32_t svc_pick_pivot(uint32_t first, uint32_t last, uint32_t *key, uint32_t *idx)
 {
   const uint32_t a = first + 1, b = first + (last - first) / 2, c = last - 1;
@@ -244,7 +244,8 @@ __device__ __forceinline__ uint32_t svc_pick_pivot(uint32_t first, uint32_t last
   return kp;
 }
 
-// ---- a partition node and the spine below it (the loop of k_se_tail_round, children as tasks) -------------------------------------
+// ---- a partition node and the spine below it (the larger side stays with the workgroup, children as tasks) -------------------------------------
+constexpr uint32_t TL_UNROLL = 24;  // rows of 64 keys a wave has in flight in the count and the place pass of a node
 template <uint32_t NT> struct SvcPartLds
 {
   uint32_t first, last, pivot;
@@ -508,11 +509,11 @@ __device__ __forceinline__ void svc_part(const SvcParams &P, const SvcJobLds &J,
 }
 
 // ---- the finisher of the service: a segment of at most FIN_MAX elements in LDS, its sub-segments dealt to the waves --------------
-// fin_body (the launch-per-phase form) plays the levels of ALL sub-segments in lock step: six workgroup barriers and eight passes
-// over the whole segment per level, ~20 levels whatever is left alive, and every sub-segment that runs out of depth leaves as a
-// heap segment of its own (117 us per task and 41 000 heap tasks of mostly 16-63 elements per stage, i.e. three quarters of what
-// the narrow workgroups did).  Here a sub-segment belongs to ONE wave: the wave partitions it (stoppers listed by ballots, pairs
-// swapped while l_j < r_j, cut = min(l_J, r_{J-1}): the partition of k_lv_* / k_se_tail_round bit for bit), queues the smaller side
+// An earlier form played the levels of ALL sub-segments in lock step: six workgroup barriers and eight passes over the whole
+// segment per level, ~20 levels whatever is left alive, and every sub-segment that ran out of depth left as a heap segment of
+// its own (117 us per task and 41 000 heap tasks of mostly 16-63 elements per stage, i.e. three quarters of what the narrow
+// workgroups did).  Here a sub-segment belongs to ONE wave: the wave partitions it (stoppers listed by ballots, pairs
+// swapped while l_j < r_j, cut = min(l_J, r_{J-1}): the partition of svc_part bit for bit), queues the smaller side
 // for whichever wave is free and carries on with the larger one; a sub-segment that has used up its depth is heapsorted by the
 // wave that holds it, in that wave's own buffer, when it has at most F2_HB elements (95 % of them), else it leaves as a heap task.
 // Sub-segments are disjoint, so the order in which the waves take them does not matter.

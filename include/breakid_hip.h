@@ -510,7 +510,8 @@ int bk_shard_bp_finish(bk_ctx *ctx, const void *depth_total_dev);
 int bk_debug_std_sort(bk_ctx *ctx, const uint32_t *key, const uint64_t *group_off, uint32_t n_groups, uint32_t *perm_out);
 
 /* Test hook: how the std::sort replays of this context ran so far, summed over its lanes: out[0] jobs of the resident sort
- * service, out[1] task dispatches on the caller's stream, out[2] chains of launches (BREAKID_SORT_TASKS=0). */
+ * service, out[1] task dispatches on the caller's stream.  out[2] is always 0: it counted a third form (chains of launches)
+ * that no longer exists; the three-word signature stays. */
 int bk_sort_forms(bk_ctx *ctx, uint64_t out[3]);
 
 /* Test hook: find_cluster_pairs_enspan_ahc (BreakID.cc:1304-1352) on one group of x-sorted points; returns the

@@ -547,11 +547,11 @@ print("LANES_OK", nv)
         assert "shares a hardware queue" in r.stderr, r.stderr[-1500:]
 
 
-@pytest.mark.parametrize("switch", ["BREAKID_SORT_SERVICE=0", "BREAKID_SORT_SERVICE=0,BK_SORT_NO_TAIL=1", "BK_HEAP_NO_Q", "BREAKID_SORT_SERVICE=0,BK_HEAP_NO_Q=1", "BK_JOIN_ATTEMPT=1", "BK_JOIN_ATTEMPT=2", "BREAKID_NO_SIDE"])
+@pytest.mark.parametrize("switch", ["BREAKID_SORT_SERVICE=0", "BK_JOIN_ATTEMPT=1", "BK_JOIN_ATTEMPT=2", "BREAKID_NO_SIDE"])
 def test_earlier_statements_of_the_same_computation_still_agree(switch):
-    """the behavioural switches the library keeps (INTEGRATION.md section 5): the std::sort replay as launches instead of jobs of
-    the resident service, its level loop without the tail rounds, the pop loop's earlier form, the mate join's fallback attempts,
-    the four candidate columns instead of the side rows - each must give the reference's order and the oracle's stages.
+    """the behavioural switches the library keeps (INTEGRATION.md section 5): the std::sort replay as task dispatches on the
+    caller's stream instead of jobs of the resident service, the mate join's fallback attempts, the four candidate columns
+    instead of the side rows - each must give the reference's order and the oracle's stages.
     Own process: the switches are read once."""
     import subprocess
     import sys

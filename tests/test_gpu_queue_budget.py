@@ -1,7 +1,7 @@
 """The lane stage of bk_mask_and_cluster at ROCm's default of four hardware queues: the resident sort service needs seven (four lane
 streams, two persistent kernels, a copy stream), so nothing of it is started; the launch path runs three lanes (one queue stays
-with the process's first stream) with one stream each, and every sort of a lane runs all of its heaps in one dispatch on the lane's
-own stream (k_se_heaps_fused, no side stream).  Results must not change.  Own processes: the runtime reads GPU_MAX_HW_QUEUES when
+with the process's first stream) with one stream each, and every sort of a lane is one task dispatch on the lane's own stream
+(k_sort_job, no side stream).  Results must not change.  Own processes: the runtime reads GPU_MAX_HW_QUEUES when
 it starts."""
 import os
 import subprocess
@@ -17,7 +17,7 @@ ROOT_DIR = bigcases.ROOT
 
 def _run(code, **env_extra):
     env = dict(os.environ, GPU_MAX_HW_QUEUES="4", BK_DEBUG="lanes", BREAKID_LANES_MIN_PAIRS="1000", **env_extra)
-    for k in ("BREAKID_QUIET", "BREAKID_GROUP_LANES", "BREAKID_SORT_SERVICE", "BREAKID_LANE_STREAMS"):
+    for k in ("BREAKID_QUIET", "BREAKID_GROUP_LANES", "BREAKID_SORT_SERVICE"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=900, cwd=ROOT_DIR)
     assert r.returncode == 0 and "QB_OK" in r.stdout, (r.stdout[-2000:], r.stderr[-3000:])

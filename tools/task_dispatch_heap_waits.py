@@ -1,7 +1,7 @@
 """Per sort of the task-dispatch form (sortsvc.inc, k_sort_job): how long after the dispatch started the sort's longest heap
-started, how long it took, and when the partition and finisher tasks and the whole job were done.  The sibling of
-timeline_heap_waits.py, which keys on the launch form's k_se_heaps_fused in a kernel trace: a task dispatch is one kernel, so the
-times come from the workgroups' own clocks, which the driver prints per sort under BK_DEBUG=svc.
+started, how long it took, and when the partition and finisher tasks and the whole job were done.  A task dispatch is one
+kernel, so a kernel trace cannot tell: the times come from the workgroups' own clocks, which the driver prints per sort under
+BK_DEBUG=svc.
 
     BK_DEBUG=lanes,svc python bench.py --steps 1 --warmup 1 --cpu-sample 0 2> run.err
     python tools/task_dispatch_heap_waits.py run.err
