@@ -37,12 +37,21 @@ EVIDENCE = np.dtype([("rec", "<u8"), ("qhash", "<u8"), ("qcheck", "<u4"), ("call
                      ("pos2", "<u4"), ("flag1", "<u2"), ("flag2", "<u2"), ("mapq1", "u1"), ("mapq2", "u1"), ("kind", "u1"), ("sides", "u1")])  # struct bk_evidence
 UNIQUE_SUPPORT = np.dtype([("uniq_pairs", "<u4"), ("top_pairs", "<u4"), ("uniq_splits", "<u4"), ("top_splits", "<u4")])  # struct bk_unique_support
 assert UNIQUE_SUPPORT.itemsize == 16
+CONSENSUS = np.dtype([("n_reads", "<u4"), ("len", "<u4"), ("match", "<u4"), ("total", "<u4")])  # struct bk_consensus
+assert CONSENSUS.itemsize == 16
+# the columns of a bk_reads table, in the struct's order (cigar_off and seq_off have n + 1 entries)
+READS_COLS = [("tid", np.int32), ("pos", np.int32), ("flag", np.uint16), ("mapq", np.uint8), ("key", np.uint32), ("cigar_off", np.uint32), ("cigar", np.uint32),
+              ("l_seq", np.uint32), ("seq_off", np.uint64), ("seq", np.uint8)]
 READ_KEY = np.dtype([("qhash", "<u8"), ("qcheck", "<u4"), ("tag", "<u4")])  # bk_read_key
 assert EVIDENCE.itemsize == 48 and READ_KEY.itemsize == 16
 assert PAIR.itemsize == 56 and SPLIT.itemsize == 88 and CLUSTER.itemsize == 72 and NORMAL_SUPPORT.itemsize == 16 and REF_SUPPORT.itemsize == 16
 
 STAGE_DTYPE = {STAGE_SCAN: PAIR, STAGE_ISO: PAIR, STAGE_CLUSTERED: PAIR, STAGE_SPLITS: SPLIT,
                STAGE_CLUSTERS: CLUSTER, STAGE_GROUP_KEYS: GROUP_KEY}
+
+
+class Reads(C.Structure):  # bk_reads
+    _fields_ = [("n", C.c_uint64)] + [(name, C.c_void_p) for name, _ in READS_COLS] + [("owner", C.c_void_p)]
 
 
 class Soa(C.Structure):

@@ -35,8 +35,8 @@ def build(verbose=False):
 
 EXPORTS = ["bk_init", "bk_prepare_process", "bk_free", "bk_last_error", "bk_set_stream", "bk_sync", "bk_get_stream", "bk_upload_records", "bk_records", "bk_exclude_regions", "bk_isize_stats",
            "bk_discordant_pairs", "bk_mask_and_cluster", "bk_split_evidence", "bk_cluster_summary",
-           "bk_split_breakpoints", "bk_normal_support", "bk_ref_support", "bk_genotype_call", "bk_clip_support", "bk_clip_reads", "bk_base_depth", "bk_clip_rescue", "bk_junctions", "bk_junction_sides", "bk_vcf_breakend_alt", "bk_evidence", "bk_unique_support", "bk_run", "bk_fetch", "bk_timing", "bk_timing_enable", "bk_timing_touched", "bk_group_stats", "bk_qname_hash", "bk_qname_check",
-           "bk_bam_open", "bk_bam_header", "bk_bam_decode", "bk_bam_close", "bk_bam_extract", "bk_bam_names_free", "bk_bam_decode_device", "bk_bam_decode_device_part", "bk_bam_decode_device_ctx", "bk_bam_dev_free", "bk_feed_release_caches", "bk_debug_bgzf_inflate", "bk_debug_std_sort", "bk_sort_forms", "bk_debug_ahc", "bk_debug_points", "bk_debug_cigar", "bk_debug_vote", "bk_debug_region", "bk_shard_begin", "bk_shard_get_stats", "bk_shard_set_stats",
+           "bk_split_breakpoints", "bk_normal_support", "bk_ref_support", "bk_genotype_call", "bk_clip_support", "bk_clip_reads", "bk_base_depth", "bk_clip_rescue", "bk_junctions", "bk_junction_sides", "bk_vcf_breakend_alt", "bk_evidence", "bk_unique_support", "bk_clip_consensus", "bk_run", "bk_fetch", "bk_timing", "bk_timing_enable", "bk_timing_touched", "bk_group_stats", "bk_qname_hash", "bk_qname_check",
+           "bk_bam_open", "bk_bam_header", "bk_bam_decode", "bk_bam_close", "bk_bam_extract", "bk_bam_names_free", "bk_bam_reads", "bk_reads_free", "bk_bam_decode_device", "bk_bam_decode_device_part", "bk_bam_decode_device_ctx", "bk_bam_dev_free", "bk_feed_release_caches", "bk_debug_bgzf_inflate", "bk_debug_std_sort", "bk_sort_forms", "bk_debug_ahc", "bk_debug_points", "bk_debug_cigar", "bk_debug_vote", "bk_debug_region", "bk_shard_begin", "bk_shard_get_stats", "bk_shard_set_stats",
            "bk_shard_sd_local", "bk_shard_sd_finish", "bk_shard_buffer", "bk_shard_set_buffer", "bk_shard_group_sizes",
            "bk_shard_own_groups", "bk_shard_route_candidates", "bk_shard_group_keys", "bk_shard_route_pairs", "bk_shard_group_pairs", "bk_shard_bp_cov", "bk_shard_bp_vote", "bk_shard_bp_vote_slice", "bk_shard_bp_set_voted", "bk_shard_bp_depth", "bk_shard_bp_finish"]
 
@@ -83,6 +83,7 @@ def lib():
         L.bk_vcf_breakend_alt.argtypes = [C.c_char, C.c_int, C.c_char_p, C.c_uint32, C.c_int, C.c_char_p, C.c_size_t]
         L.bk_evidence.argtypes = [vp, C.POINTER(vp), u64p, C.POINTER(C.POINTER(C.c_uint64))]
         L.bk_unique_support.argtypes = [vp, C.POINTER(vp), u64p, C.POINTER(C.POINTER(C.c_uint64)), u64p]
+        L.bk_clip_consensus.argtypes = [vp, C.POINTER(abi.Reads), vp, C.c_uint64, C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
         L.bk_fetch.argtypes = [vp, C.c_int, C.POINTER(vp), u64p, C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(C.c_uint32)]
         L.bk_timing.argtypes = [vp, C.POINTER(C.POINTER(C.c_char_p)), C.POINTER(C.POINTER(C.c_float)),
                                 C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(C.c_int)]
@@ -125,6 +126,9 @@ def lib():
         L.bk_bam_close.argtypes = [vp]
         L.bk_bam_extract.argtypes = [C.c_char_p, C.c_char_p, vp, C.c_uint64, C.POINTER(C.c_char_p), C.c_uint64, C.POINTER(vp), u64p, C.c_char_p, C.c_size_t]
         L.bk_bam_names_free.argtypes = [vp]
+        L.bk_bam_reads.argtypes = [C.c_char_p, vp, C.c_uint64, C.POINTER(abi.Reads), C.c_char_p, C.c_size_t]
+        L.bk_reads_free.argtypes = [C.POINTER(abi.Reads)]
+        L.bk_reads_free.restype = None
         L.bk_bam_names_free.restype = None
         L.bk_bam_decode_device.argtypes = [C.c_char_p, C.c_int, C.POINTER(vp), C.POINTER(abi.Soa), C.POINTER(C.c_int), C.POINTER(C.POINTER(C.c_char_p)),
                                            C.POINTER(C.POINTER(C.c_uint32)), C.c_char_p, C.c_size_t]
@@ -439,6 +443,27 @@ class Context:
             return rows
         return rows, (np.ctypeslib.as_array(first, shape=(n_rows.value,)).copy() if n_rows.value else np.zeros(0, np.uint64))
 
+    def clip_consensus(self, reads, sites, mapq_min, min_clip, max_len=64, min_depth=2, col_depth=True):
+        """The clipped bases of `reads` piled up at `sites` (bk_clip_consensus).  reads: a dict of the bk_reads columns (abi.READS_COLS;
+        `key` may be missing), as bam_reads returns it or built by hand; sites: abi.CLIP_SITE rows with tol 0.  Returns (rows, bases,
+        depth): one abi.CONSENSUS row per site, bases as uint8 [n_sites, max_len] (0 behind a site's len) and, with `col_depth`, the
+        depth of every column as uint32 [n_sites, max_len] (None without)."""
+        sites = np.ascontiguousarray(sites, abi.CLIP_SITE)
+        assert sites.ndim == 1
+        n = len(sites)
+        t, keep = reads_struct(reads)
+        out, bases, depth = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        self._check(self.L.bk_clip_consensus(self.h, C.byref(t), sites.ctypes.data if n else None, n, int(mapq_min), int(min_clip), int(max_len), int(min_depth),
+                                             C.byref(out), C.byref(bases), C.byref(depth) if col_depth else None))
+        del keep
+        if not n:
+            return np.zeros(0, abi.CONSENSUS), np.zeros((0, int(max_len)), np.uint8), (np.zeros((0, int(max_len)), np.uint32) if col_depth else None)
+        buf = (C.c_char * (n * abi.CONSENSUS.itemsize)).from_address(out.value)
+        rows = np.frombuffer(buf, dtype=abi.CONSENSUS, count=n).copy()
+        b = np.ctypeslib.as_array(C.cast(bases, C.POINTER(C.c_uint8)), shape=(n, int(max_len))).copy()
+        d = np.ctypeslib.as_array(C.cast(depth, C.POINTER(C.c_uint32)), shape=(n, int(max_len))).copy() if col_depth else None
+        return rows, b, d
+
     def ref_support(self, records, mapq_min, anchor, w):
         """Reference-allele evidence of this context's calls on the record table of `records` (bk_ref_support): one abi.REF_SUPPORT
         row per STAGE_CLUSTERS row.  `records`: this context itself, or a Context on the same device and reference list (the
@@ -690,6 +715,50 @@ def bam_extract(in_bam, out_bam, keys, tags):
     finally:
         L.bk_bam_names_free(names)
     return out, n.value
+
+
+def reads_struct(reads):
+    """A dict of bk_reads columns as (abi.Reads, the arrays that back it).  n is len(reads["tid"])."""
+    t, keep = abi.Reads(), []
+    t.n = len(reads["tid"])
+    for name, dt in abi.READS_COLS:
+        if name not in reads:
+            continue
+        a = np.ascontiguousarray(reads[name], dt)
+        keep.append(a)
+        setattr(t, name, a.ctypes.data if a.size else None)
+    return t, keep
+
+
+def bam_reads(path, keys):
+    """The alignments of named reads with their bases (bk_bam_reads; host code, no GPU).  keys: abi.READ_KEY array (tag is not
+    read).  Returns a dict of numpy copies of the bk_reads columns (abi.READS_COLS), rows in file order."""
+    keys = np.ascontiguousarray(keys, abi.READ_KEY)
+    L = lib()
+    t = abi.Reads()
+    err = C.create_string_buffer(512)
+    rc = L.bk_bam_reads(os.fsencode(path), keys.ctypes.data if len(keys) else None, len(keys), C.byref(t), err, 512)
+    if rc != 0:
+        raise BreakIDError(rc, err.value.decode())
+    try:
+        n = t.n
+        cols = {}
+
+        def col(name, dt, cnt):
+            ptr = getattr(t, name)
+            if cnt == 0 or not ptr:
+                return np.zeros(0, dt)
+            buf = (C.c_char * (cnt * np.dtype(dt).itemsize)).from_address(ptr)
+            return np.frombuffer(buf, dtype=dt, count=cnt).copy()
+        for name, dt in abi.READS_COLS:
+            if name in ("cigar", "seq"):
+                continue
+            cols[name] = col(name, dt, n + 1 if name in ("cigar_off", "seq_off") else n)
+        cols["cigar"] = col("cigar", np.uint32, int(cols["cigar_off"][-1]))
+        cols["seq"] = col("seq", np.uint8, int(cols["seq_off"][-1]))
+        return cols
+    finally:
+        L.bk_reads_free(C.byref(t))
 
 
 class BamTable:

@@ -17,6 +17,7 @@
 #include "junction.h"
 #include "evidence.h"
 #include "unique.h"
+#include "consensus.h"
 #include "exclude.h"
 #include "ahc.h"
 #include "lanes.h"
@@ -144,6 +145,11 @@ struct bk_ctx
   UniqueBufs uqb;
   std::vector<struct bk_unique_support> f_unique;
   std::vector<uint64_t> f_uq_first;
+  // junction consensus (bk_clip_consensus)
+  ConsensusBufs cnb;
+  std::vector<struct bk_consensus> f_cons;
+  std::vector<uint8_t> f_cons_bases;
+  std::vector<uint32_t> f_cons_depth;
 
   // fetch staging
   std::vector<bk_pair> f_pairs[3];
@@ -1216,6 +1222,70 @@ int bk_unique_support(bk_ctx *ctx, const struct bk_unique_support **out, uint64_
       *first = ctx->f_uq_first.data();
       *n_rows = us.n_rows;
     }
+  });
+}
+
+int bk_clip_consensus(bk_ctx *ctx, const bk_reads *reads, const struct bk_clip_site *sites, uint64_t n_sites, int mapq_min, int min_clip, uint32_t max_len,
+                      uint32_t min_depth, const struct bk_consensus **out, const uint8_t **bases, const uint32_t **col_depth)
+{
+  return guarded(ctx, [&] {
+    if (!reads || !out || !bases) throw bk_error(BK_ERR_ARG, "bk_clip_consensus: null reads, out or bases");
+    if (n_sites && !sites) throw bk_error(BK_ERR_ARG, "bk_clip_consensus: null sites");
+    if (ctx->shard) throw bk_error(BK_ERR_ARG, "bk_clip_consensus: sharded contexts (bk_shard_*) are not supported");
+    if (max_len < 1 || max_len > 256) throw bk_error(BK_ERR_ARG, "bk_clip_consensus: max_len must be 1..256");
+    if (min_depth == 0) throw bk_error(BK_ERR_ARG, "bk_clip_consensus: min_depth must be at least 1");
+    if (min_clip < 1) throw bk_error(BK_ERR_ARG, "bk_clip_consensus: min_clip must be at least 1");
+    if (mapq_min < 0) throw bk_error(BK_ERR_ARG, "bk_clip_consensus: mapq_min must not be negative");
+    if (reads->n > 0x100000000ull) throw bk_error(BK_ERR_LIMIT, "bk_clip_consensus: more than 2^32 reads");
+    if (n_sites > 0x40000000ull) throw bk_error(BK_ERR_LIMIT, "bk_clip_consensus: more than 2^30 sites");
+    for (uint64_t k = 0; k < n_sites; ++k)
+    {
+      if (sites[k].dir > 1u) throw bk_error(BK_ERR_ARG, "bk_clip_consensus: site " + std::to_string(k) + " has a dir above 1 (0 = LEFT, 1 = RIGHT)");
+      if (sites[k].tol != 0u) throw bk_error(BK_ERR_ARG, "bk_clip_consensus: site " + std::to_string(k) + " has a tol other than 0");
+    }
+    const bk_reads &t = *reads;
+    if (t.n && (!t.tid || !t.pos || !t.flag || !t.mapq || !t.cigar_off || !t.l_seq || !t.seq_off)) throw bk_error(BK_ERR_ARG, "bk_clip_consensus: the reads table lacks a column");
+    for (uint64_t i = 0; i < t.n; ++i)
+    {
+      if (t.cigar_off[i + 1] < t.cigar_off[i]) throw bk_error(BK_ERR_ARG, "bk_clip_consensus: cigar_off does not ascend at read " + std::to_string(i));
+      if (t.seq_off[i + 1] < t.seq_off[i]) throw bk_error(BK_ERR_ARG, "bk_clip_consensus: seq_off does not ascend at read " + std::to_string(i));
+      if (t.seq_off[i + 1] - t.seq_off[i] < ((uint64_t) t.l_seq[i] + 1) / 2)
+        throw bk_error(BK_ERR_ARG, "bk_clip_consensus: read " + std::to_string(i) + " has fewer seq bytes than (l_seq + 1) / 2");
+    }
+    if (t.n && ((t.cigar_off[t.n] && !t.cigar) || (t.seq_off[t.n] && !t.seq))) throw bk_error(BK_ERR_ARG, "bk_clip_consensus: the reads table lacks a column");
+    struct bk_consensus *d_res;
+    uint8_t *d_bases;
+    uint32_t *d_depth;
+    ConsensusStat *d_stat;
+    consensus_upload(t, ctx->cnb, ctx->st);  // (outside the scope: it times the work on the device copy)
+    {
+      // bytes: the columns of the reads and the sites once, the result once
+      const uint64_t words = t.n ? t.cigar_off[t.n] : 0, sbytes = t.n ? t.seq_off[t.n] : 0;
+      Scope s(ctx, "consensus", t.n * 27ull + 12ull + words * 4ull + sbytes + n_sites * (16ull + sizeof(struct bk_consensus) + 5ull * max_len));
+      clip_consensus(sites, n_sites, mapq_min, min_clip, max_len, min_depth, ctx->cnb, ctx->st, &d_res, &d_bases, &d_depth, &d_stat);
+    }
+    ConsensusStat stat{};
+    HIP_CHECK(hipMemcpyAsync(&stat, d_stat, sizeof stat, hipMemcpyDeviceToHost, ctx->st));
+    const uint64_t cols = n_sites * max_len;
+    ctx->f_cons_bases.resize(cols);
+    if (cols) HIP_CHECK(hipMemcpyAsync(ctx->f_cons_bases.data(), d_bases, cols, hipMemcpyDeviceToHost, ctx->st));
+    if (col_depth)
+    {
+      ctx->f_cons_depth.resize(cols);
+      if (cols) HIP_CHECK(hipMemcpyAsync(ctx->f_cons_depth.data(), d_depth, cols * 4, hipMemcpyDeviceToHost, ctx->st));
+    }
+    rows_to_host(ctx, d_res, n_sites, ctx->f_cons);
+    if (ctx->timing && !ctx->timers.empty())
+    {
+      // touched: both walks read the fixed columns of every read (tid, flag, mapq, l_seq, two cigar offsets: 19 B) and
+      // the CIGAR words they count themselves; a contribution is written once and read once (12 B each way) and gives
+      // ceil(min(c, max_len) / 2) bytes of SEQ; per site its slot, key and two offsets, its row and its columns
+      ctx->timers.back().touched = 2ull * t.n * 19ull + stat.words * 4ull + stat.contributions * 24ull + stat.seq_bytes +
+                                   n_sites * (4ull + 8ull + 16ull + sizeof(struct bk_consensus) + 5ull * max_len);
+    }
+    *out = ctx->f_cons.data();
+    *bases = ctx->f_cons_bases.data();
+    if (col_depth) *col_depth = ctx->f_cons_depth.data();
   });
 }
 

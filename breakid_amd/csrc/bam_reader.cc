@@ -761,23 +761,90 @@ struct KeyHash
   size_t operator()(uint64_t h) const { return (size_t) h; }
 };
 
+// qhash -> the keys that carry it, in key order; shared by bk_bam_extract and bk_bam_reads
+struct KeyMap
+{
+  const bk_read_key *keys = nullptr;
+  std::unordered_map<uint64_t, std::vector<uint64_t>, KeyHash> by_hash;
+  // `check(k)` may refuse key k before it is entered; `who` names the caller in the duplicate's message
+  template <class C> void build(const bk_read_key *ks, uint64_t n_keys, const char *who, C &&check)
+  {
+    keys = ks;
+    by_hash.reserve((size_t) n_keys * 2 + 1);
+    for (uint64_t k = 0; k < n_keys; ++k)
+    {
+      check(k);
+      std::vector<uint64_t> &v = by_hash[keys[k].qhash];
+      for (uint64_t o : v)
+        if (keys[o].qcheck == keys[k].qcheck) throw ExtractError{BK_ERR_ARG, std::string(who) + ": duplicate key " + std::to_string(k)};
+      v.push_back(k);
+    }
+  }
+  // the first key that selects the read name (-1: none); every selecting key is passed to `each`
+  template <class E> int64_t match(const char *qn, size_t qlen, E &&each) const
+  {
+    const auto it = by_hash.find(bk_qname_hash(qn, qlen));
+    if (it == by_hash.end()) return -1;
+    const uint32_t check = bk_qname_check(qn, qlen);
+    int64_t first = -1;
+    for (uint64_t k : it->second)
+      if (keys[k].qcheck == 0 || keys[k].qcheck == check)
+      {
+        if (first < 0) first = (int64_t) k;
+        each(k);
+      }
+    return first;
+  }
+};
+
+// The record walk both share: header(ptr, len) sees the header's bytes once, record(r, bs, qn, qlen) every record (r = the bs bytes
+// behind block_size, checked to hold name, CIGAR, SEQ and QUAL; qn / qlen = the read name as a C string).
+template <class H, class R> void walk_records(BgzfStream &s, H &&header, R &&record)
+{
+  if (!s.need(12) || memcmp(s.ptr(), "BAM\1", 4) != 0) throw ExtractError{BK_ERR_IO, "not a BAM file"};
+  const size_t l_text = rd32(s.ptr() + 4);
+  if (!s.need(12 + l_text)) throw ExtractError{BK_ERR_IO, "truncated BAM header"};
+  const uint32_t n_ref = rd32(s.ptr() + 8 + l_text);
+  size_t hlen = 12 + l_text;
+  for (uint32_t i = 0; i < n_ref; ++i)
+  {
+    if (!s.need(hlen + 4)) throw ExtractError{BK_ERR_IO, "truncated BAM header"};
+    const size_t l_name = rd32(s.ptr() + hlen);
+    hlen += 4 + l_name + 4;
+    if (!s.need(hlen)) throw ExtractError{BK_ERR_IO, "truncated BAM header"};
+  }
+  header(s.ptr(), hlen);
+  s.pos += hlen;
+  for (;;)
+  {
+    if (!s.need(4))
+    {
+      if (s.avail() == 0) break;
+      throw ExtractError{BK_ERR_IO, "truncated BAM record"};
+    }
+    const size_t bs = rd32(s.ptr());
+    if (bs < 32) throw ExtractError{BK_ERR_IO, "corrupt BAM record"};
+    if (!s.need(4 + bs)) throw ExtractError{BK_ERR_IO, "truncated BAM record: it is longer than its stream"};
+    const uint8_t *r = s.ptr() + 4;
+    const size_t l_name = r[8], n_cig = rd16(r + 12), l_seq = rd32(r + 16);
+    if (32 + l_name + n_cig * 4 + (l_seq + 1) / 2 + l_seq > bs) throw ExtractError{BK_ERR_IO, "corrupt BAM record"};
+    const char *qn = (const char *) r + 32;
+    const size_t qlen = l_name ? strnlen(qn, l_name) : 0;  // bam_get_qname is a C string
+    record(r, bs, qn, qlen);
+    s.pos += 4 + bs;
+  }
+}
+
 int bam_extract_impl(const char *in_bam, const char *out_bam, const bk_read_key *keys, uint64_t n_keys, const char *const *tags, uint64_t n_tags, char **names_out,
                      uint64_t *n_written, std::string &tmp_path, FILE *&fin, FILE *&fout)
 {
   if (!in_bam) throw ExtractError{BK_ERR_ARG, "bk_bam_extract: null input path"};
   if ((n_keys && !keys) || (n_tags && !tags)) throw ExtractError{BK_ERR_ARG, "bk_bam_extract: null keys or tags"};
-  // qhash -> the keys that carry it, in key order
-  std::unordered_map<uint64_t, std::vector<uint64_t>, KeyHash> by_hash;
-  by_hash.reserve((size_t) n_keys * 2 + 1);
-  for (uint64_t k = 0; k < n_keys; ++k)
-  {
+  KeyMap km;
+  km.build(keys, n_keys, "bk_bam_extract", [&](uint64_t k) {
     if (keys[k].tag >= n_tags) throw ExtractError{BK_ERR_ARG, "bk_bam_extract: key " + std::to_string(k) + " has tag " + std::to_string(keys[k].tag) + " of " + std::to_string(n_tags)};
     if (!tags[keys[k].tag]) throw ExtractError{BK_ERR_ARG, "bk_bam_extract: null tag text"};
-    std::vector<uint64_t> &v = by_hash[keys[k].qhash];
-    for (uint64_t o : v)
-      if (keys[o].qcheck == keys[k].qcheck) throw ExtractError{BK_ERR_ARG, "bk_bam_extract: duplicate key " + std::to_string(k)};
-    v.push_back(k);
-  }
+  });
   std::vector<std::string> names(n_keys);
   std::vector<uint8_t> seen(n_keys, 0);
   fin = fopen(in_bam, "rb");
@@ -796,80 +863,40 @@ int bam_extract_impl(const char *in_bam, const char *out_bam, const bk_read_key 
     }
     w.f = fout;
   }
-  // header: copied byte for byte
-  if (!s.need(12) || memcmp(s.ptr(), "BAM\1", 4) != 0) throw ExtractError{BK_ERR_IO, "not a BAM file"};
-  const size_t l_text = rd32(s.ptr() + 4);
-  if (!s.need(12 + l_text)) throw ExtractError{BK_ERR_IO, "truncated BAM header"};
-  const uint32_t n_ref = rd32(s.ptr() + 8 + l_text);
-  size_t hlen = 12 + l_text;
-  for (uint32_t i = 0; i < n_ref; ++i)
-  {
-    if (!s.need(hlen + 4)) throw ExtractError{BK_ERR_IO, "truncated BAM header"};
-    const size_t l_name = rd32(s.ptr() + hlen);
-    hlen += 4 + l_name + 4;
-    if (!s.need(hlen)) throw ExtractError{BK_ERR_IO, "truncated BAM header"};
-  }
-  if (out_bam)
-  {
-    w.write(s.ptr(), hlen);
-    w.flush();  // (htslib ends the header's block before the first record)
-  }
-  s.pos += hlen;
   uint64_t written = 0;
   std::vector<uint8_t> rec;
-  for (;;)
-  {
-    if (!s.need(4))
-    {
-      if (s.avail() == 0) break;
-      throw ExtractError{BK_ERR_IO, "truncated BAM record"};
-    }
-    const size_t bs = rd32(s.ptr());
-    if (bs < 32) throw ExtractError{BK_ERR_IO, "corrupt BAM record"};
-    if (!s.need(4 + bs)) throw ExtractError{BK_ERR_IO, "truncated BAM record: it is longer than its stream"};
-    const uint8_t *r = s.ptr() + 4;
-    const size_t l_name = r[8], n_cig = rd16(r + 12), l_seq = rd32(r + 16);
-    if (32 + l_name + n_cig * 4 + (l_seq + 1) / 2 + l_seq > bs) throw ExtractError{BK_ERR_IO, "corrupt BAM record"};
-    const char *qn = (const char *) r + 32;
-    const size_t qlen = l_name ? strnlen(qn, l_name) : 0;  // bam_get_qname is a C string
-    const auto it = by_hash.find(bk_qname_hash(qn, qlen));
-    if (it != by_hash.end())
-    {
-      const uint32_t check = bk_qname_check(qn, qlen);
-      int64_t first = -1;
-      for (uint64_t k : it->second)
-        if (keys[k].qcheck == 0 || keys[k].qcheck == check)
-        {
-          if (first < 0) first = (int64_t) k;
+  walk_records(
+      s,
+      [&](const uint8_t *h, size_t hlen) {  // header: copied byte for byte
+        if (!out_bam) return;
+        w.write(h, hlen);
+        w.flush();  // (htslib ends the header's block before the first record)
+      },
+      [&](const uint8_t *r, size_t bs, const char *qn, size_t qlen) {
+        const int64_t first = km.match(qn, qlen, [&](uint64_t k) {
           if (!seen[k])
           {
             seen[k] = 1;
             names[k].assign(qn, qlen);
           }
-        }
-      if (first >= 0)
-      {
+        });
+        if (first < 0) return;
         ++written;
-        if (out_bam)
-        {
-          const char *tag = tags[keys[first].tag];
-          const size_t tl = strlen(tag), nbs = bs + 3 + tl + 1;
-          if (nbs > 0x7FFFFFFFull) throw ExtractError{BK_ERR_IO, "record too long for a bk tag"};
-          rec.resize(4 + nbs);
-          for (int i = 0; i < 4; ++i) rec[i] = (uint8_t) (nbs >> (8 * i));
-          memcpy(rec.data() + 4, r, bs);
-          uint8_t *a = rec.data() + 4 + bs;
-          a[0] = 'b';
-          a[1] = 'k';
-          a[2] = 'Z';
-          memcpy(a + 3, tag, tl + 1);
-          w.record_follows(rec.size());
-          w.write(rec.data(), rec.size());
-        }
-      }
-    }
-    s.pos += 4 + bs;
-  }
+        if (!out_bam) return;
+        const char *tag = tags[keys[first].tag];
+        const size_t tl = strlen(tag), nbs = bs + 3 + tl + 1;
+        if (nbs > 0x7FFFFFFFull) throw ExtractError{BK_ERR_IO, "record too long for a bk tag"};
+        rec.resize(4 + nbs);
+        for (int i = 0; i < 4; ++i) rec[i] = (uint8_t) (nbs >> (8 * i));
+        memcpy(rec.data() + 4, r, bs);
+        uint8_t *a = rec.data() + 4 + bs;
+        a[0] = 'b';
+        a[1] = 'k';
+        a[2] = 'Z';
+        memcpy(a + 3, tag, tl + 1);
+        w.record_follows(rec.size());
+        w.write(rec.data(), rec.size());
+      });
   if (names_out)  // (before the rename: a failure here must leave no output file)
   {
     size_t total = 0;
@@ -894,6 +921,51 @@ int bam_extract_impl(const char *in_bam, const char *out_bam, const bk_read_key 
   }
   if (n_written) *n_written = written;
   return BK_OK;
+}
+
+// ---- bk_bam_reads: the alignments of named reads with their bases (include/breakid_hip.h) ---------------------------------------
+// The same pass as bk_bam_extract; a selected record goes into the columns of a ReadsTable instead of a file.
+struct ReadsTable
+{
+  std::vector<int32_t> tid, pos;
+  std::vector<uint16_t> flag;
+  std::vector<uint8_t> mapq;
+  std::vector<uint32_t> key, cigar_off{0}, cigar, l_seq;
+  std::vector<uint64_t> seq_off{0};
+  std::vector<uint8_t> seq;
+};
+
+void bam_reads_impl(const char *in_bam, const bk_read_key *keys, uint64_t n_keys, ReadsTable &t, FILE *&fin)
+{
+  if (!in_bam) throw ExtractError{BK_ERR_ARG, "bk_bam_reads: null input path"};
+  if (n_keys && !keys) throw ExtractError{BK_ERR_ARG, "bk_bam_reads: null keys"};
+  if (n_keys > 0xFFFFFFFFull) throw ExtractError{BK_ERR_ARG, "bk_bam_reads: more than 2^32 keys"};
+  KeyMap km;
+  km.build(keys, n_keys, "bk_bam_reads", [](uint64_t) {});
+  fin = fopen(in_bam, "rb");
+  if (!fin) throw ExtractError{BK_ERR_IO, std::string("cannot open ") + in_bam};
+  BgzfStream s;
+  s.f = fin;
+  walk_records(
+      s, [](const uint8_t *, size_t) {},
+      [&](const uint8_t *r, size_t, const char *qn, size_t qlen) {
+        const int64_t first = km.match(qn, qlen, [](uint64_t) {});
+        if (first < 0) return;
+        const size_t l_name = r[8], n_cig = rd16(r + 12), l_seq = rd32(r + 16);
+        if (t.cigar.size() + n_cig > 0xFFFFFFFFull) throw ExtractError{BK_ERR_LIMIT, "bk_bam_reads: more than 2^32 CIGAR words"};
+        t.tid.push_back((int32_t) rd32(r));
+        t.pos.push_back((int32_t) rd32(r + 4));
+        t.mapq.push_back(r[9]);
+        t.flag.push_back(rd16(r + 14));
+        t.key.push_back((uint32_t) first);
+        const uint8_t *cg = r + 32 + l_name;
+        for (size_t j = 0; j < n_cig; ++j) t.cigar.push_back(rd32(cg + 4 * j));
+        t.cigar_off.push_back((uint32_t) t.cigar.size());
+        t.l_seq.push_back((uint32_t) l_seq);
+        const uint8_t *sq = cg + 4 * n_cig;
+        t.seq.insert(t.seq.end(), sq, sq + (l_seq + 1) / 2);
+        t.seq_off.push_back((uint64_t) t.seq.size());
+      });
 }
 }  // namespace
 
@@ -931,3 +1003,54 @@ extern "C" int bk_bam_extract(const char *in_bam, const char *out_bam, const bk_
 }
 
 extern "C" void bk_bam_names_free(char *names) { free(names); }
+
+extern "C" int bk_bam_reads(const char *in_bam, const bk_read_key *keys, uint64_t n_keys, bk_reads *out, char *err, size_t errlen)
+{
+  if (!out)
+  {
+    set_err(err, errlen, "bk_bam_reads: null output");
+    return BK_ERR_ARG;
+  }
+  memset(out, 0, sizeof *out);
+  ReadsTable *t = nullptr;
+  FILE *fin = nullptr;
+  const int rc = no_throw(err, errlen, [&] {
+    try
+    {
+      t = new ReadsTable;
+      bam_reads_impl(in_bam, keys, n_keys, *t, fin);
+      return (int) BK_OK;
+    }
+    catch (const ExtractError &e)
+    {
+      set_err(err, errlen, e.msg);
+      return e.code;
+    }
+  });
+  if (fin) fclose(fin);
+  if (rc != BK_OK)
+  {
+    delete t;
+    return rc;
+  }
+  out->n = t->tid.size();
+  out->tid = t->tid.data();
+  out->pos = t->pos.data();
+  out->flag = t->flag.data();
+  out->mapq = t->mapq.data();
+  out->key = t->key.data();
+  out->cigar_off = t->cigar_off.data();
+  out->cigar = t->cigar.data();
+  out->l_seq = t->l_seq.data();
+  out->seq_off = t->seq_off.data();
+  out->seq = t->seq.data();
+  out->owner = t;
+  return BK_OK;
+}
+
+extern "C" void bk_reads_free(bk_reads *r)
+{
+  if (!r) return;
+  delete static_cast<ReadsTable *>(r->owner);
+  memset(r, 0, sizeof *r);
+}

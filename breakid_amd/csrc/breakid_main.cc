@@ -39,6 +39,9 @@ extern "C" int bk_junction_sides(const struct bk_junction *j, uint8_t *right1, u
 extern "C" int bk_vcf_breakend_alt(char ref_base, int own_right, const char *mate_chr, uint32_t mate_pos, int mate_right, char *buf, size_t cap) __attribute__((weak));
 // -evidence: the same for the evidence rows (the CPU build refuses -evidence; bk_bam_extract is host code and always there)
 extern "C" int bk_evidence(bk_ctx *ctx, const struct bk_evidence **out, uint64_t *count, const uint64_t **call_off) __attribute__((weak));
+// -consensus: the same for the junction consensus (the CPU build refuses -consensus)
+extern "C" int bk_clip_consensus(bk_ctx *ctx, const bk_reads *reads, const struct bk_clip_site *sites, uint64_t n_sites, int mapq_min, int min_clip, uint32_t max_len,
+                                 uint32_t min_depth, const struct bk_consensus **out, const uint8_t **bases, const uint32_t **col_depth) __attribute__((weak));
 // -dedup: the same for the unique fragments behind every call (the CPU build refuses -dedup)
 extern "C" int bk_unique_support(bk_ctx *ctx, const struct bk_unique_support **out, uint64_t *count, const uint64_t **first, uint64_t *n_rows) __attribute__((weak));
 // -clip: the same for the soft-clip evidence, the depth at the rescued positions and the rescue rule (the CPU build refuses -clip)
@@ -291,7 +294,9 @@ static const char *HELP =
      \t -dedup     \t count the different fragments behind every call (twin files *_dedup.txt; UPE / USR with -vcf, a Dup column with -evidence)  \n \
      \t -clip      \t count soft-clipped reads without an SA tag at every call (twin files *_clip.txt) and rescue clusters the vote left out (*_fusion_rescued.txt)  \n \
      \t -minclip   \t shortest soft clip that counts (with -clip)  [10]\n \
-     \t -clipsupport \t clipped reads at one position that each side of a rescued cluster needs (with -clip)  [3]\n ";
+     \t -clipsupport \t clipped reads at one position that each side of a rescued cluster needs (with -clip)  [3]\n \
+     \t -consensus \t vote the clipped bases at both breakpoints of every call into a junction sequence (twin files *_consensus.txt; CSEQ / CSN with -vcf)  \n \
+     \t -conslen   \t longest junction sequence per side, 1 to 256 (with -consensus)  [64]\n ";
 
 // ---- RefSeqTranscript.{h,cc} -------------------------------------------------------------------------------
 struct Txpt
@@ -593,6 +598,26 @@ static const char *CLIP_COLUMNS = "\tClip1\tClip2\tClipPeak1\tClipPeakN1\tClipPe
 static const char *CLIP_COLUMNS_NORMAL = "\tNormal_Clip1\tNormal_Clip2";
 // -dedup: the twin files' columns (bk_unique_support: fragments among the N_DRP rows and the N_SR tuples, and the rows of the largest one)
 static const char *DEDUP_COLUMNS = "\tUniq_DRP\tUniq_SR\tTop_DRP\tTop_SR";
+// -consensus: the twin files' columns (bk_clip_consensus at the two breakpoints of the call: reads, voted columns, match / total, the
+// voted bases in the orientation of the BAM)
+static const char *CONSENSUS_COLUMNS = "\tCons_N1\tCons_Len1\tCons_Agree1\tCons_Seq1\tCons_N2\tCons_Len2\tCons_Agree2\tCons_Seq2";
+// the vote's own threshold (BreakID.cc:446): a column counts from two reads on
+static const uint32_t CONSENSUS_MIN_DEPTH = 2;
+
+// One side of a written call: its bk_consensus row and its bases as the BAM reads them (reference-forward at the anchor): a LEFT side
+// is columns 0 .. len - 1, a RIGHT side the same reversed, so that the text ends at the base just left of the breakpoint.
+struct ConsensusSide
+{
+  struct bk_consensus c = {0, 0, 0, 0};
+  string seq;
+  string agree() const
+  {
+    if (!c.total) return ".";
+    char buf[32];
+    snprintf(buf, sizeof buf, "%.3f", (double) c.match / (double) c.total);
+    return buf;
+  }
+};
 // -clip -normal: what _fusion_rescued_normal.txt adds to a row of _fusion_rescued.txt
 static const char *RESCUED_COLUMNS_NORMAL = "\tNormal_DRP\tNormal_ClipAt1\tNormal_ClipAt2\tNormal_Depth1\tNormal_Depth2";
 
@@ -631,6 +656,9 @@ struct VcfInput
   // third sample field CV, the clipped reads of the side, and are never genotyped
   const vector<RescuedCall> *rescued = nullptr;
   const vector<struct bk_unique_support> *usup = nullptr;  // -dedup (else null; never for the rescued clusters): INFO/UPE and INFO/USR, last
+  // -consensus (else null; never for the rescued clusters): the two sides of every written call by its BK_STAGE_CLUSTERS row; INFO/CSEQ
+  // and INFO/CSN behind everything else
+  const std::map<uint64_t, std::pair<ConsensusSide, ConsensusSide>> *cons = nullptr;
 };
 
 static char nib_base(const string &nib_dir, const string &chr, long pos1)  // the base at a 1-based position; N without a file or beyond it
@@ -687,7 +715,7 @@ static bool write_vcf(const string &path, const vector<OutRow> &rows, const VcfI
     if (rc ? !rescued_written(r, in.all) : !call_written(r, in.all)) continue;
     const bool no_gene_pair = call_no_gene_pair(r), filt_ok = rc ? !no_gene_pair && !r.is_rpt : call_filt_ok(r);
     if (r.idx >= in.jsup->size() || (in.with_normal && !rc && r.idx >= in.n_nsup) || (in.gsup && r.idx >= in.gsup->size()) ||
-        (in.gsup_normal && r.idx >= in.gsup_normal->size()) || (in.usup && !rc && r.idx >= in.usup->size()))
+        (in.gsup_normal && r.idx >= in.gsup_normal->size()) || (in.usup && !rc && r.idx >= in.usup->size()) || (in.cons && !rc && !in.cons->count(r.idx)))
       return false;
     const struct bk_junction &j = (*in.jsup)[r.idx];
     uint8_t right[2] = {0, 1}, source = 0;
@@ -716,6 +744,12 @@ static bool write_vcf(const string &path, const vector<OutRow> &rows, const VcfI
       }
       else
       {
+        if (in.cons)
+        {
+          const ConsensusSide &cs = s ? in.cons->at(r.idx).second : in.cons->at(r.idx).first;
+          if (!cs.seq.empty()) o << ";CSEQ=" << cs.seq;
+          o << ";CSN=" << cs.c.n_reads;
+        }
         o << "\t" << (in.gsup ? "GT:GQ:DR:DV:RR:RV" : "DV:RV") << "\t" << vcf_sample(r.c.n_drp, r.c.n_sr, in.gsup ? &(*in.gsup)[r.idx] : nullptr, s);
         if (in.with_normal) o << "\t" << vcf_sample(in.nsup[r.idx].n_drp, in.nsup[r.idx].n_sr, in.gsup_normal ? &(*in.gsup_normal)[r.idx] : nullptr, s);
       }
@@ -749,6 +783,9 @@ static bool write_vcf(const string &path, const vector<OutRow> &rows, const VcfI
   if (in.usup && !in.rescued)
     v << "##INFO=<ID=UPE,Number=1,Type=Integer,Description=\"Different fragments among the discordant read pairs of the call\">\n"
          "##INFO=<ID=USR,Number=1,Type=Integer,Description=\"Different fragments among the split-read alignments of the call\">\n";
+  if (in.cons && !in.rescued)
+    v << "##INFO=<ID=CSEQ,Number=1,Type=String,Description=\"Consensus of the bases soft-clipped at this breakpoint, in the orientation of the alignments\">\n"
+         "##INFO=<ID=CSN,Number=1,Type=Integer,Description=\"Reads soft-clipped exactly at this breakpoint that the consensus was voted from\">\n";
   if (in.rescued) v << "##INFO=<ID=SC,Number=1,Type=Integer,Description=\"Soft-clipped reads without an SA tag that end at this position (the clip peak)\">\n";
   if (in.gsup)
     v << "##FORMAT=<ID=GT,Number=1,Type=String,Description=\"Genotype\">\n"
@@ -995,11 +1032,14 @@ int main(int argc, char *argv[])
                                      {"fast", 0, 0, 5},   {"t", 0, 0, 6}, {"all", 0, 0, 7}, {"gpu", 1, 0, 8}, {"gpus", 1, 0, 9},
                                      {"comm", 1, 0, 10},  {"normal", 1, 0, 11}, {"x", 1, 0, 12}, {"genotype", 0, 0, 13},
                                      {"anchor", 1, 0, 14}, {"vcf", 0, 0, 15}, {"evidence", 0, 0, 16}, {"clip", 0, 0, 17},
-                                     {"minclip", 1, 0, 18}, {"clipsupport", 1, 0, 19}, {"dedup", 0, 0, 20}, {0, 0, 0, 0}};
+                                     {"minclip", 1, 0, 18}, {"clipsupport", 1, 0, 19}, {"dedup", 0, 0, 20}, {"consensus", 0, 0, 21},
+                                     {"conslen", 1, 0, 22}, {0, 0, 0, 0}};
   string inp_file, out_file, nib_dir, normal_file, exclude_file, build = "hg19";
   int qual = 20, device = 0, n_gpus = 0, transport = BK_TRANSPORT_AUTO;  // -gpus N: one sample over N GPUs (include/breakid_multi.h)
   bool fast = false, filter = true, genotype = false, anchor_given = false, vcf = false, evidence = false;
   bool clip = false, minclip_given = false, clipsupport_given = false, dedup = false;
+  bool consensus = false, conslen_given = false;
+  long conslen = 64;  // -conslen: longest junction sequence per side
   long min_clip = 10, clip_support = 3;  // -minclip: shortest clip that counts; -clipsupport: reads at one position a rescued side needs
   long anchor = 10;  // -anchor: bases a reference read must cover on either side of the breakpoint base
   int opt, li;
@@ -1038,6 +1078,11 @@ int main(int argc, char *argv[])
       clipsupport_given = true;
       break;
     case 20: dedup = true; break;
+    case 21: consensus = true; break;
+    case 22:
+      conslen = atol(optarg);
+      conslen_given = true;
+      break;
     default: std::cerr << "Error: cannot parse arguments.\n"; exit(1);
     }
   }
@@ -1133,7 +1178,35 @@ int main(int argc, char *argv[])
       exit(1);
     }
   }
-  if ((minclip_given || clipsupport_given) && !clip)
+  if (conslen_given && !consensus)
+  {
+    std::cerr << HELP << "Error: -conslen needs -consensus.\n";
+    exit(1);
+  }
+  if (consensus)
+  {
+    if (n_gpus >= 1)
+    {
+      std::cerr << HELP << "Error: -consensus cannot be combined with -gpus.\n";
+      exit(1);
+    }
+    if (!bk_clip_consensus || !bk_clip_reads || !bk_evidence || !bk_junctions || !bk_junction_sides)
+    {
+      std::cerr << "Error: -consensus needs the GPU library" << std::endl;
+      exit(1);
+    }
+    if (conslen < 1 || conslen > 256)
+    {
+      std::cerr << HELP << "Error: -conslen must be a number from 1 to 256.\n";
+      exit(1);
+    }
+    if (min_clip < 1 || min_clip > 0x7FFFFFFFl)
+    {
+      std::cerr << HELP << "Error: -minclip must be a number from 1 to 2147483647.\n";
+      exit(1);
+    }
+  }
+  if ((minclip_given && !clip && !consensus) || (clipsupport_given && !clip))
   {
     std::cerr << HELP << "Error: -minclip and -clipsupport need -clip.\n";
     exit(1);
@@ -1426,7 +1499,7 @@ int main(int argc, char *argv[])
   }
   // -vcf: the junction evidence of every call (member pairs by strands, split tuples by clip side)
   vector<struct bk_junction> jsup;
-  if (vcf || clip)
+  if (vcf || clip || consensus)
   {
     const struct bk_junction *js = nullptr;
     uint64_t n_js = 0;
@@ -1454,7 +1527,7 @@ int main(int argc, char *argv[])
   // -evidence: the reads behind every call (one row per member pair and per matching split tuple), listed on the device
   vector<struct bk_evidence> ev_rows;
   vector<uint64_t> ev_off;
-  if (evidence)
+  if (evidence || consensus)
   {
     const struct bk_evidence *ev = nullptr;
     const uint64_t *off = nullptr;
@@ -1636,7 +1709,69 @@ int main(int argc, char *argv[])
       }
     }
   }
+  // -consensus: the clipped bases at the two breakpoints of every written call.  Sites: side s of a call is (ps_tid, ps_exact, 0, d_s),
+  // d_s from bk_junction_sides.  Reads: those of the call's BK_EV_SPLIT rows, and those bk_clip_reads lists at the sites (the reads
+  // without an SA tag), each name once.  One pass over the file brings their alignments back with the bases, one call piles them up.
+  std::map<uint64_t, std::pair<ConsensusSide, ConsensusSide>> cons;
+  if (consensus)
+  {
+    vector<struct bk_clip_site> sites;
+    vector<uint64_t> site_call;
+    std::set<std::pair<uint64_t, uint32_t>> seen;
+    vector<bk_read_key> keys;
+    auto add_key = [&](uint64_t qhash, uint32_t qcheck) {
+      if (seen.emplace(qhash, qcheck).second) keys.push_back(bk_read_key{qhash, qcheck, 0});
+    };
+    for (const OutRow &r : rows)
+    {
+      if (!call_written(r, !filter)) continue;
+      if (r.idx >= jsup.size() || r.idx + 1 >= ev_off.size() || ev_off[r.idx + 1] > ev_rows.size())
+      {
+        std::cerr << "Error: the evidence tables do not cover every call" << std::endl;
+        exit(1);
+      }
+      uint8_t right[2] = {0, 1}, source = 0;
+      bk_junction_sides(&jsup[r.idx], &right[0], &right[1], &source);
+      site_call.push_back(r.idx);
+      sites.push_back(bk_clip_site{r.c.p1_tid, r.c.p1_exact, 0u, right[0]});
+      sites.push_back(bk_clip_site{r.c.p2_tid, (uint32_t) r.c.p2_exact, 0u, right[1]});
+      for (uint64_t i = ev_off[r.idx]; i < ev_off[r.idx + 1]; ++i)
+        if (ev_rows[i].kind == BK_EV_SPLIT) add_key(ev_rows[i].qhash, ev_rows[i].qcheck);
+    }
+    {
+      const uint32_t *counts = nullptr;
+      const struct bk_clip_read *cr = nullptr;
+      const uint64_t *off = nullptr;
+      if ((rc = bk_clip_reads(ctx, sites.data(), sites.size(), qual, (int) min_clip, &counts, &cr, &off)) != BK_OK) die(rc);
+      for (uint64_t i = 0; i < off[sites.size()]; ++i) add_key(cr[i].qhash, cr[i].qcheck);
+    }
+    bk_reads reads;
+    char rerr[512] = "";
+    if (bk_bam_reads(inp_file.c_str(), keys.data(), keys.size(), &reads, rerr, sizeof rerr) != BK_OK)
+    {
+      std::cerr << "Error: cannot read the clipped reads back from " << inp_file << ": " << rerr << std::endl;
+      exit(1);
+    }
+    const struct bk_consensus *cs = nullptr;
+    const uint8_t *bases = nullptr;
+    rc = bk_clip_consensus(ctx, &reads, sites.data(), sites.size(), qual, (int) min_clip, (uint32_t) conslen, CONSENSUS_MIN_DEPTH, &cs, &bases, nullptr);
+    bk_reads_free(&reads);
+    if (rc != BK_OK) die(rc);
+    for (size_t j = 0; j < site_call.size(); ++j)
+    {
+      std::pair<ConsensusSide, ConsensusSide> &both = cons[site_call[j]];
+      for (int s = 0; s < 2; ++s)
+      {
+        ConsensusSide &side = s ? both.second : both.first;
+        side.c = cs[2 * j + s];
+        const uint8_t *b = bases + (2 * j + s) * (size_t) conslen;
+        side.seq.assign((const char *) b, side.c.len);
+        if (sites[2 * j + s].dir == 1u) std::reverse(side.seq.begin(), side.seq.end());
+      }
+    }
+  }
   std::ofstream out, outf, out_n, outf_n;  // (_n: the twins with the matched normal's four counts)
+  std::ofstream out_s, outf_s;             // (_s: the twins with the junction consensus, -consensus)
   std::ofstream out_g, outf_g;             // (_g: the twins with the genotype columns, -genotype)
   std::ofstream out_c, outf_c, out_r;      // (_c: the twins with the clip columns, _r: the rescued clusters, -clip)
   std::ofstream out_d, outf_d;             // (_d: the twins with the unique-support columns, -dedup)
@@ -1647,6 +1782,7 @@ int main(int argc, char *argv[])
   header_g += "\n";
   const string header_c = string(HEADER, strlen(HEADER) - 1) + CLIP_COLUMNS + (with_normal ? CLIP_COLUMNS_NORMAL : "") + "\n";
   const string header_d = string(HEADER, strlen(HEADER) - 1) + DEDUP_COLUMNS + "\n";
+  const string header_s = string(HEADER, strlen(HEADER) - 1) + CONSENSUS_COLUMNS + "\n";
   if (!filter)
   {
     out.open((out_file + "_fusion_all.txt").c_str());
@@ -1655,6 +1791,11 @@ int main(int argc, char *argv[])
     {
       out_d.open((out_file + "_fusion_all_dedup.txt").c_str());
       out_d << header_d;
+    }
+    if (consensus)
+    {
+      out_s.open((out_file + "_fusion_all_consensus.txt").c_str());
+      out_s << header_s;
     }
     if (with_normal)
     {
@@ -1678,6 +1819,11 @@ int main(int argc, char *argv[])
   {
     outf_d.open((out_file + "_fusion_dedup.txt").c_str());
     outf_d << header_d;
+  }
+  if (consensus)
+  {
+    outf_s.open((out_file + "_fusion_consensus.txt").c_str());
+    outf_s << header_s;
   }
   if (with_normal)
   {
@@ -1739,6 +1885,16 @@ int main(int argc, char *argv[])
       if (filt_ok) write_row(outf_d, r, nullptr, nullptr, nullptr, nullptr, &t);
       if (!filter && all_ok) write_row(out_d, r, nullptr, nullptr, nullptr, nullptr, &t);
     }
+    if (consensus && cons.count(r.idx))
+    {
+      const std::pair<ConsensusSide, ConsensusSide> &both = cons.at(r.idx);
+      std::ostringstream tail;
+      for (const ConsensusSide *x : {&both.first, &both.second})
+        tail << "\t" << x->c.n_reads << "\t" << x->c.len << "\t" << x->agree() << "\t" << (x->seq.empty() ? "." : x->seq);
+      const string t = tail.str();
+      if (filt_ok) write_row(outf_s, r, nullptr, nullptr, nullptr, nullptr, &t);
+      if (!filter && all_ok) write_row(out_s, r, nullptr, nullptr, nullptr, nullptr, &t);
+    }
     if (with_normal && r.idx < n_nsup)
     {
       if (filt_ok) write_row(outf_n, r, &nsup[r.idx]);
@@ -1774,6 +1930,11 @@ int main(int argc, char *argv[])
     if (!filter) out_d.close();
     outf_d.close();
   }
+  if (consensus)
+  {
+    if (!filter) out_s.close();
+    outf_s.close();
+  }
   if (vcf)
   {
     VcfInput vi;
@@ -1789,6 +1950,7 @@ int main(int argc, char *argv[])
     vi.gsup = genotype ? &gsup : nullptr;
     vi.gsup_normal = genotype && with_normal ? &gsup_normal : nullptr;
     vi.usup = dedup ? &usup : nullptr;
+    vi.cons = consensus ? &cons : nullptr;
     if (!write_vcf(out_file + "_fusion.vcf", rows, vi))
     {
       std::cerr << "Error: cannot write " << out_file << "_fusion.vcf: the evidence tables do not cover every call" << std::endl;
@@ -1798,6 +1960,7 @@ int main(int argc, char *argv[])
     {
       vi.gsup = vi.gsup_normal = nullptr;  // rescued calls are not genotyped
       vi.usup = nullptr;                   // ... and their files stay as they are with -dedup
+      vi.cons = nullptr;                   // ... and with -consensus
       vi.rescued = &rescued_calls;
       if (!write_vcf(out_file + "_fusion_rescued.vcf", rescued, vi))
       {
@@ -1843,6 +2006,7 @@ int main(int argc, char *argv[])
     if (clip) p << "clip_min_length\t" << min_clip << std::endl;
     if (clip) p << "clip_min_support\t" << clip_support << std::endl;
     if (dedup) p << "dedup\t1" << std::endl;
+    if (consensus) p << "consensus_max_len\t" << conslen << std::endl;
   }
   clock_t end = clock();
   std::cout << "the fusion process of file " << inp_file << "  costs time: " << (end - start) / double(CLOCKS_PER_SEC) << " seconds" << std::endl;

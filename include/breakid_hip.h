@@ -430,6 +430,57 @@ struct bk_unique_support { uint32_t uniq_pairs, top_pairs, uniq_splits, top_spli
  * clusters but neither mtid / mpos columns nor bk_side rows.  A context without clusters is no error: *count = 0, *n_rows = 0. */
 int bk_unique_support(bk_ctx *ctx, const struct bk_unique_support **out, uint64_t *count, const uint64_t **first, uint64_t *n_rows);
 
+/* ---- junction consensus: what the clipped reads read across a breakpoint ------------------------------------------------------
+ * bk_clip_reads says which reads are clipped at a site; bk_clip_consensus says what their clipped bases are: per site the clipped
+ * bases are piled up column by column, counting away from the junction, and every column votes one base.  No layer of a context
+ * carries SEQ, so the alignments come as a table of their own, bk_reads, in host memory: what bk_bam_reads (below, with the host
+ * feed) brings back for a set of read names, or columns the caller built.  Base q of read i is in byte seq_off[i] + q / 2 of seq,
+ * the high nibble when q is even, in BAM's 4-bit codes (=ACMGRSVTWYHKDBN); every read starts on a byte. */
+typedef struct bk_reads {       /* a table of its own, not a context's record table; host memory */
+  uint64_t n;
+  const int32_t *tid, *pos;     /* pos 0-based */
+  const uint16_t *flag;
+  const uint8_t *mapq;
+  const uint32_t *key;          /* index of the bk_read_key that selected the alignment (bk_bam_reads; bk_clip_consensus does not read it) */
+  const uint32_t *cigar_off;    /* n + 1 */
+  const uint32_t *cigar;        /* BAM words, len << 4 | op */
+  const uint32_t *l_seq;
+  const uint64_t *seq_off;      /* n + 1, in bytes */
+  const uint8_t *seq;
+  void *owner;                  /* bk_reads_free */
+} bk_reads;
+/* All comparisons in signed 64-bit.
+ * Eligible alignment i of `reads`: tid[i] >= 0, flag has none of 0x4 0x200 0x400 (0x100 and 0x800 are allowed: the second part of a
+ * chimeric read is what the far side needs, and a hard-clipped one has no S op and so no event), mapq[i] >= mapq_min, its CIGAR has
+ * a reference length > 0, l_seq[i] > 0 and l_seq[i] equals the CIGAR's query length (M, I, S, =, X).
+ * Events: (tid, p, dir) and the clip length c = the length of the S op are those bk_clip_support (above) defines, leading and
+ * trailing, with min_clip; nothing of it is restated here.  The one difference: there is no aux condition (a bk_reads table has no
+ * aux column), so reads with an SA tag count here.
+ * Membership: an event belongs to site k when tid == sites[k].tid, dir == sites[k].dir and p == sites[k].pos (sites[k].tol must be 0).
+ * Equal sites each get the event; a site with tid < 0 gets nothing.
+ * Columns count bases away from the junction, 0 <= j < min(c, max_len): of a trailing clip (LEFT) column j is base l_seq - c + j, of
+ * a leading clip (RIGHT) base c - 1 - j (leading H ops hold no bases).
+ * Per site k and column j: depth[j] = the number of events with c > j (it does not increase with j); counts are kept for A, C, G, T
+ * (codes 1, 2, 4, 8), every other code counts in depth only.
+ *   len                      the number of columns with depth[j] >= min_depth
+ *   bases[k * max_len + j]   j < len: the most frequent of A, C, G, T, on a tie the smaller in the order A < C < G < T, 'N' when all
+ *                            four counts are 0; j >= len: 0
+ *   match, total             sums over j < len of the winning count and of depth[j]
+ *   n_reads                  the number of events of the site
+ *   col_depth[k * max_len + j] = depth[j] for every j < max_len
+ * Every output is an integer sum or an argmax with a fixed tie rule: two runs, and any permutation of the rows of `reads`, give the
+ * same bytes.  The struct has no typedef: the name belongs to the call below. */
+struct bk_consensus { uint32_t n_reads, len, match, total; };   /* 16 bytes */
+/* ctx: any live context that is not a shard (bk_shard_*); it gives the device, the stream, the buffers and bk_timing (scope
+ * `consensus`).  No stage needs to have run and nothing a later bk_fetch or stage returns changes.  reads, sites: host memory.
+ * *out (n_sites rows), *bases and *col_depth (n_sites * max_len entries each) are library-owned until the next call or bk_free(ctx);
+ * col_depth may be NULL: not wanted.  BK_ERR_ARG (with the reason in bk_last_error) for shards, null ctx / reads / out / bases, null
+ * sites with n_sites > 0, a null column of a table with n > 0, max_len outside 1..256, min_depth == 0, min_clip < 1, mapq_min < 0, a
+ * dir above 1, tol != 0, cigar_off or seq_off that do not ascend, and a seq_off span shorter than (l_seq + 1) / 2 bytes.
+ * BK_ERR_LIMIT beyond 2^32 reads, 2^30 sites or 2^32 events that belong to a site.  n_sites == 0 or reads->n == 0 is no error. */
+int bk_clip_consensus(bk_ctx *ctx, const bk_reads *reads, const struct bk_clip_site *sites, uint64_t n_sites, int mapq_min, int min_clip, uint32_t max_len,
+                      uint32_t min_depth, const struct bk_consensus **out, const uint8_t **bases, const uint32_t **col_depth);
+
 /* Copy a stage's result to library-owned host memory.  *data stays valid until the next bk_fetch
  * of the same stage or bk_free.  group_off (may be NULL) receives n_groups+1 offsets for pair stages. */
 int bk_fetch(bk_ctx *ctx, int stage, const void **data, uint64_t *count, const uint64_t **group_off, uint32_t *n_groups);
@@ -565,6 +616,14 @@ typedef struct bk_read_key { uint64_t qhash; uint32_t qcheck; uint32_t tag; } bk
 int bk_bam_extract(const char *in_bam, const char *out_bam, const bk_read_key *keys, uint64_t n_keys, const char *const *tags, uint64_t n_tags, char **names_out,
                    uint64_t *n_written, char *err, size_t errlen);
 void bk_bam_names_free(char *names);
+/* The alignments of named reads with their bases: the pass of bk_bam_extract (selection by keys, streaming, both file layouts,
+ * memory bound, error codes; keys[k].tag is not read) with a table as its result instead of a file.  Rows are in file order;
+ * key[i] is the first key that selects row i, as bk_bam_extract picks its tag; a record with l_seq == 0 is kept with an empty
+ * sequence; an empty key set gives n == 0 and is no error.  The table is host memory that bk_reads_free gives back (it zeroes the
+ * struct; a table the call did not fill, or filled with an error, needs no free).  BK_ERR_ARG also for a null out, BK_ERR_LIMIT
+ * beyond 2^32 keys or CIGAR words. */
+int bk_bam_reads(const char *in_bam, const bk_read_key *keys, uint64_t n_keys, bk_reads *out, char *err, size_t errlen);
+void bk_reads_free(bk_reads *r);
 
 /* The same feed on the GPU: BGZF blocks are inflated on the device (bgzf_gpu.hip) and the records are decoded into
  * device-resident columns (cols holds device pointers: bk_upload_records(ctx, cols, BK_MEM_DEVICE)).
