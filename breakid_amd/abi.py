@@ -42,6 +42,13 @@ assert CONSENSUS.itemsize == 16
 # the columns of a bk_reads table, in the struct's order (cigar_off and seq_off have n + 1 entries)
 READS_COLS = [("tid", np.int32), ("pos", np.int32), ("flag", np.uint16), ("mapq", np.uint8), ("key", np.uint32), ("cigar_off", np.uint32), ("cigar", np.uint32),
               ("l_seq", np.uint32), ("seq_off", np.uint64), ("seq", np.uint8)]
+JUNCTION_PROBE = np.dtype([("tid_own", "<i4"), ("pos_own", "<u4"), ("dir_own", "<u4"), ("tid_mate", "<i4"), ("pos_mate", "<u4"), ("dir_mate", "<u4"), ("qlen", "<u4"),
+                           ("reserved", "<u4")])  # struct bk_junction_probe
+JUNCTION_FIT = np.dtype([("shift", "<i4"), ("ins", "<u4"), ("aligned", "<u4"), ("mism", "<u4"), ("hom_fwd", "<u4"), ("hom_back", "<u4"), ("score", "<i4"),
+                         ("placed", "<u4")])  # struct bk_junction_fit
+assert JUNCTION_PROBE.itemsize == 32 and JUNCTION_FIT.itemsize == 32
+# the columns of a bk_refseq table, in the struct's order (off has n_segs + 1 entries)
+REFSEQ_COLS = [("tid", np.int32), ("start", np.uint32), ("len", np.uint32), ("off", np.uint64), ("bases", np.uint8)]
 READ_KEY = np.dtype([("qhash", "<u8"), ("qcheck", "<u4"), ("tag", "<u4")])  # bk_read_key
 assert EVIDENCE.itemsize == 48 and READ_KEY.itemsize == 16
 assert PAIR.itemsize == 56 and SPLIT.itemsize == 88 and CLUSTER.itemsize == 72 and NORMAL_SUPPORT.itemsize == 16 and REF_SUPPORT.itemsize == 16
@@ -52,6 +59,10 @@ STAGE_DTYPE = {STAGE_SCAN: PAIR, STAGE_ISO: PAIR, STAGE_CLUSTERED: PAIR, STAGE_S
 
 class Reads(C.Structure):  # bk_reads
     _fields_ = [("n", C.c_uint64)] + [(name, C.c_void_p) for name, _ in READS_COLS] + [("owner", C.c_void_p)]
+
+
+class RefSeq(C.Structure):  # bk_refseq
+    _fields_ = [("n_segs", C.c_uint64)] + [(name, C.c_void_p) for name, _ in REFSEQ_COLS]
 
 
 class Soa(C.Structure):

@@ -18,6 +18,7 @@
 #include "evidence.h"
 #include "unique.h"
 #include "consensus.h"
+#include "jfit.h"
 #include "exclude.h"
 #include "ahc.h"
 #include "lanes.h"
@@ -150,6 +151,9 @@ struct bk_ctx
   std::vector<struct bk_consensus> f_cons;
   std::vector<uint8_t> f_cons_bases;
   std::vector<uint32_t> f_cons_depth;
+  // junction fit (bk_junction_fit)
+  JfitBufs jfb;
+  std::vector<struct bk_junction_fit> f_jfit;
 
   // fetch staging
   std::vector<bk_pair> f_pairs[3];
@@ -1286,6 +1290,66 @@ int bk_clip_consensus(bk_ctx *ctx, const bk_reads *reads, const struct bk_clip_s
     *out = ctx->f_cons.data();
     *bases = ctx->f_cons_bases.data();
     if (col_depth) *col_depth = ctx->f_cons_depth.data();
+  });
+}
+
+int bk_junction_fit(bk_ctx *ctx, const bk_refseq *ref, const struct bk_junction_probe *probes, uint64_t n, const uint8_t *query, uint32_t max_len, uint32_t max_shift,
+                    uint32_t max_ins, uint32_t max_hom, const struct bk_junction_fit **out)
+{
+  return guarded(ctx, [&] {
+    if (!ref || !out) throw bk_error(BK_ERR_ARG, "bk_junction_fit: null ref or out");
+    if (n && (!probes || !query)) throw bk_error(BK_ERR_ARG, "bk_junction_fit: null probes or query");
+    if (ctx->shard) throw bk_error(BK_ERR_ARG, "bk_junction_fit: sharded contexts (bk_shard_*) are not supported");
+    if (max_len < 1 || max_len > 256) throw bk_error(BK_ERR_ARG, "bk_junction_fit: max_len must be 1..256");
+    if (max_shift > 64) throw bk_error(BK_ERR_ARG, "bk_junction_fit: max_shift must be 0..64");
+    if (max_ins > 64) throw bk_error(BK_ERR_ARG, "bk_junction_fit: max_ins must be 0..64");
+    if (max_hom > 64) throw bk_error(BK_ERR_ARG, "bk_junction_fit: max_hom must be 0..64");
+    if (n > 0x40000000ull) throw bk_error(BK_ERR_LIMIT, "bk_junction_fit: more than 2^30 probes");
+    const bk_refseq &t = *ref;
+    if (t.n_segs > 0x100000ull) throw bk_error(BK_ERR_LIMIT, "bk_junction_fit: more than 2^20 segments");
+    if (t.n_segs && (!t.tid || !t.start || !t.len || !t.off)) throw bk_error(BK_ERR_ARG, "bk_junction_fit: the reference table lacks a column");
+    for (uint64_t g = 0; g < t.n_segs; ++g)
+    {
+      if (t.off[g + 1] < t.off[g]) throw bk_error(BK_ERR_ARG, "bk_junction_fit: off does not ascend at segment " + std::to_string(g));
+      if (t.off[g + 1] - t.off[g] < ((uint64_t) t.len[g] + 1) / 2)
+        throw bk_error(BK_ERR_ARG, "bk_junction_fit: segment " + std::to_string(g) + " has fewer bytes than (len + 1) / 2");
+      if (g + 1 < t.n_segs)
+      {
+        if (t.tid[g + 1] < t.tid[g] || (t.tid[g + 1] == t.tid[g] && t.start[g + 1] < t.start[g]))
+          throw bk_error(BK_ERR_ARG, "bk_junction_fit: segment " + std::to_string(g + 1) + " is out of order (the segments ascend by tid, then start)");
+        if (t.tid[g + 1] == t.tid[g] && (long long) t.start[g] + (long long) t.len[g] > (long long) t.start[g + 1])
+          throw bk_error(BK_ERR_ARG, "bk_junction_fit: segment " + std::to_string(g + 1) + " overlaps the one before it");
+      }
+    }
+    if (t.n_segs && t.off[t.n_segs] && !t.bases) throw bk_error(BK_ERR_ARG, "bk_junction_fit: the reference table lacks a column");
+    uint64_t qbytes = 0, walk_bases = 0;
+    for (uint64_t k = 0; k < n; ++k)
+    {
+      const struct bk_junction_probe &p = probes[k];
+      if (p.dir_own > 1u || p.dir_mate > 1u) throw bk_error(BK_ERR_ARG, "bk_junction_fit: probe " + std::to_string(k) + " has a dir above 1 (0 = LEFT, 1 = RIGHT)");
+      if (p.qlen > max_len) throw bk_error(BK_ERR_ARG, "bk_junction_fit: probe " + std::to_string(k) + " has a qlen above max_len");
+      const uint8_t *q = query + k * max_len;
+      for (uint32_t j = 0; j < p.qlen; ++j)
+        if (q[j] != 'A' && q[j] != 'C' && q[j] != 'G' && q[j] != 'T' && q[j] != 'N')
+          throw bk_error(BK_ERR_ARG, "bk_junction_fit: probe " + std::to_string(k) + " has a query byte outside ACGTN in column " + std::to_string(j));
+      if (p.qlen >= 1 && p.tid_own >= 0 && p.tid_mate >= 0)
+      {
+        qbytes += p.qlen;
+        walk_bases += 2ull * p.qlen + 2ull * max_shift + 2ull * max_hom;  // the mate walk -(S + H) .. qlen + S - 1, the own walk -H .. qlen - 1
+      }
+    }
+    struct bk_junction_fit *d_res;
+    jfit_upload(t, probes, n, query, max_len, ctx->jfb, ctx->st);  // (outside the scope: it times the work on the device copy)
+    {
+      // bytes: the probes, their queries and the result once; the reference segments once
+      Scope s(ctx, "junction_fit", n * (sizeof(struct bk_junction_probe) + sizeof(struct bk_junction_fit) + (uint64_t) max_len) + t.n_segs * 24ull +
+                                       (t.n_segs ? t.off[t.n_segs] : 0));
+      junction_fit(n, max_len, max_shift, max_ins, max_hom, ctx->jfb, ctx->st, &d_res);
+    }
+    rows_to_host(ctx, d_res, n, ctx->f_jfit);
+    // touched: the probe row, qlen query bytes, the nibbles of both walks and the result row
+    if (ctx->timing && !ctx->timers.empty()) ctx->timers.back().touched = n * (sizeof(struct bk_junction_probe) + sizeof(struct bk_junction_fit)) + qbytes + (walk_bases + 1) / 2;
+    *out = ctx->f_jfit.data();
   });
 }
 

@@ -16,6 +16,7 @@
 #include <fstream>
 #include <iostream>
 #include <map>
+#include <memory>
 #include <set>
 #include <sstream>
 #include <string>
@@ -42,6 +43,9 @@ extern "C" int bk_evidence(bk_ctx *ctx, const struct bk_evidence **out, uint64_t
 // -consensus: the same for the junction consensus (the CPU build refuses -consensus)
 extern "C" int bk_clip_consensus(bk_ctx *ctx, const bk_reads *reads, const struct bk_clip_site *sites, uint64_t n_sites, int mapq_min, int min_clip, uint32_t max_len,
                                  uint32_t min_depth, const struct bk_consensus **out, const uint8_t **bases, const uint32_t **col_depth) __attribute__((weak));
+// -homology: the same for the junction fit (the CPU build refuses -homology)
+extern "C" int bk_junction_fit(bk_ctx *ctx, const bk_refseq *ref, const struct bk_junction_probe *probes, uint64_t n, const uint8_t *query, uint32_t max_len, uint32_t max_shift,
+                               uint32_t max_ins, uint32_t max_hom, const struct bk_junction_fit **out) __attribute__((weak));
 // -dedup: the same for the unique fragments behind every call (the CPU build refuses -dedup)
 extern "C" int bk_unique_support(bk_ctx *ctx, const struct bk_unique_support **out, uint64_t *count, const uint64_t **first, uint64_t *n_rows) __attribute__((weak));
 // -clip: the same for the soft-clip evidence, the depth at the rescued positions and the rescue rule (the CPU build refuses -clip)
@@ -296,7 +300,10 @@ static const char *HELP =
      \t -minclip   \t shortest soft clip that counts (with -clip)  [10]\n \
      \t -clipsupport \t clipped reads at one position that each side of a rescued cluster needs (with -clip)  [3]\n \
      \t -consensus \t vote the clipped bases at both breakpoints of every call into a junction sequence (twin files *_consensus.txt; CSEQ / CSN with -vcf)  \n \
-     \t -conslen   \t longest junction sequence per side, 1 to 256 (with -consensus)  [64]\n ";
+     \t -conslen   \t longest junction sequence per side, 1 to 256 (with -consensus)  [64]\n \
+     \t -homology  \t fit each junction sequence to the reference at the other breakpoint: offset, inserted bases, microhomology (with -consensus; twin files *_homology.txt; HOMLEN / HOMSEQ / JINS with -vcf)  \n \
+     \t -homshift  \t largest offset of the continuation from the called position, 0 to 64 (with -homology)  [32]\n \
+     \t -homins    \t longest inserted sequence, 0 to 64 (with -homology)  [32]\n ";
 
 // ---- RefSeqTranscript.{h,cc} -------------------------------------------------------------------------------
 struct Txpt
@@ -618,6 +625,28 @@ struct ConsensusSide
     return buf;
   }
 };
+// -homology: the twin files' columns (bk_junction_fit of each side's consensus against the reference at the other side)
+static const char *HOMOLOGY_COLUMNS = "\tJ_Shift1\tJ_Ins1\tJ_Aligned1\tJ_Mism1\tJ_HomLen1\tJ_HomSeq1\tJ_InsSeq1\tJ_Shift2\tJ_Ins2\tJ_Aligned2\tJ_Mism2\tJ_HomLen2\tJ_HomSeq2\tJ_InsSeq2";
+// the homology behind the breakpoint is looked for over this many retained bases
+static const uint32_t HOMOLOGY_MAX_HOM = 32;
+
+// One side of a written call: its bk_junction_fit row (on: the side was submitted and placed), the own contig's bases over the
+// homologous stretch, reference-forward, and the inserted columns as the BAM reads them (reversed for a RIGHT side, as Cons_Seq is)
+struct HomologySide
+{
+  bool on = false;
+  struct bk_junction_fit f = {0, 0, 0, 0, 0, 0, 0, 0};
+  string hom_seq, ins_seq;
+  uint32_t hom_len() const { return f.hom_fwd + f.hom_back; }
+  string fields() const
+  {
+    if (!on) return "\t.\t.\t.\t.\t.\t.\t.";
+    std::ostringstream o;
+    o << "\t" << f.shift << "\t" << f.ins << "\t" << f.aligned << "\t" << f.mism << "\t" << hom_len() << "\t" << (hom_seq.empty() ? "." : hom_seq) << "\t"
+      << (ins_seq.empty() ? "." : ins_seq);
+    return o.str();
+  }
+};
 // -clip -normal: what _fusion_rescued_normal.txt adds to a row of _fusion_rescued.txt
 static const char *RESCUED_COLUMNS_NORMAL = "\tNormal_DRP\tNormal_ClipAt1\tNormal_ClipAt2\tNormal_Depth1\tNormal_Depth2";
 
@@ -659,6 +688,8 @@ struct VcfInput
   // -consensus (else null; never for the rescued clusters): the two sides of every written call by its BK_STAGE_CLUSTERS row; INFO/CSEQ
   // and INFO/CSN behind everything else
   const std::map<uint64_t, std::pair<ConsensusSide, ConsensusSide>> *cons = nullptr;
+  // -homology (else null; needs cons): the same for the junction fit; HOMLEN / HOMSEQ / JINS / JAL / JMM / JSH behind CSN
+  const std::map<uint64_t, std::pair<HomologySide, HomologySide>> *hom = nullptr;
 };
 
 static char nib_base(const string &nib_dir, const string &chr, long pos1)  // the base at a 1-based position; N without a file or beyond it
@@ -750,6 +781,16 @@ static bool write_vcf(const string &path, const vector<OutRow> &rows, const VcfI
           if (!cs.seq.empty()) o << ";CSEQ=" << cs.seq;
           o << ";CSN=" << cs.c.n_reads;
         }
+        if (in.cons && in.hom && in.hom->count(r.idx))
+        {
+          const HomologySide &h = s ? in.hom->at(r.idx).second : in.hom->at(r.idx).first;
+          if (h.on)
+          {
+            if (h.hom_len()) o << ";HOMLEN=" << h.hom_len() << ";HOMSEQ=" << h.hom_seq;
+            if (!h.ins_seq.empty()) o << ";JINS=" << h.ins_seq;
+            o << ";JAL=" << h.f.aligned << ";JMM=" << h.f.mism << ";JSH=" << h.f.shift;
+          }
+        }
         o << "\t" << (in.gsup ? "GT:GQ:DR:DV:RR:RV" : "DV:RV") << "\t" << vcf_sample(r.c.n_drp, r.c.n_sr, in.gsup ? &(*in.gsup)[r.idx] : nullptr, s);
         if (in.with_normal) o << "\t" << vcf_sample(in.nsup[r.idx].n_drp, in.nsup[r.idx].n_sr, in.gsup_normal ? &(*in.gsup_normal)[r.idx] : nullptr, s);
       }
@@ -786,6 +827,13 @@ static bool write_vcf(const string &path, const vector<OutRow> &rows, const VcfI
   if (in.cons && !in.rescued)
     v << "##INFO=<ID=CSEQ,Number=1,Type=String,Description=\"Consensus of the bases soft-clipped at this breakpoint, in the orientation of the alignments\">\n"
          "##INFO=<ID=CSN,Number=1,Type=Integer,Description=\"Reads soft-clipped exactly at this breakpoint that the consensus was voted from\">\n";
+  if (in.cons && in.hom && !in.rescued)
+    v << "##INFO=<ID=HOMLEN,Number=1,Type=Integer,Description=\"Length of base pair identical micro-homology at event breakpoints\">\n"
+         "##INFO=<ID=HOMSEQ,Number=1,Type=String,Description=\"Sequence of base pair identical micro-homology at event breakpoints\">\n"
+         "##INFO=<ID=JINS,Number=1,Type=String,Description=\"Bases between the two sides that neither templates, in the orientation of the alignments at this breakpoint\">\n"
+         "##INFO=<ID=JAL,Number=1,Type=Integer,Description=\"Bases of CSEQ placed in the reference at the mate breakpoint\">\n"
+         "##INFO=<ID=JMM,Number=1,Type=Integer,Description=\"Mismatches among the JAL placed bases\">\n"
+         "##INFO=<ID=JSH,Number=1,Type=Integer,Description=\"Offset of the placed sequence from the mate breakpoint, in bases into the mate's retained sequence\">\n";
   if (in.rescued) v << "##INFO=<ID=SC,Number=1,Type=Integer,Description=\"Soft-clipped reads without an SA tag that end at this position (the clip peak)\">\n";
   if (in.gsup)
     v << "##FORMAT=<ID=GT,Number=1,Type=String,Description=\"Genotype\">\n"
@@ -1033,13 +1081,15 @@ int main(int argc, char *argv[])
                                      {"comm", 1, 0, 10},  {"normal", 1, 0, 11}, {"x", 1, 0, 12}, {"genotype", 0, 0, 13},
                                      {"anchor", 1, 0, 14}, {"vcf", 0, 0, 15}, {"evidence", 0, 0, 16}, {"clip", 0, 0, 17},
                                      {"minclip", 1, 0, 18}, {"clipsupport", 1, 0, 19}, {"dedup", 0, 0, 20}, {"consensus", 0, 0, 21},
-                                     {"conslen", 1, 0, 22}, {0, 0, 0, 0}};
+                                     {"conslen", 1, 0, 22}, {"homology", 0, 0, 23}, {"homshift", 1, 0, 24}, {"homins", 1, 0, 25}, {0, 0, 0, 0}};
   string inp_file, out_file, nib_dir, normal_file, exclude_file, build = "hg19";
   int qual = 20, device = 0, n_gpus = 0, transport = BK_TRANSPORT_AUTO;  // -gpus N: one sample over N GPUs (include/breakid_multi.h)
   bool fast = false, filter = true, genotype = false, anchor_given = false, vcf = false, evidence = false;
   bool clip = false, minclip_given = false, clipsupport_given = false, dedup = false;
   bool consensus = false, conslen_given = false;
   long conslen = 64;  // -conslen: longest junction sequence per side
+  bool homology = false, homshift_given = false, homins_given = false;
+  long homshift = 32, homins = 32;  // -homshift, -homins: the largest offset and the longest insertion bk_junction_fit looks for
   long min_clip = 10, clip_support = 3;  // -minclip: shortest clip that counts; -clipsupport: reads at one position a rescued side needs
   long anchor = 10;  // -anchor: bases a reference read must cover on either side of the breakpoint base
   int opt, li;
@@ -1082,6 +1132,15 @@ int main(int argc, char *argv[])
     case 22:
       conslen = atol(optarg);
       conslen_given = true;
+      break;
+    case 23: homology = true; break;
+    case 24:
+      homshift = atol(optarg);
+      homshift_given = true;
+      break;
+    case 25:
+      homins = atol(optarg);
+      homins_given = true;
       break;
     default: std::cerr << "Error: cannot parse arguments.\n"; exit(1);
     }
@@ -1175,6 +1234,34 @@ int main(int argc, char *argv[])
     if (!bk_unique_support)
     {
       std::cerr << "Error: -dedup needs the GPU library" << std::endl;
+      exit(1);
+    }
+  }
+  if ((homshift_given || homins_given) && !homology)
+  {
+    std::cerr << HELP << "Error: -homshift and -homins need -homology.\n";
+    exit(1);
+  }
+  if (homology)
+  {
+    if (!consensus)
+    {
+      std::cerr << HELP << "Error: -homology needs -consensus.\n";
+      exit(1);
+    }
+    if (n_gpus >= 1)
+    {
+      std::cerr << HELP << "Error: -homology cannot be combined with -gpus.\n";
+      exit(1);
+    }
+    if (!bk_junction_fit)
+    {
+      std::cerr << "Error: -homology needs the GPU library" << std::endl;
+      exit(1);
+    }
+    if (homshift < 0 || homshift > 64 || homins < 0 || homins > 64)
+    {
+      std::cerr << HELP << "Error: -homshift and -homins must be numbers from 0 to 64.\n";
       exit(1);
     }
   }
@@ -1713,6 +1800,7 @@ int main(int argc, char *argv[])
   // d_s from bk_junction_sides.  Reads: those of the call's BK_EV_SPLIT rows, and those bk_clip_reads lists at the sites (the reads
   // without an SA tag), each name once.  One pass over the file brings their alignments back with the bases, one call piles them up.
   std::map<uint64_t, std::pair<ConsensusSide, ConsensusSide>> cons;
+  std::map<uint64_t, std::pair<HomologySide, HomologySide>> hom;  // -homology: the junction fit of the same sides
   if (consensus)
   {
     vector<struct bk_clip_site> sites;
@@ -1769,9 +1857,125 @@ int main(int argc, char *argv[])
         if (sites[2 * j + s].dir == 1u) std::reverse(side.seq.begin(), side.seq.end());
       }
     }
+    // -homology: one probe per side with a consensus, own = the side's site, mate = the other side's; the query is the side's row of
+    // `bases` as it lies.  The reference: per contig the nib file is opened once and the windows around every probe position are
+    // read, merged where they touch: one segment per window.  One call fits every probe of the run.
+    if (homology)
+    {
+      std::map<int32_t, std::unique_ptr<Nib>> nibs;
+      auto nib_of = [&](int32_t tid) -> Nib * {
+        if (tid < 0 || tid >= nt) return nullptr;
+        auto it = nibs.find(tid);
+        if (it == nibs.end())
+        {
+          it = nibs.emplace(tid, std::unique_ptr<Nib>(new Nib)).first;
+          it->second->open(nib_dir + "/hg19_" + string(names[tid]) + ".nib");
+        }
+        return it->second->ok ? it->second.get() : nullptr;
+      };
+      const long radius = conslen + homshift + (long) HOMOLOGY_MAX_HOM + 1;
+      vector<struct bk_junction_probe> probes;
+      vector<size_t> probe_site;
+      vector<uint8_t> query;
+      std::map<int32_t, vector<std::pair<long, long>>> spans;  // per contig the 1-based windows [a, b]
+      for (size_t x = 0; x < sites.size(); ++x)
+      {
+        const struct bk_clip_site &own = sites[x], &mate = sites[x ^ 1];
+        if (cs[x].len == 0 || !nib_of(own.tid) || !nib_of(mate.tid)) continue;
+        probes.push_back(bk_junction_probe{own.tid, own.pos, own.dir, mate.tid, mate.pos, mate.dir, cs[x].len, 0u});
+        probe_site.push_back(x);
+        query.insert(query.end(), bases + x * (size_t) conslen, bases + (x + 1) * (size_t) conslen);
+        for (const struct bk_clip_site *e : {&own, &mate})
+        {
+          const long a = std::max(1l, (long) e->pos - radius), b = std::min((long) nib_of(e->tid)->nBases, (long) e->pos + radius);
+          if (a <= b) spans[e->tid].emplace_back(a, b);
+        }
+      }
+      vector<int32_t> seg_tid;
+      vector<uint32_t> seg_start, seg_len;
+      vector<uint64_t> seg_off(1, 0);
+      vector<uint8_t> seg_bases;
+      for (auto &kv : spans)
+      {
+        std::sort(kv.second.begin(), kv.second.end());
+        vector<std::pair<long, long>> merged;
+        for (const auto &w : kv.second)
+        {
+          if (!merged.empty() && w.first <= merged.back().second + 1)
+            merged.back().second = std::max(merged.back().second, w.second);
+          else
+            merged.push_back(w);
+        }
+        Nib *nb = nib_of(kv.first);
+        for (const auto &w : merged)
+        {
+          const long start0 = (w.first - 1) & ~1l;  // a segment starts on a byte of the file
+          const long len = w.second - start0;
+          const size_t at = seg_bases.size(), nbytes = (size_t) ((len + 1) / 2);
+          seg_bases.resize(at + nbytes);
+          nb->in.clear();
+          nb->in.seekg(8 + start0 / 2);
+          nb->in.read((char *) seg_bases.data() + at, (std::streamsize) nbytes);
+          if ((size_t) nb->in.gcount() != nbytes)
+          {
+            std::cerr << "Error: " << nib_dir << "/hg19_" << names[kv.first] << ".nib is shorter than its header says" << std::endl;
+            exit(1);
+          }
+          seg_tid.push_back(kv.first);
+          seg_start.push_back((uint32_t) start0);
+          seg_len.push_back((uint32_t) len);
+          seg_off.push_back(seg_bases.size());
+        }
+      }
+      bk_refseq ref;
+      ref.n_segs = seg_tid.size();
+      ref.tid = seg_tid.data();
+      ref.start = seg_start.data();
+      ref.len = seg_len.data();
+      ref.off = seg_off.data();
+      ref.bases = seg_bases.data();
+      const struct bk_junction_fit *fit = nullptr;
+      if ((rc = bk_junction_fit(ctx, &ref, probes.data(), probes.size(), query.data(), (uint32_t) conslen, (uint32_t) homshift, (uint32_t) homins, HOMOLOGY_MAX_HOM, &fit)) !=
+          BK_OK)
+        die(rc);
+      // the base at a 1-based position from the segments read above (N outside them)
+      auto seg_base = [&](int32_t tid, long pos1) -> char {
+        static const char tab[8] = {'T', 'C', 'A', 'G', 'N', 'N', 'N', 'N'};
+        size_t lo = 0, hi = seg_tid.size();  // the segments ascend by (tid, start): the last one that starts at or before pos1
+        while (lo < hi)
+        {
+          const size_t mid = lo + (hi - lo) / 2;
+          if (seg_tid[mid] < tid || (seg_tid[mid] == tid && (long) seg_start[mid] <= pos1 - 1))
+            lo = mid + 1;
+          else
+            hi = mid;
+        }
+        if (lo == 0 || seg_tid[lo - 1] != tid) return 'N';
+        const long i = pos1 - 1 - (long) seg_start[lo - 1];
+        if (i < 0 || i >= (long) seg_len[lo - 1]) return 'N';
+        const uint8_t byte = seg_bases[seg_off[lo - 1] + (size_t) (i / 2)];
+        return tab[((i & 1) ? byte : byte >> 4) & 7];
+      };
+      for (uint64_t call : site_call) hom[call];
+      for (size_t k = 0; k < probes.size(); ++k)
+      {
+        if (!fit[k].placed) continue;
+        const size_t x = probe_site[k];
+        std::pair<HomologySide, HomologySide> &both = hom[site_call[x / 2]];
+        HomologySide &side = (x & 1) ? both.second : both.first;
+        side.on = true;
+        side.f = fit[k];
+        const long pos = probes[k].pos_own, fwd = fit[k].hom_fwd, back = fit[k].hom_back;
+        const bool right = probes[k].dir_own == 1u;
+        for (long p = right ? pos - fwd : pos - back + 1; p <= (right ? pos + back - 1 : pos + fwd); ++p) side.hom_seq += seg_base(probes[k].tid_own, p);
+        side.ins_seq.assign((const char *) query.data() + k * (size_t) conslen, fit[k].ins);
+        if (right) std::reverse(side.ins_seq.begin(), side.ins_seq.end());
+      }
+    }
   }
   std::ofstream out, outf, out_n, outf_n;  // (_n: the twins with the matched normal's four counts)
   std::ofstream out_s, outf_s;             // (_s: the twins with the junction consensus, -consensus)
+  std::ofstream out_h, outf_h;             // (_h: the twins with the junction fit, -homology)
   std::ofstream out_g, outf_g;             // (_g: the twins with the genotype columns, -genotype)
   std::ofstream out_c, outf_c, out_r;      // (_c: the twins with the clip columns, _r: the rescued clusters, -clip)
   std::ofstream out_d, outf_d;             // (_d: the twins with the unique-support columns, -dedup)
@@ -1783,6 +1987,7 @@ int main(int argc, char *argv[])
   const string header_c = string(HEADER, strlen(HEADER) - 1) + CLIP_COLUMNS + (with_normal ? CLIP_COLUMNS_NORMAL : "") + "\n";
   const string header_d = string(HEADER, strlen(HEADER) - 1) + DEDUP_COLUMNS + "\n";
   const string header_s = string(HEADER, strlen(HEADER) - 1) + CONSENSUS_COLUMNS + "\n";
+  const string header_h = string(HEADER, strlen(HEADER) - 1) + HOMOLOGY_COLUMNS + "\n";
   if (!filter)
   {
     out.open((out_file + "_fusion_all.txt").c_str());
@@ -1796,6 +2001,11 @@ int main(int argc, char *argv[])
     {
       out_s.open((out_file + "_fusion_all_consensus.txt").c_str());
       out_s << header_s;
+    }
+    if (homology)
+    {
+      out_h.open((out_file + "_fusion_all_homology.txt").c_str());
+      out_h << header_h;
     }
     if (with_normal)
     {
@@ -1824,6 +2034,11 @@ int main(int argc, char *argv[])
   {
     outf_s.open((out_file + "_fusion_consensus.txt").c_str());
     outf_s << header_s;
+  }
+  if (homology)
+  {
+    outf_h.open((out_file + "_fusion_homology.txt").c_str());
+    outf_h << header_h;
   }
   if (with_normal)
   {
@@ -1895,6 +2110,12 @@ int main(int argc, char *argv[])
       if (filt_ok) write_row(outf_s, r, nullptr, nullptr, nullptr, nullptr, &t);
       if (!filter && all_ok) write_row(out_s, r, nullptr, nullptr, nullptr, nullptr, &t);
     }
+    if (homology && hom.count(r.idx))
+    {
+      const string t = hom.at(r.idx).first.fields() + hom.at(r.idx).second.fields();
+      if (filt_ok) write_row(outf_h, r, nullptr, nullptr, nullptr, nullptr, &t);
+      if (!filter && all_ok) write_row(out_h, r, nullptr, nullptr, nullptr, nullptr, &t);
+    }
     if (with_normal && r.idx < n_nsup)
     {
       if (filt_ok) write_row(outf_n, r, &nsup[r.idx]);
@@ -1935,6 +2156,11 @@ int main(int argc, char *argv[])
     if (!filter) out_s.close();
     outf_s.close();
   }
+  if (homology)
+  {
+    if (!filter) out_h.close();
+    outf_h.close();
+  }
   if (vcf)
   {
     VcfInput vi;
@@ -1951,6 +2177,7 @@ int main(int argc, char *argv[])
     vi.gsup_normal = genotype && with_normal ? &gsup_normal : nullptr;
     vi.usup = dedup ? &usup : nullptr;
     vi.cons = consensus ? &cons : nullptr;
+    vi.hom = homology ? &hom : nullptr;
     if (!write_vcf(out_file + "_fusion.vcf", rows, vi))
     {
       std::cerr << "Error: cannot write " << out_file << "_fusion.vcf: the evidence tables do not cover every call" << std::endl;
@@ -1961,6 +2188,7 @@ int main(int argc, char *argv[])
       vi.gsup = vi.gsup_normal = nullptr;  // rescued calls are not genotyped
       vi.usup = nullptr;                   // ... and their files stay as they are with -dedup
       vi.cons = nullptr;                   // ... and with -consensus
+      vi.hom = nullptr;                    // ... and with -homology
       vi.rescued = &rescued_calls;
       if (!write_vcf(out_file + "_fusion_rescued.vcf", rescued, vi))
       {
@@ -2007,6 +2235,8 @@ int main(int argc, char *argv[])
     if (clip) p << "clip_min_support\t" << clip_support << std::endl;
     if (dedup) p << "dedup\t1" << std::endl;
     if (consensus) p << "consensus_max_len\t" << conslen << std::endl;
+    if (homology) p << "homology_max_shift\t" << homshift << std::endl;
+    if (homology) p << "homology_max_ins\t" << homins << std::endl;
   }
   clock_t end = clock();
   std::cout << "the fusion process of file " << inp_file << "  costs time: " << (end - start) / double(CLOCKS_PER_SEC) << " seconds" << std::endl;

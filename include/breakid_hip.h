@@ -481,6 +481,61 @@ struct bk_consensus { uint32_t n_reads, len, match, total; };   /* 16 bytes */
 int bk_clip_consensus(bk_ctx *ctx, const bk_reads *reads, const struct bk_clip_site *sites, uint64_t n_sites, int mapq_min, int min_clip, uint32_t max_len,
                       uint32_t min_depth, const struct bk_consensus **out, const uint8_t **bases, const uint32_t **col_depth);
 
+/* ---- junction fit: the voted sequence of a side against the reference at the other side -----------------------------------------
+ * bk_clip_consensus says what the clipped reads of a side read across the junction; bk_junction_fit says where that sequence lies in
+ * the partner locus: how much of it continues there (aligned, mism), where exactly the continuation starts (shift), how many bases
+ * that neither side templates lie in between (ins), and how many bases both sides share at the junction (hom_fwd, hom_back).
+ * All comparisons in signed 64-bit.
+ * Reference: bk_refseq, host memory, uploaded per call as bk_reads is.  Base i of segment g is nibble i of the bytes from off[g], the
+ * high nibble first; every segment starts on a byte.  The nibbles are in nib encoding: T = 0, C = 1, A = 2, G = 3, the codes 4..7 are
+ * N, bit 3 is the soft-mask and is ignored; the payload of a .nib file behind its 8-byte header is a valid segment as it lies.
+ * Segments are sorted by (tid, start) and do not overlap (start[g] + len[g] <= start[g + 1] on one tid); they may abut and may leave
+ * gaps.  ref(t, p), the base at the 1-based position p of contig t, is N when t < 0, p < 1 or no segment covers p (segment g covers
+ * start[g] < p <= start[g] + len[g]).  comp() complements a base; comp(N) = N. */
+typedef struct bk_refseq {
+  uint64_t n_segs;
+  const int32_t *tid;
+  const uint32_t *start;        /* 0-based */
+  const uint32_t *len;          /* bases */
+  const uint64_t *off;          /* n_segs + 1, in bytes */
+  const uint8_t *bases;
+} bk_refseq;
+/* Probe k: its own side (tid_own, pos_own, dir_own), the other side of the call (tid_mate, pos_mate, dir_mate), dir 0 = LEFT and
+ * 1 = RIGHT as everywhere else, and its query query[k * max_len + j], j < qlen <= max_len: ASCII A C G T N, column j counting away
+ * from the junction.  That is the layout and the stride of `bases` from bk_clip_consensus (with qlen = len): one call's output is
+ * the next call's input without repacking. */
+struct bk_junction_probe { int32_t tid_own; uint32_t pos_own, dir_own; int32_t tid_mate; uint32_t pos_mate, dir_mate; uint32_t qlen, reserved; };  /* 32 bytes */
+/* Walks, for any integer index:
+ *   own   O[j] = ref(tid_own, pos_own + 1 + j) for LEFT, ref(tid_own, pos_own - 1 - j) for RIGHT; never complemented.  O[0], O[1], ..
+ *         is what the reads would read had they gone on in their own locus; O[-1], O[-2], .. are the last bases they retain.
+ *   mate  M[i] = ref(tid_mate, pos_mate + i) when dir_mate is RIGHT, ref(tid_mate, pos_mate - i) when it is LEFT; complemented iff
+ *         dir_own == dir_mate.  M[0], M[1], .. is the retained sequence of the partner as this side's reads read it.
+ * Placements: 0 <= ins <= min(max_ins, qlen - 1), -max_shift <= shift <= max_shift; column j >= ins is compared with
+ * M[j - ins + shift].  A column matches iff the query byte is one of A C G T and equals the walk's base; everything else is a
+ * mismatch, N on either side included.  aligned = qlen - ins, mism = the mismatching columns, score = aligned - 2 * mism: a match
+ * +1, a mismatch -1, an inserted column 0.  Chosen is the placement with the largest score; on a tie the smaller ins, then the
+ * smaller |shift|, then shift >= 0 before shift < 0.
+ * Why this score: with ins + mism as a cost no insertion is ever reported, since a few random inserted bases cost less as mismatches
+ * on the neighbouring diagonal than as an insertion.  With an inserted column at 0 and a mismatch at 2 relative to a match, a single
+ * mismatch in column 0 reads as ins 1, shift 1 (one non-templated base), and a mismatch in column 1 or later stays a mismatch.  Both
+ * are intended.
+ * Microhomology, counted only when the chosen ins == 0 (else both are 0):
+ *   hom_fwd   the number of leading columns j = 0, 1, .. < qlen with query[j] == O[j] == M[j + shift], all of A C G T
+ *   hom_back  the number of leading i = 0, 1, .. < max_hom with O[-1 - i] == M[shift - 1 - i], both of A C G T
+ * (leading: the count stops at the first index that fails).  placed = 1 iff qlen >= 1 and both tids are >= 0; an unplaced row is
+ * all zeros.  Every output is an integer count or an argmax with a fixed tie rule: two runs, and any permutation of the probes, give
+ * the same bytes row for row.  The structs have no typedef: bk_junction_fit names the call below. */
+struct bk_junction_fit { int32_t shift; uint32_t ins, aligned, mism, hom_fwd, hom_back; int32_t score; uint32_t placed; };  /* 32 bytes */
+/* ctx: any live context that is not a shard (bk_shard_*); it gives the device, the stream, the buffers and bk_timing (scope
+ * `junction_fit`).  No stage needs to have run and nothing a later bk_fetch or stage returns changes.  ref, probes, query: host
+ * memory.  *out (n rows) is library-owned until the next call or bk_free(ctx).  BK_ERR_ARG (with the reason in bk_last_error) for
+ * shards, null ctx / ref / out, null probes or query with n > 0, max_len outside 1..256, max_shift, max_ins or max_hom above 64, a
+ * dir above 1, qlen > max_len, a query byte outside ACGTN within qlen, a null column of a table with n_segs > 0, segments out of
+ * order or overlapping, off that does not ascend, and an off span shorter than (len + 1) / 2 bytes.  BK_ERR_LIMIT beyond 2^30
+ * probes or 2^20 segments.  n == 0 is no error, and neither is n_segs == 0 (every walk is then N). */
+int bk_junction_fit(bk_ctx *ctx, const bk_refseq *ref, const struct bk_junction_probe *probes, uint64_t n, const uint8_t *query, uint32_t max_len, uint32_t max_shift,
+                    uint32_t max_ins, uint32_t max_hom, const struct bk_junction_fit **out);
+
 /* Copy a stage's result to library-owned host memory.  *data stays valid until the next bk_fetch
  * of the same stage or bk_free.  group_off (may be NULL) receives n_groups+1 offsets for pair stages. */
 int bk_fetch(bk_ctx *ctx, int stage, const void **data, uint64_t *count, const uint64_t **group_off, uint32_t *n_groups);
