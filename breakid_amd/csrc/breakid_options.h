@@ -1,0 +1,219 @@
+// BreakID command line: the options (help text src/BreakID.h:27-36 of the reference, and this program's own) and what a command line
+// is refused for.  Included by breakid_main.cc alone.
+#pragma once
+#include <getopt.h>
+
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <iostream>
+#include <string>
+
+#include "../../include/breakid_hip.h"
+#include "../../include/breakid_multi.h"
+
+// The entry points behind the per-call options, looked up at run time (prototypes: include/breakid_hip.h, include/breakid_multi.h), so
+// that this program also links against a library without them: the CPU build of the host code (oracle/Makefile), which refuses the
+// option.  check_options() is the only place that tests them for null.
+extern "C" {
+// -normal
+int bk_normal_support(bk_ctx *tumor, bk_ctx *normal, double w, const struct bk_normal_support **out, uint64_t *count) __attribute__((weak));
+// -genotype
+int bk_ref_support(bk_ctx *calls, bk_ctx *records, int mapq_min, int anchor, double w, const struct bk_ref_support **out, uint64_t *count) __attribute__((weak));
+int bk_genotype_call(uint32_t alt, uint32_t ref, uint8_t *gt, uint8_t *gq, float *vaf) __attribute__((weak));
+// -vcf (the junction evidence and the two breakend rules)
+int bk_junctions(bk_ctx *ctx, const struct bk_junction **out, uint64_t *count) __attribute__((weak));
+int bk_junction_sides(const struct bk_junction *j, uint8_t *right1, uint8_t *right2, uint8_t *source) __attribute__((weak));
+int bk_vcf_breakend_alt(char ref_base, int own_right, const char *mate_chr, uint32_t mate_pos, int mate_right, char *buf, size_t cap) __attribute__((weak));
+// -evidence (bk_bam_extract is host code and always there)
+int bk_evidence(bk_ctx *ctx, const struct bk_evidence **out, uint64_t *count, const uint64_t **call_off) __attribute__((weak));
+// -consensus
+int bk_clip_consensus(bk_ctx *ctx, const bk_reads *reads, const struct bk_clip_site *sites, uint64_t n_sites, int mapq_min, int min_clip, uint32_t max_len, uint32_t min_depth,
+                      const struct bk_consensus **out, const uint8_t **bases, const uint32_t **col_depth) __attribute__((weak));
+// -homology
+int bk_junction_fit(bk_ctx *ctx, const bk_refseq *ref, const struct bk_junction_probe *probes, uint64_t n, const uint8_t *query, uint32_t max_len, uint32_t max_shift,
+                    uint32_t max_ins, uint32_t max_hom, const struct bk_junction_fit **out) __attribute__((weak));
+// -dedup
+int bk_unique_support(bk_ctx *ctx, const struct bk_unique_support **out, uint64_t *count, const uint64_t **first, uint64_t *n_rows) __attribute__((weak));
+// -clip (the soft-clip evidence, the depth at the rescued positions and the rescue rule)
+int bk_clip_support(bk_ctx *calls, bk_ctx *records, int mapq_min, int min_clip, double w, const struct bk_clip_support **out, uint64_t *count) __attribute__((weak));
+int bk_clip_reads(bk_ctx *records, const struct bk_clip_site *sites, uint64_t n_sites, int mapq_min, int min_clip, const uint32_t **counts, const struct bk_clip_read **rows,
+                  const uint64_t **site_off) __attribute__((weak));
+int bk_base_depth(bk_ctx *records, const int32_t *tid, const uint32_t *pos, uint64_t n, const uint32_t **out) __attribute__((weak));
+int bk_clip_rescue(const bk_cluster *c, const struct bk_junction *j, const struct bk_clip_support *s, uint32_t min_support, uint32_t *pos1, uint32_t *pos2, uint32_t *n1,
+                   uint32_t *n2) __attribute__((weak));
+// -x
+int bk_exclude_regions(bk_ctx *ctx, const bk_regions *r, uint64_t *n_removed) __attribute__((weak));
+int bk_multi_run_ex(const bk_soa *host_table, const uint32_t *target_len, const char *const *target_name, int n_targets, const bk_regions *exclude, int n_gpus, int transport,
+                    int mapq_min, int fast, double *w_out, uint64_t *n_clustered_total, bk_ctx **ctx0_out, char *err, size_t errlen) __attribute__((weak));
+int bk_multi_run_bam_ex(const char *path, const bk_regions *exclude, int n_gpus, int transport, int mapq_min, int fast, double *w_out, uint64_t *n_clustered_total,
+                        bk_ctx **ctx0_out, int *n_targets, const char *const **names, const uint32_t **lens, char *err, size_t errlen) __attribute__((weak));
+int bk_multi_excluded(bk_ctx *ctx, uint64_t *n_removed) __attribute__((weak));
+}
+
+static const char *HELP =
+    " Usage: \n \t BreakID -i input.bam -o prefix -n nib_folder <options> \n\n \
+     DESCRIPTION\n \
+     \t -h -? -help \t help\n \
+     \t -i*        \t input bam-file\n \
+     \t -o*        \t output file (prefix only)\n \
+     \t -n*        \t folder name to nib files\n \
+     \t -q         \t encompassing reads quality thresholds  [20]\n\
+     \t -t         \t distance relative to (sqrt(2)*(insert size mean +3* insert size sd))  [2]\n \
+     \t -fast      \t use the fast cluster strategy [default no] \n \
+     \t -all       \t no filter enspan out [default is filter]  \n \
+     \t -x         \t exclude list (BED: contig [start end]); records that overlap it are ignored  \n \
+     \t -genotype  \t count reference-allele evidence and genotype every call (twin files *_genotype.txt)  \n \
+     \t -anchor    \t bases a reference read must cover on either side of a breakpoint (with -genotype)  [10]\n \
+     \t -vcf       \t also write the calls as VCF breakends (*_fusion.vcf)  \n \
+     \t -evidence  \t also list the reads behind every call (*_evidence.txt) and write them as a BAM (*_evidence.bam)  \n \
+     \t -dedup     \t count the different fragments behind every call (twin files *_dedup.txt; UPE / USR with -vcf, a Dup column with -evidence)  \n \
+     \t -clip      \t count soft-clipped reads without an SA tag at every call (twin files *_clip.txt) and rescue clusters the vote left out (*_fusion_rescued.txt)  \n \
+     \t -minclip   \t shortest soft clip that counts (with -clip)  [10]\n \
+     \t -clipsupport \t clipped reads at one position that each side of a rescued cluster needs (with -clip)  [3]\n \
+     \t -consensus \t vote the clipped bases at both breakpoints of every call into a junction sequence (twin files *_consensus.txt; CSEQ / CSN with -vcf)  \n \
+     \t -conslen   \t longest junction sequence per side, 1 to 256 (with -consensus)  [64]\n \
+     \t -homology  \t fit each junction sequence to the reference at the other breakpoint: offset, inserted bases, microhomology (with -consensus; twin files *_homology.txt; HOMLEN / HOMSEQ / JINS with -vcf)  \n \
+     \t -homshift  \t largest offset of the continuation from the called position, 0 to 64 (with -homology)  [32]\n \
+     \t -homins    \t longest inserted sequence, 0 to 64 (with -homology)  [32]\n ";
+
+struct Options
+{
+  std::string inp_file, out_file, nib_dir, normal_file, exclude_file, build = "hg19";
+  int qual = 20, device = 0, n_gpus = 0, transport = BK_TRANSPORT_AUTO;  // -gpus N: one sample over N GPUs (include/breakid_multi.h)
+  bool fast = false, all = false;                                        // -all: no gene-pair and repeat filter (the _fusion_all files)
+  bool genotype = false, vcf = false, evidence = false, clip = false, dedup = false, consensus = false, homology = false;
+  bool anchor_given = false, minclip_given = false, clipsupport_given = false, conslen_given = false, homshift_given = false, homins_given = false;
+  long anchor = 10;                      // -anchor: bases a reference read must cover on either side of the breakpoint base
+  long min_clip = 10, clip_support = 3;  // -minclip: shortest clip that counts; -clipsupport: reads at one position a rescued side needs
+  long conslen = 64;                     // -conslen: longest junction sequence per side
+  long homshift = 32, homins = 32;       // -homshift, -homins: the largest offset and the longest insertion bk_junction_fit looks for
+  bool multi() const { return n_gpus >= 1; }  // the sharded run
+  bool with_normal() const { return !normal_file.empty(); }
+  bool exclude() const { return !exclude_file.empty(); }
+};
+
+// One thing a command line is refused for.  USAGE rules stand behind the help text, as do the GPUS refusals; `text` is the rule, the
+// option's name, or what could not be opened.
+struct Refusal
+{
+  enum Kind { USAGE, GPUS, LIBRARY, OPEN } kind;
+  bool fails;
+  std::string text;
+};
+
+static bool opens(const std::string &path)
+{
+  FILE *probe = path.empty() ? nullptr : fopen(path.c_str(), "rb");
+  if (probe) fclose(probe);
+  return probe != nullptr;
+}
+
+// The first refusal that applies reports and ends the run: the order of the rows is behaviour.  An option that adds a per-call output
+// has one row in `Feature` form: its name, whether it is set, whether it runs sharded, whether the library has what it calls.
+static void check_options(const Options &o)
+{
+  struct Feature
+  {
+    const char *name;
+    bool set, gpus_ok, present;
+  };
+  const Feature normal{"-normal", o.with_normal(), false, bk_normal_support != nullptr};
+  const Feature genotype{"-genotype", o.genotype, false, bk_ref_support && bk_genotype_call};
+  const Feature vcf{"-vcf", o.vcf, false, bk_junctions && bk_junction_sides && bk_vcf_breakend_alt};
+  const Feature evidence{"-evidence", o.evidence, false, bk_evidence != nullptr};
+  const Feature dedup{"-dedup", o.dedup, false, bk_unique_support != nullptr};
+  const Feature homology{"-homology", o.homology, false, bk_junction_fit != nullptr};
+  const Feature consensus{"-consensus", o.consensus, false, bk_clip_consensus && bk_clip_reads && bk_evidence && bk_junctions && bk_junction_sides};
+  const Feature clip{"-clip", o.clip, false, bk_clip_support && bk_clip_reads && bk_base_depth && bk_clip_rescue && bk_junctions && bk_junction_sides};
+  const Feature exclude{"-x", o.exclude(), true, bk_exclude_regions && bk_multi_run_ex && bk_multi_run_bam_ex && bk_multi_excluded};
+  auto rule = [](bool broken, const char *text) { return Refusal{Refusal::USAGE, broken, text}; };
+  auto gpus = [&](const Feature &f) { return Refusal{Refusal::GPUS, f.set && !f.gpus_ok && o.multi(), f.name}; };
+  auto library = [](const Feature &f) { return Refusal{Refusal::LIBRARY, f.set && !f.present, f.name}; };
+  auto in_range = [](long v, long lo, long hi) { return v >= lo && v <= hi; };
+  const long int_max = 0x7FFFFFFFl;
+  const Refusal refusals[] = {
+      rule(o.inp_file.empty() || o.out_file.empty(), "input- and output file is required."),
+      rule(o.nib_dir.empty(), "nib file's root dir is required."),
+      gpus(normal), library(normal), {Refusal::OPEN, normal.set && !opens(o.normal_file), "normal bam-file: " + o.normal_file},
+      rule(o.anchor_given && !o.genotype, "-anchor needs -genotype."),
+      gpus(genotype), rule(o.genotype && !in_range(o.anchor, 0, int_max), "-anchor must be a number from 0 to 2147483647."), library(genotype),
+      gpus(vcf), library(vcf),
+      gpus(evidence), library(evidence),
+      gpus(dedup), library(dedup),
+      rule((o.homshift_given || o.homins_given) && !o.homology, "-homshift and -homins need -homology."),
+      rule(o.homology && !o.consensus, "-homology needs -consensus."), gpus(homology), library(homology),
+      rule(o.homology && !(in_range(o.homshift, 0, 64) && in_range(o.homins, 0, 64)), "-homshift and -homins must be numbers from 0 to 64."),
+      rule(o.conslen_given && !o.consensus, "-conslen needs -consensus."),
+      gpus(consensus), library(consensus), rule(o.consensus && !in_range(o.conslen, 1, 256), "-conslen must be a number from 1 to 256."),
+      rule(o.consensus && !in_range(o.min_clip, 1, int_max), "-minclip must be a number from 1 to 2147483647."),
+      rule((o.minclip_given && !o.clip && !o.consensus) || (o.clipsupport_given && !o.clip), "-minclip and -clipsupport need -clip."),
+      library(clip), gpus(clip),  // (the one option that looks for the library first)
+      rule(o.clip && !(in_range(o.min_clip, 1, int_max) && in_range(o.clip_support, 1, int_max)), "-minclip and -clipsupport must be numbers from 1 to 2147483647."),
+      gpus(exclude), library(exclude), {Refusal::OPEN, exclude.set && !opens(o.exclude_file), "exclude file: " + o.exclude_file},
+  };
+  for (const Refusal &r : refusals)
+  {
+    if (!r.fails) continue;
+    switch (r.kind)
+    {
+    case Refusal::USAGE: std::cerr << HELP << "Error: " << r.text << "\n"; break;
+    case Refusal::GPUS: std::cerr << HELP << "Error: " << r.text << " cannot be combined with -gpus.\n"; break;
+    case Refusal::LIBRARY: std::cerr << "Error: " << r.text << " needs the GPU library" << std::endl; break;
+    case Refusal::OPEN: std::cerr << "Error: can not open " << r.text << std::endl; break;
+    }
+    exit(1);
+  }
+}
+
+static Options parse_options(int argc, char *argv[])
+{
+  static struct option longopts[] = {{"help", 0, 0, 'h'}, {"i", 1, 0, 1}, {"o", 1, 0, 2}, {"q", 1, 0, 3}, {"n", 1, 0, 4},
+                                     {"fast", 0, 0, 5},   {"t", 0, 0, 6}, {"all", 0, 0, 7}, {"gpu", 1, 0, 8}, {"gpus", 1, 0, 9},
+                                     {"comm", 1, 0, 10},  {"normal", 1, 0, 11}, {"x", 1, 0, 12}, {"genotype", 0, 0, 13},
+                                     {"anchor", 1, 0, 14}, {"vcf", 0, 0, 15}, {"evidence", 0, 0, 16}, {"clip", 0, 0, 17},
+                                     {"minclip", 1, 0, 18}, {"clipsupport", 1, 0, 19}, {"dedup", 0, 0, 20}, {"consensus", 0, 0, 21},
+                                     {"conslen", 1, 0, 22}, {"homology", 0, 0, 23}, {"homshift", 1, 0, 24}, {"homins", 1, 0, 25}, {0, 0, 0, 0}};
+  Options o;
+  auto number = [](long &value, bool &given) {
+    value = atol(optarg);
+    given = true;
+  };
+  int opt, li;
+  optind = 0;
+  while ((opt = getopt_long_only(argc, argv, "h?", longopts, &li)) != -1)
+  {
+    switch (opt)
+    {
+    case 'h': case '?': std::cerr << HELP; exit(1);
+    case 1: o.inp_file = optarg; break;
+    case 2: o.out_file = optarg; break;
+    case 3: o.qual = (int) std::labs(atol(optarg)); break;
+    case 4: o.nib_dir = optarg; break;
+    case 5: o.fast = true; break;
+    case 6: break;  // the reference dereferences a NULL optarg here (has_arg = 0); `times` is effectively always 2
+    case 7: o.all = true; break;
+    case 8: o.device = atoi(optarg); break;
+    case 9: o.n_gpus = atoi(optarg); break;
+    case 10: o.transport = !strcmp(optarg, "rccl") ? BK_TRANSPORT_RCCL : !strcmp(optarg, "local") ? BK_TRANSPORT_LOCAL : BK_TRANSPORT_AUTO; break;
+    case 11: o.normal_file = optarg; break;
+    case 12: o.exclude_file = optarg; break;
+    case 13: o.genotype = true; break;
+    case 14: number(o.anchor, o.anchor_given); break;
+    case 15: o.vcf = true; break;
+    case 16: o.evidence = true; break;
+    case 17: o.clip = true; break;
+    case 18: number(o.min_clip, o.minclip_given); break;
+    case 19: number(o.clip_support, o.clipsupport_given); break;
+    case 20: o.dedup = true; break;
+    case 21: o.consensus = true; break;
+    case 22: number(o.conslen, o.conslen_given); break;
+    case 23: o.homology = true; break;
+    case 24: number(o.homshift, o.homshift_given); break;
+    case 25: number(o.homins, o.homins_given); break;
+    default: std::cerr << "Error: cannot parse arguments.\n"; exit(1);
+    }
+  }
+  check_options(o);
+  return o;
+}

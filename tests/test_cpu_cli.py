@@ -131,3 +131,62 @@ def check_fatal_paths(binary):
 @pytest.mark.parametrize("which", ["plain", "asan", "ubsan"])
 def test_fatal_paths_match_the_reference_messages(binaries, which):
     check_fatal_paths(binaries[which])
+
+
+# (options behind `-i in.bam -o out -n nib`, the one "Error:" line of the CPU build, that of the GPU build where it differs): command
+# lines that break one option rule, or two at once - which message wins is behaviour.  A line that starts with a blank stands behind
+# the help text.  Every answer has exit status 1 and comes before any file is opened for writing or the GPU is touched; in.bam does not
+# exist, so a command line the GPU build accepts ends at "can not open bam-file".  The CPU build has none of the per-call entry points
+# of the library: where the GPU build goes on to an option's ranges, it stops at "needs the GPU library".  Recorded from the binaries
+# of the commit in front of the split of main() into stages.
+GPU_LIB = "Error: %s needs the GPU library"
+NO_GPUS = " Error: %s cannot be combined with -gpus."
+REFUSALS = [
+    ("-clip -gpus 2", GPU_LIB % "-clip", NO_GPUS % "-clip"),  # -clip looks for the library first, every other option for -gpus
+    ("-vcf -gpus 2", NO_GPUS % "-vcf", None),
+    ("-homology", " Error: -homology needs -consensus.", None),
+    ("-consensus -homology -gpus 2", NO_GPUS % "-homology", None),
+    ("-homshift 3", " Error: -homshift and -homins need -homology.", None),
+    ("-conslen 0 -consensus", GPU_LIB % "-consensus", " Error: -conslen must be a number from 1 to 256."),
+    ("-consensus -minclip 0", GPU_LIB % "-consensus", " Error: -minclip must be a number from 1 to 2147483647."),
+    ("-minclip 5", " Error: -minclip and -clipsupport need -clip.", None),
+    ("-consensus -minclip 5", GPU_LIB % "-consensus", "Error: can not open bam-file: in.bam"),
+    ("-anchor 3", " Error: -anchor needs -genotype.", None),
+    ("-genotype -anchor -1", " Error: -anchor must be a number from 0 to 2147483647.", None),
+    ("-clip -clipsupport 0", GPU_LIB % "-clip", " Error: -minclip and -clipsupport must be numbers from 1 to 2147483647."),
+    ("-normal /nonexistent", GPU_LIB % "-normal", "Error: can not open normal bam-file: /nonexistent"),
+    ("-x /nonexistent", GPU_LIB % "-x", "Error: can not open exclude file: /nonexistent"),
+    ("-dedup -evidence -gpus 2", NO_GPUS % "-evidence", None),
+    ("-normal /nonexistent -gpus 2", NO_GPUS % "-normal", None),
+    ("-genotype -gpus 2", NO_GPUS % "-genotype", None),
+    ("-consensus -gpus 2", NO_GPUS % "-consensus", None),
+    ("-dedup -gpus 2", NO_GPUS % "-dedup", None),
+    ("-consensus -homology -homins 65", GPU_LIB % "-homology", " Error: -homshift and -homins must be numbers from 0 to 64."),
+    ("-conslen 5", " Error: -conslen needs -consensus.", None),
+    ("-clipsupport 2", " Error: -minclip and -clipsupport need -clip.", None),
+    ("-homology -gpus 2", " Error: -homology needs -consensus.", None),
+    ("-vcf -clip -gpus 2", NO_GPUS % "-vcf", None),
+    ("-anchor 3 -vcf -gpus 2", " Error: -anchor needs -genotype.", None),
+    ("-consensus -conslen 0 -minclip 0", GPU_LIB % "-consensus", " Error: -conslen must be a number from 1 to 256."),
+    ("-clip -x /nonexistent -gpus 2", GPU_LIB % "-clip", NO_GPUS % "-clip"),
+    ("-clip -minclip 0 -gpus 2", GPU_LIB % "-clip", NO_GPUS % "-clip"),
+    ("-consensus -homology -homshift -1 -conslen 0", GPU_LIB % "-homology", " Error: -homshift and -homins must be numbers from 0 to 64."),
+    ("-evidence", GPU_LIB % "-evidence", "Error: can not open bam-file: in.bam"),
+]
+
+
+def check_refusals(binary, gpu_build):
+    with tempfile.TemporaryDirectory() as tmp:
+        for options, cpu_line, gpu_line in REFUSALS:
+            line = gpu_line if gpu_build and gpu_line is not None else cpu_line
+            r = subprocess.run([binary, "-i", "in.bam", "-o", "out", "-n", "nib"] + options.split(), cwd=tmp, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0"),
+                               capture_output=True, text=True)
+            errors = [l for l in r.stderr.split("\n") if "Error" in l]
+            assert r.returncode == 1 and errors == [line] and ("Usage" in r.stderr) == line.startswith(" "), (options, r.returncode, r.stderr[-400:])
+            assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr, r.stderr[-3000:]
+            assert os.listdir(tmp) == [], options
+
+
+@pytest.mark.parametrize("which", ["plain", "asan", "ubsan"])
+def test_option_rules_refuse_with_the_recorded_message(binaries, which):
+    check_refusals(binaries[which], gpu_build=False)

@@ -1,5 +1,6 @@
 """End-to-end drop-in check: the BreakID command line (same flags, same txt files as the reference) on the
 GPU against the reference's own output files kept as golden fixtures (tools/make_golden.py)."""
+import json
 import os
 import subprocess
 import tempfile
@@ -10,6 +11,7 @@ import pytest
 from breakid_amd import synth
 from breakid_amd import bamio
 from tests import refdump
+from tools import make_cli_matrix
 from tools import make_golden
 
 pytestmark = pytest.mark.gpu
@@ -71,6 +73,49 @@ def test_cli_fatal_paths_match_the_reference_messages():
     :411-416, RefSeqTranscript.cc:212-216), same table as the CPU build of the host code (tests/test_cpu_cli.py)"""
     from tests.test_cpu_cli import check_fatal_paths
     check_fatal_paths(BIN)
+
+
+def test_cli_option_rules_refuse_with_the_recorded_message():
+    """the table of tests/test_cpu_cli.py against the GPU build: the library is there, so an option's own rules answer"""
+    from tests.test_cpu_cli import check_refusals
+    check_refusals(BIN, gpu_build=True)
+
+
+# ---- the matrix of command lines (tools/make_cli_matrix.py): every file of every run against the recording -------------------------
+with open(make_cli_matrix.GOLDEN) as _f:
+    CLI_MATRIX = json.load(_f)
+
+
+@pytest.fixture(scope="module")
+def matrix_inputs():
+    with tempfile.TemporaryDirectory() as tmp:
+        yield make_cli_matrix.build_inputs(tmp)
+
+
+def test_cli_matrix_recording_has_every_kind_of_file_with_calls():
+    """the matrix cannot pass on empty files: each of the seven twins in both forms, the rescued tables, the VCFs and the evidence
+    listings holds a data line in at least one recorded run, and every recorded run ended well"""
+    assert make_cli_matrix.kinds_without_data(CLI_MATRIX) == []
+    assert len(CLI_MATRIX["commit"]) == 40 and CLI_MATRIX["source"] == "breakid_amd/csrc/breakid_main.cc"
+    for which in make_cli_matrix.INPUTS:
+        runs = CLI_MATRIX["runs"][which]
+        assert list(runs) == sorted(name for name, _ in make_cli_matrix.command_lines())
+        assert all(rec["exit"] == 0 for rec in runs.values())
+
+
+@pytest.mark.parametrize("which", make_cli_matrix.INPUTS)
+def test_cli_matrix_matches_the_recording(matrix_inputs, which):
+    """every command line of the matrix writes the files the recorded binary wrote, byte for byte (tools/make_cli_matrix.py says
+    what is compared), prints the same stdout and ends with the same status"""
+    assert make_cli_matrix.input_hashes(matrix_inputs[which]) == CLI_MATRIX["inputs"][which], "the input changed: the recording does not apply"
+    for name, args in make_cli_matrix.command_lines():
+        exp = CLI_MATRIX["runs"][which][name]
+        got = make_cli_matrix.run_one(BIN, matrix_inputs[which], name, args)
+        assert got["exit"] == exp["exit"], (name, got)
+        assert sorted(got["files"]) == sorted(exp["files"]), (name, sorted(got["files"]), sorted(exp["files"]))
+        for suffix in exp["files"]:
+            assert got["files"][suffix] == exp["files"][suffix], (name, suffix, got["files"][suffix], exp["files"][suffix])
+        assert got == exp, (name, got["stdout"], exp["stdout"])
 
 
 @pytest.mark.parametrize("name,mode,ranks,comm,feed", [("small", "fast", 1, "rccl", "gpu"), ("edge", "ahc", 1, "rccl", "gpu"), ("small", "fast", 2, "local", "gpu"),
