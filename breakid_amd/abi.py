@@ -47,6 +47,10 @@ JUNCTION_PROBE = np.dtype([("tid_own", "<i4"), ("pos_own", "<u4"), ("dir_own", "
 JUNCTION_FIT = np.dtype([("shift", "<i4"), ("ins", "<u4"), ("aligned", "<u4"), ("mism", "<u4"), ("hom_fwd", "<u4"), ("hom_back", "<u4"), ("score", "<i4"),
                          ("placed", "<u4")])  # struct bk_junction_fit
 assert JUNCTION_PROBE.itemsize == 32 and JUNCTION_FIT.itemsize == 32
+LOCUS_PAIR = np.dtype([("tid_a", "<i4"), ("pos_a", "<u4"), ("tid_b", "<i4"), ("pos_b", "<u4")])  # struct bk_locus_pair; pos 1-based
+LOCUS_SIM = np.dtype([("score", "<u4"), ("len", "<u4"), ("mism", "<u4"), ("run", "<u4"), ("diag", "<i4"), ("start", "<u4"), ("orient", "<u4"),
+                      ("found", "<u4")])  # struct bk_locus_sim
+assert LOCUS_PAIR.itemsize == 16 and LOCUS_SIM.itemsize == 32
 # the columns of a bk_refseq table, in the struct's order (off has n_segs + 1 entries)
 REFSEQ_COLS = [("tid", np.int32), ("start", np.uint32), ("len", np.uint32), ("off", np.uint64), ("bases", np.uint8)]
 READ_KEY = np.dtype([("qhash", "<u8"), ("qcheck", "<u4"), ("tag", "<u4")])  # bk_read_key

@@ -19,6 +19,7 @@
 #include "unique.h"
 #include "consensus.h"
 #include "jfit.h"
+#include "locsim.h"
 #include "exclude.h"
 #include "ahc.h"
 #include "lanes.h"
@@ -154,6 +155,9 @@ struct bk_ctx
   // junction fit (bk_junction_fit)
   JfitBufs jfb;
   std::vector<struct bk_junction_fit> f_jfit;
+  // locus similarity (bk_locus_similarity)
+  LocsimBufs lsb;
+  std::vector<struct bk_locus_sim> f_locsim;
 
   // fetch staging
   std::vector<bk_pair> f_pairs[3];
@@ -1293,6 +1297,28 @@ int bk_clip_consensus(bk_ctx *ctx, const bk_reads *reads, const struct bk_clip_s
   });
 }
 
+// What both calls that take a bk_refseq table refuse it for (include/breakid_hip.h); `who` names the call in the message.  The limit
+// is looked at before any array.
+static void check_refseq(const bk_refseq &t, const std::string &who)
+{
+  if (t.n_segs > 0x100000ull) throw bk_error(BK_ERR_LIMIT, who +": more than 2^20 segments");
+  if (t.n_segs && (!t.tid || !t.start || !t.len || !t.off)) throw bk_error(BK_ERR_ARG, who + ": the reference table lacks a column");
+  for (uint64_t g = 0; g < t.n_segs; ++g)
+  {
+    if (t.off[g + 1] < t.off[g]) throw bk_error(BK_ERR_ARG, who + ": off does not ascend at segment " + std::to_string(g));
+    if (t.off[g + 1] - t.off[g] < ((uint64_t) t.len[g] + 1) / 2)
+      throw bk_error(BK_ERR_ARG, who + ": segment " + std::to_string(g) + " has fewer bytes than (len + 1) / 2");
+    if (g + 1 < t.n_segs)
+    {
+      if (t.tid[g + 1] < t.tid[g] || (t.tid[g + 1] == t.tid[g] && t.start[g + 1] < t.start[g]))
+        throw bk_error(BK_ERR_ARG, who + ": segment " + std::to_string(g + 1) + " is out of order (the segments ascend by tid, then start)");
+      if (t.tid[g + 1] == t.tid[g] && (long long) t.start[g] + (long long) t.len[g] > (long long) t.start[g + 1])
+        throw bk_error(BK_ERR_ARG, who + ": segment " + std::to_string(g + 1) + " overlaps the one before it");
+    }
+  }
+  if (t.n_segs && t.off[t.n_segs] && !t.bases) throw bk_error(BK_ERR_ARG, who + ": the reference table lacks a column");
+}
+
 int bk_junction_fit(bk_ctx *ctx, const bk_refseq *ref, const struct bk_junction_probe *probes, uint64_t n, const uint8_t *query, uint32_t max_len, uint32_t max_shift,
                     uint32_t max_ins, uint32_t max_hom, const struct bk_junction_fit **out)
 {
@@ -1306,22 +1332,7 @@ int bk_junction_fit(bk_ctx *ctx, const bk_refseq *ref, const struct bk_junction_
     if (max_hom > 64) throw bk_error(BK_ERR_ARG, "bk_junction_fit: max_hom must be 0..64");
     if (n > 0x40000000ull) throw bk_error(BK_ERR_LIMIT, "bk_junction_fit: more than 2^30 probes");
     const bk_refseq &t = *ref;
-    if (t.n_segs > 0x100000ull) throw bk_error(BK_ERR_LIMIT, "bk_junction_fit: more than 2^20 segments");
-    if (t.n_segs && (!t.tid || !t.start || !t.len || !t.off)) throw bk_error(BK_ERR_ARG, "bk_junction_fit: the reference table lacks a column");
-    for (uint64_t g = 0; g < t.n_segs; ++g)
-    {
-      if (t.off[g + 1] < t.off[g]) throw bk_error(BK_ERR_ARG, "bk_junction_fit: off does not ascend at segment " + std::to_string(g));
-      if (t.off[g + 1] - t.off[g] < ((uint64_t) t.len[g] + 1) / 2)
-        throw bk_error(BK_ERR_ARG, "bk_junction_fit: segment " + std::to_string(g) + " has fewer bytes than (len + 1) / 2");
-      if (g + 1 < t.n_segs)
-      {
-        if (t.tid[g + 1] < t.tid[g] || (t.tid[g + 1] == t.tid[g] && t.start[g + 1] < t.start[g]))
-          throw bk_error(BK_ERR_ARG, "bk_junction_fit: segment " + std::to_string(g + 1) + " is out of order (the segments ascend by tid, then start)");
-        if (t.tid[g + 1] == t.tid[g] && (long long) t.start[g] + (long long) t.len[g] > (long long) t.start[g + 1])
-          throw bk_error(BK_ERR_ARG, "bk_junction_fit: segment " + std::to_string(g + 1) + " overlaps the one before it");
-      }
-    }
-    if (t.n_segs && t.off[t.n_segs] && !t.bases) throw bk_error(BK_ERR_ARG, "bk_junction_fit: the reference table lacks a column");
+    check_refseq(t, "bk_junction_fit");
     uint64_t qbytes = 0, walk_bases = 0;
     for (uint64_t k = 0; k < n; ++k)
     {
@@ -1350,6 +1361,31 @@ int bk_junction_fit(bk_ctx *ctx, const bk_refseq *ref, const struct bk_junction_
     // touched: the probe row, qlen query bytes, the nibbles of both walks and the result row
     if (ctx->timing && !ctx->timers.empty()) ctx->timers.back().touched = n * (sizeof(struct bk_junction_probe) + sizeof(struct bk_junction_fit)) + qbytes + (walk_bases + 1) / 2;
     *out = ctx->f_jfit.data();
+  });
+}
+
+int bk_locus_similarity(bk_ctx *ctx, const bk_refseq *ref, const struct bk_locus_pair *pairs, uint64_t n, uint32_t flank, const struct bk_locus_sim **out)
+{
+  return guarded(ctx, [&] {
+    if (!ref || !out) throw bk_error(BK_ERR_ARG, "bk_locus_similarity: null ref or out");
+    if (n && !pairs) throw bk_error(BK_ERR_ARG, "bk_locus_similarity: null pairs");
+    if (ctx->shard) throw bk_error(BK_ERR_ARG, "bk_locus_similarity: sharded contexts (bk_shard_*) are not supported");
+    if (flank < 1 || flank > 255) throw bk_error(BK_ERR_ARG, "bk_locus_similarity: flank must be 1..255");
+    if (n > 0x40000000ull) throw bk_error(BK_ERR_LIMIT, "bk_locus_similarity: more than 2^30 pairs");
+    const bk_refseq &t = *ref;
+    check_refseq(t, "bk_locus_similarity");
+    const uint64_t L = 2ull * flank + 1;
+    struct bk_locus_sim *d_res;
+    locsim_upload(t, pairs, n, ctx->lsb, ctx->st);  // (outside the scope: it times the work on the device copy)
+    {
+      // bytes: the pairs and the result once; the reference segments once
+      Scope s(ctx, "locus_similarity", n * (sizeof(struct bk_locus_pair) + sizeof(struct bk_locus_sim)) + t.n_segs * 24ull + (t.n_segs ? t.off[t.n_segs] : 0));
+      locus_similarity(n, flank, ctx->lsb, ctx->st, &d_res);
+    }
+    rows_to_host(ctx, d_res, n, ctx->f_locsim);
+    // touched: the pair row, the result row and L nibbles of each of the two windows
+    if (ctx->timing && !ctx->timers.empty()) ctx->timers.back().touched = n * (sizeof(struct bk_locus_pair) + sizeof(struct bk_locus_sim) + L);
+    *out = ctx->f_locsim.data();
   });
 }
 

@@ -1099,10 +1099,54 @@ static HomologyMap junction_homology(const Options &o, const Sample &tumor, cons
   return hom;
 }
 
+// ---- -similar: the reference around the two breakpoints of every written call against each other -----------------------------------
+// One pair per written call whose two contigs have a nib file; the reference: the windows [pos - R, pos + R] around every position,
+// clamped to the contig.  One call scores every pair of the run.
+static SimilarMap locus_similar(const Options &o, const Sample &tumor, const vector<OutRow> &rows)
+{
+  NibFiles nibs{o, tumor, {}};
+  const long R = o.simflank;
+  vector<struct bk_locus_pair> pairs;
+  vector<uint64_t> pair_call;
+  std::map<int32_t, vector<std::pair<long, long>>> spans;
+  SimilarMap sim;
+  for (const OutRow &r : rows)
+  {
+    if (!call_written(r, o.all)) continue;
+    sim[r.idx];
+    if (!nibs.of(r.c.p1_tid) || !nibs.of(r.c.p2_tid)) continue;
+    const struct bk_locus_pair p = {r.c.p1_tid, r.c.p1_exact, r.c.p2_tid, (uint32_t) r.c.p2_exact};
+    pairs.push_back(p);
+    pair_call.push_back(r.idx);
+    for (int e = 0; e < 2; ++e)
+    {
+      const int32_t tid = e ? p.tid_b : p.tid_a;
+      const long pos = e ? (long) p.pos_b : (long) p.pos_a;
+      const long a = std::max(1l, pos - R), b = std::min((long) nibs.of(tid)->nBases, pos + R);
+      if (a <= b) spans[tid].emplace_back(a, b);
+    }
+  }
+  const RefWindows windows = read_ref_windows(spans, nibs);
+  const bk_refseq ref = windows.refseq();
+  const struct bk_locus_sim *res = nullptr;
+  const int rc = bk_locus_similarity(tumor.ctx, &ref, pairs.data(), pairs.size(), (uint32_t) R, &res);
+  if (rc != BK_OK) die(tumor, rc);
+  for (size_t k = 0; k < pairs.size(); ++k)
+  {
+    SimilarCall &c = sim[pair_call[k]];
+    c.on = true;
+    c.s = res[k];
+    const long first = (long) c.s.start + c.s.diag;  // the stretch's first column of window B in the orientation it was found in
+    c.pos1 = (long) pairs[k].pos_a - R + (long) c.s.start;
+    c.pos2 = c.s.orient ? (long) pairs[k].pos_b + R - (first + (long) c.s.len - 1) : (long) pairs[k].pos_b - R + first;
+  }
+  return sim;
+}
+
 // ---- the files behind the tables ---------------------------------------------------------------------------------------------------
 // -vcf: <prefix>_fusion.vcf, and with -clip <prefix>_fusion_rescued.vcf
 static void write_vcf_files(const Options &o, const Sample &tumor, const CallTables &t, const vector<OutRow> &rows, const Rescued &rescued, const ConsensusMap &cons,
-                            const HomologyMap &hom)
+                            const HomologyMap &hom, const SimilarMap &sim)
 {
   VcfInput vi;
   vi.nt = tumor.nt;
@@ -1119,6 +1163,7 @@ static void write_vcf_files(const Options &o, const Sample &tumor, const CallTab
   vi.usup = o.dedup ? &t.usup : nullptr;
   vi.cons = o.consensus ? &cons : nullptr;
   vi.hom = o.homology ? &hom : nullptr;
+  vi.sim = o.similar ? &sim : nullptr;
   auto write = [&](const string &path, const vector<OutRow> &calls) {
     if (write_vcf(path, calls, vi)) return;
     std::cerr << "Error: cannot write " << path << ": the evidence tables do not cover every call" << std::endl;
@@ -1130,6 +1175,7 @@ static void write_vcf_files(const Options &o, const Sample &tumor, const CallTab
   vi.usup = nullptr;                   // ... and their files stay as they are with -dedup
   vi.cons = nullptr;                   // ... and with -consensus
   vi.hom = nullptr;                    // ... and with -homology
+  vi.sim = nullptr;                    // ... and with -similar
   vi.rescued = &rescued.calls;
   write(o.out_file + "_fusion_rescued.vcf", rescued.rows);
 }
@@ -1178,6 +1224,7 @@ static void write_params(const Options &o, double w)
   if (o.consensus) p << "consensus_max_len\t" << o.conslen << std::endl;
   if (o.homology) p << "homology_max_shift\t" << o.homshift << std::endl;
   if (o.homology) p << "homology_max_ins\t" << o.homins << std::endl;
+  if (o.similar) p << "similar_flank\t" << o.simflank << std::endl;
 }
 
 // BreakID.cc:175-191.  scan_pairs_count and after_cluster_count are never updated by the reference (always 0);
@@ -1247,10 +1294,12 @@ int main(int argc, char *argv[])
   HomologyMap homology;
   if (o.consensus) junction_consensus(o, tumor, tables, rows, consensus);
   if (o.homology) homology = junction_homology(o, tumor, consensus);
+  SimilarMap similar;
+  if (o.similar) similar = locus_similar(o, tumor, rows);
 
   if (o.clip) write_rescued_tables(o, rescued, tables);
-  write_fusion_tables(o, rows, fusion_twins(o, tables, consensus.sides, homology));
-  if (o.vcf) write_vcf_files(o, tumor, tables, rows, rescued, consensus.sides, homology);
+  write_fusion_tables(o, rows, fusion_twins(o, tables, consensus.sides, homology, similar));
+  if (o.vcf) write_vcf_files(o, tumor, tables, rows, rescued, consensus.sides, homology, similar);
   if (o.evidence) write_evidence_files(o, tumor, tables, rows, rescued);
   write_params(o, run.w);
   const clock_t end = clock();

@@ -33,6 +33,8 @@ int bk_clip_consensus(bk_ctx *ctx, const bk_reads *reads, const struct bk_clip_s
 // -homology
 int bk_junction_fit(bk_ctx *ctx, const bk_refseq *ref, const struct bk_junction_probe *probes, uint64_t n, const uint8_t *query, uint32_t max_len, uint32_t max_shift,
                     uint32_t max_ins, uint32_t max_hom, const struct bk_junction_fit **out) __attribute__((weak));
+// -similar
+int bk_locus_similarity(bk_ctx *ctx, const bk_refseq *ref, const struct bk_locus_pair *pairs, uint64_t n, uint32_t flank, const struct bk_locus_sim **out) __attribute__((weak));
 // -dedup
 int bk_unique_support(bk_ctx *ctx, const struct bk_unique_support **out, uint64_t *count, const uint64_t **first, uint64_t *n_rows) __attribute__((weak));
 // -clip (the soft-clip evidence, the depth at the rescued positions and the rescue rule)
@@ -75,19 +77,22 @@ static const char *HELP =
      \t -conslen   \t longest junction sequence per side, 1 to 256 (with -consensus)  [64]\n \
      \t -homology  \t fit each junction sequence to the reference at the other breakpoint: offset, inserted bases, microhomology (with -consensus; twin files *_homology.txt; HOMLEN / HOMSEQ / JINS with -vcf)  \n \
      \t -homshift  \t largest offset of the continuation from the called position, 0 to 64 (with -homology)  [32]\n \
-     \t -homins    \t longest inserted sequence, 0 to 64 (with -homology)  [32]\n ";
+     \t -homins    \t longest inserted sequence, 0 to 64 (with -homology)  [32]\n \
+     \t -similar   \t score the reference around the two breakpoints of every call against each other, forward and reverse-complemented (twin files *_similar.txt; SIMSCORE / SIMLEN / SIMRUN with -vcf)  \n \
+     \t -simflank  \t bases either side of a breakpoint that are compared, 1 to 255 (with -similar)  [150]\n ";
 
 struct Options
 {
   std::string inp_file, out_file, nib_dir, normal_file, exclude_file, build = "hg19";
   int qual = 20, device = 0, n_gpus = 0, transport = BK_TRANSPORT_AUTO;  // -gpus N: one sample over N GPUs (include/breakid_multi.h)
   bool fast = false, all = false;                                        // -all: no gene-pair and repeat filter (the _fusion_all files)
-  bool genotype = false, vcf = false, evidence = false, clip = false, dedup = false, consensus = false, homology = false;
-  bool anchor_given = false, minclip_given = false, clipsupport_given = false, conslen_given = false, homshift_given = false, homins_given = false;
+  bool genotype = false, vcf = false, evidence = false, clip = false, dedup = false, consensus = false, homology = false, similar = false;
+  bool anchor_given = false, minclip_given = false, clipsupport_given = false, conslen_given = false, homshift_given = false, homins_given = false, simflank_given = false;
   long anchor = 10;                      // -anchor: bases a reference read must cover on either side of the breakpoint base
   long min_clip = 10, clip_support = 3;  // -minclip: shortest clip that counts; -clipsupport: reads at one position a rescued side needs
   long conslen = 64;                     // -conslen: longest junction sequence per side
   long homshift = 32, homins = 32;       // -homshift, -homins: the largest offset and the longest insertion bk_junction_fit looks for
+  long simflank = 150;                   // -simflank: the bases either side of a breakpoint that bk_locus_similarity compares
   bool multi() const { return n_gpus >= 1; }  // the sharded run
   bool with_normal() const { return !normal_file.empty(); }
   bool exclude() const { return !exclude_file.empty(); }
@@ -124,6 +129,7 @@ static void check_options(const Options &o)
   const Feature evidence{"-evidence", o.evidence, false, bk_evidence != nullptr};
   const Feature dedup{"-dedup", o.dedup, false, bk_unique_support != nullptr};
   const Feature homology{"-homology", o.homology, false, bk_junction_fit != nullptr};
+  const Feature similar{"-similar", o.similar, false, bk_locus_similarity != nullptr};
   const Feature consensus{"-consensus", o.consensus, false, bk_clip_consensus && bk_clip_reads && bk_evidence && bk_junctions && bk_junction_sides};
   const Feature clip{"-clip", o.clip, false, bk_clip_support && bk_clip_reads && bk_base_depth && bk_clip_rescue && bk_junctions && bk_junction_sides};
   const Feature exclude{"-x", o.exclude(), true, bk_exclude_regions && bk_multi_run_ex && bk_multi_run_bam_ex && bk_multi_excluded};
@@ -151,6 +157,9 @@ static void check_options(const Options &o)
       library(clip), gpus(clip),  // (the one option that looks for the library first)
       rule(o.clip && !(in_range(o.min_clip, 1, int_max) && in_range(o.clip_support, 1, int_max)), "-minclip and -clipsupport must be numbers from 1 to 2147483647."),
       gpus(exclude), library(exclude), {Refusal::OPEN, exclude.set && !opens(o.exclude_file), "exclude file: " + o.exclude_file},
+      // (behind every older row: no command line without the two options changes its answer)
+      rule(o.simflank_given && !o.similar, "-simflank needs -similar."), gpus(similar), library(similar),
+      rule(o.similar && !in_range(o.simflank, 1, 255), "-simflank must be a number from 1 to 255."),
   };
   for (const Refusal &r : refusals)
   {
@@ -173,7 +182,8 @@ static Options parse_options(int argc, char *argv[])
                                      {"comm", 1, 0, 10},  {"normal", 1, 0, 11}, {"x", 1, 0, 12}, {"genotype", 0, 0, 13},
                                      {"anchor", 1, 0, 14}, {"vcf", 0, 0, 15}, {"evidence", 0, 0, 16}, {"clip", 0, 0, 17},
                                      {"minclip", 1, 0, 18}, {"clipsupport", 1, 0, 19}, {"dedup", 0, 0, 20}, {"consensus", 0, 0, 21},
-                                     {"conslen", 1, 0, 22}, {"homology", 0, 0, 23}, {"homshift", 1, 0, 24}, {"homins", 1, 0, 25}, {0, 0, 0, 0}};
+                                     {"conslen", 1, 0, 22}, {"homology", 0, 0, 23}, {"homshift", 1, 0, 24}, {"homins", 1, 0, 25},
+                                     {"similar", 0, 0, 26}, {"simflank", 1, 0, 27}, {0, 0, 0, 0}};
   Options o;
   auto number = [](long &value, bool &given) {
     value = atol(optarg);
@@ -211,6 +221,8 @@ static Options parse_options(int argc, char *argv[])
     case 23: o.homology = true; break;
     case 24: number(o.homshift, o.homshift_given); break;
     case 25: number(o.homins, o.homins_given); break;
+    case 26: o.similar = true; break;
+    case 27: number(o.simflank, o.simflank_given); break;
     default: std::cerr << "Error: cannot parse arguments.\n"; exit(1);
     }
   }

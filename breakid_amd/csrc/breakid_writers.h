@@ -194,6 +194,28 @@ struct HomologySide
     return o.str();
   }
 };
+// -similar: the twin files' columns (bk_locus_similarity of the reference around the two breakpoints of the call)
+static const char *SIMILAR_COLUMNS = "\tSim_Score\tSim_Len\tSim_Mism\tSim_Run\tSim_Strand\tSim_Pos1\tSim_Pos2";
+
+// One written call: its bk_locus_sim row (on: both contigs have a nib file, so the pair was submitted) and the lowest coordinate of
+// the shared stretch on either contig
+struct SimilarCall
+{
+  bool on = false;
+  struct bk_locus_sim s = {0, 0, 0, 0, 0, 0, 0, 0};
+  long pos1 = 0, pos2 = 0;
+  string fields() const
+  {
+    if (!on) return "\t.\t.\t.\t.\t.\t.\t.";
+    std::ostringstream o;
+    o << "\t" << s.score << "\t" << s.len << "\t" << s.mism << "\t" << s.run;
+    if (s.found)
+      o << "\t" << (s.orient ? "-" : "+") << "\t" << pos1 << "\t" << pos2;
+    else
+      o << "\t.\t.\t.";
+    return o.str();
+  }
+};
 // -clip -normal: what _fusion_rescued_normal.txt adds to a row of _fusion_rescued.txt
 static const char *RESCUED_COLUMNS_NORMAL = "\tNormal_DRP\tNormal_ClipAt1\tNormal_ClipAt2\tNormal_Depth1\tNormal_Depth2";
 
@@ -217,6 +239,7 @@ static bool rescued_written(const OutRow &r, bool all) { return all || (!call_no
 
 using ConsensusMap = std::map<uint64_t, std::pair<ConsensusSide, ConsensusSide>>;  // by row of BK_STAGE_CLUSTERS: the written calls
 using HomologyMap = std::map<uint64_t, std::pair<HomologySide, HomologySide>>;
+using SimilarMap = std::map<uint64_t, SimilarCall>;
 
 // -clip: the rescued clusters in the order of _fusion_rescued.txt, calls[k] to rows[k]; with -evidence the clipped reads at the peaks
 // of the written ones (bk_clip_reads: the rows of sites 2 * j and 2 * j + 1 belong to the j-th written row)
@@ -257,7 +280,7 @@ struct Twin
 };
 
 // The twins of this run, the reference's own two files first.  An option that adds columns to the calls adds its entry here.
-static vector<Twin> fusion_twins(const Options &o, const CallTables &t, const ConsensusMap &cons, const HomologyMap &hom)
+static vector<Twin> fusion_twins(const Options &o, const CallTables &t, const ConsensusMap &cons, const HomologyMap &hom, const SimilarMap &sim)
 {
   const bool with_normal = o.with_normal();  // (a tumour without calls still gets header-only twins)
   vector<Twin> twins;
@@ -303,6 +326,12 @@ static vector<Twin> fusion_twins(const Options &o, const CallTables &t, const Co
     twins.push_back({"_homology", HOMOLOGY_COLUMNS, [&hom](const OutRow &r, string &tail) {
                        if (!hom.count(r.idx)) return false;
                        tail = hom.at(r.idx).first.fields() + hom.at(r.idx).second.fields();
+                       return true;
+                     }});
+  if (o.similar)
+    twins.push_back({"_similar", SIMILAR_COLUMNS, [&sim](const OutRow &r, string &tail) {
+                       if (!sim.count(r.idx)) return false;
+                       tail = sim.at(r.idx).fields();
                        return true;
                      }});
   return twins;
@@ -371,6 +400,8 @@ struct VcfInput
   const ConsensusMap *cons = nullptr;
   // -homology (else null; needs cons): the same for the junction fit; HOMLEN / HOMSEQ / JINS / JAL / JMM / JSH behind CSN
   const HomologyMap *hom = nullptr;
+  // -similar (else null; never for the rescued clusters): SIMSCORE / SIMLEN / SIMRUN on both breakends of a call, last in INFO
+  const SimilarMap *sim = nullptr;
 };
 
 static char nib_base(const string &nib_dir, const string &chr, long pos1)  // the base at a 1-based position; N without a file or beyond it
@@ -472,6 +503,11 @@ static bool write_vcf(const string &path, const vector<OutRow> &rows, const VcfI
             o << ";JAL=" << h.f.aligned << ";JMM=" << h.f.mism << ";JSH=" << h.f.shift;
           }
         }
+        if (in.sim && in.sim->count(r.idx) && in.sim->at(r.idx).on)
+        {
+          const struct bk_locus_sim &ls = in.sim->at(r.idx).s;
+          o << ";SIMSCORE=" << ls.score << ";SIMLEN=" << ls.len << ";SIMRUN=" << ls.run;
+        }
         o << "\t" << (in.gsup ? "GT:GQ:DR:DV:RR:RV" : "DV:RV") << "\t" << vcf_sample(r.c.n_drp, r.c.n_sr, in.gsup ? &(*in.gsup)[r.idx] : nullptr, s);
         if (in.with_normal) o << "\t" << vcf_sample(in.nsup[r.idx].n_drp, in.nsup[r.idx].n_sr, in.gsup_normal ? &(*in.gsup_normal)[r.idx] : nullptr, s);
       }
@@ -515,6 +551,10 @@ static bool write_vcf(const string &path, const vector<OutRow> &rows, const VcfI
          "##INFO=<ID=JAL,Number=1,Type=Integer,Description=\"Bases of CSEQ placed in the reference at the mate breakpoint\">\n"
          "##INFO=<ID=JMM,Number=1,Type=Integer,Description=\"Mismatches among the JAL placed bases\">\n"
          "##INFO=<ID=JSH,Number=1,Type=Integer,Description=\"Offset of the placed sequence from the mate breakpoint, in bases into the mate's retained sequence\">\n";
+  if (in.sim && !in.rescued)
+    v << "##INFO=<ID=SIMSCORE,Number=1,Type=Integer,Description=\"Score (+1 a match, -2 a mismatch) of the best ungapped stretch the reference around the two breakpoints shares, on either strand\">\n"
+         "##INFO=<ID=SIMLEN,Number=1,Type=Integer,Description=\"Length of that stretch\">\n"
+         "##INFO=<ID=SIMRUN,Number=1,Type=Integer,Description=\"Longest exact stretch the reference around the two breakpoints shares, on either strand\">\n";
   if (in.rescued) v << "##INFO=<ID=SC,Number=1,Type=Integer,Description=\"Soft-clipped reads without an SA tag that end at this position (the clip peak)\">\n";
   if (in.gsup)
     v << "##FORMAT=<ID=GT,Number=1,Type=String,Description=\"Genotype\">\n"

@@ -1,23 +1,13 @@
 // Interface of jfit.hip: the voted sequence of a breakpoint side fitted to the reference at the other side (bk_junction_fit).
 #pragma once
-#include "bk_common.h"
-
-// a bk_refseq table on the device (jfit_upload)
-struct JfitRef
-{
-  uint32_t n = 0;
-  const int32_t *tid = nullptr;
-  const uint32_t *start = nullptr, *len = nullptr;
-  const uint64_t *off = nullptr;
-  const uint8_t *bases = nullptr;
-};
+#include "refseq_dev.h"
 
 struct JfitBufs
 {
   // the reference, the probes and the queries, uploaded per call
-  DevBuf tid, start, len, off, bases, probes, query;
+  RefseqBufs ref;
+  DevBuf probes, query;
   DevBuf res;
-  JfitRef view;
   const struct bk_junction_probe *d_probes = nullptr;
   const uint8_t *d_query = nullptr;
 };

@@ -11,65 +11,11 @@ constexpr int JF_QW = 4;  // query words: 256 columns
 constexpr int JF_MW = 9;  // mate walk: one empty word in front (a diagonal may start left of the walk on columns the mask drops), at
                           // most 64 + 64 + 256 + 64 = 448 bases, one word behind for the shifted read
 constexpr int JF_OW = 6;  // own walk: at most 64 + 256 = 320 bases, one word behind
-constexpr uint32_t CODE_N = 4;
 
 struct WaveLds
 {
   unsigned long long q[3][JF_QW], m[3][JF_MW], o[3][JF_OW];  // [0] low bit, [1] high bit, [2] valid
 };
-
-// the segments in (tid, start) order: how many have a key <= (t, p0)
-__device__ __forceinline__ long long seg_upper(const JfitRef &r, long long t, long long p0)
-{
-  uint32_t lo = 0, hi = r.n;
-  while (lo < hi)
-  {
-    const uint32_t mid = lo + (hi - lo) / 2;
-    const long long mt = r.tid[mid], ms = r.start[mid];
-    if (mt < t || (mt == t && ms <= p0))
-      lo = mid + 1;
-    else
-      hi = mid;
-  }
-  return (long long) lo;
-}
-
-// ref(t, p1) as a 2-bit code, CODE_N for N.  g0: the last segment whose key is <= the walk's lowest position (-1: none); the lane
-// goes on from there over the segments that start at or before its own position.
-__device__ __forceinline__ uint32_t ref_code(const JfitRef &r, long long g0, long long t, long long p1)
-{
-  const long long p0 = p1 - 1;
-  if (p0 < 0) return CODE_N;
-  long long g = g0;
-  while (g + 1 < (long long) r.n)
-  {
-    const long long nt = r.tid[g + 1], ns = r.start[g + 1];
-    if (nt < t || (nt == t && ns <= p0))
-      ++g;
-    else
-      break;
-  }
-  if (g < 0 || (long long) r.tid[g] != t) return CODE_N;
-  const long long i = p0 - (long long) r.start[g];
-  if (i >= (long long) r.len[g]) return CODE_N;
-  const uint32_t byte = r.bases[r.off[g] + (unsigned long long) (i >> 1)];
-  const uint32_t nib = (i & 1) ? (byte & 15u) : (byte >> 4);
-  if (nib & 4u) return CODE_N;                // 4..7 are N; bit 3 is the soft-mask
-  return (0x87u >> ((nib & 3u) << 1)) & 3u;  // T C A G -> 3 1 0 2
-}
-
-// 64 bits of a plane from bit position `bit` on (the word behind the last one that holds data is there and is zero)
-__device__ __forceinline__ unsigned long long window(const unsigned long long *plane, uint32_t bit)
-{
-  const uint32_t k = bit >> 6, r = bit & 63u;
-  const unsigned long long a = plane[k] >> r;
-  return r ? a | (plane[k + 1] << (64u - r)) : a;
-}
-
-__device__ __forceinline__ unsigned long long low_bits(int n)  // the n lowest bits, n clamped to 0..64
-{
-  return n <= 0 ? 0ull : n >= 64 ? ~0ull : (1ull << n) - 1ull;
-}
 
 // One wavefront per probe, four to a workgroup.
 __global__ __launch_bounds__(256) void k_junction_fit(JfitRef ref, const struct bk_junction_probe *__restrict__ probes, uint32_t n, const uint8_t *__restrict__ query,
@@ -208,27 +154,24 @@ __global__ __launch_bounds__(256) void k_junction_fit(JfitRef ref, const struct 
   res[k] = v;
 }
 
-template <class T> const T *upload(DevBuf &b, const T *host, uint64_t count, hipStream_t st)
-{
-  T *d = b.as<T>(count + 1);
-  if (count) HIP_CHECK(hipMemcpyAsync(d, host, count * sizeof(T), hipMemcpyHostToDevice, st));
-  return d;
-}
 }  // namespace
 
-void jfit_upload(const bk_refseq &ref, const struct bk_junction_probe *probes, uint64_t n, const uint8_t *query, uint32_t max_len, JfitBufs &b, hipStream_t st)
+void refseq_upload(const bk_refseq &ref, RefseqBufs &b, hipStream_t st)
 {
   JfitRef &r = b.view;
   r = JfitRef{};
   r.n = (uint32_t) ref.n_segs;
-  if (ref.n_segs)
-  {
-    r.tid = upload(b.tid, ref.tid, ref.n_segs, st);
-    r.start = upload(b.start, ref.start, ref.n_segs, st);
-    r.len = upload(b.len, ref.len, ref.n_segs, st);
-    r.off = upload(b.off, ref.off, ref.n_segs + 1, st);
-    r.bases = upload(b.bases, ref.bases, ref.off[ref.n_segs], st);
-  }
+  if (!ref.n_segs) return;
+  r.tid = upload(b.tid, ref.tid, ref.n_segs, st);
+  r.start = upload(b.start, ref.start, ref.n_segs, st);
+  r.len = upload(b.len, ref.len, ref.n_segs, st);
+  r.off = upload(b.off, ref.off, ref.n_segs + 1, st);
+  r.bases = upload(b.bases, ref.bases, ref.off[ref.n_segs], st);
+}
+
+void jfit_upload(const bk_refseq &ref, const struct bk_junction_probe *probes, uint64_t n, const uint8_t *query, uint32_t max_len, JfitBufs &b, hipStream_t st)
+{
+  refseq_upload(ref, b.ref, st);
   b.d_probes = upload(b.probes, probes, n, st);
   b.d_query = upload(b.query, query, n * max_len, st);
 }
@@ -239,6 +182,6 @@ void junction_fit(uint64_t n, uint32_t max_len, uint32_t max_shift, uint32_t max
   struct bk_junction_fit *res = b.res.as<struct bk_junction_fit>(n + 1);
   *res_out = res;
   if (n == 0) return;
-  hipLaunchKernelGGL(k_junction_fit, dim3(cdiv(n, 4)), dim3(256), 0, st, b.view, b.d_probes, (uint32_t) n, b.d_query, max_len, (int) max_shift, (int) max_ins, (int) max_hom,
+  hipLaunchKernelGGL(k_junction_fit, dim3(cdiv(n, 4)), dim3(256), 0, st, b.ref.view, b.d_probes, (uint32_t) n, b.d_query, max_len, (int) max_shift, (int) max_ins, (int) max_hom,
                      res);
 }

@@ -536,6 +536,43 @@ struct bk_junction_fit { int32_t shift; uint32_t ins, aligned, mism, hom_fwd, ho
 int bk_junction_fit(bk_ctx *ctx, const bk_refseq *ref, const struct bk_junction_probe *probes, uint64_t n, const uint8_t *query, uint32_t max_len, uint32_t max_shift,
                     uint32_t max_ins, uint32_t max_hom, const struct bk_junction_fit **out);
 
+/* ---- locus similarity: the reference at one breakpoint of a call against the reference at the other ------------------------------
+ * Two paralogous genes, a processed pseudogene and its parent, or two copies of a segmental duplication share a stretch of sequence;
+ * reads of one copy align to the other and a call forms between them.  bk_locus_similarity says how alike the two loci of a call are:
+ * the best ungapped stretch that window A, the reference around one breakpoint, shares with window B around the other, forward or
+ * reverse-complemented, and the longest exact common substring.  It reads nothing but the reference (bk_refseq, ref() and comp()
+ * as above; the soft-mask bit is ignored).  All arithmetic in signed 64-bit.
+ * Pair k: (tid_a, pos_a) and (tid_b, pos_b), pos 1-based.  R = flank, L = 2 R + 1.
+ *   window A                 a[i]  = ref(tid_a, pos_a - R + i), 0 <= i < L
+ *   window B, orientation 0  b0[j] = ref(tid_b, pos_b - R + j)
+ *   window B, orientation 1  b1[j] = comp(ref(tid_b, pos_b + R - j)): the reverse complement
+ * Cell (o, i, j) matches iff a[i] is one of A C G T and equals b_o[j].  A segment (o, d, i0, n), n >= 1, covers the columns
+ * i0 .. i0 + n - 1 of A against b_o[i + d], all inside both windows; its score is matches - 2 * mismatches, and every column that
+ * does not match is a mismatch, N on either side included.  The weights are a constant of the model: a stretch below two thirds
+ * identity does not grow, which is about where reads begin to mis-align between two copies.
+ * Excluded diagonal: when tid_a == tid_b, the diagonal d = pos_a - pos_b of orientation 0 compares every base with itself; it is left
+ * out entirely, of the best segment and of `run`.  (Without this every call whose breakpoints lie within 2 R of each other, a small
+ * deletion or duplication, would score its own overlap.)
+ * Best segment: the largest key (score, -n, -o, -|d|, [d >= 0], -i0): the highest score, then the shortest, orientation 0 first, the
+ * diagonal nearest 0, d >= 0 before d < 0, the smallest start.  When its score is > 0: found = 1, score, len = n,
+ * mism = (len - score) / 3, diag = d, start = i0, orient = o; otherwise the row is all zeros (tid < 0, windows of N, n_segs == 0).
+ * run: the longest stretch of consecutive matching cells on any diagonal of either orientation but the excluded one: the longest
+ * exact common substring.  found == 1 iff run >= 1.
+ * One pass finds the best segment of a diagonal: a running sum of +1 / -2 that restarts wherever it is <= 0, every end position
+ * offering (sum, length since the restart).
+ * Among random windows the best score is about 8 to 11 and run 8 to 10 (L = 301 and 511): orientation for the reader, no threshold.
+ * Every output is an integer count or an argmax with a fixed tie rule: two runs, and any permutation of the pairs, give the same bytes
+ * row for row.  The structs have no typedef. */
+struct bk_locus_pair { int32_t tid_a; uint32_t pos_a; int32_t tid_b; uint32_t pos_b; };              /* 16 bytes, pos 1-based */
+struct bk_locus_sim  { uint32_t score, len, mism, run; int32_t diag; uint32_t start, orient, found; }; /* 32 bytes */
+/* ctx: any live context that is not a shard (bk_shard_*); it gives the device, the stream, the buffers and bk_timing (scope
+ * `locus_similarity`; bk_timing_touched is n * (48 + L): the pair row, the result row and L nibbles of each window).  No stage needs
+ * to have run and nothing a later bk_fetch or stage returns changes.  ref, pairs: host memory.  *out (n rows) is library-owned until
+ * the next call or bk_free(ctx).  BK_ERR_ARG (with the reason in bk_last_error) for shards, null ctx / ref / out, null pairs with
+ * n > 0, flank outside 1..255, and every defect of the reference table that bk_junction_fit rejects.  BK_ERR_LIMIT beyond 2^30 pairs
+ * or 2^20 segments, looked at before any array is read.  n == 0 is no error, and neither is n_segs == 0 (every row is then zero). */
+int bk_locus_similarity(bk_ctx *ctx, const bk_refseq *ref, const struct bk_locus_pair *pairs, uint64_t n, uint32_t flank, const struct bk_locus_sim **out);
+
 /* Copy a stage's result to library-owned host memory.  *data stays valid until the next bk_fetch
  * of the same stage or bk_free.  group_off (may be NULL) receives n_groups+1 offsets for pair stages. */
 int bk_fetch(bk_ctx *ctx, int stage, const void **data, uint64_t *count, const uint64_t **group_off, uint32_t *n_groups);
