@@ -51,6 +51,9 @@ LOCUS_PAIR = np.dtype([("tid_a", "<i4"), ("pos_a", "<u4"), ("tid_b", "<i4"), ("p
 LOCUS_SIM = np.dtype([("score", "<u4"), ("len", "<u4"), ("mism", "<u4"), ("run", "<u4"), ("diag", "<i4"), ("start", "<u4"), ("orient", "<u4"),
                       ("found", "<u4")])  # struct bk_locus_sim
 assert LOCUS_PAIR.itemsize == 16 and LOCUS_SIM.itemsize == 32
+COV_WINDOW = np.dtype([("tid", "<i4"), ("beg", "<u4"), ("end", "<u4"), ("reserved", "<u4")])  # struct bk_cov_window; 0-based, half-open
+WINDOW_COV = np.dtype([("bases", "<u8"), ("reads", "<u4"), ("reserved", "<u4")])  # struct bk_window_cov
+assert COV_WINDOW.itemsize == 16 and WINDOW_COV.itemsize == 16
 # the columns of a bk_refseq table, in the struct's order (off has n_segs + 1 entries)
 REFSEQ_COLS = [("tid", np.int32), ("start", np.uint32), ("len", np.uint32), ("off", np.uint64), ("bases", np.uint8)]
 READ_KEY = np.dtype([("qhash", "<u8"), ("qcheck", "<u4"), ("tag", "<u4")])  # bk_read_key

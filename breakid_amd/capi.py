@@ -35,7 +35,7 @@ def build(verbose=False):
 
 EXPORTS = ["bk_init", "bk_prepare_process", "bk_free", "bk_last_error", "bk_set_stream", "bk_sync", "bk_get_stream", "bk_upload_records", "bk_records", "bk_exclude_regions", "bk_isize_stats",
            "bk_discordant_pairs", "bk_mask_and_cluster", "bk_split_evidence", "bk_cluster_summary",
-           "bk_split_breakpoints", "bk_normal_support", "bk_ref_support", "bk_genotype_call", "bk_clip_support", "bk_clip_reads", "bk_base_depth", "bk_clip_rescue", "bk_junctions", "bk_junction_sides", "bk_vcf_breakend_alt", "bk_evidence", "bk_unique_support", "bk_clip_consensus", "bk_junction_fit", "bk_locus_similarity", "bk_run", "bk_fetch", "bk_timing", "bk_timing_enable", "bk_timing_touched", "bk_group_stats", "bk_qname_hash", "bk_qname_check",
+           "bk_split_breakpoints", "bk_normal_support", "bk_ref_support", "bk_genotype_call", "bk_clip_support", "bk_clip_reads", "bk_base_depth", "bk_clip_rescue", "bk_junctions", "bk_junction_sides", "bk_vcf_breakend_alt", "bk_evidence", "bk_unique_support", "bk_clip_consensus", "bk_junction_fit", "bk_locus_similarity", "bk_window_coverage", "bk_call_windows", "bk_run", "bk_fetch", "bk_timing", "bk_timing_enable", "bk_timing_touched", "bk_group_stats", "bk_qname_hash", "bk_qname_check",
            "bk_bam_open", "bk_bam_header", "bk_bam_decode", "bk_bam_close", "bk_bam_extract", "bk_bam_names_free", "bk_bam_reads", "bk_reads_free", "bk_bam_decode_device", "bk_bam_decode_device_part", "bk_bam_decode_device_ctx", "bk_bam_dev_free", "bk_feed_release_caches", "bk_debug_bgzf_inflate", "bk_debug_std_sort", "bk_sort_forms", "bk_debug_ahc", "bk_debug_points", "bk_debug_cigar", "bk_debug_vote", "bk_debug_region", "bk_shard_begin", "bk_shard_get_stats", "bk_shard_set_stats",
            "bk_shard_sd_local", "bk_shard_sd_finish", "bk_shard_buffer", "bk_shard_set_buffer", "bk_shard_group_sizes",
            "bk_shard_own_groups", "bk_shard_route_candidates", "bk_shard_group_keys", "bk_shard_route_pairs", "bk_shard_group_pairs", "bk_shard_bp_cov", "bk_shard_bp_vote", "bk_shard_bp_vote_slice", "bk_shard_bp_set_voted", "bk_shard_bp_depth", "bk_shard_bp_finish"]
@@ -86,6 +86,8 @@ def lib():
         L.bk_clip_consensus.argtypes = [vp, C.POINTER(abi.Reads), vp, C.c_uint64, C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
         L.bk_junction_fit.argtypes = [vp, C.POINTER(abi.RefSeq), vp, C.c_uint64, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(vp)]
         L.bk_locus_similarity.argtypes = [vp, C.POINTER(abi.RefSeq), vp, C.c_uint64, C.c_uint32, C.POINTER(vp)]
+        L.bk_window_coverage.argtypes = [vp, vp, C.c_uint64, C.c_int, C.POINTER(vp)]
+        L.bk_call_windows.argtypes = [vp, C.c_int, C.c_int, C.c_uint32, vp, vp]
         L.bk_fetch.argtypes = [vp, C.c_int, C.POINTER(vp), u64p, C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(C.c_uint32)]
         L.bk_timing.argtypes = [vp, C.POINTER(C.POINTER(C.c_char_p)), C.POINTER(C.POINTER(C.c_float)),
                                 C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(C.c_int)]
@@ -239,6 +241,20 @@ def clip_rescue(cluster, junction, clip, min_support=3):
     if rc < 0:
         raise BreakIDError(rc, "bk_clip_rescue")
     return tuple(o.value for o in out) if rc == 1 else None
+
+
+def call_windows(cluster, right1, right2, flank, target_len):
+    """The coverage windows of one call (bk_call_windows; no GPU) for one abi.CLUSTER row, the sides bk_junction_sides gives it, the
+    flank length and the reference list's lengths: five abi.COV_WINDOW rows (left and right of either cut, then the span between
+    the cuts).  flank = 0 raises BreakIDError(BK_ERR_ARG)."""
+    c = np.zeros(1, abi.CLUSTER)
+    c[0] = cluster
+    lens = np.ascontiguousarray(target_len, np.uint32)
+    out = np.zeros(5, abi.COV_WINDOW)
+    rc = lib().bk_call_windows(c.ctypes.data, int(right1), int(right2), int(flank), lens.ctypes.data, out.ctypes.data)
+    if rc != 0:
+        raise BreakIDError(rc, "bk_call_windows")
+    return out
 
 
 def vcf_breakend_alt(ref_base, own_right, mate_chr, mate_pos, mate_right, cap=None):
@@ -553,6 +569,19 @@ class Context:
         if not len(tid):
             return np.zeros(0, np.uint32)
         return np.ctypeslib.as_array(C.cast(data, C.POINTER(C.c_uint32)), shape=(len(tid),)).copy()
+
+    def window_coverage(self, windows, mapq_min=0):
+        """The aligned bases of this context's eligible records inside arbitrary windows (bk_window_coverage).  windows:
+        abi.COV_WINDOW rows, 0-based and half-open.  Returns one abi.WINDOW_COV row per window."""
+        windows = np.ascontiguousarray(windows, abi.COV_WINDOW)
+        assert windows.ndim == 1
+        n = len(windows)
+        out = C.c_void_p()
+        self._check(self.L.bk_window_coverage(self.h, windows.ctypes.data if n else None, n, int(mapq_min), C.byref(out)))
+        if not n:
+            return np.zeros(0, abi.WINDOW_COV)
+        buf = (C.c_char * (n * abi.WINDOW_COV.itemsize)).from_address(out.value)
+        return np.frombuffer(buf, dtype=abi.WINDOW_COV, count=n).copy()
 
     def run(self, qual=20, fast=True):
         w, n = C.c_double(), C.c_uint64()

@@ -20,6 +20,7 @@
 #include "consensus.h"
 #include "jfit.h"
 #include "locsim.h"
+#include "coverage.h"
 #include "exclude.h"
 #include "ahc.h"
 #include "lanes.h"
@@ -158,6 +159,9 @@ struct bk_ctx
   // locus similarity (bk_locus_similarity)
   LocsimBufs lsb;
   std::vector<struct bk_locus_sim> f_locsim;
+  // window coverage (bk_window_coverage: this context holds the records)
+  CovBufs cvb;
+  std::vector<struct bk_window_cov> f_wincov;
 
   // fetch staging
   std::vector<bk_pair> f_pairs[3];
@@ -1389,6 +1393,51 @@ int bk_locus_similarity(bk_ctx *ctx, const bk_refseq *ref, const struct bk_locus
   });
 }
 
+int bk_window_coverage(bk_ctx *records, const struct bk_cov_window *windows, uint64_t n, int mapq_min, const struct bk_window_cov **out)
+{
+  return guarded(records, [&] {
+    if (!out || (n && !windows)) throw bk_error(BK_ERR_ARG, "bk_window_coverage: null argument");
+    if (records->shard) throw bk_error(BK_ERR_ARG, "bk_window_coverage: sharded contexts (bk_shard_*) are not supported");
+    if (!records->have_records || !records->stats_done) throw bk_error(BK_ERR_ARG, "bk_window_coverage: call bk_isize_stats first");
+    if (mapq_min < 0) throw bk_error(BK_ERR_ARG, "bk_window_coverage: mapq_min must be >= 0");
+    if (n > 0x40000000ull) throw bk_error(BK_ERR_LIMIT, "bk_window_coverage: more than 2^30 windows");
+    for (uint64_t k = 0; k < n; ++k)
+      if (windows[k].reserved) throw bk_error(BK_ERR_ARG, "bk_window_coverage: window " + std::to_string(k) + " has a non-zero reserved field");
+    const bk_soa &t = records->rec;
+    if (t.n && (!t.tid || !t.pos || !t.flag || !t.mapq || !t.cigar_off)) throw bk_error(BK_ERR_ARG, "bk_window_coverage: the record table lacks a column");
+    if (t.n_cigar_words && !t.cigar) throw bk_error(BK_ERR_ARG, "bk_window_coverage: the record table lacks a column");
+    CovBufs &b = records->cvb;
+    struct bk_window_cov *d_res = nullptr;
+    if (n) HIP_CHECK(hipMemcpyAsync(b.win.as<struct bk_cov_window>(n), windows, n * sizeof(struct bk_cov_window), hipMemcpyHostToDevice, records->st));
+    {
+      // the tile sums depend on mapq_min: rebuilt by every call.  touched: flag, mapq, tid and cigar_off of every record and its CIGAR
+      // words, the tile arrays, the window and its row (include/breakid_hip.h)
+      const uint64_t bytes = t.n * 11ull + t.n_cigar_words * 4ull + cov_tiles(t.n) * 16ull + n * 32ull;
+      // (the two scopes inside push timers of their own, so the whole one ends by its index, not at timers.back())
+      struct Whole
+      {
+        bk_ctx *c;
+        size_t at;
+        ~Whole()
+        {
+          if (c->timing && at < c->timers.size()) (void) hipEventRecord(c->timers[at].b, c->st);
+        }
+      } whole{records, records->timers.size()};
+      records->tick("window_coverage", bytes, true, bytes);
+      {
+        Scope s(records, "window_coverage_tiles", 0, t.n * 11ull + t.n_cigar_words * 4ull + cov_tiles(t.n) * 16ull);
+        cov_tiles_build(rec_view(records), mapq_min, b, records->st);
+      }
+      {
+        Scope s(records, "window_coverage_windows", 0, n * 32ull);
+        window_coverage(rec_view(records), records->nt, (int) records->hc.max_span, n, mapq_min, b, records->st, &d_res);
+      }
+    }
+    rows_to_host(records, d_res, n, records->f_wincov);
+    *out = records->f_wincov.data();
+  });
+}
+
 // The side rule of one call and the ALT text of one breakend (include/breakid_hip.h): pure host code.
 int bk_junction_sides(const struct bk_junction *j, uint8_t *right1, uint8_t *right2, uint8_t *source)
 {
@@ -1413,6 +1462,34 @@ int bk_junction_sides(const struct bk_junction *j, uint8_t *right1, uint8_t *rig
   }
   *right1 = (uint8_t) (idx >> 1);
   *right2 = (uint8_t) (idx & 1);
+  return BK_OK;
+}
+
+// The windows of one call (include/breakid_hip.h): pure host code.
+int bk_call_windows(const bk_cluster *c, int right1, int right2, uint32_t flank, const uint32_t *target_len, struct bk_cov_window out[5])
+{
+  if (!c || !target_len || !out || flank == 0) return BK_ERR_ARG;
+  const int32_t tid[2] = {c->p1_tid, c->p2_tid};
+  const long long cut[2] = {(long long) c->p1_exact - (right1 ? 1 : 0), (long long) c->p2_exact - (right2 ? 1 : 0)};
+  auto window = [&](int32_t t, long long a, long long b) {
+    struct bk_cov_window w = {t, 0u, 0u, 0u};
+    if (t < 0) return w;
+    const long long len = (long long) target_len[t];
+    a = a < 0 ? 0 : a;
+    b = b > len ? len : b;
+    if (b > a)
+    {
+      w.beg = (uint32_t) a;
+      w.end = (uint32_t) b;
+    }
+    return w;
+  };
+  for (int s = 0; s < 2; ++s)
+  {
+    out[2 * s] = window(tid[s], cut[s] - (long long) flank, cut[s]);
+    out[2 * s + 1] = window(tid[s], cut[s], cut[s] + (long long) flank);
+  }
+  out[4] = tid[0] == tid[1] && tid[0] >= 0 ? window(tid[0], std::min(cut[0], cut[1]), std::max(cut[0], cut[1])) : window(-1, 0, 0);
   return BK_OK;
 }
 

@@ -713,7 +713,7 @@ static void fetch_call_tables(const Options &o, const Sample &tumor, const Sampl
   if (o.genotype) fetch_rows(tumor, t.gsup, [&](auto rows, auto n) { return bk_ref_support(ctx, ctx, qual, anchor, w, rows, n); });
   if (o.genotype && normal.ctx) fetch_rows(tumor, t.gsup_normal, [&](auto rows, auto n) { return bk_ref_support(ctx, normal.ctx, qual, anchor, w, rows, n); });
   // -vcf: the junction evidence of every call (member pairs by strands, split tuples by clip side)
-  if (o.vcf || o.clip || o.consensus) fetch_rows(tumor, t.jsup, [&](auto rows, auto n) { return bk_junctions(ctx, rows, n); });
+  if (o.vcf || o.clip || o.consensus || o.coverage) fetch_rows(tumor, t.jsup, [&](auto rows, auto n) { return bk_junctions(ctx, rows, n); });
   // -clip: the clipped reads without an SA tag at every cluster, voted or not, on the sample's records and on the normal's
   if (o.clip) fetch_rows(tumor, t.csup, [&](auto rows, auto n) { return bk_clip_support(ctx, ctx, qual, min_clip, w, rows, n); });
   if (o.clip && normal.ctx) fetch_rows(tumor, t.csup_normal, [&](auto rows, auto n) { return bk_clip_support(ctx, normal.ctx, qual, min_clip, w, rows, n); });
@@ -1143,10 +1143,66 @@ static SimilarMap locus_similar(const Options &o, const Sample &tumor, const vec
   return sim;
 }
 
+// ---- -coverage: the mean depth beside and between the breakpoints of every written call -------------------------------------------
+// Five windows per written call (bk_call_windows, with the sides -vcf uses) and one per contig that carries a call; one call of
+// bk_window_coverage answers them all on the sample's records, a second one on the normal's.
+static CoverageMap call_coverage(const Options &o, const Sample &tumor, const Sample &normal, const CallTables &t, const vector<OutRow> &rows)
+{
+  CoverageMap cov;
+  vector<struct bk_cov_window> windows;
+  vector<uint64_t> window_call;
+  std::map<int32_t, size_t> contig_at;  // the contig's window, counted from the first of them
+  for (const OutRow &r : rows)
+  {
+    if (!call_written(r, o.all)) continue;
+    if (r.idx >= t.jsup.size())
+    {
+      std::cerr << "Error: the evidence tables do not cover every call" << std::endl;
+      exit(1);
+    }
+    uint8_t right[2] = {0, 1}, source = 0;
+    bk_junction_sides(&t.jsup[r.idx], &right[0], &right[1], &source);
+    CoverageCall &c = cov[r.idx];
+    if (bk_call_windows(&r.c, right[0], right[1], (uint32_t) o.covflank, tumor.lens, c.w) != BK_OK) die(tumor, BK_ERR_ARG);
+    c.cut[0] = (long long) r.c.p1_exact - right[0];
+    c.cut[1] = (long long) r.c.p2_exact - right[1];
+    window_call.push_back(r.idx);
+    windows.insert(windows.end(), c.w, c.w + 5);
+    for (int32_t tid : {r.c.p1_tid, r.c.p2_tid})
+      if (tid >= 0) contig_at.emplace(tid, 0);
+  }
+  const size_t first_contig = windows.size();
+  for (auto &at : contig_at)
+  {
+    at.second = windows.size() - first_contig;
+    windows.push_back(bk_cov_window{at.first, 0u, tumor.lens[at.first], 0u});
+  }
+  auto count = [&](const Sample &sample, bool is_normal) {
+    const struct bk_window_cov *res = nullptr;
+    const int rc = bk_window_coverage(sample.ctx, windows.data(), windows.size(), o.qual, &res);
+    if (rc != BK_OK) die(sample, rc);
+    for (size_t k = 0; k < window_call.size(); ++k)
+    {
+      CoverageCall &c = cov[window_call[k]];
+      struct bk_window_cov *into = is_normal ? c.normal : c.tumor;
+      std::copy(res + 5 * k, res + 5 * k + 5, into);
+      for (int s = 0; s < 2; ++s)
+      {
+        const int32_t tid = c.w[2 * s].tid;
+        c.w[5 + s] = tid >= 0 ? windows[first_contig + contig_at.at(tid)] : bk_cov_window{tid, 0u, 0u, 0u};
+        into[5 + s] = tid >= 0 ? res[first_contig + contig_at.at(tid)] : bk_window_cov{0, 0, 0};
+      }
+    }
+  };
+  count(tumor, false);
+  if (normal.ctx) count(normal, true);
+  return cov;
+}
+
 // ---- the files behind the tables ---------------------------------------------------------------------------------------------------
 // -vcf: <prefix>_fusion.vcf, and with -clip <prefix>_fusion_rescued.vcf
 static void write_vcf_files(const Options &o, const Sample &tumor, const CallTables &t, const vector<OutRow> &rows, const Rescued &rescued, const ConsensusMap &cons,
-                            const HomologyMap &hom, const SimilarMap &sim)
+                            const HomologyMap &hom, const SimilarMap &sim, const CoverageMap &cov)
 {
   VcfInput vi;
   vi.nt = tumor.nt;
@@ -1164,6 +1220,7 @@ static void write_vcf_files(const Options &o, const Sample &tumor, const CallTab
   vi.cons = o.consensus ? &cons : nullptr;
   vi.hom = o.homology ? &hom : nullptr;
   vi.sim = o.similar ? &sim : nullptr;
+  vi.cov = o.coverage ? &cov : nullptr;
   auto write = [&](const string &path, const vector<OutRow> &calls) {
     if (write_vcf(path, calls, vi)) return;
     std::cerr << "Error: cannot write " << path << ": the evidence tables do not cover every call" << std::endl;
@@ -1176,6 +1233,7 @@ static void write_vcf_files(const Options &o, const Sample &tumor, const CallTab
   vi.cons = nullptr;                   // ... and with -consensus
   vi.hom = nullptr;                    // ... and with -homology
   vi.sim = nullptr;                    // ... and with -similar
+  vi.cov = nullptr;                    // ... and with -coverage
   vi.rescued = &rescued.calls;
   write(o.out_file + "_fusion_rescued.vcf", rescued.rows);
 }
@@ -1225,6 +1283,7 @@ static void write_params(const Options &o, double w)
   if (o.homology) p << "homology_max_shift\t" << o.homshift << std::endl;
   if (o.homology) p << "homology_max_ins\t" << o.homins << std::endl;
   if (o.similar) p << "similar_flank\t" << o.simflank << std::endl;
+  if (o.coverage) p << "coverage_flank\t" << o.covflank << std::endl;
 }
 
 // BreakID.cc:175-191.  scan_pairs_count and after_cluster_count are never updated by the reference (always 0);
@@ -1296,10 +1355,12 @@ int main(int argc, char *argv[])
   if (o.homology) homology = junction_homology(o, tumor, consensus);
   SimilarMap similar;
   if (o.similar) similar = locus_similar(o, tumor, rows);
+  CoverageMap coverage;
+  if (o.coverage) coverage = call_coverage(o, tumor, normal, tables, rows);
 
   if (o.clip) write_rescued_tables(o, rescued, tables);
-  write_fusion_tables(o, rows, fusion_twins(o, tables, consensus.sides, homology, similar));
-  if (o.vcf) write_vcf_files(o, tumor, tables, rows, rescued, consensus.sides, homology, similar);
+  write_fusion_tables(o, rows, fusion_twins(o, tables, consensus.sides, homology, similar, coverage));
+  if (o.vcf) write_vcf_files(o, tumor, tables, rows, rescued, consensus.sides, homology, similar, coverage);
   if (o.evidence) write_evidence_files(o, tumor, tables, rows, rescued);
   write_params(o, run.w);
   const clock_t end = clock();

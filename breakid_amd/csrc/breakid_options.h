@@ -35,6 +35,9 @@ int bk_junction_fit(bk_ctx *ctx, const bk_refseq *ref, const struct bk_junction_
                     uint32_t max_ins, uint32_t max_hom, const struct bk_junction_fit **out) __attribute__((weak));
 // -similar
 int bk_locus_similarity(bk_ctx *ctx, const bk_refseq *ref, const struct bk_locus_pair *pairs, uint64_t n, uint32_t flank, const struct bk_locus_sim **out) __attribute__((weak));
+// -coverage (the windows of a call and the aligned bases inside them)
+int bk_window_coverage(bk_ctx *records, const struct bk_cov_window *windows, uint64_t n, int mapq_min, const struct bk_window_cov **out) __attribute__((weak));
+int bk_call_windows(const bk_cluster *c, int right1, int right2, uint32_t flank, const uint32_t *target_len, struct bk_cov_window out[5]) __attribute__((weak));
 // -dedup
 int bk_unique_support(bk_ctx *ctx, const struct bk_unique_support **out, uint64_t *count, const uint64_t **first, uint64_t *n_rows) __attribute__((weak));
 // -clip (the soft-clip evidence, the depth at the rescued positions and the rescue rule)
@@ -79,20 +82,23 @@ static const char *HELP =
      \t -homshift  \t largest offset of the continuation from the called position, 0 to 64 (with -homology)  [32]\n \
      \t -homins    \t longest inserted sequence, 0 to 64 (with -homology)  [32]\n \
      \t -similar   \t score the reference around the two breakpoints of every call against each other, forward and reverse-complemented (twin files *_similar.txt; SIMSCORE / SIMLEN / SIMRUN with -vcf)  \n \
-     \t -simflank  \t bases either side of a breakpoint that are compared, 1 to 255 (with -similar)  [150]\n ";
+     \t -simflank  \t bases either side of a breakpoint that are compared, 1 to 255 (with -similar)  [150]\n \
+     \t -coverage  \t mean depth of the aligned bases either side of both breakpoints of every call, between them and over their contigs (twin files *_coverage.txt; COVL / COVR / RDRATIO with -vcf)  \n \
+     \t -covflank  \t bases either side of a breakpoint that are averaged, 1 to 1000000 (with -coverage)  [1000]\n ";
 
 struct Options
 {
   std::string inp_file, out_file, nib_dir, normal_file, exclude_file, build = "hg19";
   int qual = 20, device = 0, n_gpus = 0, transport = BK_TRANSPORT_AUTO;  // -gpus N: one sample over N GPUs (include/breakid_multi.h)
   bool fast = false, all = false;                                        // -all: no gene-pair and repeat filter (the _fusion_all files)
-  bool genotype = false, vcf = false, evidence = false, clip = false, dedup = false, consensus = false, homology = false, similar = false;
-  bool anchor_given = false, minclip_given = false, clipsupport_given = false, conslen_given = false, homshift_given = false, homins_given = false, simflank_given = false;
+  bool genotype = false, vcf = false, evidence = false, clip = false, dedup = false, consensus = false, homology = false, similar = false, coverage = false;
+  bool anchor_given = false, minclip_given = false, clipsupport_given = false, conslen_given = false, homshift_given = false, homins_given = false, simflank_given = false, covflank_given = false;
   long anchor = 10;                      // -anchor: bases a reference read must cover on either side of the breakpoint base
   long min_clip = 10, clip_support = 3;  // -minclip: shortest clip that counts; -clipsupport: reads at one position a rescued side needs
   long conslen = 64;                     // -conslen: longest junction sequence per side
   long homshift = 32, homins = 32;       // -homshift, -homins: the largest offset and the longest insertion bk_junction_fit looks for
   long simflank = 150;                   // -simflank: the bases either side of a breakpoint that bk_locus_similarity compares
+  long covflank = 1000;                  // -covflank: the bases either side of a cut that bk_call_windows gives a flank window
   bool multi() const { return n_gpus >= 1; }  // the sharded run
   bool with_normal() const { return !normal_file.empty(); }
   bool exclude() const { return !exclude_file.empty(); }
@@ -130,6 +136,7 @@ static void check_options(const Options &o)
   const Feature dedup{"-dedup", o.dedup, false, bk_unique_support != nullptr};
   const Feature homology{"-homology", o.homology, false, bk_junction_fit != nullptr};
   const Feature similar{"-similar", o.similar, false, bk_locus_similarity != nullptr};
+  const Feature coverage{"-coverage", o.coverage, false, bk_window_coverage && bk_call_windows && bk_junctions && bk_junction_sides};
   const Feature consensus{"-consensus", o.consensus, false, bk_clip_consensus && bk_clip_reads && bk_evidence && bk_junctions && bk_junction_sides};
   const Feature clip{"-clip", o.clip, false, bk_clip_support && bk_clip_reads && bk_base_depth && bk_clip_rescue && bk_junctions && bk_junction_sides};
   const Feature exclude{"-x", o.exclude(), true, bk_exclude_regions && bk_multi_run_ex && bk_multi_run_bam_ex && bk_multi_excluded};
@@ -157,9 +164,11 @@ static void check_options(const Options &o)
       library(clip), gpus(clip),  // (the one option that looks for the library first)
       rule(o.clip && !(in_range(o.min_clip, 1, int_max) && in_range(o.clip_support, 1, int_max)), "-minclip and -clipsupport must be numbers from 1 to 2147483647."),
       gpus(exclude), library(exclude), {Refusal::OPEN, exclude.set && !opens(o.exclude_file), "exclude file: " + o.exclude_file},
-      // (behind every older row: no command line without the two options changes its answer)
+      // (behind every older row: no command line without these options changes its answer)
       rule(o.simflank_given && !o.similar, "-simflank needs -similar."), gpus(similar), library(similar),
       rule(o.similar && !in_range(o.simflank, 1, 255), "-simflank must be a number from 1 to 255."),
+      rule(o.covflank_given && !o.coverage, "-covflank needs -coverage."), gpus(coverage), library(coverage),
+      rule(o.coverage && !in_range(o.covflank, 1, 1000000), "-covflank must be a number from 1 to 1000000."),
   };
   for (const Refusal &r : refusals)
   {
@@ -183,7 +192,7 @@ static Options parse_options(int argc, char *argv[])
                                      {"anchor", 1, 0, 14}, {"vcf", 0, 0, 15}, {"evidence", 0, 0, 16}, {"clip", 0, 0, 17},
                                      {"minclip", 1, 0, 18}, {"clipsupport", 1, 0, 19}, {"dedup", 0, 0, 20}, {"consensus", 0, 0, 21},
                                      {"conslen", 1, 0, 22}, {"homology", 0, 0, 23}, {"homshift", 1, 0, 24}, {"homins", 1, 0, 25},
-                                     {"similar", 0, 0, 26}, {"simflank", 1, 0, 27}, {0, 0, 0, 0}};
+                                     {"similar", 0, 0, 26}, {"simflank", 1, 0, 27}, {"coverage", 0, 0, 28}, {"covflank", 1, 0, 29}, {0, 0, 0, 0}};
   Options o;
   auto number = [](long &value, bool &given) {
     value = atol(optarg);
@@ -223,6 +232,8 @@ static Options parse_options(int argc, char *argv[])
     case 25: number(o.homins, o.homins_given); break;
     case 26: o.similar = true; break;
     case 27: number(o.simflank, o.simflank_given); break;
+    case 28: o.coverage = true; break;
+    case 29: number(o.covflank, o.covflank_given); break;
     default: std::cerr << "Error: cannot parse arguments.\n"; exit(1);
     }
   }

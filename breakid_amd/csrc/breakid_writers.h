@@ -216,6 +216,50 @@ struct SimilarCall
     return o.str();
   }
 };
+// -coverage: the twin files' columns (bk_window_coverage of the windows bk_call_windows gives the call, and of its contigs); with
+// -normal the same eight once more, from the same windows on the normal's records
+static const char *COVERAGE_NAMES[8] = {"Cov_L1", "Cov_R1", "Cov_L2", "Cov_R2", "Cov_Span", "Cov_SpanRatio", "Cov_Contig1", "Cov_Contig2"};
+static string coverage_columns(const char *prefix)
+{
+  string s;
+  for (const char *name : COVERAGE_NAMES) s += string("\t") + prefix + name;
+  return s;
+}
+
+// One written call: its seven windows (the five of bk_call_windows, then the whole contig of either side), the cut of either side, and
+// what the sample's records, and the normal's, have inside the windows
+struct CoverageCall
+{
+  struct bk_cov_window w[7];
+  long long cut[2] = {0, 0};
+  struct bk_window_cov tumor[7], normal[7];
+  bool empty(int k) const { return w[k].end <= w[k].beg; }
+  double mean(const struct bk_window_cov *cov, int k) const { return (double) cov[k].bases / (double) (w[k].end - w[k].beg); }
+  static string fixed(const char *format, double v)
+  {
+    char buf[64];
+    snprintf(buf, sizeof buf, format, v);
+    return buf;
+  }
+  string mean_text(const struct bk_window_cov *cov, int k) const { return empty(k) ? "." : fixed("%.2f", mean(cov, k)); }
+  // the span's mean over the mean of the two outer flanks: the left window of the lower cut and the right window of the higher one
+  string ratio_text(const struct bk_window_cov *cov) const
+  {
+    const int lo = cut[0] <= cut[1] ? 0 : 1, outer_l = 2 * lo, outer_r = 2 * (1 - lo) + 1;
+    if (empty(4) || empty(outer_l) || empty(outer_r)) return ".";
+    const double flanks = mean(cov, outer_l) + mean(cov, outer_r);
+    if (flanks == 0.0) return ".";
+    return fixed("%.3f", mean(cov, 4) / (flanks / 2.0));
+  }
+  string fields(const struct bk_window_cov *cov) const
+  {
+    string s;
+    for (int k = 0; k < 5; ++k) s += "\t" + mean_text(cov, k);
+    s += "\t" + ratio_text(cov);
+    for (int k = 5; k < 7; ++k) s += "\t" + mean_text(cov, k);
+    return s;
+  }
+};
 // -clip -normal: what _fusion_rescued_normal.txt adds to a row of _fusion_rescued.txt
 static const char *RESCUED_COLUMNS_NORMAL = "\tNormal_DRP\tNormal_ClipAt1\tNormal_ClipAt2\tNormal_Depth1\tNormal_Depth2";
 
@@ -240,6 +284,7 @@ static bool rescued_written(const OutRow &r, bool all) { return all || (!call_no
 using ConsensusMap = std::map<uint64_t, std::pair<ConsensusSide, ConsensusSide>>;  // by row of BK_STAGE_CLUSTERS: the written calls
 using HomologyMap = std::map<uint64_t, std::pair<HomologySide, HomologySide>>;
 using SimilarMap = std::map<uint64_t, SimilarCall>;
+using CoverageMap = std::map<uint64_t, CoverageCall>;
 
 // -clip: the rescued clusters in the order of _fusion_rescued.txt, calls[k] to rows[k]; with -evidence the clipped reads at the peaks
 // of the written ones (bk_clip_reads: the rows of sites 2 * j and 2 * j + 1 belong to the j-th written row)
@@ -280,7 +325,8 @@ struct Twin
 };
 
 // The twins of this run, the reference's own two files first.  An option that adds columns to the calls adds its entry here.
-static vector<Twin> fusion_twins(const Options &o, const CallTables &t, const ConsensusMap &cons, const HomologyMap &hom, const SimilarMap &sim)
+static vector<Twin> fusion_twins(const Options &o, const CallTables &t, const ConsensusMap &cons, const HomologyMap &hom, const SimilarMap &sim,
+                                 const CoverageMap &cov)
 {
   const bool with_normal = o.with_normal();  // (a tumour without calls still gets header-only twins)
   vector<Twin> twins;
@@ -332,6 +378,13 @@ static vector<Twin> fusion_twins(const Options &o, const CallTables &t, const Co
     twins.push_back({"_similar", SIMILAR_COLUMNS, [&sim](const OutRow &r, string &tail) {
                        if (!sim.count(r.idx)) return false;
                        tail = sim.at(r.idx).fields();
+                       return true;
+                     }});
+  if (o.coverage)
+    twins.push_back({"_coverage", coverage_columns("") + (with_normal ? coverage_columns("Normal_") : ""), [&cov, with_normal](const OutRow &r, string &tail) {
+                       if (!cov.count(r.idx)) return false;
+                       const CoverageCall &c = cov.at(r.idx);
+                       tail = c.fields(c.tumor) + (with_normal ? c.fields(c.normal) : "");
                        return true;
                      }});
   return twins;
@@ -402,6 +455,8 @@ struct VcfInput
   const HomologyMap *hom = nullptr;
   // -similar (else null; never for the rescued clusters): SIMSCORE / SIMLEN / SIMRUN on both breakends of a call, last in INFO
   const SimilarMap *sim = nullptr;
+  // -coverage (else null; never for the rescued clusters): COVL / COVR of the breakend's own side and RDRATIO, behind everything else
+  const CoverageMap *cov = nullptr;
 };
 
 static char nib_base(const string &nib_dir, const string &chr, long pos1)  // the base at a 1-based position; N without a file or beyond it
@@ -508,6 +563,12 @@ static bool write_vcf(const string &path, const vector<OutRow> &rows, const VcfI
           const struct bk_locus_sim &ls = in.sim->at(r.idx).s;
           o << ";SIMSCORE=" << ls.score << ";SIMLEN=" << ls.len << ";SIMRUN=" << ls.run;
         }
+        if (in.cov && in.cov->count(r.idx))
+        {
+          const CoverageCall &cc = in.cov->at(r.idx);
+          o << ";COVL=" << cc.mean_text(cc.tumor, 2 * s) << ";COVR=" << cc.mean_text(cc.tumor, 2 * s + 1);
+          if (cc.ratio_text(cc.tumor) != ".") o << ";RDRATIO=" << cc.ratio_text(cc.tumor);
+        }
         o << "\t" << (in.gsup ? "GT:GQ:DR:DV:RR:RV" : "DV:RV") << "\t" << vcf_sample(r.c.n_drp, r.c.n_sr, in.gsup ? &(*in.gsup)[r.idx] : nullptr, s);
         if (in.with_normal) o << "\t" << vcf_sample(in.nsup[r.idx].n_drp, in.nsup[r.idx].n_sr, in.gsup_normal ? &(*in.gsup_normal)[r.idx] : nullptr, s);
       }
@@ -555,6 +616,10 @@ static bool write_vcf(const string &path, const vector<OutRow> &rows, const VcfI
     v << "##INFO=<ID=SIMSCORE,Number=1,Type=Integer,Description=\"Score (+1 a match, -2 a mismatch) of the best ungapped stretch the reference around the two breakpoints shares, on either strand\">\n"
          "##INFO=<ID=SIMLEN,Number=1,Type=Integer,Description=\"Length of that stretch\">\n"
          "##INFO=<ID=SIMRUN,Number=1,Type=Integer,Description=\"Longest exact stretch the reference around the two breakpoints shares, on either strand\">\n";
+  if (in.cov && !in.rescued)
+    v << "##INFO=<ID=COVL,Number=1,Type=Float,Description=\"Mean depth of the aligned bases in the window left of this breakpoint's cut\">\n"
+         "##INFO=<ID=COVR,Number=1,Type=Float,Description=\"Mean depth of the aligned bases in the window right of this breakpoint's cut\">\n"
+         "##INFO=<ID=RDRATIO,Number=1,Type=Float,Description=\"Mean depth between the two breakpoints over the mean depth of the two outer flanks\">\n";
   if (in.rescued) v << "##INFO=<ID=SC,Number=1,Type=Integer,Description=\"Soft-clipped reads without an SA tag that end at this position (the clip peak)\">\n";
   if (in.gsup)
     v << "##FORMAT=<ID=GT,Number=1,Type=String,Description=\"Genotype\">\n"

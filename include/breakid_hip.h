@@ -573,6 +573,48 @@ struct bk_locus_sim  { uint32_t score, len, mism, run; int32_t diag; uint32_t st
  * or 2^20 segments, looked at before any array is read.  n == 0 is no error, and neither is n_segs == 0 (every row is then zero). */
 int bk_locus_similarity(bk_ctx *ctx, const bk_refseq *ref, const struct bk_locus_pair *pairs, uint64_t n, uint32_t flank, const struct bk_locus_sim **out);
 
+/* ---- window coverage: the aligned bases inside arbitrary windows of the record table --------------------------------------------
+ * Whether copy number changes at a breakpoint: the depth between the two breakpoints of a deletion drops, that of a tandem
+ * duplication rises, an unbalanced translocation shows a step at one breakpoint only.  depth1 / depth2 are the count at the
+ * breakpoint base itself and say nothing about either side of it.  bk_window_coverage answers any number of windows of any length,
+ * each in time that does not depend on its length.  All arithmetic in signed 64-bit.
+ * Record i of the `records` context is eligible when tid[i] >= 0, its flag has none of 0x4 0x100 0x200 0x400 0x800 (0x1 is not
+ * required), mapq[i] >= mapq_min and its CIGAR has a reference length > 0 (M, D, N, =, X).  Its interval is [pos[i], bam_endpos(i)),
+ * bam_endpos as in bk_exclude_regions and bk_ref_support: D and N count, soft clips do not, and a read with an SA tag counts like
+ * any other.  For window k = (T, a, b), 0-based and half-open:
+ *   bases  the sum over the eligible records on T of |[pos, bam_endpos) n [a, b)|
+ *   reads  the number of eligible records on T for which that overlap is not empty
+ * T < 0, T >= n_targets and b <= a give a zero row.  A window is not clamped against the contig length: no record lies beyond it.
+ * With mapq_min = 0, on a table without supplementary records (0x800, which the reference's filter lets through), `bases` is the
+ * `coverage` of the reference's cal_mean_depth (util_bed.cc:18-70) for the 1-based inclusive region [a + 1, b].
+ * How: one streaming pass sums the eligible lengths of every tile of 256 records; an exclusive scan makes them prefixes S (lengths)
+ * and C (records).  With h(x) = the first record of T with pos >= x, the records that start before x are a prefix of the table, and
+ * only those within max_span (the longest alignment, from bk_isize_stats) of x can reach beyond it:
+ *   bases = (S(h(b)) - over(b)) - (S(h(a)) - over(a)),  over(x) = the sum of bam_endpos - x over the eligible records with pos < x < bam_endpos
+ *   reads = C(h(b)) - C(h(a)) + the number of eligible records with pos < a < bam_endpos
+ * The tile sums depend on mapq_min and are rebuilt by every call.  Every output is an integer: two runs, and any permutation of the
+ * windows, give the same bytes row for row.  The structs have no typedef. */
+struct bk_cov_window { int32_t tid; uint32_t beg, end; uint32_t reserved; };   /* 16 bytes; 0-based, half-open; reserved = 0 */
+struct bk_window_cov { uint64_t bases; uint32_t reads; uint32_t reserved; };   /* 16 bytes; reserved = 0 */
+/* records: after bk_isize_stats (the stream pass gives max_span), not a shard (bk_shard_*).  windows: host memory.  *out (n rows) is
+ * library-owned until the next call or bk_free(records).  BK_ERR_ARG (with the reason in bk_last_error) for a null out, null windows
+ * with n > 0, wrong call order, shards, mapq_min < 0 and a window whose reserved is not 0; BK_ERR_LIMIT beyond 2^30 windows.  n == 0
+ * and a table without records are no errors (every row is then zero).  It changes nothing a later bk_fetch or stage returns, and
+ * works on every table form the context can hold (host upload, BK_MEM_DEVICE with and without `side`, the table bk_exclude_regions
+ * left behind, where the excluded records simply do not count, the context of bk_bam_decode_device_ctx while its bk_bam_dev lives).
+ * bk_timing: scope `window_coverage`, with `window_coverage_tiles` (the tile pass and its scans) and `window_coverage_windows` (the
+ * window kernel) inside it.  bk_timing_touched of `window_coverage`: 11 bytes of every record (flag, mapq, tid, cigar_off) and its
+ * CIGAR words, 16 bytes per tile, 32 bytes per window; the records the windows' edges visit are not modelled. */
+int bk_window_coverage(bk_ctx *records, const struct bk_cov_window *windows, uint64_t n, int mapq_min, const struct bk_window_cov **out);
+/* The windows of one call, a pure host function (no context, no GPU), so that every caller shares one rule.  Side s (0 = p1, 1 = p2)
+ * has the exact 1-based breakpoint e = ps_exact and a direction right_s from bk_junction_sides (0 = LEFT, 1 = RIGHT).  Its cut is
+ * k_s = e for a LEFT side and e - 1 for a RIGHT side, so the breakpoint base (0-based e - 1) always lies in the window on the
+ * retained side.  out[2 s] = [k_s - flank, k_s) and out[2 s + 1] = [k_s, k_s + flank), both clamped to [0, target_len[ps_tid]); a
+ * clamped window with end <= beg is written as (ps_tid, 0, 0).  out[4] = [min(k_1, k_2), max(k_1, k_2)), clamped likewise, when
+ * p1_tid == p2_tid >= 0, and (-1, 0, 0) otherwise.  A negative tid gives (tid, 0, 0).  reserved = 0 everywhere.  target_len is the reference
+ * list of bk_init (it must cover both tids).  Returns BK_OK, or BK_ERR_ARG for a null argument or flank == 0. */
+int bk_call_windows(const bk_cluster *c, int right1, int right2, uint32_t flank, const uint32_t *target_len, struct bk_cov_window out[5]);
+
 /* Copy a stage's result to library-owned host memory.  *data stays valid until the next bk_fetch
  * of the same stage or bk_free.  group_off (may be NULL) receives n_groups+1 offsets for pair stages. */
 int bk_fetch(bk_ctx *ctx, int stage, const void **data, uint64_t *count, const uint64_t **group_off, uint32_t *n_groups);
