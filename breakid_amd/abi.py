@@ -54,6 +54,16 @@ assert LOCUS_PAIR.itemsize == 16 and LOCUS_SIM.itemsize == 32
 COV_WINDOW = np.dtype([("tid", "<i4"), ("beg", "<u4"), ("end", "<u4"), ("reserved", "<u4")])  # struct bk_cov_window; 0-based, half-open
 WINDOW_COV = np.dtype([("bases", "<u8"), ("reads", "<u4"), ("reserved", "<u4")])  # struct bk_window_cov
 assert COV_WINDOW.itemsize == 16 and WINDOW_COV.itemsize == 16
+FRAME_SITE = np.dtype([("tid1", "<i4"), ("pos1", "<u4"), ("tid2", "<i4"), ("pos2", "<u4"), ("right1", "u1"), ("right2", "u1"), ("reserved", "u1", (6,))])  # struct bk_frame_site; pos 1-based
+FRAME_CALL = np.dtype([("cls", "u1"), ("order", "u1"), ("loc", "u1", (2,)), ("role", "u1", (2,)), ("exon", "<u2", (2,)), ("reserved", "<u2"), ("tx", "<i4", (2,)),
+                       ("cod", "<u4", (2,)), ("n_tx", "<u4", (2,)), ("n_inframe", "<u4"), ("n_compatible", "<u4"), ("reserved2", "<u4")])  # struct bk_frame_call
+assert FRAME_SITE.itemsize == 24 and FRAME_CALL.itemsize == 48
+FRAME_CLASSES = ["none", "antisense", "truncating", "promoter", "outframe", "inframe"]  # BK_FRAME_*
+FRAME_HEAD, FRAME_TAIL = 1, 2
+FRAME_CHUNK = 128  # csrc/frame.h: the overlapping transcripts of one side that the kernel stages at a time
+FRAME_LOCS = [".", "noncoding", "5UTR", "CDS", "intron", "3UTR"]  # BK_LOC_*
+# the columns of a bk_txmodel, in the struct's order (ex_off has n_tx + 1 entries, ex_start / ex_end n_parts)
+TXMODEL_COLS = [("tid", np.int32), ("tx_start", np.uint32), ("tx_end", np.uint32), ("strand", np.uint8), ("ex_off", np.uint32), ("ex_start", np.uint32), ("ex_end", np.uint32)]
 # the columns of a bk_refseq table, in the struct's order (off has n_segs + 1 entries)
 REFSEQ_COLS = [("tid", np.int32), ("start", np.uint32), ("len", np.uint32), ("off", np.uint64), ("bases", np.uint8)]
 READ_KEY = np.dtype([("qhash", "<u8"), ("qcheck", "<u4"), ("tag", "<u4")])  # bk_read_key
@@ -70,6 +80,10 @@ class Reads(C.Structure):  # bk_reads
 
 class RefSeq(C.Structure):  # bk_refseq
     _fields_ = [("n_segs", C.c_uint64)] + [(name, C.c_void_p) for name, _ in REFSEQ_COLS]
+
+
+class TxModel(C.Structure):  # bk_txmodel
+    _fields_ = [("n_tx", C.c_uint64), ("n_parts", C.c_uint64)] + [(name, C.c_void_p) for name, _ in TXMODEL_COLS]
 
 
 class Soa(C.Structure):

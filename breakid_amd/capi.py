@@ -35,7 +35,7 @@ def build(verbose=False):
 
 EXPORTS = ["bk_init", "bk_prepare_process", "bk_free", "bk_last_error", "bk_set_stream", "bk_sync", "bk_get_stream", "bk_upload_records", "bk_records", "bk_exclude_regions", "bk_isize_stats",
            "bk_discordant_pairs", "bk_mask_and_cluster", "bk_split_evidence", "bk_cluster_summary",
-           "bk_split_breakpoints", "bk_normal_support", "bk_ref_support", "bk_genotype_call", "bk_clip_support", "bk_clip_reads", "bk_base_depth", "bk_clip_rescue", "bk_junctions", "bk_junction_sides", "bk_vcf_breakend_alt", "bk_evidence", "bk_unique_support", "bk_clip_consensus", "bk_junction_fit", "bk_locus_similarity", "bk_window_coverage", "bk_call_windows", "bk_run", "bk_fetch", "bk_timing", "bk_timing_enable", "bk_timing_touched", "bk_group_stats", "bk_qname_hash", "bk_qname_check",
+           "bk_split_breakpoints", "bk_normal_support", "bk_ref_support", "bk_genotype_call", "bk_clip_support", "bk_clip_reads", "bk_base_depth", "bk_clip_rescue", "bk_junctions", "bk_junction_sides", "bk_vcf_breakend_alt", "bk_evidence", "bk_unique_support", "bk_clip_consensus", "bk_junction_fit", "bk_locus_similarity", "bk_window_coverage", "bk_call_windows", "bk_fusion_frame", "bk_run", "bk_fetch", "bk_timing", "bk_timing_enable", "bk_timing_touched", "bk_group_stats", "bk_qname_hash", "bk_qname_check",
            "bk_bam_open", "bk_bam_header", "bk_bam_decode", "bk_bam_close", "bk_bam_extract", "bk_bam_names_free", "bk_bam_reads", "bk_reads_free", "bk_bam_decode_device", "bk_bam_decode_device_part", "bk_bam_decode_device_ctx", "bk_bam_dev_free", "bk_feed_release_caches", "bk_debug_bgzf_inflate", "bk_debug_std_sort", "bk_sort_forms", "bk_debug_ahc", "bk_debug_points", "bk_debug_cigar", "bk_debug_vote", "bk_debug_region", "bk_shard_begin", "bk_shard_get_stats", "bk_shard_set_stats",
            "bk_shard_sd_local", "bk_shard_sd_finish", "bk_shard_buffer", "bk_shard_set_buffer", "bk_shard_group_sizes",
            "bk_shard_own_groups", "bk_shard_route_candidates", "bk_shard_group_keys", "bk_shard_route_pairs", "bk_shard_group_pairs", "bk_shard_bp_cov", "bk_shard_bp_vote", "bk_shard_bp_vote_slice", "bk_shard_bp_set_voted", "bk_shard_bp_depth", "bk_shard_bp_finish"]
@@ -88,6 +88,7 @@ def lib():
         L.bk_locus_similarity.argtypes = [vp, C.POINTER(abi.RefSeq), vp, C.c_uint64, C.c_uint32, C.POINTER(vp)]
         L.bk_window_coverage.argtypes = [vp, vp, C.c_uint64, C.c_int, C.POINTER(vp)]
         L.bk_call_windows.argtypes = [vp, C.c_int, C.c_int, C.c_uint32, vp, vp]
+        L.bk_fusion_frame.argtypes = [vp, C.POINTER(abi.TxModel), vp, C.c_uint64, C.POINTER(vp)]
         L.bk_fetch.argtypes = [vp, C.c_int, C.POINTER(vp), u64p, C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(C.c_uint32)]
         L.bk_timing.argtypes = [vp, C.POINTER(C.POINTER(C.c_char_p)), C.POINTER(C.POINTER(C.c_float)),
                                 C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(C.c_int)]
@@ -583,6 +584,21 @@ class Context:
         buf = (C.c_char * (n * abi.WINDOW_COV.itemsize)).from_address(out.value)
         return np.frombuffer(buf, dtype=abi.WINDOW_COV, count=n).copy()
 
+    def fusion_frame(self, model, sites):
+        """The 5' / 3' partners and the reading frame of every site (bk_fusion_frame).  model: a TxModel, or a dict of the bk_txmodel
+        columns (abi.TXMODEL_COLS); sites: abi.FRAME_SITE rows.  Returns one abi.FRAME_CALL row per site."""
+        sites = np.ascontiguousarray(sites, abi.FRAME_SITE)
+        assert sites.ndim == 1
+        n = len(sites)
+        t, keep = txmodel_struct(model.cols if isinstance(model, TxModel) else model)
+        out = C.c_void_p()
+        self._check(self.L.bk_fusion_frame(self.h, C.byref(t), sites.ctypes.data if n else None, n, C.byref(out)))
+        del keep
+        if not n:
+            return np.zeros(0, abi.FRAME_CALL)
+        buf = (C.c_char * (n * abi.FRAME_CALL.itemsize)).from_address(out.value)
+        return np.frombuffer(buf, dtype=abi.FRAME_CALL, count=n).copy()
+
     def run(self, qual=20, fast=True):
         w, n = C.c_double(), C.c_uint64()
         self._check(self.L.bk_run(self.h, qual, int(fast), C.byref(w), C.byref(n)))
@@ -804,6 +820,60 @@ def refseq_struct(ref):
         keep.append(a)
         setattr(t, name, a.ctypes.data if a.size else None)
     return t, keep
+
+
+def txmodel_struct(cols):
+    """A dict of bk_txmodel columns as (abi.TxModel, the arrays that back it).  n_tx is len(cols["tid"]), n_parts len(cols["ex_start"])."""
+    t, keep = abi.TxModel(), []
+    t.n_tx, t.n_parts = len(cols["tid"]), len(cols["ex_start"])
+    for name, dt in abi.TXMODEL_COLS:
+        a = np.ascontiguousarray(cols[name], dt)
+        keep.append(a)
+        setattr(t, name, a.ctypes.data if a.size else None)
+    return t, keep
+
+
+class TxModel:
+    """A transcript model for Context.fusion_frame, built from (tid, tx_start, tx_end, strand, parts, name, gene) rows: strand is
+    "+" / "-" or 0 / 1, parts a list of (start, end) coding parts, 0-based and half-open.  The rows are sorted by (tid, tx_start),
+    stably, as bk_txmodel asks; `names` and `genes` follow the sorted order, so that FRAME_CALL["tx"] indexes them."""
+
+    def __init__(self, rows):
+        rows = sorted(rows, key=lambda r: (r[0], r[1]))
+        self.names = [r[5] if len(r) > 5 else "" for r in rows]
+        self.genes = [r[6] if len(r) > 6 else "" for r in rows]
+        off, starts, ends = [0], [], []
+        for r in rows:
+            starts += [p[0] for p in r[4]]
+            ends += [p[1] for p in r[4]]
+            off.append(len(starts))
+        self.cols = {"tid": np.asarray([r[0] for r in rows], np.int32), "tx_start": np.asarray([r[1] for r in rows], np.uint32),
+                     "tx_end": np.asarray([r[2] for r in rows], np.uint32),
+                     "strand": np.asarray([{"+": 0, "-": 1}.get(r[3], r[3]) for r in rows], np.uint8),
+                     "ex_off": np.asarray(off if rows else [], np.uint32), "ex_start": np.asarray(starts, np.uint32), "ex_end": np.asarray(ends, np.uint32)}
+
+    def __len__(self):
+        return len(self.names)
+
+    @classmethod
+    def from_refgene(cls, lines, contig_names):
+        """The model the command line builds from refGene rows: NR_ rows skipped, the coding parts CDS n exons, transcripts on
+        contigs that `contig_names` lacks dropped.  Returns (model, dropped)."""
+        tid_of = {n: i for i, n in enumerate(contig_names)}
+        rows, dropped = [], 0
+        for line in lines:
+            f = line.rstrip("\n").split("\t")
+            if "NR_" in f[1]:
+                continue
+            if f[2] not in tid_of:
+                dropped += 1
+                continue
+            cs, ce, ne = int(f[6]), int(f[7]), int(f[8])
+            xs = [int(v) for v in f[9].split(",") if v][:ne]
+            xe = [int(v) for v in f[10].split(",") if v][:ne]
+            parts = [(max(s, cs), min(e, ce)) for s, e in zip(xs, xe) if cs != ce and s < ce and e > cs]
+            rows.append((tid_of[f[2]], int(f[4]), int(f[5]), f[3], parts, f[1], f[12]))
+        return cls(rows), dropped
 
 
 def bam_reads(path, keys):

@@ -21,6 +21,7 @@
 #include "jfit.h"
 #include "locsim.h"
 #include "coverage.h"
+#include "frame.h"
 #include "exclude.h"
 #include "ahc.h"
 #include "lanes.h"
@@ -162,6 +163,9 @@ struct bk_ctx
   // window coverage (bk_window_coverage: this context holds the records)
   CovBufs cvb;
   std::vector<struct bk_window_cov> f_wincov;
+  // fusion frame (bk_fusion_frame)
+  FrameBufs frb;
+  std::vector<struct bk_frame_call> f_frame;
 
   // fetch staging
   std::vector<bk_pair> f_pairs[3];
@@ -1435,6 +1439,58 @@ int bk_window_coverage(bk_ctx *records, const struct bk_cov_window *windows, uin
     }
     rows_to_host(records, d_res, n, records->f_wincov);
     *out = records->f_wincov.data();
+  });
+}
+
+// What bk_fusion_frame refuses a model for (include/breakid_hip.h).  The limits are looked at before any array.
+static void check_txmodel(const bk_txmodel &t)
+{
+  const std::string who = "bk_fusion_frame: ";
+  if (t.n_tx > 0x1000000ull) throw bk_error(BK_ERR_LIMIT, who + "more than 2^24 transcripts");
+  if (t.n_parts > 0x10000000ull) throw bk_error(BK_ERR_LIMIT, who + "more than 2^28 coding parts");
+  if (!t.n_tx) return;
+  if (!t.tid || !t.tx_start || !t.tx_end || !t.strand || !t.ex_off || (t.n_parts && (!t.ex_start || !t.ex_end))) throw bk_error(BK_ERR_ARG, who + "the model lacks a column");
+  if (t.ex_off[0] != 0 || t.ex_off[t.n_tx] != t.n_parts) throw bk_error(BK_ERR_ARG, who + "ex_off does not run from 0 to n_parts");
+  for (uint64_t i = 0; i < t.n_tx; ++i)
+  {
+    const std::string at = "transcript " + std::to_string(i);
+    if (t.tid[i] < 0) throw bk_error(BK_ERR_ARG, who + at + " has a negative tid");
+    if (t.strand[i] > 1) throw bk_error(BK_ERR_ARG, who + at + " has a strand above 1 (0 = '+', 1 = '-')");
+    if (t.tx_end[i] < t.tx_start[i]) throw bk_error(BK_ERR_ARG, who + at + " ends in front of its start");
+    if (i + 1 < t.n_tx && (t.tid[i + 1] < t.tid[i] || (t.tid[i + 1] == t.tid[i] && t.tx_start[i + 1] < t.tx_start[i])))
+      throw bk_error(BK_ERR_ARG, who + "transcript " + std::to_string(i + 1) + " is out of order (the rows ascend by tid, then tx_start)");
+    if (t.ex_off[i + 1] < t.ex_off[i] || t.ex_off[i + 1] > t.n_parts) throw bk_error(BK_ERR_ARG, who + "ex_off does not ascend at " + at);
+    for (uint64_t g = t.ex_off[i]; g < t.ex_off[i + 1]; ++g)
+    {
+      if (t.ex_end[g] <= t.ex_start[g]) throw bk_error(BK_ERR_ARG, who + at + " has an empty or descending coding part");
+      if (g > t.ex_off[i] && t.ex_start[g] < t.ex_end[g - 1]) throw bk_error(BK_ERR_ARG, who + at + " has coding parts that descend or overlap");
+      if (t.ex_start[g] < t.tx_start[i] || t.ex_end[g] > t.tx_end[i]) throw bk_error(BK_ERR_ARG, who + at + " has a coding part outside [tx_start, tx_end)");
+    }
+  }
+}
+
+int bk_fusion_frame(bk_ctx *ctx, const bk_txmodel *model, const struct bk_frame_site *sites, uint64_t n, const struct bk_frame_call **out)
+{
+  return guarded(ctx, [&] {
+    if (!model || !out) throw bk_error(BK_ERR_ARG, "bk_fusion_frame: null model or out");
+    if (n && !sites) throw bk_error(BK_ERR_ARG, "bk_fusion_frame: null sites");
+    if (ctx->shard) throw bk_error(BK_ERR_ARG, "bk_fusion_frame: sharded contexts (bk_shard_*) are not supported");
+    if (n > 0x40000000ull) throw bk_error(BK_ERR_LIMIT, "bk_fusion_frame: more than 2^30 sites");
+    const bk_txmodel &t = *model;
+    check_txmodel(t);
+    for (uint64_t k = 0; k < n; ++k)
+      if (sites[k].right1 > 1u || sites[k].right2 > 1u) throw bk_error(BK_ERR_ARG, "bk_fusion_frame: site " + std::to_string(k) + " has a right above 1 (0 = LEFT, 1 = RIGHT)");
+    struct bk_frame_call *d_res;
+    frame_upload(t, sites, n, ctx->frb, ctx->st);  // (outside the scope: it times the work on the device copy)
+    {
+      // touched (include/breakid_hip.h): the model's columns and what is derived from them once, the site and its row
+      const uint64_t bytes = t.n_tx * 21ull + (t.n_tx ? t.n_parts : 0) * 16ull + n * (sizeof(struct bk_frame_site) + sizeof(struct bk_frame_call));
+      Scope s(ctx, "fusion_frame", bytes, bytes);
+      frame_derive(t, ctx->frb, ctx->st);
+      fusion_frame(n, ctx->frb, ctx->st, &d_res);
+    }
+    rows_to_host(ctx, d_res, n, ctx->f_frame);
+    *out = ctx->f_frame.data();
   });
 }
 

@@ -713,7 +713,7 @@ static void fetch_call_tables(const Options &o, const Sample &tumor, const Sampl
   if (o.genotype) fetch_rows(tumor, t.gsup, [&](auto rows, auto n) { return bk_ref_support(ctx, ctx, qual, anchor, w, rows, n); });
   if (o.genotype && normal.ctx) fetch_rows(tumor, t.gsup_normal, [&](auto rows, auto n) { return bk_ref_support(ctx, normal.ctx, qual, anchor, w, rows, n); });
   // -vcf: the junction evidence of every call (member pairs by strands, split tuples by clip side)
-  if (o.vcf || o.clip || o.consensus || o.coverage) fetch_rows(tumor, t.jsup, [&](auto rows, auto n) { return bk_junctions(ctx, rows, n); });
+  if (o.vcf || o.clip || o.consensus || o.coverage || o.frame) fetch_rows(tumor, t.jsup, [&](auto rows, auto n) { return bk_junctions(ctx, rows, n); });
   // -clip: the clipped reads without an SA tag at every cluster, voted or not, on the sample's records and on the normal's
   if (o.clip) fetch_rows(tumor, t.csup, [&](auto rows, auto n) { return bk_clip_support(ctx, ctx, qual, min_clip, w, rows, n); });
   if (o.clip && normal.ctx) fetch_rows(tumor, t.csup_normal, [&](auto rows, auto n) { return bk_clip_support(ctx, normal.ctx, qual, min_clip, w, rows, n); });
@@ -1199,10 +1199,86 @@ static CoverageMap call_coverage(const Options &o, const Sample &tumor, const Sa
   return cov;
 }
 
+// ---- -frame: the 5' / 3' partners and the reading frame of every written call ------------------------------------------------------
+// The model: the transcripts the run read from refGene.txt (NR_ rows are not among them), their coding parts as parse_refgene_line left
+// them, on the contigs of the BAM header by exact name, sorted by (tid, txStart) with the file's order kept among equals.  One site per
+// written call, with the sides -vcf prints; one call of bk_fusion_frame answers them all.
+static FrameMap fusion_frames(const Options &o, const Sample &tumor, const CallTables &t, const vector<OutRow> &rows, const vector<Txpt> &txpts)
+{
+  std::map<string, int32_t> tid_of;
+  for (int i = 0; i < tumor.nt; ++i) tid_of.emplace(tumor.names[i], i);
+  vector<std::pair<int32_t, const Txpt *>> kept;
+  size_t dropped = 0;
+  for (const Txpt &x : txpts)
+  {
+    const auto at = tid_of.find(x.chrom);
+    if (at == tid_of.end())
+      ++dropped;
+    else
+      kept.emplace_back(at->second, &x);
+  }
+  std::stable_sort(kept.begin(), kept.end(), [](const auto &a, const auto &b) { return a.first != b.first ? a.first < b.first : a.second->txStart < b.second->txStart; });
+  std::cout << "frame model: " << kept.size() << " transcripts, " << dropped << " on contigs the input lacks" << std::endl;
+  vector<int32_t> tid;
+  vector<uint32_t> tx_start, tx_end, ex_off{0}, ex_start, ex_end;
+  vector<uint8_t> strand;
+  for (const auto &k : kept)
+  {
+    const Txpt &x = *k.second;
+    tid.push_back(k.first);
+    tx_start.push_back(x.txStart);
+    tx_end.push_back(x.txEnd);
+    strand.push_back(x.strand == "-" ? 1 : 0);
+    ex_start.insert(ex_start.end(), x.codingStarts.begin(), x.codingStarts.end());
+    ex_end.insert(ex_end.end(), x.codingEnds.begin(), x.codingEnds.end());
+    ex_off.push_back((uint32_t) ex_start.size());
+  }
+  bk_txmodel model{};
+  model.n_tx = kept.size();
+  model.n_parts = ex_start.size();
+  model.tid = tid.data(), model.tx_start = tx_start.data(), model.tx_end = tx_end.data(), model.strand = strand.data();
+  model.ex_off = ex_off.data(), model.ex_start = ex_start.data(), model.ex_end = ex_end.data();
+
+  vector<struct bk_frame_site> sites;
+  vector<uint64_t> site_call;
+  for (const OutRow &r : rows)
+  {
+    if (!call_written(r, o.all)) continue;
+    if (r.idx >= t.jsup.size())
+    {
+      std::cerr << "Error: the evidence tables do not cover every call" << std::endl;
+      exit(1);
+    }
+    uint8_t right[2] = {0, 1}, source = 0;
+    bk_junction_sides(&t.jsup[r.idx], &right[0], &right[1], &source);
+    struct bk_frame_site s = {};
+    s.tid1 = r.c.p1_tid, s.pos1 = r.c.p1_exact, s.tid2 = r.c.p2_tid, s.pos2 = (uint32_t) r.c.p2_exact;
+    s.right1 = right[0], s.right2 = right[1];
+    sites.push_back(s);
+    site_call.push_back(r.idx);
+  }
+  const struct bk_frame_call *res = nullptr;
+  const int rc = bk_fusion_frame(tumor.ctx, &model, sites.data(), sites.size(), &res);
+  if (rc != BK_OK) die(tumor, rc);
+  FrameMap frames;
+  for (size_t k = 0; k < sites.size(); ++k)
+  {
+    FrameCall &c = frames[site_call[k]];
+    c.f = res[k];
+    for (int s = 0; s < 2; ++s)
+      if (c.f.tx[s] >= 0 && (size_t) c.f.tx[s] < kept.size())
+      {
+        c.gene[s] = kept[c.f.tx[s]].second->geneName;
+        c.tx[s] = kept[c.f.tx[s]].second->transcriptID;
+      }
+  }
+  return frames;
+}
+
 // ---- the files behind the tables ---------------------------------------------------------------------------------------------------
 // -vcf: <prefix>_fusion.vcf, and with -clip <prefix>_fusion_rescued.vcf
 static void write_vcf_files(const Options &o, const Sample &tumor, const CallTables &t, const vector<OutRow> &rows, const Rescued &rescued, const ConsensusMap &cons,
-                            const HomologyMap &hom, const SimilarMap &sim, const CoverageMap &cov)
+                            const HomologyMap &hom, const SimilarMap &sim, const CoverageMap &cov, const FrameMap &frame)
 {
   VcfInput vi;
   vi.nt = tumor.nt;
@@ -1221,6 +1297,7 @@ static void write_vcf_files(const Options &o, const Sample &tumor, const CallTab
   vi.hom = o.homology ? &hom : nullptr;
   vi.sim = o.similar ? &sim : nullptr;
   vi.cov = o.coverage ? &cov : nullptr;
+  vi.frame = o.frame ? &frame : nullptr;
   auto write = [&](const string &path, const vector<OutRow> &calls) {
     if (write_vcf(path, calls, vi)) return;
     std::cerr << "Error: cannot write " << path << ": the evidence tables do not cover every call" << std::endl;
@@ -1234,6 +1311,7 @@ static void write_vcf_files(const Options &o, const Sample &tumor, const CallTab
   vi.hom = nullptr;                    // ... and with -homology
   vi.sim = nullptr;                    // ... and with -similar
   vi.cov = nullptr;                    // ... and with -coverage
+  vi.frame = nullptr;                  // ... and with -frame
   vi.rescued = &rescued.calls;
   write(o.out_file + "_fusion_rescued.vcf", rescued.rows);
 }
@@ -1284,6 +1362,7 @@ static void write_params(const Options &o, double w)
   if (o.homology) p << "homology_max_ins\t" << o.homins << std::endl;
   if (o.similar) p << "similar_flank\t" << o.simflank << std::endl;
   if (o.coverage) p << "coverage_flank\t" << o.covflank << std::endl;
+  if (o.frame) p << "frame" << std::endl;
 }
 
 // BreakID.cc:175-191.  scan_pairs_count and after_cluster_count are never updated by the reference (always 0);
@@ -1357,10 +1436,12 @@ int main(int argc, char *argv[])
   if (o.similar) similar = locus_similar(o, tumor, rows);
   CoverageMap coverage;
   if (o.coverage) coverage = call_coverage(o, tumor, normal, tables, rows);
+  FrameMap frames;
+  if (o.frame) frames = fusion_frames(o, tumor, tables, rows, txpts);
 
   if (o.clip) write_rescued_tables(o, rescued, tables);
-  write_fusion_tables(o, rows, fusion_twins(o, tables, consensus.sides, homology, similar, coverage));
-  if (o.vcf) write_vcf_files(o, tumor, tables, rows, rescued, consensus.sides, homology, similar, coverage);
+  write_fusion_tables(o, rows, fusion_twins(o, tables, consensus.sides, homology, similar, coverage, frames));
+  if (o.vcf) write_vcf_files(o, tumor, tables, rows, rescued, consensus.sides, homology, similar, coverage, frames);
   if (o.evidence) write_evidence_files(o, tumor, tables, rows, rescued);
   write_params(o, run.w);
   const clock_t end = clock();

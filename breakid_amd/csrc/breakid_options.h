@@ -38,6 +38,8 @@ int bk_locus_similarity(bk_ctx *ctx, const bk_refseq *ref, const struct bk_locus
 // -coverage (the windows of a call and the aligned bases inside them)
 int bk_window_coverage(bk_ctx *records, const struct bk_cov_window *windows, uint64_t n, int mapq_min, const struct bk_window_cov **out) __attribute__((weak));
 int bk_call_windows(const bk_cluster *c, int right1, int right2, uint32_t flank, const uint32_t *target_len, struct bk_cov_window out[5]) __attribute__((weak));
+// -frame
+int bk_fusion_frame(bk_ctx *ctx, const bk_txmodel *model, const struct bk_frame_site *sites, uint64_t n, const struct bk_frame_call **out) __attribute__((weak));
 // -dedup
 int bk_unique_support(bk_ctx *ctx, const struct bk_unique_support **out, uint64_t *count, const uint64_t **first, uint64_t *n_rows) __attribute__((weak));
 // -clip (the soft-clip evidence, the depth at the rescued positions and the rescue rule)
@@ -84,14 +86,15 @@ static const char *HELP =
      \t -similar   \t score the reference around the two breakpoints of every call against each other, forward and reverse-complemented (twin files *_similar.txt; SIMSCORE / SIMLEN / SIMRUN with -vcf)  \n \
      \t -simflank  \t bases either side of a breakpoint that are compared, 1 to 255 (with -similar)  [150]\n \
      \t -coverage  \t mean depth of the aligned bases either side of both breakpoints of every call, between them and over their contigs (twin files *_coverage.txt; COVL / COVR / RDRATIO with -vcf)  \n \
-     \t -covflank  \t bases either side of a breakpoint that are averaged, 1 to 1000000 (with -coverage)  [1000]\n ";
+     \t -covflank  \t bases either side of a breakpoint that are averaged, 1 to 1000000 (with -coverage)  [1000]\n \
+     \t -frame     \t 5' / 3' partner and reading frame of every call over all pairs of transcripts at its breakpoints (twin files *_frame.txt; FRCLASS / FR5P / FR3P with -vcf)  \n ";
 
 struct Options
 {
   std::string inp_file, out_file, nib_dir, normal_file, exclude_file, build = "hg19";
   int qual = 20, device = 0, n_gpus = 0, transport = BK_TRANSPORT_AUTO;  // -gpus N: one sample over N GPUs (include/breakid_multi.h)
   bool fast = false, all = false;                                        // -all: no gene-pair and repeat filter (the _fusion_all files)
-  bool genotype = false, vcf = false, evidence = false, clip = false, dedup = false, consensus = false, homology = false, similar = false, coverage = false;
+  bool genotype = false, vcf = false, evidence = false, clip = false, dedup = false, consensus = false, homology = false, similar = false, coverage = false, frame = false;
   bool anchor_given = false, minclip_given = false, clipsupport_given = false, conslen_given = false, homshift_given = false, homins_given = false, simflank_given = false, covflank_given = false;
   long anchor = 10;                      // -anchor: bases a reference read must cover on either side of the breakpoint base
   long min_clip = 10, clip_support = 3;  // -minclip: shortest clip that counts; -clipsupport: reads at one position a rescued side needs
@@ -137,6 +140,7 @@ static void check_options(const Options &o)
   const Feature homology{"-homology", o.homology, false, bk_junction_fit != nullptr};
   const Feature similar{"-similar", o.similar, false, bk_locus_similarity != nullptr};
   const Feature coverage{"-coverage", o.coverage, false, bk_window_coverage && bk_call_windows && bk_junctions && bk_junction_sides};
+  const Feature frame{"-frame", o.frame, false, bk_fusion_frame && bk_junctions && bk_junction_sides};
   const Feature consensus{"-consensus", o.consensus, false, bk_clip_consensus && bk_clip_reads && bk_evidence && bk_junctions && bk_junction_sides};
   const Feature clip{"-clip", o.clip, false, bk_clip_support && bk_clip_reads && bk_base_depth && bk_clip_rescue && bk_junctions && bk_junction_sides};
   const Feature exclude{"-x", o.exclude(), true, bk_exclude_regions && bk_multi_run_ex && bk_multi_run_bam_ex && bk_multi_excluded};
@@ -169,6 +173,7 @@ static void check_options(const Options &o)
       rule(o.similar && !in_range(o.simflank, 1, 255), "-simflank must be a number from 1 to 255."),
       rule(o.covflank_given && !o.coverage, "-covflank needs -coverage."), gpus(coverage), library(coverage),
       rule(o.coverage && !in_range(o.covflank, 1, 1000000), "-covflank must be a number from 1 to 1000000."),
+      gpus(frame), library(frame),
   };
   for (const Refusal &r : refusals)
   {
@@ -192,7 +197,9 @@ static Options parse_options(int argc, char *argv[])
                                      {"anchor", 1, 0, 14}, {"vcf", 0, 0, 15}, {"evidence", 0, 0, 16}, {"clip", 0, 0, 17},
                                      {"minclip", 1, 0, 18}, {"clipsupport", 1, 0, 19}, {"dedup", 0, 0, 20}, {"consensus", 0, 0, 21},
                                      {"conslen", 1, 0, 22}, {"homology", 0, 0, 23}, {"homshift", 1, 0, 24}, {"homins", 1, 0, 25},
-                                     {"similar", 0, 0, 26}, {"simflank", 1, 0, 27}, {"coverage", 0, 0, 28}, {"covflank", 1, 0, 29}, {0, 0, 0, 0}};
+                                     {"similar", 0, 0, 26}, {"simflank", 1, 0, 27}, {"coverage", 0, 0, 28}, {"covflank", 1, 0, 29}, {"frame", 0, 0, 30},
+                                     {"f", 0, 0, 5},  // (-f used to complete to -fast alone; it still means it beside -frame)
+                                     {0, 0, 0, 0}};
   Options o;
   auto number = [](long &value, bool &given) {
     value = atol(optarg);
@@ -234,6 +241,7 @@ static Options parse_options(int argc, char *argv[])
     case 27: number(o.simflank, o.simflank_given); break;
     case 28: o.coverage = true; break;
     case 29: number(o.covflank, o.covflank_given); break;
+    case 30: o.frame = true; break;
     default: std::cerr << "Error: cannot parse arguments.\n"; exit(1);
     }
   }

@@ -260,6 +260,48 @@ struct CoverageCall
     return s;
   }
 };
+// -frame: the twin files' columns (bk_fusion_frame on the call's two sides, against every transcript of the run's refGene)
+static const char *FRAME_COLUMNS =
+    "\tFr_Class\tFr_Order\tFr_Gene1\tFr_Tx1\tFr_Loc1\tFr_Exon1\tFr_Cod1\tFr_Phase1\tFr_Gene2\tFr_Tx2\tFr_Loc2\tFr_Exon2\tFr_Cod2\tFr_Phase2\tFr_Pairs\tFr_Compatible\tFr_InFrame";
+static const char *FRAME_CLASS_NAMES[6] = {"none", "antisense", "truncating", "promoter", "outframe", "inframe"};  // BK_FRAME_*
+static const char *FRAME_LOC_NAMES[6] = {".", "noncoding", "5UTR", "CDS", "intron", "3UTR"};                       // BK_LOC_*
+
+// One written call: its row, and the gene and the transcript of either side of the reported pair ("" where the side has none)
+struct FrameCall
+{
+  struct bk_frame_call f;
+  string gene[2], tx[2];
+  const char *cls() const { return FRAME_CLASS_NAMES[f.cls <= BK_FRAME_INFRAME ? f.cls : 0]; }
+  bool phased() const { return f.cls == BK_FRAME_INFRAME || f.cls == BK_FRAME_OUTFRAME; }
+  string fields() const
+  {
+    std::ostringstream o;
+    o << "\t" << cls() << "\t" << (f.order == 1 ? "5-3" : f.order == 2 ? "3-5" : ".");
+    for (int s = 0; s < 2; ++s)
+    {
+      if (f.tx[s] < 0)
+      {
+        o << "\t.\t.\t.\t.\t.\t.";
+        continue;
+      }
+      o << "\t" << gene[s] << "\t" << tx[s] << "\t" << FRAME_LOC_NAMES[f.loc[s] <= BK_LOC_3UTR ? f.loc[s] : 0] << "\t" << f.exon[s] << "\t" << f.cod[s] << "\t";
+      if (phased())
+        o << f.cod[s] % 3u;
+      else
+        o << ".";
+    }
+    o << "\t" << (unsigned long long) f.n_tx[0] * f.n_tx[1] << "\t" << f.n_compatible << "\t" << f.n_inframe;
+    return o.str();
+  }
+  // what both breakends of the call end their INFO with
+  string info() const
+  {
+    string s;
+    if (f.cls != BK_FRAME_NONE) s += string(";FRCLASS=") + cls();
+    if (f.order) s += ";FR5P=" + gene[f.order == 1 ? 0 : 1] + ";FR3P=" + gene[f.order == 1 ? 1 : 0];
+    return s;
+  }
+};
 // -clip -normal: what _fusion_rescued_normal.txt adds to a row of _fusion_rescued.txt
 static const char *RESCUED_COLUMNS_NORMAL = "\tNormal_DRP\tNormal_ClipAt1\tNormal_ClipAt2\tNormal_Depth1\tNormal_Depth2";
 
@@ -285,6 +327,7 @@ using ConsensusMap = std::map<uint64_t, std::pair<ConsensusSide, ConsensusSide>>
 using HomologyMap = std::map<uint64_t, std::pair<HomologySide, HomologySide>>;
 using SimilarMap = std::map<uint64_t, SimilarCall>;
 using CoverageMap = std::map<uint64_t, CoverageCall>;
+using FrameMap = std::map<uint64_t, FrameCall>;
 
 // -clip: the rescued clusters in the order of _fusion_rescued.txt, calls[k] to rows[k]; with -evidence the clipped reads at the peaks
 // of the written ones (bk_clip_reads: the rows of sites 2 * j and 2 * j + 1 belong to the j-th written row)
@@ -326,7 +369,7 @@ struct Twin
 
 // The twins of this run, the reference's own two files first.  An option that adds columns to the calls adds its entry here.
 static vector<Twin> fusion_twins(const Options &o, const CallTables &t, const ConsensusMap &cons, const HomologyMap &hom, const SimilarMap &sim,
-                                 const CoverageMap &cov)
+                                 const CoverageMap &cov, const FrameMap &frame)
 {
   const bool with_normal = o.with_normal();  // (a tumour without calls still gets header-only twins)
   vector<Twin> twins;
@@ -385,6 +428,12 @@ static vector<Twin> fusion_twins(const Options &o, const CallTables &t, const Co
                        if (!cov.count(r.idx)) return false;
                        const CoverageCall &c = cov.at(r.idx);
                        tail = c.fields(c.tumor) + (with_normal ? c.fields(c.normal) : "");
+                       return true;
+                     }});
+  if (o.frame)
+    twins.push_back({"_frame", FRAME_COLUMNS, [&frame](const OutRow &r, string &tail) {
+                       if (!frame.count(r.idx)) return false;
+                       tail = frame.at(r.idx).fields();
                        return true;
                      }});
   return twins;
@@ -457,6 +506,8 @@ struct VcfInput
   const SimilarMap *sim = nullptr;
   // -coverage (else null; never for the rescued clusters): COVL / COVR of the breakend's own side and RDRATIO, behind everything else
   const CoverageMap *cov = nullptr;
+  // -frame (else null; never for the rescued clusters): FRCLASS / FR5P / FR3P on both breakends of a call, behind everything else
+  const FrameMap *frame = nullptr;
 };
 
 static char nib_base(const string &nib_dir, const string &chr, long pos1)  // the base at a 1-based position; N without a file or beyond it
@@ -569,6 +620,7 @@ static bool write_vcf(const string &path, const vector<OutRow> &rows, const VcfI
           o << ";COVL=" << cc.mean_text(cc.tumor, 2 * s) << ";COVR=" << cc.mean_text(cc.tumor, 2 * s + 1);
           if (cc.ratio_text(cc.tumor) != ".") o << ";RDRATIO=" << cc.ratio_text(cc.tumor);
         }
+        if (in.frame && in.frame->count(r.idx)) o << in.frame->at(r.idx).info();
         o << "\t" << (in.gsup ? "GT:GQ:DR:DV:RR:RV" : "DV:RV") << "\t" << vcf_sample(r.c.n_drp, r.c.n_sr, in.gsup ? &(*in.gsup)[r.idx] : nullptr, s);
         if (in.with_normal) o << "\t" << vcf_sample(in.nsup[r.idx].n_drp, in.nsup[r.idx].n_sr, in.gsup_normal ? &(*in.gsup_normal)[r.idx] : nullptr, s);
       }
@@ -620,6 +672,10 @@ static bool write_vcf(const string &path, const vector<OutRow> &rows, const VcfI
     v << "##INFO=<ID=COVL,Number=1,Type=Float,Description=\"Mean depth of the aligned bases in the window left of this breakpoint's cut\">\n"
          "##INFO=<ID=COVR,Number=1,Type=Float,Description=\"Mean depth of the aligned bases in the window right of this breakpoint's cut\">\n"
          "##INFO=<ID=RDRATIO,Number=1,Type=Float,Description=\"Mean depth between the two breakpoints over the mean depth of the two outer flanks\">\n";
+  if (in.frame && !in.rescued)
+    v << "##INFO=<ID=FRCLASS,Number=1,Type=String,Description=\"Best class over all pairs of transcripts at the two breakpoints: antisense, truncating, promoter, outframe or inframe\">\n"
+         "##INFO=<ID=FR5P,Number=1,Type=String,Description=\"Gene of the 5' partner of the reported pair of transcripts\">\n"
+         "##INFO=<ID=FR3P,Number=1,Type=String,Description=\"Gene of the 3' partner of the reported pair of transcripts\">\n";
   if (in.rescued) v << "##INFO=<ID=SC,Number=1,Type=Integer,Description=\"Soft-clipped reads without an SA tag that end at this position (the clip peak)\">\n";
   if (in.gsup)
     v << "##FORMAT=<ID=GT,Number=1,Type=String,Description=\"Genotype\">\n"

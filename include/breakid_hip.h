@@ -615,6 +615,92 @@ int bk_window_coverage(bk_ctx *records, const struct bk_cov_window *windows, uin
  * list of bk_init (it must cover both tids).  Returns BK_OK, or BK_ERR_ARG for a null argument or flank == 0. */
 int bk_call_windows(const bk_cluster *c, int right1, int right2, uint32_t flank, const uint32_t *target_len, struct bk_cov_window out[5]);
 
+/* ---- fusion frame: the 5' and 3' partner and the reading frame of every call ------------------------------------------------------
+ * Whether two breakpoints, each with the side on which sequence is retained, can give a fusion transcript at all, which transcript
+ * is its 5' partner and whether the reading frame is kept.  A frame call is a property of a pair of isoforms, so every transcript
+ * that overlaps side 1 is paired with every transcript that overlaps side 2.  All arithmetic is integer.
+ * Model: bk_txmodel, host memory, uploaded per call as bk_refseq is.  Transcript i lies on contig tid[i] >= 0, covers
+ * [tx_start[i], tx_end[i]) and runs on strand[i] (0 = '+', 1 = '-'); its coding parts (CDS n exons) are the entries
+ * ex_off[i] .. ex_off[i + 1] - 1 of ex_start / ex_end.  Every coordinate is 0-based and half-open.  The parts of one transcript
+ * ascend, none is empty (ex_start < ex_end), none overlaps the one before it (they may abut) and all lie inside
+ * [tx_start, tx_end).  L(i), the coding length, is the sum of the parts' lengths; L = 0 (no part) is a non-coding transcript.
+ * cds_start / cds_end are the first start and the last end of the parts.  The rows ascend by (tid, tx_start); ex_off ascends from
+ * ex_off[0] = 0 to ex_off[n_tx] = n_parts.
+ * Site k: side 1 (tid1, pos1, right1) and side 2 (tid2, pos2, right2), pos 1-based as p1_exact is, right 0 = LEFT and 1 = RIGHT as
+ * everywhere else (bk_junction_sides).  Transcript T overlaps the side (tid, P) when T.tid == tid && T.tx_start < P && P <= T.tx_end;
+ * a side with tid < 0 overlaps nothing.
+ * Per transcript and side, with b = P - 1 the 0-based breakpoint base:
+ *   retained  the bases b' <= b of a LEFT side, b' >= b of a RIGHT side (the breakpoint base is retained, as p_exact means)
+ *   role      BK_FRAME_HEAD when (strand == '+') == (the side is LEFT): the retained part holds the transcript's 5' end and
+ *             transcription runs towards the junction; BK_FRAME_TAIL otherwise
+ *   r         the coding bases that are retained
+ *   cod       r for a head (the coding bases it contributes), L - r for a tail (the coding bases lost in front of the junction)
+ *   exon      counted over the coding parts in transcription order from 1 (part g of m in genomic order is g + 1 on '+' and m - g
+ *             on '-'): for a head the last part that has a retained base, for a tail the first one; 0 when no part has one
+ *   loc       of the base b: BK_LOC_NONCODING when L == 0; BK_LOC_CDS inside a part; BK_LOC_INTRON inside [cds_start, cds_end) but
+ *             in no part; BK_LOC_5UTR / BK_LOC_3UTR in front of / behind the CDS in transcription order (b < cds_start is 5' on
+ *             '+' and 3' on '-'; b >= cds_end the other way round).  An intron between two UTR exons counts as UTR.
+ * Per pair (A overlaps side 1, B overlaps side 2; A and B may be the same transcript), the class is
+ *   BK_FRAME_ANTISENSE (1)  the roles are equal: both promoters retained, or both lost
+ *   otherwise, with H the head, T the tail, h = cod(H), t = cod(T):
+ *   BK_FRAME_INFRAME (5)    0 < h < L(H), 0 < t < L(T) and h % 3 == t % 3
+ *   BK_FRAME_OUTFRAME (4)   the same bounds, different remainders
+ *   BK_FRAME_PROMOTER (3)   h == 0 && t == 0 && L(H) > 0 && L(T) > 0: a 5' UTR in front of the tail's whole CDS
+ *   BK_FRAME_TRUNCATING (2) everything else (the head's stop codon retained, the tail's start lost behind a non-coding head, a
+ *                           breakpoint in the tail's 3' UTR, a non-coding partner)
+ * An intragenic deletion on a '+' gene (A == B) is in frame exactly when the coding bases it removes are a multiple of 3; that
+ * needs no special case.
+ * Per call: n_tx[s] = the transcripts that overlap side s + 1, and n_pairs = n_tx[0] * n_tx[1] (not stored).  n_inframe counts the
+ * pairs of class 5, n_compatible those of classes 2..5, both over all pairs (they stop at 2^32 - 1).  The reported pair is the one
+ * with the largest class; ties go to the larger L(A) + L(B), then the smaller model index of A, then of B.  cls is its class,
+ * tx[] the model indices of A and B, and role / loc / exon / cod describe A on side 1 and B on side 2.  order is 1 when side 1 is
+ * the head, 2 when side 2 is, 0 for BK_FRAME_ANTISENSE and BK_FRAME_NONE.  With n_tx[0] == 0 or n_tx[1] == 0 the class is
+ * BK_FRAME_NONE (0); a side that has transcripts still reports the one with the largest L (the smallest index on a tie) with its
+ * role / loc / exon / cod.  A side without a transcript has tx = -1 and role = loc = exon = cod = 0.  Every output is a count or
+ * an argmax with a fixed tie rule: two runs, and any permutation of the sites, give the same bytes row for row.
+ * Hand example (the G1 fixture): GENEA '+' with the parts [40500, 41000) [50000, 51000) [58000, 59500), side 1 = 50099 LEFT: a head,
+ * r = cod = 500 + 99 = 599, CDS, exon 2.  GENEB '-' with the parts [70500, 71000) [80100, 89500), L = 9900, side 2 = 80200 RIGHT:
+ * also a head, cod = 89500 - 80199 = 9301; the class is antisense.  GENEB on '+' instead is a tail with cod = 9900 - 9301 = 599,
+ * CDS, exon 2, and the call is in frame (599 % 3 == 599 % 3), order 1. */
+#define BK_FRAME_NONE 0
+#define BK_FRAME_ANTISENSE 1
+#define BK_FRAME_TRUNCATING 2
+#define BK_FRAME_PROMOTER 3
+#define BK_FRAME_OUTFRAME 4
+#define BK_FRAME_INFRAME 5
+#define BK_FRAME_HEAD 1 /* role; 0 = the side has no transcript */
+#define BK_FRAME_TAIL 2
+#define BK_LOC_NONCODING 1 /* loc; 0 = the side has no transcript */
+#define BK_LOC_5UTR 2
+#define BK_LOC_CDS 3
+#define BK_LOC_INTRON 4
+#define BK_LOC_3UTR 5
+typedef struct bk_txmodel {
+  uint64_t n_tx, n_parts;
+  const int32_t *tid;
+  const uint32_t *tx_start, *tx_end;
+  const uint8_t *strand;        /* 0 = '+', 1 = '-' */
+  const uint32_t *ex_off;       /* n_tx + 1 */
+  const uint32_t *ex_start, *ex_end; /* n_parts each */
+} bk_txmodel;
+struct bk_frame_site { int32_t tid1; uint32_t pos1; int32_t tid2; uint32_t pos2; uint8_t right1, right2; uint8_t reserved[6]; };   /* 24 bytes */
+struct bk_frame_call { uint8_t cls, order, loc[2], role[2]; uint16_t exon[2]; uint16_t reserved; int32_t tx[2]; uint32_t cod[2], n_tx[2], n_inframe, n_compatible; uint32_t reserved2; };   /* 48 bytes; reserved = 0 */
+/* ctx: any live context that is not a shard (bk_shard_*); no stage needs to have run, and nothing a later bk_fetch or stage returns
+ * changes.  model and sites: host memory.  *out (n rows) is library-owned until the next call or bk_free(ctx).  BK_ERR_ARG (with
+ * the reason in bk_last_error) for a null model or out, null sites with n > 0, a shard, a right above 1, a model that lacks a
+ * column, rows that do not ascend by (tid, tx_start), a negative tid, tx_end < tx_start, a strand above 1, an ex_off that does not
+ * ascend from 0 to n_parts, and coding parts that are empty, descend, overlap or reach outside [tx_start, tx_end).  BK_ERR_LIMIT
+ * beyond 2^24 transcripts or 2^28 parts (looked at before any array is read) and beyond 2^30 sites.  n == 0 is no error, and
+ * neither is n_tx == 0 (every row is then BK_FRAME_NONE with tx = -1).  exon stops at 65535.
+ * How: on upload the device derives the exclusive prefix of the coding lengths over all parts and, per contig, the running maximum
+ * of tx_end.  One wavefront per site: per side a binary search for U = #{tx_start < P} on the contig, then a walk backwards from
+ * U - 1, 64 transcripts a step, until the running maximum falls below P; r / exon / loc of an overlapping transcript by a binary
+ * search over its parts; the pairs dealt to the lanes and one key reduced by shuffles.
+ * bk_timing: scope `fusion_frame` (the work on the device copy: the derived arrays and the site kernel).  bk_timing_touched: 21
+ * bytes per transcript (tid and tx_start as one key, tx_end, its running maximum, strand, ex_off) and 16 per part (start, end, the
+ * prefix), each once, and 72 per site (its row and its result); the transcripts a site's walk visits are not modelled. */
+int bk_fusion_frame(bk_ctx *ctx, const bk_txmodel *model, const struct bk_frame_site *sites, uint64_t n, const struct bk_frame_call **out);
+
 /* Copy a stage's result to library-owned host memory.  *data stays valid until the next bk_fetch
  * of the same stage or bk_free.  group_off (may be NULL) receives n_groups+1 offsets for pair stages. */
 int bk_fetch(bk_ctx *ctx, int stage, const void **data, uint64_t *count, const uint64_t **group_off, uint32_t *n_groups);
