@@ -36,7 +36,7 @@ def build(verbose=False):
 EXPORTS = ["bk_init", "bk_prepare_process", "bk_free", "bk_last_error", "bk_set_stream", "bk_sync", "bk_get_stream", "bk_upload_records", "bk_records", "bk_exclude_regions", "bk_isize_stats",
            "bk_discordant_pairs", "bk_mask_and_cluster", "bk_split_evidence", "bk_cluster_summary",
            "bk_split_breakpoints", "bk_normal_support", "bk_ref_support", "bk_genotype_call", "bk_clip_support", "bk_clip_reads", "bk_base_depth", "bk_clip_rescue", "bk_junctions", "bk_junction_sides", "bk_vcf_breakend_alt", "bk_evidence", "bk_unique_support", "bk_clip_consensus", "bk_junction_fit", "bk_locus_similarity", "bk_window_coverage", "bk_call_windows", "bk_fusion_frame", "bk_run", "bk_fetch", "bk_timing", "bk_timing_enable", "bk_timing_touched", "bk_group_stats", "bk_qname_hash", "bk_qname_check",
-           "bk_bam_open", "bk_bam_header", "bk_bam_decode", "bk_bam_close", "bk_bam_extract", "bk_bam_names_free", "bk_bam_reads", "bk_reads_free", "bk_bam_decode_device", "bk_bam_decode_device_part", "bk_bam_decode_device_ctx", "bk_bam_dev_free", "bk_feed_release_caches", "bk_debug_bgzf_inflate", "bk_debug_std_sort", "bk_sort_forms", "bk_debug_ahc", "bk_debug_points", "bk_debug_cigar", "bk_debug_vote", "bk_debug_region", "bk_shard_begin", "bk_shard_get_stats", "bk_shard_set_stats",
+           "bk_bam_open", "bk_bam_header", "bk_bam_decode", "bk_bam_close", "bk_bam_extract", "bk_bam_names_free", "bk_bam_reads", "bk_reads_free", "bk_bam_decode_device", "bk_bam_decode_device_part", "bk_bam_decode_device_ctx", "bk_bam_dev_free", "bk_feed_release_caches", "bk_debug_bgzf_inflate", "bk_debug_std_sort", "bk_debug_scan", "bk_debug_radix_sort", "bk_debug_prims_info", "bk_sort_forms", "bk_debug_ahc", "bk_debug_points", "bk_debug_cigar", "bk_debug_vote", "bk_debug_region", "bk_shard_begin", "bk_shard_get_stats", "bk_shard_set_stats",
            "bk_shard_sd_local", "bk_shard_sd_finish", "bk_shard_buffer", "bk_shard_set_buffer", "bk_shard_group_sizes",
            "bk_shard_own_groups", "bk_shard_route_candidates", "bk_shard_group_keys", "bk_shard_route_pairs", "bk_shard_group_pairs", "bk_shard_bp_cov", "bk_shard_bp_vote", "bk_shard_bp_vote_slice", "bk_shard_bp_set_voted", "bk_shard_bp_depth", "bk_shard_bp_finish"]
 
@@ -95,6 +95,9 @@ def lib():
         L.bk_timing_enable.argtypes = [vp, C.c_int]
         L.bk_timing_touched.argtypes = [vp, C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(C.c_int)]
         L.bk_debug_std_sort.argtypes = [vp, vp, vp, C.c_uint32, vp]
+        L.bk_debug_scan.argtypes = [vp, C.c_int, vp, C.c_uint64, C.c_int, vp]
+        L.bk_debug_radix_sort.argtypes = [vp, vp, vp, C.c_uint64, C.c_int, C.c_int, vp, vp]
+        L.bk_debug_prims_info.argtypes = [u64p]
         L.bk_sort_forms.argtypes = [vp, u64p]
         L.bk_debug_ahc.argtypes = [vp, vp, vp, C.c_uint32, C.c_double, vp, vp, C.POINTER(C.c_uint32)]
         L.bk_debug_points.argtypes = [vp, C.c_int, vp, vp, C.c_uint32, C.c_double, vp, vp, C.POINTER(C.c_uint32)]
@@ -202,6 +205,15 @@ def multi_run(contigs, cols, n_gpus, transport=TRANSPORT_LOCAL, qual=20, fast=Tr
         return {"w": w.value, "n_clustered": ncl.value, "mean": mean.value, "sd": sd.value, "clusters": clusters}
     finally:
         M.bk_multi_free(h)
+
+
+def prims_info():
+    """The tile constants of the built primitives (bk_debug_prims_info; no GPU): BLOCK, SCAN_TILE, SCAN_ONE_MAX, RS_TILE."""
+    out = (C.c_uint64 * 4)()
+    rc = lib().bk_debug_prims_info(out)
+    if rc != 0:
+        raise BreakIDError(rc, "bk_debug_prims_info")
+    return dict(zip(("BLOCK", "SCAN_TILE", "SCAN_ONE_MAX", "RS_TILE"), (int(v) for v in out)))
 
 
 def w_from(mean, sd):
@@ -619,6 +631,25 @@ class Context:
         perm = np.zeros(len(key), np.uint32)
         self._check(self.L.bk_debug_std_sort(self.h, key.ctypes.data, group_off.ctypes.data, len(group_off) - 1, perm.ctypes.data))
         return perm
+
+    def debug_scan(self, values, in_place=False):
+        """prims::exclusive_scan of a uint32 or uint64 array (bk_debug_scan): n + 1 entries of the same type, the total last."""
+        values = np.ascontiguousarray(values)
+        assert values.ndim == 1 and values.dtype in (np.uint32, np.uint64), values.dtype
+        out = np.zeros(len(values) + 1, values.dtype)
+        self._check(self.L.bk_debug_scan(self.h, values.dtype.itemsize, values.ctypes.data if len(values) else None, len(values), int(in_place), out.ctypes.data))
+        return out
+
+    def debug_radix_sort(self, keys, vals, begin_bit, end_bit):
+        """prims::radix_sort_pairs (bk_debug_radix_sort): (keys, vals) in the stable order of bits [begin_bit, end_bit) of the keys."""
+        keys = np.ascontiguousarray(keys, np.uint64)
+        vals = np.ascontiguousarray(vals, np.uint32)
+        assert keys.ndim == 1 and keys.shape == vals.shape
+        n = len(keys)
+        ko, vo = np.zeros(n, np.uint64), np.zeros(n, np.uint32)
+        self._check(self.L.bk_debug_radix_sort(self.h, keys.ctypes.data if n else None, vals.ctypes.data if n else None, n, int(begin_bit), int(end_bit),
+                                               ko.ctypes.data if n else None, vo.ctypes.data if n else None))
+        return ko, vo
 
     def sort_forms(self):
         """How this context's std::sort replays ran so far: (service jobs, task dispatches, chains of launches)."""

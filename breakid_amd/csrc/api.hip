@@ -167,6 +167,10 @@ struct bk_ctx
   FrameBufs frb;
   std::vector<struct bk_frame_call> f_frame;
 
+  // test hooks of the primitives (bk_debug_scan, bk_debug_radix_sort): buffers that live as long as the context, as a stage's do
+  prims::RadixBufs dbg_radix;
+  DevBuf dbg_in, dbg_out, dbg_vals;
+
   // fetch staging
   std::vector<bk_pair> f_pairs[3];
   std::vector<uint64_t> f_off[3];
@@ -1954,6 +1958,63 @@ int bk_debug_std_sort(bk_ctx *ctx, const uint32_t *key, const uint64_t *group_of
     HIP_CHECK(hipMemcpyAsync(perm_out, dp.get<uint32_t>(), n * 4, hipMemcpyDeviceToHost, ctx->st));
     HIP_CHECK(hipStreamSynchronize(ctx->st));
   });
+}
+
+int bk_debug_scan(bk_ctx *ctx, int elem_bytes, const void *in, uint64_t n, int in_place, void *out)
+{
+  return guarded(ctx, [&] {
+    if (elem_bytes != 4 && elem_bytes != 8) throw bk_error(BK_ERR_ARG, "bk_debug_scan: elem_bytes must be 4 or 8");
+    if (!out || (n && !in)) throw bk_error(BK_ERR_ARG, "bk_debug_scan: null argument");
+    auto run = [&](auto zero) {
+      using T = decltype(zero);
+      T *d_in = ctx->dbg_in.as<T>(n + 1);
+      T *d_out = in_place ? d_in : ctx->dbg_out.as<T>(n + 1);
+      // the output holds a pattern first: an entry the scan does not write shows as that, not as what an earlier call left
+      HIP_CHECK(hipMemsetAsync(d_out, 0xA5, (n + 1) * sizeof(T), ctx->st));
+      if (n) HIP_CHECK(hipMemcpyAsync(d_in, in, n * sizeof(T), hipMemcpyHostToDevice, ctx->st));
+      prims::exclusive_scan<T>(d_in, d_out, n, ctx->dbg_radix.scan_tmp, ctx->st);
+      HIP_CHECK(hipMemcpyAsync(out, d_out, (n + 1) * sizeof(T), hipMemcpyDeviceToHost, ctx->st));
+      HIP_CHECK(hipStreamSynchronize(ctx->st));
+    };
+    if (elem_bytes == 4)
+      run(uint32_t(0));
+    else
+      run(uint64_t(0));
+  });
+}
+
+int bk_debug_radix_sort(bk_ctx *ctx, const uint64_t *keys, const uint32_t *vals, uint64_t n, int begin_bit, int end_bit, uint64_t *keys_out, uint32_t *vals_out)
+{
+  return guarded(ctx, [&] {
+    if (n && (!keys || !vals || !keys_out || !vals_out)) throw bk_error(BK_ERR_ARG, "bk_debug_radix_sort: null argument");
+    if (begin_bit < 0 || end_bit > 64) throw bk_error(BK_ERR_ARG, "bk_debug_radix_sort: bits outside [0, 64]");
+    prims::radix_check_count(n);
+    if (!n) return;
+    prims::RadixBufs &rb = ctx->dbg_radix;
+    uint64_t *dk = ctx->dbg_in.as<uint64_t>(n);
+    uint32_t *dv = ctx->dbg_vals.as<uint32_t>(n);
+    // (the alternate buffers hold a pattern, not an earlier call's result, wherever this call does not write them)
+    HIP_CHECK(hipMemsetAsync(rb.keys_alt.as<uint64_t>(n), 0xA5, n * 8, ctx->st));
+    HIP_CHECK(hipMemsetAsync(rb.vals_alt.as<uint32_t>(n), 0xA5, n * 4, ctx->st));
+    HIP_CHECK(hipMemcpyAsync(dk, keys, n * 8, hipMemcpyHostToDevice, ctx->st));
+    HIP_CHECK(hipMemcpyAsync(dv, vals, n * 4, hipMemcpyHostToDevice, ctx->st));
+    uint64_t *ko = nullptr;
+    uint32_t *vo = nullptr;
+    prims::radix_sort_pairs(dk, dv, n, begin_bit, end_bit, rb, ctx->st, &ko, &vo);
+    HIP_CHECK(hipMemcpyAsync(keys_out, ko, n * 8, hipMemcpyDeviceToHost, ctx->st));
+    HIP_CHECK(hipMemcpyAsync(vals_out, vo, n * 4, hipMemcpyDeviceToHost, ctx->st));
+    HIP_CHECK(hipStreamSynchronize(ctx->st));
+  });
+}
+
+int bk_debug_prims_info(uint64_t out[4])
+{
+  if (!out) return BK_ERR_ARG;
+  out[0] = prims::BLOCK;
+  out[1] = prims::SCAN_TILE;
+  out[2] = prims::SCAN_ONE_MAX;
+  out[3] = prims::RS_TILE;
+  return BK_OK;
 }
 
 int bk_sort_forms(bk_ctx *ctx, uint64_t out[3])

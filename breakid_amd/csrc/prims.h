@@ -46,11 +46,9 @@ template <class T> __device__ __forceinline__ T block_exclusive_scan(T v, T *lds
 constexpr int SCAN_ITEMS = 8;
 constexpr int SCAN_TILE = BLOCK * SCAN_ITEMS;
 
-// (n_dev != nullptr: the element count is read from device memory, n is only the bound the grid was sized for)
-template <class T> __global__ __launch_bounds__(BLOCK) void k_scan_reduce(const T *__restrict__ in, T *__restrict__ sums, uint64_t n, const uint32_t *__restrict__ n_dev = nullptr)
+template <class T> __global__ __launch_bounds__(BLOCK) void k_scan_reduce(const T *__restrict__ in, T *__restrict__ sums, uint64_t n)
 {
   __shared__ T lds[WAVES];
-  if (n_dev) n = *n_dev;
   uint64_t base = (uint64_t) blockIdx.x * SCAN_TILE;
   T acc = 0;
 #pragma unroll
@@ -65,10 +63,9 @@ template <class T> __global__ __launch_bounds__(BLOCK) void k_scan_reduce(const 
 }
 
 // single block: exclusive scan of sums[0..nb) in place, total -> *total_out
-template <class T> __global__ __launch_bounds__(BLOCK) void k_scan_sums(T *sums, uint32_t nb, T *total_out, const uint32_t *__restrict__ n_dev = nullptr)
+template <class T> __global__ __launch_bounds__(BLOCK) void k_scan_sums(T *sums, uint32_t nb, T *total_out)
 {
   __shared__ T lds[WAVES];
-  if (n_dev) total_out += *n_dev;  // total_out = the output array then
   T carry = 0;
   for (uint32_t base = 0; base < nb; base += BLOCK)
   {
@@ -82,10 +79,9 @@ template <class T> __global__ __launch_bounds__(BLOCK) void k_scan_sums(T *sums,
   if (threadIdx.x == 0) *total_out = carry;
 }
 
-template <class T> __global__ __launch_bounds__(BLOCK) void k_scan_apply(const T *__restrict__ in, T *__restrict__ out, const T *__restrict__ sums, uint64_t n, const uint32_t *__restrict__ n_dev = nullptr)
+template <class T> __global__ __launch_bounds__(BLOCK) void k_scan_apply(const T *__restrict__ in, T *__restrict__ out, const T *__restrict__ sums, uint64_t n)
 {
   __shared__ T lds[WAVES];
-  if (n_dev) n = *n_dev;
   uint64_t base = (uint64_t) blockIdx.x * SCAN_TILE;
   T carry = sums[blockIdx.x];
 #pragma unroll
@@ -103,10 +99,9 @@ template <class T> __global__ __launch_bounds__(BLOCK) void k_scan_apply(const T
 // the whole scan by ONE workgroup (tiles one after the other, the carry in a register): a short array is bound by the three
 // dependent launches of the general form, not by its elements - and every dispatch of a process shares one command processor
 constexpr uint64_t SCAN_ONE_MAX = 16 * SCAN_TILE;
-template <class T> __global__ __launch_bounds__(BLOCK) void k_scan_one(const T *in, T *out, uint64_t n, const uint32_t *__restrict__ n_dev = nullptr)
+template <class T> __global__ __launch_bounds__(BLOCK) void k_scan_one(const T *in, T *out, uint64_t n)
 {
   __shared__ T lds[WAVES];
-  if (n_dev) n = *n_dev;
   T carry = 0;
   for (uint64_t base = 0; base < n; base += BLOCK)
   {
@@ -130,36 +125,21 @@ template <class T> inline void exclusive_scan(const T *in, T *out, uint64_t n, D
   }
   if (n <= SCAN_ONE_MAX)
   {
-    hipLaunchKernelGGL(k_scan_one<T>, dim3(1), dim3(BLOCK), 0, st, in, out, n, (const uint32_t *) nullptr);
+    hipLaunchKernelGGL(k_scan_one<T>, dim3(1), dim3(BLOCK), 0, st, in, out, n);
     return;
   }
   uint32_t nb = cdiv(n, SCAN_TILE);
   T *sums = tmp.as<T>(nb + 1);
-  hipLaunchKernelGGL(k_scan_reduce<T>, dim3(nb), dim3(BLOCK), 0, st, in, sums, n, (const uint32_t *) nullptr);
-  hipLaunchKernelGGL(k_scan_sums<T>, dim3(1), dim3(BLOCK), 0, st, sums, nb, out + n, (const uint32_t *) nullptr);
-  hipLaunchKernelGGL(k_scan_apply<T>, dim3(nb), dim3(BLOCK), 0, st, in, out, sums, n, (const uint32_t *) nullptr);
-}
-
-// the same with the element count in device memory (*n_dev <= n_bound); out[*n_dev] = total
-template <class T> inline void exclusive_scan_devn(const T *in, T *out, uint64_t n_bound, const uint32_t *n_dev, DevBuf &tmp, hipStream_t st)
-{
-  if (n_bound <= SCAN_ONE_MAX)
-  {
-    hipLaunchKernelGGL(k_scan_one<T>, dim3(1), dim3(BLOCK), 0, st, in, out, n_bound, n_dev);
-    return;
-  }
-  uint32_t nb = cdiv(n_bound ? n_bound : 1, SCAN_TILE);
-  T *sums = tmp.as<T>(nb + 1);
-  hipLaunchKernelGGL(k_scan_reduce<T>, dim3(nb), dim3(BLOCK), 0, st, in, sums, n_bound, n_dev);
-  hipLaunchKernelGGL(k_scan_sums<T>, dim3(1), dim3(BLOCK), 0, st, sums, nb, out, n_dev);
-  hipLaunchKernelGGL(k_scan_apply<T>, dim3(nb), dim3(BLOCK), 0, st, in, out, sums, n_bound, n_dev);
+  hipLaunchKernelGGL(k_scan_reduce<T>, dim3(nb), dim3(BLOCK), 0, st, in, sums, n);
+  hipLaunchKernelGGL(k_scan_sums<T>, dim3(1), dim3(BLOCK), 0, st, sums, nb, out + n);
+  hipLaunchKernelGGL(k_scan_apply<T>, dim3(nb), dim3(BLOCK), 0, st, in, out, sums, n);
 }
 
 // ---- stable LSD radix sort, u64 keys + u32 values, 8-bit digits -----------------------------------
 constexpr int RS_ROWS = 8;                           // rows of 64 keys per wave
 constexpr int RS_TILE = BLOCK * RS_ROWS;             // 2048 keys per block
 
-static __global__ __launch_bounds__(BLOCK) void k_radix_hist(const uint64_t *__restrict__ keys, uint32_t *__restrict__ ghist, uint64_t n, int shift, uint32_t nb)
+static __global__ __launch_bounds__(BLOCK) void k_radix_hist(const uint64_t *__restrict__ keys, uint32_t *__restrict__ ghist, uint64_t n, int shift, uint32_t mask, uint32_t nb)
 {
   __shared__ uint32_t hist[256];
   hist[threadIdx.x] = 0;
@@ -169,14 +149,14 @@ static __global__ __launch_bounds__(BLOCK) void k_radix_hist(const uint64_t *__r
   for (int k = 0; k < RS_ROWS; ++k)
   {
     uint64_t i = base + (uint64_t) k * BLOCK + threadIdx.x;
-    if (i < n) atomicAdd(&hist[(keys[i] >> shift) & 255], 1u);
+    if (i < n) atomicAdd(&hist[(uint32_t) (keys[i] >> shift) & mask], 1u);
   }
   __syncthreads();
   ghist[(uint64_t) threadIdx.x * nb + blockIdx.x] = hist[threadIdx.x];
 }
 
 static __global__ __launch_bounds__(BLOCK) void k_radix_scatter(const uint64_t *__restrict__ kin, const uint32_t *__restrict__ vin, uint64_t *__restrict__ kout,
-                                                         uint32_t *__restrict__ vout, const uint32_t *__restrict__ goff, uint64_t n, int shift, uint32_t nb)
+                                                         uint32_t *__restrict__ vout, const uint32_t *__restrict__ goff, uint64_t n, int shift, uint32_t mask, uint32_t nb)
 {
   __shared__ uint32_t whist[WAVES][256];
   const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -194,7 +174,7 @@ static __global__ __launch_bounds__(BLOCK) void k_radix_scatter(const uint64_t *
     bool valid = i < n;
     key[r] = valid ? kin[i] : 0ull;
     val[r] = valid ? vin[i] : 0u;
-    uint32_t d = (uint32_t) (key[r] >> shift) & 255u;
+    uint32_t d = (uint32_t) (key[r] >> shift) & mask;
     uint64_t peers = __ballot(valid);
 #pragma unroll
     for (int b = 0; b < 8; ++b)
@@ -230,7 +210,7 @@ static __global__ __launch_bounds__(BLOCK) void k_radix_scatter(const uint64_t *
     uint64_t i = tile + (uint64_t) r * 64 + lane;
     if (i < n)
     {
-      uint32_t d = (uint32_t) (key[r] >> shift) & 255u;
+      uint32_t d = (uint32_t) (key[r] >> shift) & mask;
       uint32_t p = whist[w][d] + rank[r];
       kout[p] = key[r];
       vout[p] = val[r];
@@ -243,24 +223,33 @@ struct RadixBufs
   DevBuf keys_alt, vals_alt, hist, scan_tmp;
 };
 
-// Sorts (keys, vals) by bits [begin_bit, end_bit) of the key, stable.  On return the sorted data is in
-// (*keys_out, *vals_out), which point either at the inputs or at the alternate buffers.
+// positions and histogram counts are 32-bit
+inline void radix_check_count(uint64_t n)
+{
+  if (n > 0xFFFFFFF0ull) throw bk_error(BK_ERR_LIMIT, "radix_sort_pairs: more than 2^32 items");
+}
+
+// Sorts (keys, vals) by bits [begin_bit, end_bit) of the key and by nothing else, stable: the last pass masks its digit to the
+// bits below end_bit, so keys that differ only outside the range keep their order whatever those bits hold.  On return the
+// sorted data is in (*keys_out, *vals_out), which point either at the inputs or (after an odd number of passes) at the
+// alternate buffers.  Nothing is done when n == 0 or end_bit <= begin_bit.
 inline void radix_sort_pairs(uint64_t *keys, uint32_t *vals, uint64_t n, int begin_bit, int end_bit, RadixBufs &rb, hipStream_t st,
                              uint64_t **keys_out, uint32_t **vals_out)
 {
   *keys_out = keys;
   *vals_out = vals;
   if (n == 0 || end_bit <= begin_bit) return;
-  if (n > 0xFFFFFFF0ull) throw bk_error(BK_ERR_LIMIT, "radix_sort_pairs: more than 2^32 items");
+  radix_check_count(n);
   uint64_t *ka = keys, *kb = rb.keys_alt.as<uint64_t>(n);
   uint32_t *va = vals, *vb = rb.vals_alt.as<uint32_t>(n);
   uint32_t nb = cdiv(n, RS_TILE);
   uint32_t *hist = rb.hist.as<uint32_t>((uint64_t) 256 * nb + 1);
   for (int shift = begin_bit; shift < end_bit; shift += 8)
   {
-    hipLaunchKernelGGL(k_radix_hist, dim3(nb), dim3(BLOCK), 0, st, ka, hist, n, shift, nb);
+    const uint32_t mask = end_bit - shift >= 8 ? 255u : (1u << (end_bit - shift)) - 1u;
+    hipLaunchKernelGGL(k_radix_hist, dim3(nb), dim3(BLOCK), 0, st, ka, hist, n, shift, mask, nb);
     exclusive_scan<uint32_t>(hist, hist, (uint64_t) 256 * nb, rb.scan_tmp, st);
-    hipLaunchKernelGGL(k_radix_scatter, dim3(nb), dim3(BLOCK), 0, st, ka, va, kb, vb, hist, n, shift, nb);
+    hipLaunchKernelGGL(k_radix_scatter, dim3(nb), dim3(BLOCK), 0, st, ka, va, kb, vb, hist, n, shift, mask, nb);
     std::swap(ka, kb);
     std::swap(va, vb);
   }

@@ -219,10 +219,10 @@ void unique_support(const JunctionPairs &p, const TupleTable &tt, const bk_clust
     ++stat->gathers;
     for (int shift = 0; shift < 64; shift += 8)
     {
-      if (!((differ >> shift) & 255u)) continue;
-      hipLaunchKernelGGL(prims::k_radix_hist, dim3(nb), dim3(prims::BLOCK), 0, st, ka, hist, n, shift, nb);
+      if (!((differ >> shift) & 255u)) continue;  // (whole digits: the mask of a pass is 255)
+      hipLaunchKernelGGL(prims::k_radix_hist, dim3(nb), dim3(prims::BLOCK), 0, st, ka, hist, n, shift, 255u, nb);
       prims::exclusive_scan<uint32_t>(hist, hist, (uint64_t) 256 * nb, b.scan_tmp, st);
-      hipLaunchKernelGGL(prims::k_radix_scatter, dim3(nb), dim3(prims::BLOCK), 0, st, ka, va, kb, vb, hist, n, shift, nb);
+      hipLaunchKernelGGL(prims::k_radix_scatter, dim3(nb), dim3(prims::BLOCK), 0, st, ka, va, kb, vb, hist, n, shift, 255u, nb);
       std::swap(ka, kb);
       std::swap(va, vb);
       ++stat->passes;

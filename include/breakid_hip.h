@@ -780,6 +780,20 @@ int bk_shard_bp_finish(bk_ctx *ctx, const void *depth_total_dev);
  * BreakID.cc:1274-1282,1091,1127) and returns the permutation (perm_out[p] = original index of the element now at p). */
 int bk_debug_std_sort(bk_ctx *ctx, const uint32_t *key, const uint64_t *group_off, uint32_t n_groups, uint32_t *perm_out);
 
+/* Test hooks of the two device-wide primitives every stage stands on (csrc/prims.h), on the context's stream and in buffers the
+ * context keeps between calls (so what an earlier call of another size left behind is part of what a test sees):
+ *   bk_debug_scan        prims::exclusive_scan of n elements of elem_bytes (4 or 8) bytes: out[0] = 0, out[i] = in[0] + .. +
+ *                        in[i-1] modulo 2^32 / 2^64, out[n] = the total (n + 1 entries).  in_place != 0: input and output are
+ *                        one device buffer of n + 1 entries, as the radix sort scans its histogram.
+ *   bk_debug_radix_sort  prims::radix_sort_pairs: (keys, vals) ordered by bits [begin_bit, end_bit) of the key alone, stable;
+ *                        begin_bit >= end_bit is the identity.  0 <= begin_bit and end_bit <= 64, else BK_ERR_ARG; more than
+ *                        2^32 - 16 items give BK_ERR_LIMIT.
+ *   bk_debug_prims_info  the tile constants of this build: BLOCK, SCAN_TILE, SCAN_ONE_MAX, RS_TILE (the sizes at which the
+ *                        primitives change their form follow from them) */
+int bk_debug_scan(bk_ctx *ctx, int elem_bytes, const void *in, uint64_t n, int in_place, void *out);
+int bk_debug_radix_sort(bk_ctx *ctx, const uint64_t *keys, const uint32_t *vals, uint64_t n, int begin_bit, int end_bit, uint64_t *keys_out, uint32_t *vals_out);
+int bk_debug_prims_info(uint64_t out[4]);
+
 /* Test hook: how the std::sort replays of this context ran so far, summed over its lanes: out[0] jobs of the resident sort
  * service, out[1] task dispatches on the caller's stream.  out[2] is always 0: it counted a third form (chains of launches)
  * that no longer exists; the three-word signature stays. */
