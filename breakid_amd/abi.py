@@ -62,6 +62,12 @@ FRAME_CLASSES = ["none", "antisense", "truncating", "promoter", "outframe", "inf
 FRAME_HEAD, FRAME_TAIL = 1, 2
 FRAME_CHUNK = 128  # csrc/frame.h: the overlapping transcripts of one side that the kernel stages at a time
 FRAME_LOCS = [".", "noncoding", "5UTR", "CDS", "intron", "3UTR"]  # BK_LOC_*
+LINK_SITE = np.dtype([("tid1", "<i4"), ("pos1", "<u4"), ("tid2", "<i4"), ("pos2", "<u4"), ("right1", "u1"), ("right2", "u1"), ("reserved", "u1", (6,))])  # struct bk_link_site; pos 1-based
+CALL_LINK = np.dtype([("n_dup", "<u4"), ("n_recip", "<u4"), ("n_adj", "<u4"), ("dup_of", "<i4"), ("mate", "<i4"), ("off", "<i4", (2,)), ("event", "<u4"), ("event_size", "<u4"),
+                      ("mate_crossed", "u1"), ("reserved", "u1", (3,))])  # struct bk_call_link
+assert LINK_SITE.itemsize == 24 and CALL_LINK.itemsize == 40
+LINK_RELATIONS = ["none", "duplicate", "reciprocal", "adjacent"]  # BK_LINK_*
+LINK_MAX_DIST = 1000000  # BK_LINK_MAX_DIST
 # the columns of a bk_txmodel, in the struct's order (ex_off has n_tx + 1 entries, ex_start / ex_end n_parts)
 TXMODEL_COLS = [("tid", np.int32), ("tx_start", np.uint32), ("tx_end", np.uint32), ("strand", np.uint8), ("ex_off", np.uint32), ("ex_start", np.uint32), ("ex_end", np.uint32)]
 # the columns of a bk_refseq table, in the struct's order (off has n_segs + 1 entries)

@@ -22,6 +22,7 @@
 #include "locsim.h"
 #include "coverage.h"
 #include "frame.h"
+#include "link.h"
 #include "exclude.h"
 #include "ahc.h"
 #include "lanes.h"
@@ -166,6 +167,9 @@ struct bk_ctx
   // fusion frame (bk_fusion_frame)
   FrameBufs frb;
   std::vector<struct bk_frame_call> f_frame;
+  // linked calls (bk_link_calls)
+  LinkBufs lkb;
+  std::vector<struct bk_call_link> f_link;
 
   // test hooks of the primitives (bk_debug_scan, bk_debug_radix_sort): buffers that live as long as the context, as a stage's do
   prims::RadixBufs dbg_radix;
@@ -1495,6 +1499,41 @@ int bk_fusion_frame(bk_ctx *ctx, const bk_txmodel *model, const struct bk_frame_
     }
     rows_to_host(ctx, d_res, n, ctx->f_frame);
     *out = ctx->f_frame.data();
+  });
+}
+
+int bk_link_calls(bk_ctx *ctx, const struct bk_link_site *sites, uint64_t n, uint32_t max_dist, const struct bk_call_link **out)
+{
+  return guarded(ctx, [&] {
+    if (!out) throw bk_error(BK_ERR_ARG, "bk_link_calls: null out");
+    if (n && !sites) throw bk_error(BK_ERR_ARG, "bk_link_calls: null sites");
+    if (ctx->shard) throw bk_error(BK_ERR_ARG, "bk_link_calls: sharded contexts (bk_shard_*) are not supported");
+    if (max_dist > BK_LINK_MAX_DIST) throw bk_error(BK_ERR_ARG, "bk_link_calls: max_dist above " + std::to_string(BK_LINK_MAX_DIST));
+    if (n > 0x40000000ull) throw bk_error(BK_ERR_LIMIT, "bk_link_calls: more than 2^30 sites");
+    LinkShape shape;
+    shape.n = n;
+    for (uint64_t k = 0; k < n; ++k)
+    {
+      if (sites[k].right1 > 1u || sites[k].right2 > 1u) throw bk_error(BK_ERR_ARG, "bk_link_calls: site " + std::to_string(k) + " has a right above 1 (0 = LEFT, 1 = RIGHT)");
+      for (const int32_t tid : {sites[k].tid1, sites[k].tid2})
+        if (tid >= 0)
+        {
+          ++shape.m;
+          if (tid > shape.max_tid) shape.max_tid = tid;
+        }
+    }
+    struct bk_call_link *d_res;
+    uint32_t rounds;
+    link_upload(sites, n, ctx->lkb, ctx->st);  // (outside the scope: it times the work on the device copy)
+    {
+      // touched (include/breakid_hip.h): the site and its row, and per breakend the sort passes and what the runs and events keep
+      const uint64_t bytes = shape.touched();
+      Scope s(ctx, "link_calls", bytes, bytes);
+      link_calls(shape, max_dist, ctx->lkb, ctx->st, &d_res, &rounds);
+    }
+    if (bk_debug("link")) fprintf(stderr, "bk_link_calls: %llu sites, %llu breakends with a contig, %d key bits, %u rounds of label propagation\n", (unsigned long long) n, (unsigned long long) shape.m, shape.key_bits(), rounds);
+    rows_to_host(ctx, d_res, n, ctx->f_link);
+    *out = ctx->f_link.data();
   });
 }
 

@@ -713,7 +713,7 @@ static void fetch_call_tables(const Options &o, const Sample &tumor, const Sampl
   if (o.genotype) fetch_rows(tumor, t.gsup, [&](auto rows, auto n) { return bk_ref_support(ctx, ctx, qual, anchor, w, rows, n); });
   if (o.genotype && normal.ctx) fetch_rows(tumor, t.gsup_normal, [&](auto rows, auto n) { return bk_ref_support(ctx, normal.ctx, qual, anchor, w, rows, n); });
   // -vcf: the junction evidence of every call (member pairs by strands, split tuples by clip side)
-  if (o.vcf || o.clip || o.consensus || o.coverage || o.frame) fetch_rows(tumor, t.jsup, [&](auto rows, auto n) { return bk_junctions(ctx, rows, n); });
+  if (o.vcf || o.clip || o.consensus || o.coverage || o.frame || o.link) fetch_rows(tumor, t.jsup, [&](auto rows, auto n) { return bk_junctions(ctx, rows, n); });
   // -clip: the clipped reads without an SA tag at every cluster, voted or not, on the sample's records and on the normal's
   if (o.clip) fetch_rows(tumor, t.csup, [&](auto rows, auto n) { return bk_clip_support(ctx, ctx, qual, min_clip, w, rows, n); });
   if (o.clip && normal.ctx) fetch_rows(tumor, t.csup_normal, [&](auto rows, auto n) { return bk_clip_support(ctx, normal.ctx, qual, min_clip, w, rows, n); });
@@ -1275,10 +1275,58 @@ static FrameMap fusion_frames(const Options &o, const Sample &tumor, const CallT
   return frames;
 }
 
+// ---- -link: reciprocal partners, duplicates and events among the voted calls -----------------------------------------------------------
+// One site per voted call, the calls of _fusion_all.txt, whether or not -all is given: a partner that the gene-pair filter removed is
+// still evidence, and an event id then means the same in both files.  The sides are those -vcf prints; one call of bk_link_calls
+// answers them all.  The sites stand in the order of their rows of BK_STAGE_CLUSTERS, so the smallest index of an event is its smallest
+// row and a tie goes to the smaller row, whatever order the tables are written in.
+static LinkMap link_calls(const Options &o, const Sample &tumor, const CallTables &t, const vector<OutRow> &rows)
+{
+  vector<const OutRow *> voted;
+  for (const OutRow &r : rows)
+    if (call_all_ok(r)) voted.push_back(&r);
+  std::sort(voted.begin(), voted.end(), [](const OutRow *a, const OutRow *b) { return a->idx < b->idx; });
+  vector<struct bk_link_site> sites;
+  vector<uint64_t> site_call;
+  for (const OutRow *v : voted)
+  {
+    const OutRow &r = *v;
+    if (r.idx >= t.jsup.size())
+    {
+      std::cerr << "Error: the evidence tables do not cover every call" << std::endl;
+      exit(1);
+    }
+    uint8_t right[2] = {0, 1}, source = 0;
+    bk_junction_sides(&t.jsup[r.idx], &right[0], &right[1], &source);
+    struct bk_link_site s = {};
+    s.tid1 = r.c.p1_tid, s.pos1 = r.c.p1_exact, s.tid2 = r.c.p2_tid, s.pos2 = (uint32_t) r.c.p2_exact;
+    s.right1 = right[0], s.right2 = right[1];
+    sites.push_back(s);
+    site_call.push_back(r.idx);
+  }
+  const struct bk_call_link *res = nullptr;
+  const int rc = bk_link_calls(tumor.ctx, sites.data(), sites.size(), (uint32_t) o.linkdist, &res);
+  if (rc != BK_OK) die(tumor, rc);
+  LinkMap links;
+  uint64_t events = 0, recip = 0;
+  for (size_t k = 0; k < sites.size(); ++k)
+  {
+    LinkCall &c = links[site_call[k]];
+    c.l = res[k];
+    c.event_row = site_call[c.l.event];
+    if (c.l.dup_of >= 0) c.dup_row = site_call[c.l.dup_of];
+    if (c.l.mate >= 0) c.mate_row = site_call[c.l.mate];
+    events += c.l.event == k && c.l.event_size > 1;
+    recip += c.l.n_recip;
+  }
+  std::cout << "link: " << sites.size() << " calls, " << events << " events of more than one call, " << recip / 2 << " reciprocal pairs" << std::endl;
+  return links;
+}
+
 // ---- the files behind the tables ---------------------------------------------------------------------------------------------------
 // -vcf: <prefix>_fusion.vcf, and with -clip <prefix>_fusion_rescued.vcf
 static void write_vcf_files(const Options &o, const Sample &tumor, const CallTables &t, const vector<OutRow> &rows, const Rescued &rescued, const ConsensusMap &cons,
-                            const HomologyMap &hom, const SimilarMap &sim, const CoverageMap &cov, const FrameMap &frame)
+                            const HomologyMap &hom, const SimilarMap &sim, const CoverageMap &cov, const FrameMap &frame, const LinkMap &link)
 {
   VcfInput vi;
   vi.nt = tumor.nt;
@@ -1298,6 +1346,7 @@ static void write_vcf_files(const Options &o, const Sample &tumor, const CallTab
   vi.sim = o.similar ? &sim : nullptr;
   vi.cov = o.coverage ? &cov : nullptr;
   vi.frame = o.frame ? &frame : nullptr;
+  vi.link = o.link ? &link : nullptr;
   auto write = [&](const string &path, const vector<OutRow> &calls) {
     if (write_vcf(path, calls, vi)) return;
     std::cerr << "Error: cannot write " << path << ": the evidence tables do not cover every call" << std::endl;
@@ -1312,6 +1361,7 @@ static void write_vcf_files(const Options &o, const Sample &tumor, const CallTab
   vi.sim = nullptr;                    // ... and with -similar
   vi.cov = nullptr;                    // ... and with -coverage
   vi.frame = nullptr;                  // ... and with -frame
+  vi.link = nullptr;                   // ... and with -link
   vi.rescued = &rescued.calls;
   write(o.out_file + "_fusion_rescued.vcf", rescued.rows);
 }
@@ -1363,6 +1413,7 @@ static void write_params(const Options &o, double w)
   if (o.similar) p << "similar_flank\t" << o.simflank << std::endl;
   if (o.coverage) p << "coverage_flank\t" << o.covflank << std::endl;
   if (o.frame) p << "frame" << std::endl;
+  if (o.link) p << "link_max_dist\t" << o.linkdist << std::endl;
 }
 
 // BreakID.cc:175-191.  scan_pairs_count and after_cluster_count are never updated by the reference (always 0);
@@ -1438,10 +1489,12 @@ int main(int argc, char *argv[])
   if (o.coverage) coverage = call_coverage(o, tumor, normal, tables, rows);
   FrameMap frames;
   if (o.frame) frames = fusion_frames(o, tumor, tables, rows, txpts);
+  LinkMap links;
+  if (o.link) links = link_calls(o, tumor, tables, rows);
 
   if (o.clip) write_rescued_tables(o, rescued, tables);
-  write_fusion_tables(o, rows, fusion_twins(o, tables, consensus.sides, homology, similar, coverage, frames));
-  if (o.vcf) write_vcf_files(o, tumor, tables, rows, rescued, consensus.sides, homology, similar, coverage, frames);
+  write_fusion_tables(o, rows, fusion_twins(o, tables, consensus.sides, homology, similar, coverage, frames, links));
+  if (o.vcf) write_vcf_files(o, tumor, tables, rows, rescued, consensus.sides, homology, similar, coverage, frames, links);
   if (o.evidence) write_evidence_files(o, tumor, tables, rows, rescued);
   write_params(o, run.w);
   const clock_t end = clock();

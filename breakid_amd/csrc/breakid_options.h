@@ -40,6 +40,8 @@ int bk_window_coverage(bk_ctx *records, const struct bk_cov_window *windows, uin
 int bk_call_windows(const bk_cluster *c, int right1, int right2, uint32_t flank, const uint32_t *target_len, struct bk_cov_window out[5]) __attribute__((weak));
 // -frame
 int bk_fusion_frame(bk_ctx *ctx, const bk_txmodel *model, const struct bk_frame_site *sites, uint64_t n, const struct bk_frame_call **out) __attribute__((weak));
+// -link
+int bk_link_calls(bk_ctx *ctx, const struct bk_link_site *sites, uint64_t n, uint32_t max_dist, const struct bk_call_link **out) __attribute__((weak));
 // -dedup
 int bk_unique_support(bk_ctx *ctx, const struct bk_unique_support **out, uint64_t *count, const uint64_t **first, uint64_t *n_rows) __attribute__((weak));
 // -clip (the soft-clip evidence, the depth at the rescued positions and the rescue rule)
@@ -87,21 +89,24 @@ static const char *HELP =
      \t -simflank  \t bases either side of a breakpoint that are compared, 1 to 255 (with -similar)  [150]\n \
      \t -coverage  \t mean depth of the aligned bases either side of both breakpoints of every call, between them and over their contigs (twin files *_coverage.txt; COVL / COVR / RDRATIO with -vcf)  \n \
      \t -covflank  \t bases either side of a breakpoint that are averaged, 1 to 1000000 (with -coverage)  [1000]\n \
-     \t -frame     \t 5' / 3' partner and reading frame of every call over all pairs of transcripts at its breakpoints (twin files *_frame.txt; FRCLASS / FR5P / FR3P with -vcf)  \n ";
+     \t -frame     \t 5' / 3' partner and reading frame of every call over all pairs of transcripts at its breakpoints (twin files *_frame.txt; FRCLASS / FR5P / FR3P with -vcf)  \n \
+     \t -link      \t reciprocal partner, duplicates and event of every call among all voted calls (twin files *_link.txt; EVENT / PARID with -vcf)  \n \
+     \t -linkdist  \t bases up to which two breakpoints count as one region, 0 to 1000000 (with -link)  [1000]\n ";
 
 struct Options
 {
   std::string inp_file, out_file, nib_dir, normal_file, exclude_file, build = "hg19";
   int qual = 20, device = 0, n_gpus = 0, transport = BK_TRANSPORT_AUTO;  // -gpus N: one sample over N GPUs (include/breakid_multi.h)
   bool fast = false, all = false;                                        // -all: no gene-pair and repeat filter (the _fusion_all files)
-  bool genotype = false, vcf = false, evidence = false, clip = false, dedup = false, consensus = false, homology = false, similar = false, coverage = false, frame = false;
-  bool anchor_given = false, minclip_given = false, clipsupport_given = false, conslen_given = false, homshift_given = false, homins_given = false, simflank_given = false, covflank_given = false;
+  bool genotype = false, vcf = false, evidence = false, clip = false, dedup = false, consensus = false, homology = false, similar = false, coverage = false, frame = false, link = false;
+  bool anchor_given = false, minclip_given = false, clipsupport_given = false, conslen_given = false, homshift_given = false, homins_given = false, simflank_given = false, covflank_given = false, linkdist_given = false;
   long anchor = 10;                      // -anchor: bases a reference read must cover on either side of the breakpoint base
   long min_clip = 10, clip_support = 3;  // -minclip: shortest clip that counts; -clipsupport: reads at one position a rescued side needs
   long conslen = 64;                     // -conslen: longest junction sequence per side
   long homshift = 32, homins = 32;       // -homshift, -homins: the largest offset and the longest insertion bk_junction_fit looks for
   long simflank = 150;                   // -simflank: the bases either side of a breakpoint that bk_locus_similarity compares
   long covflank = 1000;                  // -covflank: the bases either side of a cut that bk_call_windows gives a flank window
+  long linkdist = 1000;                  // -linkdist: the distance up to which bk_link_calls takes two breakends as near
   bool multi() const { return n_gpus >= 1; }  // the sharded run
   bool with_normal() const { return !normal_file.empty(); }
   bool exclude() const { return !exclude_file.empty(); }
@@ -141,6 +146,7 @@ static void check_options(const Options &o)
   const Feature similar{"-similar", o.similar, false, bk_locus_similarity != nullptr};
   const Feature coverage{"-coverage", o.coverage, false, bk_window_coverage && bk_call_windows && bk_junctions && bk_junction_sides};
   const Feature frame{"-frame", o.frame, false, bk_fusion_frame && bk_junctions && bk_junction_sides};
+  const Feature link{"-link", o.link, false, bk_link_calls && bk_junctions && bk_junction_sides};
   const Feature consensus{"-consensus", o.consensus, false, bk_clip_consensus && bk_clip_reads && bk_evidence && bk_junctions && bk_junction_sides};
   const Feature clip{"-clip", o.clip, false, bk_clip_support && bk_clip_reads && bk_base_depth && bk_clip_rescue && bk_junctions && bk_junction_sides};
   const Feature exclude{"-x", o.exclude(), true, bk_exclude_regions && bk_multi_run_ex && bk_multi_run_bam_ex && bk_multi_excluded};
@@ -174,6 +180,8 @@ static void check_options(const Options &o)
       rule(o.covflank_given && !o.coverage, "-covflank needs -coverage."), gpus(coverage), library(coverage),
       rule(o.coverage && !in_range(o.covflank, 1, 1000000), "-covflank must be a number from 1 to 1000000."),
       gpus(frame), library(frame),
+      rule(o.linkdist_given && !o.link, "-linkdist needs -link."), gpus(link),
+      rule(o.link && !in_range(o.linkdist, 0, 1000000), "-linkdist must be a number from 0 to 1000000."), library(link),
   };
   for (const Refusal &r : refusals)
   {
@@ -198,6 +206,7 @@ static Options parse_options(int argc, char *argv[])
                                      {"minclip", 1, 0, 18}, {"clipsupport", 1, 0, 19}, {"dedup", 0, 0, 20}, {"consensus", 0, 0, 21},
                                      {"conslen", 1, 0, 22}, {"homology", 0, 0, 23}, {"homshift", 1, 0, 24}, {"homins", 1, 0, 25},
                                      {"similar", 0, 0, 26}, {"simflank", 1, 0, 27}, {"coverage", 0, 0, 28}, {"covflank", 1, 0, 29}, {"frame", 0, 0, 30},
+                                     {"link", 0, 0, 31}, {"linkdist", 1, 0, 32},
                                      {"f", 0, 0, 5},  // (-f used to complete to -fast alone; it still means it beside -frame)
                                      {0, 0, 0, 0}};
   Options o;
@@ -242,6 +251,8 @@ static Options parse_options(int argc, char *argv[])
     case 28: o.coverage = true; break;
     case 29: number(o.covflank, o.covflank_given); break;
     case 30: o.frame = true; break;
+    case 31: o.link = true; break;
+    case 32: number(o.linkdist, o.linkdist_given); break;
     default: std::cerr << "Error: cannot parse arguments.\n"; exit(1);
     }
   }

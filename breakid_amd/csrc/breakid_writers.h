@@ -9,6 +9,7 @@
 #include <functional>
 #include <iostream>
 #include <map>
+#include <set>
 #include <sstream>
 #include <string>
 #include <vector>
@@ -302,6 +303,37 @@ struct FrameCall
     return s;
   }
 };
+// -link: the twin files' columns (bk_link_calls over every voted call; ids are rows of BK_STAGE_CLUSTERS, as bk<row> is)
+static const char *LINK_COLUMNS = "\tLk_Event\tLk_Size\tLk_Dup\tLk_Recip\tLk_Adj\tLk_DupOf\tLk_Mate\tLk_MateSide\tLk_Off1\tLk_Off2";
+
+// One voted call: its row, and the BK_STAGE_CLUSTERS rows behind the site indices it names (dup_row / mate_row only where there is one)
+struct LinkCall
+{
+  struct bk_call_link l;
+  uint64_t event_row = 0, dup_row = 0, mate_row = 0;
+  string fields() const
+  {
+    std::ostringstream o;
+    o << "\tev" << event_row << "\t" << l.event_size << "\t" << l.n_dup << "\t" << l.n_recip << "\t" << l.n_adj << "\t";
+    if (l.dup_of >= 0)
+      o << "bk" << dup_row;
+    else
+      o << ".";
+    if (l.mate >= 0)
+      o << "\tbk" << mate_row << "\t" << (l.mate_crossed ? "crossed" : "straight") << "\t" << l.off[0] << "\t" << l.off[1];
+    else
+      o << "\t.\t.\t.\t.";
+    return o.str();
+  }
+  // what breakend `side` (0 or 1) of the call ends its INFO with; PARID names the mate's paired breakend, and only one the file holds
+  string info(int side, bool mate_in_file) const
+  {
+    string s;
+    if (l.event_size > 1) s += ";EVENT=ev" + std::to_string(event_row);
+    if (l.mate >= 0 && mate_in_file) s += ";PARID=bk" + std::to_string(mate_row) + "_" + std::to_string((l.mate_crossed ? 1 - side : side) + 1);
+    return s;
+  }
+};
 // -clip -normal: what _fusion_rescued_normal.txt adds to a row of _fusion_rescued.txt
 static const char *RESCUED_COLUMNS_NORMAL = "\tNormal_DRP\tNormal_ClipAt1\tNormal_ClipAt2\tNormal_Depth1\tNormal_Depth2";
 
@@ -328,6 +360,7 @@ using HomologyMap = std::map<uint64_t, std::pair<HomologySide, HomologySide>>;
 using SimilarMap = std::map<uint64_t, SimilarCall>;
 using CoverageMap = std::map<uint64_t, CoverageCall>;
 using FrameMap = std::map<uint64_t, FrameCall>;
+using LinkMap = std::map<uint64_t, LinkCall>;  // every voted call, whichever files hold it
 
 // -clip: the rescued clusters in the order of _fusion_rescued.txt, calls[k] to rows[k]; with -evidence the clipped reads at the peaks
 // of the written ones (bk_clip_reads: the rows of sites 2 * j and 2 * j + 1 belong to the j-th written row)
@@ -369,7 +402,7 @@ struct Twin
 
 // The twins of this run, the reference's own two files first.  An option that adds columns to the calls adds its entry here.
 static vector<Twin> fusion_twins(const Options &o, const CallTables &t, const ConsensusMap &cons, const HomologyMap &hom, const SimilarMap &sim,
-                                 const CoverageMap &cov, const FrameMap &frame)
+                                 const CoverageMap &cov, const FrameMap &frame, const LinkMap &link)
 {
   const bool with_normal = o.with_normal();  // (a tumour without calls still gets header-only twins)
   vector<Twin> twins;
@@ -434,6 +467,12 @@ static vector<Twin> fusion_twins(const Options &o, const CallTables &t, const Co
     twins.push_back({"_frame", FRAME_COLUMNS, [&frame](const OutRow &r, string &tail) {
                        if (!frame.count(r.idx)) return false;
                        tail = frame.at(r.idx).fields();
+                       return true;
+                     }});
+  if (o.link)
+    twins.push_back({"_link", LINK_COLUMNS, [&link](const OutRow &r, string &tail) {
+                       if (!link.count(r.idx)) return false;
+                       tail = link.at(r.idx).fields();
                        return true;
                      }});
   return twins;
@@ -508,6 +547,9 @@ struct VcfInput
   const CoverageMap *cov = nullptr;
   // -frame (else null; never for the rescued clusters): FRCLASS / FR5P / FR3P on both breakends of a call, behind everything else
   const FrameMap *frame = nullptr;
+  // -link (else null; never for the rescued clusters): EVENT on both breakends of a call in an event of more than one call, PARID where
+  // the mate's records are in this file, behind everything else
+  const LinkMap *link = nullptr;
 };
 
 static char nib_base(const string &nib_dir, const string &chr, long pos1)  // the base at a 1-based position; N without a file or beyond it
@@ -556,6 +598,10 @@ struct VcfRecord
 static bool write_vcf(const string &path, const vector<OutRow> &rows, const VcfInput &in)
 {
   vector<VcfRecord> recs;
+  std::set<uint64_t> in_file;  // -link: the calls whose records this file holds (a PARID names no other)
+  if (in.link && !in.rescued)
+    for (const OutRow &r : rows)
+      if (call_written(r, in.all)) in_file.insert(r.idx);
   if (in.rescued && (in.rescued->size() != rows.size() || in.gsup || in.gsup_normal)) return false;
   for (size_t k = 0; k < rows.size(); ++k)
   {
@@ -621,6 +667,11 @@ static bool write_vcf(const string &path, const vector<OutRow> &rows, const VcfI
           if (cc.ratio_text(cc.tumor) != ".") o << ";RDRATIO=" << cc.ratio_text(cc.tumor);
         }
         if (in.frame && in.frame->count(r.idx)) o << in.frame->at(r.idx).info();
+        if (in.link && in.link->count(r.idx))
+        {
+          const LinkCall &lk = in.link->at(r.idx);
+          o << lk.info(s, lk.l.mate >= 0 && in_file.count(lk.mate_row));
+        }
         o << "\t" << (in.gsup ? "GT:GQ:DR:DV:RR:RV" : "DV:RV") << "\t" << vcf_sample(r.c.n_drp, r.c.n_sr, in.gsup ? &(*in.gsup)[r.idx] : nullptr, s);
         if (in.with_normal) o << "\t" << vcf_sample(in.nsup[r.idx].n_drp, in.nsup[r.idx].n_sr, in.gsup_normal ? &(*in.gsup_normal)[r.idx] : nullptr, s);
       }
@@ -676,6 +727,9 @@ static bool write_vcf(const string &path, const vector<OutRow> &rows, const VcfI
     v << "##INFO=<ID=FRCLASS,Number=1,Type=String,Description=\"Best class over all pairs of transcripts at the two breakpoints: antisense, truncating, promoter, outframe or inframe\">\n"
          "##INFO=<ID=FR5P,Number=1,Type=String,Description=\"Gene of the 5' partner of the reported pair of transcripts\">\n"
          "##INFO=<ID=FR3P,Number=1,Type=String,Description=\"Gene of the 3' partner of the reported pair of transcripts\">\n";
+  if (in.link && !in.rescued)
+    v << "##INFO=<ID=EVENT,Number=1,Type=String,Description=\"ID of the event of calls that share a breakpoint region: ev and the smallest call of the event\">\n"
+         "##INFO=<ID=PARID,Number=1,Type=String,Description=\"ID of the paired breakend of the reciprocal junction\">\n";
   if (in.rescued) v << "##INFO=<ID=SC,Number=1,Type=Integer,Description=\"Soft-clipped reads without an SA tag that end at this position (the clip peak)\">\n";
   if (in.gsup)
     v << "##FORMAT=<ID=GT,Number=1,Type=String,Description=\"Genotype\">\n"

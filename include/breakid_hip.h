@@ -701,6 +701,63 @@ struct bk_frame_call { uint8_t cls, order, loc[2], role[2]; uint16_t exon[2]; ui
  * prefix), each once, and 72 per site (its row and its result); the transcripts a site's walk visits are not modelled. */
 int bk_fusion_frame(bk_ctx *ctx, const bk_txmodel *model, const struct bk_frame_site *sites, uint64_t n, const struct bk_frame_call **out);
 
+/* ---- linked calls: reciprocal partners, duplicates and events of a list of calls -------------------------------------------------
+ * How the calls of one list relate to each other: which one is the reciprocal junction of which (der(A) and der(B) of a balanced
+ * translocation, the two ends of an inversion), which junction was called twice, and which calls share a breakpoint region and so
+ * form one event.  All arithmetic is integer.
+ * Site k: side 1 (tid1, pos1, right1) and side 2 (tid2, pos2, right2), pos 1-based as p1_exact is, right 0 = LEFT and 1 = RIGHT as
+ * everywhere else (bk_junction_sides); the layout of bk_frame_site.  Sides are numbered s = 0, 1 below.
+ *   near       A breakend is (tid, P, right).  Two breakends of different sites are near when tid == tid' >= 0 and |P - P'| <= D,
+ *              D = max_dist, compared in 64 bits (P may be 1 or 0xFFFFFFFF).  A side with tid < 0 is near nothing.
+ *   N          for sites i != j: N[s][t] = side s of i is near side t of j.
+ *   mappings   straight holds when N[0][0] && N[1][1] and pairs (0,0) and (1,1); crossed holds when N[0][1] && N[1][0] and pairs
+ *              (0,1) and (1,0).  A mapping that holds is same when both of its pairs have equal right, opposite when both have
+ *              different right (one of each is neither).
+ *   relation   of (i, j), symmetric, the first that applies:
+ *                BK_LINK_DUPLICATE (1)   a mapping holds and is same: the junction was called twice
+ *                BK_LINK_RECIPROCAL (2)  a mapping holds and is opposite: the two derivative junctions
+ *                BK_LINK_ADJACENT (3)    any N[s][t] is set (both pairs near with mixed sides are here)
+ *                BK_LINK_NONE (0)        otherwise
+ * Per site i: n_dup, n_recip and n_adj count the other sites in each relation, each other site once however many of its breakends
+ * are near.  dup_of is the smallest index among the duplicates, -1 without one.  mate is the reciprocal partner with the smallest
+ * |off[0]| + |off[1]|, ties to the smaller index; when both mappings of one partner are opposite the smaller sum wins, then
+ * straight; -1 without one.  off[s] is the partner's paired position minus P of side s, and mate_crossed is 1 for the crossed
+ * mapping; all three are 0 without a mate.  For a LEFT side (the bases up to and including P are retained) an offset of +1 is a
+ * blunt break, above +1 means off - 1 bases lost, 0 or below 1 - off bases duplicated; for a RIGHT side the signs mirror (-1 is
+ * blunt).
+ * Event: the graph whose edges are every relation other than none.  event is the smallest site index in the component of i and
+ * event_size its number of sites; a site alone has event == i and event_size == 1.  A site whose own two sides are near each other
+ * (a 300-base deletion with D = 1000) is not its own partner: only i != j counts.
+ * Every output is a count or an argmin with a fixed tie rule: two runs give the same bytes, and a permutation of the sites gives
+ * the same rows with the indices mapped.
+ * Hand example (D = 1000): site 0 = (chr1 300000 LEFT, chr2 700000 RIGHT), site 1 = (chr1 300021 RIGHT, chr2 699990 LEFT): straight
+ * holds and is opposite, RECIPROCAL; site 0 has mate = 1, off = {+21, -10}, event = 0, event_size = 2 without site 2.  Site 2 =
+ * (chr2 700400 LEFT, chr3 5000 RIGHT) is ADJACENT to both, so with it the event has size 3. */
+#define BK_LINK_NONE 0
+#define BK_LINK_DUPLICATE 1
+#define BK_LINK_RECIPROCAL 2
+#define BK_LINK_ADJACENT 3
+#define BK_LINK_MAX_DIST 1000000u
+struct bk_link_site { int32_t tid1; uint32_t pos1; int32_t tid2; uint32_t pos2; uint8_t right1, right2; uint8_t reserved[6]; };   /* 24 bytes, as bk_frame_site */
+struct bk_call_link { uint32_t n_dup, n_recip, n_adj; int32_t dup_of, mate; int32_t off[2]; uint32_t event, event_size; uint8_t mate_crossed; uint8_t reserved[3]; };   /* 40 bytes; reserved = 0 */
+/* ctx: any live context that is not a shard (bk_shard_*); no stage needs to have run, and nothing a later bk_fetch or stage returns
+ * changes.  sites: host memory.  *out (n rows) is library-owned until the next call or bk_free(ctx).  BK_ERR_ARG (with the reason
+ * in bk_last_error) for a null out, null sites with n > 0, a shard, a right above 1 and max_dist above BK_LINK_MAX_DIST.
+ * BK_ERR_LIMIT beyond 2^30 sites.  n == 0 is no error; max_dist == 0 means exact coincidence.
+ * How: the breakends with tid >= 0 are sorted by ((tid + 1) << 32) | pos over the bits in use.  A run ends where the sorted gap
+ * exceeds D or the contig changes; two breakends are joined by near-steps exactly when they lie in one run, so the events are
+ * the components of the graph whose vertices are runs and whose edges are the sites.  One wavefront per site searches, per side,
+ * the first key >= (tid, P - D) and deals the breakends up to (tid, P + D) to its lanes 64 a step; a hit on site j computes the
+ * whole N of (i, j) from the two rows and counts j only when the hit is the first set entry of N in the order (0,0) (0,1) (1,0)
+ * (1,1).  A locus with k sites inside one window therefore costs k * k for those sites; nothing is capped.  The components are
+ * min-label propagation with pointer jumping over the runs; the host reads a changed flag between rounds, and more than n + 1
+ * rounds give BK_ERR_LIMIT (they cannot be needed: a label travels at least one site a round).
+ * bk_timing: scope `link_calls` (the work on the device copy).  bk_timing_touched: 64 bytes per site (its row and its result) and,
+ * per breakend with tid >= 0 (m of them), 24 (its key and value written, its run id, its run's label and the event's two
+ * counters) + 24 per radix pass (key and value read and written), passes = ceil((32 + bits(max tid + 1)) / 8), bits(x) the
+ * position of the highest set bit of x from 1; the rows a site reads of its neighbours and the component rounds are not modelled. */
+int bk_link_calls(bk_ctx *ctx, const struct bk_link_site *sites, uint64_t n, uint32_t max_dist, const struct bk_call_link **out);
+
 /* Copy a stage's result to library-owned host memory.  *data stays valid until the next bk_fetch
  * of the same stage or bk_free.  group_off (may be NULL) receives n_groups+1 offsets for pair stages. */
 int bk_fetch(bk_ctx *ctx, int stage, const void **data, uint64_t *count, const uint64_t **group_off, uint32_t *n_groups);
