@@ -23,6 +23,7 @@
 #include "coverage.h"
 #include "frame.h"
 #include "link.h"
+#include "partners.h"
 #include "exclude.h"
 #include "ahc.h"
 #include "lanes.h"
@@ -170,6 +171,9 @@ struct bk_ctx
   // linked calls (bk_link_calls)
   LinkBufs lkb;
   std::vector<struct bk_call_link> f_link;
+  // partner loci (bk_locus_partners)
+  PartnerBufs ptb;
+  std::vector<struct bk_locus_partners> f_partners;
 
   // test hooks of the primitives (bk_debug_scan, bk_debug_radix_sort): buffers that live as long as the context, as a stage's do
   prims::RadixBufs dbg_radix;
@@ -1535,6 +1539,77 @@ int bk_link_calls(bk_ctx *ctx, const struct bk_link_site *sites, uint64_t n, uin
     rows_to_host(ctx, d_res, n, ctx->f_link);
     *out = ctx->f_link.data();
   });
+}
+
+int bk_locus_partners(bk_ctx *ctx, const struct bk_partner_site *sites, uint64_t n, uint32_t max_gap, const struct bk_locus_partners **out)
+{
+  return guarded(ctx, [&] {
+    if (!out) throw bk_error(BK_ERR_ARG, "bk_locus_partners: null out");
+    if (n && !sites) throw bk_error(BK_ERR_ARG, "bk_locus_partners: null sites");
+    if (ctx->shard) throw bk_error(BK_ERR_ARG, "bk_locus_partners: sharded contexts (bk_shard_*) are not supported");
+    if (!ctx->joined) throw bk_error(BK_ERR_ARG, "bk_locus_partners: call bk_discordant_pairs first");
+    if (n > 0x40000000ull) throw bk_error(BK_ERR_LIMIT, "bk_locus_partners: more than 2^30 sites");
+    for (uint64_t k = 0; k < n; ++k)
+      if (sites[k].reserved[0] || sites[k].reserved[1]) throw bk_error(BK_ERR_ARG, "bk_locus_partners: site " + std::to_string(k) + " has a non-zero reserved field");
+    PartnerBufs &b = ctx->ptb;
+    const uint64_t np = ctx->jr.n_pairs;
+    struct bk_locus_partners *d_res = nullptr;
+    partners_upload(sites, n, b, ctx->st);  // (outside the scope: it times the work on the device copy)
+    {
+      // (the two scopes inside push timers of their own, so the whole one ends by its index, not at timers.back(); the model needs
+      // the elsewhere rows, which are known once the count has run)
+      struct Whole
+      {
+        bk_ctx *c;
+        size_t at;
+        ~Whole()
+        {
+          if (c->timing && at < c->timers.size()) (void) hipEventRecord(c->timers[at].b, c->st);
+        }
+      } whole{ctx, ctx->timers.size()};
+      ctx->tick("locus_partners", 0, true, 0);
+      {
+        Scope s(ctx, "locus_partners_index", 0, partners_touched_index(np));
+        partners_index(ctx->jr.pairs, np, ctx->nt, b, ctx->st);
+      }
+      {
+        const size_t at = ctx->timers.size();
+        Scope s(ctx, "locus_partners_sites");
+        const uint64_t rows = partners_count(ctx->nt, n, b, ctx->st);
+        if (rows > 0xFFFFFFF0ull) throw bk_error(BK_ERR_LIMIT, "bk_locus_partners: " + std::to_string(rows) + " ends go elsewhere, more than the 2^32 - 16 rows a sort takes");
+        partners_rows(ctx->nt, n, rows, max_gap, b, ctx->st, &d_res);
+        if (ctx->timing && at < ctx->timers.size())
+        {
+          ctx->timers[at].touched = partners_touched_sites(ctx->nt, n, rows);
+          ctx->timers[whole.at].bytes = ctx->timers[whole.at].touched = partners_touched_index(np) + ctx->timers[at].touched;
+        }
+        if (bk_debug("partners")) fprintf(stderr, "bk_locus_partners: %llu sites, %llu ends in the index, %llu rows elsewhere, %u sort passes over them\n", (unsigned long long) n, (unsigned long long) (2 * np), (unsigned long long) rows, partners_row_passes(ctx->nt, n));
+      }
+    }
+    rows_to_host(ctx, d_res, n, ctx->f_partners);
+    *out = ctx->f_partners.data();
+  });
+}
+
+// The two sites of one call (include/breakid_hip.h): pure host code.
+int bk_call_partner_sites(const bk_cluster *c, double w, struct bk_partner_site out[2])
+{
+  if (!c || !out) return BK_ERR_ARG;
+  const long long W = (int) w;
+  const int32_t tid[2] = {c->p1_tid, c->p2_tid};
+  const uint32_t lo[2] = {c->p1_min, c->p2_min}, hi[2] = {c->p1_max, c->p2_max};
+  uint32_t beg[2], end[2];
+  for (int s = 0; s < 2; ++s)
+  {
+    long long a = (long long) lo[s] - W, b = (long long) hi[s] + W;
+    if (a < 1) a = 1;
+    if (a > 0xFFFFFFFFll) a = 0xFFFFFFFFll;
+    if (b > 0xFFFFFFFFll) b = 0xFFFFFFFFll;
+    if (b < a) a = 1, b = 0;
+    beg[s] = (uint32_t) a, end[s] = (uint32_t) b;
+  }
+  for (int s = 0; s < 2; ++s) out[s] = bk_partner_site{tid[s], beg[s], end[s], tid[1 - s], beg[1 - s], end[1 - s], {0u, 0u}};
+  return BK_OK;
 }
 
 // The side rule of one call and the ALT text of one breakend (include/breakid_hip.h): pure host code.

@@ -1323,10 +1323,54 @@ static LinkMap link_calls(const Options &o, const Sample &tumor, const CallTable
   return links;
 }
 
+// ---- -partners: where the discordant pairs inside the two windows of every written call point to --------------------------------------
+// Two sites per written call (bk_call_partner_sites: the window of bk_normal_support.n_drp on either side, the other side's as its
+// partner) and max_gap = (int) w, the run's own clustering distance; one call of bk_locus_partners answers them all on the sample's
+// pairs, a second one on the normal's.
+static PartnerMap locus_partners(const Options &o, const Sample &tumor, const Sample &normal, const vector<OutRow> &rows, double w)
+{
+  PartnerMap partners;
+  vector<struct bk_partner_site> sites;
+  vector<uint64_t> site_call;
+  for (const OutRow &r : rows)
+  {
+    if (!call_written(r, o.all)) continue;
+    struct bk_partner_site both[2];
+    if (bk_call_partner_sites(&r.c, w, both) != BK_OK) die(tumor, BK_ERR_ARG);
+    sites.insert(sites.end(), both, both + 2);
+    site_call.push_back(r.idx);
+  }
+  const int W = (int) w;
+  const uint32_t max_gap = W > 0 ? (uint32_t) W : 0u;
+  auto chr = [&](int32_t tid) { return tid >= 0 && tid < tumor.nt ? string(tumor.names[tid]) : string("*"); };
+  auto count = [&](const Sample &sample, bool is_normal) {
+    const struct bk_locus_partners *res = nullptr;
+    const int rc = bk_locus_partners(sample.ctx, sites.data(), sites.size(), max_gap, &res);
+    if (rc != BK_OK) die(sample, rc);
+    for (size_t k = 0; k < site_call.size(); ++k)
+    {
+      PartnerCall &c = partners[site_call[k]];
+      for (int s = 0; s < 2; ++s)
+      {
+        (is_normal ? c.normal : c.tumor)[s] = res[2 * k + s];
+        (is_normal ? c.normal_top_chr : c.top_chr)[s] = chr(res[2 * k + s].top_tid);
+      }
+    }
+    return res;
+  };
+  const struct bk_locus_partners *res = count(tumor, false);
+  uint64_t ends = 0, to_partner = 0;
+  for (size_t k = 0; k < sites.size(); ++k) ends += res[k].ends, to_partner += res[k].to_partner;
+  if (normal.ctx) count(normal, true);
+  std::cout << "partners: " << site_call.size() << " calls, " << ends << " ends in their windows, " << to_partner << " of them to the partner" << std::endl;
+  return partners;
+}
+
 // ---- the files behind the tables ---------------------------------------------------------------------------------------------------
 // -vcf: <prefix>_fusion.vcf, and with -clip <prefix>_fusion_rescued.vcf
 static void write_vcf_files(const Options &o, const Sample &tumor, const CallTables &t, const vector<OutRow> &rows, const Rescued &rescued, const ConsensusMap &cons,
-                            const HomologyMap &hom, const SimilarMap &sim, const CoverageMap &cov, const FrameMap &frame, const LinkMap &link)
+                            const HomologyMap &hom, const SimilarMap &sim, const CoverageMap &cov, const FrameMap &frame, const LinkMap &link,
+                            const PartnerMap &partners)
 {
   VcfInput vi;
   vi.nt = tumor.nt;
@@ -1347,6 +1391,7 @@ static void write_vcf_files(const Options &o, const Sample &tumor, const CallTab
   vi.cov = o.coverage ? &cov : nullptr;
   vi.frame = o.frame ? &frame : nullptr;
   vi.link = o.link ? &link : nullptr;
+  vi.partners = o.partners ? &partners : nullptr;
   auto write = [&](const string &path, const vector<OutRow> &calls) {
     if (write_vcf(path, calls, vi)) return;
     std::cerr << "Error: cannot write " << path << ": the evidence tables do not cover every call" << std::endl;
@@ -1362,6 +1407,7 @@ static void write_vcf_files(const Options &o, const Sample &tumor, const CallTab
   vi.cov = nullptr;                    // ... and with -coverage
   vi.frame = nullptr;                  // ... and with -frame
   vi.link = nullptr;                   // ... and with -link
+  vi.partners = nullptr;               // ... and with -partners
   vi.rescued = &rescued.calls;
   write(o.out_file + "_fusion_rescued.vcf", rescued.rows);
 }
@@ -1414,6 +1460,7 @@ static void write_params(const Options &o, double w)
   if (o.coverage) p << "coverage_flank\t" << o.covflank << std::endl;
   if (o.frame) p << "frame" << std::endl;
   if (o.link) p << "link_max_dist\t" << o.linkdist << std::endl;
+  if (o.partners) p << "partners" << std::endl;
 }
 
 // BreakID.cc:175-191.  scan_pairs_count and after_cluster_count are never updated by the reference (always 0);
@@ -1491,10 +1538,12 @@ int main(int argc, char *argv[])
   if (o.frame) frames = fusion_frames(o, tumor, tables, rows, txpts);
   LinkMap links;
   if (o.link) links = link_calls(o, tumor, tables, rows);
+  PartnerMap partners;
+  if (o.partners) partners = locus_partners(o, tumor, normal, rows, run.w);
 
   if (o.clip) write_rescued_tables(o, rescued, tables);
-  write_fusion_tables(o, rows, fusion_twins(o, tables, consensus.sides, homology, similar, coverage, frames, links));
-  if (o.vcf) write_vcf_files(o, tumor, tables, rows, rescued, consensus.sides, homology, similar, coverage, frames, links);
+  write_fusion_tables(o, rows, fusion_twins(o, tables, consensus.sides, homology, similar, coverage, frames, links, partners));
+  if (o.vcf) write_vcf_files(o, tumor, tables, rows, rescued, consensus.sides, homology, similar, coverage, frames, links, partners);
   if (o.evidence) write_evidence_files(o, tumor, tables, rows, rescued);
   write_params(o, run.w);
   const clock_t end = clock();

@@ -42,6 +42,9 @@ int bk_call_windows(const bk_cluster *c, int right1, int right2, uint32_t flank,
 int bk_fusion_frame(bk_ctx *ctx, const bk_txmodel *model, const struct bk_frame_site *sites, uint64_t n, const struct bk_frame_call **out) __attribute__((weak));
 // -link
 int bk_link_calls(bk_ctx *ctx, const struct bk_link_site *sites, uint64_t n, uint32_t max_dist, const struct bk_call_link **out) __attribute__((weak));
+// -partners (where the discordant pairs inside the windows of a call point to, and the windows of a call)
+int bk_locus_partners(bk_ctx *ctx, const struct bk_partner_site *sites, uint64_t n, uint32_t max_gap, const struct bk_locus_partners **out) __attribute__((weak));
+int bk_call_partner_sites(const bk_cluster *c, double w, struct bk_partner_site out[2]) __attribute__((weak));
 // -dedup
 int bk_unique_support(bk_ctx *ctx, const struct bk_unique_support **out, uint64_t *count, const uint64_t **first, uint64_t *n_rows) __attribute__((weak));
 // -clip (the soft-clip evidence, the depth at the rescued positions and the rescue rule)
@@ -91,14 +94,15 @@ static const char *HELP =
      \t -covflank  \t bases either side of a breakpoint that are averaged, 1 to 1000000 (with -coverage)  [1000]\n \
      \t -frame     \t 5' / 3' partner and reading frame of every call over all pairs of transcripts at its breakpoints (twin files *_frame.txt; FRCLASS / FR5P / FR3P with -vcf)  \n \
      \t -link      \t reciprocal partner, duplicates and event of every call among all voted calls (twin files *_link.txt; EVENT / PARID with -vcf)  \n \
-     \t -linkdist  \t bases up to which two breakpoints count as one region, 0 to 1000000 (with -link)  [1000]\n ";
+     \t -linkdist  \t bases up to which two breakpoints count as one region, 0 to 1000000 (with -link)  [1000]\n \
+     \t -partners  \t where the discordant pairs inside the two windows of every call point to: ends, ends to the partner window, loci elsewhere and the largest of them (twin files *_partners.txt; PTN / PTP / PTL with -vcf)  \n ";
 
 struct Options
 {
   std::string inp_file, out_file, nib_dir, normal_file, exclude_file, build = "hg19";
   int qual = 20, device = 0, n_gpus = 0, transport = BK_TRANSPORT_AUTO;  // -gpus N: one sample over N GPUs (include/breakid_multi.h)
   bool fast = false, all = false;                                        // -all: no gene-pair and repeat filter (the _fusion_all files)
-  bool genotype = false, vcf = false, evidence = false, clip = false, dedup = false, consensus = false, homology = false, similar = false, coverage = false, frame = false, link = false;
+  bool genotype = false, vcf = false, evidence = false, clip = false, dedup = false, consensus = false, homology = false, similar = false, coverage = false, frame = false, link = false, partners = false;
   bool anchor_given = false, minclip_given = false, clipsupport_given = false, conslen_given = false, homshift_given = false, homins_given = false, simflank_given = false, covflank_given = false, linkdist_given = false;
   long anchor = 10;                      // -anchor: bases a reference read must cover on either side of the breakpoint base
   long min_clip = 10, clip_support = 3;  // -minclip: shortest clip that counts; -clipsupport: reads at one position a rescued side needs
@@ -147,6 +151,7 @@ static void check_options(const Options &o)
   const Feature coverage{"-coverage", o.coverage, false, bk_window_coverage && bk_call_windows && bk_junctions && bk_junction_sides};
   const Feature frame{"-frame", o.frame, false, bk_fusion_frame && bk_junctions && bk_junction_sides};
   const Feature link{"-link", o.link, false, bk_link_calls && bk_junctions && bk_junction_sides};
+  const Feature partners{"-partners", o.partners, false, bk_locus_partners && bk_call_partner_sites};
   const Feature consensus{"-consensus", o.consensus, false, bk_clip_consensus && bk_clip_reads && bk_evidence && bk_junctions && bk_junction_sides};
   const Feature clip{"-clip", o.clip, false, bk_clip_support && bk_clip_reads && bk_base_depth && bk_clip_rescue && bk_junctions && bk_junction_sides};
   const Feature exclude{"-x", o.exclude(), true, bk_exclude_regions && bk_multi_run_ex && bk_multi_run_bam_ex && bk_multi_excluded};
@@ -182,6 +187,7 @@ static void check_options(const Options &o)
       gpus(frame), library(frame),
       rule(o.linkdist_given && !o.link, "-linkdist needs -link."), gpus(link),
       rule(o.link && !in_range(o.linkdist, 0, 1000000), "-linkdist must be a number from 0 to 1000000."), library(link),
+      gpus(partners), library(partners),
   };
   for (const Refusal &r : refusals)
   {
@@ -206,7 +212,7 @@ static Options parse_options(int argc, char *argv[])
                                      {"minclip", 1, 0, 18}, {"clipsupport", 1, 0, 19}, {"dedup", 0, 0, 20}, {"consensus", 0, 0, 21},
                                      {"conslen", 1, 0, 22}, {"homology", 0, 0, 23}, {"homshift", 1, 0, 24}, {"homins", 1, 0, 25},
                                      {"similar", 0, 0, 26}, {"simflank", 1, 0, 27}, {"coverage", 0, 0, 28}, {"covflank", 1, 0, 29}, {"frame", 0, 0, 30},
-                                     {"link", 0, 0, 31}, {"linkdist", 1, 0, 32},
+                                     {"link", 0, 0, 31}, {"linkdist", 1, 0, 32}, {"partners", 0, 0, 33},
                                      {"f", 0, 0, 5},  // (-f used to complete to -fast alone; it still means it beside -frame)
                                      {0, 0, 0, 0}};
   Options o;
@@ -253,6 +259,7 @@ static Options parse_options(int argc, char *argv[])
     case 30: o.frame = true; break;
     case 31: o.link = true; break;
     case 32: number(o.linkdist, o.linkdist_given); break;
+    case 33: o.partners = true; break;
     default: std::cerr << "Error: cannot parse arguments.\n"; exit(1);
     }
   }

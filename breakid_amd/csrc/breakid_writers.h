@@ -334,6 +334,41 @@ struct LinkCall
     return s;
   }
 };
+// -partners: the twin files' columns (bk_locus_partners on the two windows of the call, bk_call_partner_sites)
+static const char *PARTNERS_NAMES[11] = {"Pt_Ends1", "Pt_Partner1", "Pt_Loci1", "Pt_Top1", "Pt_TopN1", "Pt_Ends2", "Pt_Partner2", "Pt_Loci2", "Pt_Top2", "Pt_TopN2", "Pt_Frac"};
+static string partners_columns(const string &prefix)
+{
+  string s;
+  for (const char *name : PARTNERS_NAMES) s += string("\t") + prefix + name;
+  return s;
+}
+
+// One written call: the rows of its two sides on the sample's pairs and on the normal's, and the contig names of their top loci
+struct PartnerCall
+{
+  struct bk_locus_partners tumor[2], normal[2];
+  string top_chr[2], normal_top_chr[2];  // "*" for tid -1
+  static string top_text(const struct bk_locus_partners &p, const string &chr)
+  {
+    if (!p.top_n) return ".";
+    return chr + ":" + std::to_string(p.top_beg) + "-" + std::to_string(p.top_end);
+  }
+  static string fields(const struct bk_locus_partners *p, const string *chr)
+  {
+    std::ostringstream o;
+    for (int s = 0; s < 2; ++s) o << "\t" << p[s].ends << "\t" << p[s].to_partner << "\t" << p[s].loci << "\t" << top_text(p[s], chr[s]) << "\t" << p[s].top_n;
+    const uint64_t ends = (uint64_t) p[0].ends + p[1].ends, to_partner = (uint64_t) p[0].to_partner + p[1].to_partner;
+    char frac[64] = ".";
+    if (ends) snprintf(frac, sizeof frac, "%.3f", (double) to_partner / (double) ends);
+    o << "\t" << frac;
+    return o.str();
+  }
+  // what breakend `side` (0 or 1) of the call ends its INFO with
+  string info(int side) const
+  {
+    return ";PTN=" + std::to_string(tumor[side].ends) + ";PTP=" + std::to_string(tumor[side].to_partner) + ";PTL=" + std::to_string(tumor[side].loci);
+  }
+};
 // -clip -normal: what _fusion_rescued_normal.txt adds to a row of _fusion_rescued.txt
 static const char *RESCUED_COLUMNS_NORMAL = "\tNormal_DRP\tNormal_ClipAt1\tNormal_ClipAt2\tNormal_Depth1\tNormal_Depth2";
 
@@ -361,6 +396,7 @@ using SimilarMap = std::map<uint64_t, SimilarCall>;
 using CoverageMap = std::map<uint64_t, CoverageCall>;
 using FrameMap = std::map<uint64_t, FrameCall>;
 using LinkMap = std::map<uint64_t, LinkCall>;  // every voted call, whichever files hold it
+using PartnerMap = std::map<uint64_t, PartnerCall>;
 
 // -clip: the rescued clusters in the order of _fusion_rescued.txt, calls[k] to rows[k]; with -evidence the clipped reads at the peaks
 // of the written ones (bk_clip_reads: the rows of sites 2 * j and 2 * j + 1 belong to the j-th written row)
@@ -402,7 +438,7 @@ struct Twin
 
 // The twins of this run, the reference's own two files first.  An option that adds columns to the calls adds its entry here.
 static vector<Twin> fusion_twins(const Options &o, const CallTables &t, const ConsensusMap &cons, const HomologyMap &hom, const SimilarMap &sim,
-                                 const CoverageMap &cov, const FrameMap &frame, const LinkMap &link)
+                                 const CoverageMap &cov, const FrameMap &frame, const LinkMap &link, const PartnerMap &partners)
 {
   const bool with_normal = o.with_normal();  // (a tumour without calls still gets header-only twins)
   vector<Twin> twins;
@@ -473,6 +509,13 @@ static vector<Twin> fusion_twins(const Options &o, const CallTables &t, const Co
     twins.push_back({"_link", LINK_COLUMNS, [&link](const OutRow &r, string &tail) {
                        if (!link.count(r.idx)) return false;
                        tail = link.at(r.idx).fields();
+                       return true;
+                     }});
+  if (o.partners)
+    twins.push_back({"_partners", partners_columns("") + (with_normal ? partners_columns("Normal_") : ""), [&partners, with_normal](const OutRow &r, string &tail) {
+                       if (!partners.count(r.idx)) return false;
+                       const PartnerCall &c = partners.at(r.idx);
+                       tail = PartnerCall::fields(c.tumor, c.top_chr) + (with_normal ? PartnerCall::fields(c.normal, c.normal_top_chr) : "");
                        return true;
                      }});
   return twins;
@@ -550,6 +593,8 @@ struct VcfInput
   // -link (else null; never for the rescued clusters): EVENT on both breakends of a call in an event of more than one call, PARID where
   // the mate's records are in this file, behind everything else
   const LinkMap *link = nullptr;
+  // -partners (else null; never for the rescued clusters): PTN / PTP / PTL of its own side on every breakend of a call, behind everything else
+  const PartnerMap *partners = nullptr;
 };
 
 static char nib_base(const string &nib_dir, const string &chr, long pos1)  // the base at a 1-based position; N without a file or beyond it
@@ -672,6 +717,7 @@ static bool write_vcf(const string &path, const vector<OutRow> &rows, const VcfI
           const LinkCall &lk = in.link->at(r.idx);
           o << lk.info(s, lk.l.mate >= 0 && in_file.count(lk.mate_row));
         }
+        if (in.partners && in.partners->count(r.idx)) o << in.partners->at(r.idx).info(s);
         o << "\t" << (in.gsup ? "GT:GQ:DR:DV:RR:RV" : "DV:RV") << "\t" << vcf_sample(r.c.n_drp, r.c.n_sr, in.gsup ? &(*in.gsup)[r.idx] : nullptr, s);
         if (in.with_normal) o << "\t" << vcf_sample(in.nsup[r.idx].n_drp, in.nsup[r.idx].n_sr, in.gsup_normal ? &(*in.gsup_normal)[r.idx] : nullptr, s);
       }
@@ -730,6 +776,10 @@ static bool write_vcf(const string &path, const vector<OutRow> &rows, const VcfI
   if (in.link && !in.rescued)
     v << "##INFO=<ID=EVENT,Number=1,Type=String,Description=\"ID of the event of calls that share a breakpoint region: ev and the smallest call of the event\">\n"
          "##INFO=<ID=PARID,Number=1,Type=String,Description=\"ID of the paired breakend of the reciprocal junction\">\n";
+  if (in.partners && !in.rescued)
+    v << "##INFO=<ID=PTN,Number=1,Type=Integer,Description=\"Ends of discordant pairs inside the window of this side of the call\">\n"
+         "##INFO=<ID=PTP,Number=1,Type=Integer,Description=\"Those whose mate lies inside the window of the other side\">\n"
+         "##INFO=<ID=PTL,Number=1,Type=Integer,Description=\"Loci elsewhere that the mates of the others fall into\">\n";
   if (in.rescued) v << "##INFO=<ID=SC,Number=1,Type=Integer,Description=\"Soft-clipped reads without an SA tag that end at this position (the clip peak)\">\n";
   if (in.gsup)
     v << "##FORMAT=<ID=GT,Number=1,Type=String,Description=\"Genotype\">\n"

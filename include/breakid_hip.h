@@ -758,6 +758,58 @@ struct bk_call_link { uint32_t n_dup, n_recip, n_adj; int32_t dup_of, mate; int3
  * position of the highest set bit of x from 1; the rows a site reads of its neighbours and the component rounds are not modelled. */
 int bk_link_calls(bk_ctx *ctx, const struct bk_link_site *sites, uint64_t n, uint32_t max_dist, const struct bk_call_link **out);
 
+/* ---- partner loci: where the discordant pairs at a locus point to -------------------------------------------------------------------
+ * A call reports the pairs that agree with each other (N_DRP).  The same window may hold hundreds of ends whose mates scatter over
+ * many other places: the signature of a repeat, a collapsed duplication or an aligner's dumping ground.
+ * All arithmetic is signed 64-bit.
+ * The ends of a context are the 2 P sides of the P rows of its BK_STAGE_SCAN table.  Pair i gives two ends: end 2 i has own locus
+ * (p1_tid, p1_pos) and mate locus (p2_tid, p2_pos); end 2 i + 1 is the same pair the other way round.  Positions are the table's own
+ * (1-based).  For a site (T, a, b | MT, ma, mb) = (tid, beg, end | mtid, mbeg, mend):
+ *   ends        the number of ends with own tid == T and a <= pos <= b.
+ *   to_partner  the number of those whose mate has tid == MT and ma <= mpos <= mb.  MT < 0 or mb < ma means no end goes to the
+ *               partner.
+ *   elsewhere   the other ends.  Sort their mates ascending by (mtid, mpos); tid -1 sorts first.  A locus is a maximal run in which
+ *               neighbours have equal mtid and mpos differing by at most max_gap.  loci is the number of runs.  top_* describes the
+ *               run with the most ends; a tie goes to the first in sorted order.  top_n is its ends; top_tid, top_beg, top_end are
+ *               its contig and its smallest and largest mpos.  With no end elsewhere: loci = top_n = 0, top_tid = -1, top_beg =
+ *               top_end = 0; top_n == 0 is the "none" signal.
+ * T < 0, T >= n_targets and b < a give a zero row with top_tid = -1.  An end elsewhere whose mate lies inside the site's own window
+ * is a locus like any other: it is a local event, and worth seeing.  reserved = 0 everywhere.
+ * Hand example: chr1 = 0, chr2 = 1, chr3 = 2, and ten pairs (p1 -> p2): five chr1:1000, 1010, 1020, 1030, 1040 -> chr2:5000, 5010,
+ * 5020, 5030, 5040; three chr1:1100, 1110, 1120 -> chr3:9000, 9100, 9500; one chr1:1200 -> chr1:80000; one chr1:900 -> chr2:5600.
+ * The site (0, 800, 1300 | 1, 4800, 5300) has ends = 10 and to_partner = 5.  With max_gap = 200 and 399 it has loci = 4 (chr1:80000,
+ * chr2:5600, chr3:9000-9100, chr3:9500) and top = chr3:9000-9100 with top_n = 2; with max_gap = 400 it has loci = 3 and top =
+ * chr3:9000-9500 with top_n = 3.  The mirror site (1, 4800, 5300 | 0, 800, 1300) has ends = 5, to_partner = 5, loci = 0, top_n = 0.
+ * Every output is a count or an argmax with a fixed tie rule: two runs, and any permutation of the sites, give the same bytes row for
+ * row.  The structs have no typedef. */
+struct bk_partner_site { int32_t tid; uint32_t beg, end; int32_t mtid; uint32_t mbeg, mend; uint32_t reserved[2]; };   /* 32 bytes; 1-based, inclusive; reserved = 0 */
+struct bk_locus_partners { uint32_t ends, to_partner, loci, top_n; int32_t top_tid; uint32_t top_beg, top_end, reserved; }; /* 32 bytes */
+/* ctx: after bk_discordant_pairs and not a shard (bk_shard_*); any later stage may have run.  sites: host memory.  *out (n rows) is
+ * library-owned until the next call or bk_free(ctx).  BK_ERR_ARG (with the reason in bk_last_error) for a null out, null sites with
+ * n > 0, wrong call order, shards and a site whose reserved is not 0.  BK_ERR_LIMIT beyond 2^30 sites, or when the elsewhere ends of
+ * all sites together exceed what the radix sort takes (2^32 - 16 rows).  n == 0 and a context without pairs are no errors.  It
+ * changes nothing a later bk_fetch or stage returns, and works on every table form the context can hold (host upload, BK_MEM_DEVICE
+ * with and without `side`, the table bk_exclude_regions left behind, the context of bk_bam_decode_device_ctx while its bk_bam_dev
+ * lives): it reads the pair table alone.
+ * How: the ends are sorted by ((tid + 1) << 32) | pos over the bits in use, 32 + bits(n_targets + 1), and the mates' keys gathered
+ * into that order; the index is rebuilt by every call.  One wavefront per site finds its range [lo, hi) with two wave-wide lower
+ * bounds and tests the mates 64 per ballot.  An exclusive scan of the elsewhere counts gives every site a segment of rows; the host
+ * reads their total once.  One wavefront per site writes its elsewhere mates' keys there (a row's slot is the matches in front of
+ * it: no atomic), the rows are sorted stably by the mate key's bits and then by the site's, and one wavefront per site walks its
+ * sorted segment 64 rows a step for the runs.
+ * bk_timing: scope `locus_partners` (the work on the device copy), with `locus_partners_index` and `locus_partners_sites` inside it.
+ * bk_timing_touched of `locus_partners`: 56 bytes per pair row read and 12 bytes per end of the index (its key and its value), which
+ * is `locus_partners_index`; 64 bytes per site (its row and its result) and 12 bytes per elsewhere row (its key and its value) per
+ * sort pass, passes = ceil((32 + bits(n_targets + 1)) / 8) + ceil(bits(n - 1) / 8), bits(x) the position of the highest set bit of x
+ * from 1, which is `locus_partners_sites`.  The passes of the index's own sort and the ends the sites read are not modelled. */
+int bk_locus_partners(bk_ctx *ctx, const struct bk_partner_site *sites, uint64_t n, uint32_t max_gap, const struct bk_locus_partners **out);
+/* The two sites of one call, a pure host function (no context, no GPU), so that every caller shares one rule.  With W = (int) w, side
+ * s (0 = p1, 1 = p2) of a cluster has the own window [max(1, ps_min - W), ps_max + W] on ps_tid, the call's window as
+ * bk_normal_support defines it, and the other side's window as its partner window.  out[s] is side s; a bound above 0xFFFFFFFF is
+ * written as 0xFFFFFFFF and a window whose upper bound lies below its lower one as (1, 0).  Returns BK_OK, or BK_ERR_ARG for a null
+ * argument. */
+int bk_call_partner_sites(const bk_cluster *c, double w, struct bk_partner_site out[2]);   /* pure host function */
+
 /* Copy a stage's result to library-owned host memory.  *data stays valid until the next bk_fetch
  * of the same stage or bk_free.  group_off (may be NULL) receives n_groups+1 offsets for pair stages. */
 int bk_fetch(bk_ctx *ctx, int stage, const void **data, uint64_t *count, const uint64_t **group_off, uint32_t *n_groups);
