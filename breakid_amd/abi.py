@@ -71,6 +71,9 @@ LINK_MAX_DIST = 1000000  # BK_LINK_MAX_DIST
 PARTNER_SITE = np.dtype([("tid", "<i4"), ("beg", "<u4"), ("end", "<u4"), ("mtid", "<i4"), ("mbeg", "<u4"), ("mend", "<u4"), ("reserved", "<u4", (2,))])  # struct bk_partner_site; 1-based, inclusive
 LOCUS_PARTNERS = np.dtype([("ends", "<u4"), ("to_partner", "<u4"), ("loci", "<u4"), ("top_n", "<u4"), ("top_tid", "<i4"), ("top_beg", "<u4"), ("top_end", "<u4"), ("reserved", "<u4")])  # struct bk_locus_partners
 assert PARTNER_SITE.itemsize == 32 and LOCUS_PARTNERS.itemsize == 32
+FRAG_SITE = np.dtype([("pos1", "<u4"), ("pos2", "<u4"), ("right1", "u1"), ("right2", "u1"), ("skip", "u1"), ("reserved", "u1", (5,))])  # struct bk_frag_site; pos 1-based
+FRAG_SIZES = np.dtype([("n_used", "<u4"), ("n_off", "<u4"), ("n_lost", "<u4"), ("n_short", "<u4"), ("n_long", "<u4"), ("min", "<i4"), ("max", "<i4"), ("reserved", "<u4"), ("sum", "<i8"), ("abs_dev", "<u8")])  # struct bk_frag_sizes
+assert FRAG_SITE.itemsize == 16 and FRAG_SIZES.itemsize == 48
 # the columns of a bk_txmodel, in the struct's order (ex_off has n_tx + 1 entries, ex_start / ex_end n_parts)
 TXMODEL_COLS = [("tid", np.int32), ("tx_start", np.uint32), ("tx_end", np.uint32), ("strand", np.uint8), ("ex_off", np.uint32), ("ex_start", np.uint32), ("ex_end", np.uint32)]
 # the columns of a bk_refseq table, in the struct's order (off has n_segs + 1 entries)

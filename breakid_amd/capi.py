@@ -35,7 +35,7 @@ def build(verbose=False):
 
 EXPORTS = ["bk_init", "bk_prepare_process", "bk_free", "bk_last_error", "bk_set_stream", "bk_sync", "bk_get_stream", "bk_upload_records", "bk_records", "bk_exclude_regions", "bk_isize_stats",
            "bk_discordant_pairs", "bk_mask_and_cluster", "bk_split_evidence", "bk_cluster_summary",
-           "bk_split_breakpoints", "bk_normal_support", "bk_ref_support", "bk_genotype_call", "bk_clip_support", "bk_clip_reads", "bk_base_depth", "bk_clip_rescue", "bk_junctions", "bk_junction_sides", "bk_vcf_breakend_alt", "bk_evidence", "bk_unique_support", "bk_clip_consensus", "bk_junction_fit", "bk_locus_similarity", "bk_window_coverage", "bk_call_windows", "bk_fusion_frame", "bk_link_calls", "bk_locus_partners", "bk_call_partner_sites", "bk_run", "bk_fetch", "bk_timing", "bk_timing_enable", "bk_timing_touched", "bk_group_stats", "bk_qname_hash", "bk_qname_check",
+           "bk_split_breakpoints", "bk_normal_support", "bk_ref_support", "bk_genotype_call", "bk_clip_support", "bk_clip_reads", "bk_base_depth", "bk_clip_rescue", "bk_junctions", "bk_junction_sides", "bk_vcf_breakend_alt", "bk_evidence", "bk_unique_support", "bk_clip_consensus", "bk_junction_fit", "bk_locus_similarity", "bk_window_coverage", "bk_call_windows", "bk_fusion_frame", "bk_link_calls", "bk_locus_partners", "bk_call_partner_sites", "bk_fragment_sizes", "bk_fragment_bounds", "bk_run", "bk_fetch", "bk_timing", "bk_timing_enable", "bk_timing_touched", "bk_group_stats", "bk_qname_hash", "bk_qname_check",
            "bk_bam_open", "bk_bam_header", "bk_bam_decode", "bk_bam_close", "bk_bam_extract", "bk_bam_names_free", "bk_bam_reads", "bk_reads_free", "bk_bam_decode_device", "bk_bam_decode_device_part", "bk_bam_decode_device_ctx", "bk_bam_dev_free", "bk_feed_release_caches", "bk_debug_bgzf_inflate", "bk_debug_std_sort", "bk_debug_scan", "bk_debug_radix_sort", "bk_debug_prims_info", "bk_sort_forms", "bk_debug_ahc", "bk_debug_points", "bk_debug_cigar", "bk_debug_vote", "bk_debug_region", "bk_shard_begin", "bk_shard_get_stats", "bk_shard_set_stats",
            "bk_shard_sd_local", "bk_shard_sd_finish", "bk_shard_buffer", "bk_shard_set_buffer", "bk_shard_group_sizes",
            "bk_shard_own_groups", "bk_shard_route_candidates", "bk_shard_group_keys", "bk_shard_route_pairs", "bk_shard_group_pairs", "bk_shard_bp_cov", "bk_shard_bp_vote", "bk_shard_bp_vote_slice", "bk_shard_bp_set_voted", "bk_shard_bp_depth", "bk_shard_bp_finish"]
@@ -92,6 +92,8 @@ def lib():
         L.bk_link_calls.argtypes = [vp, vp, C.c_uint64, C.c_uint32, C.POINTER(vp)]
         L.bk_locus_partners.argtypes = [vp, vp, C.c_uint64, C.c_uint32, C.POINTER(vp)]
         L.bk_call_partner_sites.argtypes = [vp, C.c_double, vp]
+        L.bk_fragment_sizes.argtypes = [vp, vp, C.c_uint64, C.c_int32, C.c_int32, C.POINTER(vp)]
+        L.bk_fragment_bounds.argtypes = [C.c_double, C.c_double, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         L.bk_fetch.argtypes = [vp, C.c_int, C.POINTER(vp), u64p, C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(C.c_uint32)]
         L.bk_timing.argtypes = [vp, C.POINTER(C.POINTER(C.c_char_p)), C.POINTER(C.POINTER(C.c_float)),
                                 C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(C.c_int)]
@@ -284,6 +286,16 @@ def call_partner_sites(cluster, w):
     if rc != 0:
         raise BreakIDError(rc, "bk_call_partner_sites")
     return out
+
+
+def fragment_bounds(mean, sd):
+    """The library's bounds for Context.fragment_sizes (bk_fragment_bounds; no GPU): (max(0, floor(mean - 3 sd)), ceil(mean + 3 sd)), both
+    clamped to int32.  A non-finite value or sd < 0 raises BreakIDError(BK_ERR_ARG)."""
+    lo, hi = C.c_int32(), C.c_int32()
+    rc = lib().bk_fragment_bounds(float(mean), float(sd), C.byref(lo), C.byref(hi))
+    if rc != 0:
+        raise BreakIDError(rc, "bk_fragment_bounds")
+    return lo.value, hi.value
 
 
 def vcf_breakend_alt(ref_base, own_right, mate_chr, mate_pos, mate_right, cap=None):
@@ -652,6 +664,19 @@ class Context:
             return np.zeros(0, abi.LOCUS_PARTNERS)
         buf = (C.c_char * (n * abi.LOCUS_PARTNERS.itemsize)).from_address(out.value)
         return np.frombuffer(buf, dtype=abi.LOCUS_PARTNERS, count=n).copy()
+
+    def fragment_sizes(self, sites, lo, hi):
+        """The fragment lengths the member pairs of every call imply across its junction (bk_fragment_sizes).  sites: abi.FRAG_SITE rows,
+        one per BK_STAGE_CLUSTERS row; lo, hi: the library's bounds (capi.fragment_bounds).  Returns one abi.FRAG_SIZES row per site."""
+        sites = np.ascontiguousarray(sites, abi.FRAG_SITE)
+        assert sites.ndim == 1
+        n = len(sites)
+        out = C.c_void_p()
+        self._check(self.L.bk_fragment_sizes(self.h, sites.ctypes.data if n else None, n, lo, hi, C.byref(out)))
+        if not n:
+            return np.zeros(0, abi.FRAG_SIZES)
+        buf = (C.c_char * (n * abi.FRAG_SIZES.itemsize)).from_address(out.value)
+        return np.frombuffer(buf, dtype=abi.FRAG_SIZES, count=n).copy()
 
     def run(self, qual=20, fast=True):
         w, n = C.c_double(), C.c_uint64()

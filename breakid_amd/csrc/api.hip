@@ -24,6 +24,7 @@
 #include "frame.h"
 #include "link.h"
 #include "partners.h"
+#include "fragsize.h"
 #include "exclude.h"
 #include "ahc.h"
 #include "lanes.h"
@@ -174,6 +175,9 @@ struct bk_ctx
   // partner loci (bk_locus_partners)
   PartnerBufs ptb;
   std::vector<struct bk_locus_partners> f_partners;
+  // fragment sizes (bk_fragment_sizes)
+  FragBufs fgb;
+  std::vector<struct bk_frag_sizes> f_fragsize;
 
   // test hooks of the primitives (bk_debug_scan, bk_debug_radix_sort): buffers that live as long as the context, as a stage's do
   prims::RadixBufs dbg_radix;
@@ -1609,6 +1613,98 @@ int bk_call_partner_sites(const bk_cluster *c, double w, struct bk_partner_site 
     beg[s] = (uint32_t) a, end[s] = (uint32_t) b;
   }
   for (int s = 0; s < 2; ++s) out[s] = bk_partner_site{tid[s], beg[s], end[s], tid[1 - s], beg[1 - s], end[1 - s], {0u, 0u}};
+  return BK_OK;
+}
+
+int bk_fragment_sizes(bk_ctx *ctx, const struct bk_frag_site *sites, uint64_t n, int32_t lo, int32_t hi, const struct bk_frag_sizes **out)
+{
+  return guarded(ctx, [&] {
+    if (!out) throw bk_error(BK_ERR_ARG, "bk_fragment_sizes: null out");
+    if (n && !sites) throw bk_error(BK_ERR_ARG, "bk_fragment_sizes: null sites");
+    if (ctx->shard) throw bk_error(BK_ERR_ARG, "bk_fragment_sizes: sharded contexts (bk_shard_*) are not supported");
+    if (!ctx->bp_done || !ctx->clustered || !ctx->summary_map) throw bk_error(BK_ERR_ARG, "bk_fragment_sizes: call bk_split_breakpoints first");
+    const uint64_t ncl = ctx->n_clusters;
+    if (n != ncl) throw bk_error(BK_ERR_ARG, "bk_fragment_sizes: " + std::to_string(n) + " sites for " + std::to_string(ncl) + " clusters (one site per BK_STAGE_CLUSTERS row)");
+    if (lo > hi) throw bk_error(BK_ERR_ARG, "bk_fragment_sizes: lo above hi");
+    for (uint64_t k = 0; k < n; ++k)
+    {
+      const struct bk_frag_site &s = sites[k];
+      if (s.right1 > 1u || s.right2 > 1u || s.skip > 1u) throw bk_error(BK_ERR_ARG, "bk_fragment_sizes: site " + std::to_string(k) + " has a right or a skip above 1");
+      for (const uint8_t r : s.reserved)
+        if (r) throw bk_error(BK_ERR_ARG, "bk_fragment_sizes: site " + std::to_string(k) + " has a non-zero reserved field");
+    }
+    const bk_soa &t = ctx->rec;
+    if (ncl && (!ctx->have_records || !t.tid || !t.pos || !t.flag || !t.mapq || !t.cigar_off || (t.n_cigar_words && !t.cigar) || (!t.side && !t.qhash)))
+      throw bk_error(BK_ERR_ARG, "bk_fragment_sizes: the record table lacks a column");
+    const JunctionPairs jp = junction_pairs(ctx);
+    EvidenceRecs er{t.n, t.side, t.qhash, t.qcheck, t.mapq};
+    FragBufs &b = ctx->fgb;
+    struct bk_frag_sizes *d_res;
+    FragLen *d_len;
+    uint64_t *d_off;
+    uint64_t n_rows = 0;
+    EvidenceStat *d_ev_stat;
+    FragStat *d_stat;
+    fragsize_upload(sites, n, b, ctx->st);  // (outside the scope: it times the work on the device copy)
+    {
+      // bytes: what bk_evidence reads to list the rows
+      Scope s(ctx, "fragment_sizes", jp.n * (12ull + 4ull + 2ull * 12ull));
+      fragment_sizes(jp, tuple_table(ctx), ctx->clusters_ptr(), ncl, er, rec_view(ctx), lo, hi, b, ctx->st, &d_res, &d_len, &d_off, &n_rows, &d_ev_stat, &d_stat);
+    }
+    EvidenceStat ev_stat{};
+    FragStat stat{};
+    HIP_CHECK(hipMemcpyAsync(&ev_stat, d_ev_stat, sizeof ev_stat, hipMemcpyDeviceToHost, ctx->st));
+    HIP_CHECK(hipMemcpyAsync(&stat, d_stat, sizeof stat, hipMemcpyDeviceToHost, ctx->st));
+    rows_to_host(ctx, d_res, ncl, ctx->f_fragsize);
+    if (ev_stat.bad || stat.bad) throw bk_error(BK_ERR_HIP, "bk_fragment_sizes: the listing and the counts of bk_junctions disagree (internal error)");
+    uint64_t used = 0;
+    for (const struct bk_frag_sizes &r : ctx->f_fragsize) used += r.n_used;
+    if (ctx->timing && !ctx->timers.empty())
+    {
+      // touched (include/breakid_hip.h): the listing as in bk_evidence without the split rows, then per pair row, per looked-up
+      // record, per walked record, per used side and per site
+      int bits = 1;
+      while ((ncl >> bits) != 0) ++bits;
+      const uint64_t ev_passes = (uint64_t) (bits + 7) / 8;
+      ctx->timers.back().bytes += n_rows * 120ull;
+      ctx->timers.back().touched = jp.n * (12ull + 32ull) + ncl * (sizeof(bk_cluster) + 2ull * sizeof(struct bk_junction) + 20ull) + jp.n * (12ull + 12ull + ev_passes * 32ull + 12ull) +
+                                   n_rows * (64ull + 32ull) + n_rows * 120ull + stat.lookups * 80ull + stat.walked * 18ull + 2ull * used * 8ull + ncl * 80ull;
+    }
+    if (bk_debug("fragsize"))
+    {
+      fprintf(stderr, "bk_fragment_sizes: %llu sites, %llu pair rows, %llu used, library %d-%d; %llu records looked up, their walks read %llu records, the longest %u, %llu finished by a wavefront\n",
+              (unsigned long long) n, (unsigned long long) n_rows, (unsigned long long) used, lo, hi, (unsigned long long) stat.lookups, (unsigned long long) stat.walked, stat.longest,
+              (unsigned long long) stat.wave_walks);
+      std::vector<FragLen> len(n_rows);
+      std::vector<uint64_t> off(ncl + 1, 0);
+      if (n_rows) HIP_CHECK(hipMemcpyAsync(len.data(), d_len, n_rows * sizeof(FragLen), hipMemcpyDeviceToHost, ctx->st));
+      if (ncl) HIP_CHECK(hipMemcpyAsync(off.data(), d_off, (ncl + 1) * 8, hipMemcpyDeviceToHost, ctx->st));
+      HIP_CHECK(hipStreamSynchronize(ctx->st));
+      int shown = 0;
+      for (uint64_t c = 0; c < ncl && shown < 32; ++c)
+      {
+        if (sites[c].skip) continue;
+        ++shown;
+        fprintf(stderr, "  call %llu (%u-%u, %c%c):", (unsigned long long) c, sites[c].pos1, sites[c].pos2, sites[c].right1 ? 'R' : 'L', sites[c].right2 ? 'R' : 'L');
+        for (uint64_t i = off[c]; i < off[c + 1] && i < off[c] + 64; ++i)
+          if (len[i].mark == FRAG_USED) fprintf(stderr, " %d", len[i].len);
+          else fprintf(stderr, " %s", len[i].mark == FRAG_OFF ? "off" : len[i].mark == FRAG_LOST ? "lost" : "?");
+        fprintf(stderr, "%s\n", off[c + 1] - off[c] > 64 ? " ..." : "");
+      }
+    }
+    *out = ctx->f_fragsize.data();
+  });
+}
+
+// The library's bounds (include/breakid_hip.h): pure host code.
+int bk_fragment_bounds(double mean, double sd, int32_t *lo, int32_t *hi)
+{
+  if (!lo || !hi || !std::isfinite(mean) || !std::isfinite(sd) || sd < 0) return BK_ERR_ARG;
+  auto clamp = [](double v) { return v >= 2147483647.0 ? (int32_t) 2147483647 : v <= -2147483648.0 ? (int32_t) (-2147483647 - 1) : (int32_t) v; };
+  const double three = 3.0 * sd;
+  const double a = std::floor(mean - three), b = std::ceil(mean + three);
+  *lo = clamp(a < 0 ? 0.0 : a);
+  *hi = clamp(b);
   return BK_OK;
 }
 

@@ -582,6 +582,7 @@ static void decode_tumor(const Options &o, Sample &tumor, const Exclusion &x)
 struct Run
 {
   double w = 0;
+  double mean = 0, sd = 0;  // the library's insert sizes (bk_isize_stats), kept for -fragsize
   uint64_t n_clustered = 0, n_valid = 0;
   clock_t scan_start = clock(), scan_end = scan_start, cluster_start = scan_start, cluster_end = scan_start, bp_start = scan_start, bp_end = scan_start;
 };
@@ -607,6 +608,7 @@ static Run run_stages(const Options &o, Sample &t, const Exclusion &x)
   double mean = 0, sd = 0;
   if ((rc = bk_isize_stats(t.ctx, &mean, &sd)) != BK_OK) die(t, rc);
   std::cout << "the insert size mean: " << mean << ", the insert size sd:" << sd << " .\n";
+  run.mean = mean, run.sd = sd;
   const int times = 2;
   run.w = times * std::sqrt(times) * (mean + 3 * sd);
   std::cout << "cluster_dist = span_dist = mask_dist = scan_dist = " << run.w << " .\n";
@@ -713,7 +715,7 @@ static void fetch_call_tables(const Options &o, const Sample &tumor, const Sampl
   if (o.genotype) fetch_rows(tumor, t.gsup, [&](auto rows, auto n) { return bk_ref_support(ctx, ctx, qual, anchor, w, rows, n); });
   if (o.genotype && normal.ctx) fetch_rows(tumor, t.gsup_normal, [&](auto rows, auto n) { return bk_ref_support(ctx, normal.ctx, qual, anchor, w, rows, n); });
   // -vcf: the junction evidence of every call (member pairs by strands, split tuples by clip side)
-  if (o.vcf || o.clip || o.consensus || o.coverage || o.frame || o.link) fetch_rows(tumor, t.jsup, [&](auto rows, auto n) { return bk_junctions(ctx, rows, n); });
+  if (o.vcf || o.clip || o.consensus || o.coverage || o.frame || o.link || o.fragsize) fetch_rows(tumor, t.jsup, [&](auto rows, auto n) { return bk_junctions(ctx, rows, n); });
   // -clip: the clipped reads without an SA tag at every cluster, voted or not, on the sample's records and on the normal's
   if (o.clip) fetch_rows(tumor, t.csup, [&](auto rows, auto n) { return bk_clip_support(ctx, ctx, qual, min_clip, w, rows, n); });
   if (o.clip && normal.ctx) fetch_rows(tumor, t.csup_normal, [&](auto rows, auto n) { return bk_clip_support(ctx, normal.ctx, qual, min_clip, w, rows, n); });
@@ -1366,11 +1368,58 @@ static PartnerMap locus_partners(const Options &o, const Sample &tumor, const Sa
   return partners;
 }
 
+// ---- -fragsize: the fragment lengths the member pairs of every written call imply across its junction ---------------------------------
+// One site per BK_STAGE_CLUSTERS row, as bk_fragment_sizes wants them: a written call gets its voted positions and the sides -vcf prints,
+// every other row is skipped.  The bounds are bk_fragment_bounds of the run's own insert sizes.
+static FragsizeMap fragment_sizes(const Options &o, const Sample &tumor, const CallTables &t, const vector<OutRow> &rows, const Run &run)
+{
+  FragsizeMap frags;
+  int32_t lo = 0, hi = 0;
+  if (bk_fragment_bounds(run.mean, run.sd, &lo, &hi) != BK_OK) die(tumor, BK_ERR_ARG);
+  vector<struct bk_frag_site> sites(t.cnt);
+  for (struct bk_frag_site &s : sites)
+  {
+    s = bk_frag_site{};
+    s.skip = 1;
+  }
+  vector<uint64_t> site_call;
+  for (const OutRow &r : rows)
+  {
+    if (!call_written(r, o.all)) continue;
+    if (r.idx >= t.jsup.size() || r.idx >= sites.size())
+    {
+      std::cerr << "Error: the evidence tables do not cover every call" << std::endl;
+      exit(1);
+    }
+    uint8_t right[2] = {0, 1}, source = 0;
+    bk_junction_sides(&t.jsup[r.idx], &right[0], &right[1], &source);
+    struct bk_frag_site &s = sites[r.idx];
+    s.pos1 = r.c.p1_exact, s.pos2 = (uint32_t) r.c.p2_exact;
+    s.right1 = right[0], s.right2 = right[1];
+    s.skip = 0;
+    site_call.push_back(r.idx);
+  }
+  const struct bk_frag_sizes *res = nullptr;
+  const int rc = bk_fragment_sizes(tumor.ctx, sites.data(), sites.size(), lo, hi, &res);
+  if (rc != BK_OK) die(tumor, rc);
+  uint64_t used = 0, off = 0, lost = 0;
+  for (const uint64_t idx : site_call)
+  {
+    FragsizeCall &c = frags[idx];
+    c.f = res[idx];
+    c.mean = run.mean, c.sd = run.sd;
+    used += c.f.n_used, off += c.f.n_off, lost += c.f.n_lost;
+  }
+  if (lost) std::cerr << "Warning: -fragsize found no record for " << lost << " pair rows; they are left out of the lengths" << std::endl;
+  std::cout << "fragsize: " << site_call.size() << " calls, " << used << " pairs used, " << off << " off the junction's sides, library " << lo << "-" << hi << std::endl;
+  return frags;
+}
+
 // ---- the files behind the tables ---------------------------------------------------------------------------------------------------
 // -vcf: <prefix>_fusion.vcf, and with -clip <prefix>_fusion_rescued.vcf
 static void write_vcf_files(const Options &o, const Sample &tumor, const CallTables &t, const vector<OutRow> &rows, const Rescued &rescued, const ConsensusMap &cons,
                             const HomologyMap &hom, const SimilarMap &sim, const CoverageMap &cov, const FrameMap &frame, const LinkMap &link,
-                            const PartnerMap &partners)
+                            const PartnerMap &partners, const FragsizeMap &frags)
 {
   VcfInput vi;
   vi.nt = tumor.nt;
@@ -1392,6 +1441,7 @@ static void write_vcf_files(const Options &o, const Sample &tumor, const CallTab
   vi.frame = o.frame ? &frame : nullptr;
   vi.link = o.link ? &link : nullptr;
   vi.partners = o.partners ? &partners : nullptr;
+  vi.frags = o.fragsize ? &frags : nullptr;
   auto write = [&](const string &path, const vector<OutRow> &calls) {
     if (write_vcf(path, calls, vi)) return;
     std::cerr << "Error: cannot write " << path << ": the evidence tables do not cover every call" << std::endl;
@@ -1408,6 +1458,7 @@ static void write_vcf_files(const Options &o, const Sample &tumor, const CallTab
   vi.frame = nullptr;                  // ... and with -frame
   vi.link = nullptr;                   // ... and with -link
   vi.partners = nullptr;               // ... and with -partners
+  vi.frags = nullptr;                  // ... and with -fragsize
   vi.rescued = &rescued.calls;
   write(o.out_file + "_fusion_rescued.vcf", rescued.rows);
 }
@@ -1461,6 +1512,7 @@ static void write_params(const Options &o, double w)
   if (o.frame) p << "frame" << std::endl;
   if (o.link) p << "link_max_dist\t" << o.linkdist << std::endl;
   if (o.partners) p << "partners" << std::endl;
+  if (o.fragsize) p << "fragsize" << std::endl;
 }
 
 // BreakID.cc:175-191.  scan_pairs_count and after_cluster_count are never updated by the reference (always 0);
@@ -1540,10 +1592,12 @@ int main(int argc, char *argv[])
   if (o.link) links = link_calls(o, tumor, tables, rows);
   PartnerMap partners;
   if (o.partners) partners = locus_partners(o, tumor, normal, rows, run.w);
+  FragsizeMap frags;
+  if (o.fragsize) frags = fragment_sizes(o, tumor, tables, rows, run);
 
   if (o.clip) write_rescued_tables(o, rescued, tables);
-  write_fusion_tables(o, rows, fusion_twins(o, tables, consensus.sides, homology, similar, coverage, frames, links, partners));
-  if (o.vcf) write_vcf_files(o, tumor, tables, rows, rescued, consensus.sides, homology, similar, coverage, frames, links, partners);
+  write_fusion_tables(o, rows, fusion_twins(o, tables, consensus.sides, homology, similar, coverage, frames, links, partners, frags));
+  if (o.vcf) write_vcf_files(o, tumor, tables, rows, rescued, consensus.sides, homology, similar, coverage, frames, links, partners, frags);
   if (o.evidence) write_evidence_files(o, tumor, tables, rows, rescued);
   write_params(o, run.w);
   const clock_t end = clock();

@@ -45,6 +45,9 @@ int bk_link_calls(bk_ctx *ctx, const struct bk_link_site *sites, uint64_t n, uin
 // -partners (where the discordant pairs inside the windows of a call point to, and the windows of a call)
 int bk_locus_partners(bk_ctx *ctx, const struct bk_partner_site *sites, uint64_t n, uint32_t max_gap, const struct bk_locus_partners **out) __attribute__((weak));
 int bk_call_partner_sites(const bk_cluster *c, double w, struct bk_partner_site out[2]) __attribute__((weak));
+// -fragsize (the fragment lengths the member pairs imply across a junction, and the library's bounds)
+int bk_fragment_sizes(bk_ctx *ctx, const struct bk_frag_site *sites, uint64_t n, int32_t lo, int32_t hi, const struct bk_frag_sizes **out) __attribute__((weak));
+int bk_fragment_bounds(double mean, double sd, int32_t *lo, int32_t *hi) __attribute__((weak));
 // -dedup
 int bk_unique_support(bk_ctx *ctx, const struct bk_unique_support **out, uint64_t *count, const uint64_t **first, uint64_t *n_rows) __attribute__((weak));
 // -clip (the soft-clip evidence, the depth at the rescued positions and the rescue rule)
@@ -95,14 +98,15 @@ static const char *HELP =
      \t -frame     \t 5' / 3' partner and reading frame of every call over all pairs of transcripts at its breakpoints (twin files *_frame.txt; FRCLASS / FR5P / FR3P with -vcf)  \n \
      \t -link      \t reciprocal partner, duplicates and event of every call among all voted calls (twin files *_link.txt; EVENT / PARID with -vcf)  \n \
      \t -linkdist  \t bases up to which two breakpoints count as one region, 0 to 1000000 (with -link)  [1000]\n \
-     \t -partners  \t where the discordant pairs inside the two windows of every call point to: ends, ends to the partner window, loci elsewhere and the largest of them (twin files *_partners.txt; PTN / PTP / PTL with -vcf)  \n ";
+     \t -partners  \t where the discordant pairs inside the two windows of every call point to: ends, ends to the partner window, loci elsewhere and the largest of them (twin files *_partners.txt; PTN / PTP / PTL with -vcf)  \n \
+     \t -fragsize  \t the fragment lengths the discordant pairs of every call imply across its junction, against the library's insert sizes (twin files *_fragsize.txt; FGN / FGMEAN / FGZ with -vcf)  \n ";
 
 struct Options
 {
   std::string inp_file, out_file, nib_dir, normal_file, exclude_file, build = "hg19";
   int qual = 20, device = 0, n_gpus = 0, transport = BK_TRANSPORT_AUTO;  // -gpus N: one sample over N GPUs (include/breakid_multi.h)
   bool fast = false, all = false;                                        // -all: no gene-pair and repeat filter (the _fusion_all files)
-  bool genotype = false, vcf = false, evidence = false, clip = false, dedup = false, consensus = false, homology = false, similar = false, coverage = false, frame = false, link = false, partners = false;
+  bool genotype = false, vcf = false, evidence = false, clip = false, dedup = false, consensus = false, homology = false, similar = false, coverage = false, frame = false, link = false, partners = false, fragsize = false;
   bool anchor_given = false, minclip_given = false, clipsupport_given = false, conslen_given = false, homshift_given = false, homins_given = false, simflank_given = false, covflank_given = false, linkdist_given = false;
   long anchor = 10;                      // -anchor: bases a reference read must cover on either side of the breakpoint base
   long min_clip = 10, clip_support = 3;  // -minclip: shortest clip that counts; -clipsupport: reads at one position a rescued side needs
@@ -152,6 +156,7 @@ static void check_options(const Options &o)
   const Feature frame{"-frame", o.frame, false, bk_fusion_frame && bk_junctions && bk_junction_sides};
   const Feature link{"-link", o.link, false, bk_link_calls && bk_junctions && bk_junction_sides};
   const Feature partners{"-partners", o.partners, false, bk_locus_partners && bk_call_partner_sites};
+  const Feature fragsize{"-fragsize", o.fragsize, false, bk_fragment_sizes && bk_fragment_bounds && bk_junctions && bk_junction_sides};
   const Feature consensus{"-consensus", o.consensus, false, bk_clip_consensus && bk_clip_reads && bk_evidence && bk_junctions && bk_junction_sides};
   const Feature clip{"-clip", o.clip, false, bk_clip_support && bk_clip_reads && bk_base_depth && bk_clip_rescue && bk_junctions && bk_junction_sides};
   const Feature exclude{"-x", o.exclude(), true, bk_exclude_regions && bk_multi_run_ex && bk_multi_run_bam_ex && bk_multi_excluded};
@@ -188,6 +193,7 @@ static void check_options(const Options &o)
       rule(o.linkdist_given && !o.link, "-linkdist needs -link."), gpus(link),
       rule(o.link && !in_range(o.linkdist, 0, 1000000), "-linkdist must be a number from 0 to 1000000."), library(link),
       gpus(partners), library(partners),
+      gpus(fragsize), library(fragsize),
   };
   for (const Refusal &r : refusals)
   {
@@ -212,7 +218,7 @@ static Options parse_options(int argc, char *argv[])
                                      {"minclip", 1, 0, 18}, {"clipsupport", 1, 0, 19}, {"dedup", 0, 0, 20}, {"consensus", 0, 0, 21},
                                      {"conslen", 1, 0, 22}, {"homology", 0, 0, 23}, {"homshift", 1, 0, 24}, {"homins", 1, 0, 25},
                                      {"similar", 0, 0, 26}, {"simflank", 1, 0, 27}, {"coverage", 0, 0, 28}, {"covflank", 1, 0, 29}, {"frame", 0, 0, 30},
-                                     {"link", 0, 0, 31}, {"linkdist", 1, 0, 32}, {"partners", 0, 0, 33},
+                                     {"link", 0, 0, 31}, {"linkdist", 1, 0, 32}, {"partners", 0, 0, 33}, {"fragsize", 0, 0, 34},
                                      {"f", 0, 0, 5},  // (-f used to complete to -fast alone; it still means it beside -frame)
                                      {0, 0, 0, 0}};
   Options o;
@@ -260,6 +266,7 @@ static Options parse_options(int argc, char *argv[])
     case 31: o.link = true; break;
     case 32: number(o.linkdist, o.linkdist_given); break;
     case 33: o.partners = true; break;
+    case 34: o.fragsize = true; break;
     default: std::cerr << "Error: cannot parse arguments.\n"; exit(1);
     }
   }

@@ -369,6 +369,36 @@ struct PartnerCall
     return ";PTN=" + std::to_string(tumor[side].ends) + ";PTP=" + std::to_string(tumor[side].to_partner) + ";PTL=" + std::to_string(tumor[side].loci);
   }
 };
+// -fragsize: the twin files' columns (bk_fragment_sizes on the call's voted positions, against the library's mean and sd)
+static const char *FRAGSIZE_COLUMNS = "\tFg_N\tFg_Off\tFg_Mean\tFg_Dev\tFg_Min\tFg_Max\tFg_Short\tFg_Long\tFg_Z";
+struct FragsizeCall
+{
+  struct bk_frag_sizes f;
+  double mean = 0, sd = 0;  // of the library (bk_isize_stats)
+  string mean_text() const { return f.n_used ? number("%.1f", (double) f.sum / (double) f.n_used) : "."; }
+  string z_text() const { return f.n_used && sd != 0 ? number("%.2f", ((double) f.sum / (double) f.n_used - mean) / sd) : "."; }
+  static string number(const char *format, double v)
+  {
+    char buf[64];
+    snprintf(buf, sizeof buf, format, v);
+    return buf;
+  }
+  string fields() const
+  {
+    std::ostringstream o;
+    o << "\t" << f.n_used << "\t" << f.n_off << "\t" << mean_text() << "\t" << (f.n_used ? number("%.1f", (double) f.abs_dev / (double) f.n_used) : ".") << "\t"
+      << (f.n_used ? std::to_string(f.min) : ".") << "\t" << (f.n_used ? std::to_string(f.max) : ".") << "\t" << f.n_short << "\t" << f.n_long << "\t" << z_text();
+    return o.str();
+  }
+  // what both breakends of the call end their INFO with
+  string info() const
+  {
+    string s = ";FGN=" + std::to_string(f.n_used);
+    if (mean_text() != ".") s += ";FGMEAN=" + mean_text();
+    if (z_text() != ".") s += ";FGZ=" + z_text();
+    return s;
+  }
+};
 // -clip -normal: what _fusion_rescued_normal.txt adds to a row of _fusion_rescued.txt
 static const char *RESCUED_COLUMNS_NORMAL = "\tNormal_DRP\tNormal_ClipAt1\tNormal_ClipAt2\tNormal_Depth1\tNormal_Depth2";
 
@@ -397,6 +427,7 @@ using CoverageMap = std::map<uint64_t, CoverageCall>;
 using FrameMap = std::map<uint64_t, FrameCall>;
 using LinkMap = std::map<uint64_t, LinkCall>;  // every voted call, whichever files hold it
 using PartnerMap = std::map<uint64_t, PartnerCall>;
+using FragsizeMap = std::map<uint64_t, FragsizeCall>;
 
 // -clip: the rescued clusters in the order of _fusion_rescued.txt, calls[k] to rows[k]; with -evidence the clipped reads at the peaks
 // of the written ones (bk_clip_reads: the rows of sites 2 * j and 2 * j + 1 belong to the j-th written row)
@@ -438,7 +469,8 @@ struct Twin
 
 // The twins of this run, the reference's own two files first.  An option that adds columns to the calls adds its entry here.
 static vector<Twin> fusion_twins(const Options &o, const CallTables &t, const ConsensusMap &cons, const HomologyMap &hom, const SimilarMap &sim,
-                                 const CoverageMap &cov, const FrameMap &frame, const LinkMap &link, const PartnerMap &partners)
+                                 const CoverageMap &cov, const FrameMap &frame, const LinkMap &link, const PartnerMap &partners,
+                                 const FragsizeMap &frags)
 {
   const bool with_normal = o.with_normal();  // (a tumour without calls still gets header-only twins)
   vector<Twin> twins;
@@ -518,6 +550,12 @@ static vector<Twin> fusion_twins(const Options &o, const CallTables &t, const Co
                        tail = PartnerCall::fields(c.tumor, c.top_chr) + (with_normal ? PartnerCall::fields(c.normal, c.normal_top_chr) : "");
                        return true;
                      }});
+  if (o.fragsize)
+    twins.push_back({"_fragsize", FRAGSIZE_COLUMNS, [&frags](const OutRow &r, string &tail) {
+                       if (!frags.count(r.idx)) return false;
+                       tail = frags.at(r.idx).fields();
+                       return true;
+                     }});
   return twins;
 }
 
@@ -595,6 +633,8 @@ struct VcfInput
   const LinkMap *link = nullptr;
   // -partners (else null; never for the rescued clusters): PTN / PTP / PTL of its own side on every breakend of a call, behind everything else
   const PartnerMap *partners = nullptr;
+  // -fragsize (else null; never for the rescued clusters): FGN, and FGMEAN / FGZ where the columns have a value, on both breakends, behind everything else
+  const FragsizeMap *frags = nullptr;
 };
 
 static char nib_base(const string &nib_dir, const string &chr, long pos1)  // the base at a 1-based position; N without a file or beyond it
@@ -718,6 +758,7 @@ static bool write_vcf(const string &path, const vector<OutRow> &rows, const VcfI
           o << lk.info(s, lk.l.mate >= 0 && in_file.count(lk.mate_row));
         }
         if (in.partners && in.partners->count(r.idx)) o << in.partners->at(r.idx).info(s);
+        if (in.frags && in.frags->count(r.idx)) o << in.frags->at(r.idx).info();
         o << "\t" << (in.gsup ? "GT:GQ:DR:DV:RR:RV" : "DV:RV") << "\t" << vcf_sample(r.c.n_drp, r.c.n_sr, in.gsup ? &(*in.gsup)[r.idx] : nullptr, s);
         if (in.with_normal) o << "\t" << vcf_sample(in.nsup[r.idx].n_drp, in.nsup[r.idx].n_sr, in.gsup_normal ? &(*in.gsup_normal)[r.idx] : nullptr, s);
       }
@@ -780,6 +821,10 @@ static bool write_vcf(const string &path, const vector<OutRow> &rows, const VcfI
     v << "##INFO=<ID=PTN,Number=1,Type=Integer,Description=\"Ends of discordant pairs inside the window of this side of the call\">\n"
          "##INFO=<ID=PTP,Number=1,Type=Integer,Description=\"Those whose mate lies inside the window of the other side\">\n"
          "##INFO=<ID=PTL,Number=1,Type=Integer,Description=\"Loci elsewhere that the mates of the others fall into\">\n";
+  if (in.frags && !in.rescued)
+    v << "##INFO=<ID=FGN,Number=1,Type=Integer,Description=\"Discordant pairs whose implied fragment length across the junction was computed\">\n"
+         "##INFO=<ID=FGMEAN,Number=1,Type=Float,Description=\"Mean fragment length those pairs imply across the junction\">\n"
+         "##INFO=<ID=FGZ,Number=1,Type=Float,Description=\"That mean less the library's mean insert size, in units of the library's sd\">\n";
   if (in.rescued) v << "##INFO=<ID=SC,Number=1,Type=Integer,Description=\"Soft-clipped reads without an SA tag that end at this position (the clip peak)\">\n";
   if (in.gsup)
     v << "##FORMAT=<ID=GT,Number=1,Type=String,Description=\"Genotype\">\n"

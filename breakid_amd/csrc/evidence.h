@@ -47,6 +47,7 @@ struct EvidenceStat
 
 // Rows in their final order (include/breakid_hip.h) in *rows_out, call_off_out[ncl + 1] over the rows of `cl` (BK_STAGE_CLUSTERS
 // order: bp.hip, cluster_summary), both device arrays owned by `b`.  *stat_out: device, one entry.  keys != nullptr: the fragment
-// keys as well (above).
+// keys as well (above).  pairs_only: the BK_EV_PAIR rows alone, same order, packed, so that *call_off_out bounds a call's pair rows;
+// the tuples are counted (junctions()) but not listed.
 void evidence(const JunctionPairs &p, const TupleTable &tt, const bk_cluster *cl, uint64_t ncl, const EvidenceRecs &recs, EvidenceBufs &b, hipStream_t st,
-              struct bk_evidence **rows_out, uint64_t **call_off_out, EvidenceStat **stat_out, EvidenceKeys *keys = nullptr);
+              struct bk_evidence **rows_out, uint64_t **call_off_out, EvidenceStat **stat_out, EvidenceKeys *keys = nullptr, bool pairs_only = false);

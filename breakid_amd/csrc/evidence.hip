@@ -232,7 +232,7 @@ __global__ __launch_bounds__(256) void k_ev_emit_splits(TupleTable tt, const bk_
 }  // namespace
 
 void evidence(const JunctionPairs &p, const TupleTable &tt, const bk_cluster *cl, uint64_t ncl, const EvidenceRecs &recs, EvidenceBufs &b, hipStream_t st,
-              struct bk_evidence **rows_out, uint64_t **call_off_out, EvidenceStat **stat_out, EvidenceKeys *keys)
+              struct bk_evidence **rows_out, uint64_t **call_off_out, EvidenceStat **stat_out, EvidenceKeys *keys, bool pairs_only)
 {
   uint64_t *call_off = b.call_off.as<uint64_t>(ncl + 1);
   EvidenceStat *stat = b.stat.as<EvidenceStat>(1);
@@ -255,12 +255,17 @@ void evidence(const JunctionPairs &p, const TupleTable &tt, const bk_cluster *cl
   const uint32_t n32 = (uint32_t) ncl;
   struct bk_junction *res;
   uint32_t *vis;
-  junctions(p, tt, cl, ncl, b.jn, st, &res, &vis);
+  junctions(p, tt, cl, ncl, b.jn, st, &res, &vis, pairs_only);
   // every call's counts and the two scans
   uint64_t *cnt = b.cnt.as<uint64_t>(ncl + 1), *npair = b.npair.as<uint64_t>(ncl + 1), *pair_off = b.pair_off.as<uint64_t>(ncl + 1);
   hipLaunchKernelGGL(k_ev_counts, dim3(cdiv(ncl, 256)), dim3(256), 0, st, res, n32, cnt, npair);
   prims::exclusive_scan<uint64_t>(cnt, call_off, ncl, b.scan_tmp, st);
   prims::exclusive_scan<uint64_t>(npair, pair_off, ncl, b.scan_tmp, st);
+  if (pairs_only)  // the pair rows alone, packed: a call's range of rows is its range of sorted list entries
+  {
+    call_off = pair_off;
+    *call_off_out = pair_off;
+  }
   uint64_t total = 0;
   HIP_CHECK(hipMemcpyAsync(&total, call_off + ncl, 8, hipMemcpyDeviceToHost, st));
   HIP_CHECK(hipStreamSynchronize(st));  // the row count sizes the output
@@ -284,5 +289,5 @@ void evidence(const JunctionPairs &p, const TupleTable &tt, const bk_cluster *cl
     prims::radix_sort_pairs(keys, vals, p.n, 0, bits, b.radix, st, &keys, &vals);
     hipLaunchKernelGGL(k_ev_emit_pairs, dim3(cdiv(p.n, 256)), dim3(256), 0, st, p, keys, vals, n32, call_off, pair_off, recs, rows, total, stat, kw);
   }
-  hipLaunchKernelGGL(k_ev_emit_splits, dim3(cdiv(ncl, 4)), dim3(256), 0, st, tt, cl, n32, call_off, pair_off, recs, rows, total, stat, kw);
+  if (!pairs_only) hipLaunchKernelGGL(k_ev_emit_splits, dim3(cdiv(ncl, 4)), dim3(256), 0, st, tt, cl, n32, call_off, pair_off, recs, rows, total, stat, kw);
 }

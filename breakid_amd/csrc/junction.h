@@ -21,6 +21,7 @@ struct JunctionPairs
 };
 
 // out[c] = the junction evidence of cluster c, row c of `cl` (BK_STAGE_CLUSTERS order: bp.hip, cluster_summary); visited_out[c] =
-// tuples its wave searched (the byte model).  Device arrays of ncl entries owned by `b`.
+// tuples its wave searched (the byte model).  Device arrays of ncl entries owned by `b`.  pairs_only: the member pairs alone are
+// counted, no tuple is searched (splits and visited stay 0).
 void junctions(const JunctionPairs &p, const TupleTable &tt, const bk_cluster *cl, uint64_t ncl, JunctionBufs &b, hipStream_t st, struct bk_junction **out,
-               uint32_t **visited_out);
+               uint32_t **visited_out, bool pairs_only = false);

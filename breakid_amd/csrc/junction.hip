@@ -96,7 +96,7 @@ __global__ __launch_bounds__(256) void k_junction_sr(TupleTable tt, const bk_clu
 }  // namespace
 
 void junctions(const JunctionPairs &p, const TupleTable &tt, const bk_cluster *cl, uint64_t ncl, JunctionBufs &b, hipStream_t st, struct bk_junction **out,
-               uint32_t **visited_out)
+               uint32_t **visited_out, bool pairs_only)
 {
   struct bk_junction *res = b.res.as<struct bk_junction>(ncl + 1);
   uint32_t *visited = b.visited.as<uint32_t>(ncl + 1);
@@ -106,5 +106,8 @@ void junctions(const JunctionPairs &p, const TupleTable &tt, const bk_cluster *c
   if (ncl > 0x7FFFFFFFull) throw bk_error(BK_ERR_LIMIT, "too many clusters");
   HIP_CHECK(hipMemsetAsync(res, 0, ncl * sizeof(struct bk_junction), st));
   if (p.n) hipLaunchKernelGGL(k_junction_pairs, dim3(cdiv(p.n, 256)), dim3(256), 0, st, p, (uint32_t) ncl, res);
-  hipLaunchKernelGGL(k_junction_sr, dim3(cdiv(ncl, 4)), dim3(256), 0, st, tt, cl, (uint32_t) ncl, res, visited);
+  if (pairs_only)  // (no tuple is looked at: the split counts stay 0)
+    HIP_CHECK(hipMemsetAsync(visited, 0, ncl * sizeof(uint32_t), st));
+  else
+    hipLaunchKernelGGL(k_junction_sr, dim3(cdiv(ncl, 4)), dim3(256), 0, st, tt, cl, (uint32_t) ncl, res, visited);
 }

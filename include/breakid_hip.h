@@ -810,6 +810,55 @@ int bk_locus_partners(bk_ctx *ctx, const struct bk_partner_site *sites, uint64_t
  * argument. */
 int bk_call_partner_sites(const bk_cluster *c, double w, struct bk_partner_site out[2]);   /* pure host function */
 
+/* ---- fragment sizes: the fragment lengths the member pairs imply across each junction ------------------------------------------------
+ * A pair supports a junction physically when the fragment, read through the junction, has a length the library could have produced:
+ * the bases from read 1 to breakpoint 1 plus the bases from breakpoint 2 to read 2.  All arithmetic is signed 64-bit.
+ * n must equal the number of BK_STAGE_CLUSTERS rows; site c belongs to call c.  A site with skip != 0 gives an all-zero row.  Otherwise
+ * the rows of call c are its BK_EV_PAIR rows of bk_evidence, same membership and order, voted or not: the call works for any cluster
+ * row a caller has positions for.  For one such row take (T_s, P_s, F_s) = (tid_s, pos_s, flag_s) for side s = 1, 2 and H = its qhash.
+ *   off       the row is off when ((F_s & 0x10) != 0) != (right_s != 0) on either side: the read does not lie on the side of the
+ *             breakpoint that the site keeps.  An off row is never looked up.
+ *   lookup    R_s = the smallest index i of the context's record table with tid[i] == T_s, pos[i] == P_s - 1, flag[i] == F_s and
+ *             qhash[i] == H (the qhash from the bk_side row where the table has them).  The mate join builds both sides from records
+ *             of this table, so R_s exists; a row without one is lost and counted, never guessed.
+ *   end       E_s = bam_endpos of R_s: pos + the reference length of its M, D, N, =, X operations, pos + 1 without a CIGAR (or with
+ *             flag 0x4, as htslib has it).  Read as a 1-based coordinate it is the last aligned base.
+ *   retained  the breakpoint base is retained on both kinds of side, as -consensus and -link read it:
+ *             right_s == 0: a_s = site.pos_s - P_s + 1;   otherwise: a_s = E_s - site.pos_s + 1.
+ *   length    L = a_1 + a_2, clamped to [-2^31 + 1, 2^31 - 1].  a_s may be negative when a read lies beyond the breakpoint; it is taken
+ *             as it is.
+ * Per call, over the used rows (neither off nor lost): n_used; n_short counts L < lo and n_long counts L > hi; min and max (both 0
+ * without a used row); sum; abs_dev = the sum of |L - centre| with centre = floor((2 sum + n_used) / (2 n_used)), the floor towards
+ * minus infinity.  n_used + n_off + n_lost equals the call's pair rows.
+ * Limit: positions are aligned coordinates, so soft-clipped bases are not added back (as for bk_unique_support): a clipped read's
+ * fragment reads short by its clip on the outer end.
+ * Hand example: a library of mean 350 and sd 40 (bk_fragment_bounds: lo = 230, hi = 470); the site (pos1 = 10000, right1 = 0 | pos2 =
+ * 50000, right2 = 1); four pairs whose read 1 is forward and starts at 9801, 9851, 9901, 9951.  Their mates: reverse at 50101 with
+ * 100M (E = 50200); reverse at 50051 with 50M10D50M (E = 50160); reverse at 49991 with 40S60M (E = 50050); forward at 50201.  The
+ * lengths are 200 + 201 = 401, 150 + 161 = 311 and 100 + 51 = 151; the fourth row is off.  So n_used = 3, n_off = 1, n_short = 1,
+ * n_long = 0, min = 151, max = 401, sum = 863, centre = floor(1729 / 6) = 288, abs_dev = 113 + 23 + 137 = 273.
+ * Every output is a count, an extreme or an integer sum: two runs give the same bytes.  The structs have no typedef. */
+struct bk_frag_site  { uint32_t pos1, pos2; uint8_t right1, right2, skip; uint8_t reserved[5]; };   /* 16 bytes; pos 1-based; reserved = 0 */
+struct bk_frag_sizes { uint32_t n_used, n_off, n_lost, n_short, n_long; int32_t min, max; uint32_t reserved; int64_t sum; uint64_t abs_dev; };  /* 48 bytes */
+/* ctx, call order, table forms, shards and lifetime: as for bk_unique_support.  It runs after bk_split_breakpoints, needs no earlier
+ * bk_evidence call, and leaves bk_evidence's buffers and every later bk_fetch unchanged.  sites: host memory.  *out (n rows) is
+ * library-owned until the next bk_fragment_sizes or bk_free(ctx).  BK_ERR_ARG (with the reason in bk_last_error) for null arguments
+ * (sites may be null when n == 0), n != the cluster count, lo > hi, a non-zero reserved, right* or skip above 1, shards and wrong
+ * call order.  A context without clusters with n == 0 is no error.
+ * How: the pair rows are listed per call as bk_unique_support lists them (the split rows are left out); one lane per (row, side)
+ * finds the side's first record of equal (tid, pos) by a binary search over the sampled keys of every 1024th record and then the
+ * stride, and walks the records of that position for flag and hash, 8 on its own, the rest by its whole wavefront 64 a step; one
+ * wavefront per call reduces its rows in two passes.
+ * bk_timing: scope `fragment_sizes`.  bk_timing_touched: per member pair what bk_evidence's listing reads and sorts; per pair row its
+ * 48-byte row written and read and its 8-byte length written and read twice (120 bytes); per looked-up record ten probes of tid and
+ * pos in its stride (80 bytes), per record its walk reads tid, pos, flag and hash (18 bytes), and per used side its two CIGAR offsets
+ * (8 bytes); per site its 16 bytes, its two offsets and its 48-byte row (80 bytes).  The probes of the sampled keys (cache
+ * resident) and the CIGAR words are not modelled. */
+int bk_fragment_sizes(bk_ctx *ctx, const struct bk_frag_site *sites, uint64_t n, int32_t lo, int32_t hi, const struct bk_frag_sizes **out);
+/* The library's bounds, a pure host function (no context, no GPU): lo = max(0, floor(mean - 3 sd)), hi = ceil(mean + 3 sd), both
+ * clamped to int32.  Returns BK_OK, or BK_ERR_ARG for a null pointer, a non-finite value or sd < 0. */
+int bk_fragment_bounds(double mean, double sd, int32_t *lo, int32_t *hi);   /* pure host function */
+
 /* Copy a stage's result to library-owned host memory.  *data stays valid until the next bk_fetch
  * of the same stage or bk_free.  group_off (may be NULL) receives n_groups+1 offsets for pair stages. */
 int bk_fetch(bk_ctx *ctx, int stage, const void **data, uint64_t *count, const uint64_t **group_off, uint32_t *n_groups);
