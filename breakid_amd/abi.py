@@ -74,6 +74,15 @@ assert PARTNER_SITE.itemsize == 32 and LOCUS_PARTNERS.itemsize == 32
 FRAG_SITE = np.dtype([("pos1", "<u4"), ("pos2", "<u4"), ("right1", "u1"), ("right2", "u1"), ("skip", "u1"), ("reserved", "u1", (5,))])  # struct bk_frag_site; pos 1-based
 FRAG_SIZES = np.dtype([("n_used", "<u4"), ("n_off", "<u4"), ("n_lost", "<u4"), ("n_short", "<u4"), ("n_long", "<u4"), ("min", "<i4"), ("max", "<i4"), ("reserved", "<u4"), ("sum", "<i8"), ("abs_dev", "<u8")])  # struct bk_frag_sizes
 assert FRAG_SITE.itemsize == 16 and FRAG_SIZES.itemsize == 48
+KNOWN_ENTRY = np.dtype([("tid1", "<i4"), ("beg1", "<u4"), ("end1", "<u4"), ("tid2", "<i4"), ("beg2", "<u4"), ("end2", "<u4"), ("name", "<u4"), ("score", "<i4"),
+                        ("strand1", "u1"), ("strand2", "u1"), ("reserved", "u1", (6,))])  # struct bk_known_entry; [beg, end) 0-based
+KNOWN_SITE = np.dtype([("tid1", "<i4"), ("pos1", "<u4"), ("tid2", "<i4"), ("pos2", "<u4"), ("right1", "u1"), ("right2", "u1"), ("reserved", "u1", (6,))])  # struct bk_known_site; pos 1-based
+KNOWN_CALL = np.dtype([("n_hits", "<u4"), ("n_oriented", "<u4"), ("n_opposed", "<u4"), ("n_names", "<u4"), ("n_side", "<u4", (2,)), ("best", "<i4"), ("best_score", "<i4"),
+                       ("best_dist", "<u4"), ("best_crossed", "u1"), ("best_oriented", "u1"), ("reserved", "u1", (2,))])  # struct bk_known_call
+assert KNOWN_ENTRY.itemsize == 40 and KNOWN_SITE.itemsize == 24 and KNOWN_CALL.itemsize == 40
+KNOWN_MAX_SLOP = 1000000  # BK_KNOWN_MAX_SLOP
+KNOWN_NO_SCORE = -2147483648  # BK_KNOWN_NO_SCORE
+STRAND_NONE, STRAND_LEFT, STRAND_RIGHT = 0, 1, 2  # BK_STRAND_*
 # the columns of a bk_txmodel, in the struct's order (ex_off has n_tx + 1 entries, ex_start / ex_end n_parts)
 TXMODEL_COLS = [("tid", np.int32), ("tx_start", np.uint32), ("tx_end", np.uint32), ("strand", np.uint8), ("ex_off", np.uint32), ("ex_start", np.uint32), ("ex_end", np.uint32)]
 # the columns of a bk_refseq table, in the struct's order (off has n_segs + 1 entries)

@@ -25,6 +25,7 @@
 #include "link.h"
 #include "partners.h"
 #include "fragsize.h"
+#include "known.h"
 #include "exclude.h"
 #include "ahc.h"
 #include "lanes.h"
@@ -178,6 +179,9 @@ struct bk_ctx
   // fragment sizes (bk_fragment_sizes)
   FragBufs fgb;
   std::vector<struct bk_frag_sizes> f_fragsize;
+  // known junctions (bk_known_calls)
+  KnownBufs knb;
+  std::vector<struct bk_known_call> f_known;
 
   // test hooks of the primitives (bk_debug_scan, bk_debug_radix_sort): buffers that live as long as the context, as a stage's do
   prims::RadixBufs dbg_radix;
@@ -1706,6 +1710,84 @@ int bk_fragment_bounds(double mean, double sd, int32_t *lo, int32_t *hi)
   *lo = clamp(a < 0 ? 0.0 : a);
   *hi = clamp(b);
   return BK_OK;
+}
+
+// Every call against a panel of pairs of intervals (include/breakid_hip.h).
+int bk_known_calls(bk_ctx *ctx, const struct bk_known_entry *entries, uint64_t n_entries, const struct bk_known_site *sites, uint64_t n, uint32_t slop, const struct bk_known_call **out)
+{
+  return guarded(ctx, [&] {
+    if (!out) throw bk_error(BK_ERR_ARG, "bk_known_calls: null out");
+    if (n && !sites) throw bk_error(BK_ERR_ARG, "bk_known_calls: null sites");
+    if (n_entries && !entries) throw bk_error(BK_ERR_ARG, "bk_known_calls: null entries");
+    if (ctx->shard) throw bk_error(BK_ERR_ARG, "bk_known_calls: sharded contexts (bk_shard_*) are not supported");
+    if (slop > BK_KNOWN_MAX_SLOP) throw bk_error(BK_ERR_ARG, "bk_known_calls: slop above " + std::to_string(BK_KNOWN_MAX_SLOP));
+    if (n > 0x40000000ull) throw bk_error(BK_ERR_LIMIT, "bk_known_calls: more than 2^30 sites");
+    if (n_entries > 0x40000000ull) throw bk_error(BK_ERR_LIMIT, "bk_known_calls: more than 2^30 entries");
+    KnownShape shape;
+    shape.n = n;
+    shape.n_entries = n_entries;
+    for (uint64_t k = 0; k < n; ++k)
+    {
+      if (sites[k].right1 > 1u || sites[k].right2 > 1u) throw bk_error(BK_ERR_ARG, "bk_known_calls: site " + std::to_string(k) + " has a right above 1 (0 = LEFT, 1 = RIGHT)");
+      for (const uint8_t r : sites[k].reserved)
+        if (r) throw bk_error(BK_ERR_ARG, "bk_known_calls: site " + std::to_string(k) + " has a non-zero reserved field");
+    }
+    for (uint64_t k = 0; k < n_entries; ++k)
+    {
+      const struct bk_known_entry &e = entries[k];
+      if (e.strand1 > 2u || e.strand2 > 2u) throw bk_error(BK_ERR_ARG, "bk_known_calls: entry " + std::to_string(k) + " has a strand above 2 (0 = unstated, 1 = LEFT, 2 = RIGHT)");
+      for (const uint8_t r : e.reserved)
+        if (r) throw bk_error(BK_ERR_ARG, "bk_known_calls: entry " + std::to_string(k) + " has a non-zero reserved field");
+      const int32_t tid[2] = {e.tid1, e.tid2};
+      const uint32_t beg[2] = {e.beg1, e.beg2}, end[2] = {e.end1, e.end2};
+      for (int i = 0; i < 2; ++i)
+        if (tid[i] >= 0)
+        {
+          if (end[i] <= beg[i]) throw bk_error(BK_ERR_ARG, "bk_known_calls: entry " + std::to_string(k) + " has an interval with end <= beg");
+          ++shape.m;
+          if (tid[i] > shape.max_tid) shape.max_tid = tid[i];
+        }
+      if (e.name > shape.max_name) shape.max_name = e.name;
+    }
+    KnownBufs &b = ctx->knb;
+    struct bk_known_call *d_res = nullptr;
+    known_upload(entries, n_entries, sites, n, b, ctx->st);  // (outside the scope: it times the work on the device copies)
+    {
+      // (the two scopes inside push timers of their own, so the whole one ends by its index, not at timers.back(); the model needs
+      // the listed hits, which are known once the count has run)
+      struct Whole
+      {
+        bk_ctx *c;
+        size_t at;
+        ~Whole()
+        {
+          if (c->timing && at < c->timers.size()) (void) hipEventRecord(c->timers[at].b, c->st);
+        }
+      } whole{ctx, ctx->timers.size()};
+      ctx->tick("known_calls", 0, true, 0);
+      {
+        Scope s(ctx, "known_calls_index", shape.touched_index(), shape.touched_index());
+        known_index(shape, b, ctx->st);
+      }
+      {
+        const size_t at = ctx->timers.size();
+        Scope s(ctx, "known_calls_sites");
+        const uint64_t hits = known_count(shape, slop, b, ctx->st, &d_res);
+        if (hits > 0xFFFFFFF0ull) throw bk_error(BK_ERR_LIMIT, "bk_known_calls: " + std::to_string(hits) + " listed hits, more than the 2^32 - 16 rows a sort takes");
+        known_names(shape, slop, hits, b, ctx->st);
+        if (ctx->timing && at < ctx->timers.size())
+        {
+          ctx->timers[at].bytes = ctx->timers[at].touched = shape.touched_sites(hits);
+          ctx->timers[whole.at].bytes = ctx->timers[whole.at].touched = shape.touched_index() + shape.touched_sites(hits);
+        }
+        if (bk_debug("known"))
+          fprintf(stderr, "bk_known_calls: %llu sites, %llu entries, %llu intervals with a contig, %u index passes, %llu listed hits, %u name passes\n", (unsigned long long) n,
+                  (unsigned long long) n_entries, (unsigned long long) shape.m, shape.index_passes(), (unsigned long long) hits, shape.name_passes());
+      }
+    }
+    rows_to_host(ctx, d_res, n, ctx->f_known);
+    *out = ctx->f_known.data();
+  });
 }
 
 // The side rule of one call and the ALT text of one breakend (include/breakid_hip.h): pure host code.

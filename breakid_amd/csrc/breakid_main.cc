@@ -233,6 +233,104 @@ static ExcludeList read_exclude_bed(const std::string &path, const std::vector<s
   return x;
 }
 
+// -known panel.bedpe: whitespace-separated fields, 0-based half-open coordinates; chrom1 start1 end1 chrom2 start2 end2, then name,
+// score, strand1 and strand2 where the line has them, further columns ignored.  Blank lines and lines that start with '#', "track" or
+// "browser" are skipped.  Names match the header's exactly: an interval on a contig the header lacks ('.' included) holds nothing
+// (tid -1), and its line is counted; its entry stays, because the other interval can still hold a breakpoint.  Intervals are clamped to
+// the contig's length, and one that lies behind it holds nothing either.  A missing or '.' name is the name "."; name ids ascend in
+// order of first appearance.  The score goes through strtod, is truncated towards zero and clamped to int32; a field that strtod does
+// not consume whole, or NaN, means no score.  Strand '+' is LEFT, '-' is RIGHT, anything else unstated.  Fewer than six fields, a
+// coordinate that is not a number, and on a contig of the header a negative coordinate or end <= start end the run.
+struct KnownPanel
+{
+  vector<struct bk_known_entry> entries;
+  vector<string> names;  // by name id
+  uint64_t unknown = 0;  // lines with a contig that the header lacks
+};
+static KnownPanel read_known_bedpe(const string &path, const char *const *names, const uint32_t *lens, int nt)
+{
+  std::ifstream in(path.c_str());
+  if (!in.is_open())
+  {
+    std::cerr << "Error: can not open known file: " << path << std::endl;
+    exit(1);
+  }
+  std::map<string, int> id;
+  for (int i = 0; i < nt; ++i) id.emplace(names[i], i);
+  std::map<string, uint32_t> name_id;
+  KnownPanel p;
+  string line;
+  uint64_t no = 0;
+  auto fail = [&](const string &why) {
+    std::cerr << "Error: known file " << path << ", line " << no << ": " << why << std::endl;
+    exit(1);
+  };
+  auto number = [&](const string &f) {
+    char *e = nullptr;
+    errno = 0;
+    const long long v = strtoll(f.c_str(), &e, 10);
+    if (f.empty() || *e || errno) fail("not a number: " + f);
+    return v;
+  };
+  auto strand = [](const vector<string> &f, size_t k) { return k < f.size() && f[k] == "+" ? BK_STRAND_LEFT : k < f.size() && f[k] == "-" ? BK_STRAND_RIGHT : BK_STRAND_NONE; };
+  while (std::getline(in, line))
+  {
+    ++no;
+    std::istringstream ss(line);
+    vector<string> f;
+    for (string w; ss >> w;) f.push_back(w);
+    if (f.empty() || f[0][0] == '#' || f[0] == "track" || f[0] == "browser") continue;
+    if (f.size() < 6) fail("fewer than six fields (chrom1 start1 end1 chrom2 start2 end2)");
+    struct bk_known_entry e = {};
+    bool lacking = false;
+    for (int k = 0; k < 2; ++k)
+    {
+      long long b = number(f[3 * k + 1]), x = number(f[3 * k + 2]);
+      int32_t tid = -1;
+      const auto it = id.find(f[3 * k]);
+      if (it == id.end())
+        lacking = true;
+      else
+      {
+        if (b < 0) fail("negative coordinate: " + f[3 * k + 1]);
+        if (x < 0) fail("negative coordinate: " + f[3 * k + 2]);
+        if (x <= b) fail("end <= start");
+        const long long len = lens[it->second];
+        b = std::min(b, len);
+        x = std::min(x, len);
+        if (x > b) tid = it->second;  // (else behind the contig's end)
+      }
+      if (tid < 0) b = x = 0;
+      (k ? e.tid2 : e.tid1) = tid;
+      (k ? e.beg2 : e.beg1) = (uint32_t) b;
+      (k ? e.end2 : e.end1) = (uint32_t) x;
+    }
+    p.unknown += lacking;
+    const string name = f.size() > 6 ? f[6] : string(".");
+    const auto at = name_id.find(name);
+    if (at == name_id.end())
+    {
+      e.name = (uint32_t) p.names.size();
+      name_id.emplace(name, e.name);
+      p.names.push_back(name);
+    }
+    else
+      e.name = at->second;
+    e.score = BK_KNOWN_NO_SCORE;
+    if (f.size() > 7)
+    {
+      char *end = nullptr;
+      const double v = strtod(f[7].c_str(), &end);
+      if (end != f[7].c_str() && !*end && v == v) e.score = v >= 2147483647.0 ? (int32_t) 2147483647 : v <= -2147483648.0 ? (int32_t) (-2147483647 - 1) : (int32_t) v;
+    }
+    e.strand1 = (uint8_t) strand(f, 8);
+    e.strand2 = (uint8_t) strand(f, 9);
+    p.entries.push_back(e);
+  }
+  if (p.unknown) std::cerr << "Warning: " << p.unknown << " lines of the known file " << path << " name contigs that are not in the BAM header" << std::endl;
+  return p;
+}
+
 #ifndef BREAKID_INSTALLDIR
 #define BREAKID_INSTALLDIR "."
 #endif
@@ -715,7 +813,7 @@ static void fetch_call_tables(const Options &o, const Sample &tumor, const Sampl
   if (o.genotype) fetch_rows(tumor, t.gsup, [&](auto rows, auto n) { return bk_ref_support(ctx, ctx, qual, anchor, w, rows, n); });
   if (o.genotype && normal.ctx) fetch_rows(tumor, t.gsup_normal, [&](auto rows, auto n) { return bk_ref_support(ctx, normal.ctx, qual, anchor, w, rows, n); });
   // -vcf: the junction evidence of every call (member pairs by strands, split tuples by clip side)
-  if (o.vcf || o.clip || o.consensus || o.coverage || o.frame || o.link || o.fragsize) fetch_rows(tumor, t.jsup, [&](auto rows, auto n) { return bk_junctions(ctx, rows, n); });
+  if (o.vcf || o.clip || o.consensus || o.coverage || o.frame || o.known() || o.bedpe || o.link || o.fragsize) fetch_rows(tumor, t.jsup, [&](auto rows, auto n) { return bk_junctions(ctx, rows, n); });
   // -clip: the clipped reads without an SA tag at every cluster, voted or not, on the sample's records and on the normal's
   if (o.clip) fetch_rows(tumor, t.csup, [&](auto rows, auto n) { return bk_clip_support(ctx, ctx, qual, min_clip, w, rows, n); });
   if (o.clip && normal.ctx) fetch_rows(tumor, t.csup_normal, [&](auto rows, auto n) { return bk_clip_support(ctx, normal.ctx, qual, min_clip, w, rows, n); });
@@ -1415,11 +1513,50 @@ static FragsizeMap fragment_sizes(const Options &o, const Sample &tumor, const C
   return frags;
 }
 
+// ---- -known: every written call against the panel -----------------------------------------------------------------------------------------
+// One site per written call, with the sides -vcf prints (a call without a side's evidence keeps LEFT, as elsewhere); one call of
+// bk_known_calls answers them all.
+static KnownMap known_calls(const Options &o, const Sample &tumor, const CallTables &t, const vector<OutRow> &rows, const KnownPanel &panel)
+{
+  vector<struct bk_known_site> sites;
+  vector<uint64_t> site_call;
+  for (const OutRow &r : rows)
+  {
+    if (!call_written(r, o.all)) continue;
+    if (r.idx >= t.jsup.size())
+    {
+      std::cerr << "Error: the evidence tables do not cover every call" << std::endl;
+      exit(1);
+    }
+    uint8_t right[2] = {0, 1}, source = 0;
+    bk_junction_sides(&t.jsup[r.idx], &right[0], &right[1], &source);
+    struct bk_known_site s = {};
+    s.tid1 = r.c.p1_tid, s.pos1 = r.c.p1_exact, s.tid2 = r.c.p2_tid, s.pos2 = (uint32_t) r.c.p2_exact;
+    s.right1 = source ? right[0] : 0, s.right2 = source ? right[1] : 0;
+    sites.push_back(s);
+    site_call.push_back(r.idx);
+  }
+  const struct bk_known_call *res = nullptr;
+  const int rc = bk_known_calls(tumor.ctx, panel.entries.data(), panel.entries.size(), sites.data(), sites.size(), (uint32_t) o.knownslop, &res);
+  if (rc != BK_OK) die(tumor, rc);
+  KnownMap known;
+  uint64_t with_hit = 0;
+  for (size_t k = 0; k < sites.size(); ++k)
+  {
+    KnownCall &c = known[site_call[k]];
+    c.k = res[k];
+    if (c.k.best >= 0 && (size_t) c.k.best < panel.entries.size()) c.best_name = panel.names[panel.entries[c.k.best].name];
+    with_hit += c.k.n_hits > 0;
+  }
+  std::cout << "known: " << panel.entries.size() << " entries, " << panel.unknown << " on contigs the input lacks, " << with_hit << " calls with a hit" << std::endl;
+  return known;
+}
+
 // ---- the files behind the tables ---------------------------------------------------------------------------------------------------
 // -vcf: <prefix>_fusion.vcf, and with -clip <prefix>_fusion_rescued.vcf
 static void write_vcf_files(const Options &o, const Sample &tumor, const CallTables &t, const vector<OutRow> &rows, const Rescued &rescued, const ConsensusMap &cons,
                             const HomologyMap &hom, const SimilarMap &sim, const CoverageMap &cov, const FrameMap &frame, const LinkMap &link,
-                            const PartnerMap &partners, const FragsizeMap &frags)
+                            const PartnerMap &partners, const FragsizeMap &frags, const KnownMap &known)
 {
   VcfInput vi;
   vi.nt = tumor.nt;
@@ -1442,6 +1579,7 @@ static void write_vcf_files(const Options &o, const Sample &tumor, const CallTab
   vi.link = o.link ? &link : nullptr;
   vi.partners = o.partners ? &partners : nullptr;
   vi.frags = o.fragsize ? &frags : nullptr;
+  vi.known = o.known() ? &known : nullptr;
   auto write = [&](const string &path, const vector<OutRow> &calls) {
     if (write_vcf(path, calls, vi)) return;
     std::cerr << "Error: cannot write " << path << ": the evidence tables do not cover every call" << std::endl;
@@ -1459,6 +1597,7 @@ static void write_vcf_files(const Options &o, const Sample &tumor, const CallTab
   vi.link = nullptr;                   // ... and with -link
   vi.partners = nullptr;               // ... and with -partners
   vi.frags = nullptr;                  // ... and with -fragsize
+  vi.known = nullptr;                  // ... and with -known
   vi.rescued = &rescued.calls;
   write(o.out_file + "_fusion_rescued.vcf", rescued.rows);
 }
@@ -1513,6 +1652,9 @@ static void write_params(const Options &o, double w)
   if (o.link) p << "link_max_dist\t" << o.linkdist << std::endl;
   if (o.partners) p << "partners" << std::endl;
   if (o.fragsize) p << "fragsize" << std::endl;
+  if (o.known()) p << "known_file\t" << o.known_file << std::endl;
+  if (o.known()) p << "known_slop\t" << o.knownslop << std::endl;
+  if (o.bedpe) p << "bedpe" << std::endl;
 }
 
 // BreakID.cc:175-191.  scan_pairs_count and after_cluster_count are never updated by the reference (always 0);
@@ -1555,6 +1697,8 @@ int main(int argc, char *argv[])
   Exclusion exclusion;
   if (o.exclude()) read_exclusion(o, exclusion);
   decode_tumor(o, tumor, exclusion);
+  KnownPanel panel;  // (read against the file's reference list before the stages run: a line that ends the run does so early)
+  if (o.known()) panel = read_known_bedpe(o.known_file, tumor.names, tumor.lens, tumor.nt);
   if (!opens(o.nib_dir + "/ref_names.txt"))
   {
     std::cerr << "Error: cannot open reference names file.\n";
@@ -1594,11 +1738,18 @@ int main(int argc, char *argv[])
   if (o.partners) partners = locus_partners(o, tumor, normal, rows, run.w);
   FragsizeMap frags;
   if (o.fragsize) frags = fragment_sizes(o, tumor, tables, rows, run);
+  KnownMap known;
+  if (o.known()) known = known_calls(o, tumor, tables, rows, panel);
 
   if (o.clip) write_rescued_tables(o, rescued, tables);
-  write_fusion_tables(o, rows, fusion_twins(o, tables, consensus.sides, homology, similar, coverage, frames, links, partners, frags));
-  if (o.vcf) write_vcf_files(o, tumor, tables, rows, rescued, consensus.sides, homology, similar, coverage, frames, links, partners, frags);
+  write_fusion_tables(o, rows, fusion_twins(o, tables, consensus.sides, homology, similar, coverage, frames, links, partners, frags, known));
+  if (o.vcf) write_vcf_files(o, tumor, tables, rows, rescued, consensus.sides, homology, similar, coverage, frames, links, partners, frags, known);
   if (o.evidence) write_evidence_files(o, tumor, tables, rows, rescued);
+  if (o.bedpe && !write_bedpe_files(o, rows, tables.jsup))
+  {
+    std::cerr << "Error: cannot write " << o.out_file << "_fusion.bedpe: the evidence tables do not cover every call" << std::endl;
+    exit(1);
+  }
   write_params(o, run.w);
   const clock_t end = clock();
   std::cout << "the fusion process of file " << o.inp_file << "  costs time: " << (end - start) / double(CLOCKS_PER_SEC) << " seconds" << std::endl;

@@ -48,6 +48,9 @@ int bk_call_partner_sites(const bk_cluster *c, double w, struct bk_partner_site 
 // -fragsize (the fragment lengths the member pairs imply across a junction, and the library's bounds)
 int bk_fragment_sizes(bk_ctx *ctx, const struct bk_frag_site *sites, uint64_t n, int32_t lo, int32_t hi, const struct bk_frag_sizes **out) __attribute__((weak));
 int bk_fragment_bounds(double mean, double sd, int32_t *lo, int32_t *hi) __attribute__((weak));
+// -known
+int bk_known_calls(bk_ctx *ctx, const struct bk_known_entry *entries, uint64_t n_entries, const struct bk_known_site *sites, uint64_t n, uint32_t slop,
+                   const struct bk_known_call **out) __attribute__((weak));
 // -dedup
 int bk_unique_support(bk_ctx *ctx, const struct bk_unique_support **out, uint64_t *count, const uint64_t **first, uint64_t *n_rows) __attribute__((weak));
 // -clip (the soft-clip evidence, the depth at the rescued positions and the rescue rule)
@@ -99,15 +102,18 @@ static const char *HELP =
      \t -link      \t reciprocal partner, duplicates and event of every call among all voted calls (twin files *_link.txt; EVENT / PARID with -vcf)  \n \
      \t -linkdist  \t bases up to which two breakpoints count as one region, 0 to 1000000 (with -link)  [1000]\n \
      \t -partners  \t where the discordant pairs inside the two windows of every call point to: ends, ends to the partner window, loci elsewhere and the largest of them (twin files *_partners.txt; PTN / PTP / PTL with -vcf)  \n \
-     \t -fragsize  \t the fragment lengths the discordant pairs of every call imply across its junction, against the library's insert sizes (twin files *_fragsize.txt; FGN / FGMEAN / FGZ with -vcf)  \n ";
+     \t -fragsize  \t the fragment lengths the discordant pairs of every call imply across its junction, against the library's insert sizes (twin files *_fragsize.txt; FGN / FGMEAN / FGZ with -vcf)  \n \
+     \t -known     \t match every call against a panel of known junctions (BEDPE: chrom1 start1 end1 chrom2 start2 end2 [name score strand1 strand2]; twin files *_known.txt; KNOWN / KNAMES / KBEST with -vcf)  \n \
+     \t -knownslop \t bases up to which a breakpoint beside an interval of the panel still falls into it, 0 to 1000000 (with -known)  [100]\n \
+     \t -bedpe     \t also write the calls as BEDPE (*_fusion.bedpe), the format -known reads  \n ";
 
 struct Options
 {
-  std::string inp_file, out_file, nib_dir, normal_file, exclude_file, build = "hg19";
+  std::string inp_file, out_file, nib_dir, normal_file, exclude_file, known_file, build = "hg19";
   int qual = 20, device = 0, n_gpus = 0, transport = BK_TRANSPORT_AUTO;  // -gpus N: one sample over N GPUs (include/breakid_multi.h)
   bool fast = false, all = false;                                        // -all: no gene-pair and repeat filter (the _fusion_all files)
-  bool genotype = false, vcf = false, evidence = false, clip = false, dedup = false, consensus = false, homology = false, similar = false, coverage = false, frame = false, link = false, partners = false, fragsize = false;
-  bool anchor_given = false, minclip_given = false, clipsupport_given = false, conslen_given = false, homshift_given = false, homins_given = false, simflank_given = false, covflank_given = false, linkdist_given = false;
+  bool genotype = false, vcf = false, evidence = false, clip = false, dedup = false, consensus = false, homology = false, similar = false, coverage = false, frame = false, link = false, partners = false, fragsize = false, bedpe = false;
+  bool anchor_given = false, minclip_given = false, clipsupport_given = false, conslen_given = false, homshift_given = false, homins_given = false, simflank_given = false, covflank_given = false, linkdist_given = false, knownslop_given = false;
   long anchor = 10;                      // -anchor: bases a reference read must cover on either side of the breakpoint base
   long min_clip = 10, clip_support = 3;  // -minclip: shortest clip that counts; -clipsupport: reads at one position a rescued side needs
   long conslen = 64;                     // -conslen: longest junction sequence per side
@@ -115,7 +121,9 @@ struct Options
   long simflank = 150;                   // -simflank: the bases either side of a breakpoint that bk_locus_similarity compares
   long covflank = 1000;                  // -covflank: the bases either side of a cut that bk_call_windows gives a flank window
   long linkdist = 1000;                  // -linkdist: the distance up to which bk_link_calls takes two breakends as near
+  long knownslop = 100;                  // -knownslop: the distance up to which bk_known_calls lets a breakend fall into an interval
   bool multi() const { return n_gpus >= 1; }  // the sharded run
+  bool known() const { return !known_file.empty(); }
   bool with_normal() const { return !normal_file.empty(); }
   bool exclude() const { return !exclude_file.empty(); }
 };
@@ -157,6 +165,8 @@ static void check_options(const Options &o)
   const Feature link{"-link", o.link, false, bk_link_calls && bk_junctions && bk_junction_sides};
   const Feature partners{"-partners", o.partners, false, bk_locus_partners && bk_call_partner_sites};
   const Feature fragsize{"-fragsize", o.fragsize, false, bk_fragment_sizes && bk_fragment_bounds && bk_junctions && bk_junction_sides};
+  const Feature known{"-known", o.known(), false, bk_known_calls && bk_junctions && bk_junction_sides};
+  const Feature bedpe{"-bedpe", o.bedpe, false, bk_junctions && bk_junction_sides};
   const Feature consensus{"-consensus", o.consensus, false, bk_clip_consensus && bk_clip_reads && bk_evidence && bk_junctions && bk_junction_sides};
   const Feature clip{"-clip", o.clip, false, bk_clip_support && bk_clip_reads && bk_base_depth && bk_clip_rescue && bk_junctions && bk_junction_sides};
   const Feature exclude{"-x", o.exclude(), true, bk_exclude_regions && bk_multi_run_ex && bk_multi_run_bam_ex && bk_multi_excluded};
@@ -194,6 +204,10 @@ static void check_options(const Options &o)
       rule(o.link && !in_range(o.linkdist, 0, 1000000), "-linkdist must be a number from 0 to 1000000."), library(link),
       gpus(partners), library(partners),
       gpus(fragsize), library(fragsize),
+      rule(o.knownslop_given && !o.known(), "-knownslop needs -known."), gpus(known),
+      rule(o.known() && !in_range(o.knownslop, 0, 1000000), "-knownslop must be a number from 0 to 1000000."), library(known),
+      {Refusal::OPEN, known.set && !opens(o.known_file), "known file: " + o.known_file},
+      gpus(bedpe), library(bedpe),
   };
   for (const Refusal &r : refusals)
   {
@@ -219,6 +233,7 @@ static Options parse_options(int argc, char *argv[])
                                      {"conslen", 1, 0, 22}, {"homology", 0, 0, 23}, {"homshift", 1, 0, 24}, {"homins", 1, 0, 25},
                                      {"similar", 0, 0, 26}, {"simflank", 1, 0, 27}, {"coverage", 0, 0, 28}, {"covflank", 1, 0, 29}, {"frame", 0, 0, 30},
                                      {"link", 0, 0, 31}, {"linkdist", 1, 0, 32}, {"partners", 0, 0, 33}, {"fragsize", 0, 0, 34},
+                                     {"known", 1, 0, 35}, {"knownslop", 1, 0, 36}, {"bedpe", 0, 0, 37},
                                      {"f", 0, 0, 5},  // (-f used to complete to -fast alone; it still means it beside -frame)
                                      {0, 0, 0, 0}};
   Options o;
@@ -267,6 +282,9 @@ static Options parse_options(int argc, char *argv[])
     case 32: number(o.linkdist, o.linkdist_given); break;
     case 33: o.partners = true; break;
     case 34: o.fragsize = true; break;
+    case 35: o.known_file = optarg; break;
+    case 36: number(o.knownslop, o.knownslop_given); break;
+    case 37: o.bedpe = true; break;
     default: std::cerr << "Error: cannot parse arguments.\n"; exit(1);
     }
   }

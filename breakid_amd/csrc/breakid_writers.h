@@ -399,6 +399,26 @@ struct FragsizeCall
     return s;
   }
 };
+// -known: the twin files' columns (bk_known_calls of the written calls against the panel)
+static const char *KNOWN_COLUMNS = "\tKn_Hits\tKn_Names\tKn_Oriented\tKn_Opposed\tKn_Best\tKn_Score\tKn_BestDist\tKn_BestMap\tKn_Side1\tKn_Side2";
+struct KnownCall
+{
+  struct bk_known_call k;
+  string best_name = ".";  // the name text of the best hit's entry
+  string fields() const
+  {
+    std::ostringstream o;
+    o << "\t" << k.n_hits << "\t" << k.n_names << "\t" << k.n_oriented << "\t" << k.n_opposed << "\t" << (k.best >= 0 ? best_name : ".") << "\t";
+    if (k.best >= 0 && k.best_score != BK_KNOWN_NO_SCORE)
+      o << k.best_score;
+    else
+      o << ".";
+    o << "\t" << k.best_dist << "\t" << (k.best < 0 ? "." : k.best_crossed ? "crossed" : "straight") << "\t" << k.n_side[0] << "\t" << k.n_side[1];
+    return o.str();
+  }
+  // what both breakends of the call end their INFO with
+  string info() const;
+};
 // -clip -normal: what _fusion_rescued_normal.txt adds to a row of _fusion_rescued.txt
 static const char *RESCUED_COLUMNS_NORMAL = "\tNormal_DRP\tNormal_ClipAt1\tNormal_ClipAt2\tNormal_Depth1\tNormal_Depth2";
 
@@ -428,6 +448,7 @@ using FrameMap = std::map<uint64_t, FrameCall>;
 using LinkMap = std::map<uint64_t, LinkCall>;  // every voted call, whichever files hold it
 using PartnerMap = std::map<uint64_t, PartnerCall>;
 using FragsizeMap = std::map<uint64_t, FragsizeCall>;
+using KnownMap = std::map<uint64_t, KnownCall>;
 
 // -clip: the rescued clusters in the order of _fusion_rescued.txt, calls[k] to rows[k]; with -evidence the clipped reads at the peaks
 // of the written ones (bk_clip_reads: the rows of sites 2 * j and 2 * j + 1 belong to the j-th written row)
@@ -470,7 +491,7 @@ struct Twin
 // The twins of this run, the reference's own two files first.  An option that adds columns to the calls adds its entry here.
 static vector<Twin> fusion_twins(const Options &o, const CallTables &t, const ConsensusMap &cons, const HomologyMap &hom, const SimilarMap &sim,
                                  const CoverageMap &cov, const FrameMap &frame, const LinkMap &link, const PartnerMap &partners,
-                                 const FragsizeMap &frags)
+                                 const FragsizeMap &frags, const KnownMap &known)
 {
   const bool with_normal = o.with_normal();  // (a tumour without calls still gets header-only twins)
   vector<Twin> twins;
@@ -556,6 +577,12 @@ static vector<Twin> fusion_twins(const Options &o, const CallTables &t, const Co
                        tail = frags.at(r.idx).fields();
                        return true;
                      }});
+  if (o.known())
+    twins.push_back({"_known", KNOWN_COLUMNS, [&known](const OutRow &r, string &tail) {
+                       if (!known.count(r.idx)) return false;
+                       tail = known.at(r.idx).fields();
+                       return true;
+                     }});
   return twins;
 }
 
@@ -575,6 +602,34 @@ static void write_fusion_tables(const Options &o, const vector<OutRow> &rows, co
       if (twins[k].tail(r, tail)) files[k].put(r, all_ok, filt_ok, tail);
     }
   }
+}
+
+// -bedpe: <prefix>_fusion.bedpe and, with -all, <prefix>_fusion_all.bedpe: one line per row of the fusion file in its order, no header,
+// in the format -known reads.  Each breakpoint is the one-base interval [P - 1, P); the name is the prefix's base name, so that files of
+// several samples put together count samples by name; the score is N_DRP + N_SR; the strands are the sides of bk_junction_sides ('+'
+// keeps the bases up to the breakpoint, '-' those from it on, '.' when no evidence gives a side).  False when a call has no junction row.
+static bool write_bedpe_files(const Options &o, const vector<OutRow> &rows, const vector<struct bk_junction> &jsup)
+{
+  const size_t slash = o.out_file.find_last_of('/');
+  const string sample = slash == string::npos ? o.out_file : o.out_file.substr(slash + 1);
+  std::ofstream all, filt((o.out_file + "_fusion.bedpe").c_str());
+  if (o.all) all.open((o.out_file + "_fusion_all.bedpe").c_str());
+  for (const OutRow &r : rows)
+  {
+    const bool all_ok = call_all_ok(r), filt_ok = call_filt_ok(r);
+    if (!all_ok) continue;
+    if (r.idx >= jsup.size()) return false;
+    uint8_t right[2] = {0, 1}, source = 0;
+    bk_junction_sides(&jsup[r.idx], &right[0], &right[1], &source);
+    const long long p1 = r.c.p1_exact, p2 = (uint32_t) r.c.p2_exact;
+    std::ostringstream l;
+    l << r.p1_chr << "\t" << p1 - 1 << "\t" << p1 << "\t" << r.p2_chr << "\t" << p2 - 1 << "\t" << p2 << "\t" << (sample.empty() ? "." : sample) << "\t"
+      << (uint64_t) r.c.n_drp + r.c.n_sr << "\t" << (source ? (right[0] ? "-" : "+") : ".") << "\t" << (source ? (right[1] ? "-" : "+") : ".") << "\tbk" << r.idx << "\t"
+      << fusion_type(r.c.type_mask) << "\t" << (long) r.c.n_drp << "\t" << (long) r.c.n_sr << "\n";
+    if (filt_ok) filt << l.str();
+    if (all.is_open()) all << l.str();
+  }
+  return true;
 }
 
 // -clip: <prefix>_fusion_rescued.txt, a table with the clip columns, and with -normal <prefix>_fusion_rescued_normal.txt: the same rows
@@ -635,6 +690,8 @@ struct VcfInput
   const PartnerMap *partners = nullptr;
   // -fragsize (else null; never for the rescued clusters): FGN, and FGMEAN / FGZ where the columns have a value, on both breakends, behind everything else
   const FragsizeMap *frags = nullptr;
+  // -known (else null; never for the rescued clusters): KNOWN / KNAMES, and KBEST where there is a hit, on both breakends, behind everything else
+  const KnownMap *known = nullptr;
 };
 
 static char nib_base(const string &nib_dir, const string &chr, long pos1)  // the base at a 1-based position; N without a file or beyond it
@@ -652,6 +709,13 @@ static string vcf_info_text(string s)  // an INFO value holds no blank, ';', '='
   for (char &c : s)
     if (c == ' ' || c == '\t' || c == ';' || c == '=' || c == ',') c = '_';
   return s.empty() ? "." : s;
+}
+
+string KnownCall::info() const
+{
+  string s = ";KNOWN=" + std::to_string(k.n_hits) + ";KNAMES=" + std::to_string(k.n_names);
+  if (k.best >= 0) s += ";KBEST=" + vcf_info_text(best_name);
+  return s;
 }
 
 // one sample column: DV:RV, or with the reference-allele counts GT:GQ:DR:DV:RR:RV (GT / GQ as in the *_genotype.txt twins: the call
@@ -759,6 +823,7 @@ static bool write_vcf(const string &path, const vector<OutRow> &rows, const VcfI
         }
         if (in.partners && in.partners->count(r.idx)) o << in.partners->at(r.idx).info(s);
         if (in.frags && in.frags->count(r.idx)) o << in.frags->at(r.idx).info();
+        if (in.known && in.known->count(r.idx)) o << in.known->at(r.idx).info();
         o << "\t" << (in.gsup ? "GT:GQ:DR:DV:RR:RV" : "DV:RV") << "\t" << vcf_sample(r.c.n_drp, r.c.n_sr, in.gsup ? &(*in.gsup)[r.idx] : nullptr, s);
         if (in.with_normal) o << "\t" << vcf_sample(in.nsup[r.idx].n_drp, in.nsup[r.idx].n_sr, in.gsup_normal ? &(*in.gsup_normal)[r.idx] : nullptr, s);
       }
@@ -825,6 +890,10 @@ static bool write_vcf(const string &path, const vector<OutRow> &rows, const VcfI
     v << "##INFO=<ID=FGN,Number=1,Type=Integer,Description=\"Discordant pairs whose implied fragment length across the junction was computed\">\n"
          "##INFO=<ID=FGMEAN,Number=1,Type=Float,Description=\"Mean fragment length those pairs imply across the junction\">\n"
          "##INFO=<ID=FGZ,Number=1,Type=Float,Description=\"That mean less the library's mean insert size, in units of the library's sd\">\n";
+  if (in.known && !in.rescued)
+    v << "##INFO=<ID=KNOWN,Number=1,Type=Integer,Description=\"Entries of the panel of known junctions that hold both breakpoints of the call\">\n"
+         "##INFO=<ID=KNAMES,Number=1,Type=Integer,Description=\"Different names among those entries\">\n"
+         "##INFO=<ID=KBEST,Number=1,Type=String,Description=\"Name of the entry with the largest score among them\">\n";
   if (in.rescued) v << "##INFO=<ID=SC,Number=1,Type=Integer,Description=\"Soft-clipped reads without an SA tag that end at this position (the clip peak)\">\n";
   if (in.gsup)
     v << "##FORMAT=<ID=GT,Number=1,Type=String,Description=\"Genotype\">\n"

@@ -859,6 +859,71 @@ int bk_fragment_sizes(bk_ctx *ctx, const struct bk_frag_site *sites, uint64_t n,
  * clamped to int32.  Returns BK_OK, or BK_ERR_ARG for a null pointer, a non-finite value or sd < 0. */
 int bk_fragment_bounds(double mean, double sd, int32_t *lo, int32_t *hi);   /* pure host function */
 
+/* ---- known junctions: every call of a list against a panel of pairs of intervals (BEDPE) ------------------------------------------
+ * What is already known about a junction: in how many entries of a panel of normals it was seen, or which entry of a catalogue of
+ * known fusions it is.  Both are lists of pairs of genomic intervals.  All arithmetic is integer.
+ * Site: breakend s = 0, 1 is (tid_s, P_s, right_s), P 1-based as p1_exact is, x = P - 1; the layout of bk_frame_site.  Entry:
+ * interval k = 0, 1 is (tid, [beg, end)), 0-based and half-open as in BED, then a name id, a score and two strands.
+ *   dist       dist(x, [b, e)) is 0 when b <= x < e, b - x below the interval and x - (e - 1) at or above end, compared in 64 bits
+ *              (P may be 1 or 0xFFFFFFFF, beg may be 0).  A breakend falls into an interval when the tids are equal and >= 0 and
+ *              dist <= slop.
+ *   mappings   straight holds when breakend 0 falls into interval 0 and breakend 1 into interval 1; crossed holds when 0 falls into
+ *              1 and 1 into 0.  A mapping's dist is the sum of its two distances.
+ *   agree      a mapping agrees when the entry states both strands and each stated strand equals the side of the breakend paired
+ *              with it (BK_STRAND_LEFT for right == 0, BK_STRAND_RIGHT for right == 1); it opposes when both strands are stated and
+ *              it does not agree.  An entry with one strand stated counts as unstated.
+ *   hit        an entry is a hit of the site when a mapping holds, once even when both hold.  The hit's mapping is the first by:
+ *              agrees, then the smaller dist, then straight.
+ * Per site: n_hits; n_oriented and n_opposed from the hit's mapping; n_names, the distinct `name` values among the hits;
+ * n_side[s], the entries with at least one interval that breakend s falls into, whatever the other breakend does, each entry once.
+ * best is the hit with the largest score (BK_KNOWN_NO_SCORE sorts below every score), ties to the smaller dist, then to the smaller
+ * entry index; best_score, best_dist, best_crossed and best_oriented (1 when its mapping agrees) describe it.  Without a hit
+ * best = -1, best_score = BK_KNOWN_NO_SCORE and the rest is 0.
+ * Every output is a count or an argmax with a fixed tie rule: two runs give the same bytes, and a permutation of the sites permutes
+ * the rows.
+ * Hand example (chr1 = 0, chr2 = 1, slop 100; site = chr1 300000 LEFT, chr2 700000 RIGHT, so x = 299999 and 699999):
+ *   e0 = chr1 [299950,300050) / chr2 [699900,700100), name 0, score 12, + -   straight holds and agrees, dist 0
+ *   e1 = chr2 [700050,700060) / chr1 [299000,299990), name 1, score 40, - +   crossed holds with distances 51 and 10, and agrees
+ *   e2 = chr1 [299990,300010) / chr1 [100,200), name 0                        no hit (breakend 0 alone)
+ *   e3 = chr2 [699000,701000) / chr2 [699500,700500), name 2                  no hit (breakend 1 alone, through both intervals)
+ *   row: n_hits 2, n_oriented 2, n_opposed 0, n_names 2, n_side {3, 3}, best 1, best_score 40, best_dist 61, best_crossed 1,
+ *   best_oriented 1. */
+#define BK_KNOWN_MAX_SLOP 1000000u
+#define BK_KNOWN_NO_SCORE INT32_MIN
+#define BK_STRAND_NONE 0   /* unstated */
+#define BK_STRAND_LEFT 1   /* '+': the bases up to the breakpoint are retained (right == 0) */
+#define BK_STRAND_RIGHT 2  /* '-': right == 1 */
+struct bk_known_entry { int32_t tid1; uint32_t beg1, end1; int32_t tid2; uint32_t beg2, end2; uint32_t name; int32_t score; uint8_t strand1, strand2; uint8_t reserved[6]; };   /* 40 bytes */
+struct bk_known_site  { int32_t tid1; uint32_t pos1; int32_t tid2; uint32_t pos2; uint8_t right1, right2; uint8_t reserved[6]; };   /* 24 bytes, as bk_frame_site */
+struct bk_known_call  { uint32_t n_hits, n_oriented, n_opposed, n_names, n_side[2]; int32_t best, best_score; uint32_t best_dist; uint8_t best_crossed, best_oriented; uint8_t reserved[2]; };   /* 40 bytes; reserved = 0 */
+/* ctx: any live context that is not a shard (bk_shard_*); no stage needs to have run, and nothing a later bk_fetch or stage returns
+ * changes.  entries, sites: host memory.  *out (n rows) is library-owned until the next call or bk_free(ctx).  BK_ERR_ARG (with the
+ * reason and the index in bk_last_error) for a null out, null sites with n > 0, null entries with n_entries > 0, a shard, slop
+ * above BK_KNOWN_MAX_SLOP, a right above 1, a strand above 2, a non-zero reserved byte of a site or an entry, and an interval with
+ * tid >= 0 and end <= beg.  BK_ERR_LIMIT beyond 2^30 sites, 2^30 entries or 2^32 - 16 listed hits (the sum of n_hits).  n == 0 and
+ * n_entries == 0 are no errors; with no entries every row is the no-hit row.  An interval with tid < 0 holds nothing; its entry can
+ * still count in n_side through its other interval.
+ * How: the intervals with tid >= 0 (m of the 2 n_entries) are sorted by ((tid + 1) << 32) | beg over the bits in use, the value
+ * being 2 * entry + k, and a running maximum of end is kept inside every contig's run.  One wavefront per site searches, per
+ * breakend, the last key with beg <= x + slop and walks backwards 64 intervals a step while the running maximum still reaches
+ * x - slop; each lane tests its own interval.  On a hold the lane reads the entry's row and computes the whole table of (breakend,
+ * interval) from it.  An entry reached through both of its intervals is counted at the first of them that holds the breakend, in
+ * the order (interval 0, interval 1); hits are found from breakend 0 only, n_side from both walks.  The counts and the best hit are
+ * wave reductions.  For n_names the hits per site are scanned, a second walk lists (site << 32) | name at the site's offset, the
+ * list is sorted over the name's and the site's bits in use, and one wavefront per site counts the run heads.  No atomics, and
+ * nothing is capped: an entry that spans a whole contig makes every site on that contig walk that contig's whole run, because the
+ * running maximum never drops below it.  The entries are uploaded and indexed per call; the buffers are the context's and are
+ * reused when they are large enough.
+ * bk_timing: scope `known_calls` (the work on the device copies) around `known_calls_index` and `known_calls_sites`.
+ * bk_timing_touched, with bits(x) the position of the highest set bit of x from 1 (0 for 0):
+ *   index  per entry 40 (its row) + 24 (two keys and values written) + 48 per radix pass (two keys and values read and written),
+ *          passes = ceil((32 + bits(max tid + 1)) / 8), 0 without an interval with tid >= 0; per such interval 16 (its end
+ *          gathered, its running maximum written)
+ *   sites  per site 80 (its 24-byte row, its 40-byte result, its count and its offset); per listed hit 12 (its key and value
+ *          written) + 24 per radix pass, passes = ceil(bits(max name) / 8) + ceil(bits(n - 1) / 8)
+ *   known_calls is their sum.  The intervals and entries that a site's walks read are not modelled. */
+int bk_known_calls(bk_ctx *ctx, const struct bk_known_entry *entries, uint64_t n_entries, const struct bk_known_site *sites, uint64_t n, uint32_t slop, const struct bk_known_call **out);
+
 /* Copy a stage's result to library-owned host memory.  *data stays valid until the next bk_fetch
  * of the same stage or bk_free.  group_off (may be NULL) receives n_groups+1 offsets for pair stages. */
 int bk_fetch(bk_ctx *ctx, int stage, const void **data, uint64_t *count, const uint64_t **group_off, uint32_t *n_groups);
