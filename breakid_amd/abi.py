@@ -53,6 +53,9 @@ LOCUS_SIM = np.dtype([("score", "<u4"), ("len", "<u4"), ("mism", "<u4"), ("run",
 assert LOCUS_PAIR.itemsize == 16 and LOCUS_SIM.itemsize == 32
 COV_WINDOW = np.dtype([("tid", "<i4"), ("beg", "<u4"), ("end", "<u4"), ("reserved", "<u4")])  # struct bk_cov_window; 0-based, half-open
 WINDOW_COV = np.dtype([("bases", "<u8"), ("reads", "<u4"), ("reserved", "<u4")])  # struct bk_window_cov
+WINDOW_CTX = np.dtype([("mapq_sum", "<u8"), ("reads", "<u4"), ("mq0", "<u4"), ("lowq", "<u4"), ("clipped", "<u4"), ("improper", "<u4"), ("orphan", "<u4"), ("dup", "<u4"),
+                       ("secsup", "<u4")])  # struct bk_window_ctx; records by start, not by overlap
+assert WINDOW_CTX.itemsize == 40
 assert COV_WINDOW.itemsize == 16 and WINDOW_COV.itemsize == 16
 FRAME_SITE = np.dtype([("tid1", "<i4"), ("pos1", "<u4"), ("tid2", "<i4"), ("pos2", "<u4"), ("right1", "u1"), ("right2", "u1"), ("reserved", "u1", (6,))])  # struct bk_frame_site; pos 1-based
 FRAME_CALL = np.dtype([("cls", "u1"), ("order", "u1"), ("loc", "u1", (2,)), ("role", "u1", (2,)), ("exon", "<u2", (2,)), ("reserved", "<u2"), ("tx", "<i4", (2,)),

@@ -35,7 +35,7 @@ def build(verbose=False):
 
 EXPORTS = ["bk_init", "bk_prepare_process", "bk_free", "bk_last_error", "bk_set_stream", "bk_sync", "bk_get_stream", "bk_upload_records", "bk_records", "bk_exclude_regions", "bk_isize_stats",
            "bk_discordant_pairs", "bk_mask_and_cluster", "bk_split_evidence", "bk_cluster_summary",
-           "bk_split_breakpoints", "bk_normal_support", "bk_ref_support", "bk_genotype_call", "bk_clip_support", "bk_clip_reads", "bk_base_depth", "bk_clip_rescue", "bk_junctions", "bk_junction_sides", "bk_vcf_breakend_alt", "bk_evidence", "bk_unique_support", "bk_clip_consensus", "bk_junction_fit", "bk_locus_similarity", "bk_window_coverage", "bk_call_windows", "bk_fusion_frame", "bk_link_calls", "bk_locus_partners", "bk_call_partner_sites", "bk_fragment_sizes", "bk_fragment_bounds", "bk_known_calls", "bk_run", "bk_fetch", "bk_timing", "bk_timing_enable", "bk_timing_touched", "bk_group_stats", "bk_qname_hash", "bk_qname_check",
+           "bk_split_breakpoints", "bk_normal_support", "bk_ref_support", "bk_genotype_call", "bk_clip_support", "bk_clip_reads", "bk_base_depth", "bk_clip_rescue", "bk_junctions", "bk_junction_sides", "bk_vcf_breakend_alt", "bk_evidence", "bk_unique_support", "bk_clip_consensus", "bk_junction_fit", "bk_locus_similarity", "bk_window_coverage", "bk_window_context", "bk_call_windows", "bk_fusion_frame", "bk_link_calls", "bk_locus_partners", "bk_call_partner_sites", "bk_fragment_sizes", "bk_fragment_bounds", "bk_known_calls", "bk_run", "bk_fetch", "bk_timing", "bk_timing_enable", "bk_timing_touched", "bk_group_stats", "bk_qname_hash", "bk_qname_check",
            "bk_bam_open", "bk_bam_header", "bk_bam_decode", "bk_bam_close", "bk_bam_extract", "bk_bam_names_free", "bk_bam_reads", "bk_reads_free", "bk_bam_decode_device", "bk_bam_decode_device_part", "bk_bam_decode_device_ctx", "bk_bam_dev_free", "bk_feed_release_caches", "bk_debug_bgzf_inflate", "bk_debug_std_sort", "bk_debug_scan", "bk_debug_radix_sort", "bk_debug_prims_info", "bk_sort_forms", "bk_debug_ahc", "bk_debug_points", "bk_debug_cigar", "bk_debug_vote", "bk_debug_region", "bk_shard_begin", "bk_shard_get_stats", "bk_shard_set_stats",
            "bk_shard_sd_local", "bk_shard_sd_finish", "bk_shard_buffer", "bk_shard_set_buffer", "bk_shard_group_sizes",
            "bk_shard_own_groups", "bk_shard_route_candidates", "bk_shard_group_keys", "bk_shard_route_pairs", "bk_shard_group_pairs", "bk_shard_bp_cov", "bk_shard_bp_vote", "bk_shard_bp_vote_slice", "bk_shard_bp_set_voted", "bk_shard_bp_depth", "bk_shard_bp_finish"]
@@ -87,6 +87,7 @@ def lib():
         L.bk_junction_fit.argtypes = [vp, C.POINTER(abi.RefSeq), vp, C.c_uint64, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(vp)]
         L.bk_locus_similarity.argtypes = [vp, C.POINTER(abi.RefSeq), vp, C.c_uint64, C.c_uint32, C.POINTER(vp)]
         L.bk_window_coverage.argtypes = [vp, vp, C.c_uint64, C.c_int, C.POINTER(vp)]
+        L.bk_window_context.argtypes = [vp, vp, C.c_uint64, C.c_int, C.POINTER(vp)]
         L.bk_call_windows.argtypes = [vp, C.c_int, C.c_int, C.c_uint32, vp, vp]
         L.bk_fusion_frame.argtypes = [vp, C.POINTER(abi.TxModel), vp, C.c_uint64, C.POINTER(vp)]
         L.bk_link_calls.argtypes = [vp, vp, C.c_uint64, C.c_uint32, C.POINTER(vp)]
@@ -624,6 +625,20 @@ class Context:
             return np.zeros(0, abi.WINDOW_COV)
         buf = (C.c_char * (n * abi.WINDOW_COV.itemsize)).from_address(out.value)
         return np.frombuffer(buf, dtype=abi.WINDOW_COV, count=n).copy()
+
+    def window_context(self, windows, mapq_min=0):
+        """The record classes and the mapping quality of this context's records that start inside arbitrary windows
+        (bk_window_context).  windows: abi.COV_WINDOW rows, 0-based and half-open; mapq_min: the threshold of `lowq`.  Returns one
+        abi.WINDOW_CTX row per window."""
+        windows = np.ascontiguousarray(windows, abi.COV_WINDOW)
+        assert windows.ndim == 1
+        n = len(windows)
+        out = C.c_void_p()
+        self._check(self.L.bk_window_context(self.h, windows.ctypes.data if n else None, n, int(mapq_min), C.byref(out)))
+        if not n:
+            return np.zeros(0, abi.WINDOW_CTX)
+        buf = (C.c_char * (n * abi.WINDOW_CTX.itemsize)).from_address(out.value)
+        return np.frombuffer(buf, dtype=abi.WINDOW_CTX, count=n).copy()
 
     def fusion_frame(self, model, sites):
         """The 5' / 3' partners and the reading frame of every site (bk_fusion_frame).  model: a TxModel, or a dict of the bk_txmodel

@@ -21,6 +21,7 @@
 #include "jfit.h"
 #include "locsim.h"
 #include "coverage.h"
+#include "context.h"
 #include "frame.h"
 #include "link.h"
 #include "partners.h"
@@ -167,6 +168,9 @@ struct bk_ctx
   // window coverage (bk_window_coverage: this context holds the records)
   CovBufs cvb;
   std::vector<struct bk_window_cov> f_wincov;
+  // window context (bk_window_context: this context holds the records)
+  CtxBufs cxb;
+  std::vector<struct bk_window_ctx> f_winctx;
   // fusion frame (bk_fusion_frame)
   FrameBufs frb;
   std::vector<struct bk_frame_call> f_frame;
@@ -1459,6 +1463,51 @@ int bk_window_coverage(bk_ctx *records, const struct bk_cov_window *windows, uin
     }
     rows_to_host(records, d_res, n, records->f_wincov);
     *out = records->f_wincov.data();
+  });
+}
+
+int bk_window_context(bk_ctx *records, const struct bk_cov_window *windows, uint64_t n, int mapq_min, const struct bk_window_ctx **out)
+{
+  return guarded(records, [&] {
+    if (!out || (n && !windows)) throw bk_error(BK_ERR_ARG, "bk_window_context: null argument");
+    if (records->shard) throw bk_error(BK_ERR_ARG, "bk_window_context: sharded contexts (bk_shard_*) are not supported");
+    if (!records->have_records) throw bk_error(BK_ERR_ARG, "bk_window_context: the context holds no record table");
+    if (mapq_min < 0) throw bk_error(BK_ERR_ARG, "bk_window_context: mapq_min must be >= 0");
+    if (n > 0x40000000ull) throw bk_error(BK_ERR_LIMIT, "bk_window_context: more than 2^30 windows");
+    for (uint64_t k = 0; k < n; ++k)
+      if (windows[k].reserved) throw bk_error(BK_ERR_ARG, "bk_window_context: window " + std::to_string(k) + " has a non-zero reserved field");
+    const bk_soa &t = records->rec;
+    if (t.n && (!t.tid || !t.pos || !t.flag || !t.mapq || !t.cigar_off)) throw bk_error(BK_ERR_ARG, "bk_window_context: the record table lacks a column");
+    if (t.n_cigar_words && !t.cigar) throw bk_error(BK_ERR_ARG, "bk_window_context: the record table lacks a column");
+    CtxBufs &b = records->cxb;
+    struct bk_window_ctx *d_res = nullptr;
+    if (n) HIP_CHECK(hipMemcpyAsync(b.win.as<struct bk_cov_window>(n), windows, n * sizeof(struct bk_cov_window), hipMemcpyHostToDevice, records->st));
+    {
+      // lowq depends on mapq_min: the tile sums are rebuilt by every call.  touched: flag, mapq, tid and cigar_off of every record and two
+      // of its CIGAR words, the tile words, the window and its row (include/breakid_hip.h)
+      const uint64_t tiles_bytes = t.n * 19ull + ctx_tiles(t.n) * CTX_TILE_BYTES, windows_bytes = n * (sizeof(struct bk_cov_window) + sizeof(struct bk_window_ctx));
+      // (the two scopes inside push timers of their own, so the whole one ends by its index, not at timers.back())
+      struct Whole
+      {
+        bk_ctx *c;
+        size_t at;
+        ~Whole()
+        {
+          if (c->timing && at < c->timers.size()) (void) hipEventRecord(c->timers[at].b, c->st);
+        }
+      } whole{records, records->timers.size()};
+      records->tick("window_context", tiles_bytes + windows_bytes, true, tiles_bytes + windows_bytes);
+      {
+        Scope s(records, "window_context_tiles", 0, tiles_bytes);
+        ctx_tiles_build(rec_view(records), mapq_min, b, records->st);
+      }
+      {
+        Scope s(records, "window_context_windows", 0, windows_bytes);
+        window_context(rec_view(records), records->nt, n, mapq_min, b, records->st, &d_res);
+      }
+    }
+    rows_to_host(records, d_res, n, records->f_winctx);
+    *out = records->f_winctx.data();
   });
 }
 

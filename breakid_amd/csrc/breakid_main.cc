@@ -813,7 +813,7 @@ static void fetch_call_tables(const Options &o, const Sample &tumor, const Sampl
   if (o.genotype) fetch_rows(tumor, t.gsup, [&](auto rows, auto n) { return bk_ref_support(ctx, ctx, qual, anchor, w, rows, n); });
   if (o.genotype && normal.ctx) fetch_rows(tumor, t.gsup_normal, [&](auto rows, auto n) { return bk_ref_support(ctx, normal.ctx, qual, anchor, w, rows, n); });
   // -vcf: the junction evidence of every call (member pairs by strands, split tuples by clip side)
-  if (o.vcf || o.clip || o.consensus || o.coverage || o.frame || o.known() || o.bedpe || o.link || o.fragsize) fetch_rows(tumor, t.jsup, [&](auto rows, auto n) { return bk_junctions(ctx, rows, n); });
+  if (o.vcf || o.clip || o.consensus || o.coverage || o.frame || o.known() || o.bedpe || o.context || o.link || o.fragsize) fetch_rows(tumor, t.jsup, [&](auto rows, auto n) { return bk_junctions(ctx, rows, n); });
   // -clip: the clipped reads without an SA tag at every cluster, voted or not, on the sample's records and on the normal's
   if (o.clip) fetch_rows(tumor, t.csup, [&](auto rows, auto n) { return bk_clip_support(ctx, ctx, qual, min_clip, w, rows, n); });
   if (o.clip && normal.ctx) fetch_rows(tumor, t.csup_normal, [&](auto rows, auto n) { return bk_clip_support(ctx, normal.ctx, qual, min_clip, w, rows, n); });
@@ -1552,11 +1552,56 @@ static KnownMap known_calls(const Options &o, const Sample &tumor, const CallTab
   return known;
 }
 
+// ---- -context: what the alignments that start beside the breakpoints of every written call look like -------------------------------
+// The four flank windows of every written call (bk_call_windows with -ctxflank and the sides -vcf uses; the span window is left out);
+// one call of bk_window_context answers them all on the sample's records, a second one on the normal's.  A side is the sum of its two
+// windows' rows.
+static ContextMap call_context(const Options &o, const Sample &tumor, const Sample &normal, const CallTables &t, const vector<OutRow> &rows)
+{
+  ContextMap ctx;
+  vector<struct bk_cov_window> windows;
+  vector<uint64_t> window_call;
+  for (const OutRow &r : rows)
+  {
+    if (!call_written(r, o.all)) continue;
+    if (r.idx >= t.jsup.size())
+    {
+      std::cerr << "Error: the evidence tables do not cover every call" << std::endl;
+      exit(1);
+    }
+    uint8_t right[2] = {0, 1}, source = 0;
+    bk_junction_sides(&t.jsup[r.idx], &right[0], &right[1], &source);
+    struct bk_cov_window w[5];
+    if (bk_call_windows(&r.c, right[0], right[1], (uint32_t) o.ctxflank, tumor.lens, w) != BK_OK) die(tumor, BK_ERR_ARG);
+    ctx[r.idx];
+    window_call.push_back(r.idx);
+    windows.insert(windows.end(), w, w + 4);
+  }
+  auto count = [&](const Sample &sample, bool is_normal) {
+    const struct bk_window_ctx *res = nullptr;
+    const int rc = bk_window_context(sample.ctx, windows.data(), windows.size(), o.qual, &res);
+    if (rc != BK_OK) die(sample, rc);
+    for (size_t k = 0; k < window_call.size(); ++k)
+    {
+      ContextCall &c = ctx[window_call[k]];
+      struct bk_window_ctx *into = is_normal ? c.normal : c.tumor;
+      for (int j = 0; j < 4; ++j) ContextCall::add(into[j / 2], res[4 * k + j]);
+    }
+  };
+  count(tumor, false);
+  if (normal.ctx) count(normal, true);
+  uint64_t reads = 0, mq0 = 0;
+  for (const auto &at : ctx)
+    for (int s = 0; s < 2; ++s) reads += at.second.tumor[s].reads, mq0 += at.second.tumor[s].mq0;
+  std::cout << "context: " << window_call.size() << " calls, " << reads << " reads in their windows, " << mq0 << " of them with mapping quality 0" << std::endl;
+  return ctx;
+}
+
 // ---- the files behind the tables ---------------------------------------------------------------------------------------------------
 // -vcf: <prefix>_fusion.vcf, and with -clip <prefix>_fusion_rescued.vcf
 static void write_vcf_files(const Options &o, const Sample &tumor, const CallTables &t, const vector<OutRow> &rows, const Rescued &rescued, const ConsensusMap &cons,
                             const HomologyMap &hom, const SimilarMap &sim, const CoverageMap &cov, const FrameMap &frame, const LinkMap &link,
-                            const PartnerMap &partners, const FragsizeMap &frags, const KnownMap &known)
+                            const PartnerMap &partners, const FragsizeMap &frags, const KnownMap &known, const ContextMap &context)
 {
   VcfInput vi;
   vi.nt = tumor.nt;
@@ -1580,6 +1625,7 @@ static void write_vcf_files(const Options &o, const Sample &tumor, const CallTab
   vi.partners = o.partners ? &partners : nullptr;
   vi.frags = o.fragsize ? &frags : nullptr;
   vi.known = o.known() ? &known : nullptr;
+  vi.context = o.context ? &context : nullptr;
   auto write = [&](const string &path, const vector<OutRow> &calls) {
     if (write_vcf(path, calls, vi)) return;
     std::cerr << "Error: cannot write " << path << ": the evidence tables do not cover every call" << std::endl;
@@ -1598,6 +1644,7 @@ static void write_vcf_files(const Options &o, const Sample &tumor, const CallTab
   vi.partners = nullptr;               // ... and with -partners
   vi.frags = nullptr;                  // ... and with -fragsize
   vi.known = nullptr;                  // ... and with -known
+  vi.context = nullptr;                // ... and with -context
   vi.rescued = &rescued.calls;
   write(o.out_file + "_fusion_rescued.vcf", rescued.rows);
 }
@@ -1655,6 +1702,7 @@ static void write_params(const Options &o, double w)
   if (o.known()) p << "known_file\t" << o.known_file << std::endl;
   if (o.known()) p << "known_slop\t" << o.knownslop << std::endl;
   if (o.bedpe) p << "bedpe" << std::endl;
+  if (o.context) p << "context_flank\t" << o.ctxflank << std::endl;
 }
 
 // BreakID.cc:175-191.  scan_pairs_count and after_cluster_count are never updated by the reference (always 0);
@@ -1740,10 +1788,12 @@ int main(int argc, char *argv[])
   if (o.fragsize) frags = fragment_sizes(o, tumor, tables, rows, run);
   KnownMap known;
   if (o.known()) known = known_calls(o, tumor, tables, rows, panel);
+  ContextMap context;
+  if (o.context) context = call_context(o, tumor, normal, tables, rows);
 
   if (o.clip) write_rescued_tables(o, rescued, tables);
-  write_fusion_tables(o, rows, fusion_twins(o, tables, consensus.sides, homology, similar, coverage, frames, links, partners, frags, known));
-  if (o.vcf) write_vcf_files(o, tumor, tables, rows, rescued, consensus.sides, homology, similar, coverage, frames, links, partners, frags, known);
+  write_fusion_tables(o, rows, fusion_twins(o, tables, consensus.sides, homology, similar, coverage, frames, links, partners, frags, known, context));
+  if (o.vcf) write_vcf_files(o, tumor, tables, rows, rescued, consensus.sides, homology, similar, coverage, frames, links, partners, frags, known, context);
   if (o.evidence) write_evidence_files(o, tumor, tables, rows, rescued);
   if (o.bedpe && !write_bedpe_files(o, rows, tables.jsup))
   {

@@ -38,6 +38,8 @@ int bk_locus_similarity(bk_ctx *ctx, const bk_refseq *ref, const struct bk_locus
 // -coverage (the windows of a call and the aligned bases inside them)
 int bk_window_coverage(bk_ctx *records, const struct bk_cov_window *windows, uint64_t n, int mapq_min, const struct bk_window_cov **out) __attribute__((weak));
 int bk_call_windows(const bk_cluster *c, int right1, int right2, uint32_t flank, const uint32_t *target_len, struct bk_cov_window out[5]) __attribute__((weak));
+// -context (the record classes and the mapping quality inside the windows of a call)
+int bk_window_context(bk_ctx *records, const struct bk_cov_window *windows, uint64_t n, int mapq_min, const struct bk_window_ctx **out) __attribute__((weak));
 // -frame
 int bk_fusion_frame(bk_ctx *ctx, const bk_txmodel *model, const struct bk_frame_site *sites, uint64_t n, const struct bk_frame_call **out) __attribute__((weak));
 // -link
@@ -105,15 +107,17 @@ static const char *HELP =
      \t -fragsize  \t the fragment lengths the discordant pairs of every call imply across its junction, against the library's insert sizes (twin files *_fragsize.txt; FGN / FGMEAN / FGZ with -vcf)  \n \
      \t -known     \t match every call against a panel of known junctions (BEDPE: chrom1 start1 end1 chrom2 start2 end2 [name score strand1 strand2]; twin files *_known.txt; KNOWN / KNAMES / KBEST with -vcf)  \n \
      \t -knownslop \t bases up to which a breakpoint beside an interval of the panel still falls into it, 0 to 1000000 (with -known)  [100]\n \
-     \t -bedpe     \t also write the calls as BEDPE (*_fusion.bedpe), the format -known reads  \n ";
+     \t -bedpe     \t also write the calls as BEDPE (*_fusion.bedpe), the format -known reads  \n \
+     \t -context   \t what the alignments that start beside both breakpoints of every call look like before any filter: mean mapping quality, shares of MAPQ 0, low MAPQ, soft-clipped and improper reads, unmapped mates, duplicates, secondary and supplementary alignments (twin files *_context.txt; CXN / MQ0F / MEANMQ with -vcf)  \n \
+     \t -ctxflank  \t bases either side of a breakpoint in which a read must start, about one fragment length, 1 to 1000000 (with -context)  [500]\n ";
 
 struct Options
 {
   std::string inp_file, out_file, nib_dir, normal_file, exclude_file, known_file, build = "hg19";
   int qual = 20, device = 0, n_gpus = 0, transport = BK_TRANSPORT_AUTO;  // -gpus N: one sample over N GPUs (include/breakid_multi.h)
   bool fast = false, all = false;                                        // -all: no gene-pair and repeat filter (the _fusion_all files)
-  bool genotype = false, vcf = false, evidence = false, clip = false, dedup = false, consensus = false, homology = false, similar = false, coverage = false, frame = false, link = false, partners = false, fragsize = false, bedpe = false;
-  bool anchor_given = false, minclip_given = false, clipsupport_given = false, conslen_given = false, homshift_given = false, homins_given = false, simflank_given = false, covflank_given = false, linkdist_given = false, knownslop_given = false;
+  bool genotype = false, vcf = false, evidence = false, clip = false, dedup = false, consensus = false, homology = false, similar = false, coverage = false, frame = false, link = false, partners = false, fragsize = false, bedpe = false, context = false;
+  bool anchor_given = false, minclip_given = false, clipsupport_given = false, conslen_given = false, homshift_given = false, homins_given = false, simflank_given = false, covflank_given = false, linkdist_given = false, knownslop_given = false, ctxflank_given = false;
   long anchor = 10;                      // -anchor: bases a reference read must cover on either side of the breakpoint base
   long min_clip = 10, clip_support = 3;  // -minclip: shortest clip that counts; -clipsupport: reads at one position a rescued side needs
   long conslen = 64;                     // -conslen: longest junction sequence per side
@@ -122,6 +126,7 @@ struct Options
   long covflank = 1000;                  // -covflank: the bases either side of a cut that bk_call_windows gives a flank window
   long linkdist = 1000;                  // -linkdist: the distance up to which bk_link_calls takes two breakends as near
   long knownslop = 100;                  // -knownslop: the distance up to which bk_known_calls lets a breakend fall into an interval
+  long ctxflank = 500;                   // -ctxflank: the bases either side of a cut in which bk_window_context counts the records that start there
   bool multi() const { return n_gpus >= 1; }  // the sharded run
   bool known() const { return !known_file.empty(); }
   bool with_normal() const { return !normal_file.empty(); }
@@ -167,6 +172,7 @@ static void check_options(const Options &o)
   const Feature fragsize{"-fragsize", o.fragsize, false, bk_fragment_sizes && bk_fragment_bounds && bk_junctions && bk_junction_sides};
   const Feature known{"-known", o.known(), false, bk_known_calls && bk_junctions && bk_junction_sides};
   const Feature bedpe{"-bedpe", o.bedpe, false, bk_junctions && bk_junction_sides};
+  const Feature context{"-context", o.context, false, bk_window_context && bk_call_windows && bk_junctions && bk_junction_sides};
   const Feature consensus{"-consensus", o.consensus, false, bk_clip_consensus && bk_clip_reads && bk_evidence && bk_junctions && bk_junction_sides};
   const Feature clip{"-clip", o.clip, false, bk_clip_support && bk_clip_reads && bk_base_depth && bk_clip_rescue && bk_junctions && bk_junction_sides};
   const Feature exclude{"-x", o.exclude(), true, bk_exclude_regions && bk_multi_run_ex && bk_multi_run_bam_ex && bk_multi_excluded};
@@ -208,6 +214,8 @@ static void check_options(const Options &o)
       rule(o.known() && !in_range(o.knownslop, 0, 1000000), "-knownslop must be a number from 0 to 1000000."), library(known),
       {Refusal::OPEN, known.set && !opens(o.known_file), "known file: " + o.known_file},
       gpus(bedpe), library(bedpe),
+      rule(o.ctxflank_given && !o.context, "-ctxflank needs -context."), gpus(context), library(context),
+      rule(o.context && !in_range(o.ctxflank, 1, 1000000), "-ctxflank must be a number from 1 to 1000000."),
   };
   for (const Refusal &r : refusals)
   {
@@ -234,6 +242,7 @@ static Options parse_options(int argc, char *argv[])
                                      {"similar", 0, 0, 26}, {"simflank", 1, 0, 27}, {"coverage", 0, 0, 28}, {"covflank", 1, 0, 29}, {"frame", 0, 0, 30},
                                      {"link", 0, 0, 31}, {"linkdist", 1, 0, 32}, {"partners", 0, 0, 33}, {"fragsize", 0, 0, 34},
                                      {"known", 1, 0, 35}, {"knownslop", 1, 0, 36}, {"bedpe", 0, 0, 37},
+                                     {"context", 0, 0, 38}, {"ctxflank", 1, 0, 39},
                                      {"f", 0, 0, 5},  // (-f used to complete to -fast alone; it still means it beside -frame)
                                      {0, 0, 0, 0}};
   Options o;
@@ -285,6 +294,8 @@ static Options parse_options(int argc, char *argv[])
     case 35: o.known_file = optarg; break;
     case 36: number(o.knownslop, o.knownslop_given); break;
     case 37: o.bedpe = true; break;
+    case 38: o.context = true; break;
+    case 39: number(o.ctxflank, o.ctxflank_given); break;
     default: std::cerr << "Error: cannot parse arguments.\n"; exit(1);
     }
   }

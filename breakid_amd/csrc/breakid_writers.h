@@ -419,6 +419,50 @@ struct KnownCall
   // what both breakends of the call end their INFO with
   string info() const;
 };
+// -context: the twin files' columns (bk_window_context of the four flank windows bk_call_windows gives the call); with -normal the same
+// eighteen once more, from the same windows on the normal's records
+static const char *CONTEXT_NAMES[9] = {"Cx_Reads", "Cx_MeanMQ", "Cx_MQ0", "Cx_LowQ", "Cx_Clip", "Cx_Improper", "Cx_Orphan", "Cx_Dup", "Cx_SecSup"};
+static string context_columns(const char *prefix)
+{
+  string s;
+  for (int side = 1; side <= 2; ++side)
+    for (const char *name : CONTEXT_NAMES) s += string("\t") + prefix + name + std::to_string(side);
+  return s;
+}
+
+// One written call: per side the sum of its two flank windows' rows (membership is by start, so adjacent windows add exactly), on the
+// sample's records and on the normal's.  Every ratio is a quotient of two doubles made from the integers; "." where reads == 0.
+struct ContextCall
+{
+  struct bk_window_ctx tumor[2] = {}, normal[2] = {};
+  static void add(struct bk_window_ctx &into, const struct bk_window_ctx &x)
+  {
+    into.mapq_sum += x.mapq_sum;
+    into.reads += x.reads, into.mq0 += x.mq0, into.lowq += x.lowq, into.clipped += x.clipped;
+    into.improper += x.improper, into.orphan += x.orphan, into.dup += x.dup, into.secsup += x.secsup;
+  }
+  static string ratio(const char *format, uint64_t part, uint32_t reads) { return reads ? CoverageCall::fixed(format, (double) part / (double) reads) : string("."); }
+  static string mean_mq(const struct bk_window_ctx &x) { return ratio("%.1f", x.mapq_sum, x.reads); }
+  static string mq0(const struct bk_window_ctx &x) { return ratio("%.3f", x.mq0, x.reads); }
+  static string fields(const struct bk_window_ctx *ctx)
+  {
+    std::ostringstream o;
+    for (int s = 0; s < 2; ++s)
+    {
+      const struct bk_window_ctx &x = ctx[s];
+      o << "\t" << x.reads << "\t" << mean_mq(x) << "\t" << mq0(x) << "\t" << ratio("%.3f", x.lowq, x.reads) << "\t" << ratio("%.3f", x.clipped, x.reads) << "\t"
+        << ratio("%.3f", x.improper, x.reads) << "\t" << x.orphan << "\t" << x.dup << "\t" << x.secsup;
+    }
+    return o.str();
+  }
+  // what the breakend of side s ends its INFO with
+  string info(int s) const
+  {
+    string t = ";CXN=" + std::to_string(tumor[s].reads);
+    if (tumor[s].reads) t += ";MQ0F=" + mq0(tumor[s]) + ";MEANMQ=" + mean_mq(tumor[s]);
+    return t;
+  }
+};
 // -clip -normal: what _fusion_rescued_normal.txt adds to a row of _fusion_rescued.txt
 static const char *RESCUED_COLUMNS_NORMAL = "\tNormal_DRP\tNormal_ClipAt1\tNormal_ClipAt2\tNormal_Depth1\tNormal_Depth2";
 
@@ -449,6 +493,7 @@ using LinkMap = std::map<uint64_t, LinkCall>;  // every voted call, whichever fi
 using PartnerMap = std::map<uint64_t, PartnerCall>;
 using FragsizeMap = std::map<uint64_t, FragsizeCall>;
 using KnownMap = std::map<uint64_t, KnownCall>;
+using ContextMap = std::map<uint64_t, ContextCall>;
 
 // -clip: the rescued clusters in the order of _fusion_rescued.txt, calls[k] to rows[k]; with -evidence the clipped reads at the peaks
 // of the written ones (bk_clip_reads: the rows of sites 2 * j and 2 * j + 1 belong to the j-th written row)
@@ -491,7 +536,7 @@ struct Twin
 // The twins of this run, the reference's own two files first.  An option that adds columns to the calls adds its entry here.
 static vector<Twin> fusion_twins(const Options &o, const CallTables &t, const ConsensusMap &cons, const HomologyMap &hom, const SimilarMap &sim,
                                  const CoverageMap &cov, const FrameMap &frame, const LinkMap &link, const PartnerMap &partners,
-                                 const FragsizeMap &frags, const KnownMap &known)
+                                 const FragsizeMap &frags, const KnownMap &known, const ContextMap &context)
 {
   const bool with_normal = o.with_normal();  // (a tumour without calls still gets header-only twins)
   vector<Twin> twins;
@@ -581,6 +626,13 @@ static vector<Twin> fusion_twins(const Options &o, const CallTables &t, const Co
     twins.push_back({"_known", KNOWN_COLUMNS, [&known](const OutRow &r, string &tail) {
                        if (!known.count(r.idx)) return false;
                        tail = known.at(r.idx).fields();
+                       return true;
+                     }});
+  if (o.context)
+    twins.push_back({"_context", context_columns("") + (with_normal ? context_columns("Normal_") : ""), [&context, with_normal](const OutRow &r, string &tail) {
+                       if (!context.count(r.idx)) return false;
+                       const ContextCall &c = context.at(r.idx);
+                       tail = ContextCall::fields(c.tumor) + (with_normal ? ContextCall::fields(c.normal) : "");
                        return true;
                      }});
   return twins;
@@ -692,6 +744,8 @@ struct VcfInput
   const FragsizeMap *frags = nullptr;
   // -known (else null; never for the rescued clusters): KNOWN / KNAMES, and KBEST where there is a hit, on both breakends, behind everything else
   const KnownMap *known = nullptr;
+  // -context (else null; never for the rescued clusters): CXN, and MQ0F / MEANMQ where the side has a read, of the breakend's own side, behind everything else
+  const ContextMap *context = nullptr;
 };
 
 static char nib_base(const string &nib_dir, const string &chr, long pos1)  // the base at a 1-based position; N without a file or beyond it
@@ -824,6 +878,7 @@ static bool write_vcf(const string &path, const vector<OutRow> &rows, const VcfI
         if (in.partners && in.partners->count(r.idx)) o << in.partners->at(r.idx).info(s);
         if (in.frags && in.frags->count(r.idx)) o << in.frags->at(r.idx).info();
         if (in.known && in.known->count(r.idx)) o << in.known->at(r.idx).info();
+        if (in.context && in.context->count(r.idx)) o << in.context->at(r.idx).info(s);
         o << "\t" << (in.gsup ? "GT:GQ:DR:DV:RR:RV" : "DV:RV") << "\t" << vcf_sample(r.c.n_drp, r.c.n_sr, in.gsup ? &(*in.gsup)[r.idx] : nullptr, s);
         if (in.with_normal) o << "\t" << vcf_sample(in.nsup[r.idx].n_drp, in.nsup[r.idx].n_sr, in.gsup_normal ? &(*in.gsup_normal)[r.idx] : nullptr, s);
       }
@@ -894,6 +949,10 @@ static bool write_vcf(const string &path, const vector<OutRow> &rows, const VcfI
     v << "##INFO=<ID=KNOWN,Number=1,Type=Integer,Description=\"Entries of the panel of known junctions that hold both breakpoints of the call\">\n"
          "##INFO=<ID=KNAMES,Number=1,Type=Integer,Description=\"Different names among those entries\">\n"
          "##INFO=<ID=KBEST,Number=1,Type=String,Description=\"Name of the entry with the largest score among them\">\n";
+  if (in.context && !in.rescued)
+    v << "##INFO=<ID=CXN,Number=1,Type=Integer,Description=\"Primary alignments, duplicates and failed reads aside, that start within the context flank of this breakpoint, before any mapping-quality filter\">\n"
+         "##INFO=<ID=MQ0F,Number=1,Type=Float,Description=\"Share of those alignments with mapping quality 0\">\n"
+         "##INFO=<ID=MEANMQ,Number=1,Type=Float,Description=\"Mean mapping quality of those alignments\">\n";
   if (in.rescued) v << "##INFO=<ID=SC,Number=1,Type=Integer,Description=\"Soft-clipped reads without an SA tag that end at this position (the clip peak)\">\n";
   if (in.gsup)
     v << "##FORMAT=<ID=GT,Number=1,Type=String,Description=\"Genotype\">\n"

@@ -615,6 +615,47 @@ int bk_window_coverage(bk_ctx *records, const struct bk_cov_window *windows, uin
  * list of bk_init (it must cover both tids).  Returns BK_OK, or BK_ERR_ARG for a null argument or flank == 0. */
 int bk_call_windows(const bk_cluster *c, int right1, int right2, uint32_t flank, const uint32_t *target_len, struct bk_cov_window out[5]);
 
+/* ---- window context: record classes and mapping quality of the records that start inside arbitrary windows ------------------------
+ * What the alignments around a breakpoint looked like before any filter: every record-level call above applies its mapping-quality
+ * and flag filter first and reports what survived.  A locus where a third of the reads have mapping quality 0 is a paralogue or a
+ * repeat whatever its read support says; unmapped mates mark an insertion site.  bk_window_context answers any number of windows of
+ * any length, each in time that does not depend on its length.  Every output is an integer.
+ * Membership is by leftmost aligned position, NOT by overlap: record i belongs to window k = (T, a, b), 0-based and half-open, when
+ * tid[i] == T and a <= pos[i] < b.  Adjacent half-open windows are therefore disjoint and their rows add: the row of [a, b) is the
+ * sum of the rows of [a, m) and [m, b).  (bk_window_coverage counts aligned bases by overlap; this call counts records by start.)
+ * Record i is mapped when tid[i] >= 0 and flag 0x4 is clear.  The base set: mapped records with none of 0x100 0x200 0x400 0x800.
+ * 0x1 is not required and neither is a reference length, so a record with an empty CIGAR or with 100S is in it.  A row counts:
+ *   reads     the base set
+ *   mapq_sum  the sum of mapq over the base set, in 64 bits
+ *   mq0       base set, mapq == 0
+ *   lowq      base set, mapq < mapq_min: 0 for mapq_min == 0, and mq0 is among them otherwise
+ *   clipped   base set, CIGAR not empty, and the first or the last operation is S after one leading and one trailing H have been
+ *             skipped: H S ... and ... S H count, a hard clip alone does not, an S inside the CIGAR does not, H alone is not clipped
+ *   improper  base set, 0x1 set, 0x8 clear, 0x2 clear
+ *   orphan    base set, 0x1 and 0x8 set: reads whose mate is unmapped
+ *   dup       mapped, 0x400 set, none of 0x100 0x200 0x800
+ *   secsup    mapped, 0x100 or 0x800 set; 0x200 and 0x400 do not matter
+ * A record with tid >= 0 and 0x4 set (an unmapped mate placed beside its partner) counts nowhere.  T < 0, T >= n_targets and
+ * b <= a give a zero row.  A window is not clamped against the contig length: no record lies beyond it.
+ * How: one streaming pass classifies every record and sums the nine counters of every tile of 256 records; exclusive scans in 64
+ * bits make them prefixes.  With h(x) = the first record of T with pos >= x, the records in front of h(x) are a prefix of the table:
+ * a counter's value there is the prefix of tile h / 256 plus the at most 255 records of that tile in front of h, classified by the
+ * same function.  A row is the value at h(b) less the value at h(a).  No atomics anywhere: two runs, and any permutation of the
+ * windows, give the same bytes row for row.  lowq depends on mapq_min, so the tile sums are rebuilt by every call.  The struct has
+ * no typedef. */
+struct bk_window_ctx { uint64_t mapq_sum; uint32_t reads, mq0, lowq, clipped, improper, orphan, dup, secsup; };   /* 40 bytes */
+/* records: a context that holds a record table, not a shard (bk_shard_*); bk_isize_stats need not have run, because no record
+ * reaches across an edge here.  windows: host memory, struct bk_cov_window as above.  *out (n rows) is library-owned until the next
+ * call or bk_free(records).  BK_ERR_ARG (with the reason in bk_last_error) for a null out, null windows with n > 0, a context
+ * without a table, shards, mapq_min < 0 and a window whose reserved is not 0; BK_ERR_LIMIT beyond 2^30 windows.  n == 0 and a table
+ * without records are no errors (every row is then zero).  It changes nothing a later bk_fetch or stage returns, and works on every
+ * table form bk_window_coverage does.
+ * bk_timing: scope `window_context`, with `window_context_tiles` (the tile pass and its scans) and `window_context_windows` (the
+ * window kernel) inside it.  bk_timing_touched of `window_context`: 19 bytes of every record (flag 2, mapq 1, tid 4, cigar_off 4,
+ * and 8 for the first and the last CIGAR word), 40 bytes per tile (five 64-bit words: mapq_sum, and the eight counts two to a
+ * word), 16 + 40 bytes per window; the partial tiles the windows' edges visit are not modelled. */
+int bk_window_context(bk_ctx *records, const struct bk_cov_window *windows, uint64_t n, int mapq_min, const struct bk_window_ctx **out);
+
 /* ---- fusion frame: the 5' and 3' partner and the reading frame of every call ------------------------------------------------------
  * Whether two breakpoints, each with the side on which sequence is retained, can give a fusion transcript at all, which transcript
  * is its 5' partner and whether the reading frame is kept.  A frame call is a property of a pair of isoforms, so every transcript
