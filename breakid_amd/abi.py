@@ -85,6 +85,11 @@ KNOWN_CALL = np.dtype([("n_hits", "<u4"), ("n_oriented", "<u4"), ("n_opposed", "
 assert KNOWN_ENTRY.itemsize == 40 and KNOWN_SITE.itemsize == 24 and KNOWN_CALL.itemsize == 40
 KNOWN_MAX_SLOP = 1000000  # BK_KNOWN_MAX_SLOP
 KNOWN_NO_SCORE = -2147483648  # BK_KNOWN_NO_SCORE
+SPLIT_JUNCTION = np.dtype([("tid1", "<i4"), ("pos1", "<u4"), ("tid2", "<i4"), ("pos2", "<u4"), ("n_reads", "<u4"), ("n_tuples", "<u4"), ("n_exact", "<u4"), ("lo1", "<u4"), ("hi1", "<u4"),
+                           ("lo2", "<u4"), ("hi2", "<u4"), ("n_own", "<u4", (2,)), ("mapq_sum", "<u4", (2,)), ("call", "<i4"), ("right1", "u1"), ("right2", "u1"), ("call_crossed", "u1"),
+                           ("reserved", "u1"), ("top_reads", "<u4")])  # struct bk_split_junction; pos 1-based
+assert SPLIT_JUNCTION.itemsize == 72
+SJ_MAX_TOL = 100  # BK_SJ_MAX_TOL
 STRAND_NONE, STRAND_LEFT, STRAND_RIGHT = 0, 1, 2  # BK_STRAND_*
 # the columns of a bk_txmodel, in the struct's order (ex_off has n_tx + 1 entries, ex_start / ex_end n_parts)
 TXMODEL_COLS = [("tid", np.int32), ("tx_start", np.uint32), ("tx_end", np.uint32), ("strand", np.uint8), ("ex_off", np.uint32), ("ex_start", np.uint32), ("ex_end", np.uint32)]

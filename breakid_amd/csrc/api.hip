@@ -27,6 +27,7 @@
 #include "partners.h"
 #include "fragsize.h"
 #include "known.h"
+#include "sjcall.h"
 #include "exclude.h"
 #include "ahc.h"
 #include "lanes.h"
@@ -186,6 +187,12 @@ struct bk_ctx
   // known junctions (bk_known_calls)
   KnownBufs knb;
   std::vector<struct bk_known_call> f_known;
+  // split junctions (bk_split_junctions)
+  SjBufs sjb;
+  SjStats sj_stats;
+  std::vector<SjClaim> sj_claims;  // the voted rows' breakpoints, sorted; valid until the breakpoint stage runs again
+  bool sj_claims_valid = false;
+  std::vector<struct bk_split_junction> f_sj;
 
   // test hooks of the primitives (bk_debug_scan, bk_debug_radix_sort): buffers that live as long as the context, as a stage's do
   prims::RadixBufs dbg_radix;
@@ -573,6 +580,7 @@ int bk_upload_records(bk_ctx *ctx, const bk_soa *s, int mem_space)
     if (s->n > 0xFFFFFFF0ull) throw bk_error(BK_ERR_LIMIT, "more than 2^32 records in one context (shard across GPUs)");
     ctx->stream_done = ctx->stats_done = ctx->clustered = false;
     ctx->joined = ctx->bp_done = ctx->shard = false;
+    ctx->sj_claims_valid = false;
     ctx->ext_cand = nullptr;
     ctx->ext_split = nullptr;
     ctx->ext_clusters = nullptr;
@@ -804,6 +812,7 @@ int bk_discordant_pairs(bk_ctx *ctx, int mapq_min, double w, uint64_t *n_pairs, 
     ctx->clustered = false;
     ctx->joined = true;
     ctx->bp_done = false;
+    ctx->sj_claims_valid = false;
     ctx->join_w = w;
     if (n_pairs) *n_pairs = ctx->jr.n_pairs;
     if (n_groups) *n_groups = ctx->jr.n_groups;
@@ -837,6 +846,7 @@ int bk_cluster_summary(bk_ctx *ctx, double w, uint64_t *n_clusters)
   return guarded(ctx, [&] {
     if (!ctx->clustered) throw bk_error(BK_ERR_ARG, "bk_cluster_summary: call bk_mask_and_cluster first");
     ctx->bp_done = false;
+    ctx->sj_claims_valid = false;
     // (lex_to_num, glex and gkey are tables over the groups of the join; the list's groups are the same ones: lanes.hip)
     if (ctx->stage.list.ng != ctx->jr.n_groups) throw bk_error(BK_ERR_HIP, "bk_cluster_summary: the clustered list and the join disagree on the groups (internal error)");
     Scope s(ctx, "cluster_summary");
@@ -861,6 +871,7 @@ int bk_split_breakpoints(bk_ctx *ctx, double w, uint64_t *n_valid)
                         ctx->d_hdr.get<int32_t>(), ctx->bb, ctx->st);
     }
     ctx->bp_done = true;
+    ctx->sj_claims_valid = false;
     if (n_valid) *n_valid = count_valid_clusters(ctx->clusters_ptr(), ctx->n_clusters, ctx->bb, ctx->st);
   });
 }
@@ -1836,6 +1847,96 @@ int bk_known_calls(bk_ctx *ctx, const struct bk_known_entry *entries, uint64_t n
     }
     rows_to_host(ctx, d_res, n, ctx->f_known);
     *out = ctx->f_known.data();
+  });
+}
+
+// Junction calls from the split-evidence tuples alone (include/breakid_hip.h, sjcall.hip).  `rows` (null: the context's own voted rows,
+// once bk_split_breakpoints has run) is the cluster table in which the claimed row is looked up.
+static void sj_claim_table(const bk_cluster *cl, uint64_t n, std::vector<SjClaim> &claims)
+{
+  // the voted rows' exact breakpoints, both orientations, sorted: they are few
+  claims.clear();
+  for (uint64_t r = 0; r < n && r < 0x40000000ull; ++r)
+  {
+    const bk_cluster &c = cl[r];
+    if (!(c.flags & 2u) || c.p1_tid < 0 || c.p2_tid < 0 || c.p2_exact < 0) continue;
+    claims.push_back(SjClaim{((uint64_t) (c.p1_tid + 1) << 32) | c.p1_exact, c.p2_tid, (uint32_t) c.p2_exact, (uint32_t) (2 * r), 0});
+    claims.push_back(SjClaim{((uint64_t) (c.p2_tid + 1) << 32) | (uint32_t) c.p2_exact, c.p1_tid, c.p1_exact, (uint32_t) (2 * r + 1), 0});
+  }
+  std::sort(claims.begin(), claims.end(), [](const SjClaim &a, const SjClaim &b) { return a.key != b.key ? a.key < b.key : a.code < b.code; });
+}
+
+static void sj_run(bk_ctx *ctx, const std::string &who, int mapq_min, uint32_t tol, uint32_t min_reads, const bk_cluster *rows, uint64_t n_rows, bool own_rows,
+                   const struct bk_split_junction **out, uint64_t *count)
+{
+  if (!out || !count) throw bk_error(BK_ERR_ARG, who + ": null output");
+  if (ctx->shard) throw bk_error(BK_ERR_ARG, who + ": sharded contexts (bk_shard_*) are not supported");
+  if (!ctx->stream_done || !ctx->splits_sorted) throw bk_error(BK_ERR_ARG, who + ": call bk_split_evidence first");
+  if (mapq_min < 0) throw bk_error(BK_ERR_ARG, who + ": mapq_min below 0");
+  if (tol > BK_SJ_MAX_TOL) throw bk_error(BK_ERR_ARG, who + ": tol above " + std::to_string(BK_SJ_MAX_TOL));
+  if (min_reads == 0) throw bk_error(BK_ERR_ARG, who + ": min_reads must be at least 1");
+  if (!own_rows && n_rows && !rows) throw bk_error(BK_ERR_ARG, who + ": null rows");
+  if (ctx->nt > 0x40000000) throw bk_error(BK_ERR_LIMIT, who + ": more than 2^30 reference sequences (the group key takes two contig numbers and two sides in 64 bits)");
+  SjInput in;
+  in.split = ctx->d_split.get<bk_split>();
+  in.n = ctx->hc.n_split;
+  in.flag = ctx->rec.flag;
+  in.mapq = ctx->rec.mapq;
+  in.n_rec = ctx->rec.n;
+  in.tprefix = ctx->d_tprefix.get<uint32_t>();
+  in.nt = ctx->nt;
+  for (const uint32_t l : ctx->tlen) in.max_len = std::max(in.max_len, l);
+  if (in.n && (!ctx->have_records || !in.flag || !in.mapq)) throw bk_error(BK_ERR_ARG, who + ": the record table lacks a column");
+  std::vector<SjClaim> given;
+  const std::vector<SjClaim> *claims = &given;
+  if (!own_rows)
+    sj_claim_table(rows, n_rows, given);
+  else if (ctx->bp_done)
+  {
+    // the context's own table: fetched and sorted once, kept until the breakpoint stage runs again
+    if (!ctx->sj_claims_valid)
+    {
+      std::vector<bk_cluster> cl;
+      rows_to_host(ctx, ctx->clusters_ptr(), ctx->n_clusters, cl);
+      sj_claim_table(cl.data(), cl.size(), ctx->sj_claims);
+      ctx->sj_claims_valid = true;
+    }
+    claims = &ctx->sj_claims;
+  }
+  struct bk_split_junction *d_rows;
+  ctx->sj_stats = SjStats{};
+  {
+    Scope s(ctx, "split_junctions");
+    split_junctions(in, mapq_min, tol, min_reads, claims->data(), claims->size(), ctx->sjb, ctx->st, &d_rows, &ctx->sj_stats);
+  }
+  if (ctx->timing && !ctx->timers.empty()) ctx->timers.back().bytes = ctx->timers.back().touched = ctx->sj_stats.touched();  // (include/breakid_hip.h)
+  const SjStats &t = ctx->sj_stats;
+  if (bk_debug("sj"))
+    fprintf(stderr, "%s: %llu tuples, %llu eligible, %llu exact, %llu calls, %llu rounds of label propagation, %llu returned\n", who.c_str(), (unsigned long long) t.n,
+            (unsigned long long) t.eligible, (unsigned long long) t.exact, (unsigned long long) t.calls, (unsigned long long) t.rounds, (unsigned long long) t.written);
+  rows_to_host(ctx, d_rows, t.written, ctx->f_sj);
+  *out = ctx->f_sj.data();
+  *count = t.written;
+}
+
+int bk_split_junctions(bk_ctx *ctx, int mapq_min, uint32_t tol, uint32_t min_reads, const struct bk_split_junction **out, uint64_t *count)
+{
+  return guarded(ctx, [&] { sj_run(ctx, "bk_split_junctions", mapq_min, tol, min_reads, nullptr, 0, true, out, count); });
+}
+
+// test hook: the same call with the claimed row looked up in a cluster table of the caller's (a context's own rows put the lower end first)
+int bk_debug_split_junctions(bk_ctx *ctx, int mapq_min, uint32_t tol, uint32_t min_reads, const bk_cluster *rows, uint64_t n_rows, const struct bk_split_junction **out,
+                             uint64_t *count)
+{
+  return guarded(ctx, [&] { sj_run(ctx, "bk_debug_split_junctions", mapq_min, tol, min_reads, rows, n_rows, false, out, count); });
+}
+
+int bk_split_junction_counts(bk_ctx *ctx, uint64_t out[6])
+{
+  return guarded(ctx, [&] {
+    if (!out) throw bk_error(BK_ERR_ARG, "bk_split_junction_counts: null out");
+    const SjStats &t = ctx->sj_stats;
+    out[0] = t.n; out[1] = t.eligible; out[2] = t.exact; out[3] = t.calls; out[4] = t.claimed; out[5] = t.rounds;
   });
 }
 

@@ -1672,6 +1672,51 @@ static void write_evidence_files(const Options &o, const Sample &tumor, const Ca
   }
 }
 
+// ---- -junctions: junction calls from the split reads alone --------------------------------------------------------------------------
+// One call of bk_split_junctions on the sample's own tuples (-q is its mapq_min; -x applies by itself, because tuples come from kept
+// records); the calls that no voted row claims get the depth at their two positions (one call of bk_base_depth) and the gene on either
+// side.  It runs behind every other stage and reads what they left: no other file changes.
+static void split_junction_calls(const Options &o, const Sample &tumor, const vector<Txpt> &txpts)
+{
+  const struct bk_split_junction *calls = nullptr;
+  uint64_t n = 0, counts[6] = {};
+  int rc = bk_split_junctions(tumor.ctx, o.qual, (uint32_t) o.jtol, (uint32_t) o.jsupport, &calls, &n);
+  if (rc == BK_OK) rc = bk_split_junction_counts(tumor.ctx, counts);
+  if (rc != BK_OK) die(tumor, rc);
+  vector<SjRow> rows;
+  vector<int32_t> q_tid;
+  vector<uint32_t> q_pos;
+  for (uint64_t i = 0; i < n; ++i)
+  {
+    if (calls[i].call >= 0) continue;
+    SjRow r;
+    r.j = calls[i];
+    r.index = i;
+    r.depth[0] = r.depth[1] = 0;
+    rows.push_back(r);
+    q_tid.insert(q_tid.end(), {calls[i].tid1, calls[i].tid2});
+    q_pos.insert(q_pos.end(), {calls[i].pos1, calls[i].pos2});
+  }
+  const uint32_t *depth = nullptr;
+  if (!rows.empty() && (rc = bk_base_depth(tumor.ctx, q_tid.data(), q_pos.data(), q_tid.size(), &depth)) != BK_OK) die(tumor, rc);
+  for (size_t k = 0; k < rows.size(); ++k)
+  {
+    SjRow &r = rows[k];
+    const uint32_t pos[2] = {r.j.pos1, r.j.pos2};
+    const int32_t tid[2] = {r.j.tid1, r.j.tid2};
+    for (int s = 0; s < 2; ++s)
+    {
+      string exon, strand;
+      r.depth[s] = depth[2 * k + s];
+      r.chr[s] = tumor.names[tid[s]];
+      annotate_side(txpts, r.chr[s], (long) pos[s], r.gene[s], exon, strand);
+    }
+  }
+  write_junction_files(o, rows);
+  std::cout << "junctions: " << counts[1] << " tuples eligible, " << counts[2] << " exact, " << n << " calls, " << n - rows.size() << " claimed by a voted call, " << rows.size()
+            << " written" << std::endl;
+}
+
 // write_enspan_params (:1170-1182); an option that changes what is called adds its line behind the reference's
 static void write_params(const Options &o, double w)
 {
@@ -1703,6 +1748,8 @@ static void write_params(const Options &o, double w)
   if (o.known()) p << "known_slop\t" << o.knownslop << std::endl;
   if (o.bedpe) p << "bedpe" << std::endl;
   if (o.context) p << "context_flank\t" << o.ctxflank << std::endl;
+  if (o.junctions) p << "junction_min_support\t" << o.jsupport << std::endl;
+  if (o.junctions) p << "junction_tol\t" << o.jtol << std::endl;
 }
 
 // BreakID.cc:175-191.  scan_pairs_count and after_cluster_count are never updated by the reference (always 0);
@@ -1800,6 +1847,7 @@ int main(int argc, char *argv[])
     std::cerr << "Error: cannot write " << o.out_file << "_fusion.bedpe: the evidence tables do not cover every call" << std::endl;
     exit(1);
   }
+  if (o.junctions) split_junction_calls(o, tumor, txpts);
   write_params(o, run.w);
   const clock_t end = clock();
   std::cout << "the fusion process of file " << o.inp_file << "  costs time: " << (end - start) / double(CLOCKS_PER_SEC) << " seconds" << std::endl;

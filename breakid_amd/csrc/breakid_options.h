@@ -53,6 +53,9 @@ int bk_fragment_bounds(double mean, double sd, int32_t *lo, int32_t *hi) __attri
 // -known
 int bk_known_calls(bk_ctx *ctx, const struct bk_known_entry *entries, uint64_t n_entries, const struct bk_known_site *sites, uint64_t n, uint32_t slop,
                    const struct bk_known_call **out) __attribute__((weak));
+// -junctions (junction calls from the split reads alone; bk_base_depth is listed with -clip)
+int bk_split_junctions(bk_ctx *ctx, int mapq_min, uint32_t tol, uint32_t min_reads, const struct bk_split_junction **out, uint64_t *count) __attribute__((weak));
+int bk_split_junction_counts(bk_ctx *ctx, uint64_t out[6]) __attribute__((weak));
 // -dedup
 int bk_unique_support(bk_ctx *ctx, const struct bk_unique_support **out, uint64_t *count, const uint64_t **first, uint64_t *n_rows) __attribute__((weak));
 // -clip (the soft-clip evidence, the depth at the rescued positions and the rescue rule)
@@ -109,15 +112,18 @@ static const char *HELP =
      \t -knownslop \t bases up to which a breakpoint beside an interval of the panel still falls into it, 0 to 1000000 (with -known)  [100]\n \
      \t -bedpe     \t also write the calls as BEDPE (*_fusion.bedpe), the format -known reads  \n \
      \t -context   \t what the alignments that start beside both breakpoints of every call look like before any filter: mean mapping quality, shares of MAPQ 0, low MAPQ, soft-clipped and improper reads, unmapped mates, duplicates, secondary and supplementary alignments (twin files *_context.txt; CXN / MQ0F / MEANMQ with -vcf)  \n \
-     \t -ctxflank  \t bases either side of a breakpoint in which a read must start, about one fragment length, 1 to 1000000 (with -context)  [500]\n ";
+     \t -ctxflank  \t bases either side of a breakpoint in which a read must start, about one fragment length, 1 to 1000000 (with -context)  [500]\n \
+     \t -junctions \t also call junctions from the split reads alone, with or without discordant pairs: deletions and duplications shorter than the library's spread, small inversions (*_junctions.txt; *_junctions.bedpe with -bedpe)  \n \
+     \t -jsupport  \t distinct reads a junction needs, 1 to 1000000 (with -junctions)  [3]\n \
+     \t -jtol      \t bases up to which two junctions with equal sides are one call, 0 to 100 (with -junctions)  [2]\n ";
 
 struct Options
 {
   std::string inp_file, out_file, nib_dir, normal_file, exclude_file, known_file, build = "hg19";
   int qual = 20, device = 0, n_gpus = 0, transport = BK_TRANSPORT_AUTO;  // -gpus N: one sample over N GPUs (include/breakid_multi.h)
   bool fast = false, all = false;                                        // -all: no gene-pair and repeat filter (the _fusion_all files)
-  bool genotype = false, vcf = false, evidence = false, clip = false, dedup = false, consensus = false, homology = false, similar = false, coverage = false, frame = false, link = false, partners = false, fragsize = false, bedpe = false, context = false;
-  bool anchor_given = false, minclip_given = false, clipsupport_given = false, conslen_given = false, homshift_given = false, homins_given = false, simflank_given = false, covflank_given = false, linkdist_given = false, knownslop_given = false, ctxflank_given = false;
+  bool genotype = false, vcf = false, evidence = false, clip = false, dedup = false, consensus = false, homology = false, similar = false, coverage = false, frame = false, link = false, partners = false, fragsize = false, bedpe = false, context = false, junctions = false;
+  bool anchor_given = false, minclip_given = false, clipsupport_given = false, conslen_given = false, homshift_given = false, homins_given = false, simflank_given = false, covflank_given = false, linkdist_given = false, knownslop_given = false, ctxflank_given = false, jsupport_given = false, jtol_given = false;
   long anchor = 10;                      // -anchor: bases a reference read must cover on either side of the breakpoint base
   long min_clip = 10, clip_support = 3;  // -minclip: shortest clip that counts; -clipsupport: reads at one position a rescued side needs
   long conslen = 64;                     // -conslen: longest junction sequence per side
@@ -127,6 +133,7 @@ struct Options
   long linkdist = 1000;                  // -linkdist: the distance up to which bk_link_calls takes two breakends as near
   long knownslop = 100;                  // -knownslop: the distance up to which bk_known_calls lets a breakend fall into an interval
   long ctxflank = 500;                   // -ctxflank: the bases either side of a cut in which bk_window_context counts the records that start there
+  long jsupport = 3, jtol = 2;           // -jsupport, -jtol: min_reads and tol of bk_split_junctions
   bool multi() const { return n_gpus >= 1; }  // the sharded run
   bool known() const { return !known_file.empty(); }
   bool with_normal() const { return !normal_file.empty(); }
@@ -173,6 +180,7 @@ static void check_options(const Options &o)
   const Feature known{"-known", o.known(), false, bk_known_calls && bk_junctions && bk_junction_sides};
   const Feature bedpe{"-bedpe", o.bedpe, false, bk_junctions && bk_junction_sides};
   const Feature context{"-context", o.context, false, bk_window_context && bk_call_windows && bk_junctions && bk_junction_sides};
+  const Feature junctions{"-junctions", o.junctions, false, bk_split_junctions && bk_split_junction_counts && bk_base_depth};
   const Feature consensus{"-consensus", o.consensus, false, bk_clip_consensus && bk_clip_reads && bk_evidence && bk_junctions && bk_junction_sides};
   const Feature clip{"-clip", o.clip, false, bk_clip_support && bk_clip_reads && bk_base_depth && bk_clip_rescue && bk_junctions && bk_junction_sides};
   const Feature exclude{"-x", o.exclude(), true, bk_exclude_regions && bk_multi_run_ex && bk_multi_run_bam_ex && bk_multi_excluded};
@@ -216,6 +224,9 @@ static void check_options(const Options &o)
       gpus(bedpe), library(bedpe),
       rule(o.ctxflank_given && !o.context, "-ctxflank needs -context."), gpus(context), library(context),
       rule(o.context && !in_range(o.ctxflank, 1, 1000000), "-ctxflank must be a number from 1 to 1000000."),
+      rule((o.jsupport_given || o.jtol_given) && !o.junctions, "-jsupport and -jtol need -junctions."), gpus(junctions),
+      rule(o.junctions && !in_range(o.jsupport, 1, 1000000), "-jsupport must be a number from 1 to 1000000."),
+      rule(o.junctions && !in_range(o.jtol, 0, 100), "-jtol must be a number from 0 to 100."), library(junctions),
   };
   for (const Refusal &r : refusals)
   {
@@ -243,6 +254,7 @@ static Options parse_options(int argc, char *argv[])
                                      {"link", 0, 0, 31}, {"linkdist", 1, 0, 32}, {"partners", 0, 0, 33}, {"fragsize", 0, 0, 34},
                                      {"known", 1, 0, 35}, {"knownslop", 1, 0, 36}, {"bedpe", 0, 0, 37},
                                      {"context", 0, 0, 38}, {"ctxflank", 1, 0, 39},
+                                     {"junctions", 0, 0, 40}, {"jsupport", 1, 0, 41}, {"jtol", 1, 0, 42},
                                      {"f", 0, 0, 5},  // (-f used to complete to -fast alone; it still means it beside -frame)
                                      {0, 0, 0, 0}};
   Options o;
@@ -296,6 +308,9 @@ static Options parse_options(int argc, char *argv[])
     case 37: o.bedpe = true; break;
     case 38: o.context = true; break;
     case 39: number(o.ctxflank, o.ctxflank_given); break;
+    case 40: o.junctions = true; break;
+    case 41: number(o.jsupport, o.jsupport_given); break;
+    case 42: number(o.jtol, o.jtol_given); break;
     default: std::cerr << "Error: cannot parse arguments.\n"; exit(1);
     }
   }

@@ -684,6 +684,56 @@ static bool write_bedpe_files(const Options &o, const vector<OutRow> &rows, cons
   return true;
 }
 
+// -junctions: <prefix>_junctions.txt, the calls of bk_split_junctions that no voted row claims (a claimed one is a row of the fusion files
+// already), in the order of the call's table, and with -bedpe <prefix>_junctions.bedpe in the layout of write_bedpe_files: score = Reads,
+// strands from the sides, then sj<row>, Type, 0 and Reads.  Nothing is filtered beyond -jsupport.
+struct SjRow
+{
+  struct bk_split_junction j;
+  uint64_t index;  // in the table bk_split_junctions returned
+  uint32_t depth[2];
+  string chr[2], gene[2];
+};
+static const char *JUNCTION_COLUMNS =
+    "Junction\tChr1\tPos1\tSide1\tChr2\tPos2\tSide2\tType\tSize\tReads\tTuples\tExact\tTopReads\tOwn1\tOwn2\tMeanMQ1\tMeanMQ2\tSpan1\tSpan2\tDepth1\tDepth2\tGene1\tGene2";
+// translocation on different contigs; on one contig with pos1 < pos2 deletion for (L, R), duplication for (R, L), inversion for equal
+// sides; "." for anything else
+static const char *junction_type(const struct bk_split_junction &j)
+{
+  if (j.tid1 != j.tid2) return "translocation";
+  if (j.pos1 >= j.pos2) return ".";
+  return j.right1 == j.right2 ? "inversion" : j.right1 ? "duplication" : "deletion";
+}
+static void write_junction_files(const Options &o, const vector<SjRow> &rows)
+{
+  const size_t slash = o.out_file.find_last_of('/');
+  const string sample = slash == string::npos ? o.out_file : o.out_file.substr(slash + 1);
+  std::ofstream table((o.out_file + "_junctions.txt").c_str()), bedpe;
+  if (o.bedpe) bedpe.open((o.out_file + "_junctions.bedpe").c_str());
+  table << JUNCTION_COLUMNS << "\n";
+  char mq[2][32];
+  for (const SjRow &r : rows)
+  {
+    const struct bk_split_junction &j = r.j;
+    for (int k = 0; k < 2; ++k)
+      if (j.n_own[k])
+        snprintf(mq[k], sizeof mq[k], "%.1f", (double) j.mapq_sum[k] / (double) j.n_own[k]);
+      else
+        snprintf(mq[k], sizeof mq[k], ".");
+    table << "sj" << r.index << "\t" << r.chr[0] << "\t" << j.pos1 << "\t" << (j.right1 ? "R" : "L") << "\t" << r.chr[1] << "\t" << j.pos2 << "\t" << (j.right2 ? "R" : "L") << "\t"
+          << junction_type(j) << "\t";
+    if (j.tid1 == j.tid2)
+      table << (long long) j.pos2 - (long long) j.pos1;
+    else
+      table << ".";
+    table << "\t" << j.n_reads << "\t" << j.n_tuples << "\t" << j.n_exact << "\t" << j.top_reads << "\t" << j.n_own[0] << "\t" << j.n_own[1] << "\t" << mq[0] << "\t" << mq[1] << "\t"
+          << j.lo1 << "-" << j.hi1 << "\t" << j.lo2 << "-" << j.hi2 << "\t" << r.depth[0] << "\t" << r.depth[1] << "\t" << r.gene[0] << "\t" << r.gene[1] << "\n";
+    if (bedpe.is_open())
+      bedpe << r.chr[0] << "\t" << (long long) j.pos1 - 1 << "\t" << j.pos1 << "\t" << r.chr[1] << "\t" << (long long) j.pos2 - 1 << "\t" << j.pos2 << "\t" << (sample.empty() ? "." : sample)
+            << "\t" << j.n_reads << "\t" << (j.right1 ? "-" : "+") << "\t" << (j.right2 ? "-" : "+") << "\tsj" << r.index << "\t" << junction_type(j) << "\t0\t" << j.n_reads << "\n";
+  }
+}
+
 // -clip: <prefix>_fusion_rescued.txt, a table with the clip columns, and with -normal <prefix>_fusion_rescued_normal.txt: the same rows
 // with the normal's evidence at the rescued peaks behind them
 static void write_rescued_tables(const Options &o, const Rescued &rescued, const CallTables &t)

@@ -965,6 +965,96 @@ struct bk_known_call  { uint32_t n_hits, n_oriented, n_opposed, n_names, n_side[
  *   known_calls is their sum.  The intervals and entries that a site's walks read are not modelled. */
 int bk_known_calls(bk_ctx *ctx, const struct bk_known_entry *entries, uint64_t n_entries, const struct bk_known_site *sites, uint64_t n, uint32_t slop, const struct bk_known_call **out);
 
+/* ---- split junctions: junction calls from the split-evidence tuples alone ------------------------------------------------------------
+ * Every BK_STAGE_CLUSTERS row starts from a cluster of discordant pairs; a junction whose fragments are not discordant (a deletion
+ * or duplication shorter than the library's spread, a small inversion) has no row however many split reads cross it.  This call
+ * groups the tuples of BK_STAGE_SPLITS by the junction they state.  All arithmetic is integer, compared in signed 64-bit.
+ *   ends        The own end of a tuple is sec_* when flags & 1, else prim_*; the other end is the remaining one.  An end's position is
+ *               its *_bp; it is RIGHT (1) when *_bp == *_start, else LEFT (0), as for bk_junctions.  The own end's contig is the
+ *               tuple's tid, the record's real contig, not the interned *_chr.  The other end's contig is its interned *_chr when
+ *               0 <= chr < n_targets: the first header entry of that name.
+ *   eligible    A tuple is eligible when !(flags & 2), tid >= 0, the other contig is a header id as above, both positions lie in
+ *               1 .. target_len of their contig, the own record (row `rec` of the table, as bk_evidence.rec is) has neither 0x4 nor
+ *               0x200 set and mapq >= mapq_min, and the two ends are not identical in (contig, pos, right).
+ *   canonical   The two ends are ordered ascending by (contig, pos, right) and become end 1 and end 2; own_end (0 or 1) says which of
+ *               them the own end became.
+ *   exact       An exact junction is a maximal set of eligible tuples with equal (tid1, pos1, right1, tid2, pos2, right2).
+ *   near        Two exact junctions are near when tid1, tid2, right1 and right2 are equal, |pos1 - pos1'| <= tol and
+ *               |pos2 - pos2'| <= tol.
+ *   call        A connected component of the exact junctions under near (single linkage; tol == 0 makes every exact junction a
+ *               call).  Single linkage can chain: exact junctions each tol apart form one call however long the chain grows; lo / hi
+ *               show its extent.
+ *   reads       Read identity is qhash (64 bits) alone: n_reads counts the distinct qhash of a call's tuples.
+ * Row: (tid1, pos1, right1, tid2, pos2, right2) is the representative, the call's exact junction with the most distinct reads
+ * (top_reads of them), ties to the smallest in the order (tid1, tid2, right1, right2, pos1, pos2).  n_tuples and n_exact count the
+ * call's tuples and exact junctions; lo1 .. hi2 are the extremes of pos1 and pos2 over its exact junctions; n_own[k] counts the tuples
+ * with own_end == k and mapq_sum[k] adds their own records' mapq.  reserved = 0.
+ *   call        -1 unless bk_split_breakpoints has run and the context has voted rows (flags bit 1).  Then the smallest voted
+ *               BK_STAGE_CLUSTERS row that some exact junction of the call matches: straight, when tid1 == p1_tid, |pos1 - p1_exact|
+ *               <= 2, tid2 == p2_tid and |pos2 - p2_exact| <= 2 (the +-2 of the vote), or crossed, when the same holds with p1 and p2
+ *               exchanged.  Sides are not compared.  call_crossed = 0 when some exact junction matches that row straight, else 1 (0
+ *               without a row).
+ * Output: the calls with n_reads >= min_reads, ordered by their smallest exact junction in the order above.  Every output is a
+ * count, a sum, an extreme or an argmax with a fixed tie rule: two runs give the same bytes, and a renaming of the reads that keeps
+ * qhash equality gives the same rows.
+ * Hand example (chr1 = 0, chr2 = 1, every flags 0, every mapq 60, tol 2, min_reads 1).  Reads a, b, c: own end chr1 5000 LEFT, other
+ * end chr1 5250 RIGHT.  Read d, first alignment: own end chr1 5251 RIGHT, other end chr1 5001 LEFT (the own end becomes end 2); second
+ * alignment: own end chr1 5001 LEFT, other end chr1 5251 RIGHT.  Read e: own end chr2 700 RIGHT, other end chr1 5000 LEFT.  The exact
+ * junctions are (chr1 5000 L, chr1 5250 R) with 3 reads, (chr1 5001 L, chr1 5251 R) with 1 read in 2 tuples, and (chr1 5000 L,
+ * chr2 700 R).  Row 0: 0 5000 0 5250, n_reads 4, n_tuples 5, n_exact 2, lo1 5000, hi1 5001, lo2 5250, hi2 5251, n_own {4, 1},
+ * mapq_sum {240, 60}, call -1, right 0 1, top_reads 3.  Row 1: 0 5000 1 700, n_reads 1, n_tuples 1, n_exact 1, n_own {0, 1}, mapq_sum
+ * {0, 60}, right 0 1, top_reads 1.  With tol 0 there are three rows; with min_reads 3 only row 0.
+ * The struct has no typedef. */
+#define BK_SJ_MAX_TOL 100u
+struct bk_split_junction {
+  int32_t tid1; uint32_t pos1; int32_t tid2; uint32_t pos2;   /* the representative exact junction */
+  uint32_t n_reads, n_tuples, n_exact;   /* distinct qhash, tuples, exact junctions of the call */
+  uint32_t lo1, hi1, lo2, hi2;           /* min / max of pos1 and pos2 over the call's exact junctions */
+  uint32_t n_own[2];                     /* tuples whose own record carries end 1 / end 2 */
+  uint32_t mapq_sum[2];                  /* sum of the own records' mapq, by own_end */
+  int32_t call;                          /* BK_STAGE_CLUSTERS row that claims it, -1 without */
+  uint8_t right1, right2, call_crossed, reserved;
+  uint32_t top_reads;                    /* distinct reads of the representative */
+};                                       /* 72 bytes */
+/* ctx: after bk_split_evidence and not a shard (bk_shard_*); whether bk_split_breakpoints has run decides only `call`.  *out (*count
+ * rows) is library-owned until the next call or bk_free(ctx).  BK_ERR_ARG (with the reason in bk_last_error) for wrong call order,
+ * shards, null outputs, mapq_min < 0, tol > BK_SJ_MAX_TOL and min_reads == 0.  BK_ERR_LIMIT beyond 2^30 eligible tuples, and for a
+ * reference list of more than 2^30 sequences (the group key holds two contig numbers and two sides in 64 bits).  A context
+ * without tuples is no error: *count = 0.  It changes nothing a later bk_fetch or stage returns, and works on every table form the
+ * context can hold (host upload, BK_MEM_DEVICE with and without `side`, the table bk_exclude_regions left behind, the context of
+ * bk_bam_decode_device_ctx while its bk_bam_dev lives): of the records it reads flag and mapq alone.
+ * How: one lane per tuple classifies it; a scan compacts the e eligible tuples into 32-byte canonical rows.  Three stable LSD stages
+ * of the radix sort order them: by qhash (64 bits; run heads and a scan turn the hash into a dense rank), by (pos1, pos2) over
+ * 2 * bits(longest contig) bits, by ((tid1 * n_targets + tid2) << 2 | right1 << 1 | right2) over its bits in use.  Run heads and
+ * scans give the x exact junctions and their distinct reads; one wavefront per exact junction sums its tuples.  Components: one
+ * wavefront per exact junction finds, by binary search, the first exact junction of its group with pos1' >= pos1 - tol and deals
+ * the rows up to pos1 + tol to its lanes 64 a step, each lane testing pos2 and offering its row's label; the smallest becomes the
+ * exact junction's own label and, by an integer atomic minimum, that of the exact junction it pointed to so far; pointer jumping
+ * follows.  The host reads a changed flag between rounds; more than x + 1 rounds give
+ * BK_ERR_LIMIT (they cannot be needed: a label travels at least one near-step a round).  Nothing is capped: a locus with k exact
+ * junctions inside one window costs k * k for those, every round.  The exact junctions are then sorted by label and the tuples by
+ * (label, read rank), which makes every call a contiguous range of both; one wavefront per call reduces them.  The claimed row: the
+ * host sorts the voted rows' two orientations by ((tid + 1) << 32) | exact (they are few), one lane per exact junction searches
+ * them.  A scan compacts the calls by min_reads.  No atomics on results: every result word has one writer; the labels alone take
+ * atomic minima, whose outcome does not depend on the order.
+ * bk_timing: scope `split_junctions`.  bk_timing_touched, with bits(x) the position of the highest set bit of x from 1 (0 for 0) and
+ * a radix pass costing 36 bytes per item (key and value read by the histogram, read and written by the scatter): per tuple 96 (its
+ * row, its flag written and scanned); per eligible tuple 123 (its row read again with the record's flag and mapq, the canonical row
+ * written) + 36 * P1 + 132 (three key gathers) + 64 (the sorted copy) + 24 (heads, scans, ids) + 36 * P2 + 48 (the second key, its
+ * heads and scans), P1 = 8 + ceil(2 * bits(longest contig) / 8) + ceil(bits(largest group key) / 8), P2 = ceil((bits(e) + bits(x))
+ * / 8); per exact junction 80 (its row written and read) + 36 * ceil(bits(x) / 8) + 24; per call 84; per returned row 72.  The rows
+ * the walks read and the rounds are not modelled. */
+int bk_split_junctions(bk_ctx *ctx, int mapq_min, uint32_t tol, uint32_t min_reads, const struct bk_split_junction **out, uint64_t *count);
+/* What the last bk_split_junctions of this context counted: out[0] tuples, [1] eligible tuples, [2] exact junctions, [3] calls before
+ * min_reads, [4] returned calls that a voted row claims, [5] rounds of label propagation.  BK_ERR_ARG for a null argument. */
+int bk_split_junction_counts(bk_ctx *ctx, uint64_t out[6]);
+/* Test hook: bk_split_junctions with the claimed row looked up in `rows` (host memory, n_rows of them, any order of p1 and p2)
+ * instead of the context's own table; bk_split_breakpoints need not have run.  A context's own rows put the lower (contig, position)
+ * first, so only a caller's table reaches the crossed match.  Errors as bk_split_junctions, and BK_ERR_ARG for null rows with
+ * n_rows > 0. */
+int bk_debug_split_junctions(bk_ctx *ctx, int mapq_min, uint32_t tol, uint32_t min_reads, const bk_cluster *rows, uint64_t n_rows, const struct bk_split_junction **out,
+                             uint64_t *count);
+
 /* Copy a stage's result to library-owned host memory.  *data stays valid until the next bk_fetch
  * of the same stage or bk_free.  group_off (may be NULL) receives n_groups+1 offsets for pair stages. */
 int bk_fetch(bk_ctx *ctx, int stage, const void **data, uint64_t *count, const uint64_t **group_off, uint32_t *n_groups);
