@@ -2684,50 +2684,84 @@ int bk_group_stats(bk_ctx *ctx, const bk_group_stat **out, uint32_t *n_groups)
   });
 }
 
-int bk_debug_points(bk_ctx *ctx, int mode, const uint32_t *x, const uint32_t *y, uint32_t n, double w, uint32_t *idx_out, int32_t *cluster_out, uint32_t *n_out)
+int bk_debug_points_groups(bk_ctx *ctx, int mode, const uint32_t *x, const uint32_t *y, const uint64_t *group_off, uint32_t n_groups, double w, uint32_t *idx_out,
+                           int32_t *cluster_out, uint64_t *goff_out, uint32_t *n_out)
 {
   return guarded(ctx, [&] {
-    if ((n && (!x || !y)) || !idx_out || !n_out || mode < 0 || mode > 2) throw bk_error(BK_ERR_ARG, "bk_debug_points: bad argument");
+    if (!group_off || !idx_out || !n_out || mode < 0 || mode > 2) throw bk_error(BK_ERR_ARG, "bk_debug_points_groups: bad argument");
+    if (group_off[0] != 0) throw bk_error(BK_ERR_ARG, "bk_debug_points_groups: group_off[0] must be 0");
+    for (uint32_t g = 0; g < n_groups; ++g)
+      if (group_off[g + 1] < group_off[g]) throw bk_error(BK_ERR_ARG, "bk_debug_points_groups: group_off must ascend");
+    const uint64_t n = group_off[n_groups];
+    if (n >= (1ull << 31) || (n && (!x || !y))) throw bk_error(BK_ERR_ARG, "bk_debug_points_groups: bad argument");
     std::vector<bk_pair> hp(n);
-    for (uint32_t i = 0; i < n; ++i)
-    {
-      memset(&hp[i], 0, sizeof(bk_pair));
-      hp[i].x = x[i];
-      hp[i].y = y[i];
-    }
+    std::vector<uint32_t> gof(n);
+    for (uint32_t g = 0; g < n_groups; ++g)
+      for (uint64_t i = group_off[g]; i < group_off[g + 1]; ++i)
+      {
+        memset(&hp[i], 0, sizeof(bk_pair));
+        hp[i].x = x[i];
+        hp[i].y = y[i];
+        gof[i] = g;
+      }
     DevBuf dp, dcl, dgof, dgoff;
     PairList L;
-    std::vector<uint32_t> gof(n, 0);
-    uint64_t goff[2] = {0, n};
+    const size_t goff_bytes = ((size_t) n_groups + 1) * 8;
     if (n) HIP_CHECK(hipMemcpy(dp.as<bk_pair>(n + 1), hp.data(), n * sizeof(bk_pair), hipMemcpyHostToDevice));
     if (n) HIP_CHECK(hipMemcpy(dgof.as<uint32_t>(n + 1), gof.data(), n * 4, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(dgoff.as<uint64_t>(2), goff, 16, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(dgoff.as<uint64_t>((uint64_t) n_groups + 1), group_off, goff_bytes, hipMemcpyHostToDevice));
     const bk_pair *pairs = dp.as<bk_pair>(n + 1);
-    // one group holding the points in the given order
-    remove_isolated_all(pairs, dgof.get<uint32_t>(), dgoff.get<uint64_t>(), 1, mode == 1 ? n : 0, w, L, ctx->stage.cb(), ctx->st);
-    if (mode != 1)
+    // one list over all groups, as the lanes hand it to these functions (lanes.hip)
+    if (mode == 1)
+      remove_isolated_all(pairs, dgof.get<uint32_t>(), dgoff.get<uint64_t>(), n_groups, n, w, L, ctx->stage.cb(), ctx->st);
+    else
     {
-      // the list as given (remove_isolated_all sized the buffers; fill identity order)
+      // the list as given: identity order
       L.n = n;
-      L.ng = 1;
+      L.ng = n_groups;
       std::vector<uint32_t> iota(n);
       std::iota(iota.begin(), iota.end(), 0u);
-      if (n) HIP_CHECK(hipMemcpy(L.idx.as<uint32_t>(n + 1), iota.data(), n * 4, hipMemcpyHostToDevice));
-      if (n) HIP_CHECK(hipMemcpy(L.gof.as<uint32_t>(n + 1), gof.data(), n * 4, hipMemcpyHostToDevice));
-      HIP_CHECK(hipMemcpy(L.goff.as<uint64_t>(2), goff, 16, hipMemcpyHostToDevice));
+      uint32_t *lidx = L.idx.as<uint32_t>(n + 1), *lgof = L.gof.as<uint32_t>(n + 1);
+      if (n) HIP_CHECK(hipMemcpy(lidx, iota.data(), n * 4, hipMemcpyHostToDevice));
+      if (n) HIP_CHECK(hipMemcpy(lgof, gof.data(), n * 4, hipMemcpyHostToDevice));
+      HIP_CHECK(hipMemcpy(L.goff.as<uint64_t>((uint64_t) n_groups + 1), group_off, goff_bytes, hipMemcpyHostToDevice));
       if (mode == 0)
         debug_mask_list(pairs, L, (long) w, ctx->stage.cb(), ctx->st);
       else
         fast_cluster_all(pairs, L, w, dcl, ctx->stage.cb(), ctx->st);
     }
+    if (L.n > 2 * n) throw bk_error(BK_ERR_LIMIT, "bk_debug_points_groups: the list grew beyond 2 n entries");
     *n_out = (uint32_t) L.n;
     if (L.n)
     {
       HIP_CHECK(hipMemcpyAsync(idx_out, L.idx.get<uint32_t>(), L.n * 4, hipMemcpyDeviceToHost, ctx->st));
       if (mode == 2 && cluster_out) HIP_CHECK(hipMemcpyAsync(cluster_out, dcl.get<uint32_t>(), L.n * 4, hipMemcpyDeviceToHost, ctx->st));
     }
+    if (goff_out)
+    {
+      // (without a point nothing ran and the list's offsets were never written: they are all 0)
+      if (n)
+        HIP_CHECK(hipMemcpyAsync(goff_out, L.goff.get<uint64_t>(), goff_bytes, hipMemcpyDeviceToHost, ctx->st));
+      else
+        memset(goff_out, 0, goff_bytes);
+    }
     HIP_CHECK(hipStreamSynchronize(ctx->st));
   });
+}
+
+int bk_debug_points(bk_ctx *ctx, int mode, const uint32_t *x, const uint32_t *y, uint32_t n, double w, uint32_t *idx_out, int32_t *cluster_out, uint32_t *n_out)
+{
+  // one group holding the points in the given order
+  const uint64_t goff[2] = {0, n};
+  return bk_debug_points_groups(ctx, mode, x, y, goff, 1, w, idx_out, cluster_out, nullptr, n_out);
+}
+
+int bk_debug_cluster_info(uint64_t out[2])
+{
+  if (!out) return BK_ERR_ARG;
+  out[0] = FW_TILE;
+  out[1] = FW_LEVELS;
+  return BK_OK;
 }
 
 int bk_debug_cigar(bk_ctx *ctx, uint32_t n, const uint8_t *kind, const uint32_t *c1_off, const uint8_t *c1, const uint32_t *c2_off, const uint8_t *c2, const int32_t *e,

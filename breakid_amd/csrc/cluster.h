@@ -4,6 +4,21 @@
 #include "prims.h"
 #include "sortemu.h"
 
+// The chain-following kernels of the fast clustering (cluster.hip: k_fw_exit, k_fw_chain, k_fw_mark) work on tiles of FW_TILE
+// positions with FW_LEVELS rounds of pointer doubling in LDS.  2^FW_LEVELS >= FW_TILE must hold, and at 1024 / 10 it holds with
+// nothing to spare:
+//   k_fw_exit  starts one hop along the chain and doubles FW_LEVELS times: 2^FW_LEVELS hops.  A tile whose every nxt[p] = p + 1
+//              (one-element windows throughout) needs FW_TILE hops to leave from its first position.
+//   k_fw_mark  spreads a seed over 2^(FW_LEVELS-1) + ... + 2 + 1 = 2^FW_LEVELS - 1 hops: from local position 0 to FW_TILE - 1.
+// With the bound k_fw_chain makes at most one hop per tile and k_fw_mark reaches the whole tile from any seed, whatever k_fw_exit
+// returns.  Below it the marks would only be complete while every exit is EXACTLY 2^FW_LEVELS hops along (seeds 2^FW_LEVELS anchors
+// apart, each spread over 2^FW_LEVELS - 1), and k_fw_exit does not promise that: its rounds read entries that their owners may
+// already have moved on, so an exit can lie further along the chain.
+// (FW_TILE is also the workgroup size of both kernels, and local positions are uint16 with 0xFFFF = "leaves the tile".)
+constexpr uint32_t FW_TILE = 1024, FW_LEVELS = 10;
+static_assert((1ull << FW_LEVELS) >= FW_TILE, "k_fw_exit / k_fw_mark: FW_LEVELS rounds of doubling must cover a tile of one-element windows");
+static_assert(FW_LEVELS < 32 && FW_TILE <= 1024 && FW_TILE < 0xFFFFu, "FW_TILE is a workgroup size and its positions are uint16");
+
 // an ordered list of pair-table indices partitioned into groups
 struct PairList
 {

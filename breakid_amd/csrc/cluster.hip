@@ -123,7 +123,9 @@ __global__ void k_mark_starts(const uint64_t *__restrict__ goff, uint32_t ng, ui
 //               visits is marked (at most one hop per tile)
 //   k_fw_mark   per tile, in LDS: exact 2^k-hop tables of the tile's part of nxt, then the marks spread from the seeds (group
 //               starts and chain entries) highest level first
-constexpr uint32_t FW_TILE = 1024, FW_LEVELS = 10;
+// FW_TILE and FW_LEVELS live in cluster.h (bk_debug_cluster_info reports them): 2^FW_LEVELS >= FW_TILE, because k_fw_exit makes
+// 2^FW_LEVELS hops and k_fw_mark 2^FW_LEVELS - 1, and a tile of one-element windows needs FW_TILE and FW_TILE - 1 of them
+// (static_assert there; tests/test_gpu_points.py places exactly such tiles).
 __global__ __launch_bounds__(FW_TILE) void k_fw_exit(const uint32_t *__restrict__ nxt, uint64_t n, uint32_t *__restrict__ exitp)
 {
   __shared__ uint32_t e[FW_TILE];

@@ -1161,7 +1161,16 @@ int bk_debug_ahc(bk_ctx *ctx, const uint32_t *x, const uint32_t *y, uint32_t n, 
  * product path - the same kernels / device functions the stages use:
  *   bk_debug_points  one group of points in the given order; mode 0 = mask_pairs_chr_pos (BreakID.cc:1813-1877), 1 =
  *                    remove_isolated_pairs (:1271-1285), 2 = find_cluster_pairs_enspan_fast (:1046-1160, x-sorted input):
- *                    surviving point indices in output order (+ cluster numbers for mode 2)
+ *                    surviving point indices in output order (+ cluster numbers for mode 2).  It is the one-group call of
+ *   bk_debug_points_groups  the same for n_groups groups in ONE list, as the lanes hand it to the product functions (mask_list,
+ *                    remove_isolated_all, fast_cluster_all with ng = n_groups): group_off has n_groups + 1 ascending entries
+ *                    starting at 0 (equal neighbours = an empty group), the points of group g are x / y [group_off[g],
+ *                    group_off[g+1]).  idx_out (room for 2 * n entries: masking can emit a group's element 1 twice) indexes x / y,
+ *                    cluster_out (mode 2, may be NULL) restarts at 1 in every group, goff_out (n_groups + 1 entries, may be NULL)
+ *                    receives the list's group offsets afterwards, *n_out its length.  BK_ERR_ARG for offsets that do not
+ *                    ascend from 0.
+ *   bk_debug_cluster_info  FW_TILE and FW_LEVELS of this build (csrc/cluster.h: the tile of the chain-following kernels of the fast
+ *                    clustering and their rounds of pointer doubling); no GPU needed
  *   bk_debug_cigar   n rows of the CIGAR model (CigarRoller.cc / Cigar.cc): c1 = text (kind 0) or BAM words (kind 1, 4-byte
  *                    aligned rows), c2 = SA cigar text, e = tolerance; out6 = rolled op count, begin clips, end clips,
  *                    reference length, matches, is_complementary_cigar(c2, e) (CigarRoller.cc:323-346)
@@ -1170,6 +1179,9 @@ int bk_debug_ahc(bk_ctx *ctx, const uint32_t *x, const uint32_t *y, uint32_t n, 
  *   bk_debug_region  find_sa_reads (:868-1037) on a raw region of the uploaded table: evidence tuples that survive the region
  *                    verdict, total_coverage capped at 5, and cal_single_base_depth (util_bed.cc:154-192) at depth_pos */
 int bk_debug_points(bk_ctx *ctx, int mode, const uint32_t *x, const uint32_t *y, uint32_t n, double w, uint32_t *idx_out, int32_t *cluster_out, uint32_t *n_out);
+int bk_debug_points_groups(bk_ctx *ctx, int mode, const uint32_t *x, const uint32_t *y, const uint64_t *group_off, uint32_t n_groups, double w, uint32_t *idx_out,
+                           int32_t *cluster_out, uint64_t *goff_out, uint32_t *n_out);
+int bk_debug_cluster_info(uint64_t out[2]);
 int bk_debug_cigar(bk_ctx *ctx, uint32_t n, const uint8_t *kind, const uint32_t *c1_off, const uint8_t *c1, const uint32_t *c2_off, const uint8_t *c2, const int32_t *e,
                    int32_t *out6);
 int bk_debug_vote(bk_ctx *ctx, const bk_split *side1, uint32_t n1, const bk_split *side2, uint32_t n2, int32_t p1_tid, int32_t p2_tid, int32_t *out3);
