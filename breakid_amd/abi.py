@@ -51,6 +51,11 @@ LOCUS_PAIR = np.dtype([("tid_a", "<i4"), ("pos_a", "<u4"), ("tid_b", "<i4"), ("p
 LOCUS_SIM = np.dtype([("score", "<u4"), ("len", "<u4"), ("mism", "<u4"), ("run", "<u4"), ("diag", "<i4"), ("start", "<u4"), ("orient", "<u4"),
                       ("found", "<u4")])  # struct bk_locus_sim
 assert LOCUS_PAIR.itemsize == 16 and LOCUS_SIM.itemsize == 32
+REF_SITE = np.dtype([("tid", "<i4"), ("pos", "<u4")])  # struct bk_ref_site; pos 1-based
+SITE_CPLX = np.dtype([("covered", "<u4"), ("valid", "<u4"), ("gc", "<u4"), ("masked", "<u4"), ("mask_run", "<u4"), ("tri_total", "<u4"), ("tri_pairs", "<u4"),
+                      ("tri_distinct", "<u4"), ("bp_period", "<u4"), ("bp_len", "<u4"), ("bp_start", "<u4"), ("max_period", "<u4"), ("max_len", "<u4"),
+                      ("max_start", "<u4"), ("reserved", "<u4", (2,))])  # struct bk_site_cplx
+assert REF_SITE.itemsize == 8 and SITE_CPLX.itemsize == 64
 COV_WINDOW = np.dtype([("tid", "<i4"), ("beg", "<u4"), ("end", "<u4"), ("reserved", "<u4")])  # struct bk_cov_window; 0-based, half-open
 WINDOW_COV = np.dtype([("bases", "<u8"), ("reads", "<u4"), ("reserved", "<u4")])  # struct bk_window_cov
 WINDOW_CTX = np.dtype([("mapq_sum", "<u8"), ("reads", "<u4"), ("mq0", "<u4"), ("lowq", "<u4"), ("clipped", "<u4"), ("improper", "<u4"), ("orphan", "<u4"), ("dup", "<u4"),

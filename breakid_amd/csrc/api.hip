@@ -20,6 +20,7 @@
 #include "consensus.h"
 #include "jfit.h"
 #include "locsim.h"
+#include "seqcx.h"
 #include "coverage.h"
 #include "context.h"
 #include "frame.h"
@@ -166,6 +167,9 @@ struct bk_ctx
   // locus similarity (bk_locus_similarity)
   LocsimBufs lsb;
   std::vector<struct bk_locus_sim> f_locsim;
+  // site complexity (bk_site_complexity)
+  SeqcxBufs scb;
+  std::vector<struct bk_site_cplx> f_sitecx;
   // window coverage (bk_window_coverage: this context holds the records)
   CovBufs cvb;
   std::vector<struct bk_window_cov> f_wincov;
@@ -1429,6 +1433,32 @@ int bk_locus_similarity(bk_ctx *ctx, const bk_refseq *ref, const struct bk_locus
     // touched: the pair row, the result row and L nibbles of each of the two windows
     if (ctx->timing && !ctx->timers.empty()) ctx->timers.back().touched = n * (sizeof(struct bk_locus_pair) + sizeof(struct bk_locus_sim) + L);
     *out = ctx->f_locsim.data();
+  });
+}
+
+int bk_site_complexity(bk_ctx *ctx, const bk_refseq *ref, const struct bk_ref_site *sites, uint64_t n, uint32_t flank, uint32_t max_period, const struct bk_site_cplx **out)
+{
+  return guarded(ctx, [&] {
+    if (!ref || !out) throw bk_error(BK_ERR_ARG, "bk_site_complexity: null ref or out");
+    if (n && !sites) throw bk_error(BK_ERR_ARG, "bk_site_complexity: null sites");
+    if (ctx->shard) throw bk_error(BK_ERR_ARG, "bk_site_complexity: sharded contexts (bk_shard_*) are not supported");
+    if (flank < 1 || flank > 255) throw bk_error(BK_ERR_ARG, "bk_site_complexity: flank must be 1..255");
+    if (max_period < 1 || max_period > 64) throw bk_error(BK_ERR_ARG, "bk_site_complexity: max_period must be 1..64");
+    if (n > 0x40000000ull) throw bk_error(BK_ERR_LIMIT, "bk_site_complexity: more than 2^30 sites");
+    const bk_refseq &t = *ref;
+    check_refseq(t, "bk_site_complexity");
+    const uint64_t L = 2ull * flank + 1;
+    struct bk_site_cplx *d_res;
+    seqcx_upload(t, sites, n, ctx->scb, ctx->st);  // (outside the scope: it times the work on the device copy)
+    {
+      // bytes: the sites and the result once; the reference segments once
+      Scope s(ctx, "site_complexity", n * (sizeof(struct bk_ref_site) + sizeof(struct bk_site_cplx)) + t.n_segs * 24ull + (t.n_segs ? t.off[t.n_segs] : 0));
+      site_complexity(n, flank, max_period, ctx->scb, ctx->st, &d_res);
+    }
+    rows_to_host(ctx, d_res, n, ctx->f_sitecx);
+    // touched: the site row, the result row and the L nibbles of the window
+    if (ctx->timing && !ctx->timers.empty()) ctx->timers.back().touched = n * (sizeof(struct bk_ref_site) + sizeof(struct bk_site_cplx) + L);
+    *out = ctx->f_sitecx.data();
   });
 }
 

@@ -1243,6 +1243,56 @@ static SimilarMap locus_similar(const Options &o, const Sample &tumor, const vec
   return sim;
 }
 
+// ---- -complexity: the reference around each breakpoint of every written call described by itself ---------------------------------
+// Two sites per written call, a side on a contig without a nib file left out; the reference: the windows [pos - R, pos + R] around
+// every site, clamped to the contig.  One call describes every site of the run.
+static ComplexityMap site_complexity(const Options &o, const Sample &tumor, const vector<OutRow> &rows)
+{
+  NibFiles nibs{o, tumor, {}};
+  const long R = o.cplxflank;
+  vector<struct bk_ref_site> sites;
+  vector<std::pair<uint64_t, int>> site_side;  // the call and the side of it
+  std::map<int32_t, vector<std::pair<long, long>>> spans;
+  ComplexityMap cplx;
+  for (const OutRow &r : rows)
+  {
+    if (!call_written(r, o.all)) continue;
+    cplx[r.idx];
+    for (int e = 0; e < 2; ++e)
+    {
+      const struct bk_ref_site s = {e ? r.c.p2_tid : r.c.p1_tid, e ? (uint32_t) r.c.p2_exact : r.c.p1_exact};
+      if (!nibs.of(s.tid)) continue;
+      sites.push_back(s);
+      site_side.emplace_back(r.idx, e);
+      const long a = std::max(1l, (long) s.pos - R), b = std::min((long) nibs.of(s.tid)->nBases, (long) s.pos + R);
+      if (a <= b) spans[s.tid].emplace_back(a, b);
+    }
+  }
+  const RefWindows windows = read_ref_windows(spans, nibs);
+  const bk_refseq ref = windows.refseq();
+  const struct bk_site_cplx *res = nullptr;
+  const int rc = bk_site_complexity(tumor.ctx, &ref, sites.data(), sites.size(), (uint32_t) R, (uint32_t) o.cplxperiod, &res);
+  if (rc != BK_OK) die(tumor, rc);
+  const uint32_t LOG_TRACT = 12;  // only what the log line below counts: no column and no filter looks at it
+  size_t n_tract = 0, n_masked = 0;
+  for (size_t k = 0; k < sites.size(); ++k)
+  {
+    ComplexitySide &c = site_side[k].second ? cplx[site_side[k].first].second : cplx[site_side[k].first].first;
+    c.on = true;
+    c.c = res[k];
+    const long first = (long) sites[k].pos - R;  // the position of column 0
+    c.bp_pos = first + (long) c.c.bp_start;
+    c.max_pos = first + (long) c.c.max_start;
+    for (uint32_t j = 0; j < c.c.bp_period; ++j) c.bp_unit += windows.base(sites[k].tid, c.bp_pos + j);
+    for (uint32_t j = 0; j < c.c.max_period; ++j) c.max_unit += windows.base(sites[k].tid, c.max_pos + j);
+    n_tract += c.c.bp_len >= LOG_TRACT;
+    n_masked += c.c.mask_run > 0;
+  }
+  std::cout << "complexity: " << sites.size() << " sites, " << n_tract << " with a tract of " << LOG_TRACT << " or more columns at the breakpoint, " << n_masked
+            << " with the breakpoint base soft-masked" << std::endl;
+  return cplx;
+}
+
 // ---- -coverage: the mean depth beside and between the breakpoints of every written call -------------------------------------------
 // Five windows per written call (bk_call_windows, with the sides -vcf uses) and one per contig that carries a call; one call of
 // bk_window_coverage answers them all on the sample's records, a second one on the normal's.
@@ -1601,7 +1651,8 @@ static ContextMap call_context(const Options &o, const Sample &tumor, const Samp
 // -vcf: <prefix>_fusion.vcf, and with -clip <prefix>_fusion_rescued.vcf
 static void write_vcf_files(const Options &o, const Sample &tumor, const CallTables &t, const vector<OutRow> &rows, const Rescued &rescued, const ConsensusMap &cons,
                             const HomologyMap &hom, const SimilarMap &sim, const CoverageMap &cov, const FrameMap &frame, const LinkMap &link,
-                            const PartnerMap &partners, const FragsizeMap &frags, const KnownMap &known, const ContextMap &context)
+                            const PartnerMap &partners, const FragsizeMap &frags, const KnownMap &known, const ContextMap &context,
+                            const ComplexityMap &cplx)
 {
   VcfInput vi;
   vi.nt = tumor.nt;
@@ -1626,6 +1677,7 @@ static void write_vcf_files(const Options &o, const Sample &tumor, const CallTab
   vi.frags = o.fragsize ? &frags : nullptr;
   vi.known = o.known() ? &known : nullptr;
   vi.context = o.context ? &context : nullptr;
+  vi.cplx = o.complexity ? &cplx : nullptr;
   auto write = [&](const string &path, const vector<OutRow> &calls) {
     if (write_vcf(path, calls, vi)) return;
     std::cerr << "Error: cannot write " << path << ": the evidence tables do not cover every call" << std::endl;
@@ -1645,6 +1697,7 @@ static void write_vcf_files(const Options &o, const Sample &tumor, const CallTab
   vi.frags = nullptr;                  // ... and with -fragsize
   vi.known = nullptr;                  // ... and with -known
   vi.context = nullptr;                // ... and with -context
+  vi.cplx = nullptr;                   // ... and with -complexity
   vi.rescued = &rescued.calls;
   write(o.out_file + "_fusion_rescued.vcf", rescued.rows);
 }
@@ -1750,6 +1803,8 @@ static void write_params(const Options &o, double w)
   if (o.context) p << "context_flank\t" << o.ctxflank << std::endl;
   if (o.junctions) p << "junction_min_support\t" << o.jsupport << std::endl;
   if (o.junctions) p << "junction_tol\t" << o.jtol << std::endl;
+  if (o.complexity) p << "complexity_flank\t" << o.cplxflank << std::endl;
+  if (o.complexity) p << "complexity_max_period\t" << o.cplxperiod << std::endl;
 }
 
 // BreakID.cc:175-191.  scan_pairs_count and after_cluster_count are never updated by the reference (always 0);
@@ -1837,10 +1892,12 @@ int main(int argc, char *argv[])
   if (o.known()) known = known_calls(o, tumor, tables, rows, panel);
   ContextMap context;
   if (o.context) context = call_context(o, tumor, normal, tables, rows);
+  ComplexityMap complexity;
+  if (o.complexity) complexity = site_complexity(o, tumor, rows);
 
   if (o.clip) write_rescued_tables(o, rescued, tables);
-  write_fusion_tables(o, rows, fusion_twins(o, tables, consensus.sides, homology, similar, coverage, frames, links, partners, frags, known, context));
-  if (o.vcf) write_vcf_files(o, tumor, tables, rows, rescued, consensus.sides, homology, similar, coverage, frames, links, partners, frags, known, context);
+  write_fusion_tables(o, rows, fusion_twins(o, tables, consensus.sides, homology, similar, coverage, frames, links, partners, frags, known, context, complexity));
+  if (o.vcf) write_vcf_files(o, tumor, tables, rows, rescued, consensus.sides, homology, similar, coverage, frames, links, partners, frags, known, context, complexity);
   if (o.evidence) write_evidence_files(o, tumor, tables, rows, rescued);
   if (o.bedpe && !write_bedpe_files(o, rows, tables.jsup))
   {

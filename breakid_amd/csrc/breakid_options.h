@@ -56,6 +56,8 @@ int bk_known_calls(bk_ctx *ctx, const struct bk_known_entry *entries, uint64_t n
 // -junctions (junction calls from the split reads alone; bk_base_depth is listed with -clip)
 int bk_split_junctions(bk_ctx *ctx, int mapq_min, uint32_t tol, uint32_t min_reads, const struct bk_split_junction **out, uint64_t *count) __attribute__((weak));
 int bk_split_junction_counts(bk_ctx *ctx, uint64_t out[6]) __attribute__((weak));
+// -complexity
+int bk_site_complexity(bk_ctx *ctx, const bk_refseq *ref, const struct bk_ref_site *sites, uint64_t n, uint32_t flank, uint32_t max_period, const struct bk_site_cplx **out) __attribute__((weak));
 // -dedup
 int bk_unique_support(bk_ctx *ctx, const struct bk_unique_support **out, uint64_t *count, const uint64_t **first, uint64_t *n_rows) __attribute__((weak));
 // -clip (the soft-clip evidence, the depth at the rescued positions and the rescue rule)
@@ -115,15 +117,18 @@ static const char *HELP =
      \t -ctxflank  \t bases either side of a breakpoint in which a read must start, about one fragment length, 1 to 1000000 (with -context)  [500]\n \
      \t -junctions \t also call junctions from the split reads alone, with or without discordant pairs: deletions and duplications shorter than the library's spread, small inversions (*_junctions.txt; *_junctions.bedpe with -bedpe)  \n \
      \t -jsupport  \t distinct reads a junction needs, 1 to 1000000 (with -junctions)  [3]\n \
-     \t -jtol      \t bases up to which two junctions with equal sides are one call, 0 to 100 (with -junctions)  [2]\n ";
+     \t -jtol      \t bases up to which two junctions with equal sides are one call, 0 to 100 (with -junctions)  [2]\n \
+     \t -complexity \t describe the reference around both breakpoints of every call by itself: soft-masked share, DUST score, GC and the exact tandem repeat at the breakpoint (twin files *_complexity.txt; LCDUST / LCGC / LCMASK / LCSTR with -vcf)  \n \
+     \t -cplxflank \t bases either side of a breakpoint that are described, 1 to 255 (with -complexity)  [32]\n \
+     \t -cplxperiod \t longest repeat unit that is looked for, 1 to 64 (with -complexity)  [6]\n ";
 
 struct Options
 {
   std::string inp_file, out_file, nib_dir, normal_file, exclude_file, known_file, build = "hg19";
   int qual = 20, device = 0, n_gpus = 0, transport = BK_TRANSPORT_AUTO;  // -gpus N: one sample over N GPUs (include/breakid_multi.h)
   bool fast = false, all = false;                                        // -all: no gene-pair and repeat filter (the _fusion_all files)
-  bool genotype = false, vcf = false, evidence = false, clip = false, dedup = false, consensus = false, homology = false, similar = false, coverage = false, frame = false, link = false, partners = false, fragsize = false, bedpe = false, context = false, junctions = false;
-  bool anchor_given = false, minclip_given = false, clipsupport_given = false, conslen_given = false, homshift_given = false, homins_given = false, simflank_given = false, covflank_given = false, linkdist_given = false, knownslop_given = false, ctxflank_given = false, jsupport_given = false, jtol_given = false;
+  bool genotype = false, vcf = false, evidence = false, clip = false, dedup = false, consensus = false, homology = false, similar = false, coverage = false, frame = false, link = false, partners = false, fragsize = false, bedpe = false, context = false, junctions = false, complexity = false;
+  bool anchor_given = false, minclip_given = false, clipsupport_given = false, conslen_given = false, homshift_given = false, homins_given = false, simflank_given = false, covflank_given = false, linkdist_given = false, knownslop_given = false, ctxflank_given = false, jsupport_given = false, jtol_given = false, cplxflank_given = false, cplxperiod_given = false;
   long anchor = 10;                      // -anchor: bases a reference read must cover on either side of the breakpoint base
   long min_clip = 10, clip_support = 3;  // -minclip: shortest clip that counts; -clipsupport: reads at one position a rescued side needs
   long conslen = 64;                     // -conslen: longest junction sequence per side
@@ -134,6 +139,7 @@ struct Options
   long knownslop = 100;                  // -knownslop: the distance up to which bk_known_calls lets a breakend fall into an interval
   long ctxflank = 500;                   // -ctxflank: the bases either side of a cut in which bk_window_context counts the records that start there
   long jsupport = 3, jtol = 2;           // -jsupport, -jtol: min_reads and tol of bk_split_junctions
+  long cplxflank = 32, cplxperiod = 6;   // -cplxflank, -cplxperiod: flank and max_period of bk_site_complexity
   bool multi() const { return n_gpus >= 1; }  // the sharded run
   bool known() const { return !known_file.empty(); }
   bool with_normal() const { return !normal_file.empty(); }
@@ -181,6 +187,7 @@ static void check_options(const Options &o)
   const Feature bedpe{"-bedpe", o.bedpe, false, bk_junctions && bk_junction_sides};
   const Feature context{"-context", o.context, false, bk_window_context && bk_call_windows && bk_junctions && bk_junction_sides};
   const Feature junctions{"-junctions", o.junctions, false, bk_split_junctions && bk_split_junction_counts && bk_base_depth};
+  const Feature complexity{"-complexity", o.complexity, false, bk_site_complexity != nullptr};
   const Feature consensus{"-consensus", o.consensus, false, bk_clip_consensus && bk_clip_reads && bk_evidence && bk_junctions && bk_junction_sides};
   const Feature clip{"-clip", o.clip, false, bk_clip_support && bk_clip_reads && bk_base_depth && bk_clip_rescue && bk_junctions && bk_junction_sides};
   const Feature exclude{"-x", o.exclude(), true, bk_exclude_regions && bk_multi_run_ex && bk_multi_run_bam_ex && bk_multi_excluded};
@@ -227,6 +234,10 @@ static void check_options(const Options &o)
       rule((o.jsupport_given || o.jtol_given) && !o.junctions, "-jsupport and -jtol need -junctions."), gpus(junctions),
       rule(o.junctions && !in_range(o.jsupport, 1, 1000000), "-jsupport must be a number from 1 to 1000000."),
       rule(o.junctions && !in_range(o.jtol, 0, 100), "-jtol must be a number from 0 to 100."), library(junctions),
+      rule(o.cplxflank_given && !o.complexity, "-cplxflank needs -complexity."), rule(o.cplxperiod_given && !o.complexity, "-cplxperiod needs -complexity."),
+      gpus(complexity), library(complexity),
+      rule(o.complexity && !in_range(o.cplxflank, 1, 255), "-cplxflank must be a number from 1 to 255."),
+      rule(o.complexity && !in_range(o.cplxperiod, 1, 64), "-cplxperiod must be a number from 1 to 64."),
   };
   for (const Refusal &r : refusals)
   {
@@ -255,6 +266,7 @@ static Options parse_options(int argc, char *argv[])
                                      {"known", 1, 0, 35}, {"knownslop", 1, 0, 36}, {"bedpe", 0, 0, 37},
                                      {"context", 0, 0, 38}, {"ctxflank", 1, 0, 39},
                                      {"junctions", 0, 0, 40}, {"jsupport", 1, 0, 41}, {"jtol", 1, 0, 42},
+                                     {"complexity", 0, 0, 43}, {"cplxflank", 1, 0, 44}, {"cplxperiod", 1, 0, 45},
                                      {"f", 0, 0, 5},  // (-f used to complete to -fast alone; it still means it beside -frame)
                                      {0, 0, 0, 0}};
   Options o;
@@ -311,6 +323,9 @@ static Options parse_options(int argc, char *argv[])
     case 40: o.junctions = true; break;
     case 41: number(o.jsupport, o.jsupport_given); break;
     case 42: number(o.jtol, o.jtol_given); break;
+    case 43: o.complexity = true; break;
+    case 44: number(o.cplxflank, o.cplxflank_given); break;
+    case 45: number(o.cplxperiod, o.cplxperiod_given); break;
     default: std::cerr << "Error: cannot parse arguments.\n"; exit(1);
     }
   }

@@ -463,6 +463,56 @@ struct ContextCall
     return t;
   }
 };
+// -complexity: the twin files' columns (bk_site_complexity of the reference around each of the two breakpoints of the call), side 1 and
+// then side 2
+static const char *COMPLEXITY_NAMES[12] = {"Lc_N", "Lc_GC", "Lc_Dust", "Lc_Tri", "Lc_Mask", "Lc_MaskRun", "Lc_BpUnit", "Lc_BpLen", "Lc_BpPos", "Lc_MaxUnit", "Lc_MaxLen", "Lc_MaxPos"};
+static string complexity_columns()
+{
+  string s;
+  for (int side = 1; side <= 2; ++side)
+    for (const char *name : COMPLEXITY_NAMES) s += string("\t") + name + std::to_string(side);
+  return s;
+}
+
+// One side of a written call: its bk_site_cplx row (on: the contig has a nib file, so the site was submitted), the repeat units as
+// the reference spells them from each tract's start, and each tract's first 1-based position.  Every ratio is a quotient of two
+// doubles made from the integers.
+struct ComplexitySide
+{
+  bool on = false;
+  struct bk_site_cplx c = {};
+  string bp_unit, max_unit;
+  long bp_pos = 0, max_pos = 0;
+  string gc_text() const { return c.valid ? CoverageCall::fixed("%.3f", (double) c.gc / (double) c.valid) : string("."); }
+  string dust_text() const { return c.tri_total >= 2 ? CoverageCall::fixed("%.2f", (double) c.tri_pairs / (double) (c.tri_total - 1)) : string("."); }
+  string mask_text() const { return c.covered ? CoverageCall::fixed("%.3f", (double) c.masked / (double) c.covered) : string("."); }
+  string fields() const
+  {
+    if (!on) return "\t.\t.\t.\t.\t.\t.\t.\t.\t.\t.\t.\t.";
+    std::ostringstream o;
+    o << "\t" << c.valid << "\t" << gc_text() << "\t" << dust_text() << "\t" << c.tri_distinct << "\t" << mask_text() << "\t" << c.mask_run;
+    if (c.bp_len)
+      o << "\t" << bp_unit << "\t" << c.bp_len << "\t" << bp_pos;
+    else
+      o << "\t.\t0\t.";
+    if (c.max_len)
+      o << "\t" << max_unit << "\t" << c.max_len << "\t" << max_pos;
+    else
+      o << "\t.\t0\t.";
+    return o.str();
+  }
+  // what the breakend of this side ends its INFO with
+  string info() const
+  {
+    string t;
+    if (!on) return t;
+    if (dust_text() != ".") t += ";LCDUST=" + dust_text();
+    if (gc_text() != ".") t += ";LCGC=" + gc_text();
+    if (mask_text() != ".") t += ";LCMASK=" + mask_text();
+    if (c.bp_len) t += ";LCSTR=" + bp_unit + "x" + std::to_string(c.bp_len);
+    return t;
+  }
+};
 // -clip -normal: what _fusion_rescued_normal.txt adds to a row of _fusion_rescued.txt
 static const char *RESCUED_COLUMNS_NORMAL = "\tNormal_DRP\tNormal_ClipAt1\tNormal_ClipAt2\tNormal_Depth1\tNormal_Depth2";
 
@@ -494,6 +544,7 @@ using PartnerMap = std::map<uint64_t, PartnerCall>;
 using FragsizeMap = std::map<uint64_t, FragsizeCall>;
 using KnownMap = std::map<uint64_t, KnownCall>;
 using ContextMap = std::map<uint64_t, ContextCall>;
+using ComplexityMap = std::map<uint64_t, std::pair<ComplexitySide, ComplexitySide>>;
 
 // -clip: the rescued clusters in the order of _fusion_rescued.txt, calls[k] to rows[k]; with -evidence the clipped reads at the peaks
 // of the written ones (bk_clip_reads: the rows of sites 2 * j and 2 * j + 1 belong to the j-th written row)
@@ -536,7 +587,7 @@ struct Twin
 // The twins of this run, the reference's own two files first.  An option that adds columns to the calls adds its entry here.
 static vector<Twin> fusion_twins(const Options &o, const CallTables &t, const ConsensusMap &cons, const HomologyMap &hom, const SimilarMap &sim,
                                  const CoverageMap &cov, const FrameMap &frame, const LinkMap &link, const PartnerMap &partners,
-                                 const FragsizeMap &frags, const KnownMap &known, const ContextMap &context)
+                                 const FragsizeMap &frags, const KnownMap &known, const ContextMap &context, const ComplexityMap &cplx)
 {
   const bool with_normal = o.with_normal();  // (a tumour without calls still gets header-only twins)
   vector<Twin> twins;
@@ -633,6 +684,12 @@ static vector<Twin> fusion_twins(const Options &o, const CallTables &t, const Co
                        if (!context.count(r.idx)) return false;
                        const ContextCall &c = context.at(r.idx);
                        tail = ContextCall::fields(c.tumor) + (with_normal ? ContextCall::fields(c.normal) : "");
+                       return true;
+                     }});
+  if (o.complexity)
+    twins.push_back({"_complexity", complexity_columns(), [&cplx](const OutRow &r, string &tail) {
+                       if (!cplx.count(r.idx)) return false;
+                       tail = cplx.at(r.idx).first.fields() + cplx.at(r.idx).second.fields();
                        return true;
                      }});
   return twins;
@@ -796,6 +853,9 @@ struct VcfInput
   const KnownMap *known = nullptr;
   // -context (else null; never for the rescued clusters): CXN, and MQ0F / MEANMQ where the side has a read, of the breakend's own side, behind everything else
   const ContextMap *context = nullptr;
+  // -complexity (else null; never for the rescued clusters): LCDUST / LCGC / LCMASK where the columns have a value and LCSTR where a tract
+  // lies at the breakpoint, of the breakend's own side, behind everything else
+  const ComplexityMap *cplx = nullptr;
 };
 
 static char nib_base(const string &nib_dir, const string &chr, long pos1)  // the base at a 1-based position; N without a file or beyond it
@@ -929,6 +989,7 @@ static bool write_vcf(const string &path, const vector<OutRow> &rows, const VcfI
         if (in.frags && in.frags->count(r.idx)) o << in.frags->at(r.idx).info();
         if (in.known && in.known->count(r.idx)) o << in.known->at(r.idx).info();
         if (in.context && in.context->count(r.idx)) o << in.context->at(r.idx).info(s);
+        if (in.cplx && in.cplx->count(r.idx)) o << (s ? in.cplx->at(r.idx).second : in.cplx->at(r.idx).first).info();
         o << "\t" << (in.gsup ? "GT:GQ:DR:DV:RR:RV" : "DV:RV") << "\t" << vcf_sample(r.c.n_drp, r.c.n_sr, in.gsup ? &(*in.gsup)[r.idx] : nullptr, s);
         if (in.with_normal) o << "\t" << vcf_sample(in.nsup[r.idx].n_drp, in.nsup[r.idx].n_sr, in.gsup_normal ? &(*in.gsup_normal)[r.idx] : nullptr, s);
       }
@@ -1003,6 +1064,11 @@ static bool write_vcf(const string &path, const vector<OutRow> &rows, const VcfI
     v << "##INFO=<ID=CXN,Number=1,Type=Integer,Description=\"Primary alignments, duplicates and failed reads aside, that start within the context flank of this breakpoint, before any mapping-quality filter\">\n"
          "##INFO=<ID=MQ0F,Number=1,Type=Float,Description=\"Share of those alignments with mapping quality 0\">\n"
          "##INFO=<ID=MEANMQ,Number=1,Type=Float,Description=\"Mean mapping quality of those alignments\">\n";
+  if (in.cplx && !in.rescued)
+    v << "##INFO=<ID=LCDUST,Number=1,Type=Float,Description=\"DUST score of the reference window around this breakpoint: pairs of equal trinucleotides over the trinucleotides less one\">\n"
+         "##INFO=<ID=LCGC,Number=1,Type=Float,Description=\"Share of C and G among the bases of that window\">\n"
+         "##INFO=<ID=LCMASK,Number=1,Type=Float,Description=\"Share of that window the reference files soft-mask\">\n"
+         "##INFO=<ID=LCSTR,Number=1,Type=String,Description=\"Longest exact tandem repeat that holds the breakpoint base or a neighbour of it: the unit, x, the columns it covers\">\n";
   if (in.rescued) v << "##INFO=<ID=SC,Number=1,Type=Integer,Description=\"Soft-clipped reads without an SA tag that end at this position (the clip peak)\">\n";
   if (in.gsup)
     v << "##FORMAT=<ID=GT,Number=1,Type=String,Description=\"Genotype\">\n"

@@ -1,5 +1,6 @@
 // A bk_refseq table on the device and how a kernel reads it: the upload of its columns, the lookup of ref(t, p) as a 2-bit code, and the
-// shifted read of a bit plane.  Shared by jfit.hip (bk_junction_fit) and locsim.hip (bk_locus_similarity).
+// shifted read of a bit plane.  Shared by jfit.hip (bk_junction_fit), locsim.hip (bk_locus_similarity) and seqcx.hip
+// (bk_site_complexity, which also reads the raw nibble).
 #pragma once
 #include "bk_common.h"
 
@@ -71,6 +72,30 @@ __device__ __forceinline__ uint32_t ref_code(const JfitRef &r, long long g0, lon
   const uint32_t nib = (i & 1) ? (byte & 15u) : (byte >> 4);
   if (nib & 4u) return CODE_N;                // 4..7 are N; bit 3 is the soft-mask
   return (0x87u >> ((nib & 3u) << 1)) & 3u;  // T C A G -> 3 1 0 2
+}
+
+constexpr uint32_t NIB_COVERED = 16;  // ref_nibble: a segment holds the position
+
+// ref(t, p1) as it lies in the table: NIB_COVERED | the raw nibble (bit 3 the soft-mask, bit 2 N, the low bits T C A G) when a segment
+// covers the position, 0 otherwise.  g0 and the walk as in ref_code.
+__device__ __forceinline__ uint32_t ref_nibble(const JfitRef &r, long long g0, long long t, long long p1)
+{
+  const long long p0 = p1 - 1;
+  if (p0 < 0) return 0;
+  long long g = g0;
+  while (g + 1 < (long long) r.n)
+  {
+    const long long nt = r.tid[g + 1], ns = r.start[g + 1];
+    if (nt < t || (nt == t && ns <= p0))
+      ++g;
+    else
+      break;
+  }
+  if (g < 0 || (long long) r.tid[g] != t) return 0;
+  const long long i = p0 - (long long) r.start[g];
+  if (i >= (long long) r.len[g]) return 0;
+  const uint32_t byte = r.bases[r.off[g] + (unsigned long long) (i >> 1)];
+  return NIB_COVERED | ((i & 1) ? (byte & 15u) : (byte >> 4));
 }
 
 // 64 bits of a plane from bit position `bit` on (the word behind the last one that holds data is there and is zero)

@@ -573,6 +573,48 @@ struct bk_locus_sim  { uint32_t score, len, mism, run; int32_t diag; uint32_t st
  * or 2^20 segments, looked at before any array is read.  n == 0 is no error, and neither is n_segs == 0 (every row is then zero). */
 int bk_locus_similarity(bk_ctx *ctx, const bk_refseq *ref, const struct bk_locus_pair *pairs, uint64_t n, uint32_t flank, const struct bk_locus_sim **out);
 
+/* ---- site complexity: what the reference looks like at one position ---------------------------------------------------------------
+ * Aligners clip and split reads in microsatellites, low-complexity stretches and annotated repeats for reasons that have nothing to do
+ * with a rearrangement.  bk_site_complexity describes the reference window around one position by itself: how much of it is
+ * soft-masked (bit 3 of the nibble, which nothing else reads), its trinucleotide counts (the DUST score of the window) and its exact
+ * tandem tracts.  It reads nothing but the reference (bk_refseq as above).  All arithmetic is integer.
+ * Site k: (tid, pos), pos 1-based.  R = flank, L = 2 R + 1.  Column i, 0 <= i < L, is position pos - R + i of contig tid, and nib[i]
+ * the raw nibble there when a segment of `ref` holds the position.  Column i is
+ *   covered  when a segment holds the position (never before position 1, outside every segment, or on tid < 0),
+ *   masked   when covered and nib[i] & 8,
+ *   valid    when covered and (nib[i] & 4) == 0; its base is then w[i] in A C G T = 0 1 2 3 (nib T C A G = 0 1 2 3 -> 3 1 0 2).
+ * Counts: covered, valid, masked are the numbers of such columns; gc the valid columns with C or G.  mask_run is the length of the
+ * maximal run of consecutive masked columns that contains column R, 0 when column R is not masked; a run that reaches an end of the
+ * window is a lower bound of the interval's length.
+ * Trinucleotides: column i <= L - 3 starts triplet t = 16 w[i] + 4 w[i + 1] + w[i + 2] when i, i + 1 and i + 2 are all valid; c_t is
+ * the count of triplet t.  tri_total = sum c_t, tri_pairs = sum c_t (c_t - 1) / 2, tri_distinct = the number of t with c_t > 0.
+ * sdust's score of the whole window is tri_pairs / (tri_total - 1).
+ * Tandem tracts: for a period p, 1 <= p <= max_period and p < L, m_p[i] = 1 for 0 <= i < L - p when columns i and i + p are both
+ * valid and w[i] == w[i + p].  A maximal run of n >= p consecutive ones of m_p that starts at i0 (two full copies at least) is a
+ * tract of period p, start i0 and length n + p: it covers the columns i0 .. i0 + n + p - 1.  Tracts are exact; one N or one mismatch
+ * ends a tract.  They are ordered by the key (-length, period, start): the longest first, then the shortest period, then the
+ * smallest start, so that a homopolymer is reported with period 1 and not with 2 or 3.  max_period / max_len / max_start is the first
+ * tract of the window in that order; bp_period / bp_len / bp_start the first tract whose columns intersect [R - 1, R + 1], the base
+ * at `pos` and its two neighbours (a junction lies on one side of the base or the other).  All three fields are 0 without a tract.
+ * By hand, R = 3 on GTACACA: w = 2 3 0 1 0 1 0.  m_2 = 0 0 1 1 1: one run of n = 3 >= 2 from i0 = 2, the tract (period 2, start 2,
+ * length 5), columns 2 .. 6.  m_1 has no one and m_3 = 0 0 0 0, so max_* = bp_* = (2, 5, 2) (the tract holds column 2 = R - 1).  The
+ * triplets are GTA TAC ACA CAC ACA: tri_total 5, tri_pairs 1 (ACA twice), tri_distinct 4; gc = 3.
+ * Every output is an integer count or an argmax with a fixed tie rule: two runs, and any permutation of the sites, give the same bytes
+ * row for row.  The structs have no typedef. */
+struct bk_ref_site   { int32_t tid; uint32_t pos; };                       /* 8 bytes, pos 1-based */
+struct bk_site_cplx  { uint32_t covered, valid, gc, masked, mask_run,
+                       tri_total, tri_pairs, tri_distinct,
+                       bp_period, bp_len, bp_start,
+                       max_period, max_len, max_start, reserved[2]; };     /* 64 bytes, reserved = 0 */
+/* ctx: any live context that is not a shard (bk_shard_*); it gives the device, the stream, the buffers and bk_timing (scope
+ * `site_complexity`; bk_timing_touched is n * (72 + L): the site row, the result row and L nibbles).  No stage needs to have run and
+ * nothing a later bk_fetch or stage returns changes.  ref, sites: host memory.  *out (n rows) is library-owned until the next call or
+ * bk_free(ctx).  BK_ERR_ARG (with the reason in bk_last_error) for shards, null ctx / ref / out, null sites with n > 0, flank outside
+ * 1..255, max_period outside 1..64, and every defect of the reference table that bk_junction_fit rejects.  BK_ERR_LIMIT beyond 2^30
+ * sites or 2^20 segments, looked at before any array is read.  n == 0 is no error, and neither is n_segs == 0 (every row is then
+ * zero).  A period at or above L has no tract and is no error. */
+int bk_site_complexity(bk_ctx *ctx, const bk_refseq *ref, const struct bk_ref_site *sites, uint64_t n, uint32_t flank, uint32_t max_period, const struct bk_site_cplx **out);
+
 /* ---- window coverage: the aligned bases inside arbitrary windows of the record table --------------------------------------------
  * Whether copy number changes at a breakpoint: the depth between the two breakpoints of a deletion drops, that of a tandem
  * duplication rises, an unbalanced translocation shows a step at one breakpoint only.  depth1 / depth2 are the count at the
