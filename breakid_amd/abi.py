@@ -95,6 +95,12 @@ SPLIT_JUNCTION = np.dtype([("tid1", "<i4"), ("pos1", "<u4"), ("tid2", "<i4"), ("
                            ("reserved", "u1"), ("top_reads", "<u4")])  # struct bk_split_junction; pos 1-based
 assert SPLIT_JUNCTION.itemsize == 72
 SJ_MAX_TOL = 100  # BK_SJ_MAX_TOL
+CIGAR_GAP = np.dtype([("tid", "<i4"), ("start", "<u4"), ("len", "<u4"), ("kind", "<u4"), ("n_reads", "<u4"), ("n_rows", "<u4"), ("n_exact", "<u4"), ("top_reads", "<u4"),
+                      ("lo_start", "<u4"), ("hi_start", "<u4"), ("lo_len", "<u4"), ("hi_len", "<u4"), ("n_fwd", "<u4"), ("n_rev", "<u4"), ("mapq_sum", "<u8")])  # struct bk_cigar_gap; start 1-based
+assert CIGAR_GAP.itemsize == 64
+GAP_DEL, GAP_INS = 0, 1  # BK_GAP_DEL, BK_GAP_INS
+GAP_MAX_TOL = 100  # BK_GAP_MAX_TOL
+GAP_MAX_LEN = 1000000  # BK_GAP_MAX_LEN
 STRAND_NONE, STRAND_LEFT, STRAND_RIGHT = 0, 1, 2  # BK_STRAND_*
 # the columns of a bk_txmodel, in the struct's order (ex_off has n_tx + 1 entries, ex_start / ex_end n_parts)
 TXMODEL_COLS = [("tid", np.int32), ("tx_start", np.uint32), ("tx_end", np.uint32), ("strand", np.uint8), ("ex_off", np.uint32), ("ex_start", np.uint32), ("ex_end", np.uint32)]

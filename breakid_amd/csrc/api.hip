@@ -29,6 +29,7 @@
 #include "fragsize.h"
 #include "known.h"
 #include "sjcall.h"
+#include "gaps.h"
 #include "exclude.h"
 #include "ahc.h"
 #include "lanes.h"
@@ -197,6 +198,10 @@ struct bk_ctx
   std::vector<SjClaim> sj_claims;  // the voted rows' breakpoints, sorted; valid until the breakpoint stage runs again
   bool sj_claims_valid = false;
   std::vector<struct bk_split_junction> f_sj;
+  // CIGAR gaps (bk_cigar_gaps: this context holds the records)
+  GapBufs gpb;
+  GapStats gap_stats;
+  std::vector<struct bk_cigar_gap> f_gaps;
 
   // test hooks of the primitives (bk_debug_scan, bk_debug_radix_sort): buffers that live as long as the context, as a stage's do
   prims::RadixBufs dbg_radix;
@@ -1967,6 +1972,77 @@ int bk_split_junction_counts(bk_ctx *ctx, uint64_t out[6])
     if (!out) throw bk_error(BK_ERR_ARG, "bk_split_junction_counts: null out");
     const SjStats &t = ctx->sj_stats;
     out[0] = t.n; out[1] = t.eligible; out[2] = t.exact; out[3] = t.calls; out[4] = t.claimed; out[5] = t.rounds;
+  });
+}
+
+// Deletions and insertions from the CIGAR gaps of the context's record table (include/breakid_hip.h, gaps.hip)
+int bk_cigar_gaps(bk_ctx *records, int mapq_min, uint32_t min_len, uint32_t anchor, uint32_t tol, uint32_t min_reads, const struct bk_cigar_gap **out, uint64_t *count)
+{
+  return guarded(records, [&] {
+    if (!out || !count) throw bk_error(BK_ERR_ARG, "bk_cigar_gaps: null output");
+    if (records->shard) throw bk_error(BK_ERR_ARG, "bk_cigar_gaps: sharded contexts (bk_shard_*) are not supported");
+    if (!records->have_records) throw bk_error(BK_ERR_ARG, "bk_cigar_gaps: the context holds no record table");
+    if (mapq_min < 0) throw bk_error(BK_ERR_ARG, "bk_cigar_gaps: mapq_min below 0");
+    if (min_len == 0) throw bk_error(BK_ERR_ARG, "bk_cigar_gaps: min_len must be at least 1");
+    if (min_len > BK_GAP_MAX_LEN) throw bk_error(BK_ERR_ARG, "bk_cigar_gaps: min_len above " + std::to_string(BK_GAP_MAX_LEN));
+    if (anchor == 0) throw bk_error(BK_ERR_ARG, "bk_cigar_gaps: anchor must be at least 1");
+    if (tol > BK_GAP_MAX_TOL) throw bk_error(BK_ERR_ARG, "bk_cigar_gaps: tol above " + std::to_string(BK_GAP_MAX_TOL));
+    if (min_reads == 0) throw bk_error(BK_ERR_ARG, "bk_cigar_gaps: min_reads must be at least 1");
+    const bk_soa &t = records->rec;
+    if (t.n && (!t.tid || !t.pos || !t.flag || !t.mapq || !t.cigar_off || (!t.side && !t.qhash))) throw bk_error(BK_ERR_ARG, "bk_cigar_gaps: the record table lacks a column");
+    if (t.n_cigar_words && !t.cigar) throw bk_error(BK_ERR_ARG, "bk_cigar_gaps: the record table lacks a column");
+    GapInput in;
+    in.rec = rec_view(records);
+    in.n_cigar_words = t.n_cigar_words;
+    in.side = t.side;
+    in.qhash = t.qhash;
+    in.tprefix = records->d_tprefix.get<uint32_t>();
+    in.nt = records->nt;
+    for (const uint32_t l : records->tlen) in.max_len = std::max(in.max_len, l);
+    const GapParams p{mapq_min, min_len, anchor, tol, min_reads};
+    struct bk_cigar_gap *d_rows = nullptr;
+    records->gap_stats = GapStats{};
+    GapStats &s = records->gap_stats;
+    {
+      // (the two scopes inside push timers of their own, so the whole one ends by its index, not at timers.back())
+      struct Whole
+      {
+        bk_ctx *c;
+        size_t at;
+        ~Whole()
+        {
+          if (c->timing && at < c->timers.size()) (void) hipEventRecord(c->timers[at].b, c->st);
+        }
+      } whole{records, records->timers.size()};
+      records->tick("cigar_gaps", 0, true, 0);
+      {
+        Scope sc(records, "cigar_gaps_records");
+        gap_events(in, p, records->gpb, records->st, &s);
+      }
+      if (records->timing && !records->timers.empty()) records->timers.back().bytes = records->timers.back().touched = s.touched_records();
+      {
+        Scope sc(records, "cigar_gaps_calls");
+        gap_calls(p, records->gpb, records->st, &d_rows, &s);
+      }
+      if (records->timing && !records->timers.empty()) records->timers.back().bytes = records->timers.back().touched = s.touched_calls();
+      if (records->timing && whole.at < records->timers.size()) records->timers[whole.at].bytes = records->timers[whole.at].touched = s.touched_records() + s.touched_calls();
+    }
+    if (bk_debug("gaps"))
+      fprintf(stderr, "bk_cigar_gaps: %llu records, %llu eligible, %llu events, %llu beyond, %llu exact, %llu loci, %llu calls, %llu returned\n", (unsigned long long) s.n,
+              (unsigned long long) s.eligible, (unsigned long long) s.events, (unsigned long long) s.beyond, (unsigned long long) s.exact, (unsigned long long) s.loci,
+              (unsigned long long) s.calls, (unsigned long long) s.written);
+    rows_to_host(records, d_rows, s.written, records->f_gaps);
+    *out = records->f_gaps.data();
+    *count = s.written;
+  });
+}
+
+int bk_cigar_gap_counts(bk_ctx *records, uint64_t out[8])
+{
+  return guarded(records, [&] {
+    if (!out) throw bk_error(BK_ERR_ARG, "bk_cigar_gap_counts: null out");
+    const GapStats &t = records->gap_stats;
+    out[0] = t.n; out[1] = t.eligible; out[2] = t.events; out[3] = t.beyond; out[4] = t.exact; out[5] = t.loci; out[6] = t.calls; out[7] = t.written;
   });
 }
 

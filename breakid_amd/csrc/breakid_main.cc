@@ -1770,6 +1770,44 @@ static void split_junction_calls(const Options &o, const Sample &tumor, const ve
             << " written" << std::endl;
 }
 
+// ---- -gaps: deletions and insertions from CIGAR gaps --------------------------------------------------------------------------------
+// One call of bk_cigar_gaps on the sample's own table (-q is its mapq_min; -x applies by itself, because the table holds the kept records);
+// every returned call gets the depth at its start and at its right end (one call of bk_base_depth) and the gene at either.  It runs behind
+// every other stage and reads the table alone: no other file changes.
+static void cigar_gap_calls(const Options &o, const Sample &tumor, const vector<Txpt> &txpts)
+{
+  const struct bk_cigar_gap *calls = nullptr;
+  uint64_t n = 0, counts[8] = {};
+  int rc = bk_cigar_gaps(tumor.ctx, o.qual, (uint32_t) o.mingap, (uint32_t) o.gapanchor, (uint32_t) o.gaptol, (uint32_t) o.gapsupport, &calls, &n);
+  if (rc == BK_OK) rc = bk_cigar_gap_counts(tumor.ctx, counts);
+  if (rc != BK_OK) die(tumor, rc);
+  vector<GapRow> rows(n);
+  vector<int32_t> q_tid;
+  vector<uint32_t> q_pos;
+  for (uint64_t i = 0; i < n; ++i)
+  {
+    rows[i].g = calls[i];
+    q_tid.insert(q_tid.end(), {calls[i].tid, calls[i].tid});
+    q_pos.insert(q_pos.end(), {calls[i].start, gap_end(calls[i])});
+  }
+  const uint32_t *depth = nullptr;
+  if (n && (rc = bk_base_depth(tumor.ctx, q_tid.data(), q_pos.data(), q_tid.size(), &depth)) != BK_OK) die(tumor, rc);
+  for (size_t k = 0; k < rows.size(); ++k)
+  {
+    GapRow &r = rows[k];
+    r.chr = tumor.names[r.g.tid];
+    for (int s = 0; s < 2; ++s)
+    {
+      string exon, strand;
+      r.depth[s] = depth[2 * k + s];
+      annotate_side(txpts, r.chr, (long) q_pos[2 * k + s], r.gene[s], exon, strand);
+    }
+  }
+  write_gap_files(o, rows);
+  std::cout << "gaps: " << counts[1] << " records eligible, " << counts[2] << " events, " << counts[3] << " beyond a contig's end, " << counts[4] << " exact, " << counts[6]
+            << " calls, " << rows.size() << " written" << std::endl;
+}
+
 // write_enspan_params (:1170-1182); an option that changes what is called adds its line behind the reference's
 static void write_params(const Options &o, double w)
 {
@@ -1805,6 +1843,10 @@ static void write_params(const Options &o, double w)
   if (o.junctions) p << "junction_tol\t" << o.jtol << std::endl;
   if (o.complexity) p << "complexity_flank\t" << o.cplxflank << std::endl;
   if (o.complexity) p << "complexity_max_period\t" << o.cplxperiod << std::endl;
+  if (o.gaps) p << "gap_min_length\t" << o.mingap << std::endl;
+  if (o.gaps) p << "gap_anchor\t" << o.gapanchor << std::endl;
+  if (o.gaps) p << "gap_tol\t" << o.gaptol << std::endl;
+  if (o.gaps) p << "gap_min_support\t" << o.gapsupport << std::endl;
 }
 
 // BreakID.cc:175-191.  scan_pairs_count and after_cluster_count are never updated by the reference (always 0);
@@ -1905,6 +1947,7 @@ int main(int argc, char *argv[])
     exit(1);
   }
   if (o.junctions) split_junction_calls(o, tumor, txpts);
+  if (o.gaps) cigar_gap_calls(o, tumor, txpts);
   write_params(o, run.w);
   const clock_t end = clock();
   std::cout << "the fusion process of file " << o.inp_file << "  costs time: " << (end - start) / double(CLOCKS_PER_SEC) << " seconds" << std::endl;

@@ -56,6 +56,9 @@ int bk_known_calls(bk_ctx *ctx, const struct bk_known_entry *entries, uint64_t n
 // -junctions (junction calls from the split reads alone; bk_base_depth is listed with -clip)
 int bk_split_junctions(bk_ctx *ctx, int mapq_min, uint32_t tol, uint32_t min_reads, const struct bk_split_junction **out, uint64_t *count) __attribute__((weak));
 int bk_split_junction_counts(bk_ctx *ctx, uint64_t out[6]) __attribute__((weak));
+// -gaps (deletions and insertions from CIGAR gaps; bk_base_depth is listed with -clip)
+int bk_cigar_gaps(bk_ctx *records, int mapq_min, uint32_t min_len, uint32_t anchor, uint32_t tol, uint32_t min_reads, const struct bk_cigar_gap **out, uint64_t *count) __attribute__((weak));
+int bk_cigar_gap_counts(bk_ctx *records, uint64_t out[8]) __attribute__((weak));
 // -complexity
 int bk_site_complexity(bk_ctx *ctx, const bk_refseq *ref, const struct bk_ref_site *sites, uint64_t n, uint32_t flank, uint32_t max_period, const struct bk_site_cplx **out) __attribute__((weak));
 // -dedup
@@ -120,15 +123,20 @@ static const char *HELP =
      \t -jtol      \t bases up to which two junctions with equal sides are one call, 0 to 100 (with -junctions)  [2]\n \
      \t -complexity \t describe the reference around both breakpoints of every call by itself: soft-masked share, DUST score, GC and the exact tandem repeat at the breakpoint (twin files *_complexity.txt; LCDUST / LCGC / LCMASK / LCSTR with -vcf)  \n \
      \t -cplxflank \t bases either side of a breakpoint that are described, 1 to 255 (with -complexity)  [32]\n \
-     \t -cplxperiod \t longest repeat unit that is looked for, 1 to 64 (with -complexity)  [6]\n ";
+     \t -cplxperiod \t longest repeat unit that is looked for, 1 to 64 (with -complexity)  [6]\n \
+     \t -gaps      \t also call deletions and insertions that the aligner wrote inside an alignment, as a long D or I operation of the CIGAR (*_gaps.txt; *_gaps.bedpe with -bedpe)  \n \
+     \t -mingap    \t shortest D or I operation that counts, 1 to 1000000 (with -gaps)  [20]\n \
+     \t -gapanchor \t matched bases an alignment needs on either side of the operation, 1 to 2147483647 (with -gaps)  [10]\n \
+     \t -gaptol    \t bases up to which two gaps differ in start, and then in length, and are one call, 0 to 100 (with -gaps)  [2]\n \
+     \t -gapsupport \t distinct reads a gap needs, 1 to 1000000 (with -gaps)  [3]\n ";
 
 struct Options
 {
   std::string inp_file, out_file, nib_dir, normal_file, exclude_file, known_file, build = "hg19";
   int qual = 20, device = 0, n_gpus = 0, transport = BK_TRANSPORT_AUTO;  // -gpus N: one sample over N GPUs (include/breakid_multi.h)
   bool fast = false, all = false;                                        // -all: no gene-pair and repeat filter (the _fusion_all files)
-  bool genotype = false, vcf = false, evidence = false, clip = false, dedup = false, consensus = false, homology = false, similar = false, coverage = false, frame = false, link = false, partners = false, fragsize = false, bedpe = false, context = false, junctions = false, complexity = false;
-  bool anchor_given = false, minclip_given = false, clipsupport_given = false, conslen_given = false, homshift_given = false, homins_given = false, simflank_given = false, covflank_given = false, linkdist_given = false, knownslop_given = false, ctxflank_given = false, jsupport_given = false, jtol_given = false, cplxflank_given = false, cplxperiod_given = false;
+  bool genotype = false, vcf = false, evidence = false, clip = false, dedup = false, consensus = false, homology = false, similar = false, coverage = false, frame = false, link = false, partners = false, fragsize = false, bedpe = false, context = false, junctions = false, complexity = false, gaps = false;
+  bool anchor_given = false, minclip_given = false, clipsupport_given = false, conslen_given = false, homshift_given = false, homins_given = false, simflank_given = false, covflank_given = false, linkdist_given = false, knownslop_given = false, ctxflank_given = false, jsupport_given = false, jtol_given = false, cplxflank_given = false, cplxperiod_given = false, mingap_given = false, gapanchor_given = false, gaptol_given = false, gapsupport_given = false;
   long anchor = 10;                      // -anchor: bases a reference read must cover on either side of the breakpoint base
   long min_clip = 10, clip_support = 3;  // -minclip: shortest clip that counts; -clipsupport: reads at one position a rescued side needs
   long conslen = 64;                     // -conslen: longest junction sequence per side
@@ -140,6 +148,7 @@ struct Options
   long ctxflank = 500;                   // -ctxflank: the bases either side of a cut in which bk_window_context counts the records that start there
   long jsupport = 3, jtol = 2;           // -jsupport, -jtol: min_reads and tol of bk_split_junctions
   long cplxflank = 32, cplxperiod = 6;   // -cplxflank, -cplxperiod: flank and max_period of bk_site_complexity
+  long mingap = 20, gapanchor = 10, gaptol = 2, gapsupport = 3;  // -mingap, -gapanchor, -gaptol, -gapsupport: min_len, anchor, tol and min_reads of bk_cigar_gaps
   bool multi() const { return n_gpus >= 1; }  // the sharded run
   bool known() const { return !known_file.empty(); }
   bool with_normal() const { return !normal_file.empty(); }
@@ -188,6 +197,7 @@ static void check_options(const Options &o)
   const Feature context{"-context", o.context, false, bk_window_context && bk_call_windows && bk_junctions && bk_junction_sides};
   const Feature junctions{"-junctions", o.junctions, false, bk_split_junctions && bk_split_junction_counts && bk_base_depth};
   const Feature complexity{"-complexity", o.complexity, false, bk_site_complexity != nullptr};
+  const Feature gaps{"-gaps", o.gaps, false, bk_cigar_gaps && bk_cigar_gap_counts && bk_base_depth};
   const Feature consensus{"-consensus", o.consensus, false, bk_clip_consensus && bk_clip_reads && bk_evidence && bk_junctions && bk_junction_sides};
   const Feature clip{"-clip", o.clip, false, bk_clip_support && bk_clip_reads && bk_base_depth && bk_clip_rescue && bk_junctions && bk_junction_sides};
   const Feature exclude{"-x", o.exclude(), true, bk_exclude_regions && bk_multi_run_ex && bk_multi_run_bam_ex && bk_multi_excluded};
@@ -238,6 +248,11 @@ static void check_options(const Options &o)
       gpus(complexity), library(complexity),
       rule(o.complexity && !in_range(o.cplxflank, 1, 255), "-cplxflank must be a number from 1 to 255."),
       rule(o.complexity && !in_range(o.cplxperiod, 1, 64), "-cplxperiod must be a number from 1 to 64."),
+      rule((o.mingap_given || o.gapanchor_given || o.gaptol_given || o.gapsupport_given) && !o.gaps, "-mingap, -gapanchor, -gaptol and -gapsupport need -gaps."), gpus(gaps),
+      rule(o.gaps && !in_range(o.mingap, 1, 1000000), "-mingap must be a number from 1 to 1000000."),
+      rule(o.gaps && !in_range(o.gapanchor, 1, int_max), "-gapanchor must be a number from 1 to 2147483647."),
+      rule(o.gaps && !in_range(o.gaptol, 0, 100), "-gaptol must be a number from 0 to 100."),
+      rule(o.gaps && !in_range(o.gapsupport, 1, 1000000), "-gapsupport must be a number from 1 to 1000000."), library(gaps),
   };
   for (const Refusal &r : refusals)
   {
@@ -267,6 +282,7 @@ static Options parse_options(int argc, char *argv[])
                                      {"context", 0, 0, 38}, {"ctxflank", 1, 0, 39},
                                      {"junctions", 0, 0, 40}, {"jsupport", 1, 0, 41}, {"jtol", 1, 0, 42},
                                      {"complexity", 0, 0, 43}, {"cplxflank", 1, 0, 44}, {"cplxperiod", 1, 0, 45},
+                                     {"gaps", 0, 0, 46}, {"mingap", 1, 0, 47}, {"gapanchor", 1, 0, 48}, {"gaptol", 1, 0, 49}, {"gapsupport", 1, 0, 50},
                                      {"f", 0, 0, 5},  // (-f used to complete to -fast alone; it still means it beside -frame)
                                      {0, 0, 0, 0}};
   Options o;
@@ -326,6 +342,11 @@ static Options parse_options(int argc, char *argv[])
     case 43: o.complexity = true; break;
     case 44: number(o.cplxflank, o.cplxflank_given); break;
     case 45: number(o.cplxperiod, o.cplxperiod_given); break;
+    case 46: o.gaps = true; break;
+    case 47: number(o.mingap, o.mingap_given); break;
+    case 48: number(o.gapanchor, o.gapanchor_given); break;
+    case 49: number(o.gaptol, o.gaptol_given); break;
+    case 50: number(o.gapsupport, o.gapsupport_given); break;
     default: std::cerr << "Error: cannot parse arguments.\n"; exit(1);
     }
   }

@@ -791,6 +791,41 @@ static void write_junction_files(const Options &o, const vector<SjRow> &rows)
   }
 }
 
+// -gaps: <prefix>_gaps.txt, the calls of bk_cigar_gaps in the order of the call's table, and with -bedpe <prefix>_gaps.bedpe in the layout of
+// write_junction_files: score = Reads, then gp<row>, Type, 0 and Reads.  Start is the last reference base in front of the gap, End the
+// first one behind it (Start + Len + 1 for a deletion, Start + 1 for an insertion).  Nothing is filtered beyond -gapsupport.
+struct GapRow
+{
+  struct bk_cigar_gap g;
+  uint32_t depth[2];
+  string chr, gene[2];
+};
+static const char *GAP_COLUMNS = "Gap\tChr\tStart\tEnd\tType\tLen\tReads\tRows\tExact\tTopReads\tFwd\tRev\tMeanMQ\tStartSpan\tLenSpan\tDepth1\tDepth2\tGene1\tGene2";
+static uint32_t gap_end(const struct bk_cigar_gap &g) { return g.kind == BK_GAP_DEL ? g.start + g.len + 1 : g.start + 1; }
+static void write_gap_files(const Options &o, const vector<GapRow> &rows)
+{
+  const size_t slash = o.out_file.find_last_of('/');
+  const string sample = slash == string::npos ? o.out_file : o.out_file.substr(slash + 1);
+  std::ofstream table((o.out_file + "_gaps.txt").c_str()), bedpe;
+  if (o.bedpe) bedpe.open((o.out_file + "_gaps.bedpe").c_str());
+  table << GAP_COLUMNS << "\n";
+  char mq[32];
+  for (size_t i = 0; i < rows.size(); ++i)
+  {
+    const GapRow &r = rows[i];
+    const struct bk_cigar_gap &g = r.g;
+    const char *type = g.kind == BK_GAP_DEL ? "deletion" : "insertion";
+    const uint32_t end = gap_end(g);
+    snprintf(mq, sizeof mq, "%.1f", (double) g.mapq_sum / (double) g.n_rows);  // (a call has at least one row)
+    table << "gp" << i << "\t" << r.chr << "\t" << g.start << "\t" << end << "\t" << type << "\t" << g.len << "\t" << g.n_reads << "\t" << g.n_rows << "\t" << g.n_exact << "\t"
+          << g.top_reads << "\t" << g.n_fwd << "\t" << g.n_rev << "\t" << mq << "\t" << g.lo_start << "-" << g.hi_start << "\t" << g.lo_len << "-" << g.hi_len << "\t" << r.depth[0]
+          << "\t" << r.depth[1] << "\t" << r.gene[0] << "\t" << r.gene[1] << "\n";
+    if (bedpe.is_open())
+      bedpe << r.chr << "\t" << (long long) g.start - 1 << "\t" << g.start << "\t" << r.chr << "\t" << (long long) end - 1 << "\t" << end << "\t" << (sample.empty() ? "." : sample) << "\t"
+            << g.n_reads << "\t+\t-\tgp" << i << "\t" << type << "\t0\t" << g.n_reads << "\n";
+  }
+}
+
 // -clip: <prefix>_fusion_rescued.txt, a table with the clip columns, and with -normal <prefix>_fusion_rescued_normal.txt: the same rows
 // with the normal's evidence at the rescued peaks behind them
 static void write_rescued_tables(const Options &o, const Rescued &rescued, const CallTables &t)

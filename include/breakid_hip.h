@@ -1097,6 +1097,89 @@ int bk_split_junction_counts(bk_ctx *ctx, uint64_t out[6]);
 int bk_debug_split_junctions(bk_ctx *ctx, int mapq_min, uint32_t tol, uint32_t min_reads, const bk_cluster *rows, uint64_t n_rows, const struct bk_split_junction **out,
                              uint64_t *count);
 
+/* ---- CIGAR gaps: deletions and insertions the aligner wrote inside an alignment -------------------------------------------------------
+ * An aligner writes a 30- to 100-base deletion in the middle of a read as 70M45D80M, not as a split read: such a record has no SA
+ * tag, no soft clip and a proper pair, so no other call sees it.  This call walks the CIGAR of every record of the table and groups
+ * the long D and I operations.  All arithmetic is integer.
+ *   eligible    A record is eligible when tid >= 0, none of the flags 0x4 0x100 0x200 0x400 0x800 is set and mapq >= mapq_min.
+ *   walk        p = pos (0-based) equals the 1-based coordinate of the last reference base consumed so far.  M = X add their length
+ *               to p and to the matched count; D N add their length to p only; I S H P do not move p.
+ *   event       An operation D (kind BK_GAP_DEL = 0) or I (kind BK_GAP_INS = 1) of length len >= min_len gives an event with start =
+ *               p before the operation.  A deletion removes start + 1 .. start + len; its right end is start + len + 1.  An insertion
+ *               lies between start and start + 1; its right end is start + 1.  N never gives an event: it is the aligner's statement
+ *               of a splice.
+ *   anchor      The M = X lengths of all operations in front of the event, and of all operations behind it, must each sum to at least
+ *               `anchor`.  Other gaps in between do not reset the sums.
+ *   beyond      An event whose right end exceeds the contig's length is dropped and counted as beyond.  (So is one with a start
+ *               below 0, which needs pos < 0 on a mapped record, and every event of a tid at or above n_targets: neither is valid BAM.)
+ *   read        A read is its qhash.  Two mates that both cross a gap are one read.
+ *   exact       Equal (kind, tid, start, len) are one exact event.
+ *   locus       A maximal run of exact events of one kind on one contig whose sorted starts differ by at most tol from one to the next.
+ *   call        Within a locus, a maximal run of sorted lens that differ by at most tol from one to the next.
+ * This is two one-dimensional single linkages, first on start, then on len inside the locus; both can chain, and the spans in the row
+ * show the extent.  It is not the two-dimensional linkage of bk_split_junctions: two events 2 * tol apart in start with equal len are
+ * one call when a third event of any other length bridges their starts.  Nothing is capped and nothing costs k * k.
+ * Row: (tid, start, len, kind) is the representative, the call's exact event with the most distinct reads (top_reads of them), ties
+ * to the smaller (start, len).  n_reads counts the distinct qhash of the call, n_rows its events (records x operations), n_exact its
+ * exact events; lo_start .. hi_len are the extremes over its events; n_fwd / n_rev count the rows by flag 0x10 (one-strand support
+ * is the classic gap artefact); mapq_sum adds the records' mapq over the rows.
+ * Output: the calls with n_reads >= min_reads, ordered by (kind, tid, first start of the locus, lowest len of the call).  Every
+ * output is a count, a sum, an extreme or an argmax with a fixed tie rule: two runs give the same bytes.
+ * Hand example (one contig of 1 000 000 bases, mapq_min 20, min_len 20, anchor 10, tol 2, min_reads 1; pos 0-based; flag 0x10 = reverse):
+ *   a, b, c   pos  999  70M45D80M    mapq 60            DEL start 1069 len 45 (removes 1070 .. 1114, right end 1115)
+ *   d         pos 1000  70M46D79M    mapq 40, reverse   DEL start 1070 len 46
+ *   d (mate)  pos 1039  30M45D120M   mapq 60            DEL start 1069 len 45
+ *   e         pos 1059  10M30I110M   mapq 30            INS start 1069 len 30
+ *   f         pos 1060  9M45D141M    mapq 60            none: 9 matched bases in front
+ *   g         pos  999  70M45N80M    mapq 60            none: N
+ * Counts: 8 records, 8 eligible, 6 events, 0 beyond, 3 exact, 2 loci, 2 calls, 2 written.  Row 0: tid 0 start 1069 len 45 kind 0,
+ * n_reads 4, n_rows 5, n_exact 2, top_reads 4, lo_start 1069, hi_start 1070, lo_len 45, hi_len 46, n_fwd 4, n_rev 1, mapq_sum 280.
+ * Row 1: tid 0 start 1069 len 30 kind 1, n_reads 1, n_rows 1, n_exact 1, top_reads 1, 1069 1069 30 30, n_fwd 1, n_rev 0, mapq_sum 30.
+ * With tol 0 there are three calls; with min_reads 2 only row 0.
+ * The struct has no typedef. */
+#define BK_GAP_DEL 0u
+#define BK_GAP_INS 1u
+#define BK_GAP_MAX_TOL 100u
+#define BK_GAP_MAX_LEN 1000000u
+struct bk_cigar_gap {
+  int32_t tid; uint32_t start; uint32_t len; uint32_t kind;   /* the representative exact event */
+  uint32_t n_reads, n_rows, n_exact;     /* distinct qhash, events, exact events of the call */
+  uint32_t top_reads;                    /* distinct reads of the representative */
+  uint32_t lo_start, hi_start, lo_len, hi_len;   /* spans of the call */
+  uint32_t n_fwd, n_rev;                 /* rows by flag 0x10 */
+  uint64_t mapq_sum;                     /* over rows */
+};                                       /* 64 bytes */
+/* records: a context that holds a record table (host upload, BK_MEM_DEVICE with and without `side`, the table bk_exclude_regions
+ * left behind - so excluded regions are honoured by themselves -, the context of bk_bam_decode_device_ctx while its bk_bam_dev
+ * lives) and is not a shard (bk_shard_*); no stage need have run.  *out (*count rows) is library-owned until the next call or
+ * bk_free.  BK_ERR_ARG (with the reason in bk_last_error) for null outputs, a sharded context, a context without a table, mapq_min
+ * < 0, min_len, anchor or min_reads of 0, min_len > BK_GAP_MAX_LEN and tol > BK_GAP_MAX_TOL.  BK_ERR_LIMIT beyond 2^30 events.  A
+ * table without events is no error: *count = 0.  It changes nothing a later bk_fetch or bk_run returns.
+ * How: the record pass, one wavefront per tile of 256 records, four consecutive records a lane, cigar_off, flag and mapq read as
+ * vectors; only a record whose flag and mapq pass and that has three or more operations (fewer cannot hold an anchored gap) has its
+ * tid, pos and CIGAR words fetched, and one lane walks one CIGAR of any length.  Pass one sums the events per tile (it also reads
+ * tid as a vector: the count of eligible records needs it and the table need not be sorted yet), a scan makes the sums offsets, pass
+ * two walks the records of the tiles that hold an event again and writes the events in record order (32 bytes: qhash, start, len,
+ * kind and contig, strand and mapq).  Then stable LSD stages of the radix sort by qhash (64 bits; run heads and a scan turn the hash
+ * into a dense rank), by len (28 bits) and by (kind, tid, start) over 1 + bits(n_targets - 1) + bits(longest contig) bits; the
+ * heads of the loci and a scan; one stage by (locus, len) over bits(loci) + 28 bits; the heads of the calls, of the exact events and
+ * of the reads inside them, with their scans; one stage by (call, read rank), whose run heads are the distinct reads of a call; one
+ * wavefront per call for its row; a scan compacts the calls by min_reads.  No atomic anywhere: every result word has one writer.
+ * The host reads a count four times, where a buffer or a key must be sized: the events (with the eligible records and beyond), the
+ * loci, the exact events with the calls, the returned rows.
+ * bk_timing: scope `cigar_gaps`, and inside it `cigar_gaps_records` (the record pass) and `cigar_gaps_calls`.  bk_timing_touched,
+ * with T = ceil(records / 256), bits(x) the position of the highest set bit of x from 1 (0 for 0) and a radix pass costing 36 bytes
+ * per item: cigar_gaps_records = 11 * records (cigar_off, flag, mapq, tid) + 56 * T (the two tile words written, scanned and read)
+ * + 1792 * min(events, T) (at most that many tiles are read again, 7 bytes a record) + 48 * events (tid, pos, qhash, the row);
+ * cigar_gaps_calls = events * (36 * (P1 + P2 + P3) + 400) + 144 * calls + 128 * written, P1 = 8 + 4 + ceil((bits(longest contig) +
+ * bits(n_targets - 1) + 1) / 8), P2 = ceil((bits(loci) + 28) / 8), P3 = ceil((bits(calls) + bits(events)) / 8); 400 = three key
+ * gathers (132), the read ranks (24), two sorted copies (128), the loci (20), the three heads, scans and two start lists (60), the
+ * read key with its heads and scan (36).  cigar_gaps is their sum.  The CIGAR words that the walks read are not modelled. */
+int bk_cigar_gaps(bk_ctx *records, int mapq_min, uint32_t min_len, uint32_t anchor, uint32_t tol, uint32_t min_reads, const struct bk_cigar_gap **out, uint64_t *count);
+/* What the last bk_cigar_gaps of this context counted: out[0] records, [1] eligible records, [2] events, [3] events beyond a contig's
+ * end, [4] exact events, [5] loci, [6] calls before min_reads, [7] returned rows.  BK_ERR_ARG for a null argument. */
+int bk_cigar_gap_counts(bk_ctx *records, uint64_t out[8]);
+
 /* Copy a stage's result to library-owned host memory.  *data stays valid until the next bk_fetch
  * of the same stage or bk_free.  group_off (may be NULL) receives n_groups+1 offsets for pair stages. */
 int bk_fetch(bk_ctx *ctx, int stage, const void **data, uint64_t *count, const uint64_t **group_off, uint32_t *n_groups);
