@@ -193,6 +193,10 @@ class ShardStats(C.Structure):
 
 
 BUF_CANDIDATES, BUF_TUPLES, BUF_CLUSTERS = 0, 1, 2
+# struct Cand (csrc/bk_common.h): a row of BUF_CANDIDATES
+CAND = np.dtype([("qhash", "<u8"), ("rec", "<u8"), ("tid", "<i4"), ("pos", "<i4"), ("mtid", "<i4"), ("mpos", "<i4"), ("flag", "<u2"), ("mapq", "u1"), ("pad", "u1"),
+                 ("qcheck", "<u4")])
+assert CAND.itemsize == 40
 
 
 def device_ptrs(cols):

@@ -36,7 +36,7 @@ def build(verbose=False):
 EXPORTS = ["bk_init", "bk_prepare_process", "bk_free", "bk_last_error", "bk_set_stream", "bk_sync", "bk_get_stream", "bk_upload_records", "bk_records", "bk_exclude_regions", "bk_isize_stats",
            "bk_discordant_pairs", "bk_mask_and_cluster", "bk_split_evidence", "bk_cluster_summary",
            "bk_split_breakpoints", "bk_normal_support", "bk_ref_support", "bk_genotype_call", "bk_clip_support", "bk_clip_reads", "bk_base_depth", "bk_clip_rescue", "bk_junctions", "bk_junction_sides", "bk_vcf_breakend_alt", "bk_evidence", "bk_unique_support", "bk_clip_consensus", "bk_junction_fit", "bk_locus_similarity", "bk_site_complexity", "bk_window_coverage", "bk_window_context", "bk_call_windows", "bk_fusion_frame", "bk_link_calls", "bk_locus_partners", "bk_call_partner_sites", "bk_fragment_sizes", "bk_fragment_bounds", "bk_known_calls", "bk_split_junctions", "bk_split_junction_counts", "bk_debug_split_junctions", "bk_cigar_gaps", "bk_cigar_gap_counts", "bk_run", "bk_fetch", "bk_timing", "bk_timing_enable", "bk_timing_touched", "bk_group_stats", "bk_qname_hash", "bk_qname_check",
-           "bk_bam_open", "bk_bam_header", "bk_bam_decode", "bk_bam_close", "bk_bam_extract", "bk_bam_names_free", "bk_bam_reads", "bk_reads_free", "bk_bam_decode_device", "bk_bam_decode_device_part", "bk_bam_decode_device_ctx", "bk_bam_dev_free", "bk_feed_release_caches", "bk_debug_bgzf_inflate", "bk_debug_std_sort", "bk_debug_scan", "bk_debug_radix_sort", "bk_debug_prims_info", "bk_sort_forms", "bk_debug_ahc", "bk_debug_points", "bk_debug_points_groups", "bk_debug_cluster_info", "bk_debug_cigar", "bk_debug_vote", "bk_debug_region", "bk_shard_begin", "bk_shard_get_stats", "bk_shard_set_stats",
+           "bk_bam_open", "bk_bam_header", "bk_bam_decode", "bk_bam_close", "bk_bam_extract", "bk_bam_names_free", "bk_bam_reads", "bk_reads_free", "bk_bam_decode_device", "bk_bam_decode_device_part", "bk_bam_decode_device_ctx", "bk_bam_dev_free", "bk_feed_release_caches", "bk_debug_bgzf_inflate", "bk_debug_std_sort", "bk_debug_scan", "bk_debug_radix_sort", "bk_debug_prims_info", "bk_sort_forms", "bk_debug_ahc", "bk_debug_points", "bk_debug_points_groups", "bk_debug_cluster_info", "bk_debug_stream_info", "bk_debug_stream_blocks", "bk_debug_cigar", "bk_debug_vote", "bk_debug_region", "bk_shard_begin", "bk_shard_get_stats", "bk_shard_set_stats",
            "bk_shard_sd_local", "bk_shard_sd_finish", "bk_shard_buffer", "bk_shard_set_buffer", "bk_shard_group_sizes",
            "bk_shard_own_groups", "bk_shard_route_candidates", "bk_shard_group_keys", "bk_shard_route_pairs", "bk_shard_group_pairs", "bk_shard_bp_cov", "bk_shard_bp_vote", "bk_shard_bp_vote_slice", "bk_shard_bp_set_voted", "bk_shard_bp_depth", "bk_shard_bp_finish"]
 
@@ -116,6 +116,8 @@ def lib():
         L.bk_debug_points.argtypes = [vp, C.c_int, vp, vp, C.c_uint32, C.c_double, vp, vp, C.POINTER(C.c_uint32)]
         L.bk_debug_points_groups.argtypes = [vp, C.c_int, vp, vp, vp, C.c_uint32, C.c_double, vp, vp, vp, C.POINTER(C.c_uint32)]
         L.bk_debug_cluster_info.argtypes = [u64p]
+        L.bk_debug_stream_info.argtypes = [u64p]
+        L.bk_debug_stream_blocks.argtypes = [C.c_uint]
         L.bk_debug_cigar.argtypes = [vp, C.c_uint32, vp, vp, vp, vp, vp, vp, vp]
         L.bk_debug_vote.argtypes = [vp, vp, C.c_uint32, vp, C.c_uint32, C.c_int32, C.c_int32, vp]
         L.bk_debug_region.argtypes = [vp, C.c_int32, C.c_uint32, C.c_uint32, C.c_uint64, vp, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
@@ -238,6 +240,23 @@ def cluster_info():
     if rc != 0:
         raise BreakIDError(rc, "bk_debug_cluster_info")
     return dict(zip(("FW_TILE", "FW_LEVELS"), (int(v) for v in out)))
+
+
+def stream_info():
+    """The constants of the built stream pass (bk_debug_stream_info): STREAM_V, ST_CAND_CAP, ST_SA_CAP and RESIDENT, the number of
+    blocks launch_stream takes for one resident set (0 in a process without a device; the other three need none)."""
+    out = (C.c_uint64 * 4)()
+    rc = lib().bk_debug_stream_info(out)
+    if rc != 0:
+        raise BreakIDError(rc, "bk_debug_stream_info")
+    return dict(zip(("STREAM_V", "ST_CAND_CAP", "ST_SA_CAP", "RESIDENT"), (int(v) for v in out)))
+
+
+def stream_blocks(blocks):
+    """Cap the grid of k_stream for the whole process (bk_debug_stream_blocks); 0 = no cap, the default.  Tests only: set it back."""
+    rc = lib().bk_debug_stream_blocks(int(blocks))
+    if rc != 0:
+        raise BreakIDError(rc, "bk_debug_stream_blocks")
 
 
 def w_from(mean, sd):

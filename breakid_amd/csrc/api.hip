@@ -2870,6 +2870,26 @@ int bk_debug_cluster_info(uint64_t out[2])
   return BK_OK;
 }
 
+int bk_debug_stream_info(uint64_t out[4])
+{
+  if (!out) return BK_ERR_ARG;
+  try
+  {
+    stream_debug_info(out);
+  }
+  catch (const bk_error &e)
+  {
+    return e.code;
+  }
+  return BK_OK;
+}
+
+int bk_debug_stream_blocks(unsigned blocks)
+{
+  stream_debug_blocks(blocks);
+  return BK_OK;
+}
+
 int bk_debug_cigar(bk_ctx *ctx, uint32_t n, const uint8_t *kind, const uint32_t *c1_off, const uint8_t *c1, const uint32_t *c2_off, const uint8_t *c2, const int32_t *e,
                    int32_t *out6)
 {

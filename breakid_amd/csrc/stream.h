@@ -67,6 +67,10 @@ struct StreamArgs
 };
 
 void launch_stream(const StreamArgs &a, hipStream_t st);
+// test hooks: a cap on the grid of k_stream (0 = none); STREAM_V, the two LDS bin capacities and the resident block count of launch_stream
+// (0 without a device)
+void stream_debug_blocks(unsigned blocks);
+void stream_debug_info(uint64_t out[4]);
 // side[i] = {qhash[i], mtid[i], mpos[i], qcheck ? qcheck[i] : 0} (include/breakid_hip.h: bk_side)
 void launch_make_side(const uint64_t *qhash, const int32_t *mtid, const int32_t *mpos, const uint32_t *qcheck, uint64_t n, bk_side *side, hipStream_t st);
 void launch_split_records(const StreamArgs &a, unsigned long long n_sa, hipStream_t st);

@@ -895,12 +895,10 @@ __global__ __launch_bounds__(64) void k_sd_walk(const SdException *__restrict__ 
 }  // namespace
 
 // ---- host side ----------------------------------------------------------------------------------------
-void launch_stream(const StreamArgs &a, hipStream_t st)
+// exactly one resident set of blocks (grid-stride loop inside): a block more than fits leaves a tail that runs at
+// a fraction of the occupancy (measured 4.7 vs 6.1 TB/s at 6 vs 5 blocks per CU, LDS bins ~29 KiB per block)
+static unsigned stream_resident_blocks()
 {
-  if (a.n <= (uint64_t) STREAM_V * a.q_begin) return;
-  unsigned blocks = cdiv(a.n / STREAM_V - a.q_begin + 1, 256);
-  // exactly one resident set of blocks (grid-stride loop inside): a block more than fits leaves a tail that runs at
-  // a fraction of the occupancy (measured 4.7 vs 6.1 TB/s at 6 vs 5 blocks per CU, LDS bins ~29 KiB per block)
   static unsigned resident = 0;
   if (!resident)
   {
@@ -911,8 +909,32 @@ void launch_stream(const StreamArgs &a, hipStream_t st)
     HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_stream, 256, 0));
     resident = (unsigned) (per_cu < 1 ? 1 : per_cu) * (unsigned) prop.multiProcessorCount;
   }
+  return resident;
+}
+
+// test hook (bk_debug_stream_blocks): a process-wide cap on the grid of k_stream, 0 = none.  With a small grid a table of a few
+// thousand records runs many iterations per block, which is what the flush windows and the bin edges of k_stream depend on.
+static unsigned g_stream_block_cap = 0;
+
+void launch_stream(const StreamArgs &a, hipStream_t st)
+{
+  if (a.n <= (uint64_t) STREAM_V * a.q_begin) return;
+  unsigned blocks = cdiv(a.n / STREAM_V - a.q_begin + 1, 256);
+  const unsigned resident = stream_resident_blocks();
   if (blocks > resident) blocks = resident;
+  if (g_stream_block_cap && blocks > g_stream_block_cap) blocks = g_stream_block_cap;
   hipLaunchKernelGGL(k_stream, dim3(blocks), dim3(256), 0, st, a);
+}
+
+void stream_debug_blocks(unsigned blocks) { g_stream_block_cap = blocks; }
+
+void stream_debug_info(uint64_t out[4])
+{
+  out[0] = ST_V;
+  out[1] = ST_CAND_CAP;
+  out[2] = ST_SA_CAP;
+  int ndev = 0;
+  out[3] = (hipGetDeviceCount(&ndev) == hipSuccess && ndev > 0) ? stream_resident_blocks() : 0;  // (0: no device to ask)
 }
 
 void launch_split_records(const StreamArgs &a, unsigned long long n_sa, hipStream_t st)

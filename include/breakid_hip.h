@@ -1307,6 +1307,14 @@ int bk_debug_points(bk_ctx *ctx, int mode, const uint32_t *x, const uint32_t *y,
 int bk_debug_points_groups(bk_ctx *ctx, int mode, const uint32_t *x, const uint32_t *y, const uint64_t *group_off, uint32_t n_groups, double w, uint32_t *idx_out,
                            int32_t *cluster_out, uint64_t *goff_out, uint32_t *n_out);
 int bk_debug_cluster_info(uint64_t out[2]);
+/*   bk_debug_stream_info    the constants of the built stream pass (csrc/stream.hip): STREAM_V (records per lane and iteration), the
+ *                    capacities of the LDS candidate bin and of the LDS bin of SA-bearing record indices, and the number of blocks
+ *                    launch_stream takes for one resident set (0 in a process without a device; nothing else needs one)
+ *   bk_debug_stream_blocks  a process-wide cap on the grid of k_stream, applied after the resident cap; 0 = none (the default).
+ *                    With a cap of 1 .. 3 a table of a few thousand records runs many iterations per block, so the tests reach
+ *                    the flush windows and the edges of the two bins at small sizes.  Set it back to 0 afterwards. */
+int bk_debug_stream_info(uint64_t out[4]);
+int bk_debug_stream_blocks(unsigned blocks);
 int bk_debug_cigar(bk_ctx *ctx, uint32_t n, const uint8_t *kind, const uint32_t *c1_off, const uint8_t *c1, const uint32_t *c2_off, const uint8_t *c2, const int32_t *e,
                    int32_t *out6);
 int bk_debug_vote(bk_ctx *ctx, const bk_split *side1, uint32_t n1, const bk_split *side2, uint32_t n2, int32_t p1_tid, int32_t p2_tid, int32_t *out3);
