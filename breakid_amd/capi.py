@@ -36,7 +36,7 @@ def build(verbose=False):
 EXPORTS = ["bk_init", "bk_prepare_process", "bk_free", "bk_last_error", "bk_set_stream", "bk_sync", "bk_get_stream", "bk_upload_records", "bk_records", "bk_exclude_regions", "bk_isize_stats",
            "bk_discordant_pairs", "bk_mask_and_cluster", "bk_split_evidence", "bk_cluster_summary",
            "bk_split_breakpoints", "bk_normal_support", "bk_ref_support", "bk_genotype_call", "bk_clip_support", "bk_clip_reads", "bk_base_depth", "bk_clip_rescue", "bk_junctions", "bk_junction_sides", "bk_vcf_breakend_alt", "bk_evidence", "bk_unique_support", "bk_clip_consensus", "bk_junction_fit", "bk_locus_similarity", "bk_site_complexity", "bk_window_coverage", "bk_window_context", "bk_call_windows", "bk_fusion_frame", "bk_link_calls", "bk_locus_partners", "bk_call_partner_sites", "bk_fragment_sizes", "bk_fragment_bounds", "bk_known_calls", "bk_split_junctions", "bk_split_junction_counts", "bk_debug_split_junctions", "bk_cigar_gaps", "bk_cigar_gap_counts", "bk_run", "bk_fetch", "bk_timing", "bk_timing_enable", "bk_timing_touched", "bk_group_stats", "bk_qname_hash", "bk_qname_check",
-           "bk_bam_open", "bk_bam_header", "bk_bam_decode", "bk_bam_close", "bk_bam_extract", "bk_bam_names_free", "bk_bam_reads", "bk_reads_free", "bk_bam_decode_device", "bk_bam_decode_device_part", "bk_bam_decode_device_ctx", "bk_bam_dev_free", "bk_feed_release_caches", "bk_debug_bgzf_inflate", "bk_debug_std_sort", "bk_debug_scan", "bk_debug_radix_sort", "bk_debug_prims_info", "bk_sort_forms", "bk_debug_ahc", "bk_debug_points", "bk_debug_points_groups", "bk_debug_cluster_info", "bk_debug_stream_info", "bk_debug_stream_blocks", "bk_debug_cigar", "bk_debug_vote", "bk_debug_region", "bk_shard_begin", "bk_shard_get_stats", "bk_shard_set_stats",
+           "bk_bam_open", "bk_bam_header", "bk_bam_decode", "bk_bam_close", "bk_bam_extract", "bk_bam_names_free", "bk_bam_reads", "bk_reads_free", "bk_bam_decode_device", "bk_bam_decode_device_part", "bk_bam_decode_device_ctx", "bk_bam_dev_free", "bk_feed_release_caches", "bk_debug_bgzf_inflate", "bk_debug_std_sort", "bk_debug_scan", "bk_debug_radix_sort", "bk_debug_prims_info", "bk_sort_forms", "bk_debug_sort_info", "bk_debug_ahc", "bk_debug_points", "bk_debug_points_groups", "bk_debug_cluster_info", "bk_debug_stream_info", "bk_debug_stream_blocks", "bk_debug_cigar", "bk_debug_vote", "bk_debug_region", "bk_shard_begin", "bk_shard_get_stats", "bk_shard_set_stats",
            "bk_shard_sd_local", "bk_shard_sd_finish", "bk_shard_buffer", "bk_shard_set_buffer", "bk_shard_group_sizes",
            "bk_shard_own_groups", "bk_shard_route_candidates", "bk_shard_group_keys", "bk_shard_route_pairs", "bk_shard_group_pairs", "bk_shard_bp_cov", "bk_shard_bp_vote", "bk_shard_bp_vote_slice", "bk_shard_bp_set_voted", "bk_shard_bp_depth", "bk_shard_bp_finish"]
 
@@ -112,6 +112,7 @@ def lib():
         L.bk_debug_radix_sort.argtypes = [vp, vp, vp, C.c_uint64, C.c_int, C.c_int, vp, vp]
         L.bk_debug_prims_info.argtypes = [u64p]
         L.bk_sort_forms.argtypes = [vp, u64p]
+        L.bk_debug_sort_info.argtypes = [vp, u64p]
         L.bk_debug_ahc.argtypes = [vp, vp, vp, C.c_uint32, C.c_double, vp, vp, C.POINTER(C.c_uint32)]
         L.bk_debug_points.argtypes = [vp, C.c_int, vp, vp, C.c_uint32, C.c_double, vp, vp, C.POINTER(C.c_uint32)]
         L.bk_debug_points_groups.argtypes = [vp, C.c_int, vp, vp, vp, C.c_uint32, C.c_double, vp, vp, vp, C.POINTER(C.c_uint32)]
@@ -849,6 +850,16 @@ class Context:
         out = (C.c_uint64 * 3)()
         self._check(self.L.bk_sort_forms(self.h, out))
         return tuple(int(v) for v in out)
+
+    SORT_INFO = ("FIN_MAX", "HEAP_BIG_MIN", "HEAP_RANKED_MAX", "HEAP_LARGE", "SVC_WIDE_MIN", "F2_HB", "F2_EXT", "HEAP_PAD", "SJ_MAX_WIDE", "SJ_MAX_NARROW",
+                 "cap32", "max_heap", "n_heap")
+
+    def debug_sort_info(self):
+        """The sizes at which the std::sort replay changes its code path in this build, cap32 of the task dispatch on this device,
+        and max_heap / n_heap of this context's last debug_std_sort (bk_debug_sort_info; 0xFFFFFFFF each: a job of the service)."""
+        out = (C.c_uint64 * len(self.SORT_INFO))()
+        self._check(self.L.bk_debug_sort_info(self.h, out))
+        return dict(zip(self.SORT_INFO, (int(v) for v in out)))
 
     def debug_ahc(self, x, y, w):
         x = np.ascontiguousarray(x, np.uint32)

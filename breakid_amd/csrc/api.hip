@@ -2573,6 +2573,18 @@ int bk_sort_forms(bk_ctx *ctx, uint64_t out[3])
   });
 }
 
+int bk_debug_sort_info(bk_ctx *ctx, uint64_t out[13])
+{
+  return guarded(ctx, [&] {
+    if (!out) throw bk_error(BK_ERR_ARG, "bk_debug_sort_info: null output");
+    static_assert(SORT_INFO_WORDS == 11, "bk_debug_sort_info: eleven words of the build, two of the last sort");
+    std_sort_info(out);
+    const SortEmuBufs &se = ctx->stage.cb().se;
+    out[11] = se.last_heap[0];
+    out[12] = se.last_heap[1];
+  });
+}
+
 int bk_debug_ahc(bk_ctx *ctx, const uint32_t *x, const uint32_t *y, uint32_t n, double w, uint32_t *idx_out, int32_t *cluster_out, uint32_t *n_out)
 {
   return guarded(ctx, [&] {

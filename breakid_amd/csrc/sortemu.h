@@ -51,6 +51,9 @@ struct SortEmuBufs
   bool tj_ready = false;  // the rings are initialised and consistent (a failed sort clears it)
   // sorts through these buffers by form: [0] jobs of the resident service, [1] task dispatches
   uint64_t sorts[2] = {0, 0};
+  // the job statistics of the last sort through these buffers (bk_debug_sort_info): [0] its longest heap segment, [1] the elements in
+  // its heap segments, as the task dispatch's look at its job read them; 0xFFFFFFFF = not read (a job of the resident service)
+  uint32_t last_heap[2] = {0, 0};
   SortEmuBufs() = default;
   SortEmuBufs(const SortEmuBufs &) = delete;
   SortEmuBufs &operator=(const SortEmuBufs &) = delete;
@@ -59,3 +62,9 @@ struct SortEmuBufs
 // key/idx: n elements, groups are the contiguous ranges goff[g]..goff[g+1]; gof[p] = group of position p.
 // On return every group is ordered exactly as std::sort(begin, end, [](a,b){return a.key < b.key;}) leaves it.
 void std_sort_groups(uint32_t *key, uint32_t *idx, const uint32_t *gof, const uint64_t *goff, uint32_t ng, uint64_t n, SortEmuBufs &b, hipStream_t st);
+
+// Test hook (bk_debug_sort_info): the constants of this build at which the replay changes its code path - FIN_MAX, HEAP_BIG_MIN,
+// HEAP_RANKED_MAX, HEAP_LARGE, SVC_WIDE_MIN, F2_HB, F2_EXT, HEAP_PAD, SJ_MAX_WIDE, SJ_MAX_NARROW - and out[10] = cap32 of the task
+// dispatch (the ranked heap entries that fit a wide workgroup's LDS, from the kernel's attributes on the current device).
+constexpr int SORT_INFO_WORDS = 11;
+void std_sort_info(uint64_t out[SORT_INFO_WORDS]);

@@ -1419,6 +1419,8 @@ static void std_sort_groups_tasks(uint32_t *key, uint32_t *idx, const uint32_t *
   SvcJob j = {};
   HIP_CHECK(hipMemcpyAsync(&j, P.jobs, sizeof j, hipMemcpyDeviceToHost, st));
   HIP_CHECK(hipStreamSynchronize(st));
+  b.last_heap[0] = j.max_heap;
+  b.last_heap[1] = j.n_heap;
   if (h[0] || j.remaining != 0u)
   {
     b.tj_ready = false;  // (tasks may be left in the rings: initialised again before the next sort)
@@ -1450,6 +1452,7 @@ void std_sort_groups(uint32_t *key, uint32_t *idx, const uint32_t *gof, const ui
   if (b.svc && b.svc->running)
   {
     ++b.sorts[0];
+    b.last_heap[0] = b.last_heap[1] = 0xFFFFFFFFu;  // (the service's job is not read back)
     std_sort_groups_svc(key, idx, gof, goff, ng, n, b, st);
     return;
   }
@@ -1497,6 +1500,12 @@ void std_sort_groups(uint32_t *key, uint32_t *idx, const uint32_t *gof, const ui
     ++call;
   }
   std_sort_groups_tasks(key, idx, gof, goff, ng, n, b, st, chk ? key0 : nullptr);
+}
+void std_sort_info(uint64_t out[SORT_INFO_WORDS])
+{
+  const uint64_t c[SORT_INFO_WORDS] = {FIN_MAX, HEAP_BIG_MIN, HEAP_RANKED_MAX, HEAP_LARGE, SVC_WIDE_MIN, F2_HB, F2_EXT, HEAP_PAD, SJ_MAX_WIDE, SJ_MAX_NARROW,
+                                       wide_lds_split(reinterpret_cast<const void *>(k_sort_job)).cap32};
+  std::copy(c, c + SORT_INFO_WORDS, out);
 }
 static void window_sorts(uint32_t *key, uint32_t *idx, const uint32_t *gof, uint32_t n, hipStream_t st)
 {

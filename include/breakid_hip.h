@@ -1278,6 +1278,14 @@ int bk_debug_prims_info(uint64_t out[4]);
  * that no longer exists; the three-word signature stays. */
 int bk_sort_forms(bk_ctx *ctx, uint64_t out[3]);
 
+/* Test hook: the sizes at which the std::sort replay changes its code path in this build, and what the last sort through
+ * bk_debug_std_sort met.  out[0..9] = FIN_MAX, HEAP_BIG_MIN, HEAP_RANKED_MAX, HEAP_LARGE, SVC_WIDE_MIN, F2_HB, F2_EXT, HEAP_PAD,
+ * SJ_MAX_WIDE, SJ_MAX_NARROW; out[10] = cap32, the ranked heap entries that fit a wide workgroup's LDS in the task dispatch (from
+ * the kernel's attributes on the context's device); out[11] = the longest heap segment and out[12] = the elements in heap
+ * segments of the context's last debug sort, as its task dispatch counted them (0xFFFFFFFF each when that sort ran as a job of
+ * the resident service, whose statistics are not read back; 0 before the first sort). */
+int bk_debug_sort_info(bk_ctx *ctx, uint64_t out[13]);
+
 /* Test hook: find_cluster_pairs_enspan_ahc (BreakID.cc:1304-1352) on one group of x-sorted points; returns the
  * surviving point indices in output order with their cluster numbers. */
 int bk_debug_ahc(bk_ctx *ctx, const uint32_t *x, const uint32_t *y, uint32_t n, double w, uint32_t *idx_out, int32_t *cluster_out, uint32_t *n_out);

@@ -278,23 +278,30 @@ struct SortStats
 };
 SortStats g_sort_stats;
 bool g_sort_probe = false;
-template <class It, class Cmp> void probe_loop(It first, It last, long depth, Cmp c)
+// heap(first, last) is told every segment that runs out of depth (ora_sort_stats counts them, ora_unit_sort_shape lists them)
+template <class It, class Cmp, class Heap> void probe_loop(It first, It last, long depth, Cmp c, Heap &&heap)
 {
   while (last - first > 16)
   {
     if (depth == 0)
     {
-      uint64_t m = (uint64_t) (last - first);
-      g_sort_stats.heap_segments++;
-      g_sort_stats.heap_elems += m;
-      if (m > g_sort_stats.max_heap) g_sort_stats.max_heap = m;
+      heap(first, last);
       return;
     }
     --depth;
     It cut = std::__unguarded_partition_pivot(first, last, __gnu_cxx::__ops::__iter_comp_iter(c));
-    probe_loop(cut, last, depth, c);
+    probe_loop(cut, last, depth, c, heap);
     last = cut;
   }
+}
+template <class It, class Cmp> void probe_loop(It first, It last, long depth, Cmp c)
+{
+  probe_loop(first, last, depth, c, [](It f, It l) {
+    uint64_t m = (uint64_t) (l - f);
+    g_sort_stats.heap_segments++;
+    g_sort_stats.heap_elems += m;
+    if (m > g_sort_stats.max_heap) g_sort_stats.max_heap = m;
+  });
 }
 template <class T, class Cmp> void ref_sort(std::vector<T> &v, Cmp c)
 {
@@ -1271,6 +1278,33 @@ int ora_unit_std_sort(const uint32_t *key, const uint64_t *group_off, uint32_t n
     for (size_t i = 0; i < v.size(); ++i) perm_out[group_off[g] + i] = v[i].id;
   }
   return 0;
+}
+
+// The heap segments of the same sorts: probe_loop (the library's own partition step on a copy of every group) lists every segment
+// that runs out of its depth budget, as (first, length) pairs of uint64 in absolute positions, in the order the loop meets them
+// (right sides first).  Returns their number; at most `cap` pairs are written.
+int ora_unit_sort_shape(const uint32_t *key, const uint64_t *group_off, uint32_t n_groups, uint64_t *out, uint32_t cap)
+{
+  struct KI { uint32_t key, id; };
+  uint32_t n_seg = 0;
+  for (uint32_t g = 0; g < n_groups; ++g)
+  {
+    std::vector<KI> v;
+    for (uint64_t p = group_off[g]; p < group_off[g + 1]; ++p) v.push_back(KI{key[p], (uint32_t) p});
+    if (v.size() <= 16) continue;
+    const uint64_t base = group_off[g];
+    const auto begin = v.begin();
+    probe_loop(v.begin(), v.end(), 2 * (long) std::__lg((long) v.size()), [](KI a, KI b) { return a.key < b.key; },
+               [&](std::vector<KI>::iterator f, std::vector<KI>::iterator l) {
+                 if (n_seg < cap)
+                 {
+                   out[2 * (size_t) n_seg] = base + (uint64_t) (f - begin);
+                   out[2 * (size_t) n_seg + 1] = (uint64_t) (l - f);
+                 }
+                 ++n_seg;
+               });
+  }
+  return (int) n_seg;
 }
 
 // find_sa_reads on one region (BreakID.cc:868-1037): tuples after the region verdict, as bk_split rows

@@ -45,6 +45,7 @@ def lib():
                                       C.c_void_p, C.POINTER(C.c_int)]
         L.ora_unit_vote.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p]
         L.ora_unit_std_sort.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+        L.ora_unit_sort_shape.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]
         L.ora_unit_region.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32]
         L.ora_unit_depth.restype = C.c_uint32
         L.ora_unit_depth.argtypes = [C.c_void_p, C.c_int, C.c_uint64]
@@ -184,6 +185,19 @@ def unit_std_sort(key, group_off):
     perm = np.zeros(len(key), np.uint32)
     L.ora_unit_std_sort(key.ctypes.data, group_off.ctypes.data, len(group_off) - 1, perm.ctypes.data)
     return perm
+
+
+def unit_sort_shape(key, group_off):
+    """The heap segments of unit_std_sort's sorts, by the library's own partition step on a copy of every group: a list of
+    (first, length) in absolute positions, in the order the introsort loop meets them (right sides first)."""
+    L = lib()
+    key = np.ascontiguousarray(key, np.uint32)
+    group_off = np.ascontiguousarray(group_off, np.uint64)
+    cap = len(key) // 17 + 1  # (heap segments are disjoint and hold more than 16 elements)
+    out = np.zeros((cap, 2), np.uint64)
+    n = L.ora_unit_sort_shape(key.ctypes.data, group_off.ctypes.data, len(group_off) - 1, out.ctypes.data, cap)
+    assert 0 <= n <= cap, n
+    return [(int(f), int(m)) for f, m in out[:n]]
 
 
 def sort_probe(on=True):
