@@ -101,6 +101,12 @@ assert CIGAR_GAP.itemsize == 64
 GAP_DEL, GAP_INS = 0, 1  # BK_GAP_DEL, BK_GAP_INS
 GAP_MAX_TOL = 100  # BK_GAP_MAX_TOL
 GAP_MAX_LEN = 1000000  # BK_GAP_MAX_LEN
+CLIP_LOCUS = np.dtype([("tid", "<i4"), ("pos", "<u4"), ("dir", "<u4"), ("flags", "<u4"), ("n_reads", "<u4"), ("n_rows", "<u4"), ("n_exact", "<u4"), ("top_reads", "<u4"),
+                       ("lo_pos", "<u4"), ("hi_pos", "<u4"), ("n_fwd", "<u4"), ("n_rev", "<u4"), ("max_clip", "<u4"), ("n_orphan", "<u4"), ("clip_sum", "<u8"), ("mapq_sum", "<u8"),
+                       ("n_improper", "<u4"), ("claim", "<u4"), ("mate", "<u4"), ("mate_pos", "<u4"), ("mate_reads", "<u4"), ("mate_off", "<i4")])  # struct bk_clip_locus; pos 1-based
+assert CLIP_LOCUS.itemsize == 96
+CLIPLOCI_MAX_TOL = 100  # BK_CLIPLOCI_MAX_TOL
+CLIPLOCI_MAX_PAIR = 100000  # BK_CLIPLOCI_MAX_PAIR
 STRAND_NONE, STRAND_LEFT, STRAND_RIGHT = 0, 1, 2  # BK_STRAND_*
 # the columns of a bk_txmodel, in the struct's order (ex_off has n_tx + 1 entries, ex_start / ex_end n_parts)
 TXMODEL_COLS = [("tid", np.int32), ("tx_start", np.uint32), ("tx_end", np.uint32), ("strand", np.uint8), ("ex_off", np.uint32), ("ex_start", np.uint32), ("ex_end", np.uint32)]

@@ -35,7 +35,7 @@ def build(verbose=False):
 
 EXPORTS = ["bk_init", "bk_prepare_process", "bk_free", "bk_last_error", "bk_set_stream", "bk_sync", "bk_get_stream", "bk_upload_records", "bk_records", "bk_exclude_regions", "bk_isize_stats",
            "bk_discordant_pairs", "bk_mask_and_cluster", "bk_split_evidence", "bk_cluster_summary",
-           "bk_split_breakpoints", "bk_normal_support", "bk_ref_support", "bk_genotype_call", "bk_clip_support", "bk_clip_reads", "bk_base_depth", "bk_clip_rescue", "bk_junctions", "bk_junction_sides", "bk_vcf_breakend_alt", "bk_evidence", "bk_unique_support", "bk_clip_consensus", "bk_junction_fit", "bk_locus_similarity", "bk_site_complexity", "bk_window_coverage", "bk_window_context", "bk_call_windows", "bk_fusion_frame", "bk_link_calls", "bk_locus_partners", "bk_call_partner_sites", "bk_fragment_sizes", "bk_fragment_bounds", "bk_known_calls", "bk_split_junctions", "bk_split_junction_counts", "bk_debug_split_junctions", "bk_cigar_gaps", "bk_cigar_gap_counts", "bk_run", "bk_fetch", "bk_timing", "bk_timing_enable", "bk_timing_touched", "bk_group_stats", "bk_qname_hash", "bk_qname_check",
+           "bk_split_breakpoints", "bk_normal_support", "bk_ref_support", "bk_genotype_call", "bk_clip_support", "bk_clip_reads", "bk_base_depth", "bk_clip_rescue", "bk_junctions", "bk_junction_sides", "bk_vcf_breakend_alt", "bk_evidence", "bk_unique_support", "bk_clip_consensus", "bk_junction_fit", "bk_locus_similarity", "bk_site_complexity", "bk_window_coverage", "bk_window_context", "bk_call_windows", "bk_fusion_frame", "bk_link_calls", "bk_locus_partners", "bk_call_partner_sites", "bk_fragment_sizes", "bk_fragment_bounds", "bk_known_calls", "bk_split_junctions", "bk_split_junction_counts", "bk_debug_split_junctions", "bk_cigar_gaps", "bk_cigar_gap_counts", "bk_clip_loci", "bk_clip_locus_counts", "bk_run", "bk_fetch", "bk_timing", "bk_timing_enable", "bk_timing_touched", "bk_group_stats", "bk_qname_hash", "bk_qname_check",
            "bk_bam_open", "bk_bam_header", "bk_bam_decode", "bk_bam_close", "bk_bam_extract", "bk_bam_names_free", "bk_bam_reads", "bk_reads_free", "bk_bam_decode_device", "bk_bam_decode_device_part", "bk_bam_decode_device_ctx", "bk_bam_dev_free", "bk_feed_release_caches", "bk_debug_bgzf_inflate", "bk_debug_std_sort", "bk_debug_scan", "bk_debug_radix_sort", "bk_debug_prims_info", "bk_sort_forms", "bk_debug_sort_info", "bk_debug_ahc", "bk_debug_points", "bk_debug_points_groups", "bk_debug_cluster_info", "bk_debug_stream_info", "bk_debug_stream_blocks", "bk_debug_cigar", "bk_debug_vote", "bk_debug_region", "bk_shard_begin", "bk_shard_get_stats", "bk_shard_set_stats",
            "bk_shard_sd_local", "bk_shard_sd_finish", "bk_shard_buffer", "bk_shard_set_buffer", "bk_shard_group_sizes",
            "bk_shard_own_groups", "bk_shard_route_candidates", "bk_shard_group_keys", "bk_shard_route_pairs", "bk_shard_group_pairs", "bk_shard_bp_cov", "bk_shard_bp_vote", "bk_shard_bp_vote_slice", "bk_shard_bp_set_voted", "bk_shard_bp_depth", "bk_shard_bp_finish"]
@@ -102,6 +102,8 @@ def lib():
         L.bk_debug_split_junctions.argtypes = [vp, C.c_int, C.c_uint32, C.c_uint32, vp, C.c_uint64, C.POINTER(vp), u64p]
         L.bk_cigar_gaps.argtypes = [vp, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(vp), u64p]
         L.bk_cigar_gap_counts.argtypes = [vp, u64p]
+        L.bk_clip_loci.argtypes = [vp, vp, C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(vp), u64p]
+        L.bk_clip_locus_counts.argtypes = [vp, u64p]
         L.bk_fetch.argtypes = [vp, C.c_int, C.POINTER(vp), u64p, C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(C.c_uint32)]
         L.bk_timing.argtypes = [vp, C.POINTER(C.POINTER(C.c_char_p)), C.POINTER(C.POINTER(C.c_float)),
                                 C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(C.c_int)]
@@ -804,6 +806,24 @@ class Context:
         out = (C.c_uint64 * 8)()
         self._check(self.L.bk_cigar_gap_counts(self.h, out))
         return dict(zip(("records", "eligible", "events", "beyond", "exact", "loci", "calls", "written"), (int(v) for v in out)))
+
+    def clip_loci(self, calls=None, mapq_min=20, min_clip=10, tol=2, pair_dist=50, min_reads=3):
+        """Soft-clip pile-ups of the context's record table (bk_clip_loci); no stage need have run.  calls: None, or the Context (this one
+        or another) whose voted rows may claim a locus.  Returns the abi.CLIP_LOCUS rows of the loci with at least min_reads distinct
+        reads."""
+        out, n = C.c_void_p(), C.c_uint64()
+        self._check(self.L.bk_clip_loci(self.h, calls.h if calls is not None else None, mapq_min, min_clip, tol, pair_dist, min_reads, C.byref(out), C.byref(n)))
+        if not n.value:
+            return np.zeros(0, abi.CLIP_LOCUS)
+        buf = (C.c_char * (n.value * abi.CLIP_LOCUS.itemsize)).from_address(out.value)
+        return np.frombuffer(buf, dtype=abi.CLIP_LOCUS, count=n.value).copy()
+
+    def clip_locus_counts(self):
+        """What the last clip_loci() counted (bk_clip_locus_counts): records, eligible records, events, events beyond a contig's end,
+        exact sites, loci, loci with a mutual partner, returned rows."""
+        out = (C.c_uint64 * 8)()
+        self._check(self.L.bk_clip_locus_counts(self.h, out))
+        return dict(zip(("records", "eligible", "events", "beyond", "exact", "loci", "mutual", "written"), (int(v) for v in out)))
 
     def run(self, qual=20, fast=True):
         w, n = C.c_double(), C.c_uint64()

@@ -30,6 +30,7 @@
 #include "known.h"
 #include "sjcall.h"
 #include "gaps.h"
+#include "cliploci.h"
 #include "exclude.h"
 #include "ahc.h"
 #include "lanes.h"
@@ -202,6 +203,10 @@ struct bk_ctx
   GapBufs gpb;
   GapStats gap_stats;
   std::vector<struct bk_cigar_gap> f_gaps;
+  // soft-clip loci (bk_clip_loci: this context holds the records)
+  ClipLociBufs cllb;
+  ClipLociStats cll_stats;
+  std::vector<struct bk_clip_locus> f_cll;
 
   // test hooks of the primitives (bk_debug_scan, bk_debug_radix_sort): buffers that live as long as the context, as a stage's do
   prims::RadixBufs dbg_radix;
@@ -2043,6 +2048,85 @@ int bk_cigar_gap_counts(bk_ctx *records, uint64_t out[8])
     if (!out) throw bk_error(BK_ERR_ARG, "bk_cigar_gap_counts: null out");
     const GapStats &t = records->gap_stats;
     out[0] = t.n; out[1] = t.eligible; out[2] = t.events; out[3] = t.beyond; out[4] = t.exact; out[5] = t.loci; out[6] = t.calls; out[7] = t.written;
+  });
+}
+
+// Soft-clip pile-ups of the context's record table (include/breakid_hip.h, cliploci.hip)
+int bk_clip_loci(bk_ctx *records, bk_ctx *calls, int mapq_min, int min_clip, uint32_t tol, uint32_t pair_dist, uint32_t min_reads, const struct bk_clip_locus **out,
+                 uint64_t *count)
+{
+  return guarded(records, [&] {
+    if (!out || !count) throw bk_error(BK_ERR_ARG, "bk_clip_loci: null output");
+    if (records->shard || (calls && calls->shard)) throw bk_error(BK_ERR_ARG, "bk_clip_loci: sharded contexts (bk_shard_*) are not supported");
+    if (!records->have_records) throw bk_error(BK_ERR_ARG, "bk_clip_loci: the context holds no record table");
+    if (mapq_min < 0) throw bk_error(BK_ERR_ARG, "bk_clip_loci: mapq_min below 0");
+    if (min_clip < 1) throw bk_error(BK_ERR_ARG, "bk_clip_loci: min_clip must be at least 1");
+    if (tol > BK_CLIPLOCI_MAX_TOL) throw bk_error(BK_ERR_ARG, "bk_clip_loci: tol above " + std::to_string(BK_CLIPLOCI_MAX_TOL));
+    if (pair_dist > BK_CLIPLOCI_MAX_PAIR) throw bk_error(BK_ERR_ARG, "bk_clip_loci: pair_dist above " + std::to_string(BK_CLIPLOCI_MAX_PAIR));
+    if (min_reads == 0) throw bk_error(BK_ERR_ARG, "bk_clip_loci: min_reads must be at least 1");
+    if (calls)
+    {
+      if (!calls->bp_done) throw bk_error(BK_ERR_ARG, "bk_clip_loci: call bk_split_breakpoints on the calls context first");
+      if (calls != records) require_same_reference("bk_clip_loci", "calls", calls, "records", records);
+      if (calls->n_clusters > 0x3FFFFFFFull) throw bk_error(BK_ERR_LIMIT, "bk_clip_loci: too many clusters");
+    }
+    const bk_soa &t = records->rec;
+    if (t.n && (!t.tid || !t.pos || !t.flag || !t.mapq || !t.cigar_off || !t.aux_off || (!t.side && !t.qhash)))
+      throw bk_error(BK_ERR_ARG, "bk_clip_loci: the record table lacks a column");
+    if (t.n_cigar_words && !t.cigar) throw bk_error(BK_ERR_ARG, "bk_clip_loci: the record table lacks a column");
+    ClipLociInput in;
+    in.rec = rec_view(records);
+    in.n_cigar_words = t.n_cigar_words;
+    in.side = t.side;
+    in.qhash = t.qhash;
+    in.tprefix = records->d_tprefix.get<uint32_t>();
+    in.nt = records->nt;
+    for (const uint32_t l : records->tlen) in.max_len = std::max(in.max_len, l);
+    const ClipLociParams p{mapq_min, min_clip, tol, pair_dist, min_reads};
+    if (calls && calls != records) HIP_CHECK(hipStreamSynchronize(calls->st));  // its stages ran on its own stream
+    struct bk_clip_locus *d_rows = nullptr;
+    records->cll_stats = ClipLociStats{};
+    ClipLociStats &s = records->cll_stats;
+    {
+      // (the two scopes inside push timers of their own, so the whole one ends by its index, not at timers.back())
+      struct Whole
+      {
+        bk_ctx *c;
+        size_t at;
+        ~Whole()
+        {
+          if (c->timing && at < c->timers.size()) (void) hipEventRecord(c->timers[at].b, c->st);
+        }
+      } whole{records, records->timers.size()};
+      records->tick("clip_loci", 0, true, 0);
+      {
+        Scope sc(records, "clip_loci_records");
+        cliploci_events(in, p, records->cllb, records->st, &s);
+      }
+      if (records->timing && !records->timers.empty()) records->timers.back().bytes = records->timers.back().touched = s.touched_records();
+      {
+        Scope sc(records, "clip_loci_calls");
+        cliploci_calls(p, calls ? calls->clusters_ptr() : nullptr, calls ? calls->n_clusters : 0, records->cllb, records->st, &d_rows, &s);
+      }
+      if (records->timing && !records->timers.empty()) records->timers.back().bytes = records->timers.back().touched = s.touched_calls();
+      if (records->timing && whole.at < records->timers.size()) records->timers[whole.at].bytes = records->timers[whole.at].touched = s.touched_records() + s.touched_calls();
+    }
+    if (bk_debug("cliploci"))
+      fprintf(stderr, "bk_clip_loci: %llu records, %llu eligible, %llu events, %llu beyond, %llu exact, %llu loci, %llu mutual, %llu returned\n", (unsigned long long) s.n,
+              (unsigned long long) s.eligible, (unsigned long long) (s.events + s.beyond), (unsigned long long) s.beyond, (unsigned long long) s.exact,
+              (unsigned long long) s.loci, (unsigned long long) s.mutual, (unsigned long long) s.written);
+    rows_to_host(records, d_rows, s.written, records->f_cll);
+    *out = records->f_cll.data();
+    *count = s.written;
+  });
+}
+
+int bk_clip_locus_counts(bk_ctx *records, uint64_t out[8])
+{
+  return guarded(records, [&] {
+    if (!out) throw bk_error(BK_ERR_ARG, "bk_clip_locus_counts: null out");
+    const ClipLociStats &t = records->cll_stats;
+    out[0] = t.n; out[1] = t.eligible; out[2] = t.events + t.beyond; out[3] = t.beyond; out[4] = t.exact; out[5] = t.loci; out[6] = t.mutual; out[7] = t.written;
   });
 }
 

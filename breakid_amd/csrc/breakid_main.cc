@@ -1808,6 +1808,46 @@ static void cigar_gap_calls(const Options &o, const Sample &tumor, const vector<
             << " calls, " << rows.size() << " written" << std::endl;
 }
 
+// ---- -cliploci: soft-clip pile-ups over the whole table ---------------------------------------------------------------------------------
+// One call of bk_clip_loci on the sample's own table with the run's voted rows as the claiming calls (-q is its mapq_min, -minclip its
+// min_clip; -x applies by itself, because the table holds the kept records); the loci that no voted row claims get the depth at their
+// position (one call of bk_base_depth) and the gene there.  It runs behind every other stage and reads what they left: no other file changes.
+static void clip_locus_calls(const Options &o, const Sample &tumor, const vector<Txpt> &txpts)
+{
+  const struct bk_clip_locus *loci = nullptr;
+  uint64_t n = 0, counts[8] = {};
+  int rc = bk_clip_loci(tumor.ctx, tumor.ctx, o.qual, (int) o.min_clip, (uint32_t) o.locitol, (uint32_t) o.locipair, (uint32_t) o.locisupport, &loci, &n);
+  if (rc == BK_OK) rc = bk_clip_locus_counts(tumor.ctx, counts);
+  if (rc != BK_OK) die(tumor, rc);
+  vector<ClipLocusRow> rows;
+  vector<int32_t> q_tid;
+  vector<uint32_t> q_pos;
+  for (uint64_t i = 0; i < n; ++i)
+  {
+    if (loci[i].claim != 0xFFFFFFFFu) continue;
+    ClipLocusRow r;
+    r.l = loci[i];
+    r.index = i;
+    r.depth = 0;
+    rows.push_back(r);
+    q_tid.push_back(loci[i].tid);
+    q_pos.push_back(loci[i].pos);
+  }
+  const uint32_t *depth = nullptr;
+  if (!rows.empty() && (rc = bk_base_depth(tumor.ctx, q_tid.data(), q_pos.data(), q_tid.size(), &depth)) != BK_OK) die(tumor, rc);
+  for (size_t k = 0; k < rows.size(); ++k)
+  {
+    ClipLocusRow &r = rows[k];
+    string exon, strand;
+    r.depth = depth[k];
+    r.chr = tumor.names[r.l.tid];
+    annotate_side(txpts, r.chr, (long) r.l.pos, r.gene, exon, strand);
+  }
+  write_cliploci_files(o, rows, loci, n);
+  std::cout << "cliploci: " << counts[1] << " records eligible, " << counts[2] << " events, " << counts[3] << " beyond a contig's end, " << counts[4] << " exact, " << counts[5]
+            << " loci, " << counts[6] << " with a mutual partner, " << n - rows.size() << " claimed by a voted call, " << rows.size() << " written" << std::endl;
+}
+
 // write_enspan_params (:1170-1182); an option that changes what is called adds its line behind the reference's
 static void write_params(const Options &o, double w)
 {
@@ -1847,6 +1887,9 @@ static void write_params(const Options &o, double w)
   if (o.gaps) p << "gap_anchor\t" << o.gapanchor << std::endl;
   if (o.gaps) p << "gap_tol\t" << o.gaptol << std::endl;
   if (o.gaps) p << "gap_min_support\t" << o.gapsupport << std::endl;
+  if (o.cliploci) p << "cliploci_tol\t" << o.locitol << std::endl;
+  if (o.cliploci) p << "cliploci_pair\t" << o.locipair << std::endl;
+  if (o.cliploci) p << "cliploci_min_support\t" << o.locisupport << std::endl;
 }
 
 // BreakID.cc:175-191.  scan_pairs_count and after_cluster_count are never updated by the reference (always 0);
@@ -1948,6 +1991,7 @@ int main(int argc, char *argv[])
   }
   if (o.junctions) split_junction_calls(o, tumor, txpts);
   if (o.gaps) cigar_gap_calls(o, tumor, txpts);
+  if (o.cliploci) clip_locus_calls(o, tumor, txpts);
   write_params(o, run.w);
   const clock_t end = clock();
   std::cout << "the fusion process of file " << o.inp_file << "  costs time: " << (end - start) / double(CLOCKS_PER_SEC) << " seconds" << std::endl;

@@ -59,6 +59,9 @@ int bk_split_junction_counts(bk_ctx *ctx, uint64_t out[6]) __attribute__((weak))
 // -gaps (deletions and insertions from CIGAR gaps; bk_base_depth is listed with -clip)
 int bk_cigar_gaps(bk_ctx *records, int mapq_min, uint32_t min_len, uint32_t anchor, uint32_t tol, uint32_t min_reads, const struct bk_cigar_gap **out, uint64_t *count) __attribute__((weak));
 int bk_cigar_gap_counts(bk_ctx *records, uint64_t out[8]) __attribute__((weak));
+// -cliploci (soft-clip pile-ups over the whole table; bk_base_depth is listed with -clip)
+int bk_clip_loci(bk_ctx *records, bk_ctx *calls, int mapq_min, int min_clip, uint32_t tol, uint32_t pair_dist, uint32_t min_reads, const struct bk_clip_locus **out, uint64_t *count) __attribute__((weak));
+int bk_clip_locus_counts(bk_ctx *records, uint64_t out[8]) __attribute__((weak));
 // -complexity
 int bk_site_complexity(bk_ctx *ctx, const bk_refseq *ref, const struct bk_ref_site *sites, uint64_t n, uint32_t flank, uint32_t max_period, const struct bk_site_cplx **out) __attribute__((weak));
 // -dedup
@@ -128,15 +131,19 @@ static const char *HELP =
      \t -mingap    \t shortest D or I operation that counts, 1 to 1000000 (with -gaps)  [20]\n \
      \t -gapanchor \t matched bases an alignment needs on either side of the operation, 1 to 2147483647 (with -gaps)  [10]\n \
      \t -gaptol    \t bases up to which two gaps differ in start, and then in length, and are one call, 0 to 100 (with -gaps)  [2]\n \
-     \t -gapsupport \t distinct reads a gap needs, 1 to 1000000 (with -gaps)  [3]\n ";
+     \t -gapsupport \t distinct reads a gap needs, 1 to 1000000 (with -gaps)  [3]\n \
+     \t -cliploci  \t also call the places where soft-clipped reads without an SA tag pile up, with or without discordant pairs: mobile-element and viral insertion sites (*_cliploci.txt; *_cliploci.bedpe with -bedpe; -minclip and -q apply)  \n \
+     \t -locitol   \t bases up to which two clip positions of one side are one locus, 0 to 100 (with -cliploci)  [2]\n \
+     \t -locipair  \t bases up to which a left-clipped and a right-clipped locus may lie from a blunt junction and still face each other, 0 to 100000 (with -cliploci)  [50]\n \
+     \t -locisupport \t distinct reads a locus needs, 1 to 1000000 (with -cliploci)  [3]\n ";
 
 struct Options
 {
   std::string inp_file, out_file, nib_dir, normal_file, exclude_file, known_file, build = "hg19";
   int qual = 20, device = 0, n_gpus = 0, transport = BK_TRANSPORT_AUTO;  // -gpus N: one sample over N GPUs (include/breakid_multi.h)
   bool fast = false, all = false;                                        // -all: no gene-pair and repeat filter (the _fusion_all files)
-  bool genotype = false, vcf = false, evidence = false, clip = false, dedup = false, consensus = false, homology = false, similar = false, coverage = false, frame = false, link = false, partners = false, fragsize = false, bedpe = false, context = false, junctions = false, complexity = false, gaps = false;
-  bool anchor_given = false, minclip_given = false, clipsupport_given = false, conslen_given = false, homshift_given = false, homins_given = false, simflank_given = false, covflank_given = false, linkdist_given = false, knownslop_given = false, ctxflank_given = false, jsupport_given = false, jtol_given = false, cplxflank_given = false, cplxperiod_given = false, mingap_given = false, gapanchor_given = false, gaptol_given = false, gapsupport_given = false;
+  bool genotype = false, vcf = false, evidence = false, clip = false, dedup = false, consensus = false, homology = false, similar = false, coverage = false, frame = false, link = false, partners = false, fragsize = false, bedpe = false, context = false, junctions = false, complexity = false, gaps = false, cliploci = false;
+  bool anchor_given = false, minclip_given = false, clipsupport_given = false, conslen_given = false, homshift_given = false, homins_given = false, simflank_given = false, covflank_given = false, linkdist_given = false, knownslop_given = false, ctxflank_given = false, jsupport_given = false, jtol_given = false, cplxflank_given = false, cplxperiod_given = false, mingap_given = false, gapanchor_given = false, gaptol_given = false, gapsupport_given = false, locitol_given = false, locipair_given = false, locisupport_given = false;
   long anchor = 10;                      // -anchor: bases a reference read must cover on either side of the breakpoint base
   long min_clip = 10, clip_support = 3;  // -minclip: shortest clip that counts; -clipsupport: reads at one position a rescued side needs
   long conslen = 64;                     // -conslen: longest junction sequence per side
@@ -149,6 +156,7 @@ struct Options
   long jsupport = 3, jtol = 2;           // -jsupport, -jtol: min_reads and tol of bk_split_junctions
   long cplxflank = 32, cplxperiod = 6;   // -cplxflank, -cplxperiod: flank and max_period of bk_site_complexity
   long mingap = 20, gapanchor = 10, gaptol = 2, gapsupport = 3;  // -mingap, -gapanchor, -gaptol, -gapsupport: min_len, anchor, tol and min_reads of bk_cigar_gaps
+  long locitol = 2, locipair = 50, locisupport = 3;  // -locitol, -locipair, -locisupport: tol, pair_dist and min_reads of bk_clip_loci
   bool multi() const { return n_gpus >= 1; }  // the sharded run
   bool known() const { return !known_file.empty(); }
   bool with_normal() const { return !normal_file.empty(); }
@@ -198,6 +206,7 @@ static void check_options(const Options &o)
   const Feature junctions{"-junctions", o.junctions, false, bk_split_junctions && bk_split_junction_counts && bk_base_depth};
   const Feature complexity{"-complexity", o.complexity, false, bk_site_complexity != nullptr};
   const Feature gaps{"-gaps", o.gaps, false, bk_cigar_gaps && bk_cigar_gap_counts && bk_base_depth};
+  const Feature cliploci{"-cliploci", o.cliploci, false, bk_clip_loci && bk_clip_locus_counts && bk_base_depth};
   const Feature consensus{"-consensus", o.consensus, false, bk_clip_consensus && bk_clip_reads && bk_evidence && bk_junctions && bk_junction_sides};
   const Feature clip{"-clip", o.clip, false, bk_clip_support && bk_clip_reads && bk_base_depth && bk_clip_rescue && bk_junctions && bk_junction_sides};
   const Feature exclude{"-x", o.exclude(), true, bk_exclude_regions && bk_multi_run_ex && bk_multi_run_bam_ex && bk_multi_excluded};
@@ -221,7 +230,7 @@ static void check_options(const Options &o)
       rule(o.conslen_given && !o.consensus, "-conslen needs -consensus."),
       gpus(consensus), library(consensus), rule(o.consensus && !in_range(o.conslen, 1, 256), "-conslen must be a number from 1 to 256."),
       rule(o.consensus && !in_range(o.min_clip, 1, int_max), "-minclip must be a number from 1 to 2147483647."),
-      rule((o.minclip_given && !o.clip && !o.consensus) || (o.clipsupport_given && !o.clip), "-minclip and -clipsupport need -clip."),
+      rule((o.minclip_given && !o.clip && !o.consensus && !o.cliploci) || (o.clipsupport_given && !o.clip), "-minclip and -clipsupport need -clip."),
       library(clip), gpus(clip),  // (the one option that looks for the library first)
       rule(o.clip && !(in_range(o.min_clip, 1, int_max) && in_range(o.clip_support, 1, int_max)), "-minclip and -clipsupport must be numbers from 1 to 2147483647."),
       gpus(exclude), library(exclude), {Refusal::OPEN, exclude.set && !opens(o.exclude_file), "exclude file: " + o.exclude_file},
@@ -253,6 +262,11 @@ static void check_options(const Options &o)
       rule(o.gaps && !in_range(o.gapanchor, 1, int_max), "-gapanchor must be a number from 1 to 2147483647."),
       rule(o.gaps && !in_range(o.gaptol, 0, 100), "-gaptol must be a number from 0 to 100."),
       rule(o.gaps && !in_range(o.gapsupport, 1, 1000000), "-gapsupport must be a number from 1 to 1000000."), library(gaps),
+      rule((o.locitol_given || o.locipair_given || o.locisupport_given) && !o.cliploci, "-locitol, -locipair and -locisupport need -cliploci."), gpus(cliploci),
+      rule(o.cliploci && !in_range(o.min_clip, 1, int_max), "-minclip must be a number from 1 to 2147483647."),
+      rule(o.cliploci && !in_range(o.locitol, 0, 100), "-locitol must be a number from 0 to 100."),
+      rule(o.cliploci && !in_range(o.locipair, 0, 100000), "-locipair must be a number from 0 to 100000."),
+      rule(o.cliploci && !in_range(o.locisupport, 1, 1000000), "-locisupport must be a number from 1 to 1000000."), library(cliploci),
   };
   for (const Refusal &r : refusals)
   {
@@ -283,6 +297,7 @@ static Options parse_options(int argc, char *argv[])
                                      {"junctions", 0, 0, 40}, {"jsupport", 1, 0, 41}, {"jtol", 1, 0, 42},
                                      {"complexity", 0, 0, 43}, {"cplxflank", 1, 0, 44}, {"cplxperiod", 1, 0, 45},
                                      {"gaps", 0, 0, 46}, {"mingap", 1, 0, 47}, {"gapanchor", 1, 0, 48}, {"gaptol", 1, 0, 49}, {"gapsupport", 1, 0, 50},
+                                     {"cliploci", 0, 0, 51}, {"locitol", 1, 0, 52}, {"locipair", 1, 0, 53}, {"locisupport", 1, 0, 54},
                                      {"f", 0, 0, 5},  // (-f used to complete to -fast alone; it still means it beside -frame)
                                      {0, 0, 0, 0}};
   Options o;
@@ -347,6 +362,10 @@ static Options parse_options(int argc, char *argv[])
     case 48: number(o.gapanchor, o.gapanchor_given); break;
     case 49: number(o.gaptol, o.gaptol_given); break;
     case 50: number(o.gapsupport, o.gapsupport_given); break;
+    case 51: o.cliploci = true; break;
+    case 52: number(o.locitol, o.locitol_given); break;
+    case 53: number(o.locipair, o.locipair_given); break;
+    case 54: number(o.locisupport, o.locisupport_given); break;
     default: std::cerr << "Error: cannot parse arguments.\n"; exit(1);
     }
   }

@@ -826,6 +826,56 @@ static void write_gap_files(const Options &o, const vector<GapRow> &rows)
   }
 }
 
+// -cliploci: <prefix>_cliploci.txt, the loci of bk_clip_loci that no voted row claims (a claimed one is a row of the fusion files
+// already), in the order of the call's table and named by their row in it; a mate that is not returned or is claimed prints as ".".
+// With -bedpe <prefix>_cliploci.bedpe in the layout of write_gap_files: one line per mutual pair whose two rows are both written, in the
+// order of its LEFT row; score = the reads of both rows, then cl<left row>, insertion_site, 0 and the reads again.  Nothing is filtered
+// beyond -locisupport.
+struct ClipLocusRow
+{
+  struct bk_clip_locus l;
+  uint64_t index;  // in the table bk_clip_loci returned
+  uint32_t depth;
+  string chr, gene;
+};
+static const char *CLIPLOCI_COLUMNS =
+    "Locus\tChr\tPos\tSide\tReads\tRows\tExact\tTopReads\tFwd\tRev\tMeanMQ\tSpan\tMaxClip\tMeanClip\tOrphans\tImproper\tMate\tMatePos\tMateReads\tMateOff\tMutual\tDepth\tGene";
+// all: the returned table (n rows), in which a row's mate is looked up
+static void write_cliploci_files(const Options &o, const vector<ClipLocusRow> &rows, const struct bk_clip_locus *all, uint64_t n)
+{
+  const size_t slash = o.out_file.find_last_of('/');
+  const string sample = slash == string::npos ? o.out_file : o.out_file.substr(slash + 1);
+  std::ofstream table((o.out_file + "_cliploci.txt").c_str()), bedpe;
+  if (o.bedpe) bedpe.open((o.out_file + "_cliploci.bedpe").c_str());
+  table << CLIPLOCI_COLUMNS << "\n";
+  char mq[32], mc[32];
+  for (const ClipLocusRow &r : rows)
+  {
+    const struct bk_clip_locus &l = r.l;
+    const bool facing = l.flags & 1u, mate_written = facing && l.mate < n && all[l.mate].claim == 0xFFFFFFFFu;
+    snprintf(mq, sizeof mq, "%.1f", (double) l.mapq_sum / (double) l.n_rows);  // (a locus has at least one row)
+    snprintf(mc, sizeof mc, "%.1f", (double) l.clip_sum / (double) l.n_rows);
+    table << "cl" << r.index << "\t" << r.chr << "\t" << l.pos << "\t" << (l.dir ? "R" : "L") << "\t" << l.n_reads << "\t" << l.n_rows << "\t" << l.n_exact << "\t" << l.top_reads << "\t"
+          << l.n_fwd << "\t" << l.n_rev << "\t" << mq << "\t" << l.lo_pos << "-" << l.hi_pos << "\t" << l.max_clip << "\t" << mc << "\t" << l.n_orphan << "\t" << l.n_improper << "\t";
+    if (mate_written)
+      table << "cl" << l.mate;
+    else
+      table << ".";
+    if (facing)
+      table << "\t" << l.mate_pos << "\t" << l.mate_reads << "\t" << l.mate_off;
+    else
+      table << "\t.\t.\t.";
+    table << "\t" << ((l.flags & 2u) ? 1 : 0) << "\t" << r.depth << "\t" << r.gene << "\n";
+    if (bedpe.is_open() && l.dir == BK_CLIP_LEFT && (l.flags & 2u) && mate_written)
+    {
+      const struct bk_clip_locus &m = all[l.mate];
+      const uint64_t reads = (uint64_t) l.n_reads + m.n_reads;
+      bedpe << r.chr << "\t" << (long long) l.pos - 1 << "\t" << l.pos << "\t" << r.chr << "\t" << (long long) m.pos - 1 << "\t" << m.pos << "\t" << (sample.empty() ? "." : sample) << "\t"
+            << reads << "\t+\t-\tcl" << r.index << "\tinsertion_site\t0\t" << reads << "\n";
+    }
+  }
+}
+
 // -clip: <prefix>_fusion_rescued.txt, a table with the clip columns, and with -normal <prefix>_fusion_rescued_normal.txt: the same rows
 // with the normal's evidence at the rescued peaks behind them
 static void write_rescued_tables(const Options &o, const Rescued &rescued, const CallTables &t)

@@ -1180,6 +1180,107 @@ int bk_cigar_gaps(bk_ctx *records, int mapq_min, uint32_t min_len, uint32_t anch
  * end, [4] exact events, [5] loci, [6] calls before min_reads, [7] returned rows.  BK_ERR_ARG for a null argument. */
 int bk_cigar_gap_counts(bk_ctx *records, uint64_t out[8]);
 
+/* ---- soft-clip loci: pile-ups of clipped reads over the whole table ------------------------------------------------------------------
+ * bk_clip_support counts clips inside the windows of the clusters and bk_clip_reads at sites the caller knows.  A breakpoint whose reads
+ * are clipped without an SA tag and whose mates are unmapped or scattered (a mobile-element insertion, a viral integration site, novel
+ * sequence) forms no cluster and is seen by neither.  This call groups the clip events of the whole table.  All arithmetic is integer.
+ *   events      Which records are eligible and which events (tid, p, dir) a record has is exactly what bk_clip_support (above) defines,
+ *               with the same mapq_min and min_clip; nothing of it is restated here.
+ *   beyond      An event with p above the contig's length, or on a tid >= n_targets, is dropped and counted as beyond.  (So is one with
+ *               p below 1, which needs pos < 0 on a mapped record: not valid BAM.)
+ *   read        A read is its qhash.
+ *   exact       Equal (dir, tid, p) are one exact site.
+ *   locus       A maximal run of exact sites of one direction on one contig whose sorted p differ by at most tol from one to the next.
+ * This is a single linkage, as in bk_cigar_gaps: it can chain, and the span in the row shows the extent.  Nothing is capped.
+ * Row: (tid, pos, dir) is the representative, the locus's exact site with the most distinct reads (top_reads of them), ties to the
+ * smaller p.  n_reads counts the distinct qhash of the locus, n_rows its events, n_exact its exact sites; lo_pos .. hi_pos is its span;
+ * n_fwd / n_rev count the rows by flag 0x10; max_clip and clip_sum are over the lengths of the S ops that made the rows, mapq_sum adds
+ * the records' mapq; n_orphan counts the rows with flags 0x1 and 0x8 (the mate is unmapped: the mark of inserted sequence), n_improper
+ * those with 0x1 and neither 0x8 nor 0x2.
+ *   facing      A LEFT locus with representative p and a RIGHT locus with representative q on one contig face each other when
+ *               |q - p - 1| <= pair_dist; mate_off = q - p on both rows, read as bk_link_calls reads it: +1 is a blunt insertion point,
+ *               more means bases lost, 0 or less means bases duplicated (a target-site duplication).  A locus's partner is the facing
+ *               locus with the most n_reads, ties to the smaller |q - p - 1|, then to the smaller position.  flags bit 0 = the locus
+ *               has a partner, bit 1 = the relation is mutual (each is the other's partner).  Facing is decided over all loci, before
+ *               min_reads: mate is the partner's index among the returned rows, 0xFFFFFFFF when it is not returned; mate_pos and
+ *               mate_reads (the partner's representative position and n_reads) and mate_off are filled whenever bit 0 is set, 0 otherwise.
+ *   claim       With a `calls` context: the smallest voted row (flags bit 1) of its BK_STAGE_CLUSTERS with a side s such that ps_tid
+ *               == tid and lo_pos - 2 <= ps_exact <= hi_pos + 2 (sides are not compared, as bk_split_junctions claims); 0xFFFFFFFF
+ *               when there is none, and everywhere when calls is NULL.
+ * Output: the loci with n_reads >= min_reads, ordered by (dir, tid, lo_pos).  Every output word is a count, a sum, an extreme or an
+ * argmax with a fixed tie rule: two runs give the same bytes.
+ * Hand example (one contig of 1 000 000 bases, mapq_min 20, min_clip 10, tol 2, pair_dist 50, min_reads 1; pos 0-based; proper pairs
+ * unless said):
+ *   a, b, c   pos  899  100M50S     mapq 60                    LEFT 999
+ *   d         pos  900  101M49S     mapq 40, reverse           LEFT 1001
+ *   e, f      pos  989  50S100M     mapq 60                    RIGHT 990
+ *   g         pos  989  9S100M      mapq 60                    none: the clip is too short
+ *   h         pos  989  50S100M     mapq 60, an SA tag         none: not eligible
+ *   i         pos 5000  5H30S100M   mapq 60, flag 0x1 | 0x8    RIGHT 5001
+ *   j         pos  899  100M50S     mapq 10                    none: not eligible
+ * Counts: 10 records, 8 eligible, 7 events, 0 beyond, 4 exact, 3 loci, 2 with a mutual partner, 3 returned.  Row 0: tid 0 pos 999 LEFT,
+ * n_reads 4, n_rows 4, n_exact 2, top_reads 3, lo_pos 999, hi_pos 1001, n_fwd 3, n_rev 1, max_clip 50, clip_sum 199, mapq_sum 220, mate 1,
+ * mate_pos 990, mate_reads 2, mate_off -9 (ten bases duplicated), flags 3.  Row 1: tid 0 pos 990 RIGHT, n_reads 2, mate 0, mate_pos
+ * 999, mate_reads 4, mate_off -9, flags 3.  Row 2: tid 0 pos 5001 RIGHT, n_reads 1, n_orphan 1, flags 0.
+ * The struct has no typedef (bk_clip_site is the site of bk_clip_reads). */
+#define BK_CLIP_LEFT 0u
+#define BK_CLIP_RIGHT 1u
+#define BK_CLIPLOCI_MAX_TOL 100u
+#define BK_CLIPLOCI_MAX_PAIR 100000u
+struct bk_clip_locus {
+  int32_t tid; uint32_t pos; uint32_t dir;   /* the representative exact site; pos 1-based, dir 0 = LEFT, 1 = RIGHT */
+  uint32_t flags;                        /* bit 0 has a facing locus, bit 1 the relation is mutual */
+  uint32_t n_reads, n_rows, n_exact;     /* distinct qhash, events, exact sites of the locus */
+  uint32_t top_reads;                    /* distinct reads of the representative */
+  uint32_t lo_pos, hi_pos;               /* span of the locus */
+  uint32_t n_fwd, n_rev;                 /* rows by flag 0x10 */
+  uint32_t max_clip;                     /* the longest clip among the rows */
+  uint32_t n_orphan;                     /* rows with 0x1 and 0x8 */
+  uint64_t clip_sum, mapq_sum;           /* over rows */
+  uint32_t n_improper;                   /* rows with 0x1 and neither 0x8 nor 0x2 */
+  uint32_t claim;                        /* the claiming BK_STAGE_CLUSTERS row, 0xFFFFFFFF for none */
+  uint32_t mate;                         /* the partner among the returned rows, 0xFFFFFFFF when it is not returned */
+  uint32_t mate_pos, mate_reads;         /* the partner's representative position and distinct reads */
+  int32_t mate_off;                      /* q - p */
+};                                       /* 96 bytes */
+/* records: a context that holds a record table (host upload, BK_MEM_DEVICE with and without `side`, the table bk_exclude_regions
+ * left behind - so excluded regions are honoured by themselves -, the context of bk_bam_decode_device_ctx while its bk_bam_dev
+ * lives) and is not a shard (bk_shard_*); no stage need have run on it.  calls: NULL, or a context (records itself, or another one on
+ * the same device with an identical reference list) after bk_split_breakpoints, not a shard.  *out (*count rows) is library-owned until
+ * the next call or bk_free(records).  BK_ERR_ARG (with the reason in bk_last_error) for null outputs, a sharded context, a context
+ * without a table, mapq_min < 0, min_clip < 1, min_reads of 0, tol > BK_CLIPLOCI_MAX_TOL, pair_dist > BK_CLIPLOCI_MAX_PAIR, a calls
+ * context before bk_split_breakpoints and differing reference lists.  BK_ERR_LIMIT beyond 2^30 events.  A table without events is no
+ * error: *count = 0.  It changes nothing a later bk_fetch or bk_run returns.
+ * How: the record pass, one wavefront per tile of 256 records, four consecutive records a lane, flag, mapq, cigar_off and aux_off read
+ * as vectors; only a record whose flag, mapq and empty aux blob pass has its CIGAR words fetched (and its pos, when it has an event), and
+ * the rule of bk_clip_support (one device function, shared with it) looks at its first and last words and walks the whole CIGAR only
+ * where it does there; the count of eligible records reads on to the first word with a reference length, which is the first or second.  Pass one sums the events per tile (it also reads tid as a vector: the table need not be sorted), a scan makes the sums
+ * offsets, pass two looks at the tiles that hold an event again and writes the events in record order (32 bytes: qhash, p, tid and
+ * dir, the clip's length, flag bits and mapq).  Then stable LSD stages of the radix sort by qhash (64 bits; run heads and a scan turn
+ * the hash into a dense rank) and by (dir, tid, p) over 1 + bits(n_targets - 1) + bits(longest contig) bits; the heads of the loci,
+ * of the exact sites and of the reads inside them, with their scans; one stage by (locus, read rank), whose run heads are the distinct
+ * reads of a locus; one wavefront per locus for its row.  The representatives ascend within a (dir, tid), so one wavefront per locus
+ * searches the other direction's loci for the first one inside the facing window and walks the window 64 loci a step; a second kernel
+ * sets the mutual bit.  The claim: the 2 x rows breakpoints of the calls are radix-sorted by (tid, pos) and one lane per locus walks
+ * those inside its span.  A scan compacts the loci by min_reads and renumbers mate.  No atomic anywhere: every result word has one
+ * writer.  The host reads a count three times, where a buffer or a key must be sized or a count is returned: the events (with the
+ * eligible records and beyond), the exact sites with the loci, the mutual loci with the returned rows.
+ * bk_timing: scope `clip_loci`, and inside it `clip_loci_records` (the record pass) and `clip_loci_calls`.  bk_timing_touched, with
+ * T = ceil(records / 256), E = the events that are not beyond, bits(x) the position of the highest set bit of x from 1 (0 for 0) and a
+ * radix pass costing 36 bytes per item: clip_loci_records = 15 * records (flag, mapq, cigar_off, aux_off, tid) + 56 * T (the two tile
+ * words written, scanned and read) + 2816 * min(E, T) (at most that many tiles are read again, 11 bytes a record) + 48 * E (tid, pos,
+ * qhash, the row); clip_loci_calls = E * (36 * (P1 + P2 + P3) + 376) + 176 * loci + 224 * returned + B * (36 * PB + 40), P1 = 8, P2 =
+ * ceil((bits(longest contig) + bits(n_targets - 1) + 1) / 8), P3 = ceil((bits(loci) + bits(E)) / 8), B = 2 x the rows of the calls (0
+ * without them), PB = ceil((33 + bits(n_targets - 1)) / 8); 376 = two key gathers (92), the read ranks (32), the sorted copy (68), the
+ * three heads, scans and two start lists (76), the read key with its heads and scan (68), the rows' read of the sorted table (40).
+ * clip_loci is their sum.  The CIGAR words and the searches are not modelled. */
+int bk_clip_loci(bk_ctx *records, bk_ctx *calls, int mapq_min, int min_clip, uint32_t tol, uint32_t pair_dist, uint32_t min_reads, const struct bk_clip_locus **out,
+                 uint64_t *count);
+/* What the last bk_clip_loci of this context counted: out[0] records, [1] eligible records, [2] events (those beyond among them), [3]
+ * events beyond a contig's end, [4] exact sites, [5] loci, [6] loci with a mutual partner, [7] returned rows.  BK_ERR_ARG for a null
+ * argument. */
+int bk_clip_locus_counts(bk_ctx *records, uint64_t out[8]);
+
 /* Copy a stage's result to library-owned host memory.  *data stays valid until the next bk_fetch
  * of the same stage or bk_free.  group_off (may be NULL) receives n_groups+1 offsets for pair stages. */
 int bk_fetch(bk_ctx *ctx, int stage, const void **data, uint64_t *count, const uint64_t **group_off, uint32_t *n_groups);
