@@ -2,6 +2,7 @@
 #pragma once
 #include "bk_common.h"
 #include "prims.h"
+#include "wave.h"
 
 // Lower bound by a whole wavefront: every lookup of bp.hip and normal.hip is made by all 64 lanes of a wave with the same arguments (one
 // wave per cluster), and a binary search is a chain of dependent memory round trips - 30 of them for a record lookup, ~22 for
@@ -22,12 +23,6 @@ template <class Less> __device__ __forceinline__ uint64_t wave_lower(uint64_t lo
   }
   const uint64_t i = lo + lane;
   return lo + (uint64_t) __popcll(__ballot(i < hi && less(i)));
-}
-// sum of v over the 64 lanes of a wave, on every lane
-__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v)
-{
-  for (int d = 32; d; d >>= 1) v += (uint32_t) __shfl_xor((int) v, d, 64);
-  return v;
 }
 
 struct ClusterAcc

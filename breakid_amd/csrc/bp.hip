@@ -203,11 +203,6 @@ __device__ uint64_t split_lower(const bk_split *__restrict__ sp, uint64_t ns, ui
   }
   return lo;
 }
-__device__ __forceinline__ long long wave_sum(long long v)
-{
-  for (int d = 32; d; d >>= 1) v += __shfl_xor(v, d, 64);
-  return v;
-}
 
 struct Region
 {
@@ -650,11 +645,7 @@ __global__ __launch_bounds__(256) void k_split_keys(const bk_split *__restrict__
   }
   if (max_rec)  // (a sharded sample: the record indices are the whole sample's, the sort takes its passes from the largest one)
   {
-    for (int d = 32; d >= 1; d >>= 1)
-    {
-      const unsigned long long o = __shfl_xor(r, d, 64);
-      r = o > r ? o : r;
-    }
+    r = wave_max(r);
     if ((threadIdx.x & 63) == 0 && r) atomicMax(max_rec, r);
   }
 }

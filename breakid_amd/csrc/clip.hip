@@ -136,10 +136,10 @@ __global__ __launch_bounds__(64) void k_clip_support(RecView r, const bk_cluster
 #pragma unroll
   for (int d = 0; d < 2; ++d)
   {
-    n_at[d] = wave_sum_u32(n_at[d]);
-    n_ev[d] = wave_sum_u32(n_ev[d]);
+    n_at[d] = wave_sum(n_at[d]);
+    n_ev[d] = wave_sum(n_ev[d]);
   }
-  if (stat) words = wave_sum_u32(words);
+  if (stat) words = wave_sum(words);
   if (lane == 0)
   {
     // struct bk_clip_support { at, peak_pos, peak_n, events }, each [side][dir]: a wave stores the two directions of its side
@@ -291,8 +291,8 @@ __device__ __forceinline__ void clip_site_walk(const RecView &r, const ClipNames
   }
   if (!EMIT)
   {
-    const uint32_t n = wave_sum_u32(n_mine);
-    if (out.stat) words = wave_sum_u32(words);
+    const uint32_t n = wave_sum(n_mine);
+    if (out.stat) words = wave_sum(words);
     if (lane == 0)
     {
       out.counts[k] = n;

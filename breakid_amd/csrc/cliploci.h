@@ -5,8 +5,6 @@
 #include "clip.h"
 #include "prims.h"
 
-constexpr uint32_t CLL_TILE_SHIFT = 8;  // records per tile of the record pass: one wavefront, four records a lane
-
 struct ClipLociBufs
 {
   DevBuf tile_ev, tile_eb, totals, ev, sorted, keys, vals, lhead, xhead, qhead, exl, exx, exq, exd, lstart, xstart, rows, lkey, partner, mutual, bkeys, bvals, claim, keep, out;

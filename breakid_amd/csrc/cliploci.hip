@@ -7,13 +7,14 @@
 // per locus for its row; one wavefront per locus for its facing partner; the mutual bit; one lane per locus for the claiming call; a
 // scan that compacts.  Integer arithmetic only, no atomic: every result word has one writer.
 #include "cliploci.h"
+#include "runs.h"
 #include <cstddef>
+
+using runs::bits_of;
+using runs::NONE;
 
 namespace
 {
-constexpr uint32_t NONE = 0xFFFFFFFFu;
-constexpr uint32_t CLL_TILE = 1u << CLL_TILE_SHIFT;
-static_assert(CLL_TILE == 4 * 64, "the record pass deals four records to each of 64 lanes");
 static_assert(sizeof(struct bk_clip_locus) == 96 && offsetof(struct bk_clip_locus, clip_sum) == 56 && offsetof(struct bk_clip_locus, mate) == 80,
               "bk_clip_locus must be 96 bytes");
 
@@ -28,47 +29,6 @@ struct ClipEvent
   uint32_t pad;
 };
 static_assert(sizeof(ClipEvent) == 32, "event rows of cliploci.hip");
-
-struct ClipTotals
-{
-  uint32_t events;
-  uint32_t pad;
-  unsigned long long elig_beyond;  // eligible records | beyond << 32
-};
-
-int bits_of(uint64_t v)
-{
-  int b = 0;
-  for (; v; v >>= 1) ++b;
-  return b;
-}
-
-__device__ __forceinline__ uint32_t wave_max32(uint32_t v)
-{
-#pragma unroll
-  for (int d = 32; d; d >>= 1)
-  {
-    const uint32_t o = __shfl_xor(v, d, 64);
-    v = o > v ? o : v;
-  }
-  return v;
-}
-__device__ __forceinline__ unsigned long long wave_max64(unsigned long long v)
-{
-#pragma unroll
-  for (int d = 32; d; d >>= 1)
-  {
-    const unsigned long long o = __shfl_xor(v, d, 64);
-    v = o > v ? o : v;
-  }
-  return v;
-}
-__device__ __forceinline__ unsigned long long wave_sum64(unsigned long long v)
-{
-#pragma unroll
-  for (int d = 32; d; d >>= 1) v += __shfl_xor(v, d, 64);
-  return v;
-}
 
 // ---- the record pass ------------------------------------------------------------------------------------------------------------------
 // what the lane's four records look like to both passes: flag, mapq and the empty aux blob pass (bit s of `pass`)
@@ -118,7 +78,6 @@ __device__ __forceinline__ ClipLane clip_lane(const RecView &r, uint64_t i0, int
 
 // a record's CIGAR words must lie inside the CIGAR array; one without a word has no reference length
 __device__ __forceinline__ bool clip_walkable(uint32_t c0, uint32_t c1, uint64_t n_words) { return c1 > c0 && c1 <= n_words; }
-__device__ __forceinline__ uint32_t clip_tlen(const ClipLociInput &in, int32_t tid) { return tid < in.nt ? in.tprefix[tid + 1] - in.tprefix[tid] : 0u; }
 // the reference length is above 0: stops at the first word that says so (the first or second of nearly every record)
 __device__ __forceinline__ bool cigar_has_ref(const uint32_t *__restrict__ cg, uint32_t c0, uint32_t c1)
 {
@@ -170,7 +129,7 @@ __device__ __forceinline__ ClipRec clip_record(const ClipLociInput &in, uint64_t
   if (!lead && !trail) return o;
   const int32_t pos = in.rec.pos[i];  // only a record with an event has its pos read
   pt += pos;
-  const long long tl = clip_tlen(in, tid), pl = (long long) pos + 1;
+  const long long tl = runs::tlen(in.tprefix, in.nt, tid), pl = (long long) pos + 1;
   if (lead)
   {
     if (pl < 1 || pl > tl)
@@ -196,7 +155,7 @@ __global__ __launch_bounds__(256) void k_cll_count(ClipLociInput in, ClipLociPar
   if (t >= n_tiles) return;
   const int lane = threadIdx.x & 63;
   const RecView &r = in.rec;
-  const uint64_t i0 = (t << CLL_TILE_SHIFT) + 4u * (uint32_t) lane;
+  const uint64_t i0 = (t << runs::TILE_SHIFT) + 4u * (uint32_t) lane;
   const ClipLane l = clip_lane(r, i0, p.mapq_min);
   int32_t td[4] = {-1, -1, -1, -1};
   if (i0 + 4 <= r.n)
@@ -220,9 +179,9 @@ __global__ __launch_bounds__(256) void k_cll_count(ClipLociInput in, ClipLociPar
     beyond += o.beyond;
     ev += (o.kept & 1u) + (o.kept >> 1);
   }
-  ev = wave_sum_u32(ev);
-  elig = wave_sum_u32(elig);
-  beyond = wave_sum_u32(beyond);
+  ev = wave_sum(ev);
+  elig = wave_sum(elig);
+  beyond = wave_sum(beyond);
   if (lane == 0)
   {
     tile_ev[t] = ev;
@@ -242,7 +201,7 @@ __global__ __launch_bounds__(256) void k_cll_emit(ClipLociInput in, ClipLociPara
   if (base == end) return;
   const int lane = threadIdx.x & 63;
   const RecView &r = in.rec;
-  const uint64_t i0 = (t << CLL_TILE_SHIFT) + 4u * (uint32_t) lane;
+  const uint64_t i0 = (t << runs::TILE_SHIFT) + 4u * (uint32_t) lane;
   const ClipLane l = clip_lane(r, i0, p.mapq_min);
   int32_t td[4] = {-1, -1, -1, -1};
   ClipRec rc[4];
@@ -284,17 +243,6 @@ __global__ __launch_bounds__(256) void k_cll_emit(ClipLociInput in, ClipLociPara
   }
 }
 
-// the three totals in one place, for one copy to the host
-__global__ void k_cll_totals(const uint32_t *__restrict__ ex, const unsigned long long *__restrict__ eb, uint64_t n_tiles, ClipTotals *__restrict__ tot)
-{
-  if (threadIdx.x || blockIdx.x) return;
-  ClipTotals o;
-  o.events = ex[n_tiles];
-  o.pad = 0;
-  o.elig_beyond = eb[n_tiles];
-  *tot = o;
-}
-
 // ---- the sort stages ----------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ uint64_t group_of(uint32_t dt, int tid_bits) { return ((uint64_t) (dt >> 31) << tid_bits) | (dt & 0x7FFFFFFFu); }
 
@@ -308,29 +256,6 @@ __global__ __launch_bounds__(256) void k_cll_keys(const ClipEvent *__restrict__ 
   const ClipEvent t = ev[k];
   keys[i] = mode == 0 ? t.qhash : (group_of(t.dt, tid_bits) << pos_bits) | t.p;
   vals[i] = k;
-}
-
-// head[i] = 1 where sorted key i differs from its predecessor (`first` at i == 0)
-__global__ __launch_bounds__(256) void k_cll_key_heads(const uint64_t *__restrict__ keys, uint32_t n, uint32_t first, uint32_t *__restrict__ head)
-{
-  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  head[i] = i ? keys[i - 1] != keys[i] : first;
-}
-
-// ex = the exclusive scan of heads that are 0 at i == 0: ex[i + 1] is the dense rank of sorted key i
-__global__ __launch_bounds__(256) void k_cll_qrank(const uint32_t *__restrict__ vals, const uint32_t *__restrict__ ex, uint32_t e, ClipEvent *__restrict__ ev)
-{
-  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= e) return;
-  ev[vals[i]].qrank = ex[i + 1];
-}
-
-__global__ __launch_bounds__(256) void k_cll_gather(const ClipEvent *__restrict__ ev, const uint32_t *__restrict__ vals, uint32_t e, ClipEvent *__restrict__ sorted)
-{
-  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= e) return;
-  sorted[i] = ev[vals[i]];
 }
 
 // over the rows sorted by (dir, tid, p, read rank): the heads of the loci, of the exact sites and of the reads inside an exact site;
@@ -351,16 +276,6 @@ __global__ __launch_bounds__(256) void k_cll_heads(const ClipEvent *__restrict__
   lhead[i] = l;
   xhead[i] = x;
   qhead[i] = q;
-}
-
-// ex = the exclusive scan of heads that are 1 at i == 0 (n + 1 entries).  start[r] = the first item of run r, start[runs] = n (the array
-// has n + 1 entries and runs <= n).
-__global__ __launch_bounds__(256) void k_cll_starts(const uint32_t *__restrict__ ex, uint32_t n, uint32_t *__restrict__ start)
-{
-  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  if (ex[i + 1] != ex[i]) start[ex[i]] = i;
-  if (i == 0) start[ex[n]] = n;
 }
 
 // (locus of the row) << rank_bits | read rank: equal keys are one read of one locus
@@ -405,13 +320,13 @@ __global__ __launch_bounds__(256) void k_cll_loci(const ClipEvent *__restrict__ 
       rep = k > rep ? k : rep;
     }
   }
-  n_rev = wave_sum_u32(n_rev);
-  n_orphan = wave_sum_u32(n_orphan);
-  n_improper = wave_sum_u32(n_improper);
-  mq = wave_sum64(mq);
-  cs = wave_sum64(cs);
-  max_clip = wave_max32(max_clip);
-  rep = wave_max64(rep);
+  n_rev = wave_sum(n_rev);
+  n_orphan = wave_sum(n_orphan);
+  n_improper = wave_sum(n_improper);
+  mq = wave_sum(mq);
+  cs = wave_sum(cs);
+  max_clip = wave_max(max_clip);
+  rep = wave_max(rep);
   if (lane) return;
   struct bk_clip_locus r;
   const uint32_t dt = sorted[a].dt;  // (one direction and one contig in a locus)
@@ -565,14 +480,13 @@ __global__ __launch_bounds__(256) void k_cll_out(const struct bk_clip_locus *__r
   out[exk[l]] = r;
 }
 
-uint64_t tiles_of(uint64_t n) { return (n + CLL_TILE - 1) >> CLL_TILE_SHIFT; }
 }  // namespace
 
 // include/breakid_hip.h states both models
 uint64_t ClipLociStats::touched_records() const
 {
-  const uint64_t tiles = tiles_of(n);
-  return n * 15ull + tiles * 56ull + std::min(events, tiles) * (CLL_TILE * 11ull) + events * 48ull;
+  const uint64_t tiles = runs::tiles_of(n);
+  return n * 15ull + tiles * 56ull + std::min(events, tiles) * (runs::TILE * 11ull) + events * 48ull;
 }
 
 uint64_t ClipLociStats::touched_calls() const
@@ -589,25 +503,10 @@ void cliploci_events(const ClipLociInput &in, const ClipLociParams &p, ClipLociB
   s.pos_bits = bits_of(in.max_len);
   s.tid_bits = in.nt > 1 ? bits_of((uint64_t) in.nt - 1) : 0;
   *stats = s;
-  if (in.rec.n == 0) return;
-  const uint64_t nt = tiles_of(in.rec.n);
-  uint32_t *tile_ev = b.tile_ev.as<uint32_t>(nt + 1);
-  unsigned long long *tile_eb = b.tile_eb.as<unsigned long long>(nt + 1);
-  hipLaunchKernelGGL(k_cll_count, dim3(cdiv(nt, 4)), dim3(256), 0, st, in, p, nt, tile_ev, tile_eb);
-  prims::exclusive_scan<uint32_t>(tile_ev, tile_ev, nt, b.scan_tmp, st);
-  prims::exclusive_scan<unsigned long long>(tile_eb, tile_eb, nt, b.scan_tmp64, st);
-  ClipTotals *d_tot = b.totals.as<ClipTotals>(1), tot;
-  hipLaunchKernelGGL(k_cll_totals, dim3(1), dim3(64), 0, st, tile_ev, tile_eb, nt, d_tot);
-  HIP_CHECK(hipMemcpyAsync(&tot, d_tot, sizeof tot, hipMemcpyDeviceToHost, st));
-  HIP_CHECK(hipStreamSynchronize(st));
-  s.events = tot.events;
-  s.eligible = tot.elig_beyond & 0xFFFFFFFFull;
-  s.beyond = tot.elig_beyond >> 32;
-  *stats = s;
-  if (s.events == 0) return;
-  if (s.events > 0x40000000ull) throw bk_error(BK_ERR_LIMIT, "bk_clip_loci: more than 2^30 events");
-  ClipEvent *ev = b.ev.as<ClipEvent>(s.events);
-  hipLaunchKernelGGL(k_cll_emit, dim3(cdiv(nt, 4)), dim3(256), 0, st, in, p, nt, tile_ev, ev);
+  runs::record_pass(
+      in.rec.n, b, st, "bk_clip_loci: more than 2^30 events", *stats,
+      [&](uint64_t nt, uint32_t *tile_ev, unsigned long long *tile_eb) { hipLaunchKernelGGL(k_cll_count, dim3(cdiv(nt, 4)), dim3(256), 0, st, in, p, nt, tile_ev, tile_eb); },
+      [&](uint64_t nt, const uint32_t *ex) { hipLaunchKernelGGL(k_cll_emit, dim3(cdiv(nt, 4)), dim3(256), 0, st, in, p, nt, ex, b.ev.as<ClipEvent>(stats->events)); });
 }
 
 void cliploci_calls(const ClipLociParams &p, const bk_cluster *cl, uint64_t ncl, ClipLociBufs &b, hipStream_t st, struct bk_clip_locus **rows_out, ClipLociStats *stats)
@@ -625,13 +524,13 @@ void cliploci_calls(const ClipLociParams &p, const bk_cluster *cl, uint64_t ncl,
   uint32_t *lhead = b.lhead.as<uint32_t>((uint64_t) e + 1), *xhead = b.xhead.as<uint32_t>((uint64_t) e + 1), *qhead = b.qhead.as<uint32_t>((uint64_t) e + 1);
   hipLaunchKernelGGL(k_cll_keys, dim3(ge), dim3(256), 0, st, ev, (const uint32_t *) nullptr, e, 0, s.pos_bits, s.tid_bits, keys, vals);
   prims::radix_sort_pairs(keys, vals, e, 0, 64, b.radix, st, &sk, &sv);
-  hipLaunchKernelGGL(k_cll_key_heads, dim3(ge), dim3(256), 0, st, sk, e, 0u, lhead);
+  hipLaunchKernelGGL(runs::k_key_heads, dim3(ge), dim3(256), 0, st, sk, e, 0, 0u, lhead, (uint32_t *) nullptr);
   prims::exclusive_scan<uint32_t>(lhead, lhead, e, b.scan_tmp, st);
-  hipLaunchKernelGGL(k_cll_qrank, dim3(ge), dim3(256), 0, st, sv, lhead, e, ev);
+  hipLaunchKernelGGL(runs::k_dense_rank<ClipEvent>, dim3(ge), dim3(256), 0, st, sv, lhead, e, ev);
   hipLaunchKernelGGL(k_cll_keys, dim3(ge), dim3(256), 0, st, ev, sv, e, 1, s.pos_bits, s.tid_bits, keys, vals);
   prims::radix_sort_pairs(keys, vals, e, 0, s.pos_bits + s.tid_bits + 1, b.radix, st, &sk, &sv);
   ClipEvent *sorted = b.sorted.as<ClipEvent>(e);
-  hipLaunchKernelGGL(k_cll_gather, dim3(ge), dim3(256), 0, st, ev, sv, e, sorted);
+  hipLaunchKernelGGL(runs::k_gather_rows<ClipEvent>, dim3(ge), dim3(256), 0, st, ev, sv, e, sorted);
 
   // the loci, the exact sites and their reads
   uint32_t *exl = b.exl.as<uint32_t>((uint64_t) e + 1), *exx = b.exx.as<uint32_t>((uint64_t) e + 1), *exq = b.exq.as<uint32_t>((uint64_t) e + 1);
@@ -640,8 +539,8 @@ void cliploci_calls(const ClipLociParams &p, const bk_cluster *cl, uint64_t ncl,
   prims::exclusive_scan<uint32_t>(xhead, exx, e, b.scan_tmp, st);
   prims::exclusive_scan<uint32_t>(qhead, exq, e, b.scan_tmp, st);
   uint32_t *lstart = b.lstart.as<uint32_t>((uint64_t) e + 1), *xstart = b.xstart.as<uint32_t>((uint64_t) e + 1);
-  hipLaunchKernelGGL(k_cll_starts, dim3(ge), dim3(256), 0, st, exl, e, lstart);
-  hipLaunchKernelGGL(k_cll_starts, dim3(ge), dim3(256), 0, st, exx, e, xstart);
+  hipLaunchKernelGGL(runs::k_run_starts, dim3(ge), dim3(256), 0, st, exl, e, lstart, (uint32_t *) nullptr);
+  hipLaunchKernelGGL(runs::k_run_starts, dim3(ge), dim3(256), 0, st, exx, e, xstart, (uint32_t *) nullptr);
   uint32_t counts[2] = {0, 0};
   HIP_CHECK(hipMemcpyAsync(&counts[0], exl + e, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
   HIP_CHECK(hipMemcpyAsync(&counts[1], exx + e, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
@@ -656,7 +555,7 @@ void cliploci_calls(const ClipLociParams &p, const bk_cluster *cl, uint64_t ncl,
   hipLaunchKernelGGL(k_cll_read_keys, dim3(ge), dim3(256), 0, st, sorted, exl, e, rank_bits, keys, vals);
   prims::radix_sort_pairs(keys, vals, e, 0, rank_bits + bits_of(n_loci), b.radix, st, &sk, &sv);
   uint32_t *exd = b.exd.as<uint32_t>((uint64_t) e + 1);
-  hipLaunchKernelGGL(k_cll_key_heads, dim3(ge), dim3(256), 0, st, sk, e, 1u, lhead);
+  hipLaunchKernelGGL(runs::k_key_heads, dim3(ge), dim3(256), 0, st, sk, e, 0, 1u, lhead, (uint32_t *) nullptr);
   prims::exclusive_scan<uint32_t>(lhead, exd, e, b.scan_tmp, st);
 
   // the rows, the partners and the mutual bit

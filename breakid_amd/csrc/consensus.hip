@@ -123,7 +123,7 @@ __global__ __launch_bounds__(256) void k_cons_walk(ReadsView r, int mapq_min, in
       }
     }
   }
-  words = wave_sum_u32(words);
+  words = wave_sum(words);
   if ((threadIdx.x & 63) == 0 && words) atomicAdd(&stat->words, (unsigned long long) words);
 }
 
@@ -192,8 +192,8 @@ __global__ __launch_bounds__(256) void k_cons_pile(const uint32_t *__restrict__ 
       depth[o] = dep;
     }
   }
-  match = wave_sum_u32(match);
-  total = wave_sum_u32(total);
+  match = wave_sum(match);
+  total = wave_sum(total);
   if (lane == 0)
   {
     struct bk_consensus v;

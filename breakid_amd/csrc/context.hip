@@ -26,10 +26,10 @@ __device__ __forceinline__ void ctx_add(CtxAcc &x, const CtxAcc &y)
 }
 __device__ __forceinline__ CtxAcc ctx_wave_sum(CtxAcc v)
 {
-  v.a = wave_sum_u32(v.a);
-  v.b = wave_sum_u32(v.b);
-  v.c = wave_sum_u32(v.c);
-  v.q = wave_sum_u32(v.q);
+  v.a = wave_sum(v.a);
+  v.b = wave_sum(v.b);
+  v.c = wave_sum(v.c);
+  v.q = wave_sum(v.q);
   return v;
 }
 

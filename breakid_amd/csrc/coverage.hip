@@ -30,11 +30,6 @@ __device__ __forceinline__ long long cov_len(const RecView &r, uint64_t i, int m
   const uint32_t c0 = r.cigar_off[i], c1 = r.cigar_off[i + 1];
   return c1 > c0 ? cov_reflen(r.cigar + c0, c1 - c0) : 0;
 }
-__device__ __forceinline__ long long cov_wave_sum(long long v)
-{
-  for (int d = 32; d; d >>= 1) v += __shfl_xor(v, d, 64);
-  return v;
-}
 
 // Tile pass: one wavefront per tile.  Lane l takes the four consecutive records 4 l .. 4 l + 3 of the tile and reads each column with one
 // vector load (16 bytes of tid, 8 of flag, 4 of mapq, five cigar_off words): the fixed columns of every table form are 16-byte aligned
@@ -81,8 +76,8 @@ __global__ __launch_bounds__(256) void k_cov_tiles(RecView r, int mapq_min, uint
     l += v;
     k += v > 0;
   }
-  l = cov_wave_sum(l);
-  k = cov_wave_sum(k);
+  l = wave_sum(l);
+  k = wave_sum(k);
   if (lane == 0)
   {
     len[t] = (unsigned long long) l;
@@ -131,9 +126,9 @@ __device__ CovEdge cov_edge(const RecView &r, const unsigned long long *__restri
     }
   }
   CovEdge o;
-  o.below = (long long) len[tile] + cov_wave_sum(s);
-  o.n_below = (long long) cnt[tile] + cov_wave_sum(c);
-  o.straddle = cov_wave_sum(st);
+  o.below = (long long) len[tile] + wave_sum(s);
+  o.n_below = (long long) cnt[tile] + wave_sum(c);
+  o.straddle = wave_sum(st);
   return o;
 }
 

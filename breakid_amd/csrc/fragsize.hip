@@ -54,17 +54,6 @@ __device__ uint64_t lane_lower(const RecView &r, int32_t T, long long P)
 
 __device__ __forceinline__ uint64_t rec_hash(const EvidenceRecs &recs, uint64_t i) { return recs.side ? recs.side[i].qhash : recs.qhash[i]; }
 
-__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v)
-{
-  for (int d = 32; d; d >>= 1) v += __shfl_xor(v, d, 64);
-  return v;
-}
-__device__ __forceinline__ long long wave_sum_i64(long long v)
-{
-  for (int d = 32; d; d >>= 1) v += __shfl_xor(v, d, 64);
-  return v;
-}
-
 __global__ __launch_bounds__(256) void k_fg_lengths(RecView r, EvidenceRecs recs, const struct bk_evidence *__restrict__ rows, uint64_t n_rows,
                                                     const struct bk_frag_site *__restrict__ sites, uint32_t ncl, FragLen *__restrict__ out, FragStat *__restrict__ stat)
 {
@@ -208,14 +197,10 @@ __global__ __launch_bounds__(256) void k_fg_lengths(RecView r, EvidenceRecs recs
       out[t >> 1] = v;
     }
   }
-  lookups = wave_sum_u64(lookups);
-  walked = wave_sum_u64(walked);
-  wave_walks = wave_sum_u64(wave_walks);
-  for (int d = 32; d; d >>= 1)
-  {
-    const uint32_t o = (uint32_t) __shfl_xor((int) longest, d, 64);
-    if (o > longest) longest = o;
-  }
+  lookups = wave_sum(lookups);
+  walked = wave_sum(walked);
+  wave_walks = wave_sum(wave_walks);
+  longest = wave_max(longest);
   if (lane == 0)
   {
     atomicAdd(&sh[0], lookups);
@@ -266,12 +251,12 @@ __global__ __launch_bounds__(256) void k_fg_reduce(const FragLen *__restrict__ l
       sum += v.len;
     }
   }
-  n_used = wave_sum_u32(n_used);
-  n_off = wave_sum_u32(n_off);
-  n_lost = wave_sum_u32(n_lost);
-  n_short = wave_sum_u32(n_short);
-  n_long = wave_sum_u32(n_long);
-  sum = wave_sum_i64(sum);
+  n_used = wave_sum(n_used);
+  n_off = wave_sum(n_off);
+  n_lost = wave_sum(n_lost);
+  n_short = wave_sum(n_short);
+  n_long = wave_sum(n_long);
+  sum = wave_sum(sum);
   for (int d = 32; d; d >>= 1)
   {
     const int32_t a = __shfl_xor(mn, d, 64), b = __shfl_xor(mx, d, 64);
@@ -291,7 +276,7 @@ __global__ __launch_bounds__(256) void k_fg_reduce(const FragLen *__restrict__ l
       const long long d = (long long) v.len - centre;
       dev += (unsigned long long) (d < 0 ? -d : d);
     }
-    dev = wave_sum_u64(dev);
+    dev = wave_sum(dev);
   }
   if (lane == 0)
   {

@@ -4,6 +4,7 @@
 // backwards through that prefix may stop.  One wavefront per call: both sides staged in LDS a chunk at a time, the pairs dealt to the
 // lanes, one key reduced by shuffles.  Integer arithmetic only, no atomics.
 #include "frame.h"
+#include "wave.h"
 #include "prims.h"
 
 namespace
@@ -204,23 +205,6 @@ __device__ __forceinline__ uint32_t frame_fill(const FrameModel &m, int32_t tid,
   __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
   __builtin_amdgcn_wave_barrier();
   return count;
-}
-
-__device__ __forceinline__ unsigned long long wave_max(unsigned long long v)
-{
-#pragma unroll
-  for (int d = 32; d; d >>= 1)
-  {
-    const unsigned long long o = __shfl_xor(v, d, 64);
-    v = o > v ? o : v;
-  }
-  return v;
-}
-__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v)
-{
-#pragma unroll
-  for (int d = 32; d; d >>= 1) v += __shfl_xor(v, d, 64);
-  return v;
 }
 
 // One wavefront per site, four to a workgroup; a wavefront touches its own part of the LDS only, so no workgroup barrier.

@@ -4,8 +4,7 @@
 #include "bp.h"
 #include "prims.h"
 
-constexpr uint32_t GAP_TILE_SHIFT = 8;  // records per tile of the record pass: one wavefront, four records a lane
-constexpr int GAP_LEN_BITS = 28;        // a BAM CIGAR word holds its length in 28 bits
+constexpr int GAP_LEN_BITS = 28;  // a BAM CIGAR word holds its length in 28 bits
 
 struct GapBufs
 {

@@ -6,12 +6,13 @@
 // heads of the loci; one stage by (locus, len); the heads of the calls, of the exact events and of the reads inside them; one stage by
 // (call, read rank); one wavefront per call.  Integer arithmetic only, no atomic: every result word has one writer.
 #include "gaps.h"
+#include "runs.h"
+
+using runs::bits_of;
+using runs::NONE;
 
 namespace
 {
-constexpr uint32_t NONE = 0xFFFFFFFFu;
-constexpr uint32_t GAP_TILE = 1u << GAP_TILE_SHIFT;
-static_assert(GAP_TILE == 4 * 64, "the record pass deals four records to each of 64 lanes");
 constexpr uint32_t OP_M = 0, OP_I = 1, OP_D = 2, OP_N = 3, OP_EQ = 7, OP_X = 8;  // BAM CIGAR operations
 constexpr uint16_t FLAG_DROP = 0x4 | 0x100 | 0x200 | 0x400 | 0x800;
 
@@ -25,57 +26,6 @@ struct GapEvent
   uint32_t pad;
 };
 static_assert(sizeof(GapEvent) == 32, "event rows of gaps.hip");
-
-struct GapTotals
-{
-  uint32_t events;
-  uint32_t pad;
-  unsigned long long elig_beyond;  // eligible records | beyond << 32
-};
-
-int bits_of(uint64_t v)
-{
-  int b = 0;
-  for (; v; v >>= 1) ++b;
-  return b;
-}
-
-__device__ __forceinline__ uint32_t wave_min32(uint32_t v)
-{
-#pragma unroll
-  for (int d = 32; d; d >>= 1)
-  {
-    const uint32_t o = __shfl_xor(v, d, 64);
-    v = o < v ? o : v;
-  }
-  return v;
-}
-__device__ __forceinline__ uint32_t wave_max32(uint32_t v)
-{
-#pragma unroll
-  for (int d = 32; d; d >>= 1)
-  {
-    const uint32_t o = __shfl_xor(v, d, 64);
-    v = o > v ? o : v;
-  }
-  return v;
-}
-__device__ __forceinline__ unsigned long long wave_min64(unsigned long long v)
-{
-#pragma unroll
-  for (int d = 32; d; d >>= 1)
-  {
-    const unsigned long long o = __shfl_xor(v, d, 64);
-    v = o < v ? o : v;
-  }
-  return v;
-}
-__device__ __forceinline__ unsigned long long wave_sum64(unsigned long long v)
-{
-#pragma unroll
-  for (int d = 32; d; d >>= 1) v += __shfl_xor(v, d, 64);
-  return v;
-}
 
 // ---- the walk -----------------------------------------------------------------------------------------------------------------------
 // The definition of include/breakid_hip.h for one eligible record with the CIGAR words [c0, c1): f(kind, start, len) for every event
@@ -156,7 +106,6 @@ __device__ __forceinline__ GapLane gap_lane(const RecView &r, uint64_t i0, int m
 
 // a record can hold an anchored gap only with three or more operations; its words must lie inside the CIGAR array
 __device__ __forceinline__ bool gap_walkable(uint32_t c0, uint32_t c1, uint64_t n_words) { return c1 > c0 && c1 - c0 >= 3u && c1 <= n_words; }
-__device__ __forceinline__ uint32_t gap_tlen(const GapInput &in, int32_t tid) { return tid < in.nt ? in.tprefix[tid + 1] - in.tprefix[tid] : 0u; }
 
 // Pass one.  tile_ev[t] = the events of tile t, tile_eb[t] = its eligible records | its events beyond a contig's end << 32.  tid is
 // read for every record here (eligibility needs it and the table need not be sorted yet); pos only for a record that is walked.
@@ -166,7 +115,7 @@ __global__ __launch_bounds__(256) void k_gap_count(GapInput in, GapParams p, uin
   if (t >= n_tiles) return;
   const int lane = threadIdx.x & 63;
   const RecView &r = in.rec;
-  const uint64_t i0 = (t << GAP_TILE_SHIFT) + 4u * (uint32_t) lane;
+  const uint64_t i0 = (t << runs::TILE_SHIFT) + 4u * (uint32_t) lane;
   const GapLane l = gap_lane(r, i0, p.mapq_min);
   int32_t td[4] = {-1, -1, -1, -1};
   if (i0 + 4 <= r.n)
@@ -183,11 +132,11 @@ __global__ __launch_bounds__(256) void k_gap_count(GapInput in, GapParams p, uin
     if (!((l.pass >> s) & 1u) || td[s] < 0) continue;
     ++elig;
     if (!gap_walkable(l.c[s], l.c[s + 1], in.n_cigar_words)) continue;
-    beyond += gap_walk(r.cigar, l.c[s], l.c[s + 1], r.pos[i0 + s], gap_tlen(in, td[s]), p, [&](uint32_t, uint32_t, uint32_t) { ++ev; });
+    beyond += gap_walk(r.cigar, l.c[s], l.c[s + 1], r.pos[i0 + s], runs::tlen(in.tprefix, in.nt, td[s]), p, [&](uint32_t, uint32_t, uint32_t) { ++ev; });
   }
-  ev = wave_sum_u32(ev);
-  elig = wave_sum_u32(elig);
-  beyond = wave_sum_u32(beyond);
+  ev = wave_sum(ev);
+  elig = wave_sum(elig);
+  beyond = wave_sum(beyond);
   if (lane == 0)
   {
     tile_ev[t] = ev;
@@ -206,7 +155,7 @@ __global__ __launch_bounds__(256) void k_gap_emit(GapInput in, GapParams p, uint
   if (base == end) return;
   const int lane = threadIdx.x & 63;
   const RecView &r = in.rec;
-  const uint64_t i0 = (t << GAP_TILE_SHIFT) + 4u * (uint32_t) lane;
+  const uint64_t i0 = (t << runs::TILE_SHIFT) + 4u * (uint32_t) lane;
   const GapLane l = gap_lane(r, i0, p.mapq_min);
   int32_t td[4] = {-1, -1, -1, -1};
   uint32_t mine = 0;
@@ -216,7 +165,7 @@ __global__ __launch_bounds__(256) void k_gap_emit(GapInput in, GapParams p, uint
     if (!((l.pass >> s) & 1u) || !gap_walkable(l.c[s], l.c[s + 1], in.n_cigar_words)) continue;
     td[s] = r.tid[i0 + s];  // (pass is 0 for a record at or beyond n)
     if (td[s] < 0) continue;
-    (void) gap_walk(r.cigar, l.c[s], l.c[s + 1], r.pos[i0 + s], gap_tlen(in, td[s]), p, [&](uint32_t, uint32_t, uint32_t) { ++mine; });
+    (void) gap_walk(r.cigar, l.c[s], l.c[s + 1], r.pos[i0 + s], runs::tlen(in.tprefix, in.nt, td[s]), p, [&](uint32_t, uint32_t, uint32_t) { ++mine; });
   }
   uint32_t slot = base + prims::wave_inclusive_scan(mine) - mine;
   if (!mine) return;
@@ -231,7 +180,7 @@ __global__ __launch_bounds__(256) void k_gap_emit(GapInput in, GapParams p, uint
     e.qrank = 0;
     e.pad = 0;
     const uint32_t tid = (uint32_t) td[s];
-    (void) gap_walk(r.cigar, l.c[s], l.c[s + 1], r.pos[i], gap_tlen(in, td[s]), p, [&](uint32_t kind, uint32_t start, uint32_t len) {
+    (void) gap_walk(r.cigar, l.c[s], l.c[s + 1], r.pos[i], runs::tlen(in.tprefix, in.nt, td[s]), p, [&](uint32_t kind, uint32_t start, uint32_t len) {
       e.start = start;
       e.len = len;
       e.kt = (kind << 31) | tid;
@@ -239,17 +188,6 @@ __global__ __launch_bounds__(256) void k_gap_emit(GapInput in, GapParams p, uint
       ++slot;
     });
   }
-}
-
-// the three totals in one place, for one copy to the host
-__global__ void k_gap_totals(const uint32_t *__restrict__ ex, const unsigned long long *__restrict__ eb, uint64_t n_tiles, GapTotals *__restrict__ tot)
-{
-  if (threadIdx.x || blockIdx.x) return;
-  GapTotals o;
-  o.events = ex[n_tiles];
-  o.pad = 0;
-  o.elig_beyond = eb[n_tiles];
-  *tot = o;
 }
 
 // ---- the sort stages ----------------------------------------------------------------------------------------------------------------
@@ -264,29 +202,6 @@ __global__ __launch_bounds__(256) void k_gap_keys(const GapEvent *__restrict__ e
   const uint64_t group = ((uint64_t) (t.kt >> 31) << tid_bits) | (t.kt & 0x7FFFFFFFu);
   keys[i] = mode == 0 ? t.qhash : mode == 1 ? (uint64_t) t.len : (group << start_bits) | t.start;
   vals[i] = k;
-}
-
-// head[i] = 1 where sorted key i differs from its predecessor (0 at i == 0)
-__global__ __launch_bounds__(256) void k_gap_key_heads(const uint64_t *__restrict__ keys, uint32_t n, uint32_t first, uint32_t *__restrict__ head)
-{
-  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  head[i] = i ? keys[i - 1] != keys[i] : first;
-}
-
-// ex = the exclusive scan of heads that are 0 at i == 0: ex[i + 1] is the dense rank of sorted key i
-__global__ __launch_bounds__(256) void k_gap_qrank(const uint32_t *__restrict__ vals, const uint32_t *__restrict__ ex, uint32_t e, GapEvent *__restrict__ ev)
-{
-  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= e) return;
-  ev[vals[i]].qrank = ex[i + 1];
-}
-
-__global__ __launch_bounds__(256) void k_gap_gather(const GapEvent *__restrict__ ev, const uint32_t *__restrict__ vals, uint32_t e, GapEvent *__restrict__ sorted)
-{
-  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= e) return;
-  sorted[i] = ev[vals[i]];
 }
 
 // over the rows sorted by (kind, tid, start, len): 1 where a locus begins (also at i == 0)
@@ -333,16 +248,6 @@ __global__ __launch_bounds__(256) void k_gap_call_heads(const GapEvent *__restri
   qhead[i] = q;
 }
 
-// ex = the exclusive scan of heads that are 1 at i == 0 (n + 1 entries).  start[r] = the first item of run r, start[runs] = n (the array
-// has n + 1 entries and runs <= n).
-__global__ __launch_bounds__(256) void k_gap_starts(const uint32_t *__restrict__ ex, uint32_t n, uint32_t *__restrict__ start)
-{
-  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  if (ex[i + 1] != ex[i]) start[ex[i]] = i;
-  if (i == 0) start[ex[n]] = n;
-}
-
 // (call of the row) << rank_bits | read rank: equal keys are one read of one call
 __global__ __launch_bounds__(256) void k_gap_read_keys(const GapEvent *__restrict__ bylen, const uint32_t *__restrict__ exc, uint32_t e, int rank_bits, uint64_t *__restrict__ keys,
                                                        uint32_t *__restrict__ vals)
@@ -382,13 +287,13 @@ __global__ __launch_bounds__(256) void k_gap_calls(const GapEvent *__restrict__ 
       top = reads > top ? reads : top;
     }
   }
-  n_rev = wave_sum_u32(n_rev);
-  mq = wave_sum64(mq);
-  lo_s = wave_min32(lo_s);
-  hi_s = wave_max32(hi_s);
-  lo_l = wave_min32(lo_l);
-  hi_l = wave_max32(hi_l);
-  top = wave_max32(top);
+  n_rev = wave_sum(n_rev);
+  mq = wave_sum(mq);
+  lo_s = wave_min(lo_s);
+  hi_s = wave_max(hi_s);
+  lo_l = wave_min(lo_l);
+  hi_l = wave_max(hi_l);
+  top = wave_max(top);
   // the representative: among the exact events with `top` reads the smallest (start, len)
   unsigned long long rep = ~0ull;
   for (uint32_t i = a + lane; i < b; i += 64)
@@ -397,7 +302,7 @@ __global__ __launch_bounds__(256) void k_gap_calls(const GapEvent *__restrict__ 
       const unsigned long long k = ((unsigned long long) bylen[i].start << 32) | bylen[i].len;
       rep = k < rep ? k : rep;
     }
-  rep = wave_min64(rep);
+  rep = wave_min(rep);
   if (lane) return;
   struct bk_cigar_gap r;
   const uint32_t kt = bylen[a].kt;  // (one kind and one contig in a call)
@@ -420,29 +325,13 @@ __global__ __launch_bounds__(256) void k_gap_calls(const GapEvent *__restrict__ 
   keep[c] = r.n_reads >= min_reads;
 }
 
-__global__ __launch_bounds__(256) void k_gap_out(const struct bk_cigar_gap *__restrict__ rows, const uint32_t *__restrict__ exk, uint32_t n_calls, struct bk_cigar_gap *__restrict__ out)
-{
-  const uint32_t c = blockIdx.x * 256 + threadIdx.x;
-  if (c >= n_calls) return;
-  if (exk[c + 1] != exk[c]) out[exk[c]] = rows[c];
-}
-
-uint32_t read_u32(const uint32_t *d, hipStream_t st)
-{
-  uint32_t v = 0;
-  HIP_CHECK(hipMemcpyAsync(&v, d, sizeof v, hipMemcpyDeviceToHost, st));
-  HIP_CHECK(hipStreamSynchronize(st));
-  return v;
-}
-
-uint64_t tiles_of(uint64_t n) { return (n + GAP_TILE - 1) >> GAP_TILE_SHIFT; }
 }  // namespace
 
 // include/breakid_hip.h states both models
 uint64_t GapStats::touched_records() const
 {
-  const uint64_t tiles = tiles_of(n);
-  return n * 11ull + tiles * 56ull + std::min(events, tiles) * (GAP_TILE * 7ull) + events * 48ull;
+  const uint64_t tiles = runs::tiles_of(n);
+  return n * 11ull + tiles * 56ull + std::min(events, tiles) * (runs::TILE * 7ull) + events * 48ull;
 }
 
 uint64_t GapStats::touched_calls() const
@@ -459,25 +348,10 @@ void gap_events(const GapInput &in, const GapParams &p, GapBufs &b, hipStream_t 
   s.start_bits = bits_of(in.max_len);
   s.tid_bits = in.nt > 1 ? bits_of((uint64_t) in.nt - 1) : 0;
   *stats = s;
-  if (in.rec.n == 0) return;
-  const uint64_t nt = tiles_of(in.rec.n);
-  uint32_t *tile_ev = b.tile_ev.as<uint32_t>(nt + 1);
-  unsigned long long *tile_eb = b.tile_eb.as<unsigned long long>(nt + 1);
-  hipLaunchKernelGGL(k_gap_count, dim3(cdiv(nt, 4)), dim3(256), 0, st, in, p, nt, tile_ev, tile_eb);
-  prims::exclusive_scan<uint32_t>(tile_ev, tile_ev, nt, b.scan_tmp, st);
-  prims::exclusive_scan<unsigned long long>(tile_eb, tile_eb, nt, b.scan_tmp64, st);
-  GapTotals *d_tot = b.totals.as<GapTotals>(1), tot;
-  hipLaunchKernelGGL(k_gap_totals, dim3(1), dim3(64), 0, st, tile_ev, tile_eb, nt, d_tot);
-  HIP_CHECK(hipMemcpyAsync(&tot, d_tot, sizeof tot, hipMemcpyDeviceToHost, st));
-  HIP_CHECK(hipStreamSynchronize(st));
-  s.events = tot.events;
-  s.eligible = tot.elig_beyond & 0xFFFFFFFFull;
-  s.beyond = tot.elig_beyond >> 32;
-  *stats = s;
-  if (s.events == 0) return;
-  if (s.events > 0x40000000ull) throw bk_error(BK_ERR_LIMIT, "bk_cigar_gaps: more than 2^30 events");
-  GapEvent *ev = b.ev.as<GapEvent>(s.events);
-  hipLaunchKernelGGL(k_gap_emit, dim3(cdiv(nt, 4)), dim3(256), 0, st, in, p, nt, tile_ev, ev);
+  runs::record_pass(
+      in.rec.n, b, st, "bk_cigar_gaps: more than 2^30 events", *stats,
+      [&](uint64_t nt, uint32_t *tile_ev, unsigned long long *tile_eb) { hipLaunchKernelGGL(k_gap_count, dim3(cdiv(nt, 4)), dim3(256), 0, st, in, p, nt, tile_ev, tile_eb); },
+      [&](uint64_t nt, const uint32_t *ex) { hipLaunchKernelGGL(k_gap_emit, dim3(cdiv(nt, 4)), dim3(256), 0, st, in, p, nt, ex, b.ev.as<GapEvent>(stats->events)); });
 }
 
 void gap_calls(const GapParams &p, GapBufs &b, hipStream_t st, struct bk_cigar_gap **rows_out, GapStats *stats)
@@ -496,26 +370,26 @@ void gap_calls(const GapParams &p, GapBufs &b, hipStream_t st, struct bk_cigar_g
   uint32_t *head = b.head.as<uint32_t>((uint64_t) e + 1), *qhead = b.qhead.as<uint32_t>((uint64_t) e + 1);
   hipLaunchKernelGGL(k_gap_keys, dim3(ge), dim3(256), 0, st, ev, (const uint32_t *) nullptr, e, 0, s.start_bits, s.tid_bits, keys, vals);
   prims::radix_sort_pairs(keys, vals, e, 0, 64, b.radix, st, &sk, &sv);
-  hipLaunchKernelGGL(k_gap_key_heads, dim3(ge), dim3(256), 0, st, sk, e, 0u, head);
+  hipLaunchKernelGGL(runs::k_key_heads, dim3(ge), dim3(256), 0, st, sk, e, 0, 0u, head, (uint32_t *) nullptr);
   prims::exclusive_scan<uint32_t>(head, head, e, b.scan_tmp, st);
-  hipLaunchKernelGGL(k_gap_qrank, dim3(ge), dim3(256), 0, st, sv, head, e, ev);
+  hipLaunchKernelGGL(runs::k_dense_rank<GapEvent>, dim3(ge), dim3(256), 0, st, sv, head, e, ev);
   hipLaunchKernelGGL(k_gap_keys, dim3(ge), dim3(256), 0, st, ev, sv, e, 1, s.start_bits, s.tid_bits, keys, vals);
   prims::radix_sort_pairs(keys, vals, e, 0, GAP_LEN_BITS, b.radix, st, &sk, &sv);
   hipLaunchKernelGGL(k_gap_keys, dim3(ge), dim3(256), 0, st, ev, sv, e, 2, s.start_bits, s.tid_bits, keys, vals);
   prims::radix_sort_pairs(keys, vals, e, 0, s.start_bits + s.tid_bits + 1, b.radix, st, &sk, &sv);
   GapEvent *sorted = b.sorted.as<GapEvent>(e);
-  hipLaunchKernelGGL(k_gap_gather, dim3(ge), dim3(256), 0, st, ev, sv, e, sorted);
+  hipLaunchKernelGGL(runs::k_gather_rows<GapEvent>, dim3(ge), dim3(256), 0, st, ev, sv, e, sorted);
 
   // the loci, and the stage by (locus, len)
   uint32_t *exl = b.ex.as<uint32_t>((uint64_t) e + 1);
   hipLaunchKernelGGL(k_gap_locus_heads, dim3(ge), dim3(256), 0, st, sorted, e, p.tol, head);
   prims::exclusive_scan<uint32_t>(head, exl, e, b.scan_tmp, st);
-  const uint32_t n_loci = read_u32(exl + e, st);  // (1 <= n_loci <= e)
+  const uint32_t n_loci = runs::read_u32(exl + e, st);  // (1 <= n_loci <= e)
   s.loci = n_loci;
   hipLaunchKernelGGL(k_gap_locus_keys, dim3(ge), dim3(256), 0, st, sorted, exl, e, keys, vals);
   prims::radix_sort_pairs(keys, vals, e, 0, GAP_LEN_BITS + bits_of(n_loci), b.radix, st, &sk, &sv);
   GapEvent *bylen = b.bylen.as<GapEvent>(e);
-  hipLaunchKernelGGL(k_gap_gather, dim3(ge), dim3(256), 0, st, sorted, sv, e, bylen);
+  hipLaunchKernelGGL(runs::k_gather_rows<GapEvent>, dim3(ge), dim3(256), 0, st, sorted, sv, e, bylen);
 
   // the calls, the exact events and their reads
   uint32_t *exc = exl, *exx = b.exx.as<uint32_t>((uint64_t) e + 1), *exq = b.exq.as<uint32_t>((uint64_t) e + 1);
@@ -525,8 +399,8 @@ void gap_calls(const GapParams &p, GapBufs &b, hipStream_t st, struct bk_cigar_g
   prims::exclusive_scan<uint32_t>(xhead, exx, e, b.scan_tmp, st);
   prims::exclusive_scan<uint32_t>(qhead, exq, e, b.scan_tmp, st);
   uint32_t *cstart = b.cstart.as<uint32_t>((uint64_t) e + 1), *xstart = b.xstart.as<uint32_t>((uint64_t) e + 1);
-  hipLaunchKernelGGL(k_gap_starts, dim3(ge), dim3(256), 0, st, exc, e, cstart);
-  hipLaunchKernelGGL(k_gap_starts, dim3(ge), dim3(256), 0, st, exx, e, xstart);
+  hipLaunchKernelGGL(runs::k_run_starts, dim3(ge), dim3(256), 0, st, exc, e, cstart, (uint32_t *) nullptr);
+  hipLaunchKernelGGL(runs::k_run_starts, dim3(ge), dim3(256), 0, st, exx, e, xstart, (uint32_t *) nullptr);
   uint32_t counts[2] = {0, 0};
   HIP_CHECK(hipMemcpyAsync(&counts[0], exc + e, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
   HIP_CHECK(hipMemcpyAsync(&counts[1], exx + e, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
@@ -540,7 +414,7 @@ void gap_calls(const GapParams &p, GapBufs &b, hipStream_t st, struct bk_cigar_g
   hipLaunchKernelGGL(k_gap_read_keys, dim3(ge), dim3(256), 0, st, bylen, exc, e, rank_bits, keys, vals);
   prims::radix_sort_pairs(keys, vals, e, 0, rank_bits + bits_of(n_calls), b.radix, st, &sk, &sv);
   uint32_t *exd = b.exd.as<uint32_t>((uint64_t) e + 1);
-  hipLaunchKernelGGL(k_gap_key_heads, dim3(ge), dim3(256), 0, st, sk, e, 1u, head);
+  hipLaunchKernelGGL(runs::k_key_heads, dim3(ge), dim3(256), 0, st, sk, e, 0, 1u, head, (uint32_t *) nullptr);
   prims::exclusive_scan<uint32_t>(head, exd, e, b.scan_tmp, st);
 
   // the rows, and those with enough reads
@@ -549,8 +423,8 @@ void gap_calls(const GapParams &p, GapBufs &b, hipStream_t st, struct bk_cigar_g
   hipLaunchKernelGGL(k_gap_calls, dim3(cdiv(n_calls, 4)), dim3(256), 0, st, bylen, cstart, xstart, exx, exq, exd, n_calls, p.min_reads, rows, keep);
   prims::exclusive_scan<uint32_t>(keep, keep, n_calls, b.scan_tmp, st);
   struct bk_cigar_gap *out = b.out.as<struct bk_cigar_gap>((uint64_t) n_calls + 1);
-  hipLaunchKernelGGL(k_gap_out, dim3(cdiv(n_calls, 256)), dim3(256), 0, st, rows, keep, n_calls, out);
-  s.written = read_u32(keep + n_calls, st);
+  hipLaunchKernelGGL(runs::k_keep_out<struct bk_cigar_gap>, dim3(cdiv(n_calls, 256)), dim3(256), 0, st, rows, keep, n_calls, out);
+  s.written = runs::read_u32(keep + n_calls, st);
   *rows_out = out;
   *stats = s;
 }

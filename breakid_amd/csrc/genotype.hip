@@ -72,7 +72,7 @@ __global__ __launch_bounds__(256) void k_ref_support(RecView r, const bk_cluster
       }
     }
   }
-  if (stat) words = wave_sum_u32(words);
+  if (stat) words = wave_sum(words);
   if (lane == 0)
   {
     // struct bk_ref_support { ref_pairs1, ref_pairs2, ref_reads1, ref_reads2 }: each wave stores the two fields of its side

@@ -78,10 +78,10 @@ __global__ __launch_bounds__(256) void k_junction_sr(TupleTable tt, const bk_clu
       n2 += b == 2u;
       n3 += b == 3u;
     });
-    n0 = wave_sum_u32(n0);
-    n1 = wave_sum_u32(n1);
-    n2 = wave_sum_u32(n2);
-    n3 = wave_sum_u32(n3);
+    n0 = wave_sum(n0);
+    n1 = wave_sum(n1);
+    n2 = wave_sum(n2);
+    n3 = wave_sum(n3);
   }
   if (lane == 0)
   {

@@ -6,6 +6,7 @@
 // distinct names are counted without atomics: the hits per site are scanned, a second walk lists (site << 32) | name at the site's
 // offset, the list is sorted and one wavefront per site counts the run heads.  Integer arithmetic only: two runs give the same bytes.
 #include "known.h"
+#include "runs.h"
 
 namespace
 {
@@ -96,33 +97,6 @@ __device__ __forceinline__ uint32_t known_upper(const unsigned long long *__rest
       hi = mid;
   }
   return lo;
-}
-
-__device__ __forceinline__ unsigned long long wave_max64(unsigned long long v)
-{
-#pragma unroll
-  for (int d = 32; d; d >>= 1)
-  {
-    const unsigned long long o = __shfl_xor(v, d, 64);
-    v = o > v ? o : v;
-  }
-  return v;
-}
-__device__ __forceinline__ uint32_t wave_min32(uint32_t v)
-{
-#pragma unroll
-  for (int d = 32; d; d >>= 1)
-  {
-    const uint32_t o = __shfl_xor(v, d, 64);
-    v = o < v ? o : v;
-  }
-  return v;
-}
-__device__ __forceinline__ uint32_t wave_sum32(uint32_t v)
-{
-#pragma unroll
-  for (int d = 32; d; d >>= 1) v += __shfl_xor(v, d, 64);
-  return v;
 }
 
 // what an entry is to a site: the table F (bit 2 * s + k = breakend s falls into interval k) and, where a mapping holds, the hit
@@ -236,13 +210,13 @@ __global__ __launch_bounds__(256) void k_known_sites(const struct bk_known_site 
   }
   if (LIST) return;
 
-  n_hits = wave_sum32(n_hits);
-  n_oriented = wave_sum32(n_oriented);
-  n_opposed = wave_sum32(n_opposed);
-  n_side[0] = wave_sum32(n_side[0]);
-  n_side[1] = wave_sum32(n_side[1]);
-  const unsigned long long top_key = wave_max64(best_key);
-  const uint32_t top_info = wave_min32(best_key == top_key && best_key ? best_info : 0xFFFFFFFFu);
+  n_hits = wave_sum(n_hits);
+  n_oriented = wave_sum(n_oriented);
+  n_opposed = wave_sum(n_opposed);
+  n_side[0] = wave_sum(n_side[0]);
+  n_side[1] = wave_sum(n_side[1]);
+  const unsigned long long top_key = wave_max(best_key);
+  const uint32_t top_info = wave_min(best_key == top_key && best_key ? best_info : 0xFFFFFFFFu);
 
   struct bk_known_call r;
   r.n_hits = n_hits, r.n_oriented = n_oriented, r.n_opposed = n_opposed, r.n_names = 0;
@@ -277,17 +251,12 @@ __global__ __launch_bounds__(256) void k_known_name_heads(uint32_t n, const unsi
   const unsigned long long seg = off[i], seg_end = off[i + 1];
   uint32_t heads = 0;
   for (unsigned long long r = seg + lane; r < seg_end; r += 64) heads += r == seg || nkey[r] != nkey[r - 1];
-  heads = wave_sum32(heads);
+  heads = wave_sum(heads);
   if (lane == 0) res[i].n_names = heads;
 }
-
-int bits_of(uint64_t v)
-{
-  int bits = 0;
-  for (; v; v >>= 1) ++bits;
-  return bits;
-}
 }  // namespace
+
+using runs::bits_of;
 
 int KnownShape::key_bits() const { return m ? 32 + bits_of((uint64_t) max_tid + 1) : 0; }
 int KnownShape::name_bits() const { return bits_of(max_name); }

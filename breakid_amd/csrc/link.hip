@@ -5,6 +5,7 @@
 // jumping, the rounds counted by the host.  Integer arithmetic only; the atomics are integer min and add, whose results do not depend
 // on the order.
 #include "link.h"
+#include "wave.h"
 
 namespace
 {
@@ -73,23 +74,6 @@ __device__ __forceinline__ uint32_t link_lower(const unsigned long long *__restr
       hi = mid;
   }
   return lo;
-}
-
-__device__ __forceinline__ unsigned long long wave_min64(unsigned long long v)
-{
-#pragma unroll
-  for (int d = 32; d; d >>= 1)
-  {
-    const unsigned long long o = __shfl_xor(v, d, 64);
-    v = o < v ? o : v;
-  }
-  return v;
-}
-__device__ __forceinline__ unsigned long long wave_sum64(unsigned long long v)
-{
-#pragma unroll
-  for (int d = 32; d; d >>= 1) v += __shfl_xor(v, d, 64);
-  return v;
 }
 
 constexpr unsigned long long NO_KEY = ~0ull;
@@ -173,10 +157,10 @@ __global__ __launch_bounds__(256) void k_link_sites(const struct bk_link_site *_
       if (!__all(hit)) break;  // the table is sorted: behind the first miss there is no hit
     }
   }
-  counts = wave_sum64(counts);
-  const unsigned long long adj = wave_sum64(n_adj);
-  dup_min = wave_min64(dup_min);
-  mate_min = wave_min64(mate_min);
+  counts = wave_sum(counts);
+  const unsigned long long adj = wave_sum<unsigned long long>(n_adj);
+  dup_min = wave_min(dup_min);
+  mate_min = wave_min(mate_min);
 
   struct bk_call_link r;
   r.n_dup = (uint32_t) counts;

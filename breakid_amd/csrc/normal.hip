@@ -152,7 +152,7 @@ __global__ __launch_bounds__(256) void k_normal_sr(TupleTable tt, const bk_clust
   if (!(k.flags & 2u)) return;
   uint32_t n = 0;
   for_matching_tuples(tt, k, [&](const bk_split &, bool) { ++n; });
-  n = wave_sum_u32(n);
+  n = wave_sum(n);
   if (lane == 0) res[c].n_sr = n;
 }
 

@@ -5,6 +5,7 @@
 // own at scanned offsets; the rows are sorted by (site, mate key) and one wavefront per site walks its segment for the runs.  Integer
 // arithmetic only, no atomics: two runs give the same bytes.
 #include "partners.h"
+#include "runs.h"
 
 namespace
 {
@@ -148,17 +149,6 @@ __global__ __launch_bounds__(256) void k_partner_gather(const uint64_t *__restri
   fkey[r] = key_by_mate[spos[r]];
 }
 
-__device__ __forceinline__ uint64_t wave_max64(uint64_t v)
-{
-#pragma unroll
-  for (int d = 32; d; d >>= 1)
-  {
-    const uint64_t o = __shfl_xor(v, d, 64);
-    v = o > v ? o : v;
-  }
-  return v;
-}
-
 // ---- runs: one wavefront per site over its sorted segment, 64 rows a step -------------------------------------------------------------
 // Row r opens a run when it is the segment's first, when its contig differs from row r - 1's, or when its position exceeds that row's
 // by more than max_gap.  The open run is carried as its first row (`open`); a lane whose row opens a run closes the one before it,
@@ -204,7 +194,7 @@ __global__ __launch_bounds__(256) void k_partner_runs(uint32_t n, const uint64_t
     const uint64_t c = candidate(open, seg_end - open);  // the run that the segment's end closes
     best = c > best ? c : best;
   }
-  best = wave_max64(best);
+  best = wave_max(best);
   if (lane == 0)
   {
     const uint4 f = info[i];
@@ -222,12 +212,7 @@ __global__ __launch_bounds__(256) void k_partner_runs(uint32_t n, const uint64_t
   }
 }
 
-int bits_of(uint64_t v)
-{
-  int bits = 0;
-  for (; v; v >>= 1) ++bits;
-  return bits;
-}
+using runs::bits_of;
 int site_bits(uint64_t n_sites) { return n_sites ? bits_of(n_sites - 1) : 0; }
 }  // namespace
 

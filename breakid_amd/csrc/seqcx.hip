@@ -4,6 +4,7 @@
 // 64 lanes three ways: every lane popcounts the planes, lane t counts trinucleotide t, lane p - 1 walks the tracts of period p.  No
 // byte compares, no atomics, no float.
 #include "seqcx.h"
+#include "wave.h"
 
 namespace
 {
@@ -17,24 +18,6 @@ struct WaveLds
 {
   unsigned long long p[N_PLANES][CX_W];  // bit i of a plane is column i
 };
-
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v)
-{
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-  return v;
-}
-
-__device__ __forceinline__ uint32_t wave_max(uint32_t v)
-{
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1)
-  {
-    const uint32_t o = __shfl_xor(v, d, 64);
-    v = o > v ? o : v;
-  }
-  return v;
-}
 
 // the columns whose base has the 2-bit code c, 64 of them from column `at` on
 __device__ __forceinline__ unsigned long long has_code(const WaveLds &S, uint32_t at, uint32_t c)

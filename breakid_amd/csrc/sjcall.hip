@@ -7,10 +7,13 @@
 // arithmetic only.  Every result word has one writer and no atomic; the labels alone take an integer atomic minimum (a root is hooked
 // by whoever finds a smaller label), whose outcome does not depend on the order, and labels only fall.
 #include "sjcall.h"
+#include "runs.h"
+
+using runs::bits_of;
+using runs::NONE;
 
 namespace
 {
-constexpr uint32_t NONE = 0xFFFFFFFFu;
 constexpr int JUMPS = 8;  // pointer jumps of one vertex in one round
 
 struct SjTuple
@@ -26,50 +29,6 @@ struct SjExact
   uint32_t pos1, pos2, n_reads, n_tuples, n_own[2], mapq_sum[2];
 };
 static_assert(sizeof(SjTuple) == 32 && sizeof(SjExact) == 40 && sizeof(SjClaim) == 24, "row sizes of sjcall.hip");
-
-int bits_of(uint64_t v)
-{
-  int b = 0;
-  for (; v; v >>= 1) ++b;
-  return b;
-}
-
-__device__ __forceinline__ uint32_t wave_min32(uint32_t v)
-{
-#pragma unroll
-  for (int d = 32; d; d >>= 1)
-  {
-    const uint32_t o = __shfl_xor(v, d, 64);
-    v = o < v ? o : v;
-  }
-  return v;
-}
-__device__ __forceinline__ uint32_t wave_max32(uint32_t v)
-{
-#pragma unroll
-  for (int d = 32; d; d >>= 1)
-  {
-    const uint32_t o = __shfl_xor(v, d, 64);
-    v = o > v ? o : v;
-  }
-  return v;
-}
-__device__ __forceinline__ uint32_t wave_sum32(uint32_t v)
-{
-#pragma unroll
-  for (int d = 32; d; d >>= 1) v += __shfl_xor(v, d, 64);
-  return v;
-}
-__device__ __forceinline__ unsigned long long wave_max64(unsigned long long v)
-{
-#pragma unroll
-  for (int d = 32; d; d >>= 1)
-  {
-    const unsigned long long o = __shfl_xor(v, d, 64);
-    v = o > v ? o : v;
-  }
-  return v;
-}
 
 // ---- classification -----------------------------------------------------------------------------------------------------------------
 // The definition of include/breakid_hip.h, one tuple.  Every read is inside its array: tid and the other contig are checked against
@@ -134,38 +93,6 @@ __global__ __launch_bounds__(256) void k_sj_keys(const SjTuple *__restrict__ tup
   vals[i] = k;
 }
 
-// head[i] = 1 where sorted key i differs from its predecessor in the bits from `shift` up (never at i == 0 when first == 0);
-// sub[i] (may be null) = 1 where the whole key differs or head[i] is set
-__global__ __launch_bounds__(256) void k_sj_key_heads(const uint64_t *__restrict__ keys, uint32_t n, int shift, uint32_t first, uint32_t *__restrict__ head, uint32_t *__restrict__ sub)
-{
-  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  uint32_t h = first, s = first;
-  if (i)
-  {
-    const uint64_t a = keys[i - 1], b = keys[i];
-    h = (a >> shift) != (b >> shift);
-    s = a != b;
-  }
-  head[i] = h;
-  if (sub) sub[i] = s | h;
-}
-
-// ex = the exclusive scan of heads that are 0 at i == 0: ex[i + 1] is the dense rank of sorted key i
-__global__ __launch_bounds__(256) void k_sj_qrank(const uint32_t *__restrict__ vals, const uint32_t *__restrict__ ex, uint32_t e, SjTuple *__restrict__ tup)
-{
-  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= e) return;
-  tup[vals[i]].qrank = ex[i + 1];
-}
-
-__global__ __launch_bounds__(256) void k_sj_gather(const SjTuple *__restrict__ tup, const uint32_t *__restrict__ vals, uint32_t e, SjTuple *__restrict__ sorted)
-{
-  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= e) return;
-  sorted[i] = tup[vals[i]];
-}
-
 // the heads of the exact junctions and of the reads inside them, over the sorted rows; both are 1 at i == 0
 __global__ __launch_bounds__(256) void k_sj_heads(const SjTuple *__restrict__ sorted, uint32_t e, uint32_t *__restrict__ head, uint32_t *__restrict__ qhead)
 {
@@ -180,17 +107,6 @@ __global__ __launch_bounds__(256) void k_sj_heads(const SjTuple *__restrict__ so
   }
   head[i] = h;
   qhead[i] = q;
-}
-
-// ex = the exclusive scan of heads that are 1 at i == 0 (n + 1 entries).  start[r] = the first item of run r, start[runs] = n (the
-// array has n + 1 entries and runs <= n); id[i] (may be null) = the run of item i.
-__global__ __launch_bounds__(256) void k_sj_starts(const uint32_t *__restrict__ head, const uint32_t *__restrict__ ex, uint32_t n, uint32_t *__restrict__ start, uint32_t *__restrict__ id)
-{
-  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  if (head[i]) start[ex[i]] = i;
-  if (i == 0) start[ex[n]] = n;
-  if (id) id[i] = ex[i + 1] - 1u;
 }
 
 // ---- the exact junctions ------------------------------------------------------------------------------------------------------------
@@ -211,9 +127,9 @@ __global__ __launch_bounds__(256) void k_sj_exact(const SjTuple *__restrict__ so
     mq0 += o ? 0u : mq;
     mq1 += o ? mq : 0u;
   }
-  own1 = wave_sum32(own1);
-  mq0 = wave_sum32(mq0);
-  mq1 = wave_sum32(mq1);
+  own1 = wave_sum(own1);
+  mq0 = wave_sum(mq0);
+  mq1 = wave_sum(mq1);
   if (lane) return;
   const SjTuple t = sorted[a];
   SjExact r;
@@ -280,7 +196,7 @@ __global__ __launch_bounds__(256) void k_sj_hook(const SjExact *__restrict__ xro
     }
     if (!__all(hit)) break;  // the table is sorted: behind the first miss there is no hit
   }
-  m = wave_min32(m);
+  m = wave_min(m);
   if (lane == 0)
   {
     const uint32_t old = label[j];  // (old <= j < x)
@@ -387,17 +303,17 @@ __global__ __launch_bounds__(256) void k_sj_calls(const SjExact *__restrict__ xr
     const unsigned long long key = ((unsigned long long) r.n_reads << 32) | (0xFFFFFFFFu - j);
     top = key > top ? key : top;
   }
-  n_tuples = wave_sum32(n_tuples);
-  own0 = wave_sum32(own0);
-  own1 = wave_sum32(own1);
-  mq0 = wave_sum32(mq0);
-  mq1 = wave_sum32(mq1);
-  lo1 = wave_min32(lo1);
-  hi1 = wave_max32(hi1);
-  lo2 = wave_min32(lo2);
-  hi2 = wave_max32(hi2);
-  cl = wave_min32(cl);
-  top = wave_max64(top);
+  n_tuples = wave_sum(n_tuples);
+  own0 = wave_sum(own0);
+  own1 = wave_sum(own1);
+  mq0 = wave_sum(mq0);
+  mq1 = wave_sum(mq1);
+  lo1 = wave_min(lo1);
+  hi1 = wave_max(hi1);
+  lo2 = wave_min(lo2);
+  hi2 = wave_max(hi2);
+  cl = wave_min(cl);
+  top = wave_max(top);
   if (lane) return;
   const SjExact rep = xrow[0xFFFFFFFFu - (uint32_t) top];  // (a call has at least one exact junction, so top came from one)
   const uint64_t t12 = rep.g >> 2;
@@ -445,20 +361,6 @@ __global__ __launch_bounds__(256) void k_sj_count_claimed(const struct bk_split_
   if (threadIdx.x == 0) counts[1] = tot;
 }
 
-__global__ __launch_bounds__(256) void k_sj_out(const struct bk_split_junction *__restrict__ rows, const uint32_t *__restrict__ exk, uint32_t n_calls, struct bk_split_junction *__restrict__ out)
-{
-  const uint32_t c = blockIdx.x * 256 + threadIdx.x;
-  if (c >= n_calls) return;
-  if (exk[c + 1] != exk[c]) out[exk[c]] = rows[c];
-}
-
-uint32_t read_u32(const uint32_t *d, hipStream_t st)
-{
-  uint32_t v = 0;
-  HIP_CHECK(hipMemcpyAsync(&v, d, sizeof v, hipMemcpyDeviceToHost, st));
-  HIP_CHECK(hipStreamSynchronize(st));
-  return v;
-}
 }  // namespace
 
 uint64_t SjStats::touched() const
@@ -485,7 +387,7 @@ void split_junctions(const SjInput &in, int mapq_min, uint32_t tol, uint32_t min
   uint32_t *ex = b.flag.as<uint32_t>(in.n + 1);
   hipLaunchKernelGGL(k_sj_flag, dim3(cdiv(in.n, 256)), dim3(256), 0, st, in, mapq_min, ex);
   prims::exclusive_scan<uint32_t>(ex, ex, in.n, b.scan_tmp, st);
-  const uint32_t e = read_u32(ex + in.n, st);
+  const uint32_t e = runs::read_u32(ex + in.n, st);
   s.eligible = e;
   *stats = s;
   if (e == 0) return;
@@ -500,15 +402,15 @@ void split_junctions(const SjInput &in, int mapq_min, uint32_t tol, uint32_t min
   const unsigned ge = cdiv(e, 256);
   hipLaunchKernelGGL(k_sj_keys, dim3(ge), dim3(256), 0, st, tup, (const uint32_t *) nullptr, e, 0, s.pos_bits, keys, vals);
   prims::radix_sort_pairs(keys, vals, e, 0, 64, b.radix, st, &sk, &sv);
-  hipLaunchKernelGGL(k_sj_key_heads, dim3(ge), dim3(256), 0, st, sk, e, 0, 0u, head, (uint32_t *) nullptr);
+  hipLaunchKernelGGL(runs::k_key_heads, dim3(ge), dim3(256), 0, st, sk, e, 0, 0u, head, (uint32_t *) nullptr);
   prims::exclusive_scan<uint32_t>(head, head, e, b.scan_tmp, st);
-  hipLaunchKernelGGL(k_sj_qrank, dim3(ge), dim3(256), 0, st, sv, head, e, tup);
+  hipLaunchKernelGGL(runs::k_dense_rank<SjTuple>, dim3(ge), dim3(256), 0, st, sv, head, e, tup);
   hipLaunchKernelGGL(k_sj_keys, dim3(ge), dim3(256), 0, st, tup, sv, e, 1, s.pos_bits, keys, vals);
   prims::radix_sort_pairs(keys, vals, e, 0, 2 * s.pos_bits, b.radix, st, &sk, &sv);
   hipLaunchKernelGGL(k_sj_keys, dim3(ge), dim3(256), 0, st, tup, sv, e, 2, s.pos_bits, keys, vals);
   prims::radix_sort_pairs(keys, vals, e, 0, s.group_bits, b.radix, st, &sk, &sv);
   SjTuple *sorted = b.sorted.as<SjTuple>(e);
-  hipLaunchKernelGGL(k_sj_gather, dim3(ge), dim3(256), 0, st, tup, sv, e, sorted);
+  hipLaunchKernelGGL(runs::k_gather_rows<SjTuple>, dim3(ge), dim3(256), 0, st, tup, sv, e, sorted);
 
   // 4: the exact junctions
   uint32_t *exq = qhead, *xid = b.xid.as<uint32_t>(e), *xstart = b.xstart.as<uint32_t>((uint64_t) e + 1);
@@ -516,8 +418,8 @@ void split_junctions(const SjInput &in, int mapq_min, uint32_t tol, uint32_t min
   uint32_t *exh = b.ex.as<uint32_t>((uint64_t) e + 1);
   prims::exclusive_scan<uint32_t>(head, exh, e, b.scan_tmp, st);
   prims::exclusive_scan<uint32_t>(qhead, exq, e, b.scan_tmp, st);
-  hipLaunchKernelGGL(k_sj_starts, dim3(ge), dim3(256), 0, st, head, exh, e, xstart, xid);
-  const uint32_t x = read_u32(exh + e, st);  // (1 <= x <= e)
+  hipLaunchKernelGGL(runs::k_run_starts, dim3(ge), dim3(256), 0, st, exh, e, xstart, xid);
+  const uint32_t x = runs::read_u32(exh + e, st);  // (1 <= x <= e)
   s.exact = x;
   SjExact *xrow = b.xrow.as<SjExact>(x);
   uint32_t *label = b.label.as<uint32_t>(x), *changed = b.changed.as<uint32_t>(1);
@@ -533,7 +435,7 @@ void split_junctions(const SjInput &in, int mapq_min, uint32_t tol, uint32_t min
     HIP_CHECK(hipMemsetAsync(changed, 0, sizeof(uint32_t), st));
     hipLaunchKernelGGL(k_sj_hook, dim3(cdiv(x, 4)), dim3(256), 0, st, xrow, x, tol, label, changed);
     hipLaunchKernelGGL(k_sj_jump, dim3(cdiv(x, 256)), dim3(256), 0, st, label, x);
-    if (!read_u32(changed, st)) break;
+    if (!runs::read_u32(changed, st)) break;
   }
   s.rounds = rounds;
 
@@ -544,20 +446,20 @@ void split_junctions(const SjInput &in, int mapq_min, uint32_t tol, uint32_t min
   prims::radix_sort_pairs(keys, vals, x, 0, x_bits, b.radix, st, &sk, &sv);
   uint32_t *xlist = b.xlist.as<uint32_t>(x), *cx = b.cstart_x.as<uint32_t>((uint64_t) x + 1), *ct = b.cstart_t.as<uint32_t>((uint64_t) x + 1);
   HIP_CHECK(hipMemcpyAsync(xlist, sv, (uint64_t) x * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
-  hipLaunchKernelGGL(k_sj_key_heads, dim3(gx), dim3(256), 0, st, sk, x, 0, 1u, head, (uint32_t *) nullptr);
+  hipLaunchKernelGGL(runs::k_key_heads, dim3(gx), dim3(256), 0, st, sk, x, 0, 1u, head, (uint32_t *) nullptr);
   prims::exclusive_scan<uint32_t>(head, exh, x, b.scan_tmp, st);
-  hipLaunchKernelGGL(k_sj_starts, dim3(gx), dim3(256), 0, st, head, exh, x, cx, (uint32_t *) nullptr);
-  const uint32_t n_calls = read_u32(exh + x, st);  // (1 <= n_calls <= x)
+  hipLaunchKernelGGL(runs::k_run_starts, dim3(gx), dim3(256), 0, st, exh, x, cx, (uint32_t *) nullptr);
+  const uint32_t n_calls = runs::read_u32(exh + x, st);  // (1 <= n_calls <= x)
   s.calls = n_calls;
 
   // 7: the tuples by (label, read rank): the heads of the sub-runs are the distinct reads of a call
   hipLaunchKernelGGL(k_sj_tuple_keys, dim3(ge), dim3(256), 0, st, sorted, xid, label, e, rank_bits, keys, vals);
   prims::radix_sort_pairs(keys, vals, e, 0, rank_bits + x_bits, b.radix, st, &sk, &sv);
   uint32_t *exd = qhead;
-  hipLaunchKernelGGL(k_sj_key_heads, dim3(ge), dim3(256), 0, st, sk, e, rank_bits, 1u, head, qhead);
+  hipLaunchKernelGGL(runs::k_key_heads, dim3(ge), dim3(256), 0, st, sk, e, rank_bits, 1u, head, qhead);
   prims::exclusive_scan<uint32_t>(head, exh, e, b.scan_tmp, st);
   prims::exclusive_scan<uint32_t>(qhead, exd, e, b.scan_tmp, st);
-  hipLaunchKernelGGL(k_sj_starts, dim3(ge), dim3(256), 0, st, head, exh, e, ct, (uint32_t *) nullptr);  // (as many label runs as calls: ct[n_calls] = e)
+  hipLaunchKernelGGL(runs::k_run_starts, dim3(ge), dim3(256), 0, st, exh, e, ct, (uint32_t *) nullptr);  // (as many label runs as calls: ct[n_calls] = e)
 
   // 9: the claimed row of every exact junction
   uint32_t *claim = b.claim.as<uint32_t>(x);
@@ -572,9 +474,9 @@ void split_junctions(const SjInput &in, int mapq_min, uint32_t tol, uint32_t min
   hipLaunchKernelGGL(k_sj_count_claimed, dim3(1), dim3(256), 0, st, rows, keep, n_calls, counts);
   prims::exclusive_scan<uint32_t>(keep, keep, n_calls, b.scan_tmp, st);
   struct bk_split_junction *out = b.out.as<struct bk_split_junction>((uint64_t) n_calls + 1);
-  hipLaunchKernelGGL(k_sj_out, dim3(cdiv(n_calls, 256)), dim3(256), 0, st, rows, keep, n_calls, out);
-  s.written = read_u32(keep + n_calls, st);
-  s.claimed = read_u32(counts, st);
+  hipLaunchKernelGGL(runs::k_keep_out<struct bk_split_junction>, dim3(cdiv(n_calls, 256)), dim3(256), 0, st, rows, keep, n_calls, out);
+  s.written = runs::read_u32(keep + n_calls, st);
+  s.claimed = runs::read_u32(counts, st);
   *rows_out = out;
   *stats = s;
 }

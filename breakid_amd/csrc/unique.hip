@@ -11,6 +11,7 @@
 //            head, the head of a run that began in an earlier step is carried in a register; heads are counted, the longest run kept
 // Nothing hands out a slot: every write goes to an index the data alone decides, so two runs give the same bytes.
 #include "unique.h"
+#include "wave.h"
 #include <cstddef>
 
 namespace
@@ -21,12 +22,6 @@ static_assert(sizeof(struct bk_unique_support) == 16 && offsetof(struct bk_uniqu
 static_assert(UNIQUE_TILE == BK_WAVE, "k_uq_runs steps one wavefront at a time");
 
 constexpr int KEY_WORDS = 4;
-
-__device__ __forceinline__ uint64_t wave_or(uint64_t v)
-{
-  for (int d = 32; d; d >>= 1) v |= (uint64_t) __shfl_xor((unsigned long long) v, d, 64);
-  return v;
-}
 
 // d[j] |= word j of every row, d[KEY_WORDS + j] &= it (set to 0 and ~0 before); OR and AND commute: the result does not depend on who comes
 // first.  A grid of at most DIFFER_BLOCKS workgroups strides over the rows and folds its waves in LDS, so the global atomics number
