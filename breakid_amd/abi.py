@@ -51,6 +51,10 @@ LOCUS_PAIR = np.dtype([("tid_a", "<i4"), ("pos_a", "<u4"), ("tid_b", "<i4"), ("p
 LOCUS_SIM = np.dtype([("score", "<u4"), ("len", "<u4"), ("mism", "<u4"), ("run", "<u4"), ("diag", "<i4"), ("start", "<u4"), ("orient", "<u4"),
                       ("found", "<u4")])  # struct bk_locus_sim
 assert LOCUS_PAIR.itemsize == 16 and LOCUS_SIM.itemsize == 32
+SEQ_PROBE = np.dtype([("qlen", "<u4"), ("reversed", "<u4")])  # struct bk_seq_probe
+SEQ_HIT = np.dtype([("found", "<u4"), ("seq", "<i4"), ("orient", "<u4"), ("score", "<u4"), ("len", "<u4"), ("mism", "<u4"), ("run", "<u4"), ("q_start", "<u4"),
+                    ("s_start", "<u4"), ("n_seeds", "<u4"), ("seq2", "<i4"), ("score2", "<u4")])  # struct bk_seq_hit; s_start 0-based
+assert SEQ_PROBE.itemsize == 8 and SEQ_HIT.itemsize == 48
 REF_SITE = np.dtype([("tid", "<i4"), ("pos", "<u4")])  # struct bk_ref_site; pos 1-based
 SITE_CPLX = np.dtype([("covered", "<u4"), ("valid", "<u4"), ("gc", "<u4"), ("masked", "<u4"), ("mask_run", "<u4"), ("tri_total", "<u4"), ("tri_pairs", "<u4"),
                       ("tri_distinct", "<u4"), ("bp_period", "<u4"), ("bp_len", "<u4"), ("bp_start", "<u4"), ("max_period", "<u4"), ("max_len", "<u4"),
@@ -126,6 +130,10 @@ class Reads(C.Structure):  # bk_reads
 
 class RefSeq(C.Structure):  # bk_refseq
     _fields_ = [("n_segs", C.c_uint64)] + [(name, C.c_void_p) for name, _ in REFSEQ_COLS]
+
+
+class SeqPanel(C.Structure):  # bk_seq_panel
+    _fields_ = [("n_seqs", C.c_uint64), ("off", C.c_void_p), ("bases", C.c_void_p)]
 
 
 class TxModel(C.Structure):  # bk_txmodel

@@ -35,7 +35,7 @@ def build(verbose=False):
 
 EXPORTS = ["bk_init", "bk_prepare_process", "bk_free", "bk_last_error", "bk_set_stream", "bk_sync", "bk_get_stream", "bk_upload_records", "bk_records", "bk_exclude_regions", "bk_isize_stats",
            "bk_discordant_pairs", "bk_mask_and_cluster", "bk_split_evidence", "bk_cluster_summary",
-           "bk_split_breakpoints", "bk_normal_support", "bk_ref_support", "bk_genotype_call", "bk_clip_support", "bk_clip_reads", "bk_base_depth", "bk_clip_rescue", "bk_junctions", "bk_junction_sides", "bk_vcf_breakend_alt", "bk_evidence", "bk_unique_support", "bk_clip_consensus", "bk_junction_fit", "bk_locus_similarity", "bk_site_complexity", "bk_window_coverage", "bk_window_context", "bk_call_windows", "bk_fusion_frame", "bk_link_calls", "bk_locus_partners", "bk_call_partner_sites", "bk_fragment_sizes", "bk_fragment_bounds", "bk_known_calls", "bk_split_junctions", "bk_split_junction_counts", "bk_debug_split_junctions", "bk_cigar_gaps", "bk_cigar_gap_counts", "bk_clip_loci", "bk_clip_locus_counts", "bk_run", "bk_fetch", "bk_timing", "bk_timing_enable", "bk_timing_touched", "bk_group_stats", "bk_qname_hash", "bk_qname_check",
+           "bk_split_breakpoints", "bk_normal_support", "bk_ref_support", "bk_genotype_call", "bk_clip_support", "bk_clip_reads", "bk_base_depth", "bk_clip_rescue", "bk_junctions", "bk_junction_sides", "bk_vcf_breakend_alt", "bk_evidence", "bk_unique_support", "bk_clip_consensus", "bk_junction_fit", "bk_locus_similarity", "bk_sequence_match", "bk_site_complexity", "bk_window_coverage", "bk_window_context", "bk_call_windows", "bk_fusion_frame", "bk_link_calls", "bk_locus_partners", "bk_call_partner_sites", "bk_fragment_sizes", "bk_fragment_bounds", "bk_known_calls", "bk_split_junctions", "bk_split_junction_counts", "bk_debug_split_junctions", "bk_cigar_gaps", "bk_cigar_gap_counts", "bk_clip_loci", "bk_clip_locus_counts", "bk_run", "bk_fetch", "bk_timing", "bk_timing_enable", "bk_timing_touched", "bk_group_stats", "bk_qname_hash", "bk_qname_check",
            "bk_bam_open", "bk_bam_header", "bk_bam_decode", "bk_bam_close", "bk_bam_extract", "bk_bam_names_free", "bk_bam_reads", "bk_reads_free", "bk_bam_decode_device", "bk_bam_decode_device_part", "bk_bam_decode_device_ctx", "bk_bam_dev_free", "bk_feed_release_caches", "bk_debug_bgzf_inflate", "bk_debug_std_sort", "bk_debug_scan", "bk_debug_radix_sort", "bk_debug_prims_info", "bk_sort_forms", "bk_debug_sort_info", "bk_debug_ahc", "bk_debug_points", "bk_debug_points_groups", "bk_debug_cluster_info", "bk_debug_stream_info", "bk_debug_stream_blocks", "bk_debug_cigar", "bk_debug_vote", "bk_debug_region", "bk_shard_begin", "bk_shard_get_stats", "bk_shard_set_stats",
            "bk_shard_sd_local", "bk_shard_sd_finish", "bk_shard_buffer", "bk_shard_set_buffer", "bk_shard_group_sizes",
            "bk_shard_own_groups", "bk_shard_route_candidates", "bk_shard_group_keys", "bk_shard_route_pairs", "bk_shard_group_pairs", "bk_shard_bp_cov", "bk_shard_bp_vote", "bk_shard_bp_vote_slice", "bk_shard_bp_set_voted", "bk_shard_bp_depth", "bk_shard_bp_finish"]
@@ -86,6 +86,7 @@ def lib():
         L.bk_clip_consensus.argtypes = [vp, C.POINTER(abi.Reads), vp, C.c_uint64, C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
         L.bk_junction_fit.argtypes = [vp, C.POINTER(abi.RefSeq), vp, C.c_uint64, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(vp)]
         L.bk_locus_similarity.argtypes = [vp, C.POINTER(abi.RefSeq), vp, C.c_uint64, C.c_uint32, C.POINTER(vp)]
+        L.bk_sequence_match.argtypes = [vp, C.POINTER(abi.SeqPanel), vp, C.c_uint64, vp, C.c_uint32, C.c_uint32, C.POINTER(vp)]
         L.bk_site_complexity.argtypes = [vp, C.POINTER(abi.RefSeq), vp, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(vp)]
         L.bk_window_coverage.argtypes = [vp, vp, C.c_uint64, C.c_int, C.POINTER(vp)]
         L.bk_window_context.argtypes = [vp, vp, C.c_uint64, C.c_int, C.POINTER(vp)]
@@ -597,6 +598,31 @@ class Context:
             return np.zeros(0, abi.LOCUS_SIM)
         buf = (C.c_char * (n * abi.LOCUS_SIM.itemsize)).from_address(out.value)
         return np.frombuffer(buf, dtype=abi.LOCUS_SIM, count=n).copy()
+
+    def sequence_match(self, panel, probes, query, seed=12):
+        """The queries of `probes` searched in the sequences of `panel`, forward and reverse-complemented (bk_sequence_match).  panel:
+        (off, bases), uint64 [n_seqs + 1] from 0 and uint8 ASCII A C G T N, or a list of str / bytes, one per sequence; probes:
+        abi.SEQ_PROBE rows; query: uint8 [n, max_len], ASCII, as clip_consensus returns its bases.  Returns one abi.SEQ_HIT row per
+        probe."""
+        if isinstance(panel, (list, tuple)) and not (len(panel) == 2 and isinstance(panel[0], np.ndarray)):
+            seqs = [x.encode() if isinstance(x, str) else bytes(x) for x in panel]
+            panel = (np.cumsum([0] + [len(x) for x in seqs]), np.frombuffer(b"".join(seqs), np.uint8))
+        off = np.ascontiguousarray(panel[0], np.uint64)
+        bases = np.ascontiguousarray(panel[1], np.uint8)
+        probes = np.ascontiguousarray(probes, abi.SEQ_PROBE)
+        query = np.ascontiguousarray(query, np.uint8)
+        assert off.ndim == 1 and len(off) >= 1 and bases.ndim == 1 and probes.ndim == 1 and query.ndim == 2 and query.shape[0] == len(probes)
+        n, max_len = len(probes), query.shape[1]
+        t = abi.SeqPanel()
+        t.n_seqs = len(off) - 1
+        t.off = off.ctypes.data
+        t.bases = bases.ctypes.data if bases.size else None
+        out = C.c_void_p()
+        self._check(self.L.bk_sequence_match(self.h, C.byref(t), probes.ctypes.data if n else None, n, query.ctypes.data if n else None, max_len, int(seed), C.byref(out)))
+        if not n:
+            return np.zeros(0, abi.SEQ_HIT)
+        buf = (C.c_char * (n * abi.SEQ_HIT.itemsize)).from_address(out.value)
+        return np.frombuffer(buf, dtype=abi.SEQ_HIT, count=n).copy()
 
     def site_complexity(self, ref, sites, flank=32, max_period=6):
         """The reference window of `flank` bases either side of every site described by itself: soft-mask, trinucleotide counts and

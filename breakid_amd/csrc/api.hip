@@ -20,6 +20,7 @@
 #include "consensus.h"
 #include "jfit.h"
 #include "locsim.h"
+#include "seqmatch.h"
 #include "seqcx.h"
 #include "coverage.h"
 #include "context.h"
@@ -169,6 +170,9 @@ struct bk_ctx
   // locus similarity (bk_locus_similarity)
   LocsimBufs lsb;
   std::vector<struct bk_locus_sim> f_locsim;
+  // sequence match (bk_sequence_match)
+  SeqmatchBufs smb;
+  std::vector<struct bk_seq_hit> f_seqhit;
   // site complexity (bk_site_complexity)
   SeqcxBufs scb;
   std::vector<struct bk_site_cplx> f_sitecx;
@@ -1443,6 +1447,75 @@ int bk_locus_similarity(bk_ctx *ctx, const bk_refseq *ref, const struct bk_locus
     // touched: the pair row, the result row and L nibbles of each of the two windows
     if (ctx->timing && !ctx->timers.empty()) ctx->timers.back().touched = n * (sizeof(struct bk_locus_pair) + sizeof(struct bk_locus_sim) + L);
     *out = ctx->f_locsim.data();
+  });
+}
+
+// Short queries searched in a library of sequences (include/breakid_hip.h, seqmatch.hip)
+int bk_sequence_match(bk_ctx *ctx, const bk_seq_panel *panel, const struct bk_seq_probe *probes, uint64_t n, const uint8_t *query, uint32_t max_len, uint32_t seed,
+                      const struct bk_seq_hit **out)
+{
+  return guarded(ctx, [&] {
+    if (!panel || !out) throw bk_error(BK_ERR_ARG, "bk_sequence_match: null panel or out");
+    if (n && (!probes || !query)) throw bk_error(BK_ERR_ARG, "bk_sequence_match: null probes or query");
+    if (ctx->shard) throw bk_error(BK_ERR_ARG, "bk_sequence_match: sharded contexts (bk_shard_*) are not supported");
+    if (max_len < 1 || max_len > 256) throw bk_error(BK_ERR_ARG, "bk_sequence_match: max_len must be 1..256");
+    if (seed < 8 || seed > 16) throw bk_error(BK_ERR_ARG, "bk_sequence_match: seed must be 8..16");
+    if (n > 0x40000000ull) throw bk_error(BK_ERR_LIMIT, "bk_sequence_match: more than 2^30 probes");
+    const bk_seq_panel &t = *panel;
+    if (t.n_seqs > 0x100000ull) throw bk_error(BK_ERR_LIMIT, "bk_sequence_match: more than 2^20 sequences");
+    if (t.n_seqs && !t.off) throw bk_error(BK_ERR_ARG, "bk_sequence_match: null off");
+    const uint64_t total = t.n_seqs ? t.off[t.n_seqs] : 0;
+    if (total > 0x10000000ull) throw bk_error(BK_ERR_LIMIT, "bk_sequence_match: more than 2^28 panel bases");
+    if (t.n_seqs && t.off[0] != 0) throw bk_error(BK_ERR_ARG, "bk_sequence_match: off does not start at 0");
+    for (uint64_t s = 0; s < t.n_seqs; ++s)
+      if (t.off[s] > t.off[s + 1]) throw bk_error(BK_ERR_ARG, "bk_sequence_match: off does not ascend at sequence " + std::to_string(s));
+    if (total && !t.bases) throw bk_error(BK_ERR_ARG, "bk_sequence_match: null bases");
+    auto acgtn = [](uint8_t c) { return c == 'A' || c == 'C' || c == 'G' || c == 'T' || c == 'N'; };
+    for (uint64_t i = 0; i < total; ++i)
+      if (!acgtn(t.bases[i])) throw bk_error(BK_ERR_ARG, "bk_sequence_match: panel byte " + std::to_string(i) + " is outside ACGTN (lower case is the caller's to fold)");
+    for (uint64_t k = 0; k < n; ++k)
+    {
+      const struct bk_seq_probe &p = probes[k];
+      if (p.reversed > 1u) throw bk_error(BK_ERR_ARG, "bk_sequence_match: probe " + std::to_string(k) + " has reversed above 1");
+      if (p.qlen > max_len) throw bk_error(BK_ERR_ARG, "bk_sequence_match: probe " + std::to_string(k) + " has a qlen above max_len");
+      const uint8_t *q = query + k * max_len;
+      for (uint32_t j = 0; j < p.qlen; ++j)
+        if (!acgtn(q[j])) throw bk_error(BK_ERR_ARG, "bk_sequence_match: probe " + std::to_string(k) + " has a query byte outside ACGTN in column " + std::to_string(j));
+    }
+    SeqmatchBufs &b = ctx->smb;
+    struct bk_seq_hit *d_res = nullptr;
+    seqmatch_upload(t, probes, n, query, max_len, b, ctx->st);  // (outside the scope: it times the work on the device copies)
+    {
+      // (the two scopes inside push timers of their own, so the whole one ends by its index, not at timers.back(); the model needs
+      // the number of k-mers, which is known once the index has run)
+      struct Whole
+      {
+        bk_ctx *c;
+        size_t at;
+        ~Whole()
+        {
+          if (c->timing && at < c->timers.size()) (void) hipEventRecord(c->timers[at].b, c->st);
+        }
+      } whole{ctx, ctx->timers.size()};
+      ctx->tick("sequence_match", 0, true, 0);
+      uint64_t kmers = 0;
+      {
+        Scope s(ctx, "sequence_match_index");
+        kmers = seqmatch_index(t, seed, b, ctx->st);
+      }
+      const uint64_t by_index = seqmatch_touched_index(total, kmers, seed), by_probes = seqmatch_touched_probes(n, max_len);
+      if (ctx->timing && !ctx->timers.empty()) ctx->timers.back().bytes = ctx->timers.back().touched = by_index;
+      {
+        Scope s(ctx, "sequence_match_probes", by_probes, by_probes);
+        seqmatch_probes(t, n, max_len, seed, b, ctx->st, &d_res);
+      }
+      if (ctx->timing && whole.at < ctx->timers.size()) ctx->timers[whole.at].bytes = ctx->timers[whole.at].touched = by_index + by_probes;
+      if (bk_debug("seqmatch"))
+        fprintf(stderr, "bk_sequence_match: %llu probes, %llu sequences, %llu bases, %llu k-mers of %u, %u sort passes\n", (unsigned long long) n, (unsigned long long) t.n_seqs,
+                (unsigned long long) total, (unsigned long long) kmers, seed, seqmatch_passes(seed));
+    }
+    rows_to_host(ctx, d_res, n, ctx->f_seqhit);
+    *out = ctx->f_seqhit.data();
   });
 }
 

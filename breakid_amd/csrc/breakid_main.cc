@@ -1808,11 +1808,149 @@ static void cigar_gap_calls(const Options &o, const Sample &tumor, const vector<
             << " calls, " << rows.size() << " written" << std::endl;
 }
 
+// ---- -panel: the sequences a junction sequence is searched in -----------------------------------------------------------------------------
+// A FASTA: a `>` line names a sequence by its first word, bases are upper-cased, every letter other than A C G T becomes N, blank lines
+// are skipped.  Sequence data before a header, a duplicate name and a sequence without bases end the run with the line's number.
+struct SeqLibrary
+{
+  vector<string> names;
+  vector<uint64_t> off{0};
+  string bases;
+};
+
+static SeqLibrary read_panel_fasta(const string &path)
+{
+  SeqLibrary lib;
+  std::ifstream in(path.c_str());
+  std::set<string> seen;
+  auto stop = [&](long line, const string &what) {
+    std::cerr << "Error: panel file " << path << " line " << line << ": " << what << std::endl;
+    exit(1);
+  };
+  string line;
+  long no = 0, header_at = 0;
+  auto close_sequence = [&]() {
+    if (lib.names.empty()) return;
+    if (lib.bases.size() == lib.off.back()) stop(header_at, "sequence " + lib.names.back() + " has no bases");
+    lib.off.push_back(lib.bases.size());
+  };
+  while (std::getline(in, line))
+  {
+    ++no;
+    const size_t a = line.find_first_not_of(" \t\r\n\v\f"), b = line.find_last_not_of(" \t\r\n\v\f");
+    if (a == string::npos) continue;
+    line = line.substr(a, b - a + 1);
+    if (line[0] == '>')
+    {
+      close_sequence();
+      const size_t w = line.find_first_not_of(" \t", 1);
+      const string name = w == string::npos ? "" : line.substr(w, line.find_first_of(" \t", w) - w);
+      if (name.empty()) stop(no, "a header without a name");
+      if (!seen.insert(name).second) stop(no, "duplicate sequence name " + name);
+      lib.names.push_back(name);
+      header_at = no;
+      continue;
+    }
+    if (lib.names.empty()) stop(no, "sequence data before the first header");
+    for (const char ch : line)
+    {
+      const char u = (char) toupper((unsigned char) ch);
+      lib.bases.push_back(u == 'A' || u == 'C' || u == 'G' || u == 'T' ? u : 'N');
+    }
+  }
+  close_sequence();
+  return lib;
+}
+
+// ---- -lociseq: the junction sequence of every written clip locus ------------------------------------------------------------------------
+// Each written row is the site (tid, pos, 0, dir); bk_clip_reads lists the reads there, one pass over the file brings their alignments
+// back with the bases, bk_clip_consensus piles them up with -q, -minclip, -conslen and the vote's own minimum depth.  As with
+// -consensus the reads are chosen by name and bk_clip_consensus has no SA condition, so Seq_N can differ from TopReads.  With -panel one
+// call of bk_sequence_match takes the consensus as it lies, reversed = dir.
+static void clip_locus_sequences(const Options &o, const Sample &tumor, const vector<ClipLocusRow> &rows, const struct bk_clip_locus *all, uint64_t n, const SeqLibrary &lib)
+{
+  vector<LocusSeq> seqs(rows.size());
+  uint64_t with_seq = 0, with_tail = 0, with_hit = 0, pairs = 0;
+  if (!rows.empty())
+  {
+    vector<struct bk_clip_site> sites;
+    for (const ClipLocusRow &r : rows) sites.push_back(bk_clip_site{r.l.tid, r.l.pos, 0u, r.l.dir});
+    const uint32_t *counts = nullptr;
+    const struct bk_clip_read *cr = nullptr;
+    const uint64_t *off = nullptr;
+    int rc = bk_clip_reads(tumor.ctx, sites.data(), sites.size(), o.qual, (int) o.min_clip, &counts, &cr, &off);
+    if (rc != BK_OK) die(tumor, rc);
+    std::set<std::pair<uint64_t, uint32_t>> seen;
+    vector<bk_read_key> keys;
+    for (uint64_t i = 0; i < off[sites.size()]; ++i)
+      if (seen.emplace(cr[i].qhash, cr[i].qcheck).second) keys.push_back(bk_read_key{cr[i].qhash, cr[i].qcheck, 0});
+    bk_reads reads;
+    char err[512] = "";
+    if (bk_bam_reads(o.inp_file.c_str(), keys.data(), keys.size(), &reads, err, sizeof err) != BK_OK)
+    {
+      std::cerr << "Error: cannot read the clipped reads back from " << o.inp_file << ": " << err << std::endl;
+      exit(1);
+    }
+    const struct bk_consensus *crow = nullptr;
+    const uint8_t *cbases = nullptr;
+    rc = bk_clip_consensus(tumor.ctx, &reads, sites.data(), sites.size(), o.qual, (int) o.min_clip, (uint32_t) o.conslen, CONSENSUS_MIN_DEPTH, &crow, &cbases, nullptr);
+    bk_reads_free(&reads);
+    if (rc != BK_OK) die(tumor, rc);
+    for (size_t k = 0; k < rows.size(); ++k)
+    {
+      LocusSeq &x = seqs[k];
+      const char *col = (const char *) cbases + k * (size_t) o.conslen;
+      x.side.c = crow[k];
+      x.side.seq.assign(col, x.side.c.len);
+      if (x.side.c.len)
+      {
+        while (x.tail_len < x.side.c.len && col[x.tail_len] == col[0]) ++x.tail_len;
+        x.tail = string(1, col[0]) + std::to_string(x.tail_len);
+        ++with_seq;
+        with_tail += x.tail_len >= 10;
+      }
+      if (sites[k].dir == 1u) std::reverse(x.side.seq.begin(), x.side.seq.end());
+    }
+    if (o.panel())
+    {
+      vector<struct bk_seq_probe> probes;
+      for (size_t k = 0; k < rows.size(); ++k) probes.push_back(bk_seq_probe{crow[k].len, sites[k].dir});
+      const bk_seq_panel panel{lib.names.size(), lib.off.data(), (const uint8_t *) lib.bases.data()};
+      const struct bk_seq_hit *hits = nullptr;
+      rc = bk_sequence_match(tumor.ctx, &panel, probes.data(), probes.size(), cbases, (uint32_t) o.conslen, (uint32_t) o.panelseed, &hits);
+      if (rc != BK_OK) die(tumor, rc);
+      std::map<uint64_t, size_t> row_of;  // by row of the returned table
+      for (size_t k = 0; k < rows.size(); ++k)
+      {
+        seqs[k].hit = hits[k];
+        with_hit += hits[k].found;
+        row_of[rows[k].index] = k;
+      }
+      for (size_t k = 0; k < rows.size(); ++k)
+      {
+        const struct bk_clip_locus &l = rows[k].l;
+        if (!(l.flags & 1u) || !row_of.count(l.mate)) continue;  // (a mate that is written: the Mate column names it)
+        const size_t m = row_of[l.mate];
+        const struct bk_seq_hit &own = seqs[k].hit, &other = seqs[m].hit;
+        if (!own.found || !other.found || own.seq != other.seq || own.orient != other.orient || l.dir == rows[m].l.dir) continue;
+        const struct bk_seq_hit &left = l.dir == BK_CLIP_LEFT ? own : other, &right = l.dir == BK_CLIP_LEFT ? other : own;
+        const long long span = own.orient ? (long long) left.s_start + left.len - (long long) right.s_start : (long long) right.s_start + right.len - (long long) left.s_start;
+        seqs[k].pair_span = std::to_string(span);
+        pairs += l.dir == BK_CLIP_LEFT;
+      }
+    }
+  }
+  write_lociseq_file(o, rows, all, n, seqs, lib.names);
+  std::cout << "lociseq: " << rows.size() << " loci, " << with_seq << " with a sequence, " << with_tail << " with a tail of 10 or more" << std::endl;
+  if (o.panel())
+    std::cout << "panel: " << lib.names.size() << " sequences, " << lib.bases.size() << " bases, " << with_hit << " loci with a hit, " << pairs << " pairs on one sequence" << std::endl;
+}
+
 // ---- -cliploci: soft-clip pile-ups over the whole table ---------------------------------------------------------------------------------
 // One call of bk_clip_loci on the sample's own table with the run's voted rows as the claiming calls (-q is its mapq_min, -minclip its
 // min_clip; -x applies by itself, because the table holds the kept records); the loci that no voted row claims get the depth at their
 // position (one call of bk_base_depth) and the gene there.  It runs behind every other stage and reads what they left: no other file changes.
-static void clip_locus_calls(const Options &o, const Sample &tumor, const vector<Txpt> &txpts)
+static void clip_locus_calls(const Options &o, const Sample &tumor, const vector<Txpt> &txpts, const SeqLibrary &lib)
 {
   const struct bk_clip_locus *loci = nullptr;
   uint64_t n = 0, counts[8] = {};
@@ -1846,6 +1984,11 @@ static void clip_locus_calls(const Options &o, const Sample &tumor, const vector
   write_cliploci_files(o, rows, loci, n);
   std::cout << "cliploci: " << counts[1] << " records eligible, " << counts[2] << " events, " << counts[3] << " beyond a contig's end, " << counts[4] << " exact, " << counts[5]
             << " loci, " << counts[6] << " with a mutual partner, " << n - rows.size() << " claimed by a voted call, " << rows.size() << " written" << std::endl;
+  if (o.lociseq)
+  {
+    const vector<struct bk_clip_locus> table(loci, loci + n);  // (the library's rows are its own until the next call)
+    clip_locus_sequences(o, tumor, rows, table.data(), n, lib);
+  }
 }
 
 // write_enspan_params (:1170-1182); an option that changes what is called adds its line behind the reference's
@@ -1890,6 +2033,9 @@ static void write_params(const Options &o, double w)
   if (o.cliploci) p << "cliploci_tol\t" << o.locitol << std::endl;
   if (o.cliploci) p << "cliploci_pair\t" << o.locipair << std::endl;
   if (o.cliploci) p << "cliploci_min_support\t" << o.locisupport << std::endl;
+  if (o.lociseq) p << "lociseq\t" << o.conslen << std::endl;
+  if (o.panel()) p << "panel_file\t" << o.panel_file << std::endl;
+  if (o.panel()) p << "panel_seed\t" << o.panelseed << std::endl;
 }
 
 // BreakID.cc:175-191.  scan_pairs_count and after_cluster_count are never updated by the reference (always 0);
@@ -1934,6 +2080,8 @@ int main(int argc, char *argv[])
   decode_tumor(o, tumor, exclusion);
   KnownPanel panel;  // (read against the file's reference list before the stages run: a line that ends the run does so early)
   if (o.known()) panel = read_known_bedpe(o.known_file, tumor.names, tumor.lens, tumor.nt);
+  SeqLibrary library;  // (read before the stages run: a line that ends the run does so early)
+  if (o.panel()) library = read_panel_fasta(o.panel_file);
   if (!opens(o.nib_dir + "/ref_names.txt"))
   {
     std::cerr << "Error: cannot open reference names file.\n";
@@ -1991,7 +2139,7 @@ int main(int argc, char *argv[])
   }
   if (o.junctions) split_junction_calls(o, tumor, txpts);
   if (o.gaps) cigar_gap_calls(o, tumor, txpts);
-  if (o.cliploci) clip_locus_calls(o, tumor, txpts);
+  if (o.cliploci) clip_locus_calls(o, tumor, txpts, library);
   write_params(o, run.w);
   const clock_t end = clock();
   std::cout << "the fusion process of file " << o.inp_file << "  costs time: " << (end - start) / double(CLOCKS_PER_SEC) << " seconds" << std::endl;

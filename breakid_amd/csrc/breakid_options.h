@@ -62,6 +62,9 @@ int bk_cigar_gap_counts(bk_ctx *records, uint64_t out[8]) __attribute__((weak));
 // -cliploci (soft-clip pile-ups over the whole table; bk_base_depth is listed with -clip)
 int bk_clip_loci(bk_ctx *records, bk_ctx *calls, int mapq_min, int min_clip, uint32_t tol, uint32_t pair_dist, uint32_t min_reads, const struct bk_clip_locus **out, uint64_t *count) __attribute__((weak));
 int bk_clip_locus_counts(bk_ctx *records, uint64_t out[8]) __attribute__((weak));
+// -panel (the junction sequence of a clip locus searched in the sequences of a FASTA)
+int bk_sequence_match(bk_ctx *ctx, const bk_seq_panel *panel, const struct bk_seq_probe *probes, uint64_t n, const uint8_t *query, uint32_t max_len, uint32_t seed,
+                      const struct bk_seq_hit **out) __attribute__((weak));
 // -complexity
 int bk_site_complexity(bk_ctx *ctx, const bk_refseq *ref, const struct bk_ref_site *sites, uint64_t n, uint32_t flank, uint32_t max_period, const struct bk_site_cplx **out) __attribute__((weak));
 // -dedup
@@ -135,15 +138,18 @@ static const char *HELP =
      \t -cliploci  \t also call the places where soft-clipped reads without an SA tag pile up, with or without discordant pairs: mobile-element and viral insertion sites (*_cliploci.txt; *_cliploci.bedpe with -bedpe; -minclip and -q apply)  \n \
      \t -locitol   \t bases up to which two clip positions of one side are one locus, 0 to 100 (with -cliploci)  [2]\n \
      \t -locipair  \t bases up to which a left-clipped and a right-clipped locus may lie from a blunt junction and still face each other, 0 to 100000 (with -cliploci)  [50]\n \
-     \t -locisupport \t distinct reads a locus needs, 1 to 1000000 (with -cliploci)  [3]\n ";
+     \t -locisupport \t distinct reads a locus needs, 1 to 1000000 (with -cliploci)  [3]\n \
+     \t -lociseq   \t vote the clipped bases of every written locus into its junction sequence, with the length of the homopolymer tail at the junction (with -cliploci; *_cliploci_seq.txt; -conslen applies)  \n \
+     \t -panel     \t name the sequence of a FASTA (mobile-element consensus sequences, a viral genome) that each junction sequence continues into: strand, position, the runner-up and the insert length a facing pair implies (with -lociseq; further columns of *_cliploci_seq.txt)  \n \
+     \t -panelseed \t exact bases a junction sequence must share with a panel sequence to be compared with it, 8 to 16 (with -panel)  [12]\n ";
 
 struct Options
 {
-  std::string inp_file, out_file, nib_dir, normal_file, exclude_file, known_file, build = "hg19";
+  std::string inp_file, out_file, nib_dir, normal_file, exclude_file, known_file, panel_file, build = "hg19";
   int qual = 20, device = 0, n_gpus = 0, transport = BK_TRANSPORT_AUTO;  // -gpus N: one sample over N GPUs (include/breakid_multi.h)
   bool fast = false, all = false;                                        // -all: no gene-pair and repeat filter (the _fusion_all files)
-  bool genotype = false, vcf = false, evidence = false, clip = false, dedup = false, consensus = false, homology = false, similar = false, coverage = false, frame = false, link = false, partners = false, fragsize = false, bedpe = false, context = false, junctions = false, complexity = false, gaps = false, cliploci = false;
-  bool anchor_given = false, minclip_given = false, clipsupport_given = false, conslen_given = false, homshift_given = false, homins_given = false, simflank_given = false, covflank_given = false, linkdist_given = false, knownslop_given = false, ctxflank_given = false, jsupport_given = false, jtol_given = false, cplxflank_given = false, cplxperiod_given = false, mingap_given = false, gapanchor_given = false, gaptol_given = false, gapsupport_given = false, locitol_given = false, locipair_given = false, locisupport_given = false;
+  bool genotype = false, vcf = false, evidence = false, clip = false, dedup = false, consensus = false, homology = false, similar = false, coverage = false, frame = false, link = false, partners = false, fragsize = false, bedpe = false, context = false, junctions = false, complexity = false, gaps = false, cliploci = false, lociseq = false;
+  bool anchor_given = false, minclip_given = false, clipsupport_given = false, conslen_given = false, homshift_given = false, homins_given = false, simflank_given = false, covflank_given = false, linkdist_given = false, knownslop_given = false, ctxflank_given = false, jsupport_given = false, jtol_given = false, cplxflank_given = false, cplxperiod_given = false, mingap_given = false, gapanchor_given = false, gaptol_given = false, gapsupport_given = false, locitol_given = false, locipair_given = false, locisupport_given = false, panelseed_given = false;
   long anchor = 10;                      // -anchor: bases a reference read must cover on either side of the breakpoint base
   long min_clip = 10, clip_support = 3;  // -minclip: shortest clip that counts; -clipsupport: reads at one position a rescued side needs
   long conslen = 64;                     // -conslen: longest junction sequence per side
@@ -157,8 +163,10 @@ struct Options
   long cplxflank = 32, cplxperiod = 6;   // -cplxflank, -cplxperiod: flank and max_period of bk_site_complexity
   long mingap = 20, gapanchor = 10, gaptol = 2, gapsupport = 3;  // -mingap, -gapanchor, -gaptol, -gapsupport: min_len, anchor, tol and min_reads of bk_cigar_gaps
   long locitol = 2, locipair = 50, locisupport = 3;  // -locitol, -locipair, -locisupport: tol, pair_dist and min_reads of bk_clip_loci
+  long panelseed = 12;                   // -panelseed: seed of bk_sequence_match
   bool multi() const { return n_gpus >= 1; }  // the sharded run
   bool known() const { return !known_file.empty(); }
+  bool panel() const { return !panel_file.empty(); }
   bool with_normal() const { return !normal_file.empty(); }
   bool exclude() const { return !exclude_file.empty(); }
 };
@@ -207,6 +215,8 @@ static void check_options(const Options &o)
   const Feature complexity{"-complexity", o.complexity, false, bk_site_complexity != nullptr};
   const Feature gaps{"-gaps", o.gaps, false, bk_cigar_gaps && bk_cigar_gap_counts && bk_base_depth};
   const Feature cliploci{"-cliploci", o.cliploci, false, bk_clip_loci && bk_clip_locus_counts && bk_base_depth};
+  const Feature lociseq{"-lociseq", o.lociseq, false, bk_clip_consensus && bk_clip_reads};
+  const Feature panel{"-panel", o.panel(), false, bk_sequence_match != nullptr};
   const Feature consensus{"-consensus", o.consensus, false, bk_clip_consensus && bk_clip_reads && bk_evidence && bk_junctions && bk_junction_sides};
   const Feature clip{"-clip", o.clip, false, bk_clip_support && bk_clip_reads && bk_base_depth && bk_clip_rescue && bk_junctions && bk_junction_sides};
   const Feature exclude{"-x", o.exclude(), true, bk_exclude_regions && bk_multi_run_ex && bk_multi_run_bam_ex && bk_multi_excluded};
@@ -227,7 +237,7 @@ static void check_options(const Options &o)
       rule((o.homshift_given || o.homins_given) && !o.homology, "-homshift and -homins need -homology."),
       rule(o.homology && !o.consensus, "-homology needs -consensus."), gpus(homology), library(homology),
       rule(o.homology && !(in_range(o.homshift, 0, 64) && in_range(o.homins, 0, 64)), "-homshift and -homins must be numbers from 0 to 64."),
-      rule(o.conslen_given && !o.consensus, "-conslen needs -consensus."),
+      rule(o.conslen_given && !o.consensus && !o.lociseq, "-conslen needs -consensus."),
       gpus(consensus), library(consensus), rule(o.consensus && !in_range(o.conslen, 1, 256), "-conslen must be a number from 1 to 256."),
       rule(o.consensus && !in_range(o.min_clip, 1, int_max), "-minclip must be a number from 1 to 2147483647."),
       rule((o.minclip_given && !o.clip && !o.consensus && !o.cliploci) || (o.clipsupport_given && !o.clip), "-minclip and -clipsupport need -clip."),
@@ -267,6 +277,11 @@ static void check_options(const Options &o)
       rule(o.cliploci && !in_range(o.locitol, 0, 100), "-locitol must be a number from 0 to 100."),
       rule(o.cliploci && !in_range(o.locipair, 0, 100000), "-locipair must be a number from 0 to 100000."),
       rule(o.cliploci && !in_range(o.locisupport, 1, 1000000), "-locisupport must be a number from 1 to 1000000."), library(cliploci),
+      rule(o.lociseq && !o.cliploci, "-lociseq needs -cliploci."), gpus(lociseq), library(lociseq),
+      rule(o.lociseq && !in_range(o.conslen, 1, 256), "-conslen must be a number from 1 to 256."),
+      rule((o.panel() || o.panelseed_given) && !o.lociseq, "-panel and -panelseed need -lociseq."), rule(o.panelseed_given && !o.panel(), "-panelseed needs -panel."), gpus(panel),
+      rule(o.panel() && !in_range(o.panelseed, 8, 16), "-panelseed must be a number from 8 to 16."), library(panel),
+      {Refusal::OPEN, panel.set && !opens(o.panel_file), "panel file: " + o.panel_file},
   };
   for (const Refusal &r : refusals)
   {
@@ -298,6 +313,7 @@ static Options parse_options(int argc, char *argv[])
                                      {"complexity", 0, 0, 43}, {"cplxflank", 1, 0, 44}, {"cplxperiod", 1, 0, 45},
                                      {"gaps", 0, 0, 46}, {"mingap", 1, 0, 47}, {"gapanchor", 1, 0, 48}, {"gaptol", 1, 0, 49}, {"gapsupport", 1, 0, 50},
                                      {"cliploci", 0, 0, 51}, {"locitol", 1, 0, 52}, {"locipair", 1, 0, 53}, {"locisupport", 1, 0, 54},
+                                     {"lociseq", 0, 0, 55}, {"panel", 1, 0, 56}, {"panelseed", 1, 0, 57},
                                      {"f", 0, 0, 5},  // (-f used to complete to -fast alone; it still means it beside -frame)
                                      {0, 0, 0, 0}};
   Options o;
@@ -366,6 +382,9 @@ static Options parse_options(int argc, char *argv[])
     case 52: number(o.locitol, o.locitol_given); break;
     case 53: number(o.locipair, o.locipair_given); break;
     case 54: number(o.locisupport, o.locisupport_given); break;
+    case 55: o.lociseq = true; break;
+    case 56: o.panel_file = optarg; break;
+    case 57: number(o.panelseed, o.panelseed_given); break;
     default: std::cerr << "Error: cannot parse arguments.\n"; exit(1);
     }
   }

@@ -840,6 +840,29 @@ struct ClipLocusRow
 };
 static const char *CLIPLOCI_COLUMNS =
     "Locus\tChr\tPos\tSide\tReads\tRows\tExact\tTopReads\tFwd\tRev\tMeanMQ\tSpan\tMaxClip\tMeanClip\tOrphans\tImproper\tMate\tMatePos\tMateReads\tMateOff\tMutual\tDepth\tGene";
+// the line of row r in <prefix>_cliploci.txt without its newline (all: the returned table of n rows, in which a row's mate is looked up)
+static string cliploci_line(const ClipLocusRow &r, const struct bk_clip_locus *all, uint64_t n)
+{
+  std::ostringstream table;
+  char mq[32], mc[32];
+  const struct bk_clip_locus &l = r.l;
+  const bool facing = l.flags & 1u, mate_written = facing && l.mate < n && all[l.mate].claim == 0xFFFFFFFFu;
+  snprintf(mq, sizeof mq, "%.1f", (double) l.mapq_sum / (double) l.n_rows);  // (a locus has at least one row)
+  snprintf(mc, sizeof mc, "%.1f", (double) l.clip_sum / (double) l.n_rows);
+  table << "cl" << r.index << "\t" << r.chr << "\t" << l.pos << "\t" << (l.dir ? "R" : "L") << "\t" << l.n_reads << "\t" << l.n_rows << "\t" << l.n_exact << "\t" << l.top_reads << "\t"
+        << l.n_fwd << "\t" << l.n_rev << "\t" << mq << "\t" << l.lo_pos << "-" << l.hi_pos << "\t" << l.max_clip << "\t" << mc << "\t" << l.n_orphan << "\t" << l.n_improper << "\t";
+  if (mate_written)
+    table << "cl" << l.mate;
+  else
+    table << ".";
+  if (facing)
+    table << "\t" << l.mate_pos << "\t" << l.mate_reads << "\t" << l.mate_off;
+  else
+    table << "\t.\t.\t.";
+  table << "\t" << ((l.flags & 2u) ? 1 : 0) << "\t" << r.depth << "\t" << r.gene;
+  return table.str();
+}
+
 // all: the returned table (n rows), in which a row's mate is looked up
 static void write_cliploci_files(const Options &o, const vector<ClipLocusRow> &rows, const struct bk_clip_locus *all, uint64_t n)
 {
@@ -848,24 +871,11 @@ static void write_cliploci_files(const Options &o, const vector<ClipLocusRow> &r
   std::ofstream table((o.out_file + "_cliploci.txt").c_str()), bedpe;
   if (o.bedpe) bedpe.open((o.out_file + "_cliploci.bedpe").c_str());
   table << CLIPLOCI_COLUMNS << "\n";
-  char mq[32], mc[32];
   for (const ClipLocusRow &r : rows)
   {
     const struct bk_clip_locus &l = r.l;
-    const bool facing = l.flags & 1u, mate_written = facing && l.mate < n && all[l.mate].claim == 0xFFFFFFFFu;
-    snprintf(mq, sizeof mq, "%.1f", (double) l.mapq_sum / (double) l.n_rows);  // (a locus has at least one row)
-    snprintf(mc, sizeof mc, "%.1f", (double) l.clip_sum / (double) l.n_rows);
-    table << "cl" << r.index << "\t" << r.chr << "\t" << l.pos << "\t" << (l.dir ? "R" : "L") << "\t" << l.n_reads << "\t" << l.n_rows << "\t" << l.n_exact << "\t" << l.top_reads << "\t"
-          << l.n_fwd << "\t" << l.n_rev << "\t" << mq << "\t" << l.lo_pos << "-" << l.hi_pos << "\t" << l.max_clip << "\t" << mc << "\t" << l.n_orphan << "\t" << l.n_improper << "\t";
-    if (mate_written)
-      table << "cl" << l.mate;
-    else
-      table << ".";
-    if (facing)
-      table << "\t" << l.mate_pos << "\t" << l.mate_reads << "\t" << l.mate_off;
-    else
-      table << "\t.\t.\t.";
-    table << "\t" << ((l.flags & 2u) ? 1 : 0) << "\t" << r.depth << "\t" << r.gene << "\n";
+    const bool mate_written = (l.flags & 1u) && l.mate < n && all[l.mate].claim == 0xFFFFFFFFu;
+    table << cliploci_line(r, all, n) << "\n";
     if (bedpe.is_open() && l.dir == BK_CLIP_LEFT && (l.flags & 2u) && mate_written)
     {
       const struct bk_clip_locus &m = all[l.mate];
@@ -873,6 +883,46 @@ static void write_cliploci_files(const Options &o, const vector<ClipLocusRow> &r
       bedpe << r.chr << "\t" << (long long) l.pos - 1 << "\t" << l.pos << "\t" << r.chr << "\t" << (long long) m.pos - 1 << "\t" << m.pos << "\t" << (sample.empty() ? "." : sample) << "\t"
             << reads << "\t+\t-\tcl" << r.index << "\tinsertion_site\t0\t" << reads << "\n";
     }
+  }
+}
+
+// -lociseq: <prefix>_cliploci_seq.txt, the rows of <prefix>_cliploci.txt in its order with the junction sequence of each behind them: the
+// columns of -consensus for the one side a locus has, and the base of column 0 with the number of leading columns equal to it (the
+// homopolymer next to the junction; "." without a column).  With -panel the hit of bk_sequence_match behind that: the panel sequence's
+// name, the strand, the segment (Pn_QStart 1-based in Seq as printed, Pn_Start .. Pn_End 1-based and inclusive on the panel
+// sequence), the seeds, the runner-up, and for a row whose Mate is written and lies on the same sequence and strand the panel bases
+// from the LEFT row's first to the RIGHT row's last (+; mirrored for -): what the pair implies for the inserted length.
+static const char *LOCISEQ_COLUMNS = "\tSeq_N\tSeq_Len\tSeq_Agree\tSeq\tSeq_Tail";
+static const char *PANEL_COLUMNS = "\tPn_Name\tPn_Strand\tPn_Score\tPn_Len\tPn_Mism\tPn_Run\tPn_QStart\tPn_Start\tPn_End\tPn_Seeds\tPn_Second\tPn_Score2\tPn_PairSpan";
+struct LocusSeq
+{
+  ConsensusSide side;
+  string tail = ".";
+  uint32_t tail_len = 0;
+  struct bk_seq_hit hit = {0, -1, 0, 0, 0, 0, 0, 0, 0, 0, -1, 0};
+  string pair_span = ".";
+};
+
+static void write_lociseq_file(const Options &o, const vector<ClipLocusRow> &rows, const struct bk_clip_locus *all, uint64_t n, const vector<LocusSeq> &seqs,
+                               const vector<string> &panel_names)
+{
+  std::ofstream table((o.out_file + "_cliploci_seq.txt").c_str());
+  table << CLIPLOCI_COLUMNS << LOCISEQ_COLUMNS << (o.panel() ? PANEL_COLUMNS : "") << "\n";
+  for (size_t k = 0; k < rows.size(); ++k)
+  {
+    const LocusSeq &x = seqs[k];
+    table << cliploci_line(rows[k], all, n) << "\t" << x.side.c.n_reads << "\t" << x.side.c.len << "\t" << x.side.agree() << "\t" << (x.side.seq.empty() ? "." : x.side.seq) << "\t"
+          << x.tail;
+    if (o.panel())
+    {
+      const struct bk_seq_hit &h = x.hit;
+      if (h.found)
+        table << "\t" << panel_names[h.seq] << "\t" << (h.orient ? "-" : "+") << "\t" << h.score << "\t" << h.len << "\t" << h.mism << "\t" << h.run << "\t" << h.q_start + 1 << "\t"
+              << h.s_start + 1 << "\t" << h.s_start + h.len << "\t" << h.n_seeds << "\t" << (h.seq2 >= 0 ? panel_names[h.seq2] : string(".")) << "\t" << h.score2 << "\t" << x.pair_span;
+      else
+        table << "\t.\t.\t.\t.\t.\t.\t.\t.\t.\t0\t.\t.\t.";
+    }
+    table << "\n";
   }
 }
 

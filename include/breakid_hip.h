@@ -573,6 +573,73 @@ struct bk_locus_sim  { uint32_t score, len, mism, run; int32_t diag; uint32_t st
  * or 2^20 segments, looked at before any array is read.  n == 0 is no error, and neither is n_segs == 0 (every row is then zero). */
 int bk_locus_similarity(bk_ctx *ctx, const bk_refseq *ref, const struct bk_locus_pair *pairs, uint64_t n, uint32_t flank, const struct bk_locus_sim **out);
 
+/* ---- sequence match: short queries searched in a library of sequences the caller supplies -----------------------------------------
+ * bk_junction_fit and bk_locus_similarity read the sample's own reference at positions the caller knows.  bk_sequence_match answers
+ * the other question: which sequence of a panel (Alu / L1 / SVA consensus sequences, a viral genome, a vector) does a read-derived
+ * sequence such as a clip consensus continue into, on which strand and where.  The contract below describes results only; how they
+ * are found (a k-mer index, seeded ungapped extension) is the library's business, and a brute force over every diagonal gives the
+ * same bytes.  All comparisons in signed 64-bit.
+ * Panel: host memory, uploaded and indexed per call.  Sequence s is P_s = bases[off[s] .. off[s + 1]), ASCII, only A C G T N (lower
+ * case is the caller's to fold); len_s = off[s + 1] - off[s].  A sequence's neighbours in `bases` are not part of it. */
+typedef struct bk_seq_panel {
+  uint64_t n_seqs;
+  const uint64_t *off;          /* n_seqs + 1, in bases; off[0] == 0 */
+  const uint8_t *bases;
+} bk_seq_panel;
+/* Probe k has qlen <= max_len bytes at query[k * max_len ..], ASCII A C G T N: the layout and the stride of `bases` from
+ * bk_clip_consensus (with qlen = len).  Its string is q[i] = query[k * max_len + i], or query[k * max_len + qlen - 1 - i] when
+ * `reversed` is set: that is for a RIGHT site, whose columns count backwards, so that q reads in BAM orientation and one call's
+ * output is the next call's input without repacking (reversed = dir). */
+struct bk_seq_probe { uint32_t qlen, reversed; };   /* 8 bytes */
+/* Orientations: q_0 = q, q_1[i] = comp(q[qlen - 1 - i]), comp(N) = N.
+ * A diagonal (s, o, d) holds the cells i with 0 <= i < qlen and 0 <= i + d < len_s.  A cell matches iff q_o[i] is one of A C G T and
+ * equals P_s[i + d]; N never matches, on either side.
+ * A run is a maximal stretch of consecutive matching cells of one diagonal.  A diagonal is seeded when it has a run of at least `seed`
+ * cells.  n_seeds = the runs of at least `seed` cells over all diagonals of all sequences in both orientations (saturating at
+ * 2^32 - 1).  found = 1 iff n_seeds > 0; otherwise the row is all zeros but seq = seq2 = -1.
+ * Best segment, over the seeded diagonals only: a segment (i0, n), n >= 1, of a diagonal scores matches - 2 * mismatches, every
+ * cell that does not match being a mismatch: the rule of bk_locus_similarity, and its one pass, a running sum of +1 / -2 that
+ * restarts wherever it is <= 0, every matching cell offering (sum, length since the restart).  The winner has the largest key
+ * (score, -n, -s, -o, -(i0 + d), -i0): the highest score, then the shortest, the smallest sequence index, orientation 0, the smallest
+ * start on the panel, the smallest i0.  Reported of it: seq = s, orient = o, score, len = n, mism = (len - score) / 3,
+ * s_start = i0 + d (0-based and forward on the panel sequence in both orientations), q_start = the segment's first base in q (i0 for
+ * orientation 0, qlen - i0 - n for orientation 1).
+ * run = the longest run on any seeded diagonal.  score2 = the best segment score over the seeded diagonals of sequences other than
+ * seq, seq2 = the smallest such index that reaches it; 0 and -1 without one.  score2 is what tells "AluYa5 or AluYb8" from "HPV16
+ * and nothing else".
+ * Hand examples, seed 12, checked with the brute force of tests/seqmatchcases.py.  Panel:
+ *   0  GGCCGGGCGCGGTGGCTCACGCCTGTAATCCCAGCA
+ *   1  TTGACCATGGCTAGCATCGGATTACAGGCGTGAGCCACCAAAAAAAAAAAA
+ *   2  GGCCGGGCGCGGTGGCTCATGCCTGTAAT
+ *   TTTTTTTTTGGTGGCTCACGCCTGTAATCC  -> seq 1, orient 1, score 30, len 30, mism 0, run 30, q_start 0, s_start 18, n_seeds 2, seq2 0,
+ *                                      score2 21 (sequence 2 has one mismatch that leaves two runs of 9 and is never seeded)
+ *   GGTGGCTCACGC                    -> seq 0 by the index tie, s_start 10, score 12, n_seeds 2, seq2 1, score2 12
+ *   GGTGGCTCACG                     -> not found
+ *   A x 15 against the one sequence C + A x 20 + G -> score 15, s_start 1, n_seeds 12: six full diagonals and runs of 14, 13 and 12
+ *                                      at either end
+ * Cost: nothing is capped.  A k-mer that occurs R times in the panel costs R per query k-mer that equals it, so a poly-A panel makes
+ * a poly-A query expensive; a panel of consensus sequences with tails of 10 to 30 A is the intended use.
+ * Every output is a count or an argmax with a fixed tie rule: two runs, and any permutation of the probes, give the same bytes row for
+ * row.  The structs have no typedef. */
+struct bk_seq_hit { uint32_t found; int32_t seq; uint32_t orient, score, len, mism, run, q_start, s_start, n_seeds; int32_t seq2; uint32_t score2; };  /* 48 bytes */
+/* ctx: any live context that is not a shard (bk_shard_*); it gives the device, the stream, the buffers and bk_timing: scope
+ * `sequence_match` with `sequence_match_index` and `sequence_match_probes` inside it.  bk_timing_touched, with B = off[n_seqs],
+ * M = the k-mers of the panel (positions p whose `seed` bases hold no N and end inside p's sequence) and
+ * passes = (2 * seed + 7) / 8:
+ *   sequence_match_index   B + 36 * M * passes   the panel bytes; a radix pass reads a key for the histogram, reads and writes key and
+ *                                                value for the scatter and is credited 36 bytes an item as everywhere in the library
+ *   sequence_match_probes  n * (56 + max_len)    the probe row, the query and the result row
+ *   sequence_match         the sum of the two
+ * The panel reads of the extension are not modelled.  No stage needs to have run and nothing a later bk_fetch or stage returns
+ * changes.  panel, probes, query: host memory.  *out (n rows) is library-owned until the next call or bk_free(ctx).  BK_ERR_ARG
+ * (with the reason in bk_last_error) for shards, null ctx / panel / out, null probes or query with n > 0, max_len outside 1..256,
+ * seed outside 8..16, qlen > max_len, reversed > 1, a query byte outside ACGTN within qlen, a panel byte outside ACGTN, null off with
+ * n_seqs > 0, null bases with B > 0, and off that does not ascend from 0.  BK_ERR_LIMIT beyond 2^30 probes, 2^20 sequences or 2^28
+ * panel bases, looked at before any other entry of an array is read.  No errors: n == 0, n_seqs == 0 (off and bases may then be
+ * NULL), sequences shorter than seed, empty sequences. */
+int bk_sequence_match(bk_ctx *ctx, const bk_seq_panel *panel, const struct bk_seq_probe *probes, uint64_t n, const uint8_t *query, uint32_t max_len, uint32_t seed,
+                      const struct bk_seq_hit **out);
+
 /* ---- site complexity: what the reference looks like at one position ---------------------------------------------------------------
  * Aligners clip and split reads in microsatellites, low-complexity stretches and annotated repeats for reasons that have nothing to do
  * with a rearrangement.  bk_site_complexity describes the reference window around one position by itself: how much of it is
