@@ -112,6 +112,10 @@ assert CLIP_LOCUS.itemsize == 96
 CLIPLOCI_MAX_TOL = 100  # BK_CLIPLOCI_MAX_TOL
 CLIPLOCI_MAX_PAIR = 100000  # BK_CLIPLOCI_MAX_PAIR
 STRAND_NONE, STRAND_LEFT, STRAND_RIGHT = 0, 1, 2  # BK_STRAND_*
+BGZF_FORM_ROUNDS, BGZF_FORM_SHARED = 1, 2  # BK_BGZF_FORM_*: the form bits of bk_debug_bgzf_inflate_form
+# the words of bk_debug_bgzf_info, in its order
+BGZF_INFO = ("LIT_FAST", "DIST_FAST", "LANE_PART_BITS", "LANE_CHECK_BITS", "LANE_FULL_WALKS", "CHUNK_DW", "RES_WIN", "RESOLVE_THREADS", "BGZF_BATCH_BLOCKS",
+             "BGZF_TOKENS_PER_BLOCK", "BGZF_MAX_DEFLATE_BLOCKS")
 # the columns of a bk_txmodel, in the struct's order (ex_off has n_tx + 1 entries, ex_start / ex_end n_parts)
 TXMODEL_COLS = [("tid", np.int32), ("tx_start", np.uint32), ("tx_end", np.uint32), ("strand", np.uint8), ("ex_off", np.uint32), ("ex_start", np.uint32), ("ex_end", np.uint32)]
 # the columns of a bk_refseq table, in the struct's order (off has n_segs + 1 entries)

@@ -36,7 +36,7 @@ def build(verbose=False):
 EXPORTS = ["bk_init", "bk_prepare_process", "bk_free", "bk_last_error", "bk_set_stream", "bk_sync", "bk_get_stream", "bk_upload_records", "bk_records", "bk_exclude_regions", "bk_isize_stats",
            "bk_discordant_pairs", "bk_mask_and_cluster", "bk_split_evidence", "bk_cluster_summary",
            "bk_split_breakpoints", "bk_normal_support", "bk_ref_support", "bk_genotype_call", "bk_clip_support", "bk_clip_reads", "bk_base_depth", "bk_clip_rescue", "bk_junctions", "bk_junction_sides", "bk_vcf_breakend_alt", "bk_evidence", "bk_unique_support", "bk_clip_consensus", "bk_junction_fit", "bk_locus_similarity", "bk_sequence_match", "bk_site_complexity", "bk_window_coverage", "bk_window_context", "bk_call_windows", "bk_fusion_frame", "bk_link_calls", "bk_locus_partners", "bk_call_partner_sites", "bk_fragment_sizes", "bk_fragment_bounds", "bk_known_calls", "bk_split_junctions", "bk_split_junction_counts", "bk_debug_split_junctions", "bk_cigar_gaps", "bk_cigar_gap_counts", "bk_clip_loci", "bk_clip_locus_counts", "bk_run", "bk_fetch", "bk_timing", "bk_timing_enable", "bk_timing_touched", "bk_group_stats", "bk_qname_hash", "bk_qname_check",
-           "bk_bam_open", "bk_bam_header", "bk_bam_decode", "bk_bam_close", "bk_bam_extract", "bk_bam_names_free", "bk_bam_reads", "bk_reads_free", "bk_bam_decode_device", "bk_bam_decode_device_part", "bk_bam_decode_device_ctx", "bk_bam_dev_free", "bk_feed_release_caches", "bk_debug_bgzf_inflate", "bk_debug_std_sort", "bk_debug_scan", "bk_debug_radix_sort", "bk_debug_prims_info", "bk_sort_forms", "bk_debug_sort_info", "bk_debug_ahc", "bk_debug_points", "bk_debug_points_groups", "bk_debug_cluster_info", "bk_debug_stream_info", "bk_debug_stream_blocks", "bk_debug_cigar", "bk_debug_vote", "bk_debug_region", "bk_shard_begin", "bk_shard_get_stats", "bk_shard_set_stats",
+           "bk_bam_open", "bk_bam_header", "bk_bam_decode", "bk_bam_close", "bk_bam_extract", "bk_bam_names_free", "bk_bam_reads", "bk_reads_free", "bk_bam_decode_device", "bk_bam_decode_device_part", "bk_bam_decode_device_ctx", "bk_bam_dev_free", "bk_feed_release_caches", "bk_debug_bgzf_inflate", "bk_debug_bgzf_inflate_form", "bk_debug_bgzf_info", "bk_debug_std_sort", "bk_debug_scan", "bk_debug_radix_sort", "bk_debug_prims_info", "bk_sort_forms", "bk_debug_sort_info", "bk_debug_ahc", "bk_debug_points", "bk_debug_points_groups", "bk_debug_cluster_info", "bk_debug_stream_info", "bk_debug_stream_blocks", "bk_debug_cigar", "bk_debug_vote", "bk_debug_region", "bk_shard_begin", "bk_shard_get_stats", "bk_shard_set_stats",
            "bk_shard_sd_local", "bk_shard_sd_finish", "bk_shard_buffer", "bk_shard_set_buffer", "bk_shard_group_sizes",
            "bk_shard_own_groups", "bk_shard_route_candidates", "bk_shard_group_keys", "bk_shard_route_pairs", "bk_shard_group_pairs", "bk_shard_bp_cov", "bk_shard_bp_vote", "bk_shard_bp_vote_slice", "bk_shard_bp_set_voted", "bk_shard_bp_depth", "bk_shard_bp_finish"]
 
@@ -169,6 +169,8 @@ def lib():
         L.bk_bam_decode_device_ctx.argtypes = [C.c_char_p, C.c_int, C.c_int, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_int), C.POINTER(C.POINTER(C.c_char_p)),
                                                C.POINTER(C.POINTER(C.c_uint32)), C.c_char_p, C.c_size_t]
         L.bk_debug_bgzf_inflate.argtypes = [vp, C.c_uint64, vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_float), C.c_char_p, C.c_size_t]
+        L.bk_debug_bgzf_inflate_form.argtypes = [vp, C.c_uint64, vp, C.c_uint64, C.POINTER(C.c_uint64), C.c_int, C.c_uint64, C.c_char_p, C.c_size_t]
+        L.bk_debug_bgzf_info.argtypes = [u64p]
         _LIB = L
     return _LIB
 
@@ -235,6 +237,36 @@ def prims_info():
     if rc != 0:
         raise BreakIDError(rc, "bk_debug_prims_info")
     return dict(zip(("BLOCK", "SCAN_TILE", "SCAN_ONE_MAX", "RS_TILE"), (int(v) for v in out)))
+
+
+def bgzf_info():
+    """The constants of the built GPU inflate (bk_debug_bgzf_info; no GPU), named as in abi.BGZF_INFO."""
+    out = (C.c_uint64 * len(abi.BGZF_INFO))()
+    rc = lib().bk_debug_bgzf_info(out)
+    if rc != 0:
+        raise BreakIDError(rc, "bk_debug_bgzf_info")
+    return dict(zip(abi.BGZF_INFO, (int(v) for v in out)))
+
+
+def bgzf_inflate_form(data, form, out_align=256):
+    """A whole BGZF file image inflated on the GPU by the decoder and in the output layout named (bk_debug_bgzf_inflate_form; form:
+    a sum of abi.BGZF_FORM_ROUNDS and abi.BGZF_FORM_SHARED, out_align 256 or 1): (rc, the blocks' bytes back to back or None when
+    rc != 0, the error text).  No exception for a malformed stream: the return code is what the tests look at."""
+    src = np.frombuffer(bytes(data), np.uint8)
+    olen, err = C.c_uint64(), C.create_string_buffer(256)
+    total = 0
+    off = 0
+    while off + 18 <= len(src):  # the sum of the blocks' ISIZE fields sizes the buffer; the library validates the headers itself
+        bsize = int(src[off + 16]) | (int(src[off + 17]) << 8)
+        if off + bsize + 1 > len(src):
+            break
+        total += int.from_bytes(src[off + bsize - 3:off + bsize + 1].tobytes(), "little")
+        off += bsize + 1
+    out = np.zeros(total + 16, np.uint8)
+    rc = lib().bk_debug_bgzf_inflate_form(src.ctypes.data, len(src), out.ctypes.data, len(out), C.byref(olen), int(form), int(out_align), err, 256)
+    if rc != 0:
+        return rc, None, err.value.decode()
+    return 0, out[:olen.value].tobytes(), ""
 
 
 def cluster_info():

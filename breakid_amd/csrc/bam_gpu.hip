@@ -80,20 +80,25 @@ bool bgzf_scan_blocks(const uint8_t *file, uint64_t n, std::vector<BgzfBlock> &b
   return bgzf_scan_range(file, n, off, ~0ull, blocks, total, why);
 }
 
-// Test / measurement hook: inflates a whole BGZF file image on the GPU and hands the bytes back.
-extern "C" int bk_debug_bgzf_inflate(const void *file, uint64_t n, void *out, uint64_t out_cap, uint64_t *out_len, float *kernel_ms, char *err, size_t errlen)
+// Test / measurement hooks: inflate a whole BGZF file image on the GPU and hand the bytes back.
+namespace
+{
+int debug_inflate(const char *who, const void *file, uint64_t n, void *out, uint64_t out_cap, uint64_t *out_len, float *kernel_ms, int form, uint64_t out_align, char *err, size_t errlen)
 {
   try
   {
     std::vector<BgzfBlock> blocks;
-    uint64_t total = 0;
+    uint64_t total = 0, off = 0;
     std::string why;
-    if (!file || !out_len) throw bk_error(BK_ERR_ARG, "bk_debug_bgzf_inflate: null argument");
-    if (!bgzf_scan_blocks((const uint8_t *) file, n, blocks, total, why)) throw bk_error(BK_ERR_IO, why);
+    if (!file || !out_len) throw bk_error(BK_ERR_ARG, std::string(who) + ": null argument");
+    if (form != BGZF_FORM_DEFAULT && (form < 0 || form > (BGZF_FORM_ROUNDS | BGZF_FORM_SHARED))) throw bk_error(BK_ERR_ARG, std::string(who) + ": form must be 0 .. 3");
+    if (out_align != BGZF_OUT_ALIGN && out_align != 1) throw bk_error(BK_ERR_ARG, std::string(who) + ": out_align must be 256 or 1");
+    if (!bgzf_scan_range((const uint8_t *) file, n, off, ~0ull, blocks, total, why, out_align)) throw bk_error(BK_ERR_IO, why);
+    if (blocks.size() > 0xFFFFFFFFull) throw bk_error(BK_ERR_LIMIT, std::string(who) + ": too many blocks");
     uint64_t packed = 0;
     for (auto &bb : blocks) packed += bb.isize;
     *out_len = packed;
-    if (packed > out_cap) throw bk_error(BK_ERR_ARG, "bk_debug_bgzf_inflate: output buffer too small");
+    if (packed > out_cap) throw bk_error(BK_ERR_ARG, std::string(who) + ": output buffer too small");
     DevBuf dfile, dblk, dout, derr, dslab;
     uint8_t *f = dfile.as<uint8_t>(n + 8);
     BgzfBlock *b = dblk.as<BgzfBlock>(blocks.size() + 1);
@@ -107,7 +112,7 @@ extern "C" int bk_debug_bgzf_inflate(const void *file, uint64_t n, void *out, ui
     HIP_CHECK(hipEventCreate(&e0));
     HIP_CHECK(hipEventCreate(&e1));
     HIP_CHECK(hipEventRecord(e0, nullptr));
-    launch_bgzf_inflate(f, b, (uint32_t) blocks.size(), o, slab, e, nullptr);
+    launch_bgzf_inflate(f, b, (uint32_t) blocks.size(), o, slab, e, nullptr, false, form);
     HIP_CHECK(hipEventRecord(e1, nullptr));
     HIP_CHECK(hipEventSynchronize(e1));
     float ms = 0;
@@ -136,6 +141,30 @@ extern "C" int bk_debug_bgzf_inflate(const void *file, uint64_t n, void *out, ui
     if (err && errlen) snprintf(err, errlen, "%s", ex.what());
     return ex.code;
   }
+}
+}  // namespace
+
+extern "C" int bk_debug_bgzf_inflate(const void *file, uint64_t n, void *out, uint64_t out_cap, uint64_t *out_len, float *kernel_ms, char *err, size_t errlen)
+{
+  return debug_inflate("bk_debug_bgzf_inflate", file, n, out, out_cap, out_len, kernel_ms, BGZF_FORM_DEFAULT, BGZF_OUT_ALIGN, err, errlen);
+}
+
+extern "C" int bk_debug_bgzf_inflate_form(const void *file, uint64_t n, void *out, uint64_t out_cap, uint64_t *out_len, int form, uint64_t out_align, char *err, size_t errlen)
+{
+  if (form < 0)
+  {
+    if (err && errlen) snprintf(err, errlen, "bk_debug_bgzf_inflate_form: form must be 0 .. 3");
+    return BK_ERR_ARG;
+  }
+  return debug_inflate("bk_debug_bgzf_inflate_form", file, n, out, out_cap, out_len, nullptr, form, out_align, err, errlen);
+}
+
+extern "C" int bk_debug_bgzf_info(uint64_t out[11])
+{
+  static_assert(BGZF_INFO_WORDS == 11, "include/breakid_hip.h, capi.bgzf_info");
+  if (!out) return BK_ERR_ARG;
+  bgzf_info(out);
+  return BK_OK;
 }
 
 // ---------------------------------------------------------------------------------------------------------------

@@ -125,7 +125,8 @@ __device__ __forceinline__ uint32_t make_entry(uint32_t s, uint32_t len)
 // Canonical Huffman tables from n code lengths, built by the wave: counts per length (LDS atomics), first code and
 // first slot of every length (15 serial steps), then 64 symbols at a time: a symbol's rank among the symbols of its
 // length is the number of such symbols in earlier chunks plus the lanes below it in a ballot.  Symbols whose code fits
-// the direct table fill their 2^(fast_bits - len) slots.  Returns false for an over-subscribed set of lengths.
+// the direct table fill their 2^(fast_bits - len) slots.  Returns false for an over-subscribed set of lengths and for an
+// incomplete one (what zlib rejects: "invalid literal/lengths set", "invalid distances set").
 template <int T>
 __device__ __noinline__ bool build_tables(HuffLds &h, const uint8_t *lens, uint32_t n, uint16_t *fast, uint32_t fast_bits, uint16_t *sym, uint32_t *count)
 {
@@ -161,6 +162,8 @@ __device__ __noinline__ bool build_tables(HuffLds &h, const uint8_t *lens, uint3
     off += c;
     code = (code + c) << 1;
   }
+  // an incomplete set: malformed, as for zlib (inftrees.c), whose one exception is a lone 1-bit literal/length or distance code
+  if (left > 0 && (T == T_CLEN || uni(count[1]) != 1u || uni(count[0]) != n - 1u)) return false;
   __builtin_amdgcn_wave_barrier();
   uint32_t seen[16];  // symbols of each length in earlier chunks (uniform; the loops below are fully unrolled)
 #pragma unroll
@@ -520,7 +523,7 @@ __device__ __forceinline__ uint32_t decode_wave(const uint8_t *file, uint64_t in
   uint32_t o = 0;
   ntok = 0;
   ST(uint32_t st_fix = 0; uint32_t st_ll = 0; uint32_t st_dlong = 0; uint32_t st_rounds = 0; uint32_t st_slow = 0; uint32_t st_dyn = 0; uint64_t st_tb = 0; const uint64_t st_t0 = wall_clock64();)
-  for (int guard = 0; guard < 4096; ++guard)
+  for (int guard = 0; guard < BGZF_MAX_DEFLATE_BLOCKS; ++guard)
   {
     const uint32_t hdr = dc.bits(3), last = hdr & 1u, type = hdr >> 1;
     if (type == 0)
@@ -540,9 +543,9 @@ __device__ __forceinline__ uint32_t decode_wave(const uint8_t *file, uint64_t in
       if (type == 1)
       {
         for (uint32_t i = lane; i < 288; i += 64) h.lens[i] = i < 144 ? 8 : i < 256 ? 9 : i < 280 ? 7 : 8;
-        if (lane < 32) h.lens[288 + lane] = lane < 30 ? 5 : 0;
+        if (lane < 32) h.lens[288 + lane] = 5;  // 30 and 31 never occur but take part in the code construction (RFC 1951 3.2.6): a complete set
         nlen = 288;
-        ndist = 30;
+        ndist = 32;
       }
       else
       {
@@ -939,9 +942,16 @@ __global__ __launch_bounds__(RESOLVE_THREADS) void k_bgzf_resolve(const BgzfBloc
 }
 }  // namespace
 
+void bgzf_info(uint64_t out[BGZF_INFO_WORDS])
+{
+  const uint64_t v[BGZF_INFO_WORDS] = {(uint64_t) LIT_FAST, (uint64_t) DIST_FAST, LANE_PART, LANE_CHECK, (uint64_t) LANE_FULL_WALKS, CHUNK_DW, RES_WIN, RESOLVE_THREADS, BGZF_BATCH_BLOCKS,
+                                       BGZF_TOKENS_PER_BLOCK, (uint64_t) BGZF_MAX_DEFLATE_BLOCKS};
+  for (int i = 0; i < BGZF_INFO_WORDS; ++i) out[i] = v[i];
+}
+
 uint32_t bgzf_scratch_blocks(uint32_t nblk) { return nblk < BGZF_BATCH_BLOCKS ? nblk : BGZF_BATCH_BLOCKS; }
 
-void launch_bgzf_inflate(const uint8_t *file_dev, const BgzfBlock *blk_dev, uint32_t nblk, uint8_t *out_dev, void *scratch_dev, uint32_t *err_dev, hipStream_t st, bool shared_gpu)
+void launch_bgzf_inflate(const uint8_t *file_dev, const BgzfBlock *blk_dev, uint32_t nblk, uint8_t *out_dev, void *scratch_dev, uint32_t *err_dev, hipStream_t st, bool shared_gpu, int form)
 {
   if (nblk == 0) return;
   static bool attr_set = false;
@@ -950,7 +960,9 @@ void launch_bgzf_inflate(const uint8_t *file_dev, const BgzfBlock *blk_dev, uint
     HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_bgzf_resolve), hipFuncAttributeMaxDynamicSharedMemorySize, RES_WIN * 2));
     attr_set = true;
   }
-  static const bool rounds = getenv("BK_BGZF_ROUNDS") != nullptr;  // the decoder that walks 64 bit positions per round (comparison)
+  static const bool env_rounds = getenv("BK_BGZF_ROUNDS") != nullptr;  // the decoder that walks 64 bit positions per round (comparison)
+  const bool rounds = form == BGZF_FORM_DEFAULT ? env_rounds : (form & BGZF_FORM_ROUNDS) != 0;
+  if (form != BGZF_FORM_DEFAULT) shared_gpu = (form & BGZF_FORM_SHARED) != 0;
   const uint32_t cap = bgzf_scratch_blocks(nblk);
   unsigned long long *slab = static_cast<unsigned long long *>(scratch_dev);
   uint32_t *ntok = reinterpret_cast<uint32_t *>(slab + (size_t) cap * BGZF_TOKENS_PER_BLOCK);

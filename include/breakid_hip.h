@@ -1574,6 +1574,26 @@ int bk_bam_decode_device_ctx(const char *path, int device, int mapq_min, bk_bam_
 int bk_records(bk_ctx *ctx, bk_soa *cols);
 /* test / measurement hook: inflates a whole BGZF file image on the GPU, bytes back to the host */
 int bk_debug_bgzf_inflate(const void *file, uint64_t n, void *out, uint64_t out_cap, uint64_t *out_len, float *kernel_ms, char *err, size_t errlen);
+/* Test hooks of the GPU inflate alone (csrc/bgzf_gpu.hip; tests/inflatecases.py, tests/test_gpu_inflate.py):
+ *   bk_debug_bgzf_inflate_form  bk_debug_bgzf_inflate with the decoder and the output layout named outright.  form: a sum of
+ *                        BK_BGZF_FORM_ROUNDS (the decoder that takes 64 bit positions per round; without it the lanes decoder,
+ *                        which leaves windows that do not synchronise to the rounds) and BK_BGZF_FORM_SHARED (the kernels the
+ *                        streaming feed launches: another register allocation).  out_align: 256 (every block's output starts at a
+ *                        multiple of 256, as the feed of block-aligned files lays it out) or 1 (the blocks abut, as the feed of
+ *                        files whose records cross blocks lays them out: a block whose offset is no multiple of 4 takes the byte
+ *                        stores of the resolve kernel).  out receives the blocks' bytes back to back either way.  BK_ERR_ARG for
+ *                        another form or alignment; BK_ERR_IO "inflate failed" when any block is malformed or does not give isize
+ *                        bytes (one flag per call: out is then not written).  A block's CRC32 is not looked at.
+ *   bk_debug_bgzf_info   the constants of this build, no GPU needed: out[0..10] = LIT_FAST, DIST_FAST (bits of the direct tables),
+ *                        LANE_PART_BITS, LANE_CHECK_BITS, LANE_FULL_WALKS (a lane's part of a window, its checkpoint, the long
+ *                        passes after which a window goes to the rounds), CHUNK_DW (dwords the input window slides by), RES_WIN,
+ *                        RESOLVE_THREADS (output positions per resolve window, threads of a resolve block), BGZF_BATCH_BLOCKS
+ *                        (blocks per launch pair), BGZF_TOKENS_PER_BLOCK, BGZF_MAX_DEFLATE_BLOCKS (deflate blocks one BGZF block
+ *                        may hold: one more is reported as malformed) */
+#define BK_BGZF_FORM_ROUNDS 1
+#define BK_BGZF_FORM_SHARED 2
+int bk_debug_bgzf_inflate_form(const void *file, uint64_t n, void *out, uint64_t out_cap, uint64_t *out_len, int form, uint64_t out_align, char *err, size_t errlen);
+int bk_debug_bgzf_info(uint64_t out[11]);
 
 #ifdef __cplusplus
 }

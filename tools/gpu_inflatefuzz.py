@@ -1,6 +1,8 @@
 """GPU inflate against zlib on random deflate streams (GPU box): data shapes (uniform bytes, skewed alphabets, few letters, text,
 runs, repeats at random distances, mixtures), zlib levels / strategies / window sizes / flush patterns, block sizes from 0 to
-0xFF00.  Usage: python tools/gpu_inflatefuzz.py [cases] [seed]"""
+0xFF00.  Usage: python tools/gpu_inflatefuzz.py [cases] [seed] [form] [out_align]
+form: 0 lanes, 1 rounds, 2 lanes with the _shared kernels, 3 rounds with them; out_align: 256 or 1 (abutting blocks).  With either
+the case goes through bk_debug_bgzf_inflate_form (capi.bgzf_inflate_form), else through bk_debug_bgzf_inflate as before."""
 import ctypes as C, os, struct, sys, zlib
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -10,6 +12,8 @@ L = capi.lib()
 L.bk_debug_bgzf_inflate.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_float), C.c_char_p, C.c_size_t]
 cases = int(sys.argv[1]) if len(sys.argv) > 1 else 200
 rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 1)
+form = int(sys.argv[3]) if len(sys.argv) > 3 else None
+out_align = int(sys.argv[4]) if len(sys.argv) > 4 else 256
 import torch  # noqa: F401
 
 
@@ -70,13 +74,18 @@ for it in range(cases):
     raw = b"".join(b for b, _ in comp)
     data = b"".join(b"\x1f\x8b\x08\x04\0\0\0\0\0\xff\x06\0BC\x02\0" + struct.pack("<H", len(d) + 25) + d + struct.pack("<II", zlib.crc32(b), len(b)) for b, d in comp)
     data += bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000")
-    src = np.frombuffer(data, np.uint8)
-    out = np.zeros(len(raw) + 16, np.uint8)
-    olen, ms, err = C.c_uint64(), C.c_float(), C.create_string_buffer(256)
-    rc = L.bk_debug_bgzf_inflate(src.ctypes.data, len(data), out.ctypes.data, len(out), C.byref(olen), C.byref(ms), err, 256)
-    if rc != 0 or olen.value != len(raw) or out[:len(raw)].tobytes() != raw:
+    if form is not None:
+        rc, got, why = capi.bgzf_inflate_form(data, form, out_align)
+        ok = rc == 0 and got == raw
+    else:
+        src = np.frombuffer(data, np.uint8)
+        out = np.zeros(len(raw) + 16, np.uint8)
+        olen, ms, err = C.c_uint64(), C.c_float(), C.create_string_buffer(256)
+        rc = L.bk_debug_bgzf_inflate(src.ctypes.data, len(data), out.ctypes.data, len(out), C.byref(olen), C.byref(ms), err, 256)
+        ok, why = rc == 0 and olen.value == len(raw) and out[:len(raw)].tobytes() == raw, err.value
+    if not ok:
         bad += 1
-        print("case %d: rc=%d %s, %d blocks, %d bytes" % (it, rc, err.value, len(blks), len(raw)), flush=True)
+        print("case %d: rc=%d %s, %d blocks, %d bytes" % (it, rc, why, len(blks), len(raw)), flush=True)
     if it % 50 == 49:
         print("inflate fuzz: %d cases, %d bad" % (it + 1, bad), flush=True)
 print("INFLATEFUZZ %d cases, %d bad" % (cases, bad))
